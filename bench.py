@@ -16,11 +16,24 @@ scaling over batched M: every rank runs the BASELINE configs[1] problem, M=N=K=4
 with the replicated W); no data-path collective.  Timed region: barrier + synchronize, K steps,
 synchronize + barrier, max over ranks.  Rank 0 prints ONE JSON line.
 
-Extra objects on that line:
+A plain run does what the headline needs and no more: set up, warm up, time the K steps, write the outputs
+if ``--dump-outputs DIR`` asks for them, print the line.  ``--full`` adds the measurements that take runs
+of their own after the timed region (c4_node, cold_cache, quant_error, cpu_baseline below); their own
+options (--node-reps, --cold-steps, --no-error-stats, --no-cpu-baseline, --cpu-seconds) select among them
+under ``--full`` and do nothing without it.
+
+``--dump-outputs DIR`` writes what the last timed step computed, as the caller of the drop-in call receives
+it, to DIR/<name>.npy in float32 (rank 0's arrays: O for the GEMM configs, Y for c5_encoder).  An output
+above DUMP_LIMIT_BYTES is written as a fixed, seeded sample of whole rows (dump_rows); the inputs are seeded,
+so two builds run with the same arguments write comparable files.
+
+Objects on that line beside the contract's fields:
   roofline     -- the dominant kernel (the int8 GEMM): algorithmic 2*M*N*K int8 ops per launch over
                   its average launch time, measured with HIP events around each GEMM launch inside
                   the timed region, against the gfx950 dense int8 MFMA peak.
-  cpu_baseline -- the CPU oracle (a C restatement of the reference chain, oracle/) timed on the host cores
+  c4_node, cold_cache, quant_error (--full) -- the whole-node C4 step, the drop-in call with its inputs
+                  evicted from the Infinity Cache, the quantization error against the unquantized fp32 GEMM.
+  cpu_baseline (--full) -- the CPU oracle (a C restatement of the reference chain, oracle/) timed on the host cores
                   (rank 0, N=1 only): the FULL M=N=K=4096 problem repeated for ~--cpu-seconds (the oracle
                   runs one whole chain in well under a second on 16 threads), plus the unquantized fp32
                   op_mm restatement once on the full problem.
@@ -78,6 +91,13 @@ def parse(argv=None):
     p.add_argument("--steps", type=int, default=200)
     p.add_argument("--warmup", type=int, default=50)
     p.add_argument("--config", default="c2", choices=sorted(CONFIGS))
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run the measurements that take runs of their own: the whole-node "
+                        "C4 step, cold-cache calls, the quantization-error check and the CPU baseline (each with its "
+                        "own option below); a plain run skips them all")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last step computed to DIR/<name>.npy (float32; at most "
+                        "DUMP_LIMIT_BYTES in all, larger outputs as a fixed seeded sample of rows)")
     p.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU-baseline sample time")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-error-stats", action="store_true", help="skip the post-run quantization-error check")
@@ -202,6 +222,41 @@ def cpu_model():
 def outlier_columns(K):
     """The c2_outlier workload's outlier feature columns (spread over K) and their rows (every 50th)."""
     return [(K // OUTLIER_COLS) * c + 7 * c + 3 for c in range(OUTLIER_COLS)], 50
+
+
+DUMP_LIMIT_BYTES = 60_000_000  # every file of one --dump-outputs run together, .npy headers aside
+DUMP_SEED = 4096
+
+
+def dump_rows(rows, row_bytes, limit=DUMP_LIMIT_BYTES):
+    """The rows of an output that --dump-outputs writes: None (all of them) when they fit in `limit` bytes, else
+    a sorted sample without repeats drawn from numpy's default_rng(DUMP_SEED) -- a function of the shape alone,
+    so every run and every build of the same arguments writes the same rows."""
+    import numpy as np
+    keep = max(1, limit // row_bytes)
+    if keep >= rows:
+        return None
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(rows, size=keep, replace=False))
+
+
+def dump_outputs(out_dir, arrays):
+    """Write each 2-D float32 tensor of `arrays` ({name: tensor}, the timed path's outputs after its last step) to
+    out_dir/<name>.npy, DUMP_LIMIT_BYTES shared evenly among them; returns the line's `dumped` object."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    report = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        assert a.dtype == np.float32 and a.ndim == 2, (name, a.dtype, a.shape)
+        idx = dump_rows(a.shape[0], a.shape[1] * 4, DUMP_LIMIT_BYTES // len(arrays))
+        if idx is not None:
+            a = a[idx]
+        path = os.path.join(out_dir, f"{name}.npy")
+        np.save(path, np.ascontiguousarray(a))
+        report[name] = {"file": path, "dtype": "float32", "shape": list(a.shape),
+                        "rows": "all" if idx is None else f"{len(idx)} of {t.shape[0]} rows, dump_rows sample "
+                                                           f"(seed {DUMP_SEED})"}
+    return report
 
 
 def host_cpu_share():
@@ -664,6 +719,8 @@ def bench_gemm(args, qg, L, dev, world, rank, distributed, comm, rccl_world):
     else:
         gemm_ms = float("nan")
     hip.destroy()
+    # O as the last timed step left it (the timed region ended on a synchronize), before anything calls step() again
+    dumped = dump_outputs(args.dump_outputs, {"O": O}) if args.dump_outputs and rank == 0 else None
     elapsed, gemm_ms = max_over_ranks([elapsed, gemm_ms], distributed, dev)
 
     ops = 2.0 * M * N * K
@@ -709,7 +766,9 @@ def bench_gemm(args, qg, L, dev, world, rank, distributed, comm, rccl_world):
         "library": qg.version(),
         "prewarm": prewarm,
     })
-    if args.config == "c2" and args.node_reps > 0:
+    if dumped is not None:
+        result["dumped"] = dumped
+    if args.full and args.config == "c2" and args.node_reps > 0:
         def node_timed_out():
             if rank == 0:
                 result["c4_node"] = {"error": f"did not finish within {args.node_timeout:g} s (an RCCL collective "
@@ -721,7 +780,7 @@ def bench_gemm(args, qg, L, dev, world, rank, distributed, comm, rccl_world):
                                  node_timed_out)
         result["c4_node"] = node
         result["allgather_ms_median"] = node["allgather_ms_median"]
-    if rank == 0 and args.cold_steps > 0:
+    if args.full and rank == 0 and args.cold_steps > 0:
         # Steady-state steps re-read the same X and W, which (with O) fit in the 256-MB Infinity Cache;
         # this is the same call with them evicted first (a 1-GiB read sweep between calls), each call timed
         # alone by events on its stream (includes the launch of its first kernel)
@@ -743,7 +802,7 @@ def bench_gemm(args, qg, L, dev, world, rank, distributed, comm, rccl_world):
             "calls": len(cold),
             "note": "each call after a 1-GiB read sweep evicted X, W and O from the Infinity Cache; value above is the "
                     "warm steady state (same inputs every step, as GEMM benchmarks run)"}
-    if rank == 0 and not args.no_error_stats:
+    if args.full and rank == 0 and not args.no_error_stats:
         # after the timed region: the quantization error of this run's output against the reference's
         # unquantized op_mm (qgemm_mm_fp32, bit-exact sequential-k fmaf), computed on the device
         C = qg.mm_fp32(X, W)
@@ -752,7 +811,7 @@ def bench_gemm(args, qg, L, dev, world, rank, distributed, comm, rccl_world):
         result["quant_error"]["note"] = ("signed_mean_ref = the reference's printed metric (sequential fp32, "
                                          "timing_quantize.cu:67-70); the others fp64 on the device")
         del C
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(M, N, K, args.cpu_seconds, outlier=outlier)
         if prepacked:
             result["cpu_baseline"]["note"] = "the reference chain re-quantizes W every call (it has no weight cache)"
@@ -788,6 +847,7 @@ def bench_encoder(args, qg, L, dev, world, rank, distributed, rccl_world):
     elapsed = timed_region(step, args.steps, distributed, lambda: torch.cuda.synchronize(dev))
     gemm_ms = sum(hip.elapsed_ms(hip.ev[2 * i], hip.ev[2 * i + 1]) for i in timed) / len(timed)
     hip.destroy()
+    dumped = dump_outputs(args.dump_outputs, {"Y": Y}) if args.dump_outputs and rank == 0 else None
     elapsed, gemm_ms = max_over_ranks([elapsed, gemm_ms], distributed, dev)
     qkv_ops = 2.0 * seq * 3 * d * d
     lin_ops = blocks * 2.0 * seq * (3 * d * d + d * d + 2 * d * dff)
@@ -815,7 +875,9 @@ def bench_encoder(args, qg, L, dev, world, rank, distributed, rccl_world):
         "library": qg.version(),
         "prewarm": prewarm,
     })
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if dumped is not None:
+        result["dumped"] = dumped
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import oracle as O
         O.build()
         cpu = host_cpu_share()

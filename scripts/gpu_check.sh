@@ -20,9 +20,9 @@ for s in $STEPS; do
   case $s in
     pytest) run pytest_gpu 1200 python -u -m pytest tests -m gpu -x -q -p no:cacheprovider --timeout 300 --timeout-method thread ;;
     smoke)  run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench)  run bench 600 python bench.py ;;
-    benchq) run benchq 300 python bench.py --steps 50 --warmup 10 --no-cpu-baseline ;;
-    prof)   run prof 600 rocprofv3 --kernel-trace --stats -d $OUT/prof -o run --output-format csv -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-error-stats ;;
+    bench)  run bench 600 python bench.py --full ;;
+    benchq) run benchq 300 python bench.py --full --steps 50 --warmup 10 --no-cpu-baseline ;;
+    prof)   run prof 600 rocprofv3 --kernel-trace --stats -d $OUT/prof -o run --output-format csv -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-error-stats ;;
     timing) run timing 600 quantized-gemm-for-transformer-inference_amd/build/timing_quantize -m 4096 -n 4096 -k 4096 -r 3 ;;
     lab)    run lab 300 lab/build/gemm_lab 4096 4096 4096 5 ;;
     *) echo "unknown step $s";;

@@ -144,7 +144,7 @@ def test_bench_line_names_its_world_and_binary(qg):
     import sys
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-                        "--no-cpu-baseline", "--no-error-stats", "--cold-steps", "0", "--node-reps", "1",
+                        "--full", "--no-cpu-baseline", "--no-error-stats", "--cold-steps", "0", "--node-reps", "1",
                         "--prewarm-ms", "0"], capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     js = json.loads(r.stdout.strip().splitlines()[-1])
@@ -152,3 +152,36 @@ def test_bench_line_names_its_world_and_binary(qg):
     assert f"src={qg.source_hash()}" in js["library"]
     node = js["c4_node"]
     assert node["gathered_rows_match_one_gpu"] is True and node["pipelined"]["gathered_rows_match_one_gpu"] is True
+
+
+def test_plain_bench_run_is_lean_and_dumps_its_last_output(qg, device, tmp_path):
+    """A plain bench.py run (no --full) times its steps and nothing else: the line carries the contract's fields and
+    none of the objects that take runs of their own.  --dump-outputs writes the last step's O as float32 within the
+    size limit, and the file holds, bit for bit, the rows (bench.dump_rows) of the drop-in call on the same seeded
+    inputs made here."""
+    import sys
+    import bench
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=300, env=env)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]  # RCCL may print its version banner before
+    assert len(lines) == 1 and lines[0] == r.stdout.strip().splitlines()[-1]
+    js = json.loads(lines[0])
+    assert js["steps"] == 3 and js["warmup"] == 1 and js["ms_per_step"] > 0
+    assert js["unit"] == "GEMMs/s" and js["higher_is_better"] is True and js["dtype"] == "int8"
+    assert abs(js["value"] - 1e3 / js["ms_per_step"]) / js["value"] < 1e-3
+    assert js["metric"].startswith("int8 GEMMs/sec")
+    for extra in ("c4_node", "cold_cache", "quant_error", "cpu_baseline"):
+        assert extra not in js, extra
+    assert sorted(os.listdir(tmp_path)) == ["O.npy"]
+    got = np.load(tmp_path / "O.npy")
+    M, N, K, _ = bench.CONFIGS["c2"]
+    rows = bench.dump_rows(M, N * 4)
+    assert got.dtype == np.float32 and got.shape == (len(rows), N)
+    assert os.path.getsize(tmp_path / "O.npy") <= 64_000_000
+    X = qg.fill_uniform(torch.empty((M, K), device=device), seed=2 * 1000)
+    W = qg.fill_uniform(torch.empty((K, N), device=device), seed=2 * 1000 + 1)
+    want = qg.op_mm_quantize(X, W)
+    torch.cuda.synchronize()
+    assert_bits_equal(got, want.cpu().numpy()[rows], "dumped O")
