@@ -120,6 +120,26 @@ QGEMM_API size_t qgemm_linear_workspace_size(int m, int n, int k);
 QGEMM_API int qgemm_linear(const float *X, int64_t x_stride_h, int m, int k, const void *packed_w, int n,
                  const float *bias, int relu, float *Y, int64_t y_stride_h, void *workspace, size_t ws_bytes,
                  void *stream);
+/* ---- bf16 activations and outputs on the prepacked path -------------------------------------------
+ * Element-type tags of the _dt entry points; strides are in elements of the tagged type.  The arithmetic
+ * is the fp32 chain's, only its two ends change:
+ *   bf16 input : every element is widened exactly (its bits shifted left by 16; subnormals stay subnormal),
+ *                so Cx, Xq and the accumulators are bit-identical to the fp32 entry point on the widened matrix.
+ *   bf16 output: the fp32 value the fp32 entry point would store (after dequantize, + bias, relu) is rounded
+ *                once, to nearest even: past the bf16 maximum it becomes +-inf, subnormals stay subnormal, -0
+ *                stays -0, NaN stays NaN.
+ * bias stays fp32, and weights are packed from fp32 with qgemm_pack_b (a bf16 checkpoint is widened once by
+ * the caller, which is exact).  With every tag QGEMM_F32 a _dt entry point IS its fp32 counterpart (same
+ * launches, bit-identical results); an unknown tag returns hipErrorInvalidValue before any launch.
+ * qgemm_linear_dt takes the workspace of qgemm_linear_workspace_size (it does not depend on the types). */
+enum { QGEMM_F32 = 0, QGEMM_BF16 = 1 };
+QGEMM_API int qgemm_pack_a_dt(const void *A, int a_dtype, int64_t a_stride_h, int64_t a_stride_w, int m, int k,
+                    float range, void *packed_a, void *stream);
+QGEMM_API int qgemm_mm_packed_dt(const void *packed_a, const void *packed_b, void *C, int c_dtype, int64_t c_stride_h,
+                       int64_t c_stride_w, int m, int n, int k, float range, void *stream);
+QGEMM_API int qgemm_linear_dt(const void *X, int x_dtype, int64_t x_stride_h, int m, int k, const void *packed_w, int n,
+                    const float *bias, int relu, void *Y, int y_dtype, int64_t y_stride_h,
+                    void *workspace, size_t ws_bytes, void *stream);
 /* op_multiply(S, scale) then op_softmax (attention.cuh:65-68, op_softmax.cuh:6-29), per row of w
  * contiguous floats (w <= 4096); P may equal S.  exp is the correctly rounded fp32 exp. */
 QGEMM_API int qgemm_softmax_rows(const float *S, float *P, int64_t rows, int w, float scale, void *stream);

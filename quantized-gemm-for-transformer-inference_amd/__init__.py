@@ -51,6 +51,9 @@ EXPORTED_SYMBOLS = (
     "qgemm_error_stats",
     "qgemm_linear_workspace_size",
     "qgemm_linear",
+    "qgemm_pack_a_dt",
+    "qgemm_mm_packed_dt",
+    "qgemm_linear_dt",
     "op_mm_quantize_prepacked",
     "op_mm_quantize_prepacked_workspace_size",
     "op_mm_quantize_prepacked_ws",
@@ -90,6 +93,7 @@ DIST_EXPORTED_SYMBOLS = (
 COMM_ID_BYTES = 128
 
 HIP_ERROR_INVALID_VALUE = 1
+QGEMM_F32, QGEMM_BF16 = 0, 1  # element-type tags of the _dt entry points (include/qgemm.h)
 
 _lock = threading.Lock()
 _lib = None
@@ -148,6 +152,12 @@ def load() -> ctypes.CDLL:
         L.qgemm_linear_workspace_size.restype = sz
         L.qgemm_linear.argtypes = [vp, i64, i32, i32, vp, i32, vp, i32, vp, i64, vp, sz, vp]
         L.qgemm_linear.restype = i32
+        L.qgemm_pack_a_dt.argtypes = [vp, i32, i64, i64, i32, i32, f32, vp, vp]
+        L.qgemm_pack_a_dt.restype = i32
+        L.qgemm_mm_packed_dt.argtypes = [vp, vp, vp, i32, i64, i64, i32, i32, i32, f32, vp]
+        L.qgemm_mm_packed_dt.restype = i32
+        L.qgemm_linear_dt.argtypes = [vp, i32, i64, i32, i32, vp, i32, vp, i32, vp, i32, i64, vp, sz, vp]
+        L.qgemm_linear_dt.restype = i32
         L.op_mm_quantize_prepacked.argtypes = [vp, vp, vp, i32, i32, i32]
         L.op_mm_quantize_prepacked.restype = i32
         L.op_mm_quantize_prepacked_workspace_size.argtypes = [i32, i32, i32]
@@ -430,6 +440,28 @@ def _require_device_f32(t, name):
     assert t.dtype == torch.float32, f"{name} must be float32 (op_quantized_mm is instantiated at T=float)"
 
 
+def _require_device_act(t, name) -> int:
+    """An activation / output of the prepacked path: fp32 or bf16.  Returns its element-type tag."""
+    import torch
+    if isinstance(t, torch.Tensor) and t.dtype == torch.bfloat16:
+        assert t.dim() == 2, f"{name} must be a 2-D tensor"
+        assert t.is_cuda, f"{name}.on_device (op_mm.cuh:72)"
+        return QGEMM_BF16
+    _require_device_f32(t, name)
+    return QGEMM_F32
+
+
+def _out_dtype(out, out_dtype, default):
+    """The output type of mm_packed / linear: a given output tensor decides, then out_dtype, then `default`."""
+    import torch
+    if out is not None:
+        assert out_dtype is None or out_dtype == out.dtype, "out_dtype disagrees with the output tensor given"
+        return out.dtype
+    dt = default if out_dtype is None else out_dtype
+    assert dt in (torch.float32, torch.bfloat16), "out_dtype must be torch.float32 or torch.bfloat16"
+    return dt
+
+
 # ------------------------------------------------------------------------------- the operator
 def op_quantized_mm(X, W, O, range: float = DEFAULT_RANGE) -> None:  # noqa: A002 - reference name
     """O = quantized X @ W, in place -- the reference's ``op_quantized_mm<float>`` (op_mm.cuh:67-101).
@@ -507,12 +539,17 @@ def _alloc_packed(rows, k, device):
 
 
 def pack_a(A, range: float = DEFAULT_RANGE) -> Packed:  # noqa: A002
-    """Cx = absmax rows (op_mm.cuh:76-77) and X_int8 (op_mm.cuh:82-87), fused."""
-    _require_device_f32(A, "A")
+    """Cx = absmax rows (op_mm.cuh:76-77) and X_int8 (op_mm.cuh:82-87), fused.  A bf16 A is widened exactly
+    on the way in (qgemm_pack_a_dt): the packed operand is that of A.float()."""
+    tag = _require_device_act(A, "A")
     M, K = A.shape
     p = Packed(_alloc_packed(M, K, A.device), M, K, range)
-    _check("qgemm_pack_a", load().qgemm_pack_a(A.data_ptr(), A.stride(0), A.stride(1), M, K, float(range),
-                                              p.buf.data_ptr(), _stream(A.device)))
+    if tag == QGEMM_F32:
+        _check("qgemm_pack_a", load().qgemm_pack_a(A.data_ptr(), A.stride(0), A.stride(1), M, K, float(range),
+                                                  p.buf.data_ptr(), _stream(A.device)))
+    else:
+        _check("qgemm_pack_a_dt", load().qgemm_pack_a_dt(A.data_ptr(), tag, A.stride(0), A.stride(1), M, K,
+                                                        float(range), p.buf.data_ptr(), _stream(A.device)))
     return p
 
 
@@ -526,17 +563,25 @@ def pack_b(B, range: float = DEFAULT_RANGE) -> Packed:  # noqa: A002
     return p
 
 
-def mm_packed(pa: Packed, pb: Packed, C=None):
-    """int8 MFMA GEMM + fused dequantize (op_mm.cuh:92-99) on packed operands."""
+def mm_packed(pa: Packed, pb: Packed, C=None, out_dtype=None):
+    """int8 MFMA GEMM + fused dequantize (op_mm.cuh:92-99) on packed operands.  The output is fp32 unless a bf16 C
+    or out_dtype=torch.bfloat16 is given: then each fp32 result is rounded once to bf16 (qgemm_mm_packed_dt)."""
     import torch
     assert pa.k == pb.k, "X.w == W.h"
     if C is None:
-        C = torch.empty((pa.rows, pb.rows), dtype=torch.float32, device=pa.buf.device)
-    _require_device_f32(C, "C")
+        C = torch.empty((pa.rows, pb.rows), dtype=_out_dtype(None, out_dtype, torch.float32), device=pa.buf.device)
+    else:
+        _out_dtype(C, out_dtype, None)
+    tag = _require_device_act(C, "C")
     assert C.shape == (pa.rows, pb.rows)
-    _check("qgemm_mm_packed", load().qgemm_mm_packed(pa.buf.data_ptr(), pb.buf.data_ptr(), C.data_ptr(), C.stride(0),
-                                                    C.stride(1), pa.rows, pb.rows, pa.k, float(pa.range),
-                                                    _stream(C.device)))
+    if tag == QGEMM_F32:
+        _check("qgemm_mm_packed", load().qgemm_mm_packed(pa.buf.data_ptr(), pb.buf.data_ptr(), C.data_ptr(),
+                                                        C.stride(0), C.stride(1), pa.rows, pb.rows, pa.k,
+                                                        float(pa.range), _stream(C.device)))
+    else:
+        _check("qgemm_mm_packed_dt", load().qgemm_mm_packed_dt(pa.buf.data_ptr(), pb.buf.data_ptr(), C.data_ptr(), tag,
+                                                              C.stride(0), C.stride(1), pa.rows, pb.rows, pa.k,
+                                                              float(pa.range), _stream(C.device)))
     return C
 
 
@@ -583,23 +628,35 @@ def error_stats(C, O, reference_order: bool = False) -> dict:
                 rel=v[2] / v[4] if v[4] else float("nan"))
 
 
-def linear(X, pw: Packed, bias=None, relu: bool = False, Y=None):
+def linear(X, pw: Packed, bias=None, relu: bool = False, Y=None, out_dtype=None):
     """LinearLayer.forward on the quantized path (linear.cuh:50-54): quantized_mm(X, W) [+ b] [relu],
-    W packed once by pack_b."""
+    W packed once by pack_b.  X and Y are fp32 or bf16, independently (qgemm_linear_dt): a given Y decides the
+    output type, then out_dtype, then X's own type.  bias stays fp32."""
     import torch
-    _require_device_f32(X, "X")
+    xt = _require_device_act(X, "X")
     assert X.stride(1) == 1 and X.shape[1] == pw.k
     assert pw.range == DEFAULT_RANGE, f"qgemm_linear needs a weight packed with range {DEFAULT_RANGE}"
     M, K = X.shape
     N = pw.rows
     if Y is None:
-        Y = torch.empty((M, N), dtype=torch.float32, device=X.device)
+        Y = torch.empty((M, N), dtype=_out_dtype(None, out_dtype, X.dtype), device=X.device)
+    else:
+        _out_dtype(Y, out_dtype, None)
+    yt = _require_device_act(Y, "Y")
     assert Y.shape == (M, N) and Y.stride(1) == 1
+    if bias is not None:
+        assert bias.dtype == torch.float32, "bias stays float32"
     L = load()
     ws = torch.empty(max(1, L.qgemm_linear_workspace_size(M, N, K)), dtype=torch.uint8, device=X.device)
     b = 0 if bias is None else bias.data_ptr()
-    _check("qgemm_linear", L.qgemm_linear(X.data_ptr(), X.stride(0), M, K, pw.buf.data_ptr(), N, b, 1 if relu else 0,
-                                          Y.data_ptr(), Y.stride(0), ws.data_ptr(), ws.numel(), _stream(X.device)))
+    if xt == QGEMM_F32 and yt == QGEMM_F32:
+        _check("qgemm_linear", L.qgemm_linear(X.data_ptr(), X.stride(0), M, K, pw.buf.data_ptr(), N, b,
+                                              1 if relu else 0, Y.data_ptr(), Y.stride(0), ws.data_ptr(), ws.numel(),
+                                              _stream(X.device)))
+    else:
+        _check("qgemm_linear_dt", L.qgemm_linear_dt(X.data_ptr(), xt, X.stride(0), M, K, pw.buf.data_ptr(), N, b,
+                                                    1 if relu else 0, Y.data_ptr(), yt, Y.stride(0), ws.data_ptr(),
+                                                    ws.numel(), _stream(X.device)))
     return Y
 
 

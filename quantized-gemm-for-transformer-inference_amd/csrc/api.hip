@@ -35,6 +35,15 @@ hipError_t pack_vectors(const float *src, int64_t row_stride, int64_t elem_strid
     return launch_pack_rows(src, row_stride, elem_stride, rows, len, range, out, stream);
 }
 
+// A bf16 matrix (qgemm_pack_a_dt): contiguous rows take pack_rows' vector kernels where they are 16-B aligned, and
+// every other layout -- columns of a row-major image included -- its generic strided kernel.
+hipError_t pack_vectors(const bf16_t *src, int64_t row_stride, int64_t elem_stride, int rows, int len, float range,
+                        PackedView out, hipStream_t stream) {
+    return launch_pack_rows(src, row_stride, elem_stride, rows, len, range, out, stream);
+}
+
+bool dtype_ok(int t) { return t == QGEMM_F32 || t == QGEMM_BF16; }
+
 // Grow-only cached buffers for the entry points without an explicit workspace, one per (device, stream, use): a
 // buffer is only reused in its stream's order, so calls on different streams never share packed operands or split-K
 // tickets (the reference allocates its temporaries per call, op_mm.cuh:76-93).  hipStreamPerThread names a different
@@ -125,12 +134,12 @@ hipError_t cached_scratch(size_t need, hipStream_t stream, int use, void **out) 
     return cached_buffer(need, stream, use, true, 0, out);
 }
 
-hipError_t mm_packed_impl(const void *packed_a, const void *packed_b, float *C, int64_t c_stride_h,
+hipError_t mm_packed_impl(const void *packed_a, const void *packed_b, void *C, int64_t c_stride_h,
                           int64_t c_stride_w, int m, int n, int k, float range, void *scratch, size_t scratch_bytes,
-                          hipStream_t stream, bool tickets_zeroed = false) {
+                          hipStream_t stream, bool tickets_zeroed = false, bool c_bf16 = false) {
     const float inv_r2 = 1.0f / (range * range);  // op_mm.cuh:99, one rounding per operation (host IEEE)
     return launch_gemm_dequant(packed_view(packed_a, m, k), packed_view(packed_b, n, k), C, c_stride_h, c_stride_w, m,
-                               n, inv_r2, scratch, scratch_bytes, stream, nullptr, false, tickets_zeroed);
+                               n, inv_r2, scratch, scratch_bytes, stream, nullptr, false, tickets_zeroed, c_bf16);
 }
 
 }  // namespace
@@ -279,6 +288,62 @@ int qgemm_linear(const float *X, int64_t x_stride_h, int m, int k, const void *p
     const float inv_r2 = 1.0f / (kDefaultRange * kDefaultRange);
     return err(launch_gemm_dequant(va, packed_view(packed_w, n, k), Y, y_stride_h, 1, m, n, inv_r2, scratch, sb, s, bias,
                                    relu != 0));
+}
+
+// ---- bf16 activations and outputs: the same chain, only its two ends change (include/qgemm.h) ----
+
+int qgemm_pack_a_dt(const void *A, int a_dtype, int64_t a_stride_h, int64_t a_stride_w, int m, int k, float range,
+                    void *packed_a, void *stream) {
+    if (!dtype_ok(a_dtype)) return err(hipErrorInvalidValue);
+    if (a_dtype == QGEMM_F32)
+        return qgemm_pack_a(static_cast<const float *>(A), a_stride_h, a_stride_w, m, k, range, packed_a, stream);
+    if (!A || !packed_a || m < 0 || k < 1) return err(hipErrorInvalidValue);
+    if (m == 0) return 0;
+    return err(pack_vectors(static_cast<const bf16_t *>(A), a_stride_h, a_stride_w, m, k, range,
+                            packed_view(packed_a, m, k), static_cast<hipStream_t>(stream)));
+}
+
+int qgemm_mm_packed_dt(const void *packed_a, const void *packed_b, void *C, int c_dtype, int64_t c_stride_h,
+                       int64_t c_stride_w, int m, int n, int k, float range, void *stream) {
+    if (!dtype_ok(c_dtype)) return err(hipErrorInvalidValue);
+    if (c_dtype == QGEMM_F32)
+        return qgemm_mm_packed(packed_a, packed_b, static_cast<float *>(C), c_stride_h, c_stride_w, m, n, k, range, stream);
+    if (!packed_a || !packed_b || !C || !dims_ok(m, n, k)) return err(hipErrorInvalidValue);
+    if (m == 0 || n == 0) return 0;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    void *scratch = nullptr;
+    const size_t sb = gemm_scratch_bytes(m, n, k);
+    if (sb) {
+        hipError_t e = cached_scratch(sb, s, kUseSplitK, &scratch);
+        if (e != hipSuccess) return err(e);
+    }
+    return err(mm_packed_impl(packed_a, packed_b, C, c_stride_h, c_stride_w, m, n, k, range, scratch, sb, s,
+                              /*tickets_zeroed=*/true, /*c_bf16=*/true));
+}
+
+int qgemm_linear_dt(const void *X, int x_dtype, int64_t x_stride_h, int m, int k, const void *packed_w, int n,
+                    const float *bias, int relu, void *Y, int y_dtype, int64_t y_stride_h, void *workspace,
+                    size_t ws_bytes, void *stream) {
+    if (!dtype_ok(x_dtype) || !dtype_ok(y_dtype)) return err(hipErrorInvalidValue);
+    if (x_dtype == QGEMM_F32 && y_dtype == QGEMM_F32)
+        return qgemm_linear(static_cast<const float *>(X), x_stride_h, m, k, packed_w, n, bias, relu,
+                            static_cast<float *>(Y), y_stride_h, workspace, ws_bytes, stream);
+    if (!X || !packed_w || !Y || m < 0 || n < 0 || k < 1 || (relu && !bias)) return err(hipErrorInvalidValue);
+    if (m == 0 || n == 0) return 0;
+    const size_t need = qgemm_linear_workspace_size(m, n, k);
+    if (!workspace || ws_bytes < need) return err(hipErrorInvalidValue);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    char *scratch = static_cast<char *>(workspace);
+    const size_t sb = gemm_scratch_bytes(m, n, k);
+    char *pa = scratch + align256(sb);
+    const PackedView va = packed_view(pa, m, k);
+    const hipError_t e = x_dtype == QGEMM_BF16
+                             ? pack_vectors(static_cast<const bf16_t *>(X), x_stride_h, 1, m, k, kDefaultRange, va, s)
+                             : pack_vectors(static_cast<const float *>(X), x_stride_h, 1, m, k, kDefaultRange, va, s);
+    if (e != hipSuccess) return err(e);
+    const float inv_r2 = 1.0f / (kDefaultRange * kDefaultRange);
+    return err(launch_gemm_dequant(va, packed_view(packed_w, n, k), Y, y_stride_h, 1, m, n, inv_r2, scratch, sb, s, bias,
+                                   relu != 0, false, y_dtype == QGEMM_BF16));
 }
 
 size_t qgemm_linear_workspace_size(int m, int n, int k) {

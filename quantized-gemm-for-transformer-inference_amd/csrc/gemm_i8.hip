@@ -6,6 +6,7 @@
 //   op_dequantize + op_multiply    (two more M x N passes)
 // by one kernel that reads the packed int8 operands once per macro-tile and writes fp32 O once.
 #include <hip/hip_ext.h>
+#include <stdlib.h>
 
 #include "gemm_i8_kernels.h"
 
@@ -138,36 +139,71 @@ static hipError_t launch_timed(dim3 grid, dim3 block, hipStream_t stream, const 
     return e;
 }
 
-template <int kEpi>
+template <int kEpi, bool kBf16 = false>
 static hipError_t launch_v3(const GemmArgs &p, dim3 grid, hipStream_t stream) {
     if constexpr (kEpi != kEpiOutlier) {
         // ticket-first split-K, slice 0 = 31/64 of the k-steps (lab/t2_lab.hip, lab/c3d_lab.hip; profiles/
         // r04_splitfirst_*.log: FFN-down GEMM alone 110.5 -> 105.8 us, the whole drop-in call 284.7 -> 279.7 us)
         if (p.splits == 2)
-            return launch_timed(grid, dim3(kFmThreads), stream, p, gemm_i8_fm<kEpi, false, kSplitFirst, true, 31>);
+            return launch_timed(grid, dim3(kFmThreads), stream, p, gemm_i8_fm<kEpi, false, kSplitFirst, true, 31, kBf16>);
         if (p.splits > 2) return hipErrorNotSupported;  // gemm_plan never makes one (tiles in [128, 160) -> S <= 2)
     }
-    return launch_timed(grid, dim3(kFmThreads), stream, p, gemm_i8_fm<kEpi>);
+    return launch_timed(grid, dim3(kFmThreads), stream, p, gemm_i8_fm<kEpi, false, kSplitNone, true, 30, kBf16>);
 }
 
-template <int TB, int kEpi, int kDepth>
+template <int TB, int kEpi, int kDepth, bool kBf16 = false>
 static hipError_t launch_small(const GemmArgs &p, dim3 grid, hipStream_t stream) {
     const GemmEvents ev = take_gemm_events();
     if ((ev.start || ev.stop) && g_event_mode == 0) {
-        hipExtLaunchKernelGGL((gemm_i8_small<TB, kEpi, kDepth>), grid, dim3(SmallTile<TB, kDepth>::kThreads), 0, stream,
+        hipExtLaunchKernelGGL((gemm_i8_small<TB, kEpi, kDepth, kBf16>), grid, dim3(SmallTile<TB, kDepth>::kThreads), 0, stream,
                               ev.start, ev.stop, 0, p);
         return hipGetLastError();
     }
     if (ev.start) (void)hipEventRecord(ev.start, stream);
-    gemm_i8_small<TB, kEpi, kDepth><<<grid, dim3(SmallTile<TB, kDepth>::kThreads), 0, stream>>>(p);
+    gemm_i8_small<TB, kEpi, kDepth, kBf16><<<grid, dim3(SmallTile<TB, kDepth>::kThreads), 0, stream>>>(p);
     hipError_t e = hipGetLastError();
     if (ev.stop) (void)hipEventRecord(ev.stop, stream);
     return e;
 }
 
-hipError_t launch_gemm_dequant(const PackedView &a, const PackedView &b, float *C, int64_t csh, int64_t csw, int m,
+// the plan's kernel at the epilogue (none / bias / bias + relu) and output type asked for
+template <bool kBf16>
+static hipError_t dispatch_dequant(const GemmPlan &g, const GemmArgs &p, dim3 grid, int64_t tiles, const float *bias,
+                                   bool relu, hipStream_t stream) {
+    if (g.tile == 32) {
+        if (!bias) return launch_small<32, kEpiNone, 4, kBf16>(p, grid, stream);
+        return relu ? launch_small<32, kEpiBiasRelu, 4, kBf16>(p, grid, stream) : launch_small<32, kEpiBias, 4, kBf16>(p, grid, stream);
+    }
+    if (g.tile == 64) {
+        // at most two 64-tiles per CU: a 3-stage ring (two k-steps in flight, three blocks per CU); more
+        // tiles: the 2-stage ring, four blocks per CU (gemm_lab ... small, us: 512x1024x1024 6.10 -> 5.67,
+        // 512x1024x4096 S2 10.73 -> 9.91, 512x3072x1024 7.43 -> 7.20; 2048^3 18.1 -> 22.3 with 3 stages)
+        if (tiles <= 512) {
+            if (!bias) return launch_small<64, kEpiNone, 3, kBf16>(p, grid, stream);
+            return relu ? launch_small<64, kEpiBiasRelu, 3, kBf16>(p, grid, stream) : launch_small<64, kEpiBias, 3, kBf16>(p, grid, stream);
+        }
+        if (!bias) return launch_small<64, kEpiNone, 2, kBf16>(p, grid, stream);
+        return relu ? launch_small<64, kEpiBiasRelu, 2, kBf16>(p, grid, stream) : launch_small<64, kEpiBias, 2, kBf16>(p, grid, stream);
+    }
+    if (!bias) return launch_v3<kEpiNone, kBf16>(p, grid, stream);
+    return relu ? launch_v3<kEpiBiasRelu, kBf16>(p, grid, stream) : launch_v3<kEpiBias, kBf16>(p, grid, stream);
+}
+
+// First row stride (in bf16 elements) at which gemm_i8_fm's bf16 output leaves through the LDS image (and the 8-tile-row
+// XCD patches that go with it) instead of the exchanged register stores: 16 384, i.e. rows of 32 KiB -- half the
+// bytes of the fp32 switch point.  Measured at FFN up (2048 x 16384 x 4096, bf16 in and out, the whole call, same
+// process, alternated; profiles/bf16_store_paths.log): LDS image 108.2 us, register stores 114.1-114.2 us.  Narrower
+// rows are not measured and keep the register stores.  QGEMM_BF16_WIDE_MIN overrides it per call
+// (scripts/bf16_linear_probe.py --stores; 0 = always the image, a huge value = never).
+constexpr int64_t kBf16WideRowsMin = 16384;
+static int64_t bf16_wide_rows_min() {
+    const char *e = getenv("QGEMM_BF16_WIDE_MIN");
+    return e && *e ? atoll(e) : kBf16WideRowsMin;
+}
+
+hipError_t launch_gemm_dequant(const PackedView &a, const PackedView &b, void *C, int64_t csh, int64_t csw, int m,
                                int n, float inv_r2, void *scratch, size_t scratch_bytes, hipStream_t stream,
-                               const float *bias, bool relu, bool tickets_zeroed) {
+                               const float *bias, bool relu, bool tickets_zeroed, bool c_bf16) {
     if (!shape_ok(a, b)) return hipErrorInvalidValue;
     const GemmPlan g = gemm_plan(m, n, (int)a.k_pad);
     GemmArgs p{a.q, b.q, a.scale, b.scale, C, csh, csw, m, n, a.k_pad, g.tiles_m, g.tiles_n,
@@ -177,6 +213,7 @@ hipError_t launch_gemm_dequant(const PackedView &a, const PackedView &b, float *
     // segments, rotated per tile); its paired nontemporal register stores ran 122.6 vs 112.3 us there
     // (lab/ds_lab.hip) and plain ones left the output in the caches
     p.wide_rows = (csw == 1 && csh >= 16384) ? 1 : 0;
+    if (c_bf16) p.wide_rows = (csw == 1 && csh >= bf16_wide_rows_min()) ? 1 : 0;
     if (g.splits > 1 && scratch && scratch_bytes >= gemm_scratch_bytes(m, n, (int)a.k_pad)) {
         p.splits = g.splits;
         p.tickets = static_cast<unsigned *>(scratch);
@@ -191,23 +228,8 @@ hipError_t launch_gemm_dequant(const PackedView &a, const PackedView &b, float *
         }
     }
     const dim3 grid((unsigned)(tiles * p.splits));
-    if (g.tile == 32) {
-        if (!bias) return launch_small<32, kEpiNone, 4>(p, grid, stream);
-        return relu ? launch_small<32, kEpiBiasRelu, 4>(p, grid, stream) : launch_small<32, kEpiBias, 4>(p, grid, stream);
-    }
-    if (g.tile == 64) {
-        // at most two 64-tiles per CU: a 3-stage ring (two k-steps in flight, three blocks per CU); more
-        // tiles: the 2-stage ring, four blocks per CU (gemm_lab ... small, us: 512x1024x1024 6.10 -> 5.67,
-        // 512x1024x4096 S2 10.73 -> 9.91, 512x3072x1024 7.43 -> 7.20; 2048^3 18.1 -> 22.3 with 3 stages)
-        if (tiles <= 512) {
-            if (!bias) return launch_small<64, kEpiNone, 3>(p, grid, stream);
-            return relu ? launch_small<64, kEpiBiasRelu, 3>(p, grid, stream) : launch_small<64, kEpiBias, 3>(p, grid, stream);
-        }
-        if (!bias) return launch_small<64, kEpiNone, 2>(p, grid, stream);
-        return relu ? launch_small<64, kEpiBiasRelu, 2>(p, grid, stream) : launch_small<64, kEpiBias, 2>(p, grid, stream);
-    }
-    if (!bias) return launch_v3<kEpiNone>(p, grid, stream);
-    return relu ? launch_v3<kEpiBiasRelu>(p, grid, stream) : launch_v3<kEpiBias>(p, grid, stream);
+    return c_bf16 ? dispatch_dequant<true>(g, p, grid, tiles, bias, relu, stream)
+                  : dispatch_dequant<false>(g, p, grid, tiles, bias, relu, stream);
 }
 
 bool gemm_outlier_ok(int m, int n, int k) {

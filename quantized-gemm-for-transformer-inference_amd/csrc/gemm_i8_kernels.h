@@ -194,9 +194,21 @@ enum SplitMode { kSplitNone = 0, kSplitFirst = 2 };
 // kNtC: the paired full-tile output stores (rows < 64 KiB) are nontemporal -- the 64-MiB tail streams past the
 // caches (lab/ds_lab.hip: dsPn 56.30 vs plain pairs 56.99 us at 4096^3).  The wide-row LDS-image stores are
 // nontemporal in every instantiation (qgemm_mm_packed_i32, the one kNtC = false caller, never sets wide_rows).
-template <int kEpi = kEpiNone, bool kI32 = false, int kSplit = kSplitNone, bool kNtC = !kI32, int kFirst64 = 30>
+// kBf16: C holds bf16 (csh / csw in bf16 elements).  The epilogue's fp32 values are rounded once (pk_bf16: a lane's four
+// columns of a tile become two dwords) and leave in one of three shapes, chosen as for fp32:
+//   full tiles, rows below the wide-row switch: tiles 2 np and 2 np + 1 are exchanged between the lane rows kq and
+//     kq ^ 1 (v_permlane16_swap: two per tile pair), after which a lane holds 8 consecutive columns of its row --
+//     columns 8 (kq >> 1) .. + 7 of tile 2 np + (kq & 1) -- and stores them as 16 B, nontemporal: one store instruction
+//     writes 16 rows x 64 B.  (The fp32 exchange between rows c and c ^ 8 would leave 8-B stores: twice the store
+//     instructions for the same bytes, and the store tail is issue-bound.)
+//   full tiles, wide rows: the wave's LDS image holds bf16 (8-B writes, rows of TSH dwords) and leaves as 256-B row
+//     segments, 4 rows per store instruction, in the per-tile rotated order;
+//   ragged tiles, odd strides or a base off 16 B: 2-B scalar stores.
+template <int kEpi = kEpiNone, bool kI32 = false, int kSplit = kSplitNone, bool kNtC = !kI32, int kFirst64 = 30,
+          bool kBf16 = false>
 __global__ __launch_bounds__(kFmThreads, 1) void gemm_i8_fm(GemmArgs p) {
     static_assert(!(kI32 && kEpi != kEpiNone), "raw accumulators take no epilogue extras");
+    static_assert(!(kBf16 && (kI32 || kEpi == kEpiOutlier)), "bf16 output: the dequantized plain / bias / relu epilogues");
     static_assert(!(kI32 && kSplit), "raw accumulators are not split");
     static_assert(!(kEpi == kEpiOutlier && kSplit), "the outlier epilogue runs on unsplit plans");
     // the one LDS array: the tile's scales (Cx of its 256 rows, Cw of its 256 columns), the split-K ticket word,
@@ -392,12 +404,17 @@ __global__ __launch_bounds__(kFmThreads, 1) void gemm_i8_fm(GemmArgs p) {
     const v2f inv2 = {p.inv_r2, p.inv_r2};
     const v2f zero2 = {0.0f, 0.0f};
     float *C = static_cast<float *>(p.C);
-    const bool full = p.csw == 1 && (p.csh % 4 == 0) && ((reinterpret_cast<uintptr_t>(p.C) & 15) == 0) &&
+    uint16_t *Ch = static_cast<uint16_t *>(p.C);  // kBf16
+    // 16-B stores: rows of a multiple of 4 floats / 8 bf16 from a 16-B base
+    const bool full = p.csw == 1 && (p.csh % (kBf16 ? 8 : 4) == 0) && ((reinterpret_cast<uintptr_t>(p.C) & 15) == 0) &&
                       gj0 + BN <= p.n && gi0 + BM <= p.m;
     const bool pairs = full && !p.wide_rows;
     const bool image = full && p.wide_rows;
     const bool lo = c < 8;
     float *T = sS + 2 * BM + 4 + wave * 64 * TS;  // this wave's image (wide rows)
+    // kBf16: the image's rows are 64 dwords (128 bf16) + 4: 16-B aligned, and the 8-B writes of a lane group (16 rows x
+    // two k-groups) fall on 64 different banks (row stride 4 mod 64, + 2 kq + {0, 1})
+    constexpr int TSH = 68;
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
         // split-K reducer: the other slice's partial sums of this half (32 sc1 loads in flight, then the adds)
@@ -475,7 +492,36 @@ __global__ __launch_bounds__(kFmThreads, 1) void gemm_i8_fm(GemmArgs p) {
 #pragma unroll
             for (int np = 0; np < 4; ++np) {
                 const v4f o0 = tile_out(2 * np), o1 = tile_out(2 * np + 1);
-                if (pairs) {
+                if constexpr (kBf16) {
+                    // columns 4 kq .. + 3 of tiles 2 np (a) and 2 np + 1 (b), rounded: two dwords each
+                    const uint32_t a0 = pk_bf16(o0[0], o0[1]), a1 = pk_bf16(o0[2], o0[3]);
+                    const uint32_t b0 = pk_bf16(o1[0], o1[1]), b1 = pk_bf16(o1[2], o1[3]);
+                    if (pairs) {
+                        // v_permlane16_swap(a, b): a's odd lane rows <-> b's even lane rows.  Afterwards the first
+                        // result holds, in lane row kq, tile 2 np + (kq & 1) from lane row kq & 2 (columns 4 (kq & 2)
+                        // .. + 3) and the second the same tile from lane row (kq & 2) + 1 (the next four columns)
+                        const auto s0 = __builtin_amdgcn_permlane16_swap(a0, b0, false, false);
+                        const auto s1 = __builtin_amdgcn_permlane16_swap(a1, b1, false, false);
+                        const v4f x = {__uint_as_float(s0[0]), __uint_as_float(s1[0]), __uint_as_float(s0[1]),
+                                       __uint_as_float(s1[1])};
+                        const int jc = gj0 + c0 + 32 * np + 16 * (kq & 1) + 8 * (kq >> 1);
+                        __builtin_nontemporal_store(x, reinterpret_cast<v4f *>(Ch + row * p.csh + jc));
+                    } else if (image) {
+                        float *Tr = T + (16 * mq + c) * TSH + 16 * np + 2 * kq;
+                        *reinterpret_cast<v2f *>(Tr) = v2f{__uint_as_float(a0), __uint_as_float(a1)};
+                        *reinterpret_cast<v2f *>(Tr + 8) = v2f{__uint_as_float(b0), __uint_as_float(b1)};
+                    } else {
+                        const int j = gj0 + c0 + 32 * np + 4 * kq;  // tile 2 np; tile 2 np + 1 at j + 16
+                        if (row < p.m) {
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) {
+                                const uint32_t ha = (e < 2 ? a0 : a1) >> (16 * (e & 1)), hb = (e < 2 ? b0 : b1) >> (16 * (e & 1));
+                                if (j + e < p.n) Ch[row * p.csh + (int64_t)(j + e) * p.csw] = (uint16_t)ha;
+                                if (j + 16 + e < p.n) Ch[row * p.csh + (int64_t)(j + 16 + e) * p.csw] = (uint16_t)hb;
+                            }
+                        }
+                    }
+                } else if (pairs) {
                     // tiles 2 np and 2 np + 1 exchanged between lanes c and c ^ 8 (DPP row_ror:8): rows 16 mi + (c & 7)
                     // take store 1, rows 16 mi + 8 + (c & 7) store 2, each 8 rows x 128 B
                     v4f x1, x2;
@@ -512,6 +558,20 @@ __global__ __launch_bounds__(kFmThreads, 1) void gemm_i8_fm(GemmArgs p) {
                 }
             }
         }
+        if constexpr (kBf16) {
+            if (image) {
+                // a bf16 row of the quadrant is 256 B = 16 lanes: 4 rows per store instruction, 16 instructions per half
+                const int rot = __builtin_amdgcn_readfirstlane((tn * 13 + tm * 7) & 15);
+                const int d4 = (lane & 15) * 4;  // the lane's dword of the row: bf16 columns 2 d4 .. + 7
+#pragma unroll 8
+                for (int it = 0; it < 16; ++it) {
+                    const int rr = 4 * ((it + rot) & 15) + (lane >> 4);
+                    const v4f v = *reinterpret_cast<const v4f *>(T + rr * TSH + d4);
+                    __builtin_nontemporal_store(
+                        v, reinterpret_cast<v4f *>(Ch + (int64_t)(gi0 + r0 + 64 * s + rr) * p.csh + gj0 + c0 + 2 * d4));
+                }
+            }
+        } else
         if (image) {
             // wide rows: the half's 64 rows read back from the wave's own image (one wave's LDS operations stay in
             // order) and stored as 512-B row segments, nontemporal: plain stores there leave the 128-MiB FFN-up output
@@ -560,7 +620,8 @@ constexpr int TB = 128;
 constexpr int kThreads = SmallTile<128>::kThreads;
 }  // namespace t128
 
-template <int TB, int kEpi = kEpiNone, int kDepth = 2>
+// kBf16: C holds bf16: the fp32 tile image in LDS is rounded on the way out (pk_bf16), 8 columns = 16 B per lane.
+template <int TB, int kEpi = kEpiNone, int kDepth = 2, bool kBf16 = false>
 __global__ __launch_bounds__((SmallTile<TB, kDepth>::kThreads), (SmallTile<TB, kDepth>::kMinBlocks)) void gemm_i8_small(
     GemmArgs p) {
     using T_ = SmallTile<TB, kDepth>;
@@ -704,6 +765,30 @@ __global__ __launch_bounds__((SmallTile<TB, kDepth>::kThreads), (SmallTile<TB, k
             }
     }
     __syncthreads();
+    if constexpr (kBf16) {
+        uint16_t *C = static_cast<uint16_t *>(p.C);
+        const bool full = p.csw == 1 && (p.csh % 8 == 0) && ((reinterpret_cast<uintptr_t>(p.C) & 15) == 0) && gj0 + TB <= p.n;
+        constexpr int kLanesPerRow = TB / 8;
+        const int c8 = (tid % kLanesPerRow) * 8;
+#pragma unroll 2
+        for (int rr = tid / kLanesPerRow; rr < TB; rr += T_::kThreads / kLanesPerRow) {
+            const int i = gi0 + rr;
+            if (i >= p.m) break;
+            const float4 v0 = *reinterpret_cast<const float4 *>(T + rr * TB + c8);
+            const float4 v1 = *reinterpret_cast<const float4 *>(T + rr * TB + c8 + 4);
+            const uint4 h = make_uint4(pk_bf16(v0.x, v0.y), pk_bf16(v0.z, v0.w), pk_bf16(v1.x, v1.y), pk_bf16(v1.z, v1.w));
+            const int j = gj0 + c8;
+            if (full) {
+                *reinterpret_cast<uint4 *>(C + (int64_t)i * p.csh + j) = h;
+            } else {
+                const uint32_t hh[4] = {h.x, h.y, h.z, h.w};
+#pragma unroll
+                for (int e = 0; e < 8; ++e)
+                    if (j + e < p.n) C[(int64_t)i * p.csh + (int64_t)(j + e) * p.csw] = (uint16_t)(hh[e >> 1] >> (16 * (e & 1)));
+            }
+        }
+        return;
+    }
     float *C = static_cast<float *>(p.C);
     const bool full = p.csw == 1 && (p.csh % 4 == 0) && ((reinterpret_cast<uintptr_t>(p.C) & 15) == 0) && gj0 + TB <= p.n;
     constexpr int kLanesPerRow = TB / 4;

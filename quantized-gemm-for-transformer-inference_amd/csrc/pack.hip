@@ -19,6 +19,7 @@
 //               the two HBM streams overlap and a launch boundary disappears.
 #include <algorithm>
 #include <atomic>
+#include <type_traits>
 
 #include "qgemm_internal.h"
 
@@ -48,6 +49,36 @@ __device__ __forceinline__ uint32_t pack4(int a, int b, int c, int d) {
     const uint32_t lo = __builtin_amdgcn_perm((uint32_t)b, (uint32_t)a, 0x0c0c0400u);
     const uint32_t hi = __builtin_amdgcn_perm((uint32_t)d, (uint32_t)c, 0x0c0c0400u);
     return __builtin_amdgcn_perm(hi, lo, 0x05040100u);
+}
+
+// ---- bf16 source rows (launch_pack_rows(const bf16_t *)) ----
+// A 16-B load carries 8 bf16: the chunk's dword e holds elements 2e (low half) and 2e + 1 (high half).  Chunk c of a row
+// is k = 8c .. 8c + 7, i.e. dwords 2c and 2c + 1 of the packed row: 8 B that stay contiguous in the fragment-major
+// q (8c % 16 is 0 or 8, inside one 16-byte k group).
+typedef uint32_t v4u_t __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ float bf_lo(uint32_t u) { return __uint_as_float(u << 16); }
+__device__ __forceinline__ float bf_hi(uint32_t u) { return __uint_as_float(u & 0xffff0000u); }
+// |x| candidates of one chunk; `first`: the chunk starts the row, whose element 0 is the seed
+__device__ __forceinline__ float cand_max8(float p, v4u_t x, bool first) {
+    p = first ? p : cand_max(p, bf_lo(x[0]));
+    p = cand_max(p, bf_hi(x[0]));
+#pragma unroll
+    for (int e = 1; e < 4; ++e) {
+        p = cand_max(p, bf_lo(x[e]));
+        p = cand_max(p, bf_hi(x[e]));
+    }
+    return p;
+}
+// the chunk's two packed dwords
+__device__ __forceinline__ uint2 quant8(v4u_t x, float s) {
+    return make_uint2(pack4(quant_i8(bf_lo(x[0]), s), quant_i8(bf_hi(x[0]), s), quant_i8(bf_lo(x[1]), s), quant_i8(bf_hi(x[1]), s)),
+                      pack4(quant_i8(bf_lo(x[2]), s), quant_i8(bf_hi(x[2]), s), quant_i8(bf_lo(x[3]), s), quant_i8(bf_hi(x[3]), s)));
+}
+// the (len & 7) tail elements of a bf16 row from element tail0 on: up to two dwords
+__device__ __forceinline__ uint2 quant_tail8(const bf16_t *srow, int tail0, int rem, float s) {
+    int b[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (int e = 0; e < rem; ++e) b[e] = quant_i8(widen(srow[tail0 + e]), s);
+    return make_uint2(pack4(b[0], b[1], b[2], b[3]), pack4(b[4], b[5], b[6], b[7]));
 }
 
 // W strips hold 4 consecutive k of one column per dword; a 16-B piece of the fragment-major q (one packed row,
@@ -185,8 +216,10 @@ __device__ __forceinline__ void outlier_column_list(const OutlierMask &om, int *
 // kStage: the packed row goes to `stage` (the wave's LDS row, dword c at stage[c]) instead of q; the caller
 // writes the block's staged rows out as whole 128-B lines of the fragment-major q (write_staged_rows).
 // kGroup: rows per `blk` (wave w of the block takes row blk * kGroup + w).
-template <int R, bool kMask = false, bool kWT = false, bool kStage = false, int kGroup = 4>
-__device__ __forceinline__ void pack_rows_vec_body(int64_t blk, const float *__restrict__ src, int64_t sh, int rows,
+// SrcT = bf16_t: rows of bf16, 8 per 16-B chunk (R chunks per lane: len <= 512 * R), kept as loaded and widened
+// where they are used; everything else as for float.
+template <int R, bool kMask = false, bool kWT = false, bool kStage = false, int kGroup = 4, typename SrcT = float>
+__device__ __forceinline__ void pack_rows_vec_body(int64_t blk, const SrcT *__restrict__ src, int64_t sh, int rows,
                                                    int len, float range, float *__restrict__ scale,
                                                    int8_t *__restrict__ q, int64_t rows_pad, int64_t k_pad,
                                                    const OutlierMask *om = nullptr, uint32_t *stage = nullptr) {
@@ -205,6 +238,56 @@ __device__ __forceinline__ void pack_rows_vec_body(int64_t blk, const float *__r
         if (lane == 0) st_f32<kWT>(scale + row, 0.0f);
         return;
     }
+    if constexpr (!std::is_same<SrcT, float>::value) {
+        static_assert(!kMask && !kWT, "bf16 rows: the plain row packs only");
+        const bf16_t *srow = src + row * sh;
+        const int nfull = len >> 3;  // complete 8-element chunks
+        const float seed = widen(srow[0]);
+        // dwords 2c, 2c + 1 of the packed row: one 8-B store (the stage rows and the q pieces are 8-B aligned)
+        auto put2 = [&](int64_t c, uint2 d) __attribute__((always_inline)) {
+            if constexpr (kStage) *reinterpret_cast<uint2 *>(stage + 2 * c) = d;
+            else *reinterpret_cast<uint2 *>(qword(q, row, 8 * c, k_pad)) = d;
+        };
+        float p = -INFINITY;
+        v4u_t v[R > 0 ? R : 1];
+        if constexpr (R > 0) {
+            const auto rs = buf_rsrc(srow, (uint32_t)nfull * 16);  // chunks >= nfull read as zeros
+#pragma unroll
+            for (int j = 0; j < R; ++j)
+                v[j] = __builtin_bit_cast(v4u_t, __builtin_amdgcn_raw_buffer_load_b128(rs, (uint32_t)(lane + j * kWave) * 16, 0, 0));
+#pragma unroll
+            for (int j = 0; j < R; ++j) {
+                const int c = lane + j * kWave;
+                if (c < nfull) p = cand_max8(p, v[j], c == 0);
+            }
+        } else {
+            for (int c = lane; c < nfull; c += kWave) p = cand_max8(p, *reinterpret_cast<const v4u_t *>(srow + 8 * (int64_t)c), c == 0);
+        }
+        const int tail0 = nfull << 3;  // scalar tail elements [tail0, len): at most 7
+        if (tail0 + lane < len && tail0 + lane > 0) p = cand_max(p, widen(srow[tail0 + lane]));
+        p = wave_max(p);
+        const float cx = absmax_finish(seed, p);
+        const float s = inv_divide(range, cx);
+        if constexpr (R > 0) {
+#pragma unroll
+            for (int j = 0; j < R; ++j) {
+                const int c = lane + j * kWave;
+                if (c < nfull) put2(c, quant8(v[j], s));
+            }
+        } else {
+            for (int c = lane; c < nfull; c += kWave) put2(c, quant8(*reinterpret_cast<const v4u_t *>(srow + 8 * (int64_t)c), s));
+        }
+        // partial tail dwords, then zero padding words
+        const int rem = len & 7;
+        if (rem && lane == 0) {
+            const uint2 d = quant_tail8(srow, tail0, rem, s);
+            put(2 * (int64_t)nfull, d.x);
+            if (rem > 4) put(2 * (int64_t)nfull + 1, d.y);
+        }
+        for (int64_t c = (((int64_t)len + 3) >> 2) + lane; c < nq; c += kWave) put(c, 0u);
+        if (lane == 0) st_f32<kWT>(scale + row, cx);
+        return;
+    } else {
     const float *srow = src + row * sh;
     const float4 *s4 = reinterpret_cast<const float4 *>(srow);
     const int nfull = len >> 2;  // complete float4 chunks
@@ -298,6 +381,7 @@ __device__ __forceinline__ void pack_rows_vec_body(int64_t blk, const float *__r
     }
     for (int64_t c = first_zero + lane; c < nq; c += kWave) put(c, 0u);
     if (lane == 0) st_f32<kWT>(scale + row, cx);
+    }
 }
 
 // Staged packed rows: kRows (8 or 16) consecutive packed rows row0 .. (row0 % 8 == 0), one per wave, in LDS
@@ -323,8 +407,10 @@ __device__ __forceinline__ void write_staged_rows(const uint32_t *stage, int rsw
 // thread in registers (4-KiB coalesced loads per block instruction), block-wide absmax (shuffle + LDS),
 // quantized from the registers -- one HBM read of the row.  `red` holds >= 5 floats of LDS.
 constexpr int kLongRowMax = 16384;
-template <bool kNt = false>
-__device__ __forceinline__ void pack_row_block_body(int64_t row, const float *__restrict__ src, int64_t sh, int rows,
+// SrcT = bf16_t: the same 16 chunks of 16 B per thread hold 8 elements each, so one block takes rows of up to 32 768.
+constexpr int kLongRowMaxBf16 = 32768;
+template <bool kNt = false, typename SrcT = float>
+__device__ __forceinline__ void pack_row_block_body(int64_t row, const SrcT *__restrict__ src, int64_t sh, int rows,
                                                     int len, float range, float *__restrict__ scale,
                                                     int8_t *__restrict__ q, int64_t rows_pad, int64_t k_pad,
                                                     float *red) {
@@ -337,6 +423,45 @@ __device__ __forceinline__ void pack_row_block_body(int64_t row, const float *__
         if (t == 0) scale[row] = 0.0f;
         return;
     }
+    if constexpr (!std::is_same<SrcT, float>::value) {
+        const bf16_t *srow = src + row * sh;
+        const int nfull = len >> 3;
+        v4u_t v[16];
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            const int c = t + 256 * j;
+            v[j] = (c < nfull) ? *reinterpret_cast<const v4u_t *>(srow + 8 * (int64_t)c) : v4u_t{0u, 0u, 0u, 0u};
+        }
+        float p = -INFINITY;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            const int c = t + 256 * j;
+            if (c < nfull) p = cand_max8(p, v[j], c == 0);
+        }
+        const int tail0 = nfull << 3;
+        if (tail0 + t < len && tail0 + t > 0) p = cand_max(p, widen(srow[tail0 + t]));
+        p = wave_max(p);
+        if (lane == 0) red[wv] = p;
+        if (t == 0) red[4] = widen(srow[0]);  // the seed
+        __syncthreads();
+        p = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));  // -inf or >= +0: exact
+        const float cx = absmax_finish(red[4], p);
+        const float sc = inv_divide(range, cx);
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            const int c = t + 256 * j;
+            if (c < nfull) *reinterpret_cast<uint2 *>(qword(q, row, 8 * (int64_t)c, k_pad)) = quant8(v[j], sc);
+        }
+        const int rem = len & 7;
+        if (rem && t == 0) {
+            const uint2 d = quant_tail8(srow, tail0, rem, sc);
+            qrow(2 * (int64_t)nfull) = d.x;
+            if (rem > 4) qrow(2 * (int64_t)nfull + 1) = d.y;
+        }
+        for (int64_t c = (((int64_t)len + 3) >> 2) + t; c < nq; c += 256) qrow(c) = 0u;
+        if (t == 0) scale[row] = cx;
+        return;
+    } else {
     const float *srow = src + row * sh;
     const int nfull = len >> 2;
     float4 v[16];
@@ -379,9 +504,11 @@ __device__ __forceinline__ void pack_row_block_body(int64_t row, const float *__
     }
     for (int64_t c = first_zero + t; c < nq; c += 256) qrow(c) = 0u;
     if (t == 0) scale[row] = cx;
+    }
 }
 
-__global__ __launch_bounds__(256) void pack_rows_block_kernel(const float *__restrict__ src, int64_t sh, int rows,
+template <typename SrcT = float>
+__global__ __launch_bounds__(256) void pack_rows_block_kernel(const SrcT *__restrict__ src, int64_t sh, int rows,
                                                               int len, float range, float *__restrict__ scale,
                                                               int8_t *__restrict__ q, int64_t rows_pad,
                                                               int64_t k_pad) {
@@ -392,8 +519,8 @@ __global__ __launch_bounds__(256) void pack_rows_block_kernel(const float *__res
 // R > 0 (rows of <= 4096 floats): 8 rows per 512-thread block, one wave per row, staged in LDS and written out
 // as whole 128-B lines of the fragment-major q (a line = 16-B pieces of 8 rows).  R == 0 (streaming rows): 4
 // rows per 256-thread block, stored directly.
-template <int R>
-__global__ __launch_bounds__(R > 0 ? 512 : 256) void pack_rows_vec_kernel(const float *__restrict__ src, int64_t sh,
+template <int R, typename SrcT = float>
+__global__ __launch_bounds__(R > 0 ? 512 : 256) void pack_rows_vec_kernel(const SrcT *__restrict__ src, int64_t sh,
                                                                           int rows, int len, float range,
                                                                           float *__restrict__ scale,
                                                                           int8_t *__restrict__ q, int64_t rows_pad,
@@ -415,8 +542,8 @@ __global__ __launch_bounds__(R > 0 ? 512 : 256) void pack_rows_vec_kernel(const 
 // block, each wave's dwords stored straight into the fragment-major q -- 4x the blocks, so 4x the CUs pull rows
 // (lab/rowpack_lab.hip, profiles/r06_rowpack_lab.log: 512 x 4 096 4.28 vs 5.38 us, 512 x 1 024 3.03-3.15 vs 3.23 us;
 // at 2 048 rows the staged lines are as fast or faster)
-template <int R>
-__global__ __launch_bounds__(128) void pack_rows_pair_kernel(const float *__restrict__ src, int64_t sh, int rows, int len,
+template <int R, typename SrcT = float>
+__global__ __launch_bounds__(128) void pack_rows_pair_kernel(const SrcT *__restrict__ src, int64_t sh, int rows, int len,
                                                              float range, float *__restrict__ scale,
                                                              int8_t *__restrict__ q, int64_t rows_pad, int64_t k_pad) {
     pack_rows_vec_body<R, false, false, false, 2>(xcd_contig(blockIdx.x, 0, gridDim.x), src, sh, rows, len, range, scale,
@@ -424,7 +551,8 @@ __global__ __launch_bounds__(128) void pack_rows_pair_kernel(const float *__rest
 }
 
 // pack_rows, generic strides (any sh, sw): scalar loads, two passes.
-__global__ __launch_bounds__(256) void pack_rows_generic_kernel(const float *__restrict__ src, int64_t sh,
+template <typename SrcT = float>
+__global__ __launch_bounds__(256) void pack_rows_generic_kernel(const SrcT *__restrict__ src, int64_t sh,
                                                                 int64_t sw, int rows, int len, float range,
                                                                 float *__restrict__ scale, int8_t *__restrict__ q,
                                                                 int64_t rows_pad, int64_t k_pad) {
@@ -437,14 +565,14 @@ __global__ __launch_bounds__(256) void pack_rows_generic_kernel(const float *__r
         if (lane == 0) scale[row] = 0.0f;
         return;
     }
-    const float *srow = src + row * sh;
-    const float seed = srow[0];
+    const SrcT *srow = src + row * sh;
+    const float seed = widen(srow[0]);
     float p = -INFINITY;
-    for (int64_t c = 1 + lane; c < len; c += kWave) p = cand_max(p, srow[c * sw]);
+    for (int64_t c = 1 + lane; c < len; c += kWave) p = cand_max(p, widen(srow[c * sw]));
     p = wave_max(p);
     const float cx = absmax_finish(seed, p);
     const float s = inv_divide(range, cx);
-    for (int64_t c = lane; c < k_pad; c += kWave) qrow(c) = (c < len) ? (int8_t)quant_i8(srow[c * sw], s) : 0;
+    for (int64_t c = lane; c < k_pad; c += kWave) qrow(c) = (c < len) ? (int8_t)quant_i8(widen(srow[c * sw]), s) : 0;
     if (lane == 0) scale[row] = cx;
 }
 
@@ -1210,6 +1338,10 @@ __global__ __launch_bounds__(256) void fill_uniform_kernel(float *__restrict__ d
 bool rows_vec_ok(const float *src, int64_t sh, int64_t sw, int rows) {
     return sw == 1 && (sh % 4 == 0 || rows == 1) && (reinterpret_cast<uintptr_t>(src) % 16 == 0);
 }
+// bf16 rows: every row must start on a 16-B boundary, i.e. a 16-B base and a row stride of a multiple of 8 elements
+bool rows_vec_ok(const bf16_t *src, int64_t sh, int64_t sw, int rows) {
+    return sw == 1 && (sh % 8 == 0 || rows == 1) && (reinterpret_cast<uintptr_t>(src) % 16 == 0);
+}
 
 bool cols_vec_ok(const float *src, int64_t sh, int cols) {
     return (cols % 4 == 0) && (sh % 4 == 0) && (reinterpret_cast<uintptr_t>(src) % 16 == 0);
@@ -1221,10 +1353,19 @@ int rows_regs(int len) {  // float4 chunks per lane -> register-resident variant
     return per_lane <= 1 ? 1 : per_lane <= 2 ? 2 : per_lane <= 4 ? 4 : per_lane <= 8 ? 8 : 16;
 }
 
-}  // namespace
+// 16-B chunks per lane of a bf16 row (8 elements each).  The one-wave-per-row kernels end at 4096 elements -- 8 chunks
+// per lane -- because their 8-row form stages the packed rows in LDS rows of kStageRowWordsMax words (k_pad <= 4096),
+// whatever the source type; the block-per-row kernel's 16 chunks x 256 threads then reach 32 768 elements.
+int rows_regs_bf16(int len) {
+    if (len > 4096) return len <= kLongRowMaxBf16 ? -1 : 0;
+    const int per_lane = ((len >> 3) + 63) / 64;
+    return per_lane <= 1 ? 1 : per_lane <= 2 ? 2 : per_lane <= 4 ? 4 : 8;
+}
 
-hipError_t launch_pack_rows(const float *src, int64_t sh, int64_t sw, int rows, int len, float range, PackedView out,
-                            hipStream_t stream) {
+template <typename SrcT>
+hipError_t launch_pack_rows_t(const SrcT *src, int64_t sh, int64_t sw, int rows, int len, float range, PackedView out,
+                              hipStream_t stream) {
+    constexpr bool kF32 = std::is_same<SrcT, float>::value;
     const dim3 grid((unsigned)(out.rows_pad / 4)), block(256);
     if (!rows_vec_ok(src, sh, sw, rows)) {
         pack_rows_generic_kernel<<<grid, block, 0, stream>>>(src, sh, sw, rows, len, range, out.scale, out.q,
@@ -1239,21 +1380,36 @@ hipError_t launch_pack_rows(const float *src, int64_t sh, int64_t sw, int rows, 
     else                                                                                                              \
         pack_rows_vec_kernel<Rv><<<(Rv) > 0 ? (unsigned)(out.rows_pad / 8) : grid.x, (Rv) > 0 ? 512 : 256, 0, stream>>>( \
             src, sh, rows, len, range, out.scale, out.q, out.rows_pad, out.k_pad)
-    if (rows_regs(len) < 0) {
+    const int regs = kF32 ? rows_regs(len) : rows_regs_bf16(len);
+    if (regs < 0) {
         pack_rows_block_kernel<<<(unsigned)out.rows_pad, 256, 0, stream>>>(src, sh, rows, len, range, out.scale, out.q,
                                                                            out.rows_pad, out.k_pad);
         return hipGetLastError();
     }
-    switch (rows_regs(len)) {
+    switch (regs) {
         case 1: QG_ROWS(1); break;
         case 2: QG_ROWS(2); break;
         case 4: QG_ROWS(4); break;
         case 8: QG_ROWS(8); break;
-        case 16: QG_ROWS(16); break;
+        case 16:
+            if constexpr (kF32) { QG_ROWS(16); }  // bf16 rows stop at 8 chunks per lane
+            break;
         default: QG_ROWS(0); break;
     }
 #undef QG_ROWS
     return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_pack_rows(const float *src, int64_t sh, int64_t sw, int rows, int len, float range, PackedView out,
+                            hipStream_t stream) {
+    return launch_pack_rows_t(src, sh, sw, rows, len, range, out, stream);
+}
+
+hipError_t launch_pack_rows(const bf16_t *src, int64_t sh, int64_t sw, int rows, int len, float range, PackedView out,
+                            hipStream_t stream) {
+    return launch_pack_rows_t(src, sh, sw, rows, len, range, out, stream);
 }
 
 hipError_t launch_pack_cols_pass2(const float *src, int64_t sh, int len, int cols, float range, PackedView out,

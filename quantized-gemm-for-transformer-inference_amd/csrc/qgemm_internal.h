@@ -113,8 +113,29 @@ __host__ __device__ inline uint64_t mix64(uint64_t z) {
     return z ^ (z >> 31);
 }
 
+// ---- bf16 activations (qgemm_*_dt, include/qgemm.h QGEMM_BF16) ------------------------------------
+// A bf16 element as stored: the upper half of the fp32 with the same value.  Widening is exact (the bits shifted
+// left by 16, subnormals included), so a bf16 X is packed as the fp32 chain packs the widened matrix.
+struct bf16_t {
+    uint16_t bits;
+};
+__host__ __device__ inline float widen(float x) { return x; }
+__device__ __forceinline__ float widen(bf16_t x) { return __uint_as_float((uint32_t)x.bits << 16); }
+
+// Two fp32 values -> one dword of two bf16 (`lo` in the low half), each rounded to nearest even: one
+// v_cvt_pk_bf16_f32.  Past the bf16 maximum it gives +-inf; subnormals stay subnormal (the kernels run with
+// denormals on), -0 stays -0 and NaN stays NaN (tests/test_gpu_bf16.py checks each on the device).
+__device__ __forceinline__ uint32_t pk_bf16(float lo, float hi) {
+    uint32_t r;
+    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
+    return r;
+}
+
 // ---- launchers (defined in the .hip files) ------------------------------------------------------
 hipError_t launch_pack_rows(const float *src, int64_t sh, int64_t sw, int rows, int len, float range,
+                            PackedView out, hipStream_t stream);
+// the same from a bf16 source (strides in bf16 elements): its own alignment rule and length limits (pack.hip)
+hipError_t launch_pack_rows(const bf16_t *src, int64_t sh, int64_t sw, int rows, int len, float range,
                             PackedView out, hipStream_t stream);
 hipError_t launch_pack_cols(const float *src, int64_t sh, int len, int cols, float range, PackedView out,
                             hipStream_t stream);
@@ -164,9 +185,11 @@ size_t gemm_scratch_bytes(int m, int n, int k);
 // reducers re-zero their tickets instead of a memset ahead of every launch.
 // bytes at the start of the split-K scratch that must be zero before a split launch (0: no split)
 size_t gemm_ticket_bytes(int m, int n, int k);
-hipError_t launch_gemm_dequant(const PackedView &a, const PackedView &b, float *C, int64_t csh, int64_t csw,
+// c_bf16: C holds bf16 (csh / csw in bf16 elements): the fp32 value the epilogue would store, rounded once (pk_bf16)
+hipError_t launch_gemm_dequant(const PackedView &a, const PackedView &b, void *C, int64_t csh, int64_t csw,
                                int m, int n, float inv_r2, void *scratch, size_t scratch_bytes, hipStream_t stream,
-                               const float *bias = nullptr, bool relu = false, bool tickets_zeroed = false);
+                               const float *bias = nullptr, bool relu = false, bool tickets_zeroed = false,
+                               bool c_bf16 = false);
 // The LLM.int8() decomposition's GEMM: int8 part + the outlier columns' fp32 products in the epilogue, read from
 // X (m x k, row stride xsh) and W (k x n, row stride wsh) at the columns / rows ocols[0 .. *ocount) (ascending).
 // Only where the plan is the 256-tile GEMM without split-K (gemm_outlier_ok); hipErrorNotSupported otherwise.
