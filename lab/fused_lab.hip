@@ -4,7 +4,7 @@
 //
 // One launch, 512-thread blocks at one per CU (the GEMM role's 232 VGPRs), roles by blockIdx in
 // dispatch order:
-//   W strips (8 columns x all K rows, pack_w_strip8_body) -> X groups (8 rows, pack_rows_vec_body) ->
+//   W strips (8 columns x all K rows, pack_w_strip_body<8>) -> X groups (8 rows, pack_rows_vec_body) ->
 //   GEMM tiles (pp_tile_body<2>, the product's 256 x 256 ping-pong tile)
 // Orders: 0 = [all W][all X][all tiles] (the serial call without its kernel boundary);
 //         1 = [all W] then per X panel p: [its 32 X groups][its 16 tiles] (a tile is dispatched as soon as
@@ -73,7 +73,7 @@ __global__ __launch_bounds__(512, 2) void fused_kernel(Fused f) {
         // the product's XCD-contiguous strip map: blocks b, b+8, ... share an XCD
         const int xcd = idx & 7, q8 = nstrips >> 3, r8 = nstrips & 7;
         const int strip = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (idx >> 3);
-        pack_w_strip8_body<false, true>(strip, f.w, f.n, f.k, 127.f, f.vw.scale, f.vw.q, f.vw.k_pad,
+        pack_w_strip_body<kWs8Cols, false, true>(strip, f.w, f.n, f.k, 127.f, f.vw.scale, f.vw.q, f.vw.k_pad,
                                         reinterpret_cast<float *>(lds));
         signal(f.sync);
         return;

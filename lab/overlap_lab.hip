@@ -67,7 +67,7 @@ __global__ __launch_bounds__(512, 2) void probe_kernel(GemmArgs g, int ngemm, Pa
     if (i < pk.nstrips) {
         const int xcd = i & 7, q8 = pk.nstrips >> 3, r8 = pk.nstrips & 7;
         const int strip = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (i >> 3);
-        pack_w_strip8_body(strip, pk.w, pk.wsh, pk.k, 127.f, pk.vw.scale, pk.vw.q, pk.vw.k_pad,
+        pack_w_strip_body<kWs8Cols>(strip, pk.w, pk.wsh, pk.k, 127.f, pk.vw.scale, pk.vw.q, pk.vw.k_pad,
                            reinterpret_cast<float *>(lds));
     } else {
         pack_rows_vec_body<16>((int64_t)(i - pk.nstrips) * 2, pk.x, pk.xsh, pk.m, pk.k, 127.f, pk.vx.scale, pk.vx.q,

@@ -44,6 +44,14 @@ hipError_t pack_vectors(const bf16_t *src, int64_t row_stride, int64_t elem_stri
 
 bool dtype_ok(int t) { return t == QGEMM_F32 || t == QGEMM_BF16; }
 
+// the same for a matrix given by pointer and dtype tag (dtype_ok)
+hipError_t pack_vectors(const void *src, int dtype, int64_t row_stride, int64_t elem_stride, int rows, int len,
+                        float range, PackedView out, hipStream_t stream) {
+    return dtype == QGEMM_BF16
+               ? pack_vectors(static_cast<const bf16_t *>(src), row_stride, elem_stride, rows, len, range, out, stream)
+               : pack_vectors(static_cast<const float *>(src), row_stride, elem_stride, rows, len, range, out, stream);
+}
+
 // Grow-only cached buffers for the entry points without an explicit workspace, one per (device, stream, use): a
 // buffer is only reused in its stream's order, so calls on different streams never share packed operands or split-K
 // tickets (the reference allocates its temporaries per call, op_mm.cuh:76-93).  hipStreamPerThread names a different
@@ -129,6 +137,19 @@ hipError_t cached_workspace(size_t need, hipStream_t stream, void **out) {
 
 size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
+// One chain's workspace: [split-K scratch (0 unless the shape has too few tiles)][packed A][packed B], each part
+// 256-B aligned.  The prepacked-weight chain (qgemm_linear) ends after packed A.
+struct ChainWorkspace {
+    size_t scratch_bytes;  // the split-K scratch, at offset 0 (its tickets first)
+    size_t a, b;           // offsets of packed A and packed B
+    size_t end;            // bytes with packed B; `b` bytes without
+    ChainWorkspace(int m, int n, int k)
+        : scratch_bytes(gemm_scratch_bytes(m, n, k)),
+          a(align256(scratch_bytes)),
+          b(a + align256(packed_bytes(m, k))),
+          end(b + align256(packed_bytes(n, k))) {}
+};
+
 // Split-K scratch of qgemm_mm_packed and the error-statistics scratch (no workspace argument): zeroed at allocation.
 hipError_t cached_scratch(size_t need, hipStream_t stream, int use, void **out) {
     return cached_buffer(need, stream, use, true, 0, out);
@@ -153,17 +174,12 @@ size_t qgemm_packed_size(int rows, int k) {
 
 size_t op_mm_quantize_workspace_size(int m, int n, int k) {
     if (!dims_ok(m, n, k)) return 0;
-    // [split-K scratch (0 unless the shape has too few tiles)][packed A][packed B]
-    return align256(gemm_scratch_bytes(m, n, k)) + align256(packed_bytes(m, k)) + align256(packed_bytes(n, k));
+    return ChainWorkspace(m, n, k).end;
 }
 
 int qgemm_pack_a(const float *A, int64_t a_stride_h, int64_t a_stride_w, int m, int k, float range, void *packed_a,
                  void *stream) {
-    if (!A || !packed_a || m < 0 || k < 1) return err(hipErrorInvalidValue);
-    if (m == 0) return 0;
-    // reduction vectors = rows of A: (row stride, element stride) = (stride_h, stride_w)
-    return err(pack_vectors(A, a_stride_h, a_stride_w, m, k, range, packed_view(packed_a, m, k),
-                            static_cast<hipStream_t>(stream)));
+    return qgemm_pack_a_dt(A, QGEMM_F32, a_stride_h, a_stride_w, m, k, range, packed_a, stream);
 }
 
 int qgemm_pack_b(const float *B, int64_t b_stride_h, int64_t b_stride_w, int k, int n, float range, void *packed_b,
@@ -177,17 +193,7 @@ int qgemm_pack_b(const float *B, int64_t b_stride_h, int64_t b_stride_w, int k, 
 
 int qgemm_mm_packed(const void *packed_a, const void *packed_b, float *C, int64_t c_stride_h, int64_t c_stride_w,
                     int m, int n, int k, float range, void *stream) {
-    if (!packed_a || !packed_b || !C || !dims_ok(m, n, k)) return err(hipErrorInvalidValue);
-    if (m == 0 || n == 0) return 0;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    void *scratch = nullptr;
-    const size_t sb = gemm_scratch_bytes(m, n, k);
-    if (sb) {
-        hipError_t e = cached_scratch(sb, s, kUseSplitK, &scratch);
-        if (e != hipSuccess) return err(e);
-    }
-    return err(mm_packed_impl(packed_a, packed_b, C, c_stride_h, c_stride_w, m, n, k, range, scratch, sb, s,
-                              /*tickets_zeroed=*/true));
+    return qgemm_mm_packed_dt(packed_a, packed_b, C, QGEMM_F32, c_stride_h, c_stride_w, m, n, k, range, stream);
 }
 
 int qgemm_mm_packed_i32(const void *packed_a, const void *packed_b, int32_t *Acc, int m, int n, int k, void *stream) {
@@ -203,15 +209,14 @@ int op_mm_quantize_ws(const float *A, int64_t a_stride_h, int64_t a_stride_w, co
     // op_mm.cuh:71-72: shape agreement and device residency are asserted by the reference
     if (!A || !B || !C || !dims_ok(m, n, k)) return err(hipErrorInvalidValue);
     if (m == 0 || n == 0) return 0;
-    const size_t need = op_mm_quantize_workspace_size(m, n, k);
-    if (!workspace || ws_bytes < need) return err(hipErrorInvalidValue);
+    const ChainWorkspace ws(m, n, k);
+    if (!workspace || ws_bytes < ws.end) return err(hipErrorInvalidValue);
     char *scratch = static_cast<char *>(workspace);
-    const size_t sb = gemm_scratch_bytes(m, n, k);
-    char *pa = scratch + align256(sb);
-    char *pb = pa + align256(packed_bytes(m, k));
+    char *pa = scratch + ws.a, *pb = scratch + ws.b;
     hipStream_t s = static_cast<hipStream_t>(stream);
     auto gemm = [&](bool tickets_zeroed) {
-        return err(mm_packed_impl(pa, pb, C, c_stride_h, c_stride_w, m, n, k, range, scratch, sb, s, tickets_zeroed));
+        return err(mm_packed_impl(pa, pb, C, c_stride_h, c_stride_w, m, n, k, range, scratch, ws.scratch_bytes, s,
+                                  tickets_zeroed));
     };
     // the pack launch zeroes the split-K tickets at the start of the workspace (the GEMM then needs no
     // zeroing launch of its own)
@@ -274,20 +279,8 @@ int qgemm_error_stats(const float *C, const float *O, int64_t count, int referen
 
 int qgemm_linear(const float *X, int64_t x_stride_h, int m, int k, const void *packed_w, int n, const float *bias,
                  int relu, float *Y, int64_t y_stride_h, void *workspace, size_t ws_bytes, void *stream) {
-    if (!X || !packed_w || !Y || m < 0 || n < 0 || k < 1 || (relu && !bias)) return err(hipErrorInvalidValue);
-    if (m == 0 || n == 0) return 0;
-    const size_t need = qgemm_linear_workspace_size(m, n, k);
-    if (!workspace || ws_bytes < need) return err(hipErrorInvalidValue);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    char *scratch = static_cast<char *>(workspace);
-    const size_t sb = gemm_scratch_bytes(m, n, k);
-    char *pa = scratch + align256(sb);
-    const PackedView va = packed_view(pa, m, k);
-    hipError_t e = pack_vectors(X, x_stride_h, 1, m, k, kDefaultRange, va, s);
-    if (e != hipSuccess) return err(e);
-    const float inv_r2 = 1.0f / (kDefaultRange * kDefaultRange);
-    return err(launch_gemm_dequant(va, packed_view(packed_w, n, k), Y, y_stride_h, 1, m, n, inv_r2, scratch, sb, s, bias,
-                                   relu != 0));
+    return qgemm_linear_dt(X, QGEMM_F32, x_stride_h, m, k, packed_w, n, bias, relu, Y, QGEMM_F32, y_stride_h, workspace,
+                           ws_bytes, stream);
 }
 
 // ---- bf16 activations and outputs: the same chain, only its two ends change (include/qgemm.h) ----
@@ -295,19 +288,16 @@ int qgemm_linear(const float *X, int64_t x_stride_h, int m, int k, const void *p
 int qgemm_pack_a_dt(const void *A, int a_dtype, int64_t a_stride_h, int64_t a_stride_w, int m, int k, float range,
                     void *packed_a, void *stream) {
     if (!dtype_ok(a_dtype)) return err(hipErrorInvalidValue);
-    if (a_dtype == QGEMM_F32)
-        return qgemm_pack_a(static_cast<const float *>(A), a_stride_h, a_stride_w, m, k, range, packed_a, stream);
     if (!A || !packed_a || m < 0 || k < 1) return err(hipErrorInvalidValue);
     if (m == 0) return 0;
-    return err(pack_vectors(static_cast<const bf16_t *>(A), a_stride_h, a_stride_w, m, k, range,
-                            packed_view(packed_a, m, k), static_cast<hipStream_t>(stream)));
+    // reduction vectors = rows of A: (row stride, element stride) = (stride_h, stride_w)
+    return err(pack_vectors(A, a_dtype, a_stride_h, a_stride_w, m, k, range, packed_view(packed_a, m, k),
+                            static_cast<hipStream_t>(stream)));
 }
 
 int qgemm_mm_packed_dt(const void *packed_a, const void *packed_b, void *C, int c_dtype, int64_t c_stride_h,
                        int64_t c_stride_w, int m, int n, int k, float range, void *stream) {
     if (!dtype_ok(c_dtype)) return err(hipErrorInvalidValue);
-    if (c_dtype == QGEMM_F32)
-        return qgemm_mm_packed(packed_a, packed_b, static_cast<float *>(C), c_stride_h, c_stride_w, m, n, k, range, stream);
     if (!packed_a || !packed_b || !C || !dims_ok(m, n, k)) return err(hipErrorInvalidValue);
     if (m == 0 || n == 0) return 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -318,37 +308,30 @@ int qgemm_mm_packed_dt(const void *packed_a, const void *packed_b, void *C, int 
         if (e != hipSuccess) return err(e);
     }
     return err(mm_packed_impl(packed_a, packed_b, C, c_stride_h, c_stride_w, m, n, k, range, scratch, sb, s,
-                              /*tickets_zeroed=*/true, /*c_bf16=*/true));
+                              /*tickets_zeroed=*/true, /*c_bf16=*/c_dtype == QGEMM_BF16));
 }
 
 int qgemm_linear_dt(const void *X, int x_dtype, int64_t x_stride_h, int m, int k, const void *packed_w, int n,
                     const float *bias, int relu, void *Y, int y_dtype, int64_t y_stride_h, void *workspace,
                     size_t ws_bytes, void *stream) {
     if (!dtype_ok(x_dtype) || !dtype_ok(y_dtype)) return err(hipErrorInvalidValue);
-    if (x_dtype == QGEMM_F32 && y_dtype == QGEMM_F32)
-        return qgemm_linear(static_cast<const float *>(X), x_stride_h, m, k, packed_w, n, bias, relu,
-                            static_cast<float *>(Y), y_stride_h, workspace, ws_bytes, stream);
     if (!X || !packed_w || !Y || m < 0 || n < 0 || k < 1 || (relu && !bias)) return err(hipErrorInvalidValue);
     if (m == 0 || n == 0) return 0;
-    const size_t need = qgemm_linear_workspace_size(m, n, k);
-    if (!workspace || ws_bytes < need) return err(hipErrorInvalidValue);
+    const ChainWorkspace ws(m, n, k);
+    if (!workspace || ws_bytes < ws.b) return err(hipErrorInvalidValue);
     hipStream_t s = static_cast<hipStream_t>(stream);
     char *scratch = static_cast<char *>(workspace);
-    const size_t sb = gemm_scratch_bytes(m, n, k);
-    char *pa = scratch + align256(sb);
-    const PackedView va = packed_view(pa, m, k);
-    const hipError_t e = x_dtype == QGEMM_BF16
-                             ? pack_vectors(static_cast<const bf16_t *>(X), x_stride_h, 1, m, k, kDefaultRange, va, s)
-                             : pack_vectors(static_cast<const float *>(X), x_stride_h, 1, m, k, kDefaultRange, va, s);
+    const PackedView va = packed_view(scratch + ws.a, m, k);
+    const hipError_t e = pack_vectors(X, x_dtype, x_stride_h, 1, m, k, kDefaultRange, va, s);
     if (e != hipSuccess) return err(e);
     const float inv_r2 = 1.0f / (kDefaultRange * kDefaultRange);
-    return err(launch_gemm_dequant(va, packed_view(packed_w, n, k), Y, y_stride_h, 1, m, n, inv_r2, scratch, sb, s, bias,
-                                   relu != 0, false, y_dtype == QGEMM_BF16));
+    return err(launch_gemm_dequant(va, packed_view(packed_w, n, k), Y, y_stride_h, 1, m, n, inv_r2, scratch,
+                                   ws.scratch_bytes, s, bias, relu != 0, false, y_dtype == QGEMM_BF16));
 }
 
 size_t qgemm_linear_workspace_size(int m, int n, int k) {
     if (m < 0 || n < 0 || k < 1) return 0;
-    return align256(gemm_scratch_bytes(m, n, k)) + align256(packed_bytes(m, k));
+    return ChainWorkspace(m, n, k).b;
 }
 
 size_t op_mm_quantize_prepacked_workspace_size(int m, int n, int k) { return qgemm_linear_workspace_size(m, n, k); }
@@ -412,20 +395,18 @@ int qgemm_mm_outlier(const float *A, const float *B, float *C, int m, int n, int
     hipStream_t s = static_cast<hipStream_t>(stream);
     char *scratch = static_cast<char *>(workspace);
     char *ws2 = scratch + align256(outlier_scratch_bytes(m, n, k));
+    const ChainWorkspace ws(m, n, k);
     {
         // fast path: the packed operands in the plain chain's slots of ws2 (no split-K: no tickets)
-        char *pa = ws2 + align256(gemm_scratch_bytes(m, n, k));
-        char *pb = pa + align256(packed_bytes(m, k));
-        const hipError_t e = outlier_fast(A, B, C, m, n, k, threshold, scratch, packed_view(pa, m, k),
-                                          packed_view(pb, n, k), kDefaultRange, s);
+        const hipError_t e = outlier_fast(A, B, C, m, n, k, threshold, scratch, packed_view(ws2 + ws.a, m, k),
+                                          packed_view(ws2 + ws.b, n, k), kDefaultRange, s);
         if (e != hipErrorNotSupported) return err(e);
     }
     float *Xm = nullptr, *Wm = nullptr;
     hipError_t e = outlier_prepare(A, k, B, n, m, n, k, threshold, scratch, &Xm, &Wm, s);
     if (e != hipSuccess) return err(e);
     // the int8 part on the outlier-free operands (their scales no longer see the outliers)
-    const int rc = op_mm_quantize_ws(Xm, k, 1, Wm, n, 1, C, n, 1, m, n, k, kDefaultRange, ws2,
-                                     op_mm_quantize_workspace_size(m, n, k), stream);
+    const int rc = op_mm_quantize_ws(Xm, k, 1, Wm, n, 1, C, n, 1, m, n, k, kDefaultRange, ws2, ws.end, stream);
     if (rc) return rc;
     return err(outlier_finish(A, k, B, n, m, n, k, scratch, C, n, s));
 }

@@ -51,35 +51,99 @@ __device__ __forceinline__ uint32_t pack4(int a, int b, int c, int d) {
     return __builtin_amdgcn_perm(hi, lo, 0x05040100u);
 }
 
-// ---- bf16 source rows (launch_pack_rows(const bf16_t *)) ----
-// A 16-B load carries 8 bf16: the chunk's dword e holds elements 2e (low half) and 2e + 1 (high half).  Chunk c of a row
-// is k = 8c .. 8c + 7, i.e. dwords 2c and 2c + 1 of the packed row: 8 B that stay contiguous in the fragment-major
-// q (8c % 16 is 0 or 8, inside one 16-byte k group).
+typedef int v4i_t __attribute__((ext_vector_type(4)));
 typedef uint32_t v4u_t __attribute__((ext_vector_type(4)));
+
+// 16-B load; kNt: non-temporal (the line is not kept in the Infinity Cache for a later reader)
+template <bool kNt>
+__device__ __forceinline__ float4 ld_f4(const float *p) {
+    if constexpr (kNt) {
+        typedef float v4f_nt __attribute__((ext_vector_type(4)));
+        const v4f_nt v = __builtin_nontemporal_load(reinterpret_cast<const v4f_nt *>(p));
+        return make_float4(v[0], v[1], v[2], v[3]);
+    } else {
+        return *reinterpret_cast<const float4 *>(p);
+    }
+}
+
+// ---- RowSrc<SrcT>: what the row packs need to know about the source element type ----
+// A row is read in 16-B chunks of kElems elements; chunk c is k = kElems c .., i.e. kWords dwords of the packed row
+// from dword kWords c on.  The row bodies below are written once over these members:
+//   chunk_t        the chunk as the registers keep it
+//   from_bits / load<kNt>   a chunk from a 16-B buffer load / from memory
+//   elem0          element 0 of a chunk (the absmax seed, for chunk 0)
+//   cand           running max of the chunk's |x| candidates; `first`: the chunk starts the row, whose element 0 is
+//                  the seed and no candidate
+//   quant          the chunk's kWords packed dwords
+//   quant_tail     the rem (1 .. kElems - 1) tail elements from element tail0 on: dword w is live when 4 w < rem
+//   kBlockRowMax   the longest row of the block-per-row kernel (16 chunks x 256 threads)
+template <typename SrcT>
+struct RowSrc;
+
+template <>
+struct RowSrc<float> {
+    typedef float4 chunk_t;
+    static constexpr int kShift = 2, kElems = 1 << kShift, kWords = kElems / 4, kBlockRowMax = 16 * 256 * kElems;
+    static __device__ __forceinline__ chunk_t from_bits(v4i_t x) {
+        return make_float4(__int_as_float(x[0]), __int_as_float(x[1]), __int_as_float(x[2]), __int_as_float(x[3]));
+    }
+    template <bool kNt>
+    static __device__ __forceinline__ chunk_t load(const float *p) { return ld_f4<kNt>(p); }
+    static __device__ __forceinline__ float elem0(chunk_t x) { return x.x; }
+    static __device__ __forceinline__ float cand(float p, chunk_t x, bool first) {
+        p = first ? p : cand_max(p, x.x);
+        p = cand_max(p, x.y);
+        p = cand_max(p, x.z);
+        p = cand_max(p, x.w);
+        return p;
+    }
+    static __device__ __forceinline__ void quant(chunk_t x, float s, uint32_t (&d)[1]) {
+        d[0] = pack4(quant_i8(x.x, s), quant_i8(x.y, s), quant_i8(x.z, s), quant_i8(x.w, s));
+    }
+    static __device__ __forceinline__ void quant_tail(const float *srow, int tail0, int rem, float s, uint32_t (&d)[1]) {
+        int b[4] = {0, 0, 0, 0};
+        for (int e = 0; e < rem; ++e) b[e] = quant_i8(srow[tail0 + e], s);
+        d[0] = pack4(b[0], b[1], b[2], b[3]);
+    }
+};
+
+// bf16 rows (launch_pack_rows(const bf16_t *)): a 16-B load carries 8 bf16, kept as loaded and widened where they are
+// used; the chunk's dword e holds elements 2e (low half) and 2e + 1 (high half).  Its two packed dwords are 8 B that stay
+// contiguous in the fragment-major q (8c % 16 is 0 or 8, inside one 16-byte k group).
 __device__ __forceinline__ float bf_lo(uint32_t u) { return __uint_as_float(u << 16); }
 __device__ __forceinline__ float bf_hi(uint32_t u) { return __uint_as_float(u & 0xffff0000u); }
-// |x| candidates of one chunk; `first`: the chunk starts the row, whose element 0 is the seed
-__device__ __forceinline__ float cand_max8(float p, v4u_t x, bool first) {
-    p = first ? p : cand_max(p, bf_lo(x[0]));
-    p = cand_max(p, bf_hi(x[0]));
-#pragma unroll
-    for (int e = 1; e < 4; ++e) {
-        p = cand_max(p, bf_lo(x[e]));
-        p = cand_max(p, bf_hi(x[e]));
+template <>
+struct RowSrc<bf16_t> {
+    typedef v4u_t chunk_t;
+    static constexpr int kShift = 3, kElems = 1 << kShift, kWords = kElems / 4, kBlockRowMax = 16 * 256 * kElems;
+    static __device__ __forceinline__ chunk_t from_bits(v4i_t x) { return __builtin_bit_cast(v4u_t, x); }
+    template <bool kNt>
+    static __device__ __forceinline__ chunk_t load(const bf16_t *p) {
+        static_assert(!kNt, "bf16 rows are read with plain loads");
+        return *reinterpret_cast<const v4u_t *>(p);
     }
-    return p;
-}
-// the chunk's two packed dwords
-__device__ __forceinline__ uint2 quant8(v4u_t x, float s) {
-    return make_uint2(pack4(quant_i8(bf_lo(x[0]), s), quant_i8(bf_hi(x[0]), s), quant_i8(bf_lo(x[1]), s), quant_i8(bf_hi(x[1]), s)),
-                      pack4(quant_i8(bf_lo(x[2]), s), quant_i8(bf_hi(x[2]), s), quant_i8(bf_lo(x[3]), s), quant_i8(bf_hi(x[3]), s)));
-}
-// the (len & 7) tail elements of a bf16 row from element tail0 on: up to two dwords
-__device__ __forceinline__ uint2 quant_tail8(const bf16_t *srow, int tail0, int rem, float s) {
-    int b[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (int e = 0; e < rem; ++e) b[e] = quant_i8(widen(srow[tail0 + e]), s);
-    return make_uint2(pack4(b[0], b[1], b[2], b[3]), pack4(b[4], b[5], b[6], b[7]));
-}
+    static __device__ __forceinline__ float elem0(chunk_t x) { return bf_lo(x[0]); }
+    static __device__ __forceinline__ float cand(float p, chunk_t x, bool first) {
+        p = first ? p : cand_max(p, bf_lo(x[0]));
+        p = cand_max(p, bf_hi(x[0]));
+#pragma unroll
+        for (int e = 1; e < 4; ++e) {
+            p = cand_max(p, bf_lo(x[e]));
+            p = cand_max(p, bf_hi(x[e]));
+        }
+        return p;
+    }
+    static __device__ __forceinline__ void quant(chunk_t x, float s, uint32_t (&d)[2]) {
+        d[0] = pack4(quant_i8(bf_lo(x[0]), s), quant_i8(bf_hi(x[0]), s), quant_i8(bf_lo(x[1]), s), quant_i8(bf_hi(x[1]), s));
+        d[1] = pack4(quant_i8(bf_lo(x[2]), s), quant_i8(bf_hi(x[2]), s), quant_i8(bf_lo(x[3]), s), quant_i8(bf_hi(x[3]), s));
+    }
+    static __device__ __forceinline__ void quant_tail(const bf16_t *srow, int tail0, int rem, float s, uint32_t (&d)[2]) {
+        int b[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        for (int e = 0; e < rem; ++e) b[e] = quant_i8(widen(srow[tail0 + e]), s);
+        d[0] = pack4(b[0], b[1], b[2], b[3]);
+        d[1] = pack4(b[4], b[5], b[6], b[7]);
+    }
+};
 
 // W strips hold 4 consecutive k of one column per dword; a 16-B piece of the fragment-major q (one packed row,
 // 16 consecutive k) is the dwords d[col] of the 4 threads b = 0..3 of a quad (lanes qbase + stride * b) that
@@ -111,22 +175,18 @@ __device__ __forceinline__ void st_u32(uint32_t *p, uint32_t v) {
     if constexpr (kWT) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     else *p = v;
 }
+// the packed dwords of one 16-B source chunk (RowSrc::kWords of them): one store; two dwords are 8-B aligned
+template <bool kWT>
+__device__ __forceinline__ void st_words(uint32_t *p, const uint32_t (&d)[1]) { st_u32<kWT>(p, d[0]); }
+template <bool kWT>
+__device__ __forceinline__ void st_words(uint32_t *p, const uint32_t (&d)[2]) {
+    static_assert(!kWT, "8-B stores are plain");
+    *reinterpret_cast<uint2 *>(p) = make_uint2(d[0], d[1]);
+}
 template <bool kWT>
 __device__ __forceinline__ void st_f32(float *p, float v) {
     if constexpr (kWT) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     else *p = v;
-}
-
-// 16-B load; kNt: non-temporal (the line is not kept in the Infinity Cache for a later reader)
-template <bool kNt>
-__device__ __forceinline__ float4 ld_f4(const float *p) {
-    if constexpr (kNt) {
-        typedef float v4f_nt __attribute__((ext_vector_type(4)));
-        const v4f_nt v = __builtin_nontemporal_load(reinterpret_cast<const v4f_nt *>(p));
-        return make_float4(v[0], v[1], v[2], v[3]);
-    } else {
-        return *reinterpret_cast<const float4 *>(p);
-    }
 }
 
 // Blocks b and b + 8 run on one XCD.  For a role occupying blocks [base, base + count): a role-local index
@@ -143,6 +203,12 @@ __device__ __forceinline__ int xcd_contig(int bid, int base, int count) {
         if (y < x && o < count) start += (count - 1 - o) / 8 + 1;
     }
     return start + (bid - base - ((x - base) & 7)) / 8;
+}
+// The same map for the W-strip role, which starts at block 0 (bijective for any nstrips): blocks b, b + 8, ... get
+// adjacent strips, so each 128-B line of W (two 64-B, four 32-B strip segments) is fetched into that XCD's L2 once
+__device__ __forceinline__ int xcd_contig_strip(int bid, int nstrips) {
+    const int xcd = bid & 7, q8 = nstrips >> 3, r8 = nstrips & 7;
+    return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
 }
 
 // The GEMM's split-K tickets live in the caller's workspace, whose contents are arbitrary: the pack
@@ -210,14 +276,14 @@ __device__ __forceinline__ void outlier_column_list(const OutlierMask &om, int *
 }
 
 // ------------------------------------------------------------------------------------------------
-// pack_rows, vector path: rows of `len` floats at src + r*sh, unit inner stride, 16-B aligned rows.
-// R > 0: each lane keeps R float4 chunks in registers (len <= 256*R), one HBM read.
+// pack_rows, vector path: rows of `len` elements at src + r*sh, unit inner stride, 16-B aligned rows, read in the
+// 16-B chunks of RowSrc<SrcT> (4 floats or 8 bf16).
+// R > 0: each lane keeps R chunks in registers (len <= 64 R kElems), one HBM read.
 // R == 0: two streaming passes (second pass mostly L2 hits).  `blk` = kGroup-row group index.
 // kStage: the packed row goes to `stage` (the wave's LDS row, dword c at stage[c]) instead of q; the caller
 // writes the block's staged rows out as whole 128-B lines of the fragment-major q (write_staged_rows).
 // kGroup: rows per `blk` (wave w of the block takes row blk * kGroup + w).
-// SrcT = bf16_t: rows of bf16, 8 per 16-B chunk (R chunks per lane: len <= 512 * R), kept as loaded and widened
-// where they are used; everything else as for float.
+// kMask (the outlier mask) and kWT (write-through stores) are for float rows only.
 template <int R, bool kMask = false, bool kWT = false, bool kStage = false, int kGroup = 4, typename SrcT = float>
 __device__ __forceinline__ void pack_rows_vec_body(int64_t blk, const SrcT *__restrict__ src, int64_t sh, int rows,
                                                    int len, float range, float *__restrict__ scale,
@@ -238,157 +304,101 @@ __device__ __forceinline__ void pack_rows_vec_body(int64_t blk, const SrcT *__re
         if (lane == 0) st_f32<kWT>(scale + row, 0.0f);
         return;
     }
-    if constexpr (!std::is_same<SrcT, float>::value) {
-        static_assert(!kMask && !kWT, "bf16 rows: the plain row packs only");
-        const bf16_t *srow = src + row * sh;
-        const int nfull = len >> 3;  // complete 8-element chunks
-        const float seed = widen(srow[0]);
-        // dwords 2c, 2c + 1 of the packed row: one 8-B store (the stage rows and the q pieces are 8-B aligned)
-        auto put2 = [&](int64_t c, uint2 d) __attribute__((always_inline)) {
-            if constexpr (kStage) *reinterpret_cast<uint2 *>(stage + 2 * c) = d;
-            else *reinterpret_cast<uint2 *>(qword(q, row, 8 * c, k_pad)) = d;
-        };
-        float p = -INFINITY;
-        v4u_t v[R > 0 ? R : 1];
-        if constexpr (R > 0) {
-            const auto rs = buf_rsrc(srow, (uint32_t)nfull * 16);  // chunks >= nfull read as zeros
-#pragma unroll
-            for (int j = 0; j < R; ++j)
-                v[j] = __builtin_bit_cast(v4u_t, __builtin_amdgcn_raw_buffer_load_b128(rs, (uint32_t)(lane + j * kWave) * 16, 0, 0));
-#pragma unroll
-            for (int j = 0; j < R; ++j) {
-                const int c = lane + j * kWave;
-                if (c < nfull) p = cand_max8(p, v[j], c == 0);
-            }
-        } else {
-            for (int c = lane; c < nfull; c += kWave) p = cand_max8(p, *reinterpret_cast<const v4u_t *>(srow + 8 * (int64_t)c), c == 0);
-        }
-        const int tail0 = nfull << 3;  // scalar tail elements [tail0, len): at most 7
-        if (tail0 + lane < len && tail0 + lane > 0) p = cand_max(p, widen(srow[tail0 + lane]));
-        p = wave_max(p);
-        const float cx = absmax_finish(seed, p);
-        const float s = inv_divide(range, cx);
-        if constexpr (R > 0) {
-#pragma unroll
-            for (int j = 0; j < R; ++j) {
-                const int c = lane + j * kWave;
-                if (c < nfull) put2(c, quant8(v[j], s));
-            }
-        } else {
-            for (int c = lane; c < nfull; c += kWave) put2(c, quant8(*reinterpret_cast<const v4u_t *>(srow + 8 * (int64_t)c), s));
-        }
-        // partial tail dwords, then zero padding words
-        const int rem = len & 7;
-        if (rem && lane == 0) {
-            const uint2 d = quant_tail8(srow, tail0, rem, s);
-            put(2 * (int64_t)nfull, d.x);
-            if (rem > 4) put(2 * (int64_t)nfull + 1, d.y);
-        }
-        for (int64_t c = (((int64_t)len + 3) >> 2) + lane; c < nq; c += kWave) put(c, 0u);
-        if (lane == 0) st_f32<kWT>(scale + row, cx);
-        return;
-    } else {
-    const float *srow = src + row * sh;
-    const float4 *s4 = reinterpret_cast<const float4 *>(srow);
-    const int nfull = len >> 2;  // complete float4 chunks
-    float seed = srow[0];
+    typedef RowSrc<SrcT> T;
+    typedef typename T::chunk_t chunk_t;
+    static_assert(std::is_same<SrcT, float>::value || (!kMask && !kWT), "bf16 rows: the plain row packs only");
+    // the dwords kWords c .. of the packed row (chunk c) in one store
+    auto put_chunk = [&](int64_t c, const uint32_t (&d)[T::kWords]) __attribute__((always_inline)) {
+        if constexpr (kStage) st_words<false>(stage + T::kWords * c, d);
+        else st_words<kWT>(qword(q, row, T::kElems * c, k_pad), d);
+    };
+    const SrcT *srow = src + row * sh;
+    const int nfull = len >> T::kShift;  // complete 16-B chunks
+    float seed = widen(srow[0]);
 
     float p = -INFINITY;
-    float4 v[R > 0 ? R : 1];
+    chunk_t v[R > 0 ? R : 1];
     if constexpr (R > 0) {
         // buffer loads on one per-lane offset; chunks >= nfull lie past the descriptor and read as zeros
-        typedef int v4i_t __attribute__((ext_vector_type(4)));
         const auto rs = buf_rsrc(srow, (uint32_t)nfull * 16);
 #pragma unroll
-        for (int j = 0; j < R; ++j) {
-            const v4i_t x = __builtin_amdgcn_raw_buffer_load_b128(rs, (uint32_t)(lane + j * kWave) * 16, 0, 0);
-            v[j] = make_float4(__int_as_float(x[0]), __int_as_float(x[1]), __int_as_float(x[2]), __int_as_float(x[3]));
-        }
-        // the lane's mask words (chunk lane + 64 j: word (lane >> 3) + 8 j), issued behind the row's loads so that
-        // both latencies overlap (a row split past the first ORs behind a wait)
-        uint32_t mwd[R > 0 ? R : 1];
-        uint32_t mw0 = 0u;  // word 0: its bit 0 masks the absmax seed
+        for (int j = 0; j < R; ++j)
+            v[j] = T::from_bits(__builtin_amdgcn_raw_buffer_load_b128(rs, (uint32_t)(lane + j * kWave) * 16, 0, 0));
         if constexpr (kMask) {
+            // the lane's mask words (chunk lane + 64 j: word (lane >> 3) + 8 j), issued behind the row's loads so that
+            // both latencies overlap (a row split past the first ORs behind a wait)
             static_assert(R <= 16, "the mask words cover len <= 4096");
             // the wave loads the mask once (lane l: words l and l + 64), then each lane takes its words by
             // ds_bpermute: word (lane >> 3) + 8 j is < 64 exactly for j < 8
             const int wl[2] = {lane, lane + 64};
-            uint32_t m2[2];
+            uint32_t m2[2], mwd[R];
             om->words(wl, m2);
 #pragma unroll
             for (int j = 0; j < R; ++j)
                 mwd[j] = (uint32_t)__shfl((int)(j < 8 ? m2[0] : m2[1]), ((lane >> 3) + 8 * j) & 63, 64);
-            mw0 = __builtin_amdgcn_readlane(m2[0], 0);
-        }
-        if constexpr (kMask) {
-            // outlier columns: X' holds +0 there (the seed included); branch-free selects
-            {
-                if (mw0 & 1u) seed = 0.0f;
+            // outlier columns: X' holds +0 there (the seed included: bit 0 of word 0); branch-free selects
+            if (__builtin_amdgcn_readlane(m2[0], 0) & 1u) seed = 0.0f;
 #pragma unroll
-                for (int j = 0; j < R; ++j) {
-                    const uint32_t nib = (mwd[j] >> (4 * (lane & 7))) & 15u;
-                    v[j].x = (nib & 1u) ? 0.0f : v[j].x;
-                    v[j].y = (nib & 2u) ? 0.0f : v[j].y;
-                    v[j].z = (nib & 4u) ? 0.0f : v[j].z;
-                    v[j].w = (nib & 8u) ? 0.0f : v[j].w;
-                }
+            for (int j = 0; j < R; ++j) {
+                const uint32_t nib = (mwd[j] >> (4 * (lane & 7))) & 15u;
+                v[j].x = (nib & 1u) ? 0.0f : v[j].x;
+                v[j].y = (nib & 2u) ? 0.0f : v[j].y;
+                v[j].z = (nib & 4u) ? 0.0f : v[j].z;
+                v[j].w = (nib & 8u) ? 0.0f : v[j].w;
             }
         }
 #pragma unroll
         for (int j = 0; j < R; ++j) {
             const int c = lane + j * kWave;
-            if (c < nfull) {
-                p = (c == 0) ? p : cand_max(p, v[j].x);  // element 0 is the seed
-                p = cand_max(p, v[j].y);
-                p = cand_max(p, v[j].z);
-                p = cand_max(p, v[j].w);
-            }
+            if (c < nfull) p = T::cand(p, v[j], c == 0);
         }
     } else {
-        for (int c = lane; c < nfull; c += kWave) {
-            float4 x = s4[c];
-            p = (c == 0) ? p : cand_max(p, x.x);
-            p = cand_max(p, x.y);
-            p = cand_max(p, x.z);
-            p = cand_max(p, x.w);
-        }
+        for (int c = lane; c < nfull; c += kWave)
+            p = T::cand(p, T::template load<false>(srow + T::kElems * (int64_t)c), c == 0);
     }
-    const int tail0 = nfull << 2;  // scalar tail elements [tail0, len)
-    if (tail0 + lane < len && tail0 + lane > 0) p = cand_max(p, srow[tail0 + lane]);
+    const int tail0 = nfull << T::kShift;  // scalar tail elements [tail0, len): fewer than kElems
+    if (tail0 + lane < len && tail0 + lane > 0) p = cand_max(p, widen(srow[tail0 + lane]));
     p = wave_max(p);
     const float cx = absmax_finish(seed, p);
     const float s = inv_divide(range, cx);
 
+    uint32_t d[T::kWords];
     if constexpr (R > 0) {
 #pragma unroll
         for (int j = 0; j < R; ++j) {
             const int c = lane + j * kWave;
-            if (c < nfull)
-                put(c, pack4(quant_i8(v[j].x, s), quant_i8(v[j].y, s), quant_i8(v[j].z, s), quant_i8(v[j].w, s)));
+            if (c < nfull) {
+                T::quant(v[j], s, d);
+                put_chunk(c, d);
+            }
         }
     } else {
         for (int c = lane; c < nfull; c += kWave) {
-            float4 x = s4[c];
-            put(c, pack4(quant_i8(x.x, s), quant_i8(x.y, s), quant_i8(x.z, s), quant_i8(x.w, s)));
+            T::quant(T::template load<false>(srow + T::kElems * (int64_t)c), s, d);
+            put_chunk(c, d);
         }
     }
-    // partial tail word, then zero padding words
-    const int64_t first_zero = nfull + ((len & 3) ? 1 : 0);
-    if ((len & 3) && lane == 0) {
-        int b[4] = {0, 0, 0, 0};
-        for (int e = 0; e < (len & 3); ++e) b[e] = quant_i8(srow[tail0 + e], s);
-        put(nfull, pack4(b[0], b[1], b[2], b[3]));
+    // partial tail words, then zero padding words
+    const int rem = len & (T::kElems - 1);
+    if (rem && lane == 0) {
+        T::quant_tail(srow, tail0, rem, s, d);
+#pragma unroll
+        for (int w = 0; w < T::kWords; ++w)
+            if (4 * w < rem) put(T::kWords * (int64_t)nfull + w, d[w]);
     }
+    const int64_t first_zero = T::kWords * nfull + (rem ? 1 : 0) + (rem > 4 ? 1 : 0);  // past the live tail words
     for (int64_t c = first_zero + lane; c < nq; c += kWave) put(c, 0u);
     if (lane == 0) st_f32<kWT>(scale + row, cx);
-    }
 }
 
 // Staged packed rows: kRows (8 or 16) consecutive packed rows row0 .. (row0 % 8 == 0), one per wave, in LDS
 // at stage + r * rsw dwords (rsw = k_pad / 4 + 16: the 16-B reads below are conflict-free in ds_read_b128's
 // lane groups for k_pad / 4 = 0 or 32 mod 64; + 8 left 2-way conflicts, 6.5 % of the pack's LDS cycles), written out as whole 128-B lines of the fragment-major q: line (L, h) = the 16-B pieces
 // of k 16L .. 16L+15 of rows 8h .. 8h+7; one wave store instruction = 8 lines.  After a block barrier.
-constexpr int kStageRowWordsMax = 4096 / 4 + 16;
+// kWaveRowMax: the longest row (k_pad, a multiple of 128) a staged LDS row takes, and with it the longest row of the
+// one-wave-per-row kernels, whatever the source type (rows_regs): longer rows go to the block-per-row kernel.
+constexpr int kWaveRowMax = 4096;
+constexpr int kStageRowWordsMax = kWaveRowMax / 4 + 16;
 template <int kRows>
 __device__ __forceinline__ void write_staged_rows(const uint32_t *stage, int rsw, int8_t *__restrict__ q, int64_t row0,
                                                   int64_t k_pad) {
@@ -403,12 +413,23 @@ __device__ __forceinline__ void write_staged_rows(const uint32_t *stage, int rsw
     }
 }
 
-// pack_rows, long rows (4096 < len <= 16384): ONE 256-thread block per row, up to 16 float4 per
-// thread in registers (4-KiB coalesced loads per block instruction), block-wide absmax (shuffle + LDS),
+// The staged X-rows role of a block of kRows waves (8 or 16): rows kRows xb .., one wave per row (len <= kWaveRowMax),
+// packed into `xstage` (kRows * kStageRowWordsMax dwords of LDS), then written out as whole lines.
+template <int R, int kRows, bool kMask = false, typename SrcT = float>
+__device__ __forceinline__ void pack_rows_staged(int64_t xb, const SrcT *__restrict__ x, int64_t xsh, int m, int k,
+                                                 float range, float *__restrict__ x_scale, int8_t *__restrict__ x_q,
+                                                 int64_t x_rows_pad, int64_t k_pad, uint32_t *xstage,
+                                                 const OutlierMask *om = nullptr) {
+    const int rsw = (int)(k_pad >> 2) + 16;
+    pack_rows_vec_body<R, kMask, false, true, 4, SrcT>(xb * (kRows / 4), x, xsh, m, k, range, x_scale, x_q, x_rows_pad,
+                                                       k_pad, om, xstage + (threadIdx.x >> 6) * rsw);
+    __syncthreads();
+    write_staged_rows<kRows>(xstage, rsw, x_q, xb * kRows, k_pad);
+}
+
+// pack_rows, long rows (kWaveRowMax < len <= RowSrc::kBlockRowMax): ONE 256-thread block per row, up to 16 chunks of
+// 16 B per thread in registers (4-KiB coalesced loads per block instruction), block-wide absmax (shuffle + LDS),
 // quantized from the registers -- one HBM read of the row.  `red` holds >= 5 floats of LDS.
-constexpr int kLongRowMax = 16384;
-// SrcT = bf16_t: the same 16 chunks of 16 B per thread hold 8 elements each, so one block takes rows of up to 32 768.
-constexpr int kLongRowMaxBf16 = 32768;
 template <bool kNt = false, typename SrcT = float>
 __device__ __forceinline__ void pack_row_block_body(int64_t row, const SrcT *__restrict__ src, int64_t sh, int rows,
                                                     int len, float range, float *__restrict__ scale,
@@ -423,88 +444,49 @@ __device__ __forceinline__ void pack_row_block_body(int64_t row, const SrcT *__r
         if (t == 0) scale[row] = 0.0f;
         return;
     }
-    if constexpr (!std::is_same<SrcT, float>::value) {
-        const bf16_t *srow = src + row * sh;
-        const int nfull = len >> 3;
-        v4u_t v[16];
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            const int c = t + 256 * j;
-            v[j] = (c < nfull) ? *reinterpret_cast<const v4u_t *>(srow + 8 * (int64_t)c) : v4u_t{0u, 0u, 0u, 0u};
-        }
-        float p = -INFINITY;
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            const int c = t + 256 * j;
-            if (c < nfull) p = cand_max8(p, v[j], c == 0);
-        }
-        const int tail0 = nfull << 3;
-        if (tail0 + t < len && tail0 + t > 0) p = cand_max(p, widen(srow[tail0 + t]));
-        p = wave_max(p);
-        if (lane == 0) red[wv] = p;
-        if (t == 0) red[4] = widen(srow[0]);  // the seed
-        __syncthreads();
-        p = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));  // -inf or >= +0: exact
-        const float cx = absmax_finish(red[4], p);
-        const float sc = inv_divide(range, cx);
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            const int c = t + 256 * j;
-            if (c < nfull) *reinterpret_cast<uint2 *>(qword(q, row, 8 * (int64_t)c, k_pad)) = quant8(v[j], sc);
-        }
-        const int rem = len & 7;
-        if (rem && t == 0) {
-            const uint2 d = quant_tail8(srow, tail0, rem, sc);
-            qrow(2 * (int64_t)nfull) = d.x;
-            if (rem > 4) qrow(2 * (int64_t)nfull + 1) = d.y;
-        }
-        for (int64_t c = (((int64_t)len + 3) >> 2) + t; c < nq; c += 256) qrow(c) = 0u;
-        if (t == 0) scale[row] = cx;
-        return;
-    } else {
-    const float *srow = src + row * sh;
-    const int nfull = len >> 2;
-    float4 v[16];
+    typedef RowSrc<SrcT> T;
+    const SrcT *srow = src + row * sh;
+    const int nfull = len >> T::kShift;
+    typename T::chunk_t v[16];
 #pragma unroll
     for (int j = 0; j < 16; ++j) {
         const int c = t + 256 * j;
-        v[j] = (c < nfull) ? ld_f4<kNt>(srow + 4 * (int64_t)c) : make_float4(0.f, 0.f, 0.f, 0.f);
+        v[j] = (c < nfull) ? T::template load<kNt>(srow + T::kElems * (int64_t)c) : T::from_bits(v4i_t{0, 0, 0, 0});
     }
     float p = -INFINITY;
 #pragma unroll
     for (int j = 0; j < 16; ++j) {
         const int c = t + 256 * j;
-        if (c < nfull) {
-            p = (c == 0) ? p : cand_max(p, v[j].x);  // element 0 is the seed
-            p = cand_max(p, v[j].y);
-            p = cand_max(p, v[j].z);
-            p = cand_max(p, v[j].w);
-        }
+        if (c < nfull) p = T::cand(p, v[j], c == 0);
     }
-    const int tail0 = nfull << 2;
-    if (tail0 + t < len && tail0 + t > 0) p = cand_max(p, srow[tail0 + t]);
+    const int tail0 = nfull << T::kShift;
+    if (tail0 + t < len && tail0 + t > 0) p = cand_max(p, widen(srow[tail0 + t]));
     p = wave_max(p);
     if (lane == 0) red[wv] = p;
-    if (t == 0) red[4] = nfull > 0 ? v[0].x : srow[0];  // the seed
+    if (t == 0) red[4] = nfull > 0 ? T::elem0(v[0]) : widen(srow[0]);  // the seed
     __syncthreads();
     p = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));  // -inf or >= +0: exact
     const float cx = absmax_finish(red[4], p);
     const float sc = inv_divide(range, cx);
+    uint32_t d[T::kWords];
 #pragma unroll
     for (int j = 0; j < 16; ++j) {
         const int c = t + 256 * j;
-        if (c < nfull)
-            qrow(c) = pack4(quant_i8(v[j].x, sc), quant_i8(v[j].y, sc), quant_i8(v[j].z, sc), quant_i8(v[j].w, sc));
+        if (c < nfull) {
+            T::quant(v[j], sc, d);
+            st_words<false>(qword(q, row, T::kElems * (int64_t)c, k_pad), d);
+        }
     }
-    const int64_t first_zero = nfull + ((len & 3) ? 1 : 0);
-    if ((len & 3) && t == 0) {
-        int b[4] = {0, 0, 0, 0};
-        for (int e = 0; e < (len & 3); ++e) b[e] = quant_i8(srow[tail0 + e], sc);
-        qrow(nfull) = pack4(b[0], b[1], b[2], b[3]);
+    const int rem = len & (T::kElems - 1);
+    if (rem && t == 0) {
+        T::quant_tail(srow, tail0, rem, sc, d);
+#pragma unroll
+        for (int w = 0; w < T::kWords; ++w)
+            if (4 * w < rem) qrow(T::kWords * (int64_t)nfull + w) = d[w];
     }
+    const int64_t first_zero = T::kWords * nfull + (rem ? 1 : 0) + (rem > 4 ? 1 : 0);  // past the live tail words
     for (int64_t c = first_zero + t; c < nq; c += 256) qrow(c) = 0u;
     if (t == 0) scale[row] = cx;
-    }
 }
 
 template <typename SrcT = float>
@@ -528,11 +510,7 @@ __global__ __launch_bounds__(R > 0 ? 512 : 256) void pack_rows_vec_kernel(const 
     const int b = xcd_contig(blockIdx.x, 0, gridDim.x);
     if constexpr (R > 0) {
         __shared__ __attribute__((aligned(16))) uint32_t xstage[8 * kStageRowWordsMax];
-        const int rsw = (int)(k_pad >> 2) + 16;
-        pack_rows_vec_body<R, false, false, true>(2 * (int64_t)b, src, sh, rows, len, range, scale, q, rows_pad, k_pad,
-                                                  nullptr, xstage + (threadIdx.x >> 6) * rsw);
-        __syncthreads();
-        write_staged_rows<8>(xstage, rsw, q, 8 * (int64_t)b, k_pad);
+        pack_rows_staged<R, 8>(b, src, sh, rows, len, range, scale, q, rows_pad, k_pad, xstage);
     } else {
         pack_rows_vec_body<R>(b, src, sh, rows, len, range, scale, q, rows_pad, k_pad);
     }
@@ -817,139 +795,208 @@ __global__ __launch_bounds__(256) void pack_cols_then_rows_kernel(
 }
 
 // ------------------------------------------------------------------------------------------------
-// Single-pass packing for the common shapes (row-major X and W, K <= 4096, N % 16 == 0), ONE launch
-// of 1024-thread blocks with two roles:
-//   W strip (blocks [0, n/16)): 16 columns x all K rows of W held in registers (16 float4 per
-//       thread), column absmax reduced on chip (shuffle + LDS), scales computed, quantized from the
-//       registers, stored as dwords of the 16 packed rows (4 k-bytes of one column each).
+// Single-pass packing for the common shapes (row-major X and W, K <= 4096), ONE launch with three roles by block
+// id, [W strips][zero padding strips][X rows]:
+//   W strip: kCols columns x all K rows of W held in registers, column absmax reduced on chip (shuffle + LDS),
+//       scales computed, quantized from the registers, stored as packed rows (4 k-bytes of one column per dword).
 //       W is read from HBM exactly once (the two-pass path reads it twice).
-//   X rows (remaining blocks): one wave per row, 16 rows per block (pack_rows_vec_body<16>).
-// Thread t of a W strip: c4 = t & 3 (columns n0 + 4*c4 .. +3), rq = t >> 2 (0..255): rows
-// 4*rq + e + 1024*i (e, i = 0..3); one wave instruction reads 16 rows x 64 B.
-constexpr int kWsCols = 16;
+//   X rows: one wave per row, staged in LDS (pack_rows_staged).
+// Three strip widths (launch_pack_single_pass_kind chooses): 16 columns and 1024 threads, 8 columns and 512 threads
+// at two blocks per CU, 32 columns for wide W.
 constexpr int kWsMaxK = 4096;
 
-__device__ __forceinline__ void pack_w_strip_body(int strip, const float *__restrict__ w, int64_t wsh, int k,
-                                                  int n, float range, float *__restrict__ scale,
-                                                  int8_t *__restrict__ q, int64_t k_pad, uint8_t *lds) {
+// ---- the steps every strip width shares.  A strip thread holds float4 pieces of W's rows: 4 adjacent columns (its
+// column group cg = t % (kCols / 4)) of some rows; p[0..3] are its columns' running |x| maxima. ----
+
+// one row piece's candidates; `live`: the row is one of 1 .. k - 1 (row 0 is the seed)
+__device__ __forceinline__ void strip_cand(float (&p)[4], float4 x, bool live) {
+    if (live) {
+        p[0] = cand_max(p[0], x.x);
+        p[1] = cand_max(p[1], x.y);
+        p[2] = cand_max(p[2], x.z);
+        p[3] = cand_max(p[3], x.w);
+    }
+}
+
+// The strip's column scales: the maxima reduced over the lanes of the wave with the same column group, then over the
+// block's kWaves waves through `red` ([kWaves][kCols] + [kCols] floats of LDS); thread t < kCols finishes column t
+// (w_seed = W[0, t], or +0 where the mask zeroes it), stores Cw to scale_out[t] and publishes range / Cw.  Returns
+// the four scales of the thread's own columns in s.
+template <int kCols, int kWaves, bool kWT = false>
+__device__ __forceinline__ void strip_scales(const float (&pin)[4], float w_seed, float range, float *red,
+                                             float *__restrict__ scale_out, float (&s)[4], bool seed_masked = false) {
+    constexpr int kGroups = kCols / 4;
     const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-    const int c4 = t & 3, rq = t >> 2;
-    const int64_t n0 = (int64_t)strip * kWsCols;
-    const float w_seed = t < kWsCols ? w[n0 + t] : 0.0f;  // W[0, j], issued first (used after the reduction)
-    float *red = reinterpret_cast<float *>(lds);                 // [16 waves][16 cols]
-    float *s_sh = red + 16 * 16;                                 // [16] scales
-    float4 v[4][4];                                              // [i][e]
+    float p[4] = {pin[0], pin[1], pin[2], pin[3]};
 #pragma unroll
-    for (int i = 0; i < 4; ++i)
+    for (int off = kGroups; off < 64; off <<= 1)
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int r = 4 * rq + e + 1024 * i;
-            v[i][e] = (r < k) ? *reinterpret_cast<const float4 *>(w + (int64_t)r * wsh + n0 + 4 * c4)
-                              : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    // column candidates over rows >= 1 (row 0 is the seed)
-    float p0 = -INFINITY, p1 = -INFINITY, p2 = -INFINITY, p3 = -INFINITY;
+        for (int j = 0; j < 4; ++j) p[j] = fmaxf(p[j], __shfl_xor(p[j], off, 64));
+    if (lane < kGroups)
 #pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int r = 4 * rq + e + 1024 * i;
-            if (r >= 1 && r < k) {
-                p0 = cand_max(p0, v[i][e].x);
-                p1 = cand_max(p1, v[i][e].y);
-                p2 = cand_max(p2, v[i][e].z);
-                p3 = cand_max(p3, v[i][e].w);
-            }
-        }
-    // reduce over the 16 lanes of the wave with the same c4 (lane bits 2..5), then over the 16 waves
-#pragma unroll
-    for (int off = 4; off < 64; off <<= 1) {
-        p0 = fmaxf(p0, __shfl_xor(p0, off, 64));
-        p1 = fmaxf(p1, __shfl_xor(p1, off, 64));
-        p2 = fmaxf(p2, __shfl_xor(p2, off, 64));
-        p3 = fmaxf(p3, __shfl_xor(p3, off, 64));
-    }
-    if (lane < 4) {
-        red[wv * 16 + 4 * lane + 0] = p0;
-        red[wv * 16 + 4 * lane + 1] = p1;
-        red[wv * 16 + 4 * lane + 2] = p2;
-        red[wv * 16 + 4 * lane + 3] = p3;
-    }
+        for (int j = 0; j < 4; ++j) red[wv * kCols + 4 * lane + j] = p[j];
     __syncthreads();
-    if (t < kWsCols) {
-        float p = red[t];
+    float *s_sh = red + kWaves * kCols;
+    if (t < kCols) {
+        float pm = red[t];
 #pragma unroll
-        for (int ww = 1; ww < 16; ++ww) p = fmaxf(p, red[ww * 16 + t]);  // -inf or >= +0: exact
-        const float cw = absmax_finish(w_seed, p);                      // seed = W[0, j]
+        for (int ww = 1; ww < kWaves; ++ww) pm = fmaxf(pm, red[ww * kCols + t]);  // -inf or >= +0: exact
+        const float cw = absmax_finish(seed_masked ? 0.0f : w_seed, pm);  // seed = W[0, j] (W'[0, j])
         s_sh[t] = inv_divide(range, cw);
-        scale[n0 + t] = cw;
+        st_f32<kWT>(scale_out + t, cw);
     }
     __syncthreads();
-    const float s0 = s_sh[4 * c4 + 0], s1 = s_sh[4 * c4 + 1], s2 = s_sh[4 * c4 + 2], s3 = s_sh[4 * c4 + 3];
-    // quantize; 4 consecutive rows of one column = one dword of packed row n0 + 4 c4 + cc.  The quad of threads
-    // rq = 4a .. 4a+3 with the same c4 (lanes 4 rq + c4) hold the 16 k of a fragment-major piece: after the quad
-    // transpose thread b = rq & 3 stores the piece of packed row n0 + 4 c4 + b, and one wave store instruction
-    // writes a whole 1-KiB block (16 rows x 64 k).
-    const auto dst = buf_rsrc(q + n0 * k_pad, (uint32_t)(16 * k_pad));
+#pragma unroll
+    for (int j = 0; j < 4; ++j) s[j] = s_sh[4 * (t & (kGroups - 1)) + j];
+}
+
+// 4 consecutive rows r0 .. r0 + 3 (x[e]) of the thread's column cc (scale sc) -> the 4 k-bytes r0 .. of that column, one
+// dword of its packed row (rows >= k are zero bytes)
+__device__ __forceinline__ uint32_t strip_quant(const float4 (&x)[4], int cc, float sc, int r0, int k) {
+    int qe[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const float xv = cc == 0 ? x[e].x : cc == 1 ? x[e].y : cc == 2 ? x[e].z : x[e].w;
+        qe[e] = (r0 + e < k) ? quant_i8(xv, sc) : 0;
+    }
+    return pack4(qe[0], qe[1], qe[2], qe[3]);
+}
+
+// The padding-strip role: packed rows of W past its n columns (kCols per block of kThreads) are zero rows, zero scales
+template <int kCols, int kThreads>
+__device__ __forceinline__ void zero_w_strip(int pad_strip, int n, float *__restrict__ w_scale, int8_t *__restrict__ w_q,
+                                             int64_t k_pad) {
+    const int64_t n0 = n + (int64_t)pad_strip * kCols;
+    zero_packed_rows(w_q, n0, kCols, k_pad, threadIdx.x, kThreads);
+    if (threadIdx.x < kCols) w_scale[n0 + threadIdx.x] = 0.0f;
+}
+
+// ---- 16- and 8-column strips: 256 * kCols / 4 threads, 16 float4 per thread.  Thread t: cg = t % (kCols / 4) (columns
+// n0 + 4 cg .. +3), rq = t / (kCols / 4) (0..255): rows 4 rq + e + 1024 i (e, i = 0..3); one wave instruction reads
+// 16 rows x 64 B, or 32 rows x 32 B. ----
+// 8 columns, TWO blocks per CU (n % 8 == 0): a 512-thread block fits in 88 VGPRs (5 waves/SIMD), and a second block on
+// the CU streams its loads while the first reduces, quantizes and stores (the 1024-thread single pass leaves the CU's
+// HBM stream idle through those phases); the four strips sharing a 128-B line of W run on one XCD.  Its loads are
+// buffer instructions on a wave-uniform descriptor with ONE per-lane offset; rows >= K lie past the descriptor and
+// read as zeros (the descriptor limits the strip to 2 GiB of W: can8 in launch_pack_single_pass_kind).  The 16-column
+// strip keeps plain loads behind a row guard, and with them W of any size.
+// Measured (lab/pack2_lab.hip, 4096^3): 28.0 us vs 31.7 us for the 16-column single pass; better up to
+// n = 8192 at K >= 2048, worse for wider W (n = 12288, 16384) and short K, where the 16-column pass stays.
+// kMask, kWT: 8 columns only.
+constexpr int kWsCols = 16;
+constexpr int kWs8Cols = 8;
+
+template <int kCols, bool kMask = false, bool kWT = false>
+__device__ __forceinline__ void pack_w_strip_body(int strip, const float *__restrict__ w, int64_t wsh, int k,
+                                                  float range, float *__restrict__ scale, int8_t *__restrict__ q,
+                                                  int64_t k_pad, float *red /* [kWaves][kCols] + [kCols] */,
+                                                  const OutlierMask *om = nullptr) {
+    static_assert(kCols == kWs8Cols || (kCols == kWsCols && !kMask && !kWT), "mask and write-through: 8-column strips");
+    constexpr int kGroups = kCols / 4, kWaves = 4 * kGroups;
+    const int t = threadIdx.x, lane = t & 63;
+    const int cg = t & (kGroups - 1), rq = t / kGroups;
+    const int64_t n0 = (int64_t)strip * kCols;
+    const float w_seed = t < kCols ? w[n0 + t] : 0.0f;  // W[0, j], issued first (used after the reduction)
+    float4 v[4][4];  // [i][e]
+    if constexpr (kCols == kWs8Cols) {
+        const auto src = buf_rsrc(w + n0, (uint32_t)(((int64_t)(k - 1) * wsh + kCols) * 4));
+        const uint32_t vrow = (uint32_t)((4 * rq * wsh + 4 * cg) * 4);
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const v4i_t x = __builtin_amdgcn_raw_buffer_load_b128(src, vrow + (uint32_t)((e + 1024 * i) * wsh * 4), 0, 0);
+                v[i][e] = make_float4(__int_as_float(x[0]), __int_as_float(x[1]), __int_as_float(x[2]), __int_as_float(x[3]));
+            }
+    } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int r = 4 * rq + e + 1024 * i;
+                v[i][e] = (r < k) ? *reinterpret_cast<const float4 *>(w + (int64_t)r * wsh + n0 + 4 * cg)
+                                  : make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+    }
+    bool seed_masked = false;
+    if constexpr (kMask) {
+        // the mask words of the thread's rows (4 rq + e + 1024 i: word (4 rq + 1024 i) >> 5), issued behind the strip's
+        // loads: the wave's 16 words (rq >> 3 = 4 wv .. 4 wv + 3, + 32 i) are loaded once, lane b + 4 i holding word
+        // 4 wv + b + 32 i, lane 16 word 0 (its bit 0 masks the absmax seed); each thread takes its 4 by ds_bpermute
+        const int wv = t >> 6, b0 = (rq >> 3) - 4 * wv;
+        const int wl[1] = {lane < 16 ? 4 * wv + (lane & 3) + 32 * (lane >> 2) : (lane == 16 ? 0 : om->nwords)};
+        uint32_t m1[1], mw[4];
+        om->words(wl, m1);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) mw[i] = (uint32_t)__shfl((int)m1[0], b0 + 4 * i, 64);
+        seed_masked = __builtin_amdgcn_readlane(m1[0], 16) & 1u;
+        // outlier rows of W (outlier feature columns of X): W' holds +0 there; branch-free selects
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int r = 4 * rq + e + 1024 * i;
+                const bool z = r < k && ((mw[i] >> (r & 31)) & 1u);
+                v[i][e].x = z ? 0.0f : v[i][e].x;
+                v[i][e].y = z ? 0.0f : v[i][e].y;
+                v[i][e].z = z ? 0.0f : v[i][e].z;
+                v[i][e].w = z ? 0.0f : v[i][e].w;
+            }
+    }
+    float p[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY}, s[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int r = 4 * rq + e + 1024 * i;
+            strip_cand(p, v[i][e], r >= 1 && r < k);
+        }
+    strip_scales<kCols, kWaves, kWT>(p, w_seed, range, red, scale + n0, s, seed_masked);
+    // 4 consecutive rows of one column = one dword of packed row n0 + 4 cg + cc.  The strip's packed rows are a whole
+    // 16-row group of the fragment-major q or half of one (descriptor over the group), and a 16-B piece of it (one
+    // packed row, 16 consecutive k) is the dwords of the 4 threads rq = 4a .. 4a+3 with the same cg (lanes
+    // kGroups rq + cg).  A 4 x 4 transpose among those lanes (4 shuffles) leaves thread b = rq & 3 holding the piece of
+    // packed row 4 cg + b, so one wave store instruction writes 16 B per lane = 8 whole 128-B lines (a whole 1-KiB
+    // block of 16 rows x 64 k, or rows 0-7 of the group, 2 k-blocks x 4 k-chunks), not 4-B pieces of 16 lines.
+    const int64_t g0 = n0 & ~(int64_t)15;
+    const auto dst = buf_rsrc(q + g0 * k_pad, (uint32_t)(16 * k_pad));
     const int b = rq & 3;
-    const int qbase = lane - 4 * b;
+    const int qbase = lane - kGroups * b;  // lane of this quad's b = 0 thread
+    const int prow = (int)(n0 - g0) + 4 * cg + b;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int r0 = 4 * rq + 1024 * i;
         uint32_t d[4];
 #pragma unroll
-        for (int cc = 0; cc < 4; ++cc) {
-            int qe[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float x = cc == 0 ? v[i][e].x : cc == 1 ? v[i][e].y : cc == 2 ? v[i][e].z : v[i][e].w;
-                const float sc = cc == 0 ? s0 : cc == 1 ? s1 : cc == 2 ? s2 : s3;
-                qe[e] = (r0 + e < k) ? quant_i8(x, sc) : 0;
-            }
-            d[cc] = pack4(qe[0], qe[1], qe[2], qe[3]);
-        }
+        for (int cc = 0; cc < 4; ++cc) d[cc] = strip_quant(v[i], cc, s[cc], r0, k);
         uint32_t pc[4] = {0u, 0u, 0u, 0u};
-        quad_transpose(d, b, qbase, 4, pc);
-        const int kp = r0 - 4 * b;
+        quad_transpose(d, b, qbase, kGroups, pc);
+        const int kp = r0 - 4 * b;  // the piece's first k (a multiple of 16)
         if (kp < k_pad) {
-            typedef int v4i_t __attribute__((ext_vector_type(4)));
             const v4i_t val = {(int)pc[0], (int)pc[1], (int)pc[2], (int)pc[3]};
-            __builtin_amdgcn_raw_buffer_store_b128(val, dst, (uint32_t)fofs(4 * c4 + b, kp, k_pad), 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b128(val, dst, (uint32_t)fofs(prow, kp, k_pad), 0, kWT ? 16 /* sc1 */ : 0);
         }
     }
 }
 
+// 16 columns (n % 16 == 0): 16 X rows per 1024-thread block.  Role order (lab, 4096^3): 30.4 us; X rows first
+// 31.5 us; W and X interleaved in groups of 8 blocks 35.1 us.
 __global__ __launch_bounds__(1024) void pack_single_pass_kernel(
     const float *__restrict__ x, int64_t xsh, int m, int k, float *__restrict__ x_scale, int8_t *__restrict__ x_q,
     int64_t x_rows_pad, int64_t k_pad, const float *__restrict__ w, int64_t wsh, int n, float *__restrict__ w_scale,
     int8_t *__restrict__ w_q, int64_t w_rows_pad, int nstrips, float range, uint32_t *zero_words, int nzero) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t dyn_lds[];
+    extern __shared__ __attribute__((aligned(16))) uint8_t dyn_lds[];  // the strip's `red`, or 16 staged X rows
     zero_words_block0(zero_words, nzero);
-    // roles by block id: [W strips][zero padding strips][X rows] (lab, 4096^3: 30.4 us; X rows first
-    // 31.5 us; W and X interleaved in groups of 8 blocks 35.1 us)
     const int bid = blockIdx.x;
-    if (bid < nstrips) {
-        // blocks b and b+8 run on one XCD: give them adjacent strips, so each 128-B line of W (two
-        // 64-B strip segments) is fetched into that XCD's L2 once (bijective for any nstrips)
-        const int xcd = bid & 7, q8 = nstrips >> 3, r8 = nstrips & 7;
-        const int strip = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
-        pack_w_strip_body(strip, w, wsh, k, n, range, w_scale, w_q, k_pad, dyn_lds);
-    } else if (bid < nstrips + (int)((w_rows_pad - n) / kWsCols)) {
-        // padding rows of packed W: zero rows, zero scales
-        const int64_t n0 = n + (int64_t)(bid - nstrips) * kWsCols;
-        zero_packed_rows(w_q, n0, kWsCols, k_pad, threadIdx.x, 1024);
-        if (threadIdx.x < kWsCols) w_scale[n0 + threadIdx.x] = 0.0f;
-    } else {
-        // X rows: 16 rows per 1024-thread block = four 4-row groups of the 256-thread body (rows 16xb + (t>>6)),
-        // staged in LDS and written out as whole 1-KiB blocks of the fragment-major q
-        const int64_t xb = bid - nstrips - (int)((w_rows_pad - n) / kWsCols);
-        const int rsw = (int)(k_pad >> 2) + 16;
-        uint32_t *xstage = reinterpret_cast<uint32_t *>(dyn_lds);
-        pack_rows_vec_body<16, false, false, true>(xb * 4, x, xsh, m, k, range, x_scale, x_q, x_rows_pad, k_pad, nullptr,
-                                                   xstage + (threadIdx.x >> 6) * rsw);
-        __syncthreads();
-        write_staged_rows<16>(xstage, rsw, x_q, xb * 16, k_pad);
-    }
+    const int npad = (int)((w_rows_pad - n) / kWsCols);
+    if (bid < nstrips)
+        pack_w_strip_body<kWsCols>(xcd_contig_strip(bid, nstrips), w, wsh, k, range, w_scale, w_q, k_pad,
+                                   reinterpret_cast<float *>(dyn_lds));
+    else if (bid < nstrips + npad)
+        zero_w_strip<kWsCols, 1024>(bid - nstrips, n, w_scale, w_q, k_pad);
+    else
+        pack_rows_staged<16, 16>(bid - nstrips - npad, x, xsh, m, k, range, x_scale, x_q, x_rows_pad, k_pad,
+                                 reinterpret_cast<uint32_t *>(dyn_lds));
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -973,7 +1020,6 @@ typedef __attribute__((address_space(3))) void lds_void;
 __device__ __forceinline__ void pack_w_strip32_body(int strip, const float *__restrict__ w, int64_t wsh, int k,
                                                     float range, float *__restrict__ scale, int8_t *__restrict__ q,
                                                     int64_t k_pad, uint8_t *lds, float *red) {
-    typedef int v4i_t __attribute__((ext_vector_type(4)));
     const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
     const int c8 = t & 7, rq = t >> 3;  // columns n0 + 4*c8 .. +3; rows 4*rq + e + 512*i
     const int64_t n0 = (int64_t)strip * kW32Cols;
@@ -996,18 +1042,13 @@ __device__ __forceinline__ void pack_w_strip32_body(int strip, const float *__re
             const v4i_t x = __builtin_amdgcn_raw_buffer_load_b128(src, vrow + (uint32_t)((e + 512 * i) * wsh * 4), 0, 0);
             v[i][e] = make_float4(__int_as_float(x[0]), __int_as_float(x[1]), __int_as_float(x[2]), __int_as_float(x[3]));
         }
-    float p0 = -INFINITY, p1 = -INFINITY, p2 = -INFINITY, p3 = -INFINITY;
+    float p[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY}, s[4];
 #pragma unroll
     for (int i = 0; i < kW32RegI; ++i)
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const int r = 4 * rq + e + 512 * i;
-            if (r >= 1 && r < k) {
-                p0 = cand_max(p0, v[i][e].x);
-                p1 = cand_max(p1, v[i][e].y);
-                p2 = cand_max(p2, v[i][e].z);
-                p3 = cand_max(p3, v[i][e].w);
-            }
+            strip_cand(p, v[i][e], r >= 1 && r < k);
         }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's DMA slots have landed
     const float4 *ls = reinterpret_cast<const float4 *>(lds) + wv * 64 + lane;
@@ -1016,40 +1057,9 @@ __device__ __forceinline__ void pack_w_strip32_body(int strip, const float *__re
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const int r = 4 * rq + e + 512 * (i + kW32RegI);
-            if (r < k) {
-                const float4 x = ls[(i * 4 + e) * 16 * 64];
-                p0 = cand_max(p0, x.x);
-                p1 = cand_max(p1, x.y);
-                p2 = cand_max(p2, x.z);
-                p3 = cand_max(p3, x.w);
-            }
+            if (r < k) strip_cand(p, ls[(i * 4 + e) * 16 * 64], true);
         }
-    // over the 8 lanes of the wave with the same c8 (lane bits 3..5), then over the 16 waves
-#pragma unroll
-    for (int off = 8; off < 64; off <<= 1) {
-        p0 = fmaxf(p0, __shfl_xor(p0, off, 64));
-        p1 = fmaxf(p1, __shfl_xor(p1, off, 64));
-        p2 = fmaxf(p2, __shfl_xor(p2, off, 64));
-        p3 = fmaxf(p3, __shfl_xor(p3, off, 64));
-    }
-    if (lane < 8) {
-        red[wv * 32 + 4 * lane + 0] = p0;
-        red[wv * 32 + 4 * lane + 1] = p1;
-        red[wv * 32 + 4 * lane + 2] = p2;
-        red[wv * 32 + 4 * lane + 3] = p3;
-    }
-    __syncthreads();
-    float *s_sh = red + 16 * 32;
-    if (t < kW32Cols) {
-        float pm = red[t];
-#pragma unroll
-        for (int ww = 1; ww < 16; ++ww) pm = fmaxf(pm, red[ww * 32 + t]);  // -inf or >= +0: exact
-        const float cw = absmax_finish(w_seed, pm);                       // seed = W[0, j]
-        s_sh[t] = inv_divide(range, cw);
-        scale[n0 + t] = cw;
-    }
-    __syncthreads();
-    const float s0 = s_sh[4 * c8 + 0], s1 = s_sh[4 * c8 + 1], s2 = s_sh[4 * c8 + 2], s3 = s_sh[4 * c8 + 3];
+    strip_scales<kW32Cols, 16>(p, w_seed, range, red, scale + n0, s);
     // the strip's 32 packed rows = two whole 16-row groups: one contiguous region of the fragment-major q
     // (dword stores: the quad transpose to 16-B pieces spilled here, 128 VGPRs, and measured slower)
     const auto dst = buf_rsrc(q + n0 * k_pad, (uint32_t)(kW32Cols * k_pad));
@@ -1073,17 +1083,9 @@ __device__ __forceinline__ void pack_w_strip32_body(int strip, const float *__re
             }
         }
 #pragma unroll
-        for (int cc = 0; cc < 4; ++cc) {
-            int qe[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float x = cc == 0 ? x4[e].x : cc == 1 ? x4[e].y : cc == 2 ? x4[e].z : x4[e].w;
-                const float sc = cc == 0 ? s0 : cc == 1 ? s1 : cc == 2 ? s2 : s3;
-                qe[e] = (r0 + e < k) ? quant_i8(x, sc) : 0;
-            }
-            __builtin_amdgcn_raw_buffer_store_b32((int)pack4(qe[0], qe[1], qe[2], qe[3]), dst,
+        for (int cc = 0; cc < 4; ++cc)
+            __builtin_amdgcn_raw_buffer_store_b32((int)strip_quant(x4, cc, s[cc], r0, k), dst,
                                                   (uint32_t)fofs(4 * c8 + cc, r0, k_pad), 0, 0);
-        }
     }
 }
 
@@ -1102,8 +1104,7 @@ __global__ __launch_bounds__(1024) void pack_single_pass32_kernel(
     if (bid < nstrips) {
         int strip;
         if constexpr (kMap == 0) {
-            const int xcd = bid & 7, q8 = nstrips >> 3, r8 = nstrips & 7;
-            strip = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+            strip = xcd_contig_strip(bid, nstrips);
         } else if constexpr (kMap == 1) {
             strip = bid;
         } else if constexpr (kMap == 2) {
@@ -1124,167 +1125,17 @@ __global__ __launch_bounds__(1024) void pack_single_pass32_kernel(
         }
         pack_w_strip32_body(strip, w, wsh, k, range, w_scale, w_q, k_pad, lds_w, red);
     } else if (bid < nstrips + npad) {
-        const int64_t n0 = n + (int64_t)(bid - nstrips) * kW32Cols;
-        zero_packed_rows(w_q, n0, kW32Cols, k_pad, threadIdx.x, 1024);
-        if (threadIdx.x < kW32Cols) w_scale[n0 + threadIdx.x] = 0.0f;
+        zero_w_strip<kW32Cols, 1024>(bid - nstrips, n, w_scale, w_q, k_pad);
     } else {
-        // 16 rows per block, staged in LDS (the strip role's DMA region) and written out as whole 1-KiB blocks
-        const int64_t xb = bid - nstrips - npad;
-        const int rsw = (int)(k_pad >> 2) + 16;
-        uint32_t *xstage = reinterpret_cast<uint32_t *>(lds_w);
-        pack_rows_vec_body<16, false, false, true>(xb * 4, x, xsh, m, k, range, x_scale, x_q, x_rows_pad, k_pad, nullptr,
-                                                   xstage + (threadIdx.x >> 6) * rsw);
-        __syncthreads();
-        write_staged_rows<16>(xstage, rsw, x_q, xb * 16, k_pad);
+        // 16 rows per block, staged in the strip role's DMA region
+        pack_rows_staged<16, 16>(bid - nstrips - npad, x, xsh, m, k, range, x_scale, x_q, x_rows_pad, k_pad,
+                                 reinterpret_cast<uint32_t *>(lds_w));
     }
 }
 
 // ------------------------------------------------------------------------------------------------
-// Single pass at TWO blocks per CU (K <= 4096, n % 8 == 0): 512-thread blocks with the same 16 float4
-// per thread, so a block fits in 88 VGPRs (5 waves/SIMD) and a second block on the CU streams its
-// loads while the first reduces, quantizes and stores (the 1024-thread single pass leaves the CU's HBM
-// stream idle through those phases).  Roles:
-//   W strip (blocks [0, n/8)): 8 columns x all K rows; thread t: c2 = t & 1 (columns n0 + 4*c2 .. +3),
-//       rows 4*(t>>1) + e + 1024*i (e, i = 0..3).  One wave instruction reads 32 rows x 32 B; the four
-//       strips sharing a 128-B line of W run on one XCD (blocks b, b+8, b+16, b+24 get adjacent strips)
-//       so the line is fetched once.  Loads and stores are buffer instructions on a wave-uniform
-//       descriptor with ONE per-lane offset; rows >= K lie past the descriptor and read as zeros.
-//   X rows (the rest): 8 rows per block, one wave per row (pack_rows_vec_body<16>).
-// Measured (lab/pack2_lab.hip, 4096^3): 28.0 us vs 31.7 us for the 16-column single pass; better up to
-// n = 8192 at K >= 2048, worse for wider W (n = 12288, 16384) and short K, where the 16-column pass stays.
-constexpr int kWs8Cols = 8;
-
-template <bool kMask = false, bool kWT = false>
-__device__ __forceinline__ void pack_w_strip8_body(int strip, const float *__restrict__ w, int64_t wsh, int k,
-                                                   float range, float *__restrict__ scale, int8_t *__restrict__ q,
-                                                   int64_t k_pad, float *red /* [8 waves][8 cols] + [8] */,
-                                                   const OutlierMask *om = nullptr) {
-    typedef int v4i_t __attribute__((ext_vector_type(4)));
-    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-    const int c2 = t & 1, rq = t >> 1;
-    const int64_t n0 = (int64_t)strip * kWs8Cols;
-    const float w_seed = t < kWs8Cols ? w[n0 + t] : 0.0f;  // W[0, j], issued first (used after the reduction)
-    const auto src = buf_rsrc(w + n0, (uint32_t)(((int64_t)(k - 1) * wsh + kWs8Cols) * 4));
-    const uint32_t vrow = (uint32_t)((4 * rq * wsh + 4 * c2) * 4);
-    float4 v[4][4];  // [i][e]
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const v4i_t x = __builtin_amdgcn_raw_buffer_load_b128(src, vrow + (uint32_t)((e + 1024 * i) * wsh * 4), 0, 0);
-            v[i][e] = make_float4(__int_as_float(x[0]), __int_as_float(x[1]), __int_as_float(x[2]), __int_as_float(x[3]));
-        }
-    // the mask words of the thread's rows (4 rq + e + 1024 i: word (4 rq + 1024 i) >> 5), issued behind the strip's
-    // loads
-    uint32_t mw[4] = {0u, 0u, 0u, 0u}, mw0 = 0u;  // mw0: word 0, whose bit 0 masks the absmax seed
-    if constexpr (kMask) {
-        // the wave's 16 words (rq >> 3 = 4 wv .. 4 wv + 3, + 32 i) are loaded once, lane b + 4 i holding word
-        // 4 wv + b + 32 i, lane 16 word 0; each thread takes its 4 by ds_bpermute
-        const int b0 = (rq >> 3) - 4 * wv;
-        const int wl[1] = {lane < 16 ? 4 * wv + (lane & 3) + 32 * (lane >> 2) : (lane == 16 ? 0 : om->nwords)};
-        uint32_t m1[1];
-        om->words(wl, m1);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) mw[i] = (uint32_t)__shfl((int)m1[0], b0 + 4 * i, 64);
-        mw0 = __builtin_amdgcn_readlane(m1[0], 16);
-    }
-    bool seed_masked = false;
-    if constexpr (kMask) {
-        // outlier rows of W (outlier feature columns of X): W' holds +0 there; branch-free selects
-        {
-            seed_masked = mw0 & 1u;
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int r = 4 * rq + e + 1024 * i;
-                    const bool z = r < k && ((mw[i] >> (r & 31)) & 1u);
-                    v[i][e].x = z ? 0.0f : v[i][e].x;
-                    v[i][e].y = z ? 0.0f : v[i][e].y;
-                    v[i][e].z = z ? 0.0f : v[i][e].z;
-                    v[i][e].w = z ? 0.0f : v[i][e].w;
-                }
-        }
-    }
-    // column candidates over rows >= 1 (row 0 is the seed)
-    float p0 = -INFINITY, p1 = -INFINITY, p2 = -INFINITY, p3 = -INFINITY;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int r = 4 * rq + e + 1024 * i;
-            if (r >= 1 && r < k) {
-                p0 = cand_max(p0, v[i][e].x);
-                p1 = cand_max(p1, v[i][e].y);
-                p2 = cand_max(p2, v[i][e].z);
-                p3 = cand_max(p3, v[i][e].w);
-            }
-        }
-    // over the 32 lanes of the wave with the same c2 (lane bits 1..5), then over the 8 waves
-#pragma unroll
-    for (int off = 2; off < 64; off <<= 1) {
-        p0 = fmaxf(p0, __shfl_xor(p0, off, 64));
-        p1 = fmaxf(p1, __shfl_xor(p1, off, 64));
-        p2 = fmaxf(p2, __shfl_xor(p2, off, 64));
-        p3 = fmaxf(p3, __shfl_xor(p3, off, 64));
-    }
-    if (lane < 2) {
-        red[wv * 8 + 4 * lane + 0] = p0;
-        red[wv * 8 + 4 * lane + 1] = p1;
-        red[wv * 8 + 4 * lane + 2] = p2;
-        red[wv * 8 + 4 * lane + 3] = p3;
-    }
-    __syncthreads();
-    float *s_sh = red + 8 * 8;
-    if (t < kWs8Cols) {
-        float pm = red[t];
-#pragma unroll
-        for (int ww = 1; ww < 8; ++ww) pm = fmaxf(pm, red[ww * 8 + t]);  // -inf or >= +0: exact
-        const float cw = absmax_finish(seed_masked ? 0.0f : w_seed, pm);  // seed = W[0, j] (W'[0, j])
-        s_sh[t] = inv_divide(range, cw);
-        st_f32<kWT>(scale + n0 + t, cw);
-    }
-    __syncthreads();
-    const float s0 = s_sh[4 * c2 + 0], s1 = s_sh[4 * c2 + 1], s2 = s_sh[4 * c2 + 2], s3 = s_sh[4 * c2 + 3];
-    // 4 consecutive rows of one column = one dword of packed row n0 + 4*c2 + cc.  The strip's 8 packed rows are
-    // half of a 16-row group of the fragment-major q (descriptor over the group), and a 16-B piece of it (one
-    // packed row, 16 consecutive k) is the dwords of the 4 threads rq = 4a .. 4a+3 with the same c2 (lanes
-    // 2 rq + c2).  A 4 x 4 transpose among those lanes (4 shuffles) leaves thread b = rq & 3 holding the piece of
-    // packed row 4 c2 + b, so one wave store instruction writes 16 B per lane = 8 whole 128-B lines (rows 0-7
-    // of the group, 2 k-blocks x 4 k-chunks), not 4-B pieces of 16 lines.
-    const int64_t g0 = n0 & ~(int64_t)15;
-    const auto dst = buf_rsrc(q + g0 * k_pad, (uint32_t)(16 * k_pad));
-    const int b = rq & 3;
-    const int qbase = lane - 2 * b;  // lane of this quad's b = 0 thread
-    const int prow = (int)(n0 - g0) + 4 * c2 + b;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int r0 = 4 * rq + 1024 * i;
-        uint32_t d[4];
-#pragma unroll
-        for (int cc = 0; cc < 4; ++cc) {
-            int qe[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float x = cc == 0 ? v[i][e].x : cc == 1 ? v[i][e].y : cc == 2 ? v[i][e].z : v[i][e].w;
-                const float sc = cc == 0 ? s0 : cc == 1 ? s1 : cc == 2 ? s2 : s3;
-                qe[e] = (r0 + e < k) ? quant_i8(x, sc) : 0;
-            }
-            d[cc] = pack4(qe[0], qe[1], qe[2], qe[3]);
-        }
-        uint32_t pc[4] = {0u, 0u, 0u, 0u};
-        quad_transpose(d, b, qbase, 2, pc);
-        const int kp = r0 - 4 * b;  // the piece's first k (a multiple of 16)
-        if (kp < k_pad) {
-            typedef int v4i_t __attribute__((ext_vector_type(4)));
-            const v4i_t val = {(int)pc[0], (int)pc[1], (int)pc[2], (int)pc[3]};
-            __builtin_amdgcn_raw_buffer_store_b128(val, dst, (uint32_t)fofs(prow, kp, k_pad), 0, kWT ? 16 /* sc1 */ : 0);
-        }
-    }
-}
-
-// Roles by block id: [W strips][W padding][X rows] (measured against W / X alternating and X rows first:
-// 29.1 vs 35.6 / 30.5 µs at 4096^3, 41.0 vs 42.2 / 43.0 at 8192 x 4096^2; profiles/r03_pack8_order_lab.log)
+// The 8-column single pass: 8 X rows per 512-thread block.  Role order measured against W / X alternating and X rows
+// first: 29.1 vs 35.6 / 30.5 µs at 4096^3, 41.0 vs 42.2 / 43.0 at 8192 x 4096^2; profiles/r03_pack8_order_lab.log
 template <int kWavesPerEu, bool kMask = false>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(kWavesPerEu, kWavesPerEu))) void pack_single_pass8_kernel(
     const float *__restrict__ x, int64_t xsh, int m, int k, float *__restrict__ x_scale, int8_t *__restrict__ x_q,
@@ -1297,28 +1148,17 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(kWavesPerEu
     const int npad = (int)((w_rows_pad - n) / kWs8Cols);
     const int bid = blockIdx.x;
     if (bid < nstrips) {
-        // blocks b, b+8, ... run on one XCD: XCD-contiguous strip ranges (bijective for any nstrips)
-        const int xcd = bid & 7, q8 = nstrips >> 3, r8 = nstrips & 7;
-        const int strip = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
-        pack_w_strip8_body<kMask>(strip, w, wsh, k, range, w_scale, w_q, k_pad, red, &om);
+        pack_w_strip_body<kWs8Cols, kMask>(xcd_contig_strip(bid, nstrips), w, wsh, k, range, w_scale, w_q, k_pad, red, &om);
         if constexpr (kMask)
             if (bid == 0) {
                 __syncthreads();  // red is reused as the scan's wave sums
                 outlier_column_list(om, reinterpret_cast<int *>(red));
             }
     } else if (bid < nstrips + npad) {
-        const int64_t n0 = n + (int64_t)(bid - nstrips) * kWs8Cols;
-        zero_packed_rows(w_q, n0, kWs8Cols, k_pad, threadIdx.x, 512);
-        if (threadIdx.x < kWs8Cols) w_scale[n0 + threadIdx.x] = 0.0f;
+        zero_w_strip<kWs8Cols, 512>(bid - nstrips, n, w_scale, w_q, k_pad);
     } else {
-        // rows 8xb + (t>>6): two 4-row groups of the 256-thread body, staged in LDS and written out as whole
-        // 128-B lines of the fragment-major q (a line = 8 rows x 16 B: exactly this block's rows)
-        const int64_t xb = bid - nstrips - npad;
-        const int rsw = (int)(k_pad >> 2) + 16;
-        pack_rows_vec_body<16, kMask, false, true>(xb * 2, x, xsh, m, k, range, x_scale, x_q, x_rows_pad, k_pad, &om,
-                                                   xstage + (threadIdx.x >> 6) * rsw);
-        __syncthreads();
-        write_staged_rows<8>(xstage, rsw, x_q, xb * 8, k_pad);
+        pack_rows_staged<16, 8, kMask>(bid - nstrips - npad, x, xsh, m, k, range, x_scale, x_q, x_rows_pad, k_pad, xstage,
+                                       &om);
     }
 }
 
@@ -1335,37 +1175,33 @@ __global__ __launch_bounds__(256) void fill_uniform_kernel(float *__restrict__ d
     }
 }
 
-bool rows_vec_ok(const float *src, int64_t sh, int64_t sw, int rows) {
-    return sw == 1 && (sh % 4 == 0 || rows == 1) && (reinterpret_cast<uintptr_t>(src) % 16 == 0);
-}
-// bf16 rows: every row must start on a 16-B boundary, i.e. a 16-B base and a row stride of a multiple of 8 elements
-bool rows_vec_ok(const bf16_t *src, int64_t sh, int64_t sw, int rows) {
-    return sw == 1 && (sh % 8 == 0 || rows == 1) && (reinterpret_cast<uintptr_t>(src) % 16 == 0);
+// every row must start on a 16-B boundary: a 16-B base and a row stride of a multiple of 16 / sizeof(element)
+template <typename SrcT>
+bool rows_vec_ok(const SrcT *src, int64_t sh, int64_t sw, int rows) {
+    return sw == 1 && (sh % (int64_t)(16 / sizeof(SrcT)) == 0 || rows == 1) && (reinterpret_cast<uintptr_t>(src) % 16 == 0);
 }
 
 bool cols_vec_ok(const float *src, int64_t sh, int cols) {
     return (cols % 4 == 0) && (sh % 4 == 0) && (reinterpret_cast<uintptr_t>(src) % 16 == 0);
 }
 
-int rows_regs(int len) {  // float4 chunks per lane -> register-resident variant (-1 = block per row, 0 = streaming)
-    const int per_lane = ((len >> 2) + 63) / 64;
-    if (per_lane > 16) return len <= kLongRowMax ? -1 : 0;
+// The row kernel for rows of `len` elements read in 16-B chunks of chunk_elems: the chunks per lane of the
+// register-resident one-wave-per-row kernels (1, 2, 4, 8 or 16), -1 = block per row (len <= block_row_max), 0 =
+// streaming.  One wave per row ends at kWaveRowMax elements whatever the source type -- 16 chunks per lane of floats,
+// 8 of bf16 -- because the 8- and 16-row forms stage the packed rows in LDS rows of kStageRowWordsMax words; k_pad, a
+// multiple of kKPad, is <= kWaveRowMax exactly when len is.
+static_assert(kWaveRowMax % kKPad == 0 && kStageRowWordsMax == kWaveRowMax / 4 + 16, "the staged rows hold k_pad <= kWaveRowMax");
+static_assert(kWaveRowMax <= 16 * 64 * RowSrc<float>::kElems, "R = 16 is the widest one-wave-per-row kernel");
+int rows_regs(int len, int chunk_elems = RowSrc<float>::kElems, int block_row_max = RowSrc<float>::kBlockRowMax) {
+    if (len > kWaveRowMax) return len <= block_row_max ? -1 : 0;
+    const int per_lane = (len / chunk_elems + 63) / 64;
     return per_lane <= 1 ? 1 : per_lane <= 2 ? 2 : per_lane <= 4 ? 4 : per_lane <= 8 ? 8 : 16;
-}
-
-// 16-B chunks per lane of a bf16 row (8 elements each).  The one-wave-per-row kernels end at 4096 elements -- 8 chunks
-// per lane -- because their 8-row form stages the packed rows in LDS rows of kStageRowWordsMax words (k_pad <= 4096),
-// whatever the source type; the block-per-row kernel's 16 chunks x 256 threads then reach 32 768 elements.
-int rows_regs_bf16(int len) {
-    if (len > 4096) return len <= kLongRowMaxBf16 ? -1 : 0;
-    const int per_lane = ((len >> 3) + 63) / 64;
-    return per_lane <= 1 ? 1 : per_lane <= 2 ? 2 : per_lane <= 4 ? 4 : 8;
 }
 
 template <typename SrcT>
 hipError_t launch_pack_rows_t(const SrcT *src, int64_t sh, int64_t sw, int rows, int len, float range, PackedView out,
                               hipStream_t stream) {
-    constexpr bool kF32 = std::is_same<SrcT, float>::value;
+    typedef RowSrc<SrcT> T;
     const dim3 grid((unsigned)(out.rows_pad / 4)), block(256);
     if (!rows_vec_ok(src, sh, sw, rows)) {
         pack_rows_generic_kernel<<<grid, block, 0, stream>>>(src, sh, sw, rows, len, range, out.scale, out.q,
@@ -1380,7 +1216,7 @@ hipError_t launch_pack_rows_t(const SrcT *src, int64_t sh, int64_t sw, int rows,
     else                                                                                                              \
         pack_rows_vec_kernel<Rv><<<(Rv) > 0 ? (unsigned)(out.rows_pad / 8) : grid.x, (Rv) > 0 ? 512 : 256, 0, stream>>>( \
             src, sh, rows, len, range, out.scale, out.q, out.rows_pad, out.k_pad)
-    const int regs = kF32 ? rows_regs(len) : rows_regs_bf16(len);
+    const int regs = rows_regs(len, T::kElems, T::kBlockRowMax);
     if (regs < 0) {
         pack_rows_block_kernel<<<(unsigned)out.rows_pad, 256, 0, stream>>>(src, sh, rows, len, range, out.scale, out.q,
                                                                            out.rows_pad, out.k_pad);
@@ -1392,7 +1228,7 @@ hipError_t launch_pack_rows_t(const SrcT *src, int64_t sh, int64_t sw, int rows,
         case 4: QG_ROWS(4); break;
         case 8: QG_ROWS(8); break;
         case 16:
-            if constexpr (kF32) { QG_ROWS(16); }  // bf16 rows stop at 8 chunks per lane
+            if constexpr (kWaveRowMax > 8 * 64 * T::kElems) { QG_ROWS(16); }  // bf16 rows stop at 8 chunks per lane
             break;
         default: QG_ROWS(0); break;
     }

@@ -144,7 +144,7 @@ def _check_pack(qg, oracle, device, xb_view_dev, xw, what, packed=None):
     assert not pa.scale[M:].cpu().numpy().any(), f"{what}: padding scales not zero"
 
 
-# K: the issue's list, plus the value on each side of every boundary of the bf16 dispatch (pack.hip rows_regs_bf16):
+# K: the issue's list, plus the value on each side of every boundary of the bf16 dispatch (pack.hip rows_regs):
 # 8-element chunks per lane 1 | 2 | 4 | 8 at 519|520, 1031|1032, 2055|2056; one wave per row | block per row at
 # 4096|4097; block per row | streaming at 32768|32769
 PACK_K = [1, 2, 7, 8, 9, 255, 256, 264, 1000, 4096, 4104, 5003, 16384, 16392, 40000,

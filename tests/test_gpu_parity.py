@@ -78,6 +78,43 @@ def test_seeded_fixtures(qg, oracle, device):
         _check_intermediates(qg, X, W, ref, device, rec["name"])
 
 
+def _check_pack_a(qg, oracle, device, X, what):
+    """pack_a of fp32 X: scale[:M], q[:M, :K] against the oracle's Cx / Xq; padding rows, columns and scales zero."""
+    M, K = X.shape
+    _, ref = oracle.quantized_mm(X, np.ones((K, 1), np.float32), intermediates=True)
+    pa = qg.pack_a(_dev(X, device))
+    torch.cuda.synchronize()
+    assert_values_equal(pa.scale[:M].cpu().numpy(), ref["Cx"], f"{what} Cx")
+    q = pa.q.cpu().numpy()
+    assert (q[:M, :K] == ref["Xq"]).all(), f"{what} Xq: {int((q[:M, :K] != ref['Xq']).sum())} bytes differ"
+    assert not q[M:].any() and not q[:, K:].any(), f"{what}: padding not zero"
+    assert not pa.scale[M:].cpu().numpy().any(), f"{what}: padding scales not zero"
+
+
+# K on both sides of every boundary of the fp32 row dispatch (pack.hip rows_regs): float4 chunks per lane 1 | 2 | 4 | 8 |
+# 16 at 259|260, 515|516, 1027|1028, 2051|2052; one wave per row | block per row at 4096|4097 (4099|4100: the last
+# length whose 1024 whole chunks still fit 16 per lane); block per row | streaming at 16384|16385; tails and tiny rows
+PACK_A_K = [259, 260, 515, 516, 1027, 1028, 2051, 2052, 4096, 4097, 4099, 4100, 16384, 16385, 1, 2, 3, 5, 4104]
+
+
+@pytest.mark.parametrize("K", PACK_A_K)
+def test_pack_a_fp32_intermediates(qg, oracle, device, K):
+    """M = 300 pads to fewer than 2048 rows: the two-rows-per-block kernels."""
+    for M in (1, 9, 300):
+        X = oracle.uniform((M, K), 5000 + K + M, -2.0, 2.0)
+        X[::4, 0] = -2.5  # signed seed of the largest magnitude (absmax quirk, int8 saturation)
+        _check_pack_a(qg, oracle, device, X, f"pack_a {M}x{K}")
+
+
+@pytest.mark.parametrize("K", [512, 4096, 4097, 4099])
+def test_pack_a_fp32_staged_rows(qg, oracle, device, K):
+    """2048 padded rows: the 8-rows-per-block form that stages the packed rows in LDS takes K <= 4096; 4097 and
+    4099 pad to k_pad = 4224, past a staged row, and belong to the block-per-row kernel."""
+    M = 2048
+    X = oracle.uniform((M, K), 6000 + K, -2.0, 2.0)
+    _check_pack_a(qg, oracle, device, X, f"pack_a staged {M}x{K}")
+
+
 @pytest.mark.parametrize("M,N,K", [(512, 768, 384), (1000, 300, 1030), (64, 4096, 256), (2048, 2048, 2048),
                                    (64, 96, 5003), (33, 40, 16384), (300, 64, 8191),   # long rows: block per row
                                    (40, 72, 40000), (9, 24, 70001)])                   # past 16384: streaming rows
@@ -206,11 +243,12 @@ def test_256_tile_kernel_ragged_shapes(qg, oracle, device, M, N, K):
     assert_bits_equal(_run_full(qg, X, W, device), oracle.quantized_mm(X, W), f"{M}x{N}x{K}")
 
 
-@pytest.mark.parametrize("M,N,K", [(300, 1000, 5000), (257, 4104, 8193), (64, 520, 16384), (512, 2048, 12289)])
+@pytest.mark.parametrize("M,N,K", [(300, 1000, 5000), (257, 4104, 8193), (64, 520, 16384), (512, 2048, 12289),
+                                   (64, 96, 4098), (300, 520, 4099)])
 def test_long_k_drop_in(qg, oracle, device, M, N, K):
     """4096 < K <= 16384, row-major operands (the two-pass column pack of W and the fused X-row pass) -- ragged K,
-    the largest K, padding rows of the packed W (N not a multiple of 256), signed-seed quirk rows and columns;
-    every output bit."""
+    the largest K, the shortest (4098, 4099: 1024 whole float4 chunks and a tail), padding rows of the packed W
+    (N not a multiple of 256), signed-seed quirk rows and columns; every output bit."""
     X, W = oracle.inputs(M, N, K, 151)
     W[0, ::5] = -1.75  # those columns' signed seed (absmax quirk)
     X[::7, 0] = -1.5
