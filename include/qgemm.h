@@ -52,7 +52,13 @@ QGEMM_API int op_mm_quantize(const float *A, const float *B, float *C, int m, in
 /* Strided form: element (r, c) of a matrix lives at ptr[r*stride_h + c*stride_w], exactly the
  * reference's Index() macro (tensor.cuh:14), so transposed views (tensor.cuh:121-133) work.
  * range is the reference's `range` argument (127 at every reference call site). stream is a
- * hipStream_t (NULL = null stream). */
+ * hipStream_t (NULL = null stream).
+ * range, wherever an entry point takes it: a finite positive float, not checked.  It scales the operands by
+ * fl(range / absmax) before the cast to int8, and the cast saturates, so with range > 127 every element past
+ * 127 / range of its row's (column's) absmax becomes -128 or 127; the output is multiplied by
+ * fl(1 / fl(range * range)), which is +0 once range * range overflows.  The GEMM must be given the range its
+ * operands were packed with.  The prepacked drop-in and the linear entry points (op_mm_quantize_prepacked*,
+ * qgemm_linear*) take no range: they are fixed at 127. */
 QGEMM_API int op_mm_quantize_ex(const float *A, int64_t a_stride_h, int64_t a_stride_w,
                       const float *B, int64_t b_stride_h, int64_t b_stride_w,
                       float *C, int64_t c_stride_h, int64_t c_stride_w,
