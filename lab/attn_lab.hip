@@ -1,11 +1,12 @@
 // attn_lab.hip -- development harness (not part of the library): times the fused attention kernel and
-// its phase ablations (kSkip) at the encoder's config-5 shape.  Build: make -C .. attnlab
+// its phase ablations and stamps (kSkip, put back into a generated copy of the product file by make_attn_skip.py)
+// at the encoder's config-5 shape.  Build: make -C lab attn_lab
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
 #include <algorithm>
 
-#include "../quantized-gemm-for-transformer-inference_amd/csrc/attention.hip"
+#include "attention_skip.hip"
 
 using namespace qgemm;
 

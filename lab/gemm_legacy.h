@@ -179,6 +179,21 @@ __device__ __forceinline__ void epilogue(const GemmArgs &p, int8_t *lds, v16i (&
 
 enum V2Flags { kPrio = 1, kNoGlds = 2, kNoLdsRead = 4, kNoBarrier = 8, kNoVmWait = 16, kNoSlab = 32 /* lab ablation */ };
 
+// kNoSlab: the ticket protocol of splitk_combine (csrc/gemm_i8_kernels.h) without its slab stores and loads -- what
+// the slab round trip costs (gemm_lab's S2_noslab / S4_noslab; the results are wrong by construction)
+__device__ __forceinline__ bool splitk_tickets_only(const GemmArgs &p, unsigned *last, int tile, int S, int tid) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (tid == 0) {
+        const unsigned t = __hip_atomic_fetch_add(p.tickets + tile, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        *last = t;
+        if (t == (unsigned)(S - 1) && p.reset_tickets)
+            __hip_atomic_store(p.tickets + tile, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __syncthreads();
+    return *last == (unsigned)(S - 1);
+}
+
 // ------------------------------------------------------------------------------------------------
 // v1: stage(kt+1) ; compute(kt) with just-in-time fragment reads ; vmcnt(0) ; barrier
 template <int kMode, bool kDequant>
@@ -555,10 +570,12 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_i8_v3(GemmArgs p) {
         mfmas(a1, b1);
     }
 
-    if (S > 1 &&
-        !splitk_combine<8, 4, 8, !(kFlags & kNoSlab)>(p, reinterpret_cast<unsigned *>(lds + kEpiBase), acc, tile, slice,
-                                                     S, wave, lane, tid))
-        return;
+    if (S > 1) {
+        unsigned *last = reinterpret_cast<unsigned *>(lds + kEpiBase);
+        const bool reducer = (kFlags & kNoSlab) ? splitk_tickets_only(p, last, tile, S, tid)
+                                                : splitk_combine<8, 4, 8>(p, last, acc, tile, slice, S, wave, lane, tid);
+        if (!reducer) return;
+    }
     epilogue16<kMode, kEpi>(p, lds, acc, tm, tn, wm, wn, lane, tid);
 }
 

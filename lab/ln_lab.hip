@@ -1,12 +1,15 @@
 // ln_lab.hip -- development check (not part of the library): add+layernorm with and without the fused
-// pack must give identical Y; prints mismatch counts.  Build: make -C .. lnlab
+// pack must give identical Y; prints mismatch counts.  Then the product register kernel bit-compared and timed
+// against the general kernel and the superseded layouts of ln_legacy.h, and its phase stamps (kStamp, put into a
+// generated copy of the product file by make_ln_stamp.py).  Build: make -C lab ln_lab
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
 #include <algorithm>
 
-#include "../quantized-gemm-for-transformer-inference_amd/csrc/encoder_ops.hip"
+#include "encoder_ops_stamp.hip"
+#include "ln_legacy.h"
 
 using namespace qgemm;
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP %s at %d\n", hipGetErrorString(e_), __LINE__); exit(1); } } while (0)
@@ -84,13 +87,13 @@ int main(int argc, char **argv) {
                same(v.q, v2.q, v.rows_pad * v.k_pad), same(v.scale, v2.scale, v.rows_pad * 4));
         hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
         if (w <= 1024) {  // the LDS-walking chain in the same register-resident kernel
-            add_layernorm_rows_vec_kernel<true, 4, 0, false, false><<<(unsigned)((v2.rows_pad + 3) / 4), 256, sizeof(float) * 4 * w>>>(A, B, Y3, rows, w, v2.q, v2.scale, v2.k_pad, v2.rows_pad, 127.0f);
+            ln_legacy::add_layernorm_rows_vec_kernel<true, 4, false><<<(unsigned)((v2.rows_pad + 3) / 4), 256, sizeof(float) * 4 * w>>>(A, B, Y3, rows, w, v2.q, v2.scale, v2.k_pad, v2.rows_pad, 127.0f);
             CK(hipDeviceSynchronize());
             printf("hop chain vs LDS chain: Y %s  q %s  scale %s\n", same(Y2, Y3, (size_t)rows * w * 4),
                    same(v.q, v2.q, v.rows_pad * v.k_pad), same(v.scale, v2.scale, v.rows_pad * 4));
         }
         if (w <= 1024) {  // the round-3..6 interleaved layout (one hop per 4 elements)
-            add_layernorm_rows_vec_kernel<true, 4, 0, true, false><<<(unsigned)((v2.rows_pad + 3) / 4), 256, 0>>>(A, B, Y3, rows, w, v2.q, v2.scale, v2.k_pad, v2.rows_pad, 127.0f);
+            ln_legacy::add_layernorm_rows_vec_kernel<true, 4, true><<<(unsigned)((v2.rows_pad + 3) / 4), 256, 0>>>(A, B, Y3, rows, w, v2.q, v2.scale, v2.k_pad, v2.rows_pad, 127.0f);
             CK(hipDeviceSynchronize());
             printf("block hops vs interleaved hops: Y %s  q %s  scale %s\n", same(Y2, Y3, (size_t)rows * w * 4),
                    same(v.q, v2.q, v.rows_pad * v.k_pad), same(v.scale, v2.scale, v.rows_pad * 4));
@@ -102,8 +105,8 @@ int main(int argc, char **argv) {
             for (int it = 0; it < 30; ++it) {
                 CK(hipEventRecord(e0));
                 if (var == 0) CK(launch_add_layernorm_rows_pack(A, B, Y2, rows, w, 127.0f, v, nullptr));
-                else if (var == 3) add_layernorm_rows_vec_kernel<true, 4, 0, true, false><<<(unsigned)((v2.rows_pad + 3) / 4), 256, 0>>>(A, B, Y3, rows, w, v2.q, v2.scale, v2.k_pad, v2.rows_pad, 127.0f);
-                else if (var == 2) add_layernorm_rows_vec_kernel<true, 4, 0, false, false><<<(unsigned)((v2.rows_pad + 3) / 4), 256, sizeof(float) * 4 * w>>>(A, B, Y3, rows, w, v2.q, v2.scale, v2.k_pad, v2.rows_pad, 127.0f);
+                else if (var == 3) ln_legacy::add_layernorm_rows_vec_kernel<true, 4, true><<<(unsigned)((v2.rows_pad + 3) / 4), 256, 0>>>(A, B, Y3, rows, w, v2.q, v2.scale, v2.k_pad, v2.rows_pad, 127.0f);
+                else if (var == 2) ln_legacy::add_layernorm_rows_vec_kernel<true, 4, false><<<(unsigned)((v2.rows_pad + 3) / 4), 256, sizeof(float) * 4 * w>>>(A, B, Y3, rows, w, v2.q, v2.scale, v2.k_pad, v2.rows_pad, 127.0f);
                 else add_layernorm_rows_kernel<true><<<(unsigned)((v2.rows_pad + 3) / 4), 256, lds>>>(A, B, Y3, rows, w, v2.q, v2.scale, v2.k_pad, v2.rows_pad, 127.0f);
                 CK(hipEventRecord(e1)); CK(hipEventSynchronize(e1));
                 float ms; CK(hipEventElapsedTime(&ms, e0, e1)); ts.push_back(ms * 1000);
@@ -116,9 +119,8 @@ int main(int argc, char **argv) {
     // phase stamps (s_memrealtime, 100 MHz) of the fused kernel, medians over rows
     {
         PackedView v = packed_view(pk, rows, w);
-        const size_t lds = sizeof(float) * 4 * ((w + 3) & ~3);
         for (int it = 0; it < 5; ++it)
-            add_layernorm_rows_vec_kernel<true, 4, 1><<<(unsigned)((v.rows_pad + 3) / 4), 256, lds>>>(A, B, Y2, rows, w, v.q, v.scale, v.k_pad, v.rows_pad, 127.0f);
+            add_layernorm_rows_vec_kernel<true, 4, 1><<<(unsigned)((v.rows_pad + 3) / 4), 256, 0>>>(A, B, Y2, rows, w, v.q, v.scale, v.k_pad, v.rows_pad, 127.0f);
         CK(hipDeviceSynchronize());
         static unsigned long long st[4096][8];
         CK(hipMemcpyFromSymbol(st, HIP_SYMBOL(g_ln_stamp), sizeof(st)));

@@ -44,10 +44,7 @@ struct AttnTile {
 
 typedef float v4f __attribute__((ext_vector_type(4)));
 
-// kSkip (lab ablation only; 0 in the library): 1 = no QK^T MFMAs, 2 = no softmax, 4 = no PV MFMAs,
-// 8 = no sequential sums, 16 = s_memrealtime stamps at the phase boundaries (g_attn_stamp)
-__device__ unsigned long long g_attn_stamp[4096][8];
-template <int kTQ, int kChunk, int kThreads, int kSkip = 0>
+template <int kTQ, int kChunk, int kThreads>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))) void attention_fused_kernel(
     const float *__restrict__ qkv, int d, int dk, int seq, float scale, float *__restrict__ heads) {
     using T = AttnTile<kTQ, kChunk, kThreads>;
@@ -69,12 +66,6 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
     const int nchunks = (seq + kChunk - 1) / kChunk;
     const int seq32 = (seq + 31) & ~31;  // the reference's k extent for P V: seq zero-padded to its 32-wide tile
     const int dk4 = (dk + 3) >> 2;  // float4 columns of a K / V row (the last one zero-padded)
-    const int bid = blockIdx.y * gridDim.x + blockIdx.x;
-    auto stamp = [&](int i) __attribute__((always_inline)) {
-        if constexpr ((kSkip & 16) != 0)
-            if (t == 0) g_attn_stamp[bid & 4095][i] = __builtin_amdgcn_s_memrealtime();
-    };
-    stamp(0);
 
     // K / V chunks as float4 pieces, kPer per thread, fetched into registers one chunk ahead -- chunk
     // c+1's global loads are in flight under chunk c's MFMAs, V chunk 0's under the last QK chunk and
@@ -137,7 +128,6 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
             for (int rf = 0; rf < kRF; ++rf)
 #pragma unroll
                 for (int s = 0; s < 16; ++s) qa[rf][s] = Qs[(rf * 16 + lr) * kQStride + 4 * s + lk];
-            stamp(1);
         }
         const int col = c * kChunk + wave * 16 + lr;
         if (c * kChunk + wave * 16 < seq) {
@@ -159,10 +149,8 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
                     for (int rf = 0; rf < kRF; ++rf)
                         acc[rf] = __builtin_amdgcn_mfma_f32_16x16x4f32(qa[rf][s], kb[s], acc[rf], 0, 0, 0);
             };
-            if (!(kSkip & 1)) {
-                if (ns32 == 16) steps(std::integral_constant<int, 16>());
-                else steps(std::integral_constant<int, 8>());
-            }
+            if (ns32 == 16) steps(std::integral_constant<int, 16>());
+            else steps(std::integral_constant<int, 8>());
             if (col < seq) {
 #pragma unroll
                 for (int rf = 0; rf < kRF; ++rf)
@@ -172,12 +160,11 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
         }
     }
     __syncthreads();
-    stamp(2);
 
     // ---- softmax of rows 2w and 2w+1: max and exp across the lanes, the two sequential sums at once
     // (lanes 0 and 1), the division across the lanes -- all through the LDS row (keeping the scaled
     // scores and exps in registers instead measured 1 us slower per launch)
-    for (int rr = 0; rr < 2 && !(kSkip & 2); ++rr) {
+    for (int rr = 0; rr < 2; ++rr) {
         const int rl = wave * 2 + rr;
         if (rl >= rows) break;
         float *srow = S + rl * kSStride;
@@ -197,38 +184,33 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
     }
     __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): this wave's exps are in LDS
     __builtin_amdgcn_wave_barrier();
-    stamp(6);
     // the two sums at once, each hopping lane to lane (hop_left): row 2w in lanes 0-31, row 2w+1 in lanes
     // 32-63, lane h of a half holding elements 16h .. 16h+15 of its row in registers; after step t the
     // chain through lane h = t - 1 of each half sits in that lane (lane 32 starts from lane 31's initial
     // zero; both halves run the same instructions).  Elements past seq are -0.0f, which leaves any sum
     // unchanged, so the last lane's 16 adds stay uniform.  Per element one dependent add, no LDS reads
     // inside the chain (the LDS-walking form exposed one read latency per 64 elements).
-    float sum_a = 0.0f, sum_b = 0.0f;
-    if (!(kSkip & 8)) {
-        const int hl = lane & 31, nl = (seq + 15) >> 4;  // lanes per half that hold elements (nl <= 32)
-        const float *srow = S + (wave * 2 + (lane >> 5)) * kSStride + 16 * hl;
-        float e[16];
+    const int hl = lane & 31, nl = (seq + 15) >> 4;  // lanes per half that hold elements (nl <= 32)
+    const float *erow = S + (wave * 2 + (lane >> 5)) * kSStride + 16 * hl;
+    float e[16];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (hl < nl && wave * 2 + (lane >> 5) < rows) v = *reinterpret_cast<const float4 *>(srow + 4 * j);
-            e[4 * j] = v.x; e[4 * j + 1] = v.y; e[4 * j + 2] = v.z; e[4 * j + 3] = v.w;
-        }
-#pragma unroll
-        for (int j = 0; j < 16; ++j)
-            if (16 * hl + j >= seq) e[j] = -0.0f;
-        float s = 0.0f;
-        for (int t = 0; t < nl; ++t) {
-            s = __fadd_rn(hop_left(s), e[0]);
-#pragma unroll
-            for (int j = 1; j < 16; ++j) s = __fadd_rn(s, e[j]);
-        }
-        sum_a = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s), nl - 1));
-        sum_b = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s), 32 + nl - 1));
+    for (int j = 0; j < 4; ++j) {
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (hl < nl && wave * 2 + (lane >> 5) < rows) v = *reinterpret_cast<const float4 *>(erow + 4 * j);
+        e[4 * j] = v.x; e[4 * j + 1] = v.y; e[4 * j + 2] = v.z; e[4 * j + 3] = v.w;
     }
-    stamp(7);
-    for (int rr = 0; rr < 2 && !(kSkip & 2); ++rr) {
+#pragma unroll
+    for (int j = 0; j < 16; ++j)
+        if (16 * hl + j >= seq) e[j] = -0.0f;
+    float s = 0.0f;
+    for (int t = 0; t < nl; ++t) {
+        s = __fadd_rn(hop_left(s), e[0]);
+#pragma unroll
+        for (int j = 1; j < 16; ++j) s = __fadd_rn(s, e[j]);
+    }
+    const float sum_a = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s), nl - 1));
+    const float sum_b = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s), 32 + nl - 1));
+    for (int rr = 0; rr < 2; ++rr) {
         const int rl = wave * 2 + rr;
         const float srr = rr == 0 ? sum_a : sum_b;
         if (rl >= rows) break;
@@ -248,12 +230,10 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
     v4f acc = {0.f, 0.f, 0.f, 0.f};
     for (int c = 0; c < nchunks; ++c) {
         __syncthreads();  // P complete (c = 0) / the previous V chunk consumed
-        if (c == 0) stamp(3);
         put(pf, kVStride);
         __syncthreads();
-        if (c == 0) stamp(4);
         if (c + 1 < nchunks) fetch(pf, Vb, (c + 1) * kChunk);
-        if (pv_wave && !(kSkip & 4)) {
+        if (pv_wave) {
             // k-steps over the reference's zero-padded extent (seq rounded up to 32: P and V are zero
             // past seq, so those steps are its padded tile's +0 adds), in groups of 8 -- a whole number
             // of groups per chunk, no per-step conditions; group g+1's operands are read from LDS while
@@ -282,7 +262,6 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
             }
         }
     }
-    stamp(5);
     if (pv_wave && col < dk) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {

@@ -4,8 +4,13 @@
 //
 // The reference runs one THREAD per row with sequential fp32 sums.  Here one WAVE per row: the
 // elementwise parts run across the lanes, and each sum stays ONE sequential fp32 chain in element
-// order (the row is staged in LDS and every lane walks it), so the results keep the reference's
-// rounding sequence.  Decisions where the reference is not defined precisely (encoder):
+// order, so the results keep the reference's rounding sequence.  Two forms of that chain:
+//   seq_sum        the row is staged in LDS and every lane walks it (the softmax, and add+layernorm
+//                  for rows the register kernel does not take: w % 4 != 0 or unaligned);
+//   lane_block_sum the row stays in registers, 4 kV consecutive elements per lane, and the running
+//                  sum hops from lane to lane (add+layernorm, w % 4 == 0: every encoder shape).
+// The superseded register layouts (LDS walk, one hop per 4 elements) are in lab/ln_legacy.h.
+// Decisions where the reference is not defined precisely (encoder):
 //   exp    : correctly rounded fp32 exp, fl32(exp((double)x)) (CUDA's expf is within 2 ulp, host
 //            expf differs again; the oracle uses the same definition)
 //   pow(d,2): fl32(d * d) (CUDA's float pow(float, int) overload)
@@ -48,47 +53,17 @@ __device__ __forceinline__ float seq_sum(const float *row, int w) {
     return sum;
 }
 
-// The same sequential fp32 sum over a row held in registers: element 4(l + 64 i) + c is x[i].c of lane l
-// (the layout of add_layernorm_rows_vec_kernel), w4 = w / 4 float4 columns.  The running sum hops from
-// lane to lane: every step is one v_add_f32 whose first operand is the LEFT neighbour's sum (DPP
-// wave_ror:1: lane l reads lane l - 1, lane 0 reads lane 63), then three in-lane adds.  Every lane runs
-// every step, so after step t of group i lane t - 1 holds the chain through its own four elements
-// (induction: each step extends the chain that had reached the left neighbour one step earlier), and lane 63
-// hands a full group on to lane 0 of the next.  Per element one dependent add and no LDS round trip: the
-// LDS-walking chain (seq_sum) spends ~7-8 cycles per element waiting on its ds_read groups.  The result is
-// the sum in lane (w4 - 1) mod 64, broadcast.
-__device__ __forceinline__ float hop_step(float s, const float4 &v) {
-    s = __fadd_rn(hop_left(s), v.x);
-    s = __fadd_rn(s, v.y);
-    s = __fadd_rn(s, v.z);
-    return __fadd_rn(s, v.w);
-}
-template <int kV>
-__device__ __forceinline__ float lane_chain_sum(const float4 (&x)[kV], int w4) {
-    float s = 0.0f;
-    int last = 63;
-#pragma unroll
-    for (int i = 0; i < kV; ++i) {
-        const int n = w4 - 64 * i < 64 ? w4 - 64 * i : 64;
-        if (n <= 0) break;
-        int t = 0;
-        for (; t + 8 <= n; t += 8) {
-#pragma unroll
-            for (int u = 0; u < 8; ++u) s = hop_step(s, x[i]);
-        }
-        for (; t < n; ++t) s = hop_step(s, x[i]);
-        last = n - 1;
-    }
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s), last));
-}
-
-// The same chain over the block layout: lane l holds the kV consecutive float4 columns kV l .. kV l + kV - 1
-// (elements 4 kV l .. 4 kV (l + 1) - 1), so the running sum hops once per 4 kV elements instead of once per 4:
-// step t is one v_add_f32 on the left neighbour's sum, then 4 kV - 1 in-lane adds, and after step t lane t - 1
-// holds the chain through its own block (the induction of lane_chain_sum).  nl = the lanes that hold elements
-// (<= 64); elements past the row must be -0.0f (x + -0 == x for every x, -0 and NaN included), so the last
-// lane's adds stay uniform.  Each hop costs the DPP read's wait states on top of its add: 16-element blocks
-// spend ~4.5 cycles per element against ~6 for lane_chain_sum's 4.
+// The same sequential fp32 sum over a row held in registers (the layout of add_layernorm_rows_vec_kernel): lane l
+// holds the kV consecutive float4 columns kV l .. kV l + kV - 1 (elements 4 kV l .. 4 kV (l + 1) - 1).  The running
+// sum hops from lane to lane: step t is one v_add_f32 whose first operand is the LEFT neighbour's sum (hop_left,
+// DPP wave_ror:1: lane l reads lane l - 1), then 4 kV - 1 in-lane adds.  Every lane runs every step, so after step
+// t lane t - 1 holds the chain through its own block (induction: each step extends the chain that had reached the
+// left neighbour one step earlier).  nl = the lanes that hold elements (<= 64); the result is the sum in lane
+// nl - 1, broadcast.  Elements past the row must be -0.0f (x + -0 == x for every x, -0 and NaN included), so the
+// last lane's adds stay uniform.  Per element one dependent add and no LDS round trip: the LDS-walking chain
+// (seq_sum) spends ~7-8 cycles per element waiting on its ds_read groups.  Each hop costs the DPP read's wait
+// states on top of its add: 16-element blocks spend ~4.5 cycles per element against ~6 with one hop per 4
+// elements (lab/ln_legacy.h).
 template <int kV>
 __device__ __forceinline__ float block_step(float s, const float4 (&x)[kV]) {
     s = __fadd_rn(hop_left(s), x[0].x);
@@ -159,9 +134,7 @@ __global__ __launch_bounds__(64 * kRowWaves) void softmax_rows_kernel(const floa
 // s = fl(range / Cx), q = sat_i8(trunc(fl(y * s))) -- the same operations as pack_rows_vec_body, so
 // the packed row is bit-identical to packing Y afterwards.  Rows [rows, rows_pad) of the packed view
 // get zero bytes and a zero scale; columns [w, k_pad) zero bytes.
-// kStamp (lab only; 0 in the library): s_memrealtime stamps at the phase boundaries (g_ln_stamp)
-__device__ unsigned long long g_ln_stamp[4096][8];
-template <bool kPack, int kStamp = 0>
+template <bool kPack>
 __global__ __launch_bounds__(64 * kRowWaves) void add_layernorm_rows_kernel(const float *__restrict__ A,
                                                                             const float *__restrict__ B,
                                                                             float *__restrict__ Y, int64_t rows,
@@ -172,11 +145,6 @@ __global__ __launch_bounds__(64 * kRowWaves) void add_layernorm_rows_kernel(cons
     extern __shared__ __attribute__((aligned(16))) float stage[];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int64_t row = (int64_t)blockIdx.x * kRowWaves + wv;
-    auto stamp = [&](int i) __attribute__((always_inline)) {
-        if constexpr (kStamp != 0)
-            if (lane == 0 && row < 4096) g_ln_stamp[row][i] = __builtin_amdgcn_s_memrealtime();
-    };
-    stamp(0);
     if (kPack && row >= rows && row < rows_pad) {  // padding row of the packed view
         auto qrow = [&](int64_t c) __attribute__((always_inline)) -> uint32_t & { return *qword(q, row, 4 * c, k_pad); };  // fragment-major q
         for (int64_t c = lane; c < k_pad / 4; c += 64) qrow(c) = 0u;
@@ -190,10 +158,8 @@ __global__ __launch_bounds__(64 * kRowWaves) void add_layernorm_rows_kernel(cons
     for (int c = lane; c < w; c += 64) st[c] = __fadd_rn(a[c], b[c]);  // op_add (transformer.cu:58)
     __builtin_amdgcn_s_waitcnt(0xc07f);
     __builtin_amdgcn_wave_barrier();
-    stamp(1);
     const float fw = (float)w;                                 // "mean/w": int -> float
     const float mean = __fdiv_rn(seq_sum(st, w), fw);          // op_layernorm.cuh:15-19
-    stamp(2);
     __builtin_amdgcn_wave_barrier();
     // the squared deviations replace the row in LDS (each lane rewrites the columns it owns)
     for (int c = lane; c < w; c += 64) {
@@ -201,9 +167,7 @@ __global__ __launch_bounds__(64 * kRowWaves) void add_layernorm_rows_kernel(cons
     }
     __builtin_amdgcn_s_waitcnt(0xc07f);
     __builtin_amdgcn_wave_barrier();
-    stamp(3);
     const float var = __fdiv_rn(seq_sum(st, w), fw);           // :21-25
-    stamp(4);
     float cand = -INFINITY;
     __builtin_amdgcn_wave_barrier();
     for (int c = lane; c < w; c += 64) {                       // (x - mean) / var (:28), as written
@@ -214,7 +178,6 @@ __global__ __launch_bounds__(64 * kRowWaves) void add_layernorm_rows_kernel(cons
             if (c > 0) cand = fmaxf(cand, absmax_candidate(v));
         }
     }
-    stamp(5);
     if constexpr (kPack) {
 #pragma unroll
         for (int off = 32; off >= 1; off >>= 1) cand = fmaxf(cand, __shfl_xor(cand, off, 64));
@@ -232,32 +195,20 @@ __global__ __launch_bounds__(64 * kRowWaves) void add_layernorm_rows_kernel(cons
         }
         if (lane == 0) qscale[row] = cx;
     }
-    stamp(6);
 }
 
-// The same add + layernorm (+ pack) for rows of w % 4 == 0 floats, 16-B aligned: each lane holds kV float4
-// columns (columns 4j..4j+3 of float4 column j, layout below) in registers from the first load to the last
-// use, so neither the normalisation nor the pack re-reads A, B or LDS; each packed dword is one lane's four
-// columns.
-// kHop (the product): both sums hop lane to lane over the registers; false: staged in LDS and walked by
-// seq_sum (lab comparison).  kBlk (the product): lane l holds the float4 columns j = kV l + i (a block of 4 kV
-// consecutive elements, lane_block_sum: one hop per block, and each lane's packed dwords of a 16-element
-// block are one 16-B piece of the fragment-major row); false: j = lane + 64 i (lane_chain_sum, one hop per 4
-// elements; the round-3 to round-6 product, kept for the lab comparison)
-template <bool kPack, int kV, int kStamp = 0, bool kHop = true, bool kBlk = true>
+// The same add + layernorm (+ pack) for rows of w % 4 == 0 floats, 16-B aligned: lane l holds the kV float4
+// columns j = kV l + i (a block of 4 kV consecutive elements) in registers from the first load to the last use, so
+// neither the normalisation nor the pack re-reads A, B or LDS.  Both sums hop lane to lane over the registers
+// (lane_block_sum: one hop per block); each packed dword is one lane's four columns, and a lane's packed dwords of
+// a 16-element block are one 16-B piece of the fragment-major row.
+template <bool kPack, int kV>
 __global__ __launch_bounds__(64 * kRowWaves) void add_layernorm_rows_vec_kernel(
     const float *__restrict__ A, const float *__restrict__ B, float *__restrict__ Y, int64_t rows, int w,
     int8_t *__restrict__ q, float *__restrict__ qscale, int64_t k_pad, int64_t rows_pad, float range) {
-    static_assert(!kBlk || kHop, "the block layout has no LDS-walking form");
-    static_assert(!kBlk || kV % 4 == 0, "the block layout stores whole 16-B pieces of the packed row");
-    extern __shared__ __attribute__((aligned(16))) float stage[];
+    static_assert(kV % 4 == 0, "a lane stores whole 16-B pieces of the packed row");
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int64_t row = (int64_t)blockIdx.x * kRowWaves + wv;
-    auto stamp = [&](int i) __attribute__((always_inline)) {
-        if constexpr (kStamp != 0)
-            if (lane == 0 && row < 4096) g_ln_stamp[row][i] = __builtin_amdgcn_s_memrealtime();
-    };
-    stamp(0);
     if (kPack && row >= rows && row < rows_pad) {  // padding row of the packed view
         auto qrow = [&](int64_t c) __attribute__((always_inline)) -> uint32_t & { return *qword(q, row, 4 * c, k_pad); };  // fragment-major q
         for (int64_t c = lane; c < k_pad / 4; c += 64) qrow(c) = 0u;
@@ -268,61 +219,33 @@ __global__ __launch_bounds__(64 * kRowWaves) void add_layernorm_rows_vec_kernel(
     const int w4 = w >> 2;
     const float4 *a = reinterpret_cast<const float4 *>(A + row * w), *b = reinterpret_cast<const float4 *>(B + row * w);
     float4 *y = reinterpret_cast<float4 *>(Y + row * w);
-    float *st = stage + wv * w;
-    auto col = [&](int i) __attribute__((always_inline)) { return kBlk ? kV * lane + i : lane + 64 * i; };
-    const int nl = (w4 + kV - 1) / kV;  // kBlk: the lanes that hold elements
+    const int nl = (w4 + kV - 1) / kV;  // the lanes that hold elements
     float4 x[kV];
 #pragma unroll
     for (int i = 0; i < kV; ++i) {
-        const int j = col(i);
-        x[i] = kBlk ? make_float4(-0.0f, -0.0f, -0.0f, -0.0f) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        const int j = kV * lane + i;
+        x[i] = make_float4(-0.0f, -0.0f, -0.0f, -0.0f);  // past the row: the identity of the sum
         if (j < w4) {
             const float4 av = a[j], bv = b[j];
             x[i] = make_float4(__fadd_rn(av.x, bv.x), __fadd_rn(av.y, bv.y), __fadd_rn(av.z, bv.z),
                                __fadd_rn(av.w, bv.w));  // op_add (transformer.cu:58)
-            if constexpr (!kHop) reinterpret_cast<float4 *>(st)[j] = x[i];
         }
     }
-    if constexpr (!kHop) {
-        __builtin_amdgcn_s_waitcnt(0xc07f);
-        __builtin_amdgcn_wave_barrier();
-    }
-    stamp(1);
     const float fw = (float)w;
-    const float sum_x = kBlk ? lane_block_sum<kV>(x, nl) : kHop ? lane_chain_sum<kV>(x, w4) : seq_sum(st, w);
-    const float mean = __fdiv_rn(sum_x, fw);  // op_layernorm.cuh:15-19
-    stamp(2);
+    const float mean = __fdiv_rn(lane_block_sum<kV>(x, nl), fw);  // op_layernorm.cuh:15-19
     // the squared deviations, formed from the registers (a chain that formed them itself would carry the
     // sub -> mul latency on every add: measured 2x slower)
-    float var;
-    if constexpr (kHop) {
-        float4 d[kV];
+    float4 d[kV];
 #pragma unroll
-        for (int i = 0; i < kV; ++i) {
-            d[i] = make_float4(sq_dev(x[i].x, mean), sq_dev(x[i].y, mean), sq_dev(x[i].z, mean), sq_dev(x[i].w, mean));
-            if (kBlk && col(i) >= w4) d[i] = make_float4(-0.0f, -0.0f, -0.0f, -0.0f);  // past the row: the identity
-        }
-        stamp(3);
-        var = __fdiv_rn(kBlk ? lane_block_sum<kV>(d, nl) : lane_chain_sum<kV>(d, w4), fw);  // :21-25
-    } else {
-        __builtin_amdgcn_wave_barrier();
-#pragma unroll
-        for (int i = 0; i < kV; ++i) {
-            const int j = lane + 64 * i;
-            if (j < w4)
-                reinterpret_cast<float4 *>(st)[j] =
-                    make_float4(sq_dev(x[i].x, mean), sq_dev(x[i].y, mean), sq_dev(x[i].z, mean), sq_dev(x[i].w, mean));
-        }
-        __builtin_amdgcn_s_waitcnt(0xc07f);
-        __builtin_amdgcn_wave_barrier();
-        stamp(3);
-        var = __fdiv_rn(seq_sum(st, w), fw);                       // :21-25
+    for (int i = 0; i < kV; ++i) {
+        d[i] = make_float4(sq_dev(x[i].x, mean), sq_dev(x[i].y, mean), sq_dev(x[i].z, mean), sq_dev(x[i].w, mean));
+        if (kV * lane + i >= w4) d[i] = make_float4(-0.0f, -0.0f, -0.0f, -0.0f);  // past the row: the identity
     }
-    stamp(4);
+    const float var = __fdiv_rn(lane_block_sum<kV>(d, nl), fw);  // :21-25
     float cand = -INFINITY;
 #pragma unroll
     for (int i = 0; i < kV; ++i) {
-        const int j = col(i);
+        const int j = kV * lane + i;
         if (j < w4) {
             float4 v;                                                // (x - mean) / var (:28), as written
             v.x = __fdiv_rn(__fsub_rn(x[i].x, mean), var);
@@ -339,7 +262,6 @@ __global__ __launch_bounds__(64 * kRowWaves) void add_layernorm_rows_vec_kernel(
             }
         }
     }
-    stamp(5);
     if constexpr (kPack) {
 #pragma unroll
         for (int off = 32; off >= 1; off >>= 1) cand = fmaxf(cand, __shfl_xor(cand, off, 64));
@@ -352,45 +274,37 @@ __global__ __launch_bounds__(64 * kRowWaves) void add_layernorm_rows_vec_kernel(
         for (int i = 0; i < kV; ++i)
             pk[i] = (uint32_t)(quant_i8(x[i].x, sc) & 0xff) | ((uint32_t)(quant_i8(x[i].y, sc) & 0xff) << 8) |
                     ((uint32_t)(quant_i8(x[i].z, sc) & 0xff) << 16) | ((uint32_t)(quant_i8(x[i].w, sc) & 0xff) << 24);
-        if constexpr (kBlk) {
-            // dwords kV l + 4g .. + 3 = k 16 (kV l / 4 + g) .. + 15: one aligned 16-B piece of the row
+        // dwords kV l + 4g .. + 3 = k 16 (kV l / 4 + g) .. + 15: one aligned 16-B piece of the row
 #pragma unroll
-            for (int g = 0; g < kV / 4; ++g) {
-                const int j0 = col(4 * g);
-                if (j0 + 3 < w4) {
-                    *reinterpret_cast<uint4 *>(qword(q, row, 4 * j0, k_pad)) =
-                        make_uint4(pk[4 * g], pk[4 * g + 1], pk[4 * g + 2], pk[4 * g + 3]);
-                } else {
+        for (int g = 0; g < kV / 4; ++g) {
+            const int j0 = kV * lane + 4 * g;
+            if (j0 + 3 < w4) {
+                *reinterpret_cast<uint4 *>(qword(q, row, 4 * j0, k_pad)) =
+                    make_uint4(pk[4 * g], pk[4 * g + 1], pk[4 * g + 2], pk[4 * g + 3]);
+            } else {
 #pragma unroll
-                    for (int e = 0; e < 4; ++e)
-                        if (j0 + e < w4) qrow(j0 + e) = pk[4 * g + e];
-                }
+                for (int e = 0; e < 4; ++e)
+                    if (j0 + e < w4) qrow(j0 + e) = pk[4 * g + e];
             }
-        } else {
-#pragma unroll
-            for (int i = 0; i < kV; ++i)
-                if (col(i) < w4) qrow(col(i)) = pk[i];
         }
         for (int64_t c4 = w4 + lane; c4 < k_pad / 4; c4 += 64) qrow(c4) = 0u;  // padding columns
         if (lane == 0) qscale[row] = cx;
     }
-    stamp(6);
 }
 
 // register-resident path: w % 4 == 0, w <= 256 * kV (kV = 4, 8 or 16), 16-B aligned rows
 template <bool kPack>
 hipError_t launch_ln_vec(const float *A, const float *B, float *Y, int64_t rows, int w, int8_t *q, float *qscale,
                          int64_t k_pad, int64_t rows_pad, float range, int64_t grid_rows, hipStream_t stream) {
-    const size_t lds = 0;  // the sums run in registers (kHop)
     const unsigned grid = (unsigned)((grid_rows + kRowWaves - 1) / kRowWaves);
     if (w <= 1024)
-        add_layernorm_rows_vec_kernel<kPack, 4><<<grid, 64 * kRowWaves, lds, stream>>>(A, B, Y, rows, w, q, qscale, k_pad,
+        add_layernorm_rows_vec_kernel<kPack, 4><<<grid, 64 * kRowWaves, 0, stream>>>(A, B, Y, rows, w, q, qscale, k_pad,
                                                                                       rows_pad, range);
     else if (w <= 2048)
-        add_layernorm_rows_vec_kernel<kPack, 8><<<grid, 64 * kRowWaves, lds, stream>>>(A, B, Y, rows, w, q, qscale, k_pad,
+        add_layernorm_rows_vec_kernel<kPack, 8><<<grid, 64 * kRowWaves, 0, stream>>>(A, B, Y, rows, w, q, qscale, k_pad,
                                                                                       rows_pad, range);
     else
-        add_layernorm_rows_vec_kernel<kPack, 16><<<grid, 64 * kRowWaves, lds, stream>>>(A, B, Y, rows, w, q, qscale,
+        add_layernorm_rows_vec_kernel<kPack, 16><<<grid, 64 * kRowWaves, 0, stream>>>(A, B, Y, rows, w, q, qscale,
                                                                                        k_pad, rows_pad, range);
     return hipGetLastError();
 }

@@ -6,7 +6,8 @@
 //   op_dequantize + op_multiply    (two more M x N passes)
 // by one kernel that reads the packed int8 operands once per macro-tile and writes fp32 O once.
 #include <hip/hip_ext.h>
-#include <stdlib.h>
+
+#include <type_traits>
 
 #include "gemm_i8_kernels.h"
 
@@ -97,10 +98,6 @@ int gemm_plan_info(int m, int n, int k, int *tile, const char **kernel) {
 // One fixed ticket region at the start of every split-K scratch (splits happen only below 320 tiles):
 // shapes that share a library-owned scratch then never write slabs over each other's tickets.
 constexpr size_t kTicketBytes = 4096;
-static size_t ticket_bytes(int64_t tiles) {
-    (void)tiles;
-    return kTicketBytes;
-}
 
 size_t gemm_ticket_bytes(int m, int n, int k) { return gemm_plan(m, n, k).splits > 1 ? kTicketBytes : 0; }
 
@@ -110,7 +107,7 @@ size_t gemm_scratch_bytes(int m, int n, int k) {
     const int64_t tiles = (int64_t)g.tiles_m * g.tiles_n;
     // the 256-tile split (gemm_i8_fm, ticket-first) keeps ONE slab per tile; the small tiles one per slice
     const int slabs = g.tile == 256 ? 1 : g.splits;
-    return ticket_bytes(tiles) + (size_t)tiles * slabs * g.tile * g.tile * 4;
+    return kTicketBytes + (size_t)tiles * slabs * g.tile * g.tile * 4;
 }
 
 // zeroes the ticket region ahead of a split launch.  A kernel rather than hipMemsetAsync: inside a
@@ -121,10 +118,7 @@ __global__ __launch_bounds__(256) void zero_tickets_kernel(unsigned *__restrict_
     if (i < n) t[i] = 0u;
 }
 
-// 256 x 256 tiles: gemm_i8_fm (4 waves of 128 x 128, operands straight from the fragment-major packed
-// layout, no LDS in the main loop) for every plan -- unsplit, 2-way split-K and the LLM.int8() outlier
-// epilogue.  (The ping-pong kernel gemm_i8_pp of round 2 is in lab/gemm_legacy.h: the 256-tile plan splits
-// in two or not at all, so no shape reached it without an environment switch; VERDICT r03.)
+// every GEMM launch: the caller's timing events (set_gemm_events) go around exactly the kernel
 template <typename Launch>
 static hipError_t launch_timed(dim3 grid, dim3 block, hipStream_t stream, const GemmArgs &p, Launch kernel) {
     const GemmEvents ev = take_gemm_events();
@@ -139,8 +133,12 @@ static hipError_t launch_timed(dim3 grid, dim3 block, hipStream_t stream, const 
     return e;
 }
 
+// 256 x 256 tiles: gemm_i8_fm (4 waves of 128 x 128, operands straight from the fragment-major packed
+// layout, no LDS in the main loop) for every plan -- unsplit, 2-way split-K and the LLM.int8() outlier
+// epilogue.  (The ping-pong kernel gemm_i8_pp of round 2 is in lab/gemm_legacy.h: the 256-tile plan splits
+// in two or not at all, so no shape reached it without an environment switch; VERDICT r03.)
 template <int kEpi, bool kBf16 = false>
-static hipError_t launch_v3(const GemmArgs &p, dim3 grid, hipStream_t stream) {
+static hipError_t launch_fm(const GemmArgs &p, dim3 grid, hipStream_t stream) {
     if constexpr (kEpi != kEpiOutlier) {
         // ticket-first split-K, slice 0 = 31/64 of the k-steps (lab/t2_lab.hip, lab/c3d_lab.hip; profiles/
         // r04_splitfirst_*.log: FFN-down GEMM alone 110.5 -> 105.8 us, the whole drop-in call 284.7 -> 279.7 us)
@@ -153,53 +151,39 @@ static hipError_t launch_v3(const GemmArgs &p, dim3 grid, hipStream_t stream) {
 
 template <int TB, int kEpi, int kDepth, bool kBf16 = false>
 static hipError_t launch_small(const GemmArgs &p, dim3 grid, hipStream_t stream) {
-    const GemmEvents ev = take_gemm_events();
-    if ((ev.start || ev.stop) && g_event_mode == 0) {
-        hipExtLaunchKernelGGL((gemm_i8_small<TB, kEpi, kDepth, kBf16>), grid, dim3(SmallTile<TB, kDepth>::kThreads), 0, stream,
-                              ev.start, ev.stop, 0, p);
-        return hipGetLastError();
-    }
-    if (ev.start) (void)hipEventRecord(ev.start, stream);
-    gemm_i8_small<TB, kEpi, kDepth, kBf16><<<grid, dim3(SmallTile<TB, kDepth>::kThreads), 0, stream>>>(p);
-    hipError_t e = hipGetLastError();
-    if (ev.stop) (void)hipEventRecord(ev.stop, stream);
-    return e;
+    return launch_timed(grid, dim3(SmallTile<TB, kDepth>::kThreads), stream, p, gemm_i8_small<TB, kEpi, kDepth, kBf16>);
 }
 
-// the plan's kernel at the epilogue (none / bias / bias + relu) and output type asked for
+// the epilogue asked for (none / bias / bias + relu) as a compile-time constant: f(integral_constant<int, kEpi>)
+template <typename F>
+static hipError_t with_epilogue(const float *bias, bool relu, F f) {
+    if (!bias) return f(std::integral_constant<int, kEpiNone>());
+    return relu ? f(std::integral_constant<int, kEpiBiasRelu>()) : f(std::integral_constant<int, kEpiBias>());
+}
+
+// the plan's kernel at the epilogue and output type asked for
 template <bool kBf16>
 static hipError_t dispatch_dequant(const GemmPlan &g, const GemmArgs &p, dim3 grid, int64_t tiles, const float *bias,
                                    bool relu, hipStream_t stream) {
-    if (g.tile == 32) {
-        if (!bias) return launch_small<32, kEpiNone, 4, kBf16>(p, grid, stream);
-        return relu ? launch_small<32, kEpiBiasRelu, 4, kBf16>(p, grid, stream) : launch_small<32, kEpiBias, 4, kBf16>(p, grid, stream);
-    }
-    if (g.tile == 64) {
+    return with_epilogue(bias, relu, [&](auto epi) {
+        constexpr int kEpi = decltype(epi)::value;
+        if (g.tile == 32) return launch_small<32, kEpi, 4, kBf16>(p, grid, stream);
         // at most two 64-tiles per CU: a 3-stage ring (two k-steps in flight, three blocks per CU); more
         // tiles: the 2-stage ring, four blocks per CU (gemm_lab ... small, us: 512x1024x1024 6.10 -> 5.67,
         // 512x1024x4096 S2 10.73 -> 9.91, 512x3072x1024 7.43 -> 7.20; 2048^3 18.1 -> 22.3 with 3 stages)
-        if (tiles <= 512) {
-            if (!bias) return launch_small<64, kEpiNone, 3, kBf16>(p, grid, stream);
-            return relu ? launch_small<64, kEpiBiasRelu, 3, kBf16>(p, grid, stream) : launch_small<64, kEpiBias, 3, kBf16>(p, grid, stream);
-        }
-        if (!bias) return launch_small<64, kEpiNone, 2, kBf16>(p, grid, stream);
-        return relu ? launch_small<64, kEpiBiasRelu, 2, kBf16>(p, grid, stream) : launch_small<64, kEpiBias, 2, kBf16>(p, grid, stream);
-    }
-    if (!bias) return launch_v3<kEpiNone, kBf16>(p, grid, stream);
-    return relu ? launch_v3<kEpiBiasRelu, kBf16>(p, grid, stream) : launch_v3<kEpiBias, kBf16>(p, grid, stream);
+        if (g.tile == 64)
+            return tiles <= 512 ? launch_small<64, kEpi, 3, kBf16>(p, grid, stream)
+                                : launch_small<64, kEpi, 2, kBf16>(p, grid, stream);
+        return launch_fm<kEpi, kBf16>(p, grid, stream);
+    });
 }
 
 // First row stride (in bf16 elements) at which gemm_i8_fm's bf16 output leaves through the LDS image (and the 8-tile-row
 // XCD patches that go with it) instead of the exchanged register stores: 16 384, i.e. rows of 32 KiB -- half the
 // bytes of the fp32 switch point.  Measured at FFN up (2048 x 16384 x 4096, bf16 in and out, the whole call, same
 // process, alternated; profiles/bf16_store_paths.log): LDS image 108.2 us, register stores 114.1-114.2 us.  Narrower
-// rows are not measured and keep the register stores.  QGEMM_BF16_WIDE_MIN overrides it per call
-// (scripts/bf16_linear_probe.py --stores; 0 = always the image, a huge value = never).
+// rows are not measured and keep the register stores.
 constexpr int64_t kBf16WideRowsMin = 16384;
-static int64_t bf16_wide_rows_min() {
-    const char *e = getenv("QGEMM_BF16_WIDE_MIN");
-    return e && *e ? atoll(e) : kBf16WideRowsMin;
-}
 
 hipError_t launch_gemm_dequant(const PackedView &a, const PackedView &b, void *C, int64_t csh, int64_t csw, int m,
                                int n, float inv_r2, void *scratch, size_t scratch_bytes, hipStream_t stream,
@@ -213,15 +197,15 @@ hipError_t launch_gemm_dequant(const PackedView &a, const PackedView &b, void *C
     // segments, rotated per tile); its paired nontemporal register stores ran 122.6 vs 112.3 us there
     // (lab/ds_lab.hip) and plain ones left the output in the caches
     p.wide_rows = (csw == 1 && csh >= 16384) ? 1 : 0;
-    if (c_bf16) p.wide_rows = (csw == 1 && csh >= bf16_wide_rows_min()) ? 1 : 0;
+    if (c_bf16) p.wide_rows = (csw == 1 && csh >= kBf16WideRowsMin) ? 1 : 0;
     if (g.splits > 1 && scratch && scratch_bytes >= gemm_scratch_bytes(m, n, (int)a.k_pad)) {
         p.splits = g.splits;
         p.tickets = static_cast<unsigned *>(scratch);
-        p.slabs = reinterpret_cast<int32_t *>(static_cast<char *>(scratch) + ticket_bytes(tiles));
+        p.slabs = reinterpret_cast<int32_t *>(static_cast<char *>(scratch) + kTicketBytes);
         // the tickets are polled state: zeroed ahead of every launch unless the scratch is
         // library-owned, zeroed at allocation and re-zeroed by each launch's reducers
         if (!tickets_zeroed) {
-            const int nt = (int)(ticket_bytes(tiles) / sizeof(unsigned));
+            const int nt = (int)(kTicketBytes / sizeof(unsigned));
             zero_tickets_kernel<<<(nt + 255) / 256, 256, 0, stream>>>(p.tickets, nt);
             hipError_t e = hipGetLastError();
             if (e != hipSuccess) return e;
@@ -247,7 +231,7 @@ hipError_t launch_gemm_dequant_outlier(const PackedView &a, const PackedView &b,
     p.wide_rows = csh >= 16384 ? 1 : 0;
     p.xo_ld = xsh;
     p.ocols = ocols;
-    return launch_v3<kEpiOutlier>(p, dim3((unsigned)(g.tiles_m * g.tiles_n)), stream);
+    return launch_fm<kEpiOutlier>(p, dim3((unsigned)(g.tiles_m * g.tiles_n)), stream);
 }
 
 hipError_t launch_gemm_i32(const PackedView &a, const PackedView &b, int32_t *Acc, int m, int n, hipStream_t stream) {

@@ -104,7 +104,7 @@ __device__ __forceinline__ float epi_extra(float o, const float *sB, int jl) {
 // object can de-pipeline the main loop).  Returns true in the reducer, which then holds the complete
 // sums in acc.
 // MI x NI accumulator tiles per wave, kWaves waves: a slab is kWaves*MI*NI*64 v4i (= the tile's int32s).
-template <int MI, int NI, int kWaves, bool kSlab = true>
+template <int MI, int NI, int kWaves>
 __device__ __forceinline__ bool splitk_combine(const GemmArgs &p, unsigned *last, v4i (&acc)[MI][NI], int tile,
                                                int slice, int S, int wave, int lane, int tid) {
     constexpr int kSlabBytes = kWaves * MI * NI * 64 * 16;
@@ -116,8 +116,8 @@ __device__ __forceinline__ bool splitk_combine(const GemmArgs &p, unsigned *last
     for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
         for (int ni = 0; ni < NI; ++ni)
-            if constexpr (kSlab) __builtin_amdgcn_raw_buffer_store_b128(acc[mi][ni], rsrc, slice * kSlabBytes + lane_off + (mi * NI + ni) * 1024,
-                                                   0, 16 /* sc1 */);
+            __builtin_amdgcn_raw_buffer_store_b128(acc[mi][ni], rsrc, slice * kSlabBytes + lane_off + (mi * NI + ni) * 1024,
+                                                   0, 16 /* sc1 */);  // slab [slice] of this tile
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (tid == 0) {
@@ -131,7 +131,7 @@ __device__ __forceinline__ bool splitk_combine(const GemmArgs &p, unsigned *last
     if (*last != (unsigned)(S - 1)) return false;
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");  // compiler ordering only: loads stay below
     for (int s = 0; s < S; ++s) {
-        if (s == slice || !kSlab) continue;
+        if (s == slice) continue;
 #pragma unroll
         for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
@@ -593,12 +593,13 @@ __global__ __launch_bounds__(kFmThreads, 1) void gemm_i8_fm(GemmArgs p) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// gemm_i8_small<TB>: TB x TB macro-tiles (TB = 128 or 64) for problems with few 256 x 256 tiles (the
+// gemm_i8_small<TB>: TB x TB macro-tiles (TB = 64 or 32 in the library) for problems with few 256 x 256 tiles (the
 // encoder's M = 512 linears, decode-sized M): 4 waves as 2 x 2, each (TB/2) x (TB/2) = MI x MI tiles
 // of v_mfma_i32_16x16x64_i8, operands staged by LDS-DMA of whole 1-KiB fragment-major blocks (2-deep or
 // deeper ring), split-K by splitk_combine; the epilogue writes the whole TB x TB fp32 tile through
-// the ring at once.  TB = 128: 64-KiB ring, two blocks per CU; TB = 64: 32-KiB ring, four blocks per
-// CU -- four times the tiles, so shapes whose 128-tiles leave most CUs idle spread over the chip.
+// the ring at once.  TB = 64: 32-KiB ring, four blocks per CU; TB = 32: a 4-stage ring, for shapes with fewer
+// 64-tiles than CUs (gemm_plan).  TB = 128 (64-KiB ring, two blocks per CU) still instantiates and is timed by
+// lab/gemm_lab.hip only: it left most CUs idle at the shapes that come here.
 // kDepth > 2: a kDepth-stage ring with kDepth - 1 k-steps in flight (each k-step then waits for the
 // OLDEST stage only): these few-k-step GEMMs are bound by the LDS-DMA round trip, not by the MFMAs.
 template <int TB, int kDepth = 2>
@@ -615,10 +616,6 @@ struct SmallTile {
     static constexpr int kLoadsPerStage = 2 * kPieces;  // LDS-DMA instructions per wave per stage (vmcnt)
     static_assert(TB * TB * 4 <= kLdsBytes, "epilogue image fits the ring");
 };
-namespace t128 {  // the 128-tile constants (launch shape)
-constexpr int TB = 128;
-constexpr int kThreads = SmallTile<128>::kThreads;
-}  // namespace t128
 
 // kBf16: C holds bf16: the fp32 tile image in LDS is rounded on the way out (pk_bf16), 8 columns = 16 B per lane.
 template <int TB, int kEpi = kEpiNone, int kDepth = 2, bool kBf16 = false>

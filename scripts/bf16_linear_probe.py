@@ -9,8 +9,9 @@ the variants alternating round by round (and the starting variant alternating to
 One JSON line per shape: per-call microseconds of each variant (median of its rounds), the round-to-round spread
 (max - min), and the bytes that depend on the I/O types, computed from the shape alone.
 
---stores: the two bf16 store paths of gemm_i8_fm at FFN up (exchanged 16-B register stores against the LDS-image
-row segments), forced through QGEMM_BF16_WIDE_MIN, for the wide-row switch point.
+The A/B of gemm_i8_fm's two bf16 store paths at FFN up (the wide-row switch point kBf16WideRowsMin) was a --stores mode
+of this script while the library read an override from the environment; its result is profiles/bf16_store_paths.log.
+A re-measurement sets GemmArgs::wide_rows from a lab harness (lab/epi_lab.hip launches the kernel with its own GemmArgs).
 
 For the kernel-level split run the same script under `rocprofv3 --kernel-trace --stats -- python ...` with --rounds 1.
 """
@@ -47,7 +48,6 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--shapes", default=",".join(SHAPES))
-    ap.add_argument("--stores", action="store_true", help="A/B of the two bf16 store paths at FFN up")
     args = ap.parse_args()
 
     qg = _pkg.package()
@@ -79,34 +79,6 @@ def main():
     def summary(v):
         v = sorted(v)
         return {"us": round(v[len(v) // 2], 3), "spread_us": round(v[-1] - v[0], 3), "rounds": [round(x, 3) for x in v]}
-
-    if args.stores:
-        m, n, k = SHAPES["ffn_up"]
-        X, Xb, pw, Y, Yb, ws = setup(m, n, k)
-
-        def bf16():
-            assert L.qgemm_linear_dt(Xb.data_ptr(), 1, k, m, k, pw.buf.data_ptr(), n, None, 0, Yb.data_ptr(), 1, n,
-                                     ws.data_ptr(), ws.numel(), stream) == 0
-        knob = {"register_16B": str(1 << 40), "lds_image": "0"}
-        res = {name: [] for name in knob}
-        ref = None
-        for name, v in knob.items():  # warm-up, and the two paths must agree bit for bit
-            os.environ["QGEMM_BF16_WIDE_MIN"] = v
-            for _ in range(args.warmup):
-                bf16()
-            torch.cuda.synchronize()
-            bits = Yb.view(torch.int16).clone()
-            assert ref is None or torch.equal(ref, bits), "the two store paths disagree"
-            ref = bits
-        for r in range(args.rounds):
-            order = list(knob) if r % 2 == 0 else list(knob)[::-1]
-            for name in order:
-                os.environ["QGEMM_BF16_WIDE_MIN"] = knob[name]
-                res[name].append(timed(bf16, args.calls))
-        del os.environ["QGEMM_BF16_WIDE_MIN"]
-        print(json.dumps({"mode": "stores", "shape": [m, n, k], "row_bytes": 2 * n,
-                          **{name: summary(v) for name, v in res.items()}}), flush=True)
-        return
 
     for name in args.shapes.split(","):
         m, n, k = SHAPES[name]

@@ -115,6 +115,12 @@ def test_linear_fused_bias_relu_256_tiles(qg, oracle, device, M, N, K, relu, spl
     (33, 64, 1, 64, 1),       # one query row in the second tile; P V over 64 padded keys
     (300, 128, 1, 64, 1),     # d_k 128 > 64: the three-launch attention fallback
     (600, 64, 2, 64, 1),      # seq 600 > 512: fallback
+    # add+layernorm with the fused pack beyond kV = 4 (d <= 1024), reached only through the encoder:
+    (6, 1028, 1, 8, 1),       # kV 8, the last lane partly past the row; attention fallback
+    (5, 2052, 1, 8, 1),       # kV 16, ragged last lane
+    (5, 4092, 1, 8, 1),       # kV 16 at the upper end, ragged
+    (40, 2048, 32, 16, 1),    # kV 8 with full lanes; fused attention at d_k 64
+    (6, 10, 2, 8, 1),         # d % 4 != 0: the general (LDS-walking) kernel with the pack
 ])
 def test_encoder_forward_bit_exact(qg, oracle, device, seq, d, H, dff, blocks):
     X = oracle.uniform((seq, d), 11)
