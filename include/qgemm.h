@@ -172,8 +172,34 @@ QGEMM_API int qgemm_encoder_destroy(void *encoder);
 QGEMM_API size_t qgemm_mm_outlier_workspace_size(int m, int n, int k);
 QGEMM_API int qgemm_mm_outlier(const float *A, const float *B, float *C, int m, int n, int k, float threshold,
                      void *workspace, size_t ws_bytes, void *stream);
-/* number of outlier columns found by the last qgemm_mm_outlier on this workspace (synchronizes) */
+/* number of outlier columns found by the last qgemm_mm_outlier / qgemm_linear_outlier on this workspace
+ * (synchronizes) */
 QGEMM_API int qgemm_outlier_count(int k, const void *workspace, int *count);
+
+/* ---- LLM.int8() outlier decomposition on a CACHED weight ------------------------------------------
+ * Y = linear_outlier(X, packed W, threshold [, bias] [, relu]): the decomposition for a weight quantized once by
+ * qgemm_pack_b(range 127) -- int8 values Wq (k x n), scales Cw -- as LLM.int8() inference runs it: the outlier
+ * columns of the activations are found per call and multiplied against the matching weight rows DEQUANTIZED FROM THE
+ * CACHED int8, so no fp32 weight is read or kept.  X: m x k fp32, unit inner stride, row stride x_stride_h.
+ *   outlier column k : some X[i,k] with NOT(|x| <= threshold), as qgemm_mm_outlier (NaN counts)
+ *   X'               : X with those columns as +0
+ *   O8               = op_quantized_mm(X', W) on the cached Wq / Cw: X' is zero in the outlier columns, so Wq's outlier
+ *                      rows contribute nothing and are not zeroed, and Cw is the full column's scale
+ *   Wd[k,j]          = fl( fl( float(Wq[k,j]) * Cw[j] ) * fl(1/127) ), outlier rows k only: two IEEE roundings
+ *   Co               = fmaf chain from +0 over the outlier columns in ascending k of X[i,k] * Wd[k,j]
+ *   O                = fl(O8 + Co); with no outlier column O = O8 with NO add (an O8 of -0 stays -0)
+ *   Y                = O, then fl(O + bias[j]) when bias != NULL, then (y < 0 ? 0 : y) when relu (relu needs a bias)
+ * With no outlier column Y is bit-identical to qgemm_linear.  qgemm_mm_outlier differs: it takes an fp32 B, defines
+ * the int8 part on B' (outlier rows zeroed, so Cw depends on the activations) and multiplies the fp32 rows.
+ * workspace: qgemm_linear_outlier_workspace_size(m, n, k) bytes, used in stream order; the call allocates nothing,
+ * makes no host synchronization and keeps no state between calls (it can be captured in a HIP graph);
+ * qgemm_outlier_count(k, workspace, &count) reads the count of the last call on that workspace.
+ * hipErrorInvalidValue: a null X / packed_w / Y, m < 0, n < 0, k < 1, NOT(threshold >= 0), relu without bias, or a
+ * short workspace; m == 0 || n == 0 returns 0.  The workspace size is 0 for invalid dims. */
+QGEMM_API size_t qgemm_linear_outlier_workspace_size(int m, int n, int k);
+QGEMM_API int qgemm_linear_outlier(const float *X, int64_t x_stride_h, int m, int k, const void *packed_w, int n,
+                         const float *bias, int relu, float threshold, float *Y, int64_t y_stride_h,
+                         void *workspace, size_t ws_bytes, void *stream);
 
 /* The reference's quantization-error metric on the device: E = fl(C - O) per
  * element (op_subtract, op_elemwise.cuh:531-542), C = the unquantized product, O = the quantized one;

@@ -28,7 +28,7 @@ reps = [
      '__global__ __launch_bounds__(kFmThreads, 1) void gemm_i8_fm(GemmArgs p) {',
      'template <int kMap, int kStore, int kAux, int kEpi = kEpiNone, bool kI32 = false, int kSplit = kSplitNone, bool kNtC = !kI32, int kFirst64 = 30, bool kBf16 = false>\n'
      '__global__ __launch_bounds__(kFmThreads, 1) void gemm_i8_fm_epi(GemmArgs p) {'),
-    ("    group_tiles(tile, p.tiles_m, p.tiles_n, tm, tn, kEpi != kEpiOutlier && p.wide_rows ? 8 : 4);\n",
+    ("    group_tiles(tile, p.tiles_m, p.tiles_n, tm, tn, !outlier_epi(kEpi) && p.wide_rows ? 8 : 4);\n",
      """    if constexpr (kMap == 1 || kMap == 3) {  // XCD patches of 8 (2) tile-rows instead of 4
         constexpr int kG = kMap == 1 ? 8 : 2;
         const int per_group = kG * p.tiles_n, group = tile / per_group, first_m = group * kG;

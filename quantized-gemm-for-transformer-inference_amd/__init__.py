@@ -65,6 +65,8 @@ EXPORTED_SYMBOLS = (
     "qgemm_mm_outlier_workspace_size",
     "qgemm_mm_outlier",
     "qgemm_outlier_count",
+    "qgemm_linear_outlier_workspace_size",
+    "qgemm_linear_outlier",
     "qgemm_set_gemm_events",
     "qgemm_set_event_mode",
     "qgemm_fill_uniform",
@@ -180,6 +182,10 @@ def load() -> ctypes.CDLL:
         L.qgemm_mm_outlier.restype = i32
         L.qgemm_outlier_count.argtypes = [i32, vp, ctypes.POINTER(i32)]
         L.qgemm_outlier_count.restype = i32
+        L.qgemm_linear_outlier_workspace_size.argtypes = [i32, i32, i32]
+        L.qgemm_linear_outlier_workspace_size.restype = sz
+        L.qgemm_linear_outlier.argtypes = [vp, i64, i32, i32, vp, i32, vp, i32, f32, vp, i64, vp, sz, vp]
+        L.qgemm_linear_outlier.restype = i32
         L.qgemm_fill_uniform.argtypes = [vp, i64, ctypes.c_uint64, f32, f32, vp]
         L.qgemm_fill_uniform.restype = i32
         L.qgemm_set_gemm_events.argtypes = [vp, vp]
@@ -727,6 +733,38 @@ def mm_outlier(A, B, threshold: float = 6.0, C=None):
     torch.cuda.current_stream(A.device).synchronize()
     _check("qgemm_outlier_count", L.qgemm_outlier_count(K, ws.data_ptr(), ctypes.byref(cnt)))
     return C, cnt.value
+
+
+def linear_outlier(X, pw: Packed, threshold: float = 6.0, bias=None, relu: bool = False, Y=None):
+    """LLM.int8() decomposition on a cached weight (qgemm_linear_outlier): X's outlier feature columns are found per
+    call and multiplied in fp32 against the matching rows of pw dequantized from its int8 (Wq * Cw / 127), the rest runs
+    the int8 chain on pw as linear() does; then [+ b] [relu].  fp32 X and Y.  Returns (Y, number of outlier columns)."""
+    import torch
+    # the entry point quantizes X with range 127 and dequantizes the weight's rows with 1/127
+    assert pw.range == DEFAULT_RANGE, f"qgemm_linear_outlier needs a weight packed with range {DEFAULT_RANGE}"
+    _require_device_f32(X, "X")
+    assert X.stride(1) == 1 and X.shape[1] == pw.k
+    M, K = X.shape
+    N = pw.rows
+    if Y is None:
+        Y = torch.empty((M, N), dtype=torch.float32, device=X.device)
+    _require_device_f32(Y, "Y")
+    assert Y.shape == (M, N) and Y.stride(1) == 1
+    if bias is not None:
+        assert bias.dtype == torch.float32, "bias stays float32"
+    assert bias is not None or not relu, "relu follows a bias (qgemm_linear_outlier)"
+    L = load()
+    ws = torch.empty(max(4, L.qgemm_linear_outlier_workspace_size(M, N, K)), dtype=torch.uint8, device=X.device)
+    if M == 0 or N == 0:
+        return Y, 0
+    _check("qgemm_linear_outlier",
+           L.qgemm_linear_outlier(X.data_ptr(), X.stride(0), M, K, pw.buf.data_ptr(), N,
+                                  0 if bias is None else bias.data_ptr(), 1 if relu else 0, float(threshold),
+                                  Y.data_ptr(), Y.stride(0), ws.data_ptr(), ws.numel(), _stream(X.device)))
+    cnt = ctypes.c_int()
+    torch.cuda.current_stream(X.device).synchronize()
+    _check("qgemm_outlier_count", L.qgemm_outlier_count(K, ws.data_ptr(), ctypes.byref(cnt)))
+    return Y, cnt.value
 
 
 ENCODER_WEIGHT_KINDS = ("Wq", "Wk", "Wv", "Wo", "W1", "b1", "W2", "b2")

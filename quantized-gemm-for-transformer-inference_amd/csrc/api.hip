@@ -411,6 +411,41 @@ int qgemm_mm_outlier(const float *A, const float *B, float *C, int m, int n, int
     return err(outlier_finish(A, k, B, n, m, n, k, scratch, C, n, s));
 }
 
+// [outlier scratch without the W' slot (count and column list first)][the prepacked chain's workspace]
+size_t qgemm_linear_outlier_workspace_size(int m, int n, int k) {
+    if (!dims_ok(m, n, k)) return 0;
+    return align256(outlier_linear_scratch_bytes(m, k)) + ChainWorkspace(m, n, k).b;
+}
+
+int qgemm_linear_outlier(const float *X, int64_t x_stride_h, int m, int k, const void *packed_w, int n,
+                         const float *bias, int relu, float threshold, float *Y, int64_t y_stride_h, void *workspace,
+                         size_t ws_bytes, void *stream) {
+    if (!X || !packed_w || !Y || !dims_ok(m, n, k) || !(threshold >= 0.0f) || (relu && !bias))
+        return err(hipErrorInvalidValue);
+    if (m == 0 || n == 0) return 0;
+    if (!workspace || ws_bytes < qgemm_linear_outlier_workspace_size(m, n, k)) return err(hipErrorInvalidValue);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    char *scratch = static_cast<char *>(workspace);
+    char *ws2 = scratch + align256(outlier_linear_scratch_bytes(m, k));
+    const ChainWorkspace ws(m, n, k);
+    const PackedView va = packed_view(ws2 + ws.a, m, k), vb = packed_view(packed_w, n, k);
+    {
+        // fast path (no split-K: no tickets)
+        const hipError_t e = outlier_linear_fast(X, x_stride_h, m, n, k, threshold, scratch, va, vb, bias, relu != 0, Y,
+                                                 y_stride_h, s);
+        if (e != hipErrorNotSupported) return err(e);
+    }
+    float *Xm = nullptr;
+    hipError_t e = outlier_linear_prepare(X, x_stride_h, m, k, threshold, scratch, &Xm, s);
+    if (e != hipSuccess) return err(e);
+    // the int8 part on X' and the cached weight, without bias: the chain is added first
+    if ((e = launch_pack_rows(Xm, k, 1, m, k, kDefaultRange, va, s)) != hipSuccess) return err(e);
+    const float inv_r2 = 1.0f / (kDefaultRange * kDefaultRange);
+    e = launch_gemm_dequant(va, vb, Y, y_stride_h, 1, m, n, inv_r2, ws2, ws.scratch_bytes, s);
+    if (e != hipSuccess) return err(e);
+    return err(outlier_linear_finish(X, x_stride_h, m, n, k, scratch, vb, bias, relu != 0, Y, y_stride_h, s));
+}
+
 int qgemm_outlier_count(int k, const void *workspace, int *count) {
     if (!workspace || !count || k < 1) return err(hipErrorInvalidValue);
     return outlier_count_slot(k, workspace, count);

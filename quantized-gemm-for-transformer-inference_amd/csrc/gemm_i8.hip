@@ -139,7 +139,7 @@ static hipError_t launch_timed(dim3 grid, dim3 block, hipStream_t stream, const 
 // in two or not at all, so no shape reached it without an environment switch)
 template <int kEpi, bool kBf16 = false>
 static hipError_t launch_fm(const GemmArgs &p, dim3 grid, hipStream_t stream) {
-    if constexpr (kEpi != kEpiOutlier) {
+    if constexpr (!outlier_epi(kEpi)) {
         // ticket-first split-K, slice 0 = 31/64 of the k-steps (lab/t2_lab.hip, lab/c3d_lab.hip; profiles/
         // r04_splitfirst_*.log: FFN-down GEMM alone 110.5 -> 105.8 us, the whole drop-in call 284.7 -> 279.7 us)
         if (p.splits == 2)
@@ -232,6 +232,23 @@ hipError_t launch_gemm_dequant_outlier(const PackedView &a, const PackedView &b,
     p.xo_ld = xsh;
     p.ocols = ocols;
     return launch_fm<kEpiOutlier>(p, dim3((unsigned)(g.tiles_m * g.tiles_n)), stream);
+}
+
+// the same plan with the chain's W operands dequantized from the packed weight b itself (kEpiOutlierQ*): bias / relu
+// after the add of the chain
+hipError_t launch_gemm_dequant_outlier_q(const PackedView &a, const PackedView &b, float *C, int64_t csh, int m, int n,
+                                         float inv_r2, const float *x, int64_t xsh, const int *ocols, const int *ocount,
+                                         const float *bias, bool relu, hipStream_t stream) {
+    if (!shape_ok(a, b) || !gemm_outlier_ok(m, n, (int)a.k_pad) || (relu && !bias)) return hipErrorNotSupported;
+    const GemmPlan g = gemm_plan(m, n, (int)a.k_pad);
+    GemmArgs p{a.q, b.q, a.scale, b.scale, C, csh, 1, m, n, a.k_pad, g.tiles_m, g.tiles_n,
+               inv_r2, 1, nullptr, nullptr, bias, 0, x, nullptr, ocount, 0};
+    p.wide_rows = csh >= 16384 ? 1 : 0;
+    p.xo_ld = xsh;
+    p.ocols = ocols;
+    const dim3 grid((unsigned)(g.tiles_m * g.tiles_n));
+    if (!bias) return launch_fm<kEpiOutlierQ>(p, grid, stream);
+    return relu ? launch_fm<kEpiOutlierQBiasRelu>(p, grid, stream) : launch_fm<kEpiOutlierQBias>(p, grid, stream);
 }
 
 hipError_t launch_gemm_i32(const PackedView &a, const PackedView &b, int32_t *Acc, int m, int n, hipStream_t stream) {

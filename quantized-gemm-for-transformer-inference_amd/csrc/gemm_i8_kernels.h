@@ -63,7 +63,8 @@ struct GemmArgs {
     const float *bias;  // n floats, added after the dequantize (kEpi >= 1)
     int reset_tickets;  // the reducer re-zeroes its ticket (scratch zeroed once at allocation)
     // kEpiOutlier: the chain's operands where they lie -- xo = X (m x k, row stride xo_ld), wo = W (k x n, row stride
-    // wo_ld) -- at the outlier columns ocols[0 .. cnt) (ascending), cnt = *ocount on the device
+    // wo_ld) -- at the outlier columns ocols[0 .. cnt) (ascending), cnt = *ocount on the device.  kEpiOutlierQ*: wo
+    // and wo_ld are unused (the W operands are B's own bytes and Cw)
     const float *xo;
     const float *wo;
     const int *ocount;
@@ -79,8 +80,24 @@ struct GemmArgs {
 // y = fl(O + b[j]) then relu(y) = (y < 0 ? 0 : y) -- each its own rounding, as the separate launches.
 // kEpiOutlier: the LLM.int8() decomposition's fp32 part, O = fl(O8 + fmaf chain over the outlier
 // columns in ascending k of xo[i][t] * wo[t][j]) (outlier.hip; the oracle's oracle_mm_outlier)
-enum EpiMode { kEpiNone = 0, kEpiBias = 1, kEpiBiasRelu = 2, kEpiOutlier = 3 };
-constexpr bool has_bias(int e) { return e == kEpiBias || e == kEpiBiasRelu; }
+// kEpiOutlierQ (+ Bias, + BiasRelu): the same chain for a PREPACKED weight (qgemm_linear_outlier): the W operand of
+// outlier column t is row t of the cached weight dequantized, Wd[t][j] = fl(fl(float(Wq[t][j]) * Cw[j]) * fl(1/127))
+// -- the byte B[fofs(j, t, k_pad)] and the column's scale, nothing read from an fp32 W -- and the bias / relu extras
+// come after the add of the chain (O = fl(O8 + Co), then fl(O + b[j]), then relu)
+enum EpiMode {
+    kEpiNone = 0, kEpiBias = 1, kEpiBiasRelu = 2, kEpiOutlier = 3,
+    kEpiOutlierQ = 4, kEpiOutlierQBias = 5, kEpiOutlierQBiasRelu = 6
+};
+constexpr bool outlier_q(int e) { return e == kEpiOutlierQ || e == kEpiOutlierQBias || e == kEpiOutlierQBiasRelu; }
+constexpr bool outlier_epi(int e) { return e == kEpiOutlier || outlier_q(e); }
+constexpr bool has_bias(int e) { return e == kEpiBias || e == kEpiBiasRelu || e == kEpiOutlierQBias || e == kEpiOutlierQBiasRelu; }
+constexpr bool has_relu(int e) { return e == kEpiBiasRelu || e == kEpiOutlierQBiasRelu; }
+// fl(1 / range) of the prepacked weight's dequantization: qgemm_linear_outlier takes weights packed with range 127
+constexpr float kInvRange127 = 1.0f / 127.0f;
+// Wd of one cached weight byte: two separate roundings (-ffp-contract=off)
+__device__ __forceinline__ float dequant_w(int8_t q, float cw) {
+    return __fmul_rn(__fmul_rn((float)(int)q, cw), kInvRange127);
+}
 
 
 template <int kEpi>
@@ -208,16 +225,16 @@ template <int kEpi = kEpiNone, bool kI32 = false, int kSplit = kSplitNone, bool 
           bool kBf16 = false>
 __global__ __launch_bounds__(kFmThreads, 1) void gemm_i8_fm(GemmArgs p) {
     static_assert(!(kI32 && kEpi != kEpiNone), "raw accumulators take no epilogue extras");
-    static_assert(!(kBf16 && (kI32 || kEpi == kEpiOutlier)), "bf16 output: the dequantized plain / bias / relu epilogues");
+    static_assert(!(kBf16 && (kI32 || outlier_epi(kEpi))), "bf16 output: the dequantized plain / bias / relu epilogues");
     static_assert(!(kI32 && kSplit), "raw accumulators are not split");
-    static_assert(!(kEpi == kEpiOutlier && kSplit), "the outlier epilogue runs on unsplit plans");
+    static_assert(!(outlier_epi(kEpi) && kSplit), "the outlier epilogue runs on unsplit plans");
     // the one LDS array: the tile's scales (Cx of its 256 rows, Cw of its 256 columns), the split-K ticket word,
     // (wide rows) each wave's padded [64][TS] image of half its quadrant, (kEpiOutlier) the chain's operands
     constexpr int TS = 132;  // padded image row (16-B aligned, conflict-free 16-B writes of 16 rows)
     // (kEpiOutlier) stage rows of OS floats: the 4 k-groups of a wave read rows t = 4 tt + kq at the same offsets,
     // so a row stride of BM would put them on the same banks
     constexpr int OS = BM + 16;
-    constexpr int kOutlierStage = kEpi == kEpiOutlier ? 2 * 8 * OS : 0;
+    constexpr int kOutlierStage = outlier_epi(kEpi) ? 2 * 8 * OS : 0;
     __shared__ __attribute__((aligned(16))) float sS[2 * BM + 4 + 4 * 64 * TS + kOutlierStage];
     float *const sO = sS + 2 * BM + 4 + 4 * 64 * TS;  // [8][OS] X values, then [8][OS] W values
     const int tid = threadIdx.x, lane = tid & 63;
@@ -235,7 +252,7 @@ __global__ __launch_bounds__(kFmThreads, 1) void gemm_i8_fm(GemmArgs p) {
     // +0.9 %; the reads are not the difference: without stores FFN up and the 8192-row shard both run 93.6 us).  Not
     // in the outlier epilogue's instantiation: there the runtime group size made hipcc move its accumulators (+186
     // v_accvgpr_mov, c2_outlier's GEMM 58.9 -> 61.8 us, same box)
-    group_tiles(tile, p.tiles_m, p.tiles_n, tm, tn, kEpi != kEpiOutlier && p.wide_rows ? 8 : 4);
+    group_tiles(tile, p.tiles_m, p.tiles_n, tm, tn, !outlier_epi(kEpi) && p.wide_rows ? 8 : 4);
     const int nsub = (int)(p.k_pad / 64);
     // this slice's sub-steps [u0, u0 + nloc) of the nsub 64-deep k-blocks (kSplitFirst: slice 0 the shorter one)
     int cut = slice * nsub / S, end = (slice + 1) * nsub / S;
@@ -264,9 +281,9 @@ __global__ __launch_bounds__(kFmThreads, 1) void gemm_i8_fm(GemmArgs p) {
     // tile -- X[row][col_t] of its 256 rows, W[col_t][j] of its 256 columns, +0 / -0 past the count (see the
     // epilogue) -- gathered first and staged in LDS after the operand prologue is in flight, so the epilogue reads
     // them from LDS and never waits on their latency (X's columns come from HBM: the pack streamed X past the caches)
-    const int ocnt = kEpi == kEpiOutlier ? __builtin_amdgcn_readfirstlane(*p.ocount) : 0;
+    const int ocnt = outlier_epi(kEpi) ? __builtin_amdgcn_readfirstlane(*p.ocount) : 0;
     float oxv[8], owv[8];
-    if constexpr (kEpi == kEpiOutlier) {
+    if constexpr (outlier_epi(kEpi)) {
         const int64_t i = gi0 + tid;
         const int j = gj0 + tid;
         // the column list through the constant address space: scalar loads (a vector load here would make every
@@ -276,7 +293,11 @@ __global__ __launch_bounds__(kFmThreads, 1) void gemm_i8_fm(GemmArgs p) {
         for (int t = 0; t < 8; ++t) {
             const int col = t < ocnt ? ocs[t] : 0;
             oxv[t] = t < ocnt && i < p.m ? p.xo[i * p.xo_ld + col] : 0.0f;
-            owv[t] = t < ocnt ? (j < p.n ? p.wo[(int64_t)col * p.wo_ld + j] : 0.0f) : -0.0f;
+            // kEpiOutlierQ*: the cached weight's own byte of (row col, column j), dequantized with this thread's Cw
+            if constexpr (outlier_q(kEpi))
+                owv[t] = t < ocnt ? (j < p.n ? dequant_w(p.B[fofs(j, col, p.k_pad)], sw) : 0.0f) : -0.0f;
+            else
+                owv[t] = t < ocnt ? (j < p.n ? p.wo[(int64_t)col * p.wo_ld + j] : 0.0f) : -0.0f;
         }
     }
 
@@ -321,7 +342,7 @@ __global__ __launch_bounds__(kFmThreads, 1) void gemm_i8_fm(GemmArgs p) {
     sS[BM + tid] = sw;
 #pragma unroll
     for (int j = 0; j < 16; ++j) ld(a1, b1, j, nloc > 1 ? 1 : 0);
-    if constexpr (kEpi == kEpiOutlier) {
+    if constexpr (outlier_epi(kEpi)) {
 #pragma unroll
         for (int t = 0; t < 8; ++t) {
             sO[t * OS + tid] = oxv[t];
@@ -377,7 +398,7 @@ __global__ __launch_bounds__(kFmThreads, 1) void gemm_i8_fm(GemmArgs p) {
     // kEpiOutlier: the operands of the first 8 outlier columns (two f32-MFMA steps) from the LDS stage:
     // ow[step][ni] = W[col_t][j] (j = 16 ni + c), ox[mi][step] = X[row 16 mi + c][col_t], t = 4 step + kq
     float ox[8][2], ow[2][8];
-    if constexpr (kEpi == kEpiOutlier) {
+    if constexpr (outlier_epi(kEpi)) {
 #pragma unroll
         for (int tt = 0; tt < 2; ++tt) {
             const int t = 4 * tt + kq;
@@ -441,7 +462,7 @@ __global__ __launch_bounds__(kFmThreads, 1) void gemm_i8_fm(GemmArgs p) {
             // +0 would turn a -0 sum into +0).  The first 8 columns' operands were loaded once (ox / ow); columns
             // past 8 load per step.
             v4f oc[8];
-            if constexpr (kEpi == kEpiOutlier) {
+            if constexpr (outlier_epi(kEpi)) {
 #pragma unroll
                 for (int ni = 0; ni < 8; ++ni) oc[ni] = v4f{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -460,7 +481,12 @@ __global__ __launch_bounds__(kFmThreads, 1) void gemm_i8_fm(GemmArgs p) {
 #pragma unroll
                     for (int ni = 0; ni < 8; ++ni) {
                         const int j = gj0 + c0 + ni * 16 + c;
-                        wb[ni] = t < ocnt ? (j < p.n ? p.wo[(int64_t)col * p.wo_ld + j] : 0.0f) : -0.0f;
+                        // kEpiOutlierQ*: the column's Cw from the LDS scale image
+                        if constexpr (outlier_q(kEpi))
+                            wb[ni] = t < ocnt ? (j < p.n ? dequant_w(p.B[fofs(j, col, p.k_pad)], sS[BM + c0 + ni * 16 + c]) : 0.0f)
+                                              : -0.0f;
+                        else
+                            wb[ni] = t < ocnt ? (j < p.n ? p.wo[(int64_t)col * p.wo_ld + j] : 0.0f) : -0.0f;
                     }
 #pragma unroll
                     for (int ni = 0; ni < 8; ++ni) oc[ni] = __builtin_amdgcn_mfma_f32_16x16x4f32(wb[ni], xa, oc[ni], 0, 0, 0);
@@ -480,8 +506,10 @@ __global__ __launch_bounds__(kFmThreads, 1) void gemm_i8_fm(GemmArgs p) {
                 v4f o = {d01[0], d01[1], d23[0], d23[1]};
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
+                    // kEpiOutlierQ*: the chain first (skipped at count 0, as below), then the extras
+                    if constexpr (outlier_q(kEpi)) o[r] = ocnt > 0 ? __fadd_rn(o[r], oc[ni][r]) : o[r];
                     if constexpr (has_bias(kEpi)) o[r] = __fadd_rn(o[r], bv[ni][r]);
-                    if constexpr (kEpi == kEpiBiasRelu) o[r] = (o[r] < 0.0f) ? 0.0f : o[r];
+                    if constexpr (has_relu(kEpi)) o[r] = (o[r] < 0.0f) ? 0.0f : o[r];
                     // no outlier column (count 0, wave-uniform): O = O8 with no add, as the oracle
                     // (qgemm_oracle.c oracle_mm_outlier skips it) -- fl(-0 + +0) would turn an O8 of -0 into +0
                     if constexpr (kEpi == kEpiOutlier) o[r] = ocnt > 0 ? __fadd_rn(o[r], oc[ni][r]) : o[r];

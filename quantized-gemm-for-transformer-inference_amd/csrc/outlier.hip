@@ -279,6 +279,40 @@ __global__ __launch_bounds__(256) void outlier_mm_kernel(const float *__restrict
     O[(int64_t)i * osh + j] = __fadd_rn(O[(int64_t)i * osh + j], acc);
 }
 
+// (prepacked weight, fallback) Y[i,j] = fl(Y[i,j] + Co[i,j]) -- skipped at count 0 -- then fl(+ b[j]), then relu: Co the
+// fmaf chain from +0 over the outlier columns in ascending k of X[i,k] * Wd[k,j], Wd[k,j] = fl(fl(float(Wq[k,j]) *
+// Cw[j]) * fl(1/127)) from the packed weight's own bytes (q: n_pad x k_pad fragment-major, fofs) and scales.  One
+// thread per output (j fastest), rows strided over gridDim.y.
+__global__ __launch_bounds__(256) void outlier_linear_finish_kernel(const float *__restrict__ X, int64_t xsh,
+                                                                    const int8_t *__restrict__ q,
+                                                                    const float *__restrict__ Cw, int64_t k_pad,
+                                                                    const int *__restrict__ idx,
+                                                                    const int *__restrict__ count,
+                                                                    const float *__restrict__ bias, int relu,
+                                                                    float *__restrict__ Y, int64_t ysh, int m, int n) {
+    const int cnt = *count;
+    if (cnt == 0 && !bias) return;
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= n) return;
+    const float cw = Cw[j];
+    const float inv_range = 1.0f / 127.0f;
+    for (int i = blockIdx.y; i < m; i += gridDim.y) {
+        float o = Y[(int64_t)i * ysh + j];
+        if (cnt > 0) {
+            float acc = 0.0f;
+            for (int t = 0; t < cnt; ++t) {
+                const int c = idx[t];
+                const float wd = __fmul_rn(__fmul_rn((float)(int)q[fofs(j, c, k_pad)], cw), inv_range);
+                acc = __fmaf_rn(X[(int64_t)i * xsh + c], wd, acc);
+            }
+            o = __fadd_rn(o, acc);
+        }
+        if (bias) o = __fadd_rn(o, bias[j]);
+        if (relu) o = (o < 0.0f) ? 0.0f : o;
+        Y[(int64_t)i * ysh + j] = o;
+    }
+}
+
 struct OutlierScratch {
     uint32_t *partial, *bits;
     int *rank, *idx;    // idx[0] = count, idx[1 ..] = the outlier columns ascending
@@ -347,13 +381,17 @@ hipError_t outlier_scan(const float *X, int64_t xsh, int m, int k, float t, cons
 
 }  // namespace
 
-size_t outlier_scratch_bytes(int m, int n, int k) {
+// scratch_view's parts up to X' (the W' slot comes last: a prepacked weight needs none)
+size_t outlier_linear_scratch_bytes(int m, int k) {
     const size_t nwords = (size_t)(k + 31) / 32;
     const size_t nchunks = (size_t)(m + kChunkRows - 1) / kChunkRows;
     return a256(sizeof(uint32_t) * nchunks * nwords) + a256(sizeof(uint32_t) * nwords) + a256(sizeof(int) * nwords) +
            a256(sizeof(int) * ((size_t)k + 1)) + a256(sizeof(uint32_t) * state_words_for(k)) +
-           a256(sizeof(float) * (size_t)m * k) +
-           a256(sizeof(float) * (size_t)k * (size_t)round_up(n, 256));
+           a256(sizeof(float) * (size_t)m * k);
+}
+
+size_t outlier_scratch_bytes(int m, int n, int k) {
+    return outlier_linear_scratch_bytes(m, k) + a256(sizeof(float) * (size_t)k * (size_t)round_up(n, 256));
 }
 
 // Fast path: the partial masks, the masked single-pass pack (mask, count and column list), the 256-tile GEMM with the
@@ -397,6 +435,49 @@ hipError_t outlier_finish(const float *X, int64_t xsh, const float *W, int64_t w
     const OutlierScratch v = scratch_view(scratch, m, k);
     outlier_mm_kernel<<<dim3((unsigned)((n + 255) / 256), (unsigned)m), 256, 0, s>>>(X, xsh, W, wsh, v.idx + 1, v.idx,
                                                                                      O, osh, m, n);
+    return hipGetLastError();
+}
+
+// Prepacked weight, fast path: the partial masks, the masked X-only pack (mask, count and column list), the 256-tile
+// GEMM with the chain on the weight's dequantized rows (+ bias / relu) in its epilogue.  hipErrorNotSupported (nothing
+// launched) outside its envelope.
+hipError_t outlier_linear_fast(const float *X, int64_t xsh, int m, int n, int k, float t, void *scratch, PackedView va,
+                               PackedView vb, const float *bias, bool relu, float *Y, int64_t ysh, hipStream_t s) {
+    if (!gemm_outlier_ok(m, n, (int)va.k_pad) || !pack_rows_outlier_ok(X, xsh, m, k)) return hipErrorNotSupported;
+    const OutlierScratch v = scratch_view(scratch, m, k);
+    int rps = 0;
+    const int splits = colmask_splits(m, v.nwords, &rps);
+    // the partial words (splits x nwords <= 16 x 128) fit the fallback's chunk words (nchunks >= splits)
+    if (v.nwords > 128 || splits > v.nchunks || !x_vec_ok(X, xsh, k)) return hipErrorNotSupported;
+    outlier_colmask_kernel<<<dim3((unsigned)v.nwords, (unsigned)splits), kFlagThreads, 0, s>>>(X, xsh, m, k, t, rps,
+                                                                                              v.partial, v.nwords);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const float range = 127.0f;
+    e = launch_pack_rows_outlier(X, xsh, m, k, va, range, v.partial, splits, v.nwords, v.idx, s);
+    if (e == hipErrorNotSupported) return hipErrorUnknown;  // the mask already enqueued: the envelope checks disagree
+    if (e != hipSuccess) return e;
+    return launch_gemm_dequant_outlier_q(va, vb, Y, ysh, m, n, 1.0f / (range * range), X, xsh, v.idx + 1, v.idx, bias,
+                                         relu, s);
+}
+
+// Prepacked weight, fallback phase 1: flags, indices and X' into the scratch (outlier_mask_kernel's first m blocks);
+// the caller then runs the plain chain on (X', packed W) without bias, and phase 2 adds the chain and the extras.
+hipError_t outlier_linear_prepare(const float *X, int64_t xsh, int m, int k, float t, void *scratch, float **Xm,
+                                  hipStream_t s) {
+    const OutlierScratch v = scratch_view(scratch, m, k);
+    *Xm = v.xm;
+    hipError_t e = outlier_scan(X, xsh, m, k, t, v, s);
+    if (e != hipSuccess) return e;
+    outlier_mask_kernel<<<(unsigned)m, 256, 0, s>>>(X, xsh, m, k, nullptr, 0, 0, v.bits, v.xm, nullptr);
+    return hipGetLastError();
+}
+
+hipError_t outlier_linear_finish(const float *X, int64_t xsh, int m, int n, int k, void *scratch, PackedView vb,
+                                 const float *bias, bool relu, float *Y, int64_t ysh, hipStream_t s) {
+    const OutlierScratch v = scratch_view(scratch, m, k);
+    outlier_linear_finish_kernel<<<dim3((unsigned)((n + 255) / 256), (unsigned)std::min(m, 65535)), 256, 0, s>>>(
+        X, xsh, vb.q, vb.scale, vb.k_pad, v.idx + 1, v.idx, bias, relu ? 1 : 0, Y, ysh, m, n);
     return hipGetLastError();
 }
 

@@ -1163,6 +1163,23 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(kWavesPerEu
 }
 
 // ------------------------------------------------------------------------------------------------
+// The masked X rows alone (qgemm_linear_outlier: the weight was packed once, beforehand): the X role of
+// pack_single_pass8_kernel<4, true> without the W strips -- 8 rows per 512-thread block, one wave per row, R chunks
+// per lane by row length (rows_regs), staged and written out as whole lines.  Workgroup 0 also writes the outlier
+// count and the ascending column list, which the W-strip workgroup 0 does there.
+template <int R>
+__global__ __launch_bounds__(512) void pack_rows_outlier_kernel(const float *__restrict__ x, int64_t xsh, int m, int k,
+                                                                float range, float *__restrict__ x_scale,
+                                                                int8_t *__restrict__ x_q, int64_t x_rows_pad,
+                                                                int64_t k_pad, OutlierMask om) {
+    __shared__ __attribute__((aligned(16))) uint32_t xstage[8 * kStageRowWordsMax];
+    __shared__ int wsum[8];
+    pack_rows_staged<R, 8, true>(xcd_contig(blockIdx.x, 0, gridDim.x), x, xsh, m, k, range, x_scale, x_q, x_rows_pad,
+                                 k_pad, xstage, &om);
+    if (blockIdx.x == 0) outlier_column_list(om, wsum);
+}
+
+// ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void fill_uniform_kernel(float *__restrict__ dst, int64_t count, uint64_t seed,
                                                            float lo, float hi) {
     const uint64_t key = mix64(seed + 0x9E3779B97F4A7C15ULL);
@@ -1363,6 +1380,31 @@ hipError_t launch_pack_single_pass_outlier(const float *x, int64_t xsh, int m, i
     pack_single_pass8_kernel<4, true><<<nstrips + npad + nx, 512, 0, stream>>>(
         x, xsh, m, k, outx.scale, outx.q, outx.rows_pad, outx.k_pad, w, wsh, n, outw.scale, outw.q, outw.rows_pad,
         nstrips, range, nullptr, 0, om);
+    return hipGetLastError();
+}
+
+bool pack_rows_outlier_ok(const float *x, int64_t xsh, int m, int k) {
+    return k >= 1 && k <= kWaveRowMax && !(k & 3) && rows_vec_ok(x, xsh, 1, m);
+}
+
+hipError_t launch_pack_rows_outlier(const float *x, int64_t xsh, int m, int k, PackedView outx, float range,
+                                    const uint32_t *partial, int nparts, int nwords, int *idx, hipStream_t stream) {
+    if (!pack_rows_outlier_ok(x, xsh, m, k)) return hipErrorNotSupported;
+    if (nwords > 128 || nparts < 1 || nparts > 16) return hipErrorNotSupported;  // K <= 4096: nwords <= blockDim too
+    const OutlierMask om{partial, nwords, nparts, idx};
+    const unsigned grid = (unsigned)(outx.rows_pad / 8);
+#define QG_MASKED_ROWS(Rv)                                                                                          \
+    pack_rows_outlier_kernel<Rv><<<grid, 512, 0, stream>>>(x, xsh, m, k, range, outx.scale, outx.q, outx.rows_pad, \
+                                                          outx.k_pad, om)
+    switch (rows_regs(k)) {
+        case 1: QG_MASKED_ROWS(1); break;
+        case 2: QG_MASKED_ROWS(2); break;
+        case 4: QG_MASKED_ROWS(4); break;
+        case 8: QG_MASKED_ROWS(8); break;
+        case 16: QG_MASKED_ROWS(16); break;
+        default: return hipErrorNotSupported;
+    }
+#undef QG_MASKED_ROWS
     return hipGetLastError();
 }
 

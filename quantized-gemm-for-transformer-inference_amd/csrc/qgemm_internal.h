@@ -170,6 +170,13 @@ bool pack_single_pass_outlier_ok(const float *x, int64_t xsh, int m, int k, cons
 hipError_t launch_pack_single_pass_outlier(const float *x, int64_t xsh, int m, int k, PackedView outx, const float *w,
                                            int64_t wsh, int n, PackedView outw, float range, const uint32_t *partial,
                                            int nparts, int nwords, int *idx, hipStream_t stream);
+// The X role of that pack alone, for a weight packed beforehand (qgemm_linear_outlier): X's rows (row stride xsh)
+// packed with the outlier columns as +0, the register-resident row kernel chosen by row length as launch_pack_rows
+// does; workgroup 0 writes idx[0] = the outlier count, idx[1 ..] = the columns ascending.  Envelope: K % 4 == 0,
+// K <= 4096, 16-B aligned rows, nwords <= 128, nparts <= 16; hipErrorNotSupported outside it (nothing launched).
+bool pack_rows_outlier_ok(const float *x, int64_t xsh, int m, int k);
+hipError_t launch_pack_rows_outlier(const float *x, int64_t xsh, int m, int k, PackedView outx, float range,
+                                    const uint32_t *partial, int nparts, int nwords, int *idx, hipStream_t stream);
 hipError_t launch_pack_cols_pass2(const float *src, int64_t sh, int len, int cols, float range, PackedView out,
                                   hipStream_t stream);
 hipError_t launch_fill_uniform(float *dst, int64_t count, uint64_t seed, float lo, float hi, hipStream_t stream);
@@ -197,6 +204,11 @@ bool gemm_outlier_ok(int m, int n, int k);
 hipError_t launch_gemm_dequant_outlier(const PackedView &a, const PackedView &b, float *C, int64_t csh, int m, int n,
                                        float inv_r2, const float *x, int64_t xsh, const float *w, int64_t wsh,
                                        const int *ocols, const int *ocount, hipStream_t stream);
+// The same for a prepacked weight b: the chain's W operands are b's own bytes dequantized (fl(fl(q * Cw) * fl(1/127)),
+// range 127), and bias (n floats, or nullptr) / relu follow the add of the chain.
+hipError_t launch_gemm_dequant_outlier_q(const PackedView &a, const PackedView &b, float *C, int64_t csh, int m, int n,
+                                         float inv_r2, const float *x, int64_t xsh, const int *ocols, const int *ocount,
+                                         const float *bias, bool relu, hipStream_t stream);
 hipError_t launch_gemm_i32(const PackedView &a, const PackedView &b, int32_t *Acc, int m, int n,
                            hipStream_t stream);
 hipError_t launch_mm_f32(const float *A, int64_t ash, int64_t asw, const float *B, int64_t bsh, int64_t bsw, float *C,
@@ -229,6 +241,18 @@ int outlier_count_slot(int k, const void *scratch, int *count_host);
 // packed views va / vb; hipErrorNotSupported (nothing launched) outside its envelope (row-major operands)
 hipError_t outlier_fast(const float *X, const float *W, float *O, int m, int n, int k, float t, void *scratch,
                         PackedView va, PackedView vb, float range, hipStream_t s);
+// The decomposition on a PREPACKED weight (qgemm_linear_outlier): the scratch is outlier_scratch_bytes without the
+// W' slot.  outlier_linear_fast: column mask, masked X-only pack into va, the 256-tile GEMM with the chain on vb's
+// dequantized rows (+ bias / relu) in its epilogue; hipErrorNotSupported (nothing launched) outside its envelope.
+// Fallback: outlier_linear_prepare (index + X' into the scratch), the caller's plain chain on X' without bias, then
+// outlier_linear_finish (the chain on vb's dequantized rows added to Y, then bias / relu).
+size_t outlier_linear_scratch_bytes(int m, int k);
+hipError_t outlier_linear_fast(const float *X, int64_t xsh, int m, int n, int k, float t, void *scratch, PackedView va,
+                               PackedView vb, const float *bias, bool relu, float *Y, int64_t ysh, hipStream_t s);
+hipError_t outlier_linear_prepare(const float *X, int64_t xsh, int m, int k, float t, void *scratch, float **Xm,
+                                  hipStream_t s);
+hipError_t outlier_linear_finish(const float *X, int64_t xsh, int m, int n, int k, void *scratch, PackedView vb,
+                                 const float *bias, bool relu, float *Y, int64_t ysh, hipStream_t s);
 // The encoder counterpart (encoder.hip).
 struct Encoder;
 uint64_t encoder_weight_seed(uint64_t base, int block, int kind, int head);
