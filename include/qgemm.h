@@ -162,6 +162,42 @@ QGEMM_API int qgemm_encoder_create(int d_model, int n_heads, int d_ff, int n_blo
 QGEMM_API int qgemm_encoder_forward(void *encoder, const float *X, float *Y, int seq, void *stream);
 QGEMM_API int qgemm_encoder_destroy(void *encoder);
 
+/* ---- Multi-head attention core, fp32 (attention.cuh:58-69), self- or cross-attention ------------------
+ * For every head h = 0 .. n_heads-1, on columns h*d_k .. h*d_k + d_k - 1 of each matrix (d_v = d_k):
+ *   S_h = Q_h K_h^T              op_mm<float> on the transposed view: the sequential-k fmaf chain from +0
+ *   P_h = softmax(fl(S_h*scale)) op_multiply + op_softmax, as qgemm_softmax_rows
+ *   O_h = P_h V_h                op_mm<float>, the chain over seq_kv
+ * bit-identical to qgemm_mm_fp32 + qgemm_softmax_rows + qgemm_mm_fp32 per head.  Q and O have seq_q rows, K and V
+ * seq_kv rows (the decoder's cross-attention: queries from one stream, keys and values from another, of another
+ * length); each matrix has its own base pointer and row stride in floats (*_stride_h) and unit inner stride, so
+ * column slices of wider buffers work (the encoder passes the thirds of one [Q | K | V] buffer).  No mask.
+ * O must not overlap Q, K or V (not checked).
+ * One fused launch (the scores stay on chip) for d_k <= 64 and seq_kv <= 512, any seq_q; outside that three
+ * launches through `workspace`, n_heads x seq_q x seq_kv floats of scores: qgemm_attention_workspace_size returns
+ * that size in bytes, 0 inside the fused envelope (workspace may then be NULL) and 0 for invalid dimensions.
+ * The call allocates nothing and makes no host synchronization.
+ * hipErrorInvalidValue before any launch: a null Q / K / V / O, seq_q < 0, seq_kv < 1, n_heads < 1, d_k < 1,
+ * seq_kv > 4096 (qgemm_softmax_rows' row limit) or a short workspace; seq_q == 0 returns 0. */
+QGEMM_API size_t qgemm_attention_workspace_size(int seq_q, int seq_kv, int n_heads, int d_k);
+QGEMM_API int qgemm_attention(const float *Q, int64_t q_stride_h, const float *K, int64_t k_stride_h,
+                    const float *V, int64_t v_stride_h, float *O, int64_t o_stride_h,
+                    int seq_q, int seq_kv, int n_heads, int d_k, float scale,
+                    void *workspace, size_t ws_bytes, void *stream);
+
+/* ---- The decoder counterpart (transformer.cu:79-168) --------------------------------------------------
+ * Decoder stack with seeded weights drawn once and packed, like the encoder's.  X, Y: seq x d_model; enc_out:
+ * enc_seq x d_model; all row-major contiguous fp32 device arrays; seq <= max_seq <= 4096, enc_seq <= max_enc_seq
+ * <= 4096, d_model <= 4096, d_model % n_heads == 0.  Per block: self-attention on the block input (the encoder's
+ * first half), cross-attention with queries from the decoder stream and keys / values from enc_out, then the FFN
+ * whose residual is the cross-attention's multiHeadOut (DESIGN.md "Decoder").  No causal mask, as the reference.
+ * Weight kinds 0..7 as qgemm_encoder_create; 8, 9, 10 = the cross-attention's Wq2, Wk2, Wv2 (one d_model x d_k
+ * tensor per head, bound 1/sqrt(d_k)); 11 = its output projection W_O2 (head 0, U(-1, 1)). */
+QGEMM_API int qgemm_decoder_create(int d_model, int n_heads, int d_ff, int n_blocks, int max_seq, int max_enc_seq,
+                         uint64_t seed, void **decoder);
+QGEMM_API int qgemm_decoder_forward(void *decoder, const float *X, const float *enc_out, float *Y, int seq, int enc_seq,
+                          void *stream);
+QGEMM_API int qgemm_decoder_destroy(void *decoder);
+
 /* ---- LLM.int8() outlier decomposition ------------------------------------------
  * Feature columns k of A (= rows of B) holding an element with NOT(|x| <= threshold) (the reference's
  * AbsCompareLTEConstFunc, op_elemwise.cuh:293-306; NaN counts as an outlier) are multiplied in fp32,

@@ -23,7 +23,11 @@ int main(int argc, char **argv) {
     CK(hipMalloc(&qkv, (size_t)seq * 3 * d * 4)); CK(hipMalloc(&heads, (size_t)seq * d * 4));
     fill_lab<<<1024, 256>>>(qkv, (int64_t)seq * 3 * d);
     const float scale = 1.0f / 8.0f;
-    typedef void (*K)(const float *, int, int, int, float, float *);
+    // the encoder's layout: Q, K and V the thirds of one [seq x 3d] buffer, seq_q = seq_kv
+    typedef void (*K)(const float *, int64_t, const float *, int64_t, const float *, int64_t, float *, int64_t, int, int,
+                      int, float);
+    const int64_t ld = 3 * (int64_t)d;
+#define ATTN_ARGS qkv, ld, qkv + d, ld, qkv + 2 * d, ld, heads, (int64_t)d, dk, seq, seq, scale
     struct V { const char *name; K k; int tq, threads; };
     std::vector<V> vs = {{"t32 full", attention_fused_kernel<32, 256, 1024, 0>, 32, 1024},
                          {"t32 no_qk", attention_fused_kernel<32, 256, 1024, 1>, 32, 1024},
@@ -36,9 +40,9 @@ int main(int argc, char **argv) {
     for (int r = 0; r < 7; ++r)
         for (size_t i = 0; i < vs.size(); ++i) {
             const dim3 g((seq + vs[i].tq - 1) / vs[i].tq, H);
-            for (int w = 0; w < 3; ++w) vs[i].k<<<g, vs[i].threads>>>(qkv, d, dk, seq, scale, heads);
+            for (int w = 0; w < 3; ++w) vs[i].k<<<g, vs[i].threads>>>(ATTN_ARGS);
             CK(hipEventRecord(a));
-            for (int w = 0; w < 20; ++w) vs[i].k<<<g, vs[i].threads>>>(qkv, d, dk, seq, scale, heads);
+            for (int w = 0; w < 20; ++w) vs[i].k<<<g, vs[i].threads>>>(ATTN_ARGS);
             CK(hipEventRecord(z)); CK(hipEventSynchronize(z));
             float ms; CK(hipEventElapsedTime(&ms, a, z)); t[i].push_back(ms * 1000 / 20);
         }
@@ -49,7 +53,7 @@ int main(int argc, char **argv) {
     const dim3 g((seq + 31) / 32, H);
     // phase stamps (block-median durations, 100 MHz ticks): Q loads + K chunk 0 staged | QK | softmax |
     // V chunk 0 staged | PV
-    for (int w = 0; w < 5; ++w) attention_fused_kernel<32, 256, 1024, 16><<<g, 1024>>>(qkv, d, dk, seq, scale, heads);
+    for (int w = 0; w < 5; ++w) attention_fused_kernel<32, 256, 1024, 16><<<g, 1024>>>(ATTN_ARGS);
     CK(hipDeviceSynchronize());
     const int nb = g.x * g.y;
     std::vector<unsigned long long> st((size_t)4096 * 8);

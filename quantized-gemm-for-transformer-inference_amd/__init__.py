@@ -62,6 +62,11 @@ EXPORTED_SYMBOLS = (
     "qgemm_encoder_create",
     "qgemm_encoder_forward",
     "qgemm_encoder_destroy",
+    "qgemm_attention_workspace_size",
+    "qgemm_attention",
+    "qgemm_decoder_create",
+    "qgemm_decoder_forward",
+    "qgemm_decoder_destroy",
     "qgemm_mm_outlier_workspace_size",
     "qgemm_mm_outlier",
     "qgemm_outlier_count",
@@ -176,6 +181,16 @@ def load() -> ctypes.CDLL:
         L.qgemm_encoder_forward.restype = i32
         L.qgemm_encoder_destroy.argtypes = [vp]
         L.qgemm_encoder_destroy.restype = i32
+        L.qgemm_attention_workspace_size.argtypes = [i32, i32, i32, i32]
+        L.qgemm_attention_workspace_size.restype = sz
+        L.qgemm_attention.argtypes = [vp, i64, vp, i64, vp, i64, vp, i64, i32, i32, i32, i32, f32, vp, sz, vp]
+        L.qgemm_attention.restype = i32
+        L.qgemm_decoder_create.argtypes = [i32, i32, i32, i32, i32, i32, ctypes.c_uint64, ctypes.POINTER(vp)]
+        L.qgemm_decoder_create.restype = i32
+        L.qgemm_decoder_forward.argtypes = [vp, vp, vp, vp, i32, i32, vp]
+        L.qgemm_decoder_forward.restype = i32
+        L.qgemm_decoder_destroy.argtypes = [vp]
+        L.qgemm_decoder_destroy.restype = i32
         L.qgemm_mm_outlier_workspace_size.argtypes = [i32, i32, i32]
         L.qgemm_mm_outlier_workspace_size.restype = sz
         L.qgemm_mm_outlier.argtypes = [vp, vp, vp, i32, i32, i32, f32, vp, sz, vp]
@@ -768,6 +783,7 @@ def linear_outlier(X, pw: Packed, threshold: float = 6.0, bias=None, relu: bool 
 
 
 ENCODER_WEIGHT_KINDS = ("Wq", "Wk", "Wv", "Wo", "W1", "b1", "W2", "b2")
+DECODER_WEIGHT_KINDS = ENCODER_WEIGHT_KINDS + ("Wq2", "Wk2", "Wv2", "Wo2")  # kinds 8..11: the cross-attention's
 
 
 def encoder_weight_seed(base: int, block: int, kind: int, head: int) -> int:
@@ -798,6 +814,75 @@ class Encoder:
     def close(self):
         if getattr(self, "_h", None):
             load().qgemm_encoder_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def attention(Q, K, V, n_heads: int, scale=None, O=None):
+    """Multi-head fp32 attention core (qgemm_attention): O_h = softmax(Q_h K_h^T * scale) V_h on columns
+    h*d_k .. of each matrix, d_k = Q.shape[1] / n_heads.  Q: seq_q x d, K and V: seq_kv x d -- 2-D fp32 device
+    tensors or views with unit inner stride (column slices of wider buffers included); O (seq_q x d) must not
+    overlap them.  scale defaults to fl32(1 / sqrt(d_k)), as the encoder computes it.  One fused launch for
+    d_k <= 64 and seq_kv <= 512, else three launches through a scores workspace allocated here."""
+    import math
+    import torch
+    for t, nm in ((Q, "Q"), (K, "K"), (V, "V")):
+        _require_device_f32(t, nm)
+        assert t.stride(1) == 1 or t.shape[1] == 1, f"{nm} must have unit inner stride"
+    seq_q, d = Q.shape
+    seq_kv = K.shape[0]
+    assert K.shape == (seq_kv, d) and V.shape == (seq_kv, d), "K and V: seq_kv x d, d as Q"
+    assert n_heads >= 1 and d % n_heads == 0, "d % n_heads == 0"
+    dk = d // n_heads
+    if scale is None:
+        scale = ctypes.c_float(1.0 / math.sqrt(float(dk))).value  # attention.cuh:64
+    if O is None:
+        O = torch.empty((seq_q, d), dtype=torch.float32, device=Q.device)
+    _require_device_f32(O, "O")
+    assert O.shape == (seq_q, d) and (O.stride(1) == 1 or d == 1), "O: seq_q x d with unit inner stride"
+    L = load()
+    need = L.qgemm_attention_workspace_size(seq_q, seq_kv, n_heads, dk)
+    ws = torch.empty(need, dtype=torch.uint8, device=Q.device) if need else None
+    _check("qgemm_attention",
+           L.qgemm_attention(Q.data_ptr(), Q.stride(0), K.data_ptr(), K.stride(0), V.data_ptr(), V.stride(0),
+                             O.data_ptr(), O.stride(0), seq_q, seq_kv, n_heads, dk, float(scale),
+                             ws.data_ptr() if need else None, need, _stream(Q.device)))
+    return O
+
+
+class Decoder:
+    """transformer.cu:79-168's Decoder with its linears on the quantized path: per block self-attention,
+    cross-attention on the encoder's output, FFN (DESIGN.md "Decoder")."""
+
+    def __init__(self, d_model: int, n_heads: int, d_ff: int, n_blocks: int, max_seq: int, max_enc_seq: int,
+                 seed: int = 0):
+        self.d_model, self.n_heads, self.d_ff, self.n_blocks, self.max_seq, self.max_enc_seq, self.seed = (
+            d_model, n_heads, d_ff, n_blocks, max_seq, max_enc_seq, seed)
+        h = ctypes.c_void_p()
+        _check("qgemm_decoder_create", load().qgemm_decoder_create(d_model, n_heads, d_ff, n_blocks, max_seq,
+                                                                  max_enc_seq, seed, ctypes.byref(h)))
+        self._h = h
+
+    def forward(self, X, enc_out, Y=None):
+        import torch
+        _require_device_f32(X, "X")
+        _require_device_f32(enc_out, "enc_out")
+        assert X.is_contiguous() and X.shape[1] == self.d_model
+        assert enc_out.is_contiguous() and enc_out.shape[1] == self.d_model
+        Y = torch.empty_like(X) if Y is None else Y
+        _check("qgemm_decoder_forward", load().qgemm_decoder_forward(self._h, X.data_ptr(), enc_out.data_ptr(),
+                                                                    Y.data_ptr(), X.shape[0], enc_out.shape[0],
+                                                                    _stream(X.device)))
+        return Y
+
+    def close(self):
+        if getattr(self, "_h", None):
+            load().qgemm_decoder_destroy(self._h)
             self._h = None
 
     def __del__(self):

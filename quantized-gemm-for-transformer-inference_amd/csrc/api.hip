@@ -381,6 +381,46 @@ int qgemm_encoder_destroy(void *encoder) {
     return 0;
 }
 
+// the fallback's scores, n_heads x seq_q x seq_kv floats; nothing inside the fused launch's envelope
+size_t qgemm_attention_workspace_size(int seq_q, int seq_kv, int n_heads, int d_k) {
+    if (seq_q < 0 || seq_kv < 1 || seq_kv > 4096 || n_heads < 1 || d_k < 1) return 0;
+    if (attention_fused_ok(seq_kv, d_k)) return 0;
+    return sizeof(float) * (size_t)n_heads * (size_t)seq_q * (size_t)seq_kv;
+}
+
+int qgemm_attention(const float *Q, int64_t q_stride_h, const float *K, int64_t k_stride_h, const float *V,
+                    int64_t v_stride_h, float *O, int64_t o_stride_h, int seq_q, int seq_kv, int n_heads, int d_k,
+                    float scale, void *workspace, size_t ws_bytes, void *stream) {
+    if (!Q || !K || !V || !O || seq_q < 0 || seq_kv < 1 || seq_kv > 4096 || n_heads < 1 || d_k < 1)
+        return err(hipErrorInvalidValue);
+    const size_t need = qgemm_attention_workspace_size(seq_q, seq_kv, n_heads, d_k);
+    if (need && (!workspace || ws_bytes < need)) return err(hipErrorInvalidValue);
+    if (seq_q == 0) return 0;
+    return err(launch_attention(Q, q_stride_h, K, k_stride_h, V, v_stride_h, O, o_stride_h, seq_q, seq_kv, n_heads, d_k,
+                                scale, need ? static_cast<float *>(workspace) : nullptr,
+                                static_cast<hipStream_t>(stream)));
+}
+
+int qgemm_decoder_create(int d_model, int n_heads, int d_ff, int n_blocks, int max_seq, int max_enc_seq, uint64_t seed,
+                         void **decoder) {
+    if (!decoder) return err(hipErrorInvalidValue);
+    Decoder *D = nullptr;
+    hipError_t e = decoder_create(d_model, n_heads, d_ff, n_blocks, max_seq, max_enc_seq, seed, &D);
+    *decoder = D;
+    return err(e);
+}
+
+int qgemm_decoder_forward(void *decoder, const float *X, const float *enc_out, float *Y, int seq, int enc_seq,
+                          void *stream) {
+    return err(decoder_forward(static_cast<Decoder *>(decoder), X, enc_out, Y, seq, enc_seq,
+                               static_cast<hipStream_t>(stream)));
+}
+
+int qgemm_decoder_destroy(void *decoder) {
+    decoder_destroy(static_cast<Decoder *>(decoder));
+    return 0;
+}
+
 size_t qgemm_mm_outlier_workspace_size(int m, int n, int k) {
     if (!dims_ok(m, n, k)) return 0;
     return align256(outlier_scratch_bytes(m, n, k)) + op_mm_quantize_workspace_size(m, n, k);

@@ -1,18 +1,25 @@
-// attention.hip -- the encoder's fp32 attention core (attention.cuh:58-69) in ONE launch per block of
-// the encoder: for every (head, 32-query tile) a workgroup computes
+// attention.hip -- the fp32 attention core (attention.cuh:58-69) in ONE launch: for every (head, 32-query
+// tile) a workgroup computes
 //   S = Q_h K_h^T                  op_mm<float> on the transposed view    (attention.cuh:58-60)
-//   P = softmax(S * 1/sqrt(d_k))   op_multiply + op_softmax               (attention.cuh:65-68)
-//   heads[:, h*d_k..] = P V_h      op_mm<float>                           (attention.cuh:69)
-// with S and P kept in LDS (the three-launch form writes and re-reads the H x seq x seq score tensor
-// through HBM twice).  Every step keeps the arithmetic of the separate kernels bit for bit:
+//   P = softmax(S * scale)         op_multiply + op_softmax               (attention.cuh:65-68)
+//   O[:, h*d_k..] = P V_h          op_mm<float>                           (attention.cuh:69)
+// with S and P kept in LDS (the three-launch form writes and re-reads the H x seq_q x seq_kv score tensor
+// through HBM twice).
+// Q (seq_q rows), K and V (seq_kv rows) and O (seq_q rows) are four matrices with their own base pointers
+// and row strides, head h at columns h*d_k .. h*d_k + d_k - 1 of each: the encoder's self-attention passes
+// the three thirds of its [Q | K | V] buffer (seq_q = seq_kv), the decoder's cross-attention its own
+// queries and the projections of the encoder's output.  Query rows run to seq_q; everything along a score
+// row (K / V chunks, the softmax, the P V reduction) runs to seq_kv.
+// Every step keeps the arithmetic of the separate kernels bit for bit:
 //   * both products are v_mfma_f32_16x16x4_f32 chains from +0 over k ascending, zero-padded to a
 //     multiple of 4, then fl(res + 0) when k % 32 != 0 -- the reference's op_matmul_kernel chain
 //     (op_mm.cuh:37-39) with its zero-padded last 32-wide tile, exactly as gemm_f32.hip;
 //   * softmax as softmax_rows_kernel: products fl(s * scale), max seeded by the first element with a
 //     strict >, correctly rounded fp32 exp of fl(x - max), ONE sequential fp32 sum in column order,
 //     then fl(e / sum).
-// Envelope: d_k <= 64, seq <= 512 (S tile 32 x 512 fp32 = 64 KiB of LDS, Q tile and K / V staged
-// through LDS in 256-key chunks: 155 KiB in all); outside it the encoder runs the three kernels.
+// Envelope: d_k <= 64, seq_kv <= 512, any seq_q (S tile 32 x 512 fp32 = 64 KiB of LDS, Q tile and K / V
+// staged through LDS in 256-key chunks: 155 KiB in all); outside it launch_attention (encoder.hip) runs the
+// three kernels.
 #include "qgemm_internal.h"
 
 #include <type_traits>
@@ -46,7 +53,8 @@ typedef float v4f __attribute__((ext_vector_type(4)));
 
 template <int kTQ, int kChunk, int kThreads>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))) void attention_fused_kernel(
-    const float *__restrict__ qkv, int d, int dk, int seq, float scale, float *__restrict__ heads) {
+    const float *__restrict__ Q, int64_t ldq, const float *__restrict__ K, int64_t ldk, const float *__restrict__ V,
+    int64_t ldv, float *__restrict__ O, int64_t ldo, int dk, int seq_q, int seq_kv, float scale) {
     using T = AttnTile<kTQ, kChunk, kThreads>;
     constexpr int kAttnThreads = kThreads, kRF = T::kRowFrags;
     __shared__ __attribute__((aligned(16))) float S[kTQ * kSStride];
@@ -59,10 +67,10 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
     const int logical = (xc < xr ? xc * (xq + 1) : xr * (xq + 1) + (xc - xr) * xq) + (lin >> 3);
     const int h = logical / gridDim.x, q0 = (logical - h * gridDim.x) * kTQ;
     const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
-    const int64_t ld = 3 * (int64_t)d;
-    const float *Qb = qkv + (int64_t)h * dk, *Kb = qkv + d + (int64_t)h * dk, *Vb = qkv + 2 * (int64_t)d + (int64_t)h * dk;
+    const float *Qb = Q + (int64_t)h * dk, *Kb = K + (int64_t)h * dk, *Vb = V + (int64_t)h * dk;
     const int lr = lane & 15, lk = lane >> 4;  // MFMA operand lane: row lr of the fragment, k offset lk
-    const int rows = seq - q0 < kTQ ? seq - q0 : kTQ;
+    const int rows = seq_q - q0 < kTQ ? seq_q - q0 : kTQ;
+    const int seq = seq_kv;  // the extent of a score row: keys, softmax columns, the P V reduction
     const int nchunks = (seq + kChunk - 1) / kChunk;
     const int seq32 = (seq + 31) & ~31;  // the reference's k extent for P V: seq zero-padded to its 32-wide tile
     const int dk4 = (dk + 3) >> 2;  // float4 columns of a K / V row (the last one zero-padded)
@@ -71,7 +79,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
     // c+1's global loads are in flight under chunk c's MFMAs, V chunk 0's under the last QK chunk and
     // the softmax -- then written to KV ([key][stride], zero past seq and past d_k)
     constexpr int kPer = kChunk * 16 / kThreads;
-    auto fetch = [&](float4 (&r)[kPer], const float *src, int c0) __attribute__((always_inline)) {
+    auto fetch = [&](float4 (&r)[kPer], const float *src, int64_t ld, int c0) __attribute__((always_inline)) {
 #pragma unroll
         for (int i = 0; i < kPer; ++i) {
             const int f = t + i * kThreads, row = f >> 4, c4 = f & 15, j = c0 + row;
@@ -98,17 +106,17 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
         }
     };
 
-    // ---- S[32][seq] = Q K^T, one K chunk at a time: wave w computes 16-column tile w of the chunk for
+    // ---- S[32][seq_kv] = Q K^T, one K chunk at a time: wave w computes 16-column tile w of the chunk for
     // both 16-row halves (one B fragment, two A fragments)
     const int ns32 = ((dk + 31) & ~31) >> 2;  // k-steps over d_k zero-padded to 32: 8 or 16
     // the Q tile through LDS (coalesced row loads once per workgroup, not per wave), with K chunk 0
     float4 pf[kPer];
-    fetch(pf, Kb, 0);
+    fetch(pf, Kb, ldk, 0);
     for (int f = t; f < kTQ * 16; f += kAttnThreads) {
         const int row = f >> 4, c4 = f & 15, i = q0 + row;
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (i < seq && c4 < dk4) {
-            const float *p = Qb + i * ld + 4 * c4;
+        if (i < seq_q && c4 < dk4) {
+            const float *p = Qb + i * ldq + 4 * c4;
             v.x = p[0];
             v.y = 4 * c4 + 1 < dk ? p[1] : 0.f;
             v.z = 4 * c4 + 2 < dk ? p[2] : 0.f;
@@ -121,8 +129,8 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
         if (c) __syncthreads();  // every wave is done with the previous chunk
         put(pf, kKStride);
         __syncthreads();
-        if (c + 1 < nchunks) fetch(pf, Kb, (c + 1) * kChunk);
-        else fetch(pf, Vb, 0);
+        if (c + 1 < nchunks) fetch(pf, Kb, ldk, (c + 1) * kChunk);
+        else fetch(pf, Vb, ldv, 0);
         if (c == 0) {
 #pragma unroll
             for (int rf = 0; rf < kRF; ++rf)
@@ -219,7 +227,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
         if (lane < seq32 - seq) srow[seq + lane] = 0.0f;  // P over the zero-padded k range (< 32 columns)
     }
 
-    // ---- heads = P V, one V chunk at a time: waves 0 .. kRF*ceil(d_k/16)-1 own output tile (row
+    // ---- O = P V, one V chunk at a time: waves 0 .. kRF*ceil(d_k/16)-1 own output tile (row
     // fragment w % kRF, column tile w / kRF) and carry its accumulator across the chunks (the k chain
     // stays in order)
     const int nct2 = (dk + 15) >> 4, nks32 = seq32 >> 2;
@@ -232,7 +240,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
         __syncthreads();  // P complete (c = 0) / the previous V chunk consumed
         put(pf, kVStride);
         __syncthreads();
-        if (c + 1 < nchunks) fetch(pf, Vb, (c + 1) * kChunk);
+        if (c + 1 < nchunks) fetch(pf, Vb, ldv, (c + 1) * kChunk);
         if (pv_wave) {
             // k-steps over the reference's zero-padded extent (seq rounded up to 32: P and V are zero
             // past seq, so those steps are its padded tile's +0 adds), in groups of 8 -- a whole number
@@ -266,21 +274,25 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int rl = rf * 16 + 4 * lk + r;
-            if (rl < rows) heads[(int64_t)(q0 + rl) * d + (int64_t)h * dk + col] = acc[r];
+            if (rl < rows) O[(q0 + rl) * ldo + (int64_t)h * dk + col] = acc[r];
         }
     }
 }
 
 }  // namespace
 
-hipError_t launch_attention_fused(const float *qkv, int seq, int d, int n_heads, float scale, float *heads,
+bool attention_fused_ok(int seq_kv, int dk) { return seq_kv <= kAttnMaxSeq && dk <= kAttnMaxDk; }
+
+hipError_t launch_attention_fused(const float *Q, int64_t ldq, const float *K, int64_t ldk, const float *V, int64_t ldv,
+                                  float *O, int64_t ldo, int seq_q, int seq_kv, int n_heads, int dk, float scale,
                                   hipStream_t stream) {
-    if (n_heads < 1 || d % n_heads) return hipErrorInvalidValue;
-    const int dk = d / n_heads;
-    if (seq < 1 || seq > kAttnMaxSeq || dk > kAttnMaxDk) return hipErrorNotSupported;
+    if (n_heads < 1 || dk < 1 || seq_q < 0 || seq_kv < 1) return hipErrorInvalidValue;
+    if (!attention_fused_ok(seq_kv, dk)) return hipErrorNotSupported;
+    if (seq_q == 0) return hipSuccess;
     constexpr int kTQ = 32;
-    attention_fused_kernel<kTQ, 256, 1024><<<dim3((unsigned)((seq + kTQ - 1) / kTQ), (unsigned)n_heads), 1024, 0, stream>>>(
-        qkv, d, dk, seq, scale, heads);
+    const dim3 grid((unsigned)((seq_q + kTQ - 1) / kTQ), (unsigned)n_heads);
+    attention_fused_kernel<kTQ, 256, 1024><<<grid, 1024, 0, stream>>>(Q, ldq, K, ldk, V, ldv, O, ldo, dk, seq_q, seq_kv,
+                                                                       scale);
     return hipGetLastError();
 }
 

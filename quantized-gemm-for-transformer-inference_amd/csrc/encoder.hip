@@ -61,9 +61,11 @@ hipError_t alloc_f(T **p, size_t count) {
     return alloc(reinterpret_cast<void **>(p), count * sizeof(T));
 }
 
+}  // namespace
+
 // draw a K x N fp32 weight (uniform [-bound, bound), reference init formula) and pack it as B
-hipError_t make_packed(int k, int n, const std::vector<uint64_t> &col_seeds, int cols_per_seed, float bound,
-                       void **packed, float *tmp, hipStream_t s) {
+hipError_t encoder_make_packed(int k, int n, const std::vector<uint64_t> &col_seeds, int cols_per_seed, float bound,
+                               void **packed, float *tmp, hipStream_t s) {
     // col_seeds[c] fills columns [c*cols_per_seed, (c+1)*cols_per_seed) -- one reference tensor each
     hipError_t e;
     float *one = tmp + (size_t)k * n;  // k x cols_per_seed staging
@@ -78,6 +80,8 @@ hipError_t make_packed(int k, int n, const std::vector<uint64_t> &col_seeds, int
     // B = W (k x n, row-major): reduction vectors are its columns -> pack_cols path
     return launch_pack_cols(tmp, n, k, n, 127.0f, packed_view(*packed, n, k), s);
 }
+
+namespace {
 
 // the packed activations of the next linear (one buffer, reused by every linear in stream order)
 PackedView act_view(Encoder &E, int seq, int k) { return packed_view(E.ws + E.scratch_bytes, seq, k); }
@@ -95,6 +99,25 @@ hipError_t linear(Encoder &E, const float *x, int seq, int k, const void *wpacke
 }
 
 }  // namespace
+
+// The attention core of the encoder and the decoder: one fused launch where it fits (attention.hip), else the three
+// kernels it fuses, through `scores`.
+hipError_t launch_attention(const float *Q, int64_t ldq, const float *K, int64_t ldk, const float *V, int64_t ldv,
+                            float *O, int64_t ldo, int seq_q, int seq_kv, int n_heads, int dk, float scale,
+                            float *scores, hipStream_t stream) {
+    hipError_t e = launch_attention_fused(Q, ldq, K, ldk, V, ldv, O, ldo, seq_q, seq_kv, n_heads, dk, scale, stream);
+    if (e != hipErrorNotSupported) return e;
+    if (seq_q == 0) return hipSuccess;
+    if (!scores) return hipErrorInvalidValue;
+    // fp32 op_mm with the transposed view of K, softmax in place, fp32 op_mm into the head's columns of O
+    const int64_t sbs = (int64_t)seq_q * seq_kv;
+    if ((e = launch_mm_f32_batched(Q, ldq, 1, dk, K, 1, ldk, dk, scores, seq_kv, 1, sbs, seq_q, seq_kv, dk, n_heads,
+                                   stream)))
+        return e;
+    if ((e = launch_softmax_rows(scores, scores, (int64_t)n_heads * seq_q, seq_kv, scale, stream))) return e;
+    return launch_mm_f32_batched(scores, seq_kv, 1, sbs, V, ldv, 1, dk, O, ldo, 1, dk, seq_q, dk, seq_kv, n_heads,
+                                 stream);
+}
 
 void encoder_destroy(Encoder *E) {
     if (!E) return;
@@ -160,13 +183,13 @@ hipError_t encoder_create(int d_model, int n_heads, int d_ff, int n_blocks, int 
         std::vector<uint64_t> qkv_seeds;
         for (int kind = kWq; kind <= kWv; ++kind)
             for (int h = 0; h < n_heads; ++h) qkv_seeds.push_back(encoder_weight_seed(seed, i, kind, h));
-        if ((e = make_packed(d, 3 * d, qkv_seeds, dk, encoder_init_bound(dk), &B.wqkv, tmp, s))) break;
-        if ((e = make_packed(d, d, {encoder_weight_seed(seed, i, kWo, 0)}, d, 1.0f, &B.wo, tmp, s))) break;
-        if ((e = make_packed(d, d_ff, {encoder_weight_seed(seed, i, kW1, 0)}, d_ff, encoder_init_bound(d), &B.w1, tmp,
-                             s)))
+        if ((e = encoder_make_packed(d, 3 * d, qkv_seeds, dk, encoder_init_bound(dk), &B.wqkv, tmp, s))) break;
+        if ((e = encoder_make_packed(d, d, {encoder_weight_seed(seed, i, kWo, 0)}, d, 1.0f, &B.wo, tmp, s))) break;
+        if ((e = encoder_make_packed(d, d_ff, {encoder_weight_seed(seed, i, kW1, 0)}, d_ff, encoder_init_bound(d),
+                                     &B.w1, tmp, s)))
             break;
-        if ((e = make_packed(d_ff, d, {encoder_weight_seed(seed, i, kW2, 0)}, d, encoder_init_bound(d_ff), &B.w2, tmp,
-                             s)))
+        if ((e = encoder_make_packed(d_ff, d, {encoder_weight_seed(seed, i, kW2, 0)}, d, encoder_init_bound(d_ff),
+                                     &B.w2, tmp, s)))
             break;
         if ((e = alloc_f(&B.b1, d_ff)) || (e = alloc_f(&B.b2, d))) break;
         const float bd = encoder_init_bound(d), bf = encoder_init_bound(d_ff);
@@ -195,17 +218,10 @@ hipError_t encoder_forward(Encoder *E, const float *X, float *Y, int seq, hipStr
         if ((e = linear(*E, in_packed ? nullptr : in, seq, d, B.wqkv, 3 * d, E->qkv, nullptr, false, s))) return e;
         // S_h = Q_h K_h^T, P_h = softmax(S_h * 1/sqrt(d_k)), heads[:, h*d_v..] = P_h V_h
         // (attention.cuh:58-69, transformer.cu:43-50): one launch with S in LDS where it fits
-        e = launch_attention_fused(E->qkv, seq, d, H, scale, E->heads, s);
-        if (e == hipErrorNotSupported) {
-            // fp32 op_mm with the transposed view, softmax in place, fp32 op_mm into the head's columns
-            if ((e = launch_mm_f32_batched(E->qkv, 3 * d, 1, dk, E->qkv + d, 1, 3 * d, dk, E->scores, seq, 1,
-                                           (int64_t)seq * seq, seq, seq, dk, H, s)))
-                return e;
-            if ((e = launch_softmax_rows(E->scores, E->scores, (int64_t)H * seq, seq, scale, s))) return e;
-            e = launch_mm_f32_batched(E->scores, seq, 1, (int64_t)seq * seq, E->qkv + 2 * d, 3 * d, 1, dk, E->heads, d, 1,
-                                      dk, seq, dk, seq, H, s);
-        }
-        if (e) return e;
+        // (else the three launches through E->scores), Q, K and V the thirds of qkv
+        if ((e = launch_attention(E->qkv, 3 * d, E->qkv + d, 3 * d, E->qkv + 2 * d, 3 * d, E->heads, d, seq, seq, H, dk,
+                                  scale, E->scores, s)))
+            return e;
         // output = multiHeadOut @ W_O; LN(output + multiHeadOut)         (transformer.cu:52-59)
         if ((e = linear(*E, E->heads, seq, d, B.wo, d, E->t, nullptr, false, s))) return e;
         // (x1 is packed by the same launch: the FFN's first linear quantizes nothing itself)

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <vector>
+
 namespace qgemm {
 
 // Packed operand geometry (include/qgemm.h): rows padded to the GEMM macro-tile, k to its k-step.
@@ -219,11 +221,19 @@ hipError_t launch_mm_f32_batched(const float *A, int64_t ash, int64_t asw, int64
                                  int n, int k, int batch, hipStream_t stream);
 // Encoder row ops (encoder_ops.hip): the reference's op_softmax (after op_multiply by `scale`) and
 // op_add + op_layernorm, one row per wave, sums in the reference's sequential order.
-// S = QK^T, softmax(S * scale), heads = PV for every head in one launch (S in LDS), bit-identical to
-// the three separate kernels; hipErrorNotSupported outside d_k <= 64, seq <= 512 (caller falls back).
-// qkv: seq x 3d ([Q | K | V], head h at columns h*d_k of each third); heads: seq x d.
-hipError_t launch_attention_fused(const float *qkv, int seq, int d, int n_heads, float scale, float *heads,
+// S = QK^T, softmax(S * scale), O = PV for every head in one launch (S in LDS), bit-identical to
+// the three separate kernels; hipErrorNotSupported outside attention_fused_ok (d_k <= 64, seq_kv <= 512).
+// Q, O: seq_q rows; K, V: seq_kv rows; row strides ld* in floats, unit inner stride, head h at columns
+// h*d_k .. of each matrix.  O must not overlap Q, K or V.
+bool attention_fused_ok(int seq_kv, int dk);
+hipError_t launch_attention_fused(const float *Q, int64_t ldq, const float *K, int64_t ldk, const float *V, int64_t ldv,
+                                  float *O, int64_t ldo, int seq_q, int seq_kv, int n_heads, int dk, float scale,
                                   hipStream_t stream);
+// The fused launch where it fits, else launch_mm_f32_batched + launch_softmax_rows + launch_mm_f32_batched through
+// scores (n_heads x seq_q x seq_kv floats; may be nullptr inside the fused envelope; seq_kv <= 4096).
+hipError_t launch_attention(const float *Q, int64_t ldq, const float *K, int64_t ldk, const float *V, int64_t ldv,
+                            float *O, int64_t ldo, int seq_q, int seq_kv, int n_heads, int dk, float scale,
+                            float *scores, hipStream_t stream);
 hipError_t launch_softmax_rows(const float *S, float *P, int64_t rows, int w, float scale, hipStream_t stream);
 hipError_t launch_add_layernorm_rows(const float *A, const float *B, float *Y, int64_t rows, int w,
                                      hipStream_t stream);
@@ -260,6 +270,18 @@ float encoder_init_bound(int n);
 hipError_t encoder_create(int d_model, int n_heads, int d_ff, int n_blocks, int max_seq, uint64_t seed, Encoder **out);
 hipError_t encoder_forward(Encoder *E, const float *X, float *Y, int seq, hipStream_t s);
 void encoder_destroy(Encoder *E);
+// draws a k x n fp32 weight into tmp (col_seeds[c] fills columns [c*cols_per_seed, (c+1)*cols_per_seed), one
+// reference tensor each, uniform [-bound, bound)) and packs it as B into a fresh allocation; tmp holds
+// k * n + k * cols_per_seed floats
+hipError_t encoder_make_packed(int k, int n, const std::vector<uint64_t> &col_seeds, int cols_per_seed, float bound,
+                               void **packed, float *tmp, hipStream_t s);
+// The decoder counterpart (decoder.hip).
+struct Decoder;
+hipError_t decoder_create(int d_model, int n_heads, int d_ff, int n_blocks, int max_seq, int max_enc_seq, uint64_t seed,
+                          Decoder **out);
+hipError_t decoder_forward(Decoder *D, const float *X, const float *enc_out, float *Y, int seq, int enc_seq,
+                           hipStream_t s);
+void decoder_destroy(Decoder *D);
 const char *gemm_config_name();
 // Quantization-error statistics on the device (error_stats.hip); scratch = error_stats_scratch_bytes().
 size_t error_stats_scratch_bytes();
