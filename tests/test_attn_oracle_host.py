@@ -11,6 +11,7 @@ import ctypes
 import numpy as np
 import pytest
 
+import attn_cases
 import attn_oracle
 from util import assert_bits_equal, bits
 
@@ -97,3 +98,113 @@ def test_decoder_weight_kinds_extend_the_encoders(qg, oracle):
     assert qg.DECODER_WEIGHT_KINDS[8:] == ("Wq2", "Wk2", "Wv2", "Wo2")
     for kind in (8, 11):
         assert qg.encoder_weight_seed(13, 1, kind, 2) == oracle.encoder_weight_seed(13, 1, kind, 2)
+
+
+# ---- the special-value sets of tests/attn_cases.py: each produces, in the oracle's result alone, the condition the
+# GPU tests rely on it for (floors, not exact counts) ----
+
+_TINY = np.float32(1.1754944e-38)  # the smallest normal fp32
+
+
+def _subnormal(a):
+    return (a != 0) & (np.abs(a) < _TINY)
+
+
+def _softmax_row(name, row):
+    return attn_cases.softmax_expected(name)[attn_cases.SOFTMAX_ROWS.index(row)]
+
+
+def test_softmax_sets_shapes(oracle):
+    sets = attn_cases.softmax_sets()
+    assert set(sets) == {"scale_1", "scale_0", "scale_neg1", "overflow"}
+    for name, ((S, scale), what) in sets.items():
+        assert S.dtype == np.float32 and S.shape[1] == attn_cases.SOFTMAX_W and what
+        assert S.shape[0] == (1 if name == "overflow" else len(attn_cases.SOFTMAX_ROWS))
+    S = sets["scale_1"][0][0]
+    assert np.signbit(S[2, 0]) and S[2, 0] == 0 and not np.signbit(S[2, 7]) and S[2, 7] == 0 and (S[2] <= 0).all()
+    assert np.signbit(S[2, 3::3]).all() and (S[2, 3::3] == 0).all()
+    assert np.isnan(S[3, 0]) and np.isnan(S[4, 100]) and np.isposinf(S[5, 150])
+    assert np.isneginf(np.delete(S[1], 77)).all() and np.isfinite(S[1, 77])
+
+
+def test_softmax_set_scale_1(oracle):
+    a = _softmax_row("scale_1", "a")
+    assert np.isfinite(a).all() and _subnormal(a).sum() >= 20 and (a == 0).sum() >= 5 and not np.signbit(a).any()
+    b = _softmax_row("scale_1", "b")
+    assert b[77] == 1.0 and (np.delete(b, 77) == 0).all() and not np.signbit(b).any()
+    c = _softmax_row("scale_1", "c")
+    assert np.isfinite(c).all() and c[0] == c[7] and c[0] == c.max()
+    for row in "def":
+        assert np.isnan(_softmax_row("scale_1", row)).all(), row
+
+
+@pytest.mark.parametrize("name", ["scale_0", "scale_neg1"])
+def test_softmax_sets_scale_0_and_minus_1(oracle, name):
+    """Scale 0 turns every infinity into NaN (rows b and f) and every finite row into the uniform 1 / w; scale -1 turns
+    row b's -inf into +inf (inf - inf: NaN) and row f's +inf into a -inf whose exp is +0, so f comes out finite."""
+    a, c = _softmax_row(name, "a"), _softmax_row(name, "c")
+    assert np.isfinite(a).all() and np.isfinite(c).all()
+    for row in "bde":
+        assert np.isnan(_softmax_row(name, row)).all(), row
+    f = _softmax_row(name, "f")
+    if name == "scale_0":
+        assert np.isnan(f).all()
+        assert (a == a[0]).all() and (c == c[0]).all() and a[0] > 0
+    else:
+        assert np.isfinite(f).all() and f[150] == 0 and (np.delete(f, 150) > 0).all()
+        assert _subnormal(a).sum() >= 20 and (a == 0).sum() >= 5   # row a reversed: the same exps, from the far end
+
+
+def test_softmax_set_overflow(oracle):
+    (S, scale), _ = attn_cases.softmax_sets()["overflow"]
+    with np.errstate(over="ignore"):
+        prod = S * np.float32(scale)
+    assert prod[0, 0] == 0 and np.isneginf(prod[0, 1:]).all()
+    p = attn_cases.softmax_expected("overflow")[0]
+    assert not np.isnan(p).any() and p[0] == 1.0 and (p == 0).sum() >= attn_cases.SOFTMAX_W - 1
+
+
+@pytest.mark.parametrize("shape", [attn_cases.ATTN_BASE, attn_cases.ATTN_FALLBACK], ids=["fused", "fallback"])
+def test_attention_sets_produce_their_conditions(qg, oracle, shape):
+    seq_q, seq_kv, H, dk = shape
+    sets = attn_cases.attention_sets(shape)
+    assert tuple(sets) == attn_cases.ATTENTION_NAMES
+    fused = qg.load().qgemm_attention_workspace_size(seq_q, seq_kv, H, dk) == 0
+    assert fused == (shape == attn_cases.ATTN_BASE)
+    want = {n: attn_cases.attention_expected(n, shape) for n in sets}
+    for n, ((Q, K, V), what) in sets.items():
+        assert Q.shape == (seq_q, H * dk) and K.shape == V.shape == (seq_kv, H * dk) and what
+        assert want[n].shape == Q.shape
+
+    plain = attn_oracle.attention_ref(*(oracle.uniform(s, attn_cases.ATTN_SEED + i) for i, s in enumerate(
+        [(seq_q, H * dk), (seq_kv, H * dk), (seq_kv, H * dk)])), H, attn_oracle.default_scale(dk))
+    w = want["nan_in_k"]
+    assert np.isnan(w[:, :dk]).all() and np.isfinite(w[:, dk:]).all()
+    assert_bits_equal(w[:, dk:], plain[:, dk:], "head 1 beside a NaN head")
+    w = want["inf_in_v"]
+    assert np.isposinf(w[:, 30]).all() and np.isfinite(np.delete(w, 30, axis=1)).all()
+    w = want["inf_in_v_peaked"]
+    assert np.isposinf(w[:, 30]).sum() >= 1 and np.isnan(w[:, 30]).sum() >= 1
+    assert np.isfinite(np.delete(w, 30, axis=1)).all()
+    w = want["zero_q_row"]
+    assert np.isfinite(w).all()
+    V = sets["zero_q_row"][0][2]
+    P = np.full((1, seq_kv), np.float32(1.0) / np.float32(seq_kv), np.float32)  # exp(0) / fl(sum of seq_kv ones)
+    assert_bits_equal(w[4:5], oracle.mm_fp32(P, V), "row 4 is the uniform average of V")
+    w = want["overflowing_scores"]
+    assert np.isnan(w[5, :dk]).all() and np.isfinite(np.delete(w, 5, axis=0)).all() and np.isfinite(w[5, dk:]).all()
+    assert (bits(want["neg_zero_v"]) == 0).all()
+    w = want["tiny_v"]
+    assert _subnormal(w).sum() >= 1000 and (w != 0).all()
+
+
+def test_zero_row_decoder_inputs_stay_finite(oracle):
+    """A zero row of X or enc_out has absmax 0 and scale inf; 0 * inf is NaN and the pack stores it as 0.  The
+    oracle's result for these inputs is finite everywhere, and differs from the plain inputs' in nearly every bit."""
+    X, enc = attn_cases.zero_row_decoder_inputs()
+    assert not X[3].any() and not enc[7].any() and X[2].any() and enc[6].any()
+    Y = attn_oracle.decoder_forward_ref(X, enc, 64, 2, 96, 2, 13)
+    assert np.isfinite(Y).all()
+    plain = attn_oracle.decoder_forward_ref(oracle.uniform((33, 64), 11), oracle.uniform((100, 64), 12), 64, 2, 96, 2,
+                                            13)
+    assert (bits(Y) != bits(plain)).mean() > 0.9, "the zero rows reach every output through both attentions"

@@ -3,11 +3,15 @@
 The encoder's quantized linears (Q/K/V, W_O, FFN with fused bias / relu), fp32 attention GEMMs,
 softmax and add + layernorm are each compared with the oracle restatement bit for bit, then the
 whole stack at the reference's own shape (transformer.cu:171-178), a small shape and config 5.
+Further down: the softmax on special values (tests/attn_cases.py), at the ends of its width range and the seams of its
+sum; the Encoder object with a split-K GEMM inside, without scratch where the plan wants a split, in a replayed graph
+and on two streams.
 """
 import numpy as np
 import pytest
 import torch
 
+import attn_cases
 from util import assert_bits_equal
 
 pytestmark = pytest.mark.gpu
@@ -180,3 +184,169 @@ def test_transformer_harness_matches_oracle(qg, oracle):
     want = oracle.encoder_forward(X, 8, 4, 8, 2, seed)
     assert got == [[f"{v:.6f}" for v in row] for row in want]
     assert "All tests completed successfully!" in lines
+
+
+# ---- qgemm_softmax_rows: special values, the width range's ends and seq_sum's seams, rejected widths.  Every output
+# is pre-filled with NaN ----
+
+def _nan(shape, device):
+    return torch.full(shape, float("nan"), device=device)
+
+
+@pytest.mark.parametrize("in_place", [False, True], ids=["out_of_place", "in_place"])
+@pytest.mark.parametrize("name", ["scale_1", "scale_0", "scale_neg1", "overflow"])
+def test_softmax_rows_special_values(qg, device, name, in_place):
+    """softmax_rows_kernel on the rows of tests/attn_cases.py (each row's condition is asserted on the oracle by
+    tests/test_attn_oracle_host.py): exps through the subnormal range down to +0 and their fl(e / sum), a row of -inf
+    but one element, a maximum that is a zero of both signs in different lanes (the lane reduction's strict >), NaN in
+    the seed column and in a lane's share, +inf; then scale 0, scale -1 and products that overflow -- one wave per row,
+    six different rows in two blocks."""
+    (S, scale), what = attn_cases.softmax_sets()[name]
+    Sd = _dev(S, device)
+    P = Sd if in_place else _nan(S.shape, device)
+    qg.softmax_rows(Sd, scale=scale, P=P)
+    assert_bits_equal(P.cpu().numpy(), attn_cases.softmax_expected(name), f"softmax, {what}")
+
+
+@pytest.mark.parametrize("w", [1, 2, 15, 16, 17, 63, 65, 79, 80, 81, 4095, 4096])
+def test_softmax_rows_width_seams(qg, oracle, device, w):
+    """The two ends of the width range and the seams of seq_sum (groups of 64, then 16, then a scalar tail), five rows:
+    with four rows per block the second block is partial."""
+    rows = 5
+    S = oracle.uniform((rows, w), 23 + w) * np.float32(8.0)
+    P = _nan((rows, w), device)
+    qg.softmax_rows(_dev(S, device), scale=0.125, P=P)
+    assert_bits_equal(P.cpu().numpy(), oracle.softmax_rows(S, 0.125), f"softmax {rows}x{w}")
+
+
+@pytest.mark.parametrize("w", [4097, 0])
+def test_softmax_rows_rejects_widths_outside_its_range(qg, device, w):
+    """Refused on the host with hipErrorInvalidValue before any launch: the NaN prefill of P survives."""
+    rows = 5
+    S = torch.zeros((rows, 4097), device=device)
+    P = _nan((rows, 4097), device)
+    torch.cuda.synchronize()
+    rc = qg.load().qgemm_softmax_rows(S.data_ptr(), P.data_ptr(), rows, w, 0.125,
+                                      torch.cuda.current_stream(device).cuda_stream)
+    assert rc == qg.HIP_ERROR_INVALID_VALUE
+    torch.cuda.synchronize()
+    assert bool(torch.isnan(P).all()), "a rejected call wrote to P"
+
+
+# ---- the Encoder object: split-K inside it, the scratch-less drop to the unsplit kernel, graph replay of a whole
+# forward, two objects on two streams ----
+
+def _plan(qg, m, n, k):
+    import ctypes
+    tile = ctypes.c_int(0)
+    splits = qg.load().qgemm_gemm_plan(m, n, k, ctypes.byref(tile), None)
+    return tile.value, splits
+
+
+SPLIT = (33, 64, 2, 4096, 2)   # (seq, d, H, d_ff, blocks): FFN-down 33 x 64 x 4096 plans 64-tiles x 2 splits
+
+
+def test_encoder_split_k_inside_the_object(qg, oracle, device):
+    """The FFN-down GEMM of this encoder is a split-K launch on the object's own scratch with tickets_zeroed = true:
+    nothing zeroes the tickets but each launch's reducers.  Two blocks per forward and three forwards (inputs A, B, A)
+    on one object: a ticket left non-zero by any launch would break the next one.  With the bias epilogue."""
+    seq, d, H, dff, blocks = SPLIT
+    assert _plan(qg, seq, d, dff) == (64, 2)
+    A, B = oracle.uniform((seq, d), 37), oracle.uniform((seq, d), 38)
+    want = {id(X): oracle.encoder_forward(X, d, H, dff, blocks, 39) for X in (A, B)}
+    enc = qg.Encoder(d, H, dff, blocks, max_seq=seq, seed=39)
+    try:
+        for i, X in enumerate((A, B, A)):
+            Y = _nan((seq, d), device)
+            enc.forward(_dev(X, device), Y=Y)
+            assert_bits_equal(Y.cpu().numpy(), want[id(X)], f"encoder with a split-K FFN-down, forward {i}")
+    finally:
+        enc.close()
+
+
+@pytest.mark.parametrize("d,H,dff,max_seq,seq", [(128, 2, 4096, 4096, 64),     # the smallest such object
+                                                 (1024, 16, 4096, 512, 256)],  # config 5's object at half its length
+                         ids=["small", "config5"])
+def test_encoder_plan_wants_a_split_but_the_object_has_no_scratch(qg, oracle, device, d, H, dff, max_seq, seq):
+    """None of the four linear shapes plans a split at max_seq rows, so the object's split-K scratch is empty; at the
+    shorter seq FFN-down plans 2 splits, and launch_gemm_dequant must drop to the unsplit kernel (scratch too small)
+    and give the same bits."""
+    for n, k in ((3 * d, d), (d, d), (dff, d), (d, dff)):
+        assert _plan(qg, max_seq, n, k)[1] == 1, (max_seq, n, k)
+    assert _plan(qg, seq, d, dff) == (64, 2)
+    if max_seq == 512:
+        assert _plan(qg, max_seq, d, dff)[0] == 32
+    X = oracle.uniform((seq, d), 41)
+    enc = qg.Encoder(d, H, dff, 1, max_seq=max_seq, seed=43)
+    try:
+        Y = _nan((seq, d), device)
+        enc.forward(_dev(X, device), Y=Y)
+        got = Y.cpu().numpy()
+    finally:
+        enc.close()
+    assert_bits_equal(got, oracle.encoder_forward(X, d, H, dff, 1, 43), f"encoder d={d} max_seq={max_seq} at seq={seq}")
+
+
+@pytest.mark.parametrize("seq,d,H,dff,blocks", [SPLIT,                     # split-K tickets inside a replayed graph
+                                                (100, 256, 8, 512, 2)],    # fused attention, no split
+                         ids=["split_k", "fused_attention"])
+def test_encoder_forward_graph_capture_and_replay(qg, oracle, device, seq, d, H, dff, blocks):
+    """Encoder.forward allocates nothing and does not synchronize: the object is made first, one forward is warmed up
+    on the side stream, one is captured into static X / Y and replayed three times on new inputs.  On the split shape
+    the tickets are re-zeroed by kernels inside the graph (a memset node once left them unzeroed on replay: see
+    launch_gemm_dequant), so every replay must find them zero."""
+    assert (_plan(qg, seq, d, dff)[1] > 1) == (dff == 4096)
+    enc = qg.Encoder(d, H, dff, blocks, max_seq=seq, seed=47)
+    try:
+        Xs, Y = torch.zeros((seq, d), device=device), _nan((seq, d), device)
+        Xs.copy_(_dev(oracle.uniform((seq, d), 48), device))
+        torch.cuda.synchronize()
+        s = torch.cuda.Stream(device)
+        with torch.cuda.stream(s):
+            enc.forward(Xs, Y=Y)
+            s.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, stream=s):
+                enc.forward(Xs, Y=Y)
+        for i in range(3):
+            X = oracle.uniform((seq, d), 49 + i)
+            Xs.copy_(_dev(X, device))
+            Y.fill_(float("nan"))
+            torch.cuda.synchronize()
+            g.replay()
+            torch.cuda.synchronize()
+            assert_bits_equal(Y.cpu().numpy(), oracle.encoder_forward(X, d, H, dff, blocks, 47),
+                              f"encoder graph replay {i}, d_ff={dff}")
+    finally:
+        torch.cuda.synchronize()
+        enc.close()
+
+
+def test_encoders_on_two_streams(qg, oracle, device):
+    """Two objects, one with fused attention and one on the three-launch fallback (d_k 128), forward at the same time
+    on two streams, five interleaved rounds and one synchronize: an object's buffers, packed activations and scratch
+    are its own."""
+    cfgs = [(100, 256, 8, 512, 2, 53), (60, 128, 1, 64, 1, 59)]   # (seq, d, H, d_ff, blocks, seed)
+    lanes = []
+    try:
+        for li, (seq, d, H, dff, blocks, seed) in enumerate(cfgs):
+            assert (qg.load().qgemm_attention_workspace_size(seq, seq, H, d // H) == 0) == (li == 0)
+            rounds = []
+            for r in range(5):
+                X = oracle.uniform((seq, d), 61 + 10 * li + r)
+                rounds.append((_dev(X, device), _nan((seq, d), device),
+                               oracle.encoder_forward(X, d, H, dff, blocks, seed)))
+            lanes.append((qg.Encoder(d, H, dff, blocks, max_seq=seq, seed=seed), torch.cuda.Stream(device), rounds))
+        torch.cuda.synchronize()
+        for r in range(5):
+            for enc, s, rounds in lanes:
+                with torch.cuda.stream(s):
+                    enc.forward(rounds[r][0], Y=rounds[r][1])
+        torch.cuda.synchronize()
+        for li, (_, _, rounds) in enumerate(lanes):
+            for r, (_, Y, want) in enumerate(rounds):
+                assert_bits_equal(Y.cpu().numpy(), want, f"encoder stream {li} round {r}")
+    finally:
+        torch.cuda.synchronize()
+        for enc, _, _ in lanes:
+            enc.close()
