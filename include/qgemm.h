@@ -149,6 +149,13 @@ QGEMM_API int qgemm_linear_dt(const void *X, int x_dtype, int64_t x_stride_h, in
 /* op_multiply(S, scale) then op_softmax (attention.cuh:65-68, op_softmax.cuh:6-29), per row of w
  * contiguous floats (w <= 4096); P may equal S.  exp is the correctly rounded fp32 exp. */
 QGEMM_API int qgemm_softmax_rows(const float *S, float *P, int64_t rows, int w, float scale, void *stream);
+/* The same under the causal mask of qgemm_attention_causal: the rows are a stack of rows / seq_q score matrices of
+ * seq_q rows each; row r is query i = r % seq_q and sees its first L_i = min(w, i + q_pos0 + 1) columns.  Its
+ * result is qgemm_softmax_rows' on a row of width L_i (columns L_i .. w-1 are never read), then +0 in columns
+ * L_i .. w-1.  P may equal S.  hipErrorInvalidValue: a null pointer, w < 1 or > 4096, rows < 0, seq_q < 1,
+ * rows % seq_q != 0, q_pos0 < 0. */
+QGEMM_API int qgemm_softmax_rows_causal(const float *S, float *P, int64_t rows, int w, float scale, int seq_q,
+                              int q_pos0, void *stream);
 /* op_add(A, B) then op_layernorm (transformer.cu:58-59, op_layernorm.cuh:6-33) as written:
  * (y - mean) / var, sums in column order, pow(d, 2) = fl32(d*d); rows of w <= 4096 floats. */
 QGEMM_API int qgemm_add_layernorm_rows(const float *A, const float *B, float *Y, int64_t rows, int w, void *stream);
@@ -170,7 +177,7 @@ QGEMM_API int qgemm_encoder_destroy(void *encoder);
  * bit-identical to qgemm_mm_fp32 + qgemm_softmax_rows + qgemm_mm_fp32 per head.  Q and O have seq_q rows, K and V
  * seq_kv rows (the decoder's cross-attention: queries from one stream, keys and values from another, of another
  * length); each matrix has its own base pointer and row stride in floats (*_stride_h) and unit inner stride, so
- * column slices of wider buffers work (the encoder passes the thirds of one [Q | K | V] buffer).  No mask.
+ * column slices of wider buffers work (the encoder passes the thirds of one [Q | K | V] buffer).  No mask (qgemm_attention_causal has one).
  * O must not overlap Q, K or V (not checked).
  * One fused launch (the scores stay on chip) for d_k <= 64 and seq_kv <= 512, any seq_q; outside that three
  * launches through `workspace`, n_heads x seq_q x seq_kv floats of scores: qgemm_attention_workspace_size returns
@@ -183,17 +190,46 @@ QGEMM_API int qgemm_attention(const float *Q, int64_t q_stride_h, const float *K
                     const float *V, int64_t v_stride_h, float *O, int64_t o_stride_h,
                     int seq_q, int seq_kv, int n_heads, int d_k, float scale,
                     void *workspace, size_t ws_bytes, void *stream);
+/* qgemm_attention under a causal mask.  q_pos0 >= 0 is the position of query row 0 in the key sequence: query row
+ * i sees keys 0 .. L_i - 1, L_i = min(seq_kv, i + q_pos0 + 1) >= 1 (self-attention: q_pos0 = 0; queries appended
+ * to a key / value cache: q_pos0 = seq_kv - seq_q).
+ *   S_h as qgemm_attention's.
+ *   P_h: row i is qgemm_softmax_rows' result on the first L_i columns of fl(S_h*scale) (seed the first element,
+ *        strict >, correctly rounded exp, one sum in column order); columns L_i .. seq_kv-1 are +0.  No masked
+ *        score reaches the result: a NaN or inf in a K row that no query of the call sees changes nothing.
+ *   O_h = P_h V_h, the chain over ALL seq_kv keys as qgemm_attention's: a masked key contributes fmaf(+0, v, acc),
+ *        so a non-finite V at a key masked for row i makes that row's column NaN (0 * inf), as an underflowed P does
+ *        without a mask.
+ * Bit-identical on every input to qgemm_mm_fp32 + qgemm_softmax_rows_causal + qgemm_mm_fp32 per head, on the fused
+ * launch and on the three-launch path alike.  With q_pos0 >= seq_kv - 1 the mask hides nothing and the result is
+ * qgemm_attention's bit for bit.  Where V is finite at the masked keys and no product underflows to -0, row i
+ * equals row 0 of qgemm_attention(Q[i], K[:L_i], V[:L_i]).
+ * Workspace, envelope and argument checks as qgemm_attention (qgemm_attention_workspace_size); also
+ * hipErrorInvalidValue before any launch for q_pos0 < 0. */
+QGEMM_API int qgemm_attention_causal(const float *Q, int64_t q_stride_h, const float *K, int64_t k_stride_h,
+                           const float *V, int64_t v_stride_h, float *O, int64_t o_stride_h,
+                           int seq_q, int seq_kv, int n_heads, int d_k, float scale, int q_pos0,
+                           void *workspace, size_t ws_bytes, void *stream);
 
 /* ---- The decoder counterpart (transformer.cu:79-168) --------------------------------------------------
  * Decoder stack with seeded weights drawn once and packed, like the encoder's.  X, Y: seq x d_model; enc_out:
  * enc_seq x d_model; all row-major contiguous fp32 device arrays; seq <= max_seq <= 4096, enc_seq <= max_enc_seq
  * <= 4096, d_model <= 4096, d_model % n_heads == 0.  Per block: self-attention on the block input (the encoder's
  * first half), cross-attention with queries from the decoder stream and keys / values from enc_out, then the FFN
- * whose residual is the cross-attention's multiHeadOut (DESIGN.md "Decoder").  No causal mask, as the reference.
+ * whose residual is the cross-attention's multiHeadOut (DESIGN.md "Decoder").  No causal mask, as the reference
+ * (qgemm_decoder_create_ex adds one).
  * Weight kinds 0..7 as qgemm_encoder_create; 8, 9, 10 = the cross-attention's Wq2, Wk2, Wv2 (one d_model x d_k
  * tensor per head, bound 1/sqrt(d_k)); 11 = its output projection W_O2 (head 0, U(-1, 1)). */
 QGEMM_API int qgemm_decoder_create(int d_model, int n_heads, int d_ff, int n_blocks, int max_seq, int max_enc_seq,
                          uint64_t seed, void **decoder);
+/* qgemm_decoder_create with flags (0: exactly qgemm_decoder_create).  QGEMM_DECODER_CAUSAL: every block's
+ * SELF-attention runs under the causal mask with q_pos0 = 0 (row i sees rows 0 .. i); the cross-attention stays
+ * unmasked.  Every other step is row-local, so row i of a forward then depends on rows 0 .. i of X and on enc_out
+ * alone: forward(X[:n]) equals the first n rows of forward(X) bit for bit.  An unknown flag bit:
+ * hipErrorInvalidValue.  Forward and destroy are the same calls. */
+enum { QGEMM_DECODER_CAUSAL = 1 };
+QGEMM_API int qgemm_decoder_create_ex(int d_model, int n_heads, int d_ff, int n_blocks, int max_seq, int max_enc_seq,
+                            uint64_t seed, int flags, void **decoder);
 QGEMM_API int qgemm_decoder_forward(void *decoder, const float *X, const float *enc_out, float *Y, int seq, int enc_seq,
                           void *stream);
 QGEMM_API int qgemm_decoder_destroy(void *decoder);

@@ -25,16 +25,16 @@ int main(int argc, char **argv) {
     const float scale = 1.0f / 8.0f;
     // the encoder's layout: Q, K and V the thirds of one [seq x 3d] buffer, seq_q = seq_kv
     typedef void (*K)(const float *, int64_t, const float *, int64_t, const float *, int64_t, float *, int64_t, int, int,
-                      int, float);
+                      int, float, int);
     const int64_t ld = 3 * (int64_t)d;
-#define ATTN_ARGS qkv, ld, qkv + d, ld, qkv + 2 * d, ld, heads, (int64_t)d, dk, seq, seq, scale
+#define ATTN_ARGS qkv, ld, qkv + d, ld, qkv + 2 * d, ld, heads, (int64_t)d, dk, seq, seq, scale, 0
     struct V { const char *name; K k; int tq, threads; };
-    std::vector<V> vs = {{"t32 full", attention_fused_kernel<32, 256, 1024, 0>, 32, 1024},
-                         {"t32 no_qk", attention_fused_kernel<32, 256, 1024, 1>, 32, 1024},
-                         {"t32 no_softmax", attention_fused_kernel<32, 256, 1024, 2 | 8>, 32, 1024},
-                         {"t32 no_sums", attention_fused_kernel<32, 256, 1024, 8>, 32, 1024},
-                         {"t32 no_pv", attention_fused_kernel<32, 256, 1024, 4>, 32, 1024},
-                         {"t32 nothing", attention_fused_kernel<32, 256, 1024, 15>, 32, 1024}};
+    std::vector<V> vs = {{"t32 full", attention_fused_kernel<32, 256, 1024, false, 0>, 32, 1024},
+                         {"t32 no_qk", attention_fused_kernel<32, 256, 1024, false, 1>, 32, 1024},
+                         {"t32 no_softmax", attention_fused_kernel<32, 256, 1024, false, 2 | 8>, 32, 1024},
+                         {"t32 no_sums", attention_fused_kernel<32, 256, 1024, false, 8>, 32, 1024},
+                         {"t32 no_pv", attention_fused_kernel<32, 256, 1024, false, 4>, 32, 1024},
+                         {"t32 nothing", attention_fused_kernel<32, 256, 1024, false, 15>, 32, 1024}};
     hipEvent_t a, z; CK(hipEventCreate(&a)); CK(hipEventCreate(&z));
     std::vector<std::vector<float>> t(vs.size());
     for (int r = 0; r < 7; ++r)
@@ -53,7 +53,7 @@ int main(int argc, char **argv) {
     const dim3 g((seq + 31) / 32, H);
     // phase stamps (block-median durations, 100 MHz ticks): Q loads + K chunk 0 staged | QK | softmax |
     // V chunk 0 staged | PV
-    for (int w = 0; w < 5; ++w) attention_fused_kernel<32, 256, 1024, 16><<<g, 1024>>>(ATTN_ARGS);
+    for (int w = 0; w < 5; ++w) attention_fused_kernel<32, 256, 1024, false, 16><<<g, 1024>>>(ATTN_ARGS);
     CK(hipDeviceSynchronize());
     const int nb = g.x * g.y;
     std::vector<unsigned long long> st((size_t)4096 * 8);

@@ -58,13 +58,16 @@ EXPORTED_SYMBOLS = (
     "op_mm_quantize_prepacked_workspace_size",
     "op_mm_quantize_prepacked_ws",
     "qgemm_softmax_rows",
+    "qgemm_softmax_rows_causal",
     "qgemm_add_layernorm_rows",
     "qgemm_encoder_create",
     "qgemm_encoder_forward",
     "qgemm_encoder_destroy",
     "qgemm_attention_workspace_size",
     "qgemm_attention",
+    "qgemm_attention_causal",
     "qgemm_decoder_create",
+    "qgemm_decoder_create_ex",
     "qgemm_decoder_forward",
     "qgemm_decoder_destroy",
     "qgemm_mm_outlier_workspace_size",
@@ -101,6 +104,7 @@ COMM_ID_BYTES = 128
 
 HIP_ERROR_INVALID_VALUE = 1
 QGEMM_F32, QGEMM_BF16 = 0, 1  # element-type tags of the _dt entry points (include/qgemm.h)
+QGEMM_DECODER_CAUSAL = 1       # qgemm_decoder_create_ex flag: causal mask on the self-attention
 
 _lock = threading.Lock()
 _lib = None
@@ -173,6 +177,8 @@ def load() -> ctypes.CDLL:
         L.op_mm_quantize_prepacked_ws.restype = i32
         L.qgemm_softmax_rows.argtypes = [vp, vp, i64, i32, f32, vp]
         L.qgemm_softmax_rows.restype = i32
+        L.qgemm_softmax_rows_causal.argtypes = [vp, vp, i64, i32, f32, i32, i32, vp]
+        L.qgemm_softmax_rows_causal.restype = i32
         L.qgemm_add_layernorm_rows.argtypes = [vp, vp, vp, i64, i32, vp]
         L.qgemm_add_layernorm_rows.restype = i32
         L.qgemm_encoder_create.argtypes = [i32, i32, i32, i32, i32, ctypes.c_uint64, ctypes.POINTER(vp)]
@@ -185,6 +191,11 @@ def load() -> ctypes.CDLL:
         L.qgemm_attention_workspace_size.restype = sz
         L.qgemm_attention.argtypes = [vp, i64, vp, i64, vp, i64, vp, i64, i32, i32, i32, i32, f32, vp, sz, vp]
         L.qgemm_attention.restype = i32
+        L.qgemm_attention_causal.argtypes = [vp, i64, vp, i64, vp, i64, vp, i64, i32, i32, i32, i32, f32, i32, vp, sz,
+                                             vp]
+        L.qgemm_attention_causal.restype = i32
+        L.qgemm_decoder_create_ex.argtypes = [i32, i32, i32, i32, i32, i32, ctypes.c_uint64, i32, ctypes.POINTER(vp)]
+        L.qgemm_decoder_create_ex.restype = i32
         L.qgemm_decoder_create.argtypes = [i32, i32, i32, i32, i32, i32, ctypes.c_uint64, ctypes.POINTER(vp)]
         L.qgemm_decoder_create.restype = i32
         L.qgemm_decoder_forward.argtypes = [vp, vp, vp, vp, i32, i32, vp]
@@ -714,6 +725,23 @@ def softmax_rows(S, scale: float = 1.0, P=None):
     return P
 
 
+def softmax_rows_causal(S, seq_q: int, q_pos0: int = 0, scale: float = 1.0, P=None):
+    """softmax_rows under the causal mask (qgemm_softmax_rows_causal): S is a contiguous stack of score matrices of
+    seq_q rows each; query row i = r % seq_q sees its first min(w, i + q_pos0 + 1) columns, the rest of P is +0."""
+    import torch
+    assert isinstance(S, torch.Tensor) and S.dim() >= 2, "S must be a tensor of 2 or more dimensions"
+    assert S.is_cuda and S.dtype == torch.float32 and S.is_contiguous(), "S: contiguous float32 on the device"
+    rows = S.numel() // S.shape[-1]
+    assert seq_q >= 1 and rows % seq_q == 0, "the rows are whole matrices of seq_q rows"
+    assert q_pos0 >= 0
+    P = torch.empty_like(S) if P is None else P
+    assert P.shape == S.shape and P.dtype == torch.float32 and P.is_cuda and P.is_contiguous(), "P: as S"
+    _check("qgemm_softmax_rows_causal",
+           load().qgemm_softmax_rows_causal(S.data_ptr(), P.data_ptr(), rows, S.shape[-1], float(scale), seq_q, q_pos0,
+                                            _stream(S.device)))
+    return P
+
+
 def add_layernorm_rows(A, B, Y=None):
     """op_add(A, B) + op_layernorm (transformer.cu:58-59, op_layernorm.cuh as written)."""
     import torch
@@ -823,12 +851,15 @@ class Encoder:
             pass
 
 
-def attention(Q, K, V, n_heads: int, scale=None, O=None):
+def attention(Q, K, V, n_heads: int, scale=None, O=None, causal: bool = False, q_pos0=None):
     """Multi-head fp32 attention core (qgemm_attention): O_h = softmax(Q_h K_h^T * scale) V_h on columns
     h*d_k .. of each matrix, d_k = Q.shape[1] / n_heads.  Q: seq_q x d, K and V: seq_kv x d -- 2-D fp32 device
     tensors or views with unit inner stride (column slices of wider buffers included); O (seq_q x d) must not
     overlap them.  scale defaults to fl32(1 / sqrt(d_k)), as the encoder computes it.  One fused launch for
-    d_k <= 64 and seq_kv <= 512, else three launches through a scores workspace allocated here."""
+    d_k <= 64 and seq_kv <= 512, else three launches through a scores workspace allocated here.
+    causal=True (qgemm_attention_causal): query row i sees keys 0 .. min(seq_kv, i + q_pos0 + 1) - 1, the masked
+    columns of P are +0.  q_pos0 is the key position of query row 0; left out it is seq_kv - seq_q, the queries
+    aligned to the end of the keys as with a key / value cache (seq_kv >= seq_q is then asserted)."""
     import math
     import torch
     for t, nm in ((Q, "Q"), (K, "K"), (V, "V")):
@@ -845,9 +876,20 @@ def attention(Q, K, V, n_heads: int, scale=None, O=None):
         O = torch.empty((seq_q, d), dtype=torch.float32, device=Q.device)
     _require_device_f32(O, "O")
     assert O.shape == (seq_q, d) and (O.stride(1) == 1 or d == 1), "O: seq_q x d with unit inner stride"
+    assert causal or q_pos0 is None, "q_pos0 belongs to causal=True"
+    if causal and q_pos0 is None:
+        assert seq_kv >= seq_q, "causal without q_pos0 aligns the queries to the end of the keys: seq_kv >= seq_q"
+        q_pos0 = seq_kv - seq_q
     L = load()
     need = L.qgemm_attention_workspace_size(seq_q, seq_kv, n_heads, dk)
     ws = torch.empty(need, dtype=torch.uint8, device=Q.device) if need else None
+    if causal:
+        assert q_pos0 >= 0
+        _check("qgemm_attention_causal",
+               L.qgemm_attention_causal(Q.data_ptr(), Q.stride(0), K.data_ptr(), K.stride(0), V.data_ptr(), V.stride(0),
+                                        O.data_ptr(), O.stride(0), seq_q, seq_kv, n_heads, dk, float(scale), q_pos0,
+                                        ws.data_ptr() if need else None, need, _stream(Q.device)))
+        return O
     _check("qgemm_attention",
            L.qgemm_attention(Q.data_ptr(), Q.stride(0), K.data_ptr(), K.stride(0), V.data_ptr(), V.stride(0),
                              O.data_ptr(), O.stride(0), seq_q, seq_kv, n_heads, dk, float(scale),
@@ -857,15 +899,23 @@ def attention(Q, K, V, n_heads: int, scale=None, O=None):
 
 class Decoder:
     """transformer.cu:79-168's Decoder with its linears on the quantized path: per block self-attention,
-    cross-attention on the encoder's output, FFN (DESIGN.md "Decoder")."""
+    cross-attention on the encoder's output, FFN (DESIGN.md "Decoder").  causal=True (qgemm_decoder_create_ex,
+    QGEMM_DECODER_CAUSAL): the self-attention is masked, row i sees rows 0 .. i, and forward(X[:n]) equals
+    forward(X)[:n] bit for bit."""
 
     def __init__(self, d_model: int, n_heads: int, d_ff: int, n_blocks: int, max_seq: int, max_enc_seq: int,
-                 seed: int = 0):
+                 seed: int = 0, causal: bool = False):
         self.d_model, self.n_heads, self.d_ff, self.n_blocks, self.max_seq, self.max_enc_seq, self.seed = (
             d_model, n_heads, d_ff, n_blocks, max_seq, max_enc_seq, seed)
+        self.causal = bool(causal)
         h = ctypes.c_void_p()
-        _check("qgemm_decoder_create", load().qgemm_decoder_create(d_model, n_heads, d_ff, n_blocks, max_seq,
-                                                                  max_enc_seq, seed, ctypes.byref(h)))
+        if causal:
+            _check("qgemm_decoder_create_ex",
+                   load().qgemm_decoder_create_ex(d_model, n_heads, d_ff, n_blocks, max_seq, max_enc_seq, seed,
+                                                  QGEMM_DECODER_CAUSAL, ctypes.byref(h)))
+        else:
+            _check("qgemm_decoder_create", load().qgemm_decoder_create(d_model, n_heads, d_ff, n_blocks, max_seq,
+                                                                      max_enc_seq, seed, ctypes.byref(h)))
         self._h = h
 
     def forward(self, X, enc_out, Y=None):

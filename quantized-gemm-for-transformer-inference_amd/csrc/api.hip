@@ -358,6 +358,12 @@ int qgemm_softmax_rows(const float *S, float *P, int64_t rows, int w, float scal
     return err(launch_softmax_rows(S, P, rows, w, scale, static_cast<hipStream_t>(stream)));
 }
 
+int qgemm_softmax_rows_causal(const float *S, float *P, int64_t rows, int w, float scale, int seq_q, int q_pos0,
+                              void *stream) {
+    if (!S || !P) return err(hipErrorInvalidValue);
+    return err(launch_softmax_rows_causal(S, P, rows, w, scale, seq_q, q_pos0, static_cast<hipStream_t>(stream)));
+}
+
 int qgemm_add_layernorm_rows(const float *A, const float *B, float *Y, int64_t rows, int w, void *stream) {
     if (!A || !B || !Y) return err(hipErrorInvalidValue);
     return err(launch_add_layernorm_rows(A, B, Y, rows, w, static_cast<hipStream_t>(stream)));
@@ -388,26 +394,50 @@ size_t qgemm_attention_workspace_size(int seq_q, int seq_kv, int n_heads, int d_
     return sizeof(float) * (size_t)n_heads * (size_t)seq_q * (size_t)seq_kv;
 }
 
-int qgemm_attention(const float *Q, int64_t q_stride_h, const float *K, int64_t k_stride_h, const float *V,
-                    int64_t v_stride_h, float *O, int64_t o_stride_h, int seq_q, int seq_kv, int n_heads, int d_k,
-                    float scale, void *workspace, size_t ws_bytes, void *stream) {
-    if (!Q || !K || !V || !O || seq_q < 0 || seq_kv < 1 || seq_kv > 4096 || n_heads < 1 || d_k < 1)
+// qgemm_attention (q_pos0 = kNoMask) and qgemm_attention_causal: the same checks and the same workspace
+static int attention_entry(const float *Q, int64_t q_stride_h, const float *K, int64_t k_stride_h, const float *V,
+                           int64_t v_stride_h, float *O, int64_t o_stride_h, int seq_q, int seq_kv, int n_heads,
+                           int d_k, float scale, int q_pos0, void *workspace, size_t ws_bytes, void *stream) {
+    if (!Q || !K || !V || !O || seq_q < 0 || seq_kv < 1 || seq_kv > 4096 || n_heads < 1 || d_k < 1 || q_pos0 < kNoMask)
         return err(hipErrorInvalidValue);
     const size_t need = qgemm_attention_workspace_size(seq_q, seq_kv, n_heads, d_k);
     if (need && (!workspace || ws_bytes < need)) return err(hipErrorInvalidValue);
     if (seq_q == 0) return 0;
     return err(launch_attention(Q, q_stride_h, K, k_stride_h, V, v_stride_h, O, o_stride_h, seq_q, seq_kv, n_heads, d_k,
-                                scale, need ? static_cast<float *>(workspace) : nullptr,
+                                scale, q_pos0, need ? static_cast<float *>(workspace) : nullptr,
                                 static_cast<hipStream_t>(stream)));
+}
+
+int qgemm_attention(const float *Q, int64_t q_stride_h, const float *K, int64_t k_stride_h, const float *V,
+                    int64_t v_stride_h, float *O, int64_t o_stride_h, int seq_q, int seq_kv, int n_heads, int d_k,
+                    float scale, void *workspace, size_t ws_bytes, void *stream) {
+    return attention_entry(Q, q_stride_h, K, k_stride_h, V, v_stride_h, O, o_stride_h, seq_q, seq_kv, n_heads, d_k,
+                           scale, kNoMask, workspace, ws_bytes, stream);
+}
+
+int qgemm_attention_causal(const float *Q, int64_t q_stride_h, const float *K, int64_t k_stride_h, const float *V,
+                           int64_t v_stride_h, float *O, int64_t o_stride_h, int seq_q, int seq_kv, int n_heads,
+                           int d_k, float scale, int q_pos0, void *workspace, size_t ws_bytes, void *stream) {
+    if (q_pos0 < 0) return err(hipErrorInvalidValue);
+    return attention_entry(Q, q_stride_h, K, k_stride_h, V, v_stride_h, O, o_stride_h, seq_q, seq_kv, n_heads, d_k,
+                           scale, q_pos0, workspace, ws_bytes, stream);
+}
+
+int qgemm_decoder_create_ex(int d_model, int n_heads, int d_ff, int n_blocks, int max_seq, int max_enc_seq,
+                            uint64_t seed, int flags, void **decoder) {
+    if (!decoder) return err(hipErrorInvalidValue);
+    *decoder = nullptr;
+    if (flags & ~QGEMM_DECODER_CAUSAL) return err(hipErrorInvalidValue);
+    Decoder *D = nullptr;
+    hipError_t e = decoder_create(d_model, n_heads, d_ff, n_blocks, max_seq, max_enc_seq, seed,
+                                  (flags & QGEMM_DECODER_CAUSAL) != 0, &D);
+    *decoder = D;
+    return err(e);
 }
 
 int qgemm_decoder_create(int d_model, int n_heads, int d_ff, int n_blocks, int max_seq, int max_enc_seq, uint64_t seed,
                          void **decoder) {
-    if (!decoder) return err(hipErrorInvalidValue);
-    Decoder *D = nullptr;
-    hipError_t e = decoder_create(d_model, n_heads, d_ff, n_blocks, max_seq, max_enc_seq, seed, &D);
-    *decoder = D;
-    return err(e);
+    return qgemm_decoder_create_ex(d_model, n_heads, d_ff, n_blocks, max_seq, max_enc_seq, seed, 0, decoder);
 }
 
 int qgemm_decoder_forward(void *decoder, const float *X, const float *enc_out, float *Y, int seq, int enc_seq,

@@ -20,6 +20,10 @@
 // Envelope: d_k <= 64, seq_kv <= 512, any seq_q (S tile 32 x 512 fp32 = 64 KiB of LDS, Q tile and K / V
 // staged through LDS in 256-key chunks: 155 KiB in all); outside it launch_attention (encoder.hip) runs the
 // three kernels.
+// kCausal: query row i sees keys 0 .. L_i - 1, L_i = min(seq_kv, i + q_pos0 + 1).  The softmax of
+// row i is softmax_rows_kernel's on a row of width L_i and P is +0 from column L_i on; P V still runs over all of
+// seq_kv (a masked key contributes fmaf(+0, v, acc), so 0 * inf is NaN as without a mask).  Q K^T tiles that lie
+// past the workgroup's largest limit are not computed.  kCausal = false is the kernel without any of this.
 #include "qgemm_internal.h"
 
 #include <type_traits>
@@ -51,10 +55,10 @@ struct AttnTile {
 
 typedef float v4f __attribute__((ext_vector_type(4)));
 
-template <int kTQ, int kChunk, int kThreads>
+template <int kTQ, int kChunk, int kThreads, bool kCausal>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))) void attention_fused_kernel(
     const float *__restrict__ Q, int64_t ldq, const float *__restrict__ K, int64_t ldk, const float *__restrict__ V,
-    int64_t ldv, float *__restrict__ O, int64_t ldo, int dk, int seq_q, int seq_kv, float scale) {
+    int64_t ldv, float *__restrict__ O, int64_t ldo, int dk, int seq_q, int seq_kv, float scale, int q_pos0) {
     using T = AttnTile<kTQ, kChunk, kThreads>;
     constexpr int kAttnThreads = kThreads, kRF = T::kRowFrags;
     __shared__ __attribute__((aligned(16))) float S[kTQ * kSStride];
@@ -74,6 +78,21 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
     const int nchunks = (seq + kChunk - 1) / kChunk;
     const int seq32 = (seq + 31) & ~31;  // the reference's k extent for P V: seq zero-padded to its 32-wide tile
     const int dk4 = (dk + 3) >> 2;  // float4 columns of a K / V row (the last one zero-padded)
+    // kCausal: query row i sees keys 0 .. limit(i) - 1, limit(i) = min(seq, i + q_pos0 + 1) >= 1 (q_pos0 <= seq: the
+    // launcher clamps it, so the sums stay in int range); lmax = the largest limit of this workgroup's rows.  Q K^T
+    // runs only up to lmax; every softmax row runs to its own limit and stores +0 past it; P V runs all of seq32
+    auto limit = [&](int rl) __attribute__((always_inline)) { return kCausal ? min(seq, q0 + rl + q_pos0 + 1) : seq; };
+    const int lmax = limit(rows - 1);
+    const int nck = (lmax + kChunk - 1) / kChunk;  // the K chunks that start below lmax (= nchunks without a mask)
+    // kCausal: the exp and divide loops of a row run to its limit ROUNDED UP to 64 (`upto`), so every lane of the wave
+    // makes the same number of trips.  A tile's limits are no multiples of 64; with the loops ending at the limit
+    // itself some lanes had 8 columns and others 7, and the 4-way unrolled exp loop ran its main form twice for the
+    // first and its main, 2-element and 1-element forms for the others: 11 passes over the double-precision exp
+    // instead of 8, measured 2.2 us per launch at 512 x 512.  The at most 63 columns past the limit
+    // that these loops pass over hold raw scores or stale LDS on the way in and garbage on the way out (NaN
+    // included); nothing that reaches the output reads them -- the max stops at the limit, the sum chain puts -0.0f
+    // in their place, and the row stores +0 over them before P V.  They lie inside the S row (limit <= 512 < kSStride)
+    auto upto = [&](int li) __attribute__((always_inline)) { return kCausal ? (li + 63) & ~63 : seq; };
 
     // K / V chunks as float4 pieces, kPer per thread, fetched into registers one chunk ahead -- chunk
     // c+1's global loads are in flight under chunk c's MFMAs, V chunk 0's under the last QK chunk and
@@ -125,11 +144,11 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
         *reinterpret_cast<float4 *>(Qs + row * kQStride + 4 * c4) = v;
     }
     float qa[kRF][16];
-    for (int c = 0; c < nchunks; ++c) {
+    for (int c = 0; c < nck; ++c) {
         if (c) __syncthreads();  // every wave is done with the previous chunk
         put(pf, kKStride);
         __syncthreads();
-        if (c + 1 < nchunks) fetch(pf, Kb, ldk, (c + 1) * kChunk);
+        if (c + 1 < nck) fetch(pf, Kb, ldk, (c + 1) * kChunk);
         else fetch(pf, Vb, ldv, 0);
         if (c == 0) {
 #pragma unroll
@@ -138,7 +157,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
                 for (int s = 0; s < 16; ++s) qa[rf][s] = Qs[(rf * 16 + lr) * kQStride + 4 * s + lk];
         }
         const int col = c * kChunk + wave * 16 + lr;
-        if (c * kChunk + wave * 16 < seq) {
+        if (c * kChunk + wave * 16 < lmax) {  // wave-uniform; a tile at or past lmax is never read
             const float *krow = KV + (wave * 16 + lr) * kKStride + lk;
             v4f acc[kRF];
 #pragma unroll
@@ -176,9 +195,10 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
         const int rl = wave * 2 + rr;
         if (rl >= rows) break;
         float *srow = S + rl * kSStride;
+        const int li = limit(rl);  // the row's softmax width: nothing at or past it reaches the result
         const float seed = __fmul_rn(srow[0], scale);
         float cand = -INFINITY;
-        for (int c = lane + 1; c < seq; c += 64) {
+        for (int c = lane + 1; c < li; c += 64) {
             const float x = __fmul_rn(srow[c], scale);  // op_multiply(QK_T, scale_factor)
             cand = (x > cand) ? x : cand;
         }
@@ -188,7 +208,8 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
             cand = (o > cand) ? o : cand;
         }
         const float mx = (cand > seed) ? cand : seed;
-        for (int c = lane; c < seq; c += 64) srow[c] = (float)exp((double)__fsub_rn(__fmul_rn(srow[c], scale), mx));
+        for (int c = lane, cu = upto(li); c < cu; c += 64)
+            srow[c] = (float)exp((double)__fsub_rn(__fmul_rn(srow[c], scale), mx));
     }
     __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): this wave's exps are in LDS
     __builtin_amdgcn_wave_barrier();
@@ -198,7 +219,11 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
     // zero; both halves run the same instructions).  Elements past seq are -0.0f, which leaves any sum
     // unchanged, so the last lane's 16 adds stay uniform.  Per element one dependent add, no LDS reads
     // inside the chain (the LDS-walking form exposed one read latency per 64 elements).
-    const int hl = lane & 31, nl = (seq + 15) >> 4;  // lanes per half that hold elements (nl <= 32)
+    // kCausal: a half's elements past its own row's limit are -0.0f too (raw scores or stale LDS sit there), both
+    // halves run to the lane count of row 2w+1, the larger limit, and row 2w's sum passes through its -0.0f lanes
+    // unchanged, so both sums are read at that lane.
+    const int hl = lane & 31, lh = limit(wave * 2 + (lane >> 5));  // lh: the limit of this half's row
+    const int nl = (limit(wave * 2 + 1) + 15) >> 4;  // lanes per half that hold elements (nl <= 32)
     const float *erow = S + (wave * 2 + (lane >> 5)) * kSStride + 16 * hl;
     float e[16];
 #pragma unroll
@@ -209,7 +234,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
     }
 #pragma unroll
     for (int j = 0; j < 16; ++j)
-        if (16 * hl + j >= seq) e[j] = -0.0f;
+        if (16 * hl + j >= lh) e[j] = -0.0f;
     float s = 0.0f;
     for (int t = 0; t < nl; ++t) {
         s = __fadd_rn(hop_left(s), e[0]);
@@ -223,8 +248,14 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
         const float srr = rr == 0 ? sum_a : sum_b;
         if (rl >= rows) break;
         float *srow = S + rl * kSStride;
-        for (int c = lane; c < seq; c += 64) srow[c] = __fdiv_rn(srow[c], srr);
-        if (lane < seq32 - seq) srow[seq + lane] = 0.0f;  // P over the zero-padded k range (< 32 columns)
+        const int li = limit(rl);
+        for (int c = lane, cu = upto(li); c < cu; c += 64) srow[c] = __fdiv_rn(srow[c], srr);
+        if constexpr (kCausal) {
+            // P = +0 at the masked keys, the passed-over columns and the padding (to the end of what `upto` covered)
+            for (int c = li + lane, ce = max(seq32, upto(li)); c < ce; c += 64) srow[c] = 0.0f;
+        } else {
+            if (lane < seq32 - seq) srow[seq + lane] = 0.0f;  // P over the zero-padded k range (< 32 columns)
+        }
     }
 
     // ---- O = P V, one V chunk at a time: waves 0 .. kRF*ceil(d_k/16)-1 own output tile (row
@@ -285,14 +316,19 @@ bool attention_fused_ok(int seq_kv, int dk) { return seq_kv <= kAttnMaxSeq && dk
 
 hipError_t launch_attention_fused(const float *Q, int64_t ldq, const float *K, int64_t ldk, const float *V, int64_t ldv,
                                   float *O, int64_t ldo, int seq_q, int seq_kv, int n_heads, int dk, float scale,
-                                  hipStream_t stream) {
-    if (n_heads < 1 || dk < 1 || seq_q < 0 || seq_kv < 1) return hipErrorInvalidValue;
+                                  int q_pos0, hipStream_t stream) {
+    if (n_heads < 1 || dk < 1 || seq_q < 0 || seq_kv < 1 || q_pos0 < kNoMask) return hipErrorInvalidValue;
     if (!attention_fused_ok(seq_kv, dk)) return hipErrorNotSupported;
     if (seq_q == 0) return hipSuccess;
     constexpr int kTQ = 32;
     const dim3 grid((unsigned)((seq_q + kTQ - 1) / kTQ), (unsigned)n_heads);
-    attention_fused_kernel<kTQ, 256, 1024><<<grid, 1024, 0, stream>>>(Q, ldq, K, ldk, V, ldv, O, ldo, dk, seq_q, seq_kv,
-                                                                       scale);
+    if (q_pos0 == kNoMask)
+        attention_fused_kernel<kTQ, 256, 1024, false><<<grid, 1024, 0, stream>>>(Q, ldq, K, ldk, V, ldv, O, ldo, dk,
+                                                                                  seq_q, seq_kv, scale, 0);
+    else  // past seq_kv - 1 the mask hides nothing: clamped, so the kernel's row limits cannot overflow
+        attention_fused_kernel<kTQ, 256, 1024, true><<<grid, 1024, 0, stream>>>(Q, ldq, K, ldk, V, ldv, O, ldo, dk,
+                                                                                 seq_q, seq_kv, scale,
+                                                                                 q_pos0 < seq_kv ? q_pos0 : seq_kv);
     return hipGetLastError();
 }
 

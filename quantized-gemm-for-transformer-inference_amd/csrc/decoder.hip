@@ -39,6 +39,7 @@ struct DecoderBlock {
 
 struct Decoder {
     int d_model = 0, n_heads = 0, d_ff = 0, n_blocks = 0, max_seq = 0, max_enc_seq = 0;
+    bool causal = false;  // the self-attention masks keys past the query's own row (QGEMM_DECODER_CAUSAL)
     std::vector<DecoderBlock> blocks;
     float *qkv = nullptr, *scores = nullptr, *heads = nullptr, *t = nullptr, *ffn = nullptr, *x = nullptr;
     float *q2 = nullptr, *kv2 = nullptr, *heads2 = nullptr, *xa = nullptr, *xb = nullptr;
@@ -92,7 +93,7 @@ void decoder_destroy(Decoder *D) {
 }
 
 hipError_t decoder_create(int d_model, int n_heads, int d_ff, int n_blocks, int max_seq, int max_enc_seq, uint64_t seed,
-                          Decoder **out) {
+                          bool causal, Decoder **out) {
     *out = nullptr;
     if (d_model < 2 || n_heads < 1 || d_model % n_heads || d_ff < 2 || n_blocks < 1 || max_seq < 1 || max_seq > 4096 ||
         max_enc_seq < 1 || max_enc_seq > 4096 || d_model > 4096)
@@ -105,6 +106,7 @@ hipError_t decoder_create(int d_model, int n_heads, int d_ff, int n_blocks, int 
     D->n_blocks = n_blocks;
     D->max_seq = max_seq;
     D->max_enc_seq = max_enc_seq;
+    D->causal = causal;
     D->blocks.resize(n_blocks);
     const int d = d_model, dk = d_model / n_heads;
     const size_t S = (size_t)max_seq, Se = (size_t)max_enc_seq;
@@ -184,8 +186,9 @@ hipError_t decoder_forward(Decoder *D, const float *X, const float *enc_out, flo
         float *out = last ? Y : (i % 2 ? D->xb : D->xa);
         // ---- self-attention on the block input (transformer.cu:93-126): the encoder's first half
         if ((e = linear(*D, in_packed ? nullptr : in, seq, d, B.wqkv, 3 * d, D->qkv, nullptr, false, s))) return e;
+        // (causal: row i sees rows 0 .. i, so row i of the forward depends on rows 0 .. i of X alone)
         if ((e = launch_attention(D->qkv, 3 * d, D->qkv + d, 3 * d, D->qkv + 2 * d, 3 * d, D->heads, d, seq, seq, H, dk,
-                                  scale, D->scores, s)))
+                                  scale, D->causal ? 0 : kNoMask, D->scores, s)))
             return e;
         if ((e = linear(*D, D->heads, seq, d, B.wo, d, D->t, nullptr, false, s))) return e;
         // x1 = LN(t + heads), packed by the same launch for the query projection
@@ -195,7 +198,7 @@ hipError_t decoder_forward(Decoder *D, const float *X, const float *enc_out, flo
         if ((e = linear(*D, nullptr, seq, d, B.wq2, d, D->q2, nullptr, false, s))) return e;
         if ((e = gemm(*D, venc, enc_seq, d, B.wkv2, 2 * d, D->kv2, nullptr, false, s))) return e;
         if ((e = launch_attention(D->q2, d, D->kv2, 2 * d, D->kv2 + d, 2 * d, D->heads2, d, seq, enc_seq, H, dk, scale,
-                                  D->scores, s)))
+                                  kNoMask, D->scores, s)))
             return e;
         if ((e = linear(*D, D->heads2, seq, d, B.wo2, d, D->t, nullptr, false, s))) return e;
         // x2 = LN(t + heads2), packed for the FFN's first linear

@@ -101,11 +101,12 @@ hipError_t linear(Encoder &E, const float *x, int seq, int k, const void *wpacke
 }  // namespace
 
 // The attention core of the encoder and the decoder: one fused launch where it fits (attention.hip), else the three
-// kernels it fuses, through `scores`.
+// kernels it fuses, through `scores`.  q_pos0: kNoMask or the causal mask's offset (qgemm_internal.h).
 hipError_t launch_attention(const float *Q, int64_t ldq, const float *K, int64_t ldk, const float *V, int64_t ldv,
-                            float *O, int64_t ldo, int seq_q, int seq_kv, int n_heads, int dk, float scale,
+                            float *O, int64_t ldo, int seq_q, int seq_kv, int n_heads, int dk, float scale, int q_pos0,
                             float *scores, hipStream_t stream) {
-    hipError_t e = launch_attention_fused(Q, ldq, K, ldk, V, ldv, O, ldo, seq_q, seq_kv, n_heads, dk, scale, stream);
+    hipError_t e =
+        launch_attention_fused(Q, ldq, K, ldk, V, ldv, O, ldo, seq_q, seq_kv, n_heads, dk, scale, q_pos0, stream);
     if (e != hipErrorNotSupported) return e;
     if (seq_q == 0) return hipSuccess;
     if (!scores) return hipErrorInvalidValue;
@@ -114,7 +115,11 @@ hipError_t launch_attention(const float *Q, int64_t ldq, const float *K, int64_t
     if ((e = launch_mm_f32_batched(Q, ldq, 1, dk, K, 1, ldk, dk, scores, seq_kv, 1, sbs, seq_q, seq_kv, dk, n_heads,
                                    stream)))
         return e;
-    if ((e = launch_softmax_rows(scores, scores, (int64_t)n_heads * seq_q, seq_kv, scale, stream))) return e;
+    // (under the mask every score is still computed: the softmax reads only each row's visible columns)
+    e = q_pos0 == kNoMask
+            ? launch_softmax_rows(scores, scores, (int64_t)n_heads * seq_q, seq_kv, scale, stream)
+            : launch_softmax_rows_causal(scores, scores, (int64_t)n_heads * seq_q, seq_kv, scale, seq_q, q_pos0, stream);
+    if (e) return e;
     return launch_mm_f32_batched(scores, seq_kv, 1, sbs, V, ldv, 1, dk, O, ldo, 1, dk, seq_q, dk, seq_kv, n_heads,
                                  stream);
 }
@@ -220,7 +225,7 @@ hipError_t encoder_forward(Encoder *E, const float *X, float *Y, int seq, hipStr
         // (attention.cuh:58-69, transformer.cu:43-50): one launch with S in LDS where it fits
         // (else the three launches through E->scores), Q, K and V the thirds of qkv
         if ((e = launch_attention(E->qkv, 3 * d, E->qkv + d, 3 * d, E->qkv + 2 * d, 3 * d, E->heads, d, seq, seq, H, dk,
-                                  scale, E->scores, s)))
+                                  scale, kNoMask, E->scores, s)))
             return e;
         // output = multiHeadOut @ W_O; LN(output + multiHeadOut)         (transformer.cu:52-59)
         if ((e = linear(*E, E->heads, seq, d, B.wo, d, E->t, nullptr, false, s))) return e;

@@ -97,15 +97,24 @@ __device__ __forceinline__ float sq_dev(float x, float mean) {
     return __fmul_rn(d, d);
 }
 
-__global__ __launch_bounds__(64 * kRowWaves) void softmax_rows_kernel(const float *S, float *P, int64_t rows, int w,
-                                                                      float scale) {  // P may be S (in place)
+// kCausal: the rows are a stack of seq_q x w_all matrices, row r is query i = r % seq_q and sees its first
+// w = min(w_all, i + q_pos0 + 1) columns: the softmax below on a row of that width (nothing past it is read), then +0
+// in columns w .. w_all - 1.  q_pos0 <= w_all (the launcher clamps it).
+template <bool kCausal>
+__global__ __launch_bounds__(64 * kRowWaves) void softmax_rows_kernel(const float *S, float *P, int64_t rows, int w_all,
+                                                                      float scale, int seq_q, int q_pos0) {  // P may be S (in place)
     extern __shared__ __attribute__((aligned(16))) float stage[];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int64_t row = (int64_t)blockIdx.x * kRowWaves + wv;
     if (row >= rows) return;
-    const float *s = S + row * w;
-    float *p = P + row * w;
-    float *st = stage + wv * ((w + 3) & ~3);  // 16-B aligned row stage
+    int w = w_all;
+    if constexpr (kCausal) {
+        const int64_t lim = row % seq_q + q_pos0 + 1;
+        if (lim < w_all) w = (int)lim;
+    }
+    const float *s = S + row * w_all;
+    float *p = P + row * w_all;
+    float *st = stage + wv * ((w_all + 3) & ~3);  // 16-B aligned row stage
     // max: seed = first element, then "if (x > max) max = x" (op_softmax.cuh:13-18) -- NaN never wins
     const float seed = __fmul_rn(s[0], scale);
     float cand = -INFINITY;
@@ -127,6 +136,8 @@ __global__ __launch_bounds__(64 * kRowWaves) void softmax_rows_kernel(const floa
     __builtin_amdgcn_wave_barrier();
     const float sum = seq_sum(st, w);   // op_softmax.cuh:20-24, in column order
     for (int c = lane; c < w; c += 64) p[c] = __fdiv_rn(st[c], sum);
+    if constexpr (kCausal)
+        for (int c = w + lane; c < w_all; c += 64) p[c] = 0.0f;
 }
 
 // kPack: also quantize the output row for the next quantized linear (the pack_rows step of
@@ -320,8 +331,19 @@ hipError_t launch_softmax_rows(const float *S, float *P, int64_t rows, int w, fl
     if (w < 1 || w > kMaxRowLen || rows < 0) return hipErrorInvalidValue;
     if (rows == 0) return hipSuccess;
     const size_t lds = sizeof(float) * kRowWaves * ((w + 3) & ~3);
-    softmax_rows_kernel<<<(unsigned)((rows + kRowWaves - 1) / kRowWaves), 64 * kRowWaves, lds, stream>>>(S, P, rows, w,
-                                                                                                      scale);
+    softmax_rows_kernel<false><<<(unsigned)((rows + kRowWaves - 1) / kRowWaves), 64 * kRowWaves, lds, stream>>>(
+        S, P, rows, w, scale, 1, 0);
+    return hipGetLastError();
+}
+
+hipError_t launch_softmax_rows_causal(const float *S, float *P, int64_t rows, int w, float scale, int seq_q,
+                                      int q_pos0, hipStream_t stream) {
+    if (w < 1 || w > kMaxRowLen || rows < 0 || seq_q < 1 || rows % seq_q != 0 || q_pos0 < 0)
+        return hipErrorInvalidValue;
+    if (rows == 0) return hipSuccess;
+    const size_t lds = sizeof(float) * kRowWaves * ((w + 3) & ~3);
+    softmax_rows_kernel<true><<<(unsigned)((rows + kRowWaves - 1) / kRowWaves), 64 * kRowWaves, lds, stream>>>(
+        S, P, rows, w, scale, seq_q, q_pos0 < w ? q_pos0 : w);  // past w - 1 the mask hides nothing
     return hipGetLastError();
 }
 

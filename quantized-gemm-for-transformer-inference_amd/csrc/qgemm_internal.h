@@ -225,16 +225,23 @@ hipError_t launch_mm_f32_batched(const float *A, int64_t ash, int64_t asw, int64
 // the three separate kernels; hipErrorNotSupported outside attention_fused_ok (d_k <= 64, seq_kv <= 512).
 // Q, O: seq_q rows; K, V: seq_kv rows; row strides ld* in floats, unit inner stride, head h at columns
 // h*d_k .. of each matrix.  O must not overlap Q, K or V.
+// q_pos0: kNoMask, or the key position of query row 0 for the causal mask (>= 0): row i sees keys
+// 0 .. min(seq_kv, i + q_pos0 + 1) - 1, its softmax runs over those columns alone and P is +0 past them.
+constexpr int kNoMask = -1;
 bool attention_fused_ok(int seq_kv, int dk);
 hipError_t launch_attention_fused(const float *Q, int64_t ldq, const float *K, int64_t ldk, const float *V, int64_t ldv,
                                   float *O, int64_t ldo, int seq_q, int seq_kv, int n_heads, int dk, float scale,
-                                  hipStream_t stream);
-// The fused launch where it fits, else launch_mm_f32_batched + launch_softmax_rows + launch_mm_f32_batched through
-// scores (n_heads x seq_q x seq_kv floats; may be nullptr inside the fused envelope; seq_kv <= 4096).
+                                  int q_pos0, hipStream_t stream);
+// The fused launch where it fits, else launch_mm_f32_batched + launch_softmax_rows[_causal] + launch_mm_f32_batched
+// through scores (n_heads x seq_q x seq_kv floats; may be nullptr inside the fused envelope; seq_kv <= 4096).
 hipError_t launch_attention(const float *Q, int64_t ldq, const float *K, int64_t ldk, const float *V, int64_t ldv,
-                            float *O, int64_t ldo, int seq_q, int seq_kv, int n_heads, int dk, float scale,
+                            float *O, int64_t ldo, int seq_q, int seq_kv, int n_heads, int dk, float scale, int q_pos0,
                             float *scores, hipStream_t stream);
 hipError_t launch_softmax_rows(const float *S, float *P, int64_t rows, int w, float scale, hipStream_t stream);
+// the same on a stack of rows / seq_q matrices under the causal mask: row r is query i = r % seq_q and its softmax
+// runs over its first min(w, i + q_pos0 + 1) columns, +0 stored past them (P may be S)
+hipError_t launch_softmax_rows_causal(const float *S, float *P, int64_t rows, int w, float scale, int seq_q,
+                                      int q_pos0, hipStream_t stream);
 hipError_t launch_add_layernorm_rows(const float *A, const float *B, float *Y, int64_t rows, int w,
                                      hipStream_t stream);
 // the same, also writing Y's rows packed (Cx + int8) for the next quantized linear (pack_rows fused)
@@ -278,7 +285,7 @@ hipError_t encoder_make_packed(int k, int n, const std::vector<uint64_t> &col_se
 // The decoder counterpart (decoder.hip).
 struct Decoder;
 hipError_t decoder_create(int d_model, int n_heads, int d_ff, int n_blocks, int max_seq, int max_enc_seq, uint64_t seed,
-                          Decoder **out);
+                          bool causal, Decoder **out);
 hipError_t decoder_forward(Decoder *D, const float *X, const float *enc_out, float *Y, int seq, int enc_seq,
                            hipStream_t s);
 void decoder_destroy(Decoder *D);
