@@ -182,6 +182,8 @@ QGEMM_API int qgemm_encoder_destroy(void *encoder);
  * One fused launch (the scores stay on chip) for d_k <= 64 and seq_kv <= 512, any seq_q; outside that three
  * launches through `workspace`, n_heads x seq_q x seq_kv floats of scores: qgemm_attention_workspace_size returns
  * that size in bytes, 0 inside the fused envelope (workspace may then be NULL) and 0 for invalid dimensions.
+ * (seq_q <= 8 with d_k <= 64 takes a launch of its own, up to 4096 keys, which leaves the workspace untouched:
+ * qgemm_attention_plan below.  The workspace rules do not change with it.)
  * The call allocates nothing and makes no host synchronization.
  * hipErrorInvalidValue before any launch: a null Q / K / V / O, seq_q < 0, seq_kv < 1, n_heads < 1, d_k < 1,
  * seq_kv > 4096 (qgemm_softmax_rows' row limit) or a short workspace; seq_q == 0 returns 0. */
@@ -210,6 +212,13 @@ QGEMM_API int qgemm_attention_causal(const float *Q, int64_t q_stride_h, const f
                            const float *V, int64_t v_stride_h, float *O, int64_t o_stride_h,
                            int seq_q, int seq_kv, int n_heads, int d_k, float scale, int q_pos0,
                            void *workspace, size_t ws_bytes, void *stream);
+/* Diagnostics: the launch qgemm_attention / qgemm_attention_causal take for a shape, with or without a mask.  Returns
+ * 0 and, when kernel is non-NULL, a static string in *kernel that begins "attention_decode" (seq_q <= 8, d_k <= 64:
+ * one workgroup per (head, query row), up to 4096 keys -- a decoding step), "attention_fused" (d_k <= 64,
+ * seq_kv <= 512) or "three_launches"; hipErrorInvalidValue for dimensions the calls refuse.  Every path gives the
+ * same bits.  qgemm_attention_workspace_size does not depend on it: the decode launch leaves a workspace it is
+ * handed untouched, and a shape outside the fused envelope still has to bring one.  Needs no GPU. */
+QGEMM_API int qgemm_attention_plan(int seq_q, int seq_kv, int n_heads, int d_k, const char **kernel);
 
 /* ---- The decoder counterpart (transformer.cu:79-168) --------------------------------------------------
  * Decoder stack with seeded weights drawn once and packed, like the encoder's.  X, Y: seq x d_model; enc_out:
@@ -227,11 +236,36 @@ QGEMM_API int qgemm_decoder_create(int d_model, int n_heads, int d_ff, int n_blo
  * unmasked.  Every other step is row-local, so row i of a forward then depends on rows 0 .. i of X and on enc_out
  * alone: forward(X[:n]) equals the first n rows of forward(X) bit for bit.  An unknown flag bit:
  * hipErrorInvalidValue.  Forward and destroy are the same calls. */
-enum { QGEMM_DECODER_CAUSAL = 1 };
+/* QGEMM_DECODER_KV_CACHE (only together with QGEMM_DECODER_CAUSAL, else hipErrorInvalidValue): every block also owns a
+ * self-attention cache, its [Q | K | V] rows of max_seq x 3 d_model, and a cross cache [K2 | V2] of max_enc_seq x
+ * 2 d_model, for qgemm_decoder_begin / qgemm_decoder_step below.  A decoder created without it allocates nothing
+ * more and behaves as before; forward on a cached decoder still works and neither reads nor writes the caches.
+ * (Its value is 8: flag bits 2 and 4 stay unknown bits, so flags == 3 and flags == 5 are still refused.) */
+enum { QGEMM_DECODER_CAUSAL = 1, QGEMM_DECODER_KV_CACHE = 8 };
 QGEMM_API int qgemm_decoder_create_ex(int d_model, int n_heads, int d_ff, int n_blocks, int max_seq, int max_enc_seq,
                             uint64_t seed, int flags, void **decoder);
 QGEMM_API int qgemm_decoder_forward(void *decoder, const float *X, const float *enc_out, float *Y, int seq, int enc_seq,
                           void *stream);
+/* Incremental decoding on a decoder created with QGEMM_DECODER_KV_CACHE.
+ * qgemm_decoder_begin starts a sequence: it quantizes enc_out (enc_seq x d_model) once, runs every block's [K2 | V2]
+ * projection into that block's cross cache, records enc_seq and sets the filled length to 0.  Calling it again
+ * starts a new sequence.
+ * qgemm_decoder_step takes X, the n x d_model contiguous decoder input rows at positions pos .. pos + n - 1, and
+ * writes Y, their n output rows: per block the QKV projection of the n rows into cache rows pos .., the masked
+ * attention of those rows against cache rows 0 .. pos + n - 1 (qgemm_attention_causal with q_pos0 = pos), and the
+ * rest of forward's steps on n rows, the cross-attention reading the cross cache.  Y equals rows pos .. pos + n - 1
+ * of the causal qgemm_decoder_forward on the whole prefix (the rows fed at positions 0 .. pos + n - 1) and the same
+ * enc_out, BIT FOR BIT: every step but the attention is row-local, and the masked attention's row i depends on keys
+ * and values 0 .. i alone where the cached V is finite and no P V accumulator is -0 (qgemm_attention_causal above).
+ * pos is a host argument; the decoder keeps a host-side filled length, updated when the call is enqueued:
+ * 0 <= pos <= filled is required and the call sets filled = pos + n, so stepping at an earlier pos rewinds
+ * (speculative decoding, beam search), and a captured graph replays one position.
+ * Neither call allocates or synchronizes; both use the decoder's scratch buffers in stream order, as forward does,
+ * so one decoder does one thing at a time.
+ * hipErrorInvalidValue before any launch: a decoder without the cache flag, a step without a begin, a null pointer,
+ * n < 1, pos < 0, pos > filled, pos + n > max_seq, enc_seq < 1 or > max_enc_seq. */
+QGEMM_API int qgemm_decoder_begin(void *decoder, const float *enc_out, int enc_seq, void *stream);
+QGEMM_API int qgemm_decoder_step(void *decoder, const float *X, float *Y, int pos, int n, void *stream);
 QGEMM_API int qgemm_decoder_destroy(void *decoder);
 
 /* ---- LLM.int8() outlier decomposition ------------------------------------------

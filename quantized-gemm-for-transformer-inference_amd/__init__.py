@@ -66,9 +66,12 @@ EXPORTED_SYMBOLS = (
     "qgemm_attention_workspace_size",
     "qgemm_attention",
     "qgemm_attention_causal",
+    "qgemm_attention_plan",
     "qgemm_decoder_create",
     "qgemm_decoder_create_ex",
     "qgemm_decoder_forward",
+    "qgemm_decoder_begin",
+    "qgemm_decoder_step",
     "qgemm_decoder_destroy",
     "qgemm_mm_outlier_workspace_size",
     "qgemm_mm_outlier",
@@ -105,6 +108,7 @@ COMM_ID_BYTES = 128
 HIP_ERROR_INVALID_VALUE = 1
 QGEMM_F32, QGEMM_BF16 = 0, 1  # element-type tags of the _dt entry points (include/qgemm.h)
 QGEMM_DECODER_CAUSAL = 1       # qgemm_decoder_create_ex flag: causal mask on the self-attention
+QGEMM_DECODER_KV_CACHE = 8     # ... and per-block key / value caches for begin() / step() (with CAUSAL only)
 
 _lock = threading.Lock()
 _lib = None
@@ -200,6 +204,12 @@ def load() -> ctypes.CDLL:
         L.qgemm_decoder_create.restype = i32
         L.qgemm_decoder_forward.argtypes = [vp, vp, vp, vp, i32, i32, vp]
         L.qgemm_decoder_forward.restype = i32
+        L.qgemm_decoder_begin.argtypes = [vp, vp, i32, vp]
+        L.qgemm_decoder_begin.restype = i32
+        L.qgemm_decoder_step.argtypes = [vp, vp, vp, i32, i32, vp]
+        L.qgemm_decoder_step.restype = i32
+        L.qgemm_attention_plan.argtypes = [i32, i32, i32, i32, ctypes.POINTER(ctypes.c_char_p)]
+        L.qgemm_attention_plan.restype = i32
         L.qgemm_decoder_destroy.argtypes = [vp]
         L.qgemm_decoder_destroy.restype = i32
         L.qgemm_mm_outlier_workspace_size.argtypes = [i32, i32, i32]
@@ -856,7 +866,8 @@ def attention(Q, K, V, n_heads: int, scale=None, O=None, causal: bool = False, q
     h*d_k .. of each matrix, d_k = Q.shape[1] / n_heads.  Q: seq_q x d, K and V: seq_kv x d -- 2-D fp32 device
     tensors or views with unit inner stride (column slices of wider buffers included); O (seq_q x d) must not
     overlap them.  scale defaults to fl32(1 / sqrt(d_k)), as the encoder computes it.  One fused launch for
-    d_k <= 64 and seq_kv <= 512, else three launches through a scores workspace allocated here.
+    d_k <= 64 and seq_kv <= 512, else three launches through a scores workspace allocated here; at most 8 query rows
+    with d_k <= 64 take the decode launch instead, up to 4096 keys (attention_plan names the launch; the same bits).
     causal=True (qgemm_attention_causal): query row i sees keys 0 .. min(seq_kv, i + q_pos0 + 1) - 1, the masked
     columns of P are +0.  q_pos0 is the key position of query row 0; left out it is seq_kv - seq_q, the queries
     aligned to the end of the keys as with a key / value cache (seq_kv >= seq_q is then asserted)."""
@@ -897,22 +908,34 @@ def attention(Q, K, V, n_heads: int, scale=None, O=None, causal: bool = False, q
     return O
 
 
+def attention_plan(seq_q: int, seq_kv: int, n_heads: int, d_k: int) -> str:
+    """The launch attention() takes for a shape (qgemm_attention_plan): a name that begins "attention_decode",
+    "attention_fused" or "three_launches".  Needs no GPU; raises QGemmError for dimensions attention() refuses."""
+    name = ctypes.c_char_p()
+    _check("qgemm_attention_plan", load().qgemm_attention_plan(seq_q, seq_kv, n_heads, d_k, ctypes.byref(name)))
+    return name.value.decode()
+
+
 class Decoder:
     """transformer.cu:79-168's Decoder with its linears on the quantized path: per block self-attention,
     cross-attention on the encoder's output, FFN (DESIGN.md "Decoder").  causal=True (qgemm_decoder_create_ex,
     QGEMM_DECODER_CAUSAL): the self-attention is masked, row i sees rows 0 .. i, and forward(X[:n]) equals
-    forward(X)[:n] bit for bit."""
+    forward(X)[:n] bit for bit.  kv_cache=True (QGEMM_DECODER_KV_CACHE, with causal=True only): begin(enc_out) starts a
+    sequence and step(X_new) returns the output rows of the new input rows alone -- the rows forward would give for them
+    on the whole prefix, bit for bit -- from per-block key / value caches."""
 
     def __init__(self, d_model: int, n_heads: int, d_ff: int, n_blocks: int, max_seq: int, max_enc_seq: int,
-                 seed: int = 0, causal: bool = False):
+                 seed: int = 0, causal: bool = False, kv_cache: bool = False):
         self.d_model, self.n_heads, self.d_ff, self.n_blocks, self.max_seq, self.max_enc_seq, self.seed = (
             d_model, n_heads, d_ff, n_blocks, max_seq, max_enc_seq, seed)
-        self.causal = bool(causal)
+        self.causal, self.kv_cache = bool(causal), bool(kv_cache)
+        self.filled = None   # mirrors the decoder's filled length: None before begin()
         h = ctypes.c_void_p()
-        if causal:
+        if causal or kv_cache:
+            flags = (QGEMM_DECODER_CAUSAL if causal else 0) | (QGEMM_DECODER_KV_CACHE if kv_cache else 0)
             _check("qgemm_decoder_create_ex",
                    load().qgemm_decoder_create_ex(d_model, n_heads, d_ff, n_blocks, max_seq, max_enc_seq, seed,
-                                                  QGEMM_DECODER_CAUSAL, ctypes.byref(h)))
+                                                  flags, ctypes.byref(h)))
         else:
             _check("qgemm_decoder_create", load().qgemm_decoder_create(d_model, n_heads, d_ff, n_blocks, max_seq,
                                                                       max_enc_seq, seed, ctypes.byref(h)))
@@ -928,6 +951,31 @@ class Decoder:
         _check("qgemm_decoder_forward", load().qgemm_decoder_forward(self._h, X.data_ptr(), enc_out.data_ptr(),
                                                                     Y.data_ptr(), X.shape[0], enc_out.shape[0],
                                                                     _stream(X.device)))
+        return Y
+
+    def begin(self, enc_out):
+        """Start a sequence (qgemm_decoder_begin): every block's [K2 | V2] of enc_out into its cross cache."""
+        _require_device_f32(enc_out, "enc_out")
+        assert enc_out.is_contiguous() and enc_out.shape[1] == self.d_model
+        _check("qgemm_decoder_begin", load().qgemm_decoder_begin(self._h, enc_out.data_ptr(), enc_out.shape[0],
+                                                                _stream(enc_out.device)))
+        self.filled = 0
+
+    def step(self, X_new, pos=None, Y=None):
+        """The output rows of the input rows X_new (n x d_model) at positions pos .. pos + n - 1
+        (qgemm_decoder_step); pos defaults to the filled length, an earlier pos rewinds."""
+        import torch
+        _require_device_f32(X_new, "X_new")
+        assert X_new.is_contiguous() and X_new.shape[1] == self.d_model
+        if pos is None:
+            assert self.filled is not None, "step() follows begin()"
+            pos = self.filled
+        Y = torch.empty_like(X_new) if Y is None else Y
+        _require_device_f32(Y, "Y")
+        assert Y.is_contiguous() and Y.shape == X_new.shape
+        _check("qgemm_decoder_step", load().qgemm_decoder_step(self._h, X_new.data_ptr(), Y.data_ptr(), pos,
+                                                              X_new.shape[0], _stream(X_new.device)))
+        self.filled = pos + X_new.shape[0]
         return Y
 
     def close(self):

@@ -427,10 +427,11 @@ int qgemm_decoder_create_ex(int d_model, int n_heads, int d_ff, int n_blocks, in
                             uint64_t seed, int flags, void **decoder) {
     if (!decoder) return err(hipErrorInvalidValue);
     *decoder = nullptr;
-    if (flags & ~QGEMM_DECODER_CAUSAL) return err(hipErrorInvalidValue);
+    if (flags & ~(QGEMM_DECODER_CAUSAL | QGEMM_DECODER_KV_CACHE)) return err(hipErrorInvalidValue);
+    if ((flags & QGEMM_DECODER_KV_CACHE) && !(flags & QGEMM_DECODER_CAUSAL)) return err(hipErrorInvalidValue);
     Decoder *D = nullptr;
     hipError_t e = decoder_create(d_model, n_heads, d_ff, n_blocks, max_seq, max_enc_seq, seed,
-                                  (flags & QGEMM_DECODER_CAUSAL) != 0, &D);
+                                  (flags & QGEMM_DECODER_CAUSAL) != 0, (flags & QGEMM_DECODER_KV_CACHE) != 0, &D);
     *decoder = D;
     return err(e);
 }
@@ -444,6 +445,14 @@ int qgemm_decoder_forward(void *decoder, const float *X, const float *enc_out, f
                           void *stream) {
     return err(decoder_forward(static_cast<Decoder *>(decoder), X, enc_out, Y, seq, enc_seq,
                                static_cast<hipStream_t>(stream)));
+}
+
+int qgemm_decoder_begin(void *decoder, const float *enc_out, int enc_seq, void *stream) {
+    return err(decoder_begin(static_cast<Decoder *>(decoder), enc_out, enc_seq, static_cast<hipStream_t>(stream)));
+}
+
+int qgemm_decoder_step(void *decoder, const float *X, float *Y, int pos, int n, void *stream) {
+    return err(decoder_step(static_cast<Decoder *>(decoder), X, Y, pos, n, static_cast<hipStream_t>(stream)));
 }
 
 int qgemm_decoder_destroy(void *decoder) {
@@ -540,6 +549,12 @@ int qgemm_fill_uniform(float *dst, int64_t count, uint64_t seed, float lo, float
 int qgemm_gemm_plan(int m, int n, int k, int *tile, const char **kernel) {
     if (m < 1 || n < 1 || k < 1) return -(int)hipErrorInvalidValue;
     return gemm_plan_info(m, n, round_up(k, kKPad), tile, kernel);
+}
+
+int qgemm_attention_plan(int seq_q, int seq_kv, int n_heads, int d_k, const char **kernel) {
+    if (seq_q < 0 || seq_kv < 1 || seq_kv > 4096 || n_heads < 1 || d_k < 1) return (int)hipErrorInvalidValue;
+    if (kernel) *kernel = attention_plan_name(seq_q, seq_kv, d_k);
+    return 0;
 }
 
 #ifndef QGEMM_SRC_HASH

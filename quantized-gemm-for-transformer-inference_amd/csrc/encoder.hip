@@ -100,13 +100,21 @@ hipError_t linear(Encoder &E, const float *x, int seq, int k, const void *wpacke
 
 }  // namespace
 
-// The attention core of the encoder and the decoder: one fused launch where it fits (attention.hip), else the three
-// kernels it fuses, through `scores`.  q_pos0: kNoMask or the causal mask's offset (qgemm_internal.h).
+const char *attention_plan_name(int seq_q, int seq_kv, int dk) {
+    if (attention_decode_ok(seq_q, seq_kv, dk)) return "attention_decode_kernel";
+    return attention_fused_ok(seq_kv, dk) ? "attention_fused_kernel" : "three_launches";
+}
+
+// The attention core of the encoder and the decoder: the decode launch for a few query rows (attention_decode.hip), one
+// fused launch where it fits (attention.hip), else the three kernels it fuses, through `scores` -- the same bits on
+// every path.  q_pos0: kNoMask or the causal mask's offset (qgemm_internal.h).
 hipError_t launch_attention(const float *Q, int64_t ldq, const float *K, int64_t ldk, const float *V, int64_t ldv,
                             float *O, int64_t ldo, int seq_q, int seq_kv, int n_heads, int dk, float scale, int q_pos0,
                             float *scores, hipStream_t stream) {
     hipError_t e =
-        launch_attention_fused(Q, ldq, K, ldk, V, ldv, O, ldo, seq_q, seq_kv, n_heads, dk, scale, q_pos0, stream);
+        launch_attention_decode(Q, ldq, K, ldk, V, ldv, O, ldo, seq_q, seq_kv, n_heads, dk, scale, q_pos0, stream);
+    if (e != hipErrorNotSupported) return e;
+    e = launch_attention_fused(Q, ldq, K, ldk, V, ldv, O, ldo, seq_q, seq_kv, n_heads, dk, scale, q_pos0, stream);
     if (e != hipErrorNotSupported) return e;
     if (seq_q == 0) return hipSuccess;
     if (!scores) return hipErrorInvalidValue;

@@ -232,8 +232,16 @@ bool attention_fused_ok(int seq_kv, int dk);
 hipError_t launch_attention_fused(const float *Q, int64_t ldq, const float *K, int64_t ldk, const float *V, int64_t ldv,
                                   float *O, int64_t ldo, int seq_q, int seq_kv, int n_heads, int dk, float scale,
                                   int q_pos0, hipStream_t stream);
-// The fused launch where it fits, else launch_mm_f32_batched + launch_softmax_rows[_causal] + launch_mm_f32_batched
-// through scores (n_heads x seq_q x seq_kv floats; may be nullptr inside the fused envelope; seq_kv <= 4096).
+// The launch for a few query rows against up to 4096 keys (attention_decode.hip): one workgroup per (head, query
+// row), the same bits; hipErrorNotSupported outside attention_decode_ok (seq_q <= 8, seq_kv <= 4096, d_k <= 64).
+bool attention_decode_ok(int seq_q, int seq_kv, int dk);
+hipError_t launch_attention_decode(const float *Q, int64_t ldq, const float *K, int64_t ldk, const float *V, int64_t ldv,
+                                   float *O, int64_t ldo, int seq_q, int seq_kv, int n_heads, int dk, float scale,
+                                   int q_pos0, hipStream_t stream);
+// the kernel launch_attention takes for a shape (qgemm_attention_plan): a static string
+const char *attention_plan_name(int seq_q, int seq_kv, int dk);
+// The decode launch for seq_q <= 8, else the fused launch where it fits, else launch_mm_f32_batched + launch_softmax_rows[_causal] + launch_mm_f32_batched
+// through scores (n_heads x seq_q x seq_kv floats; may be nullptr inside the other two envelopes; seq_kv <= 4096).
 hipError_t launch_attention(const float *Q, int64_t ldq, const float *K, int64_t ldk, const float *V, int64_t ldv,
                             float *O, int64_t ldo, int seq_q, int seq_kv, int n_heads, int dk, float scale, int q_pos0,
                             float *scores, hipStream_t stream);
@@ -285,7 +293,9 @@ hipError_t encoder_make_packed(int k, int n, const std::vector<uint64_t> &col_se
 // The decoder counterpart (decoder.hip).
 struct Decoder;
 hipError_t decoder_create(int d_model, int n_heads, int d_ff, int n_blocks, int max_seq, int max_enc_seq, uint64_t seed,
-                          bool causal, Decoder **out);
+                          bool causal, bool kv_cache, Decoder **out);
+hipError_t decoder_begin(Decoder *D, const float *enc_out, int enc_seq, hipStream_t s);
+hipError_t decoder_step(Decoder *D, const float *X, float *Y, int pos, int n, hipStream_t s);
 hipError_t decoder_forward(Decoder *D, const float *X, const float *enc_out, float *Y, int seq, int enc_seq,
                            hipStream_t s);
 void decoder_destroy(Decoder *D);
