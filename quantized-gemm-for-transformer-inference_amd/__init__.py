@@ -825,7 +825,7 @@ DECODER_WEIGHT_KINDS = ENCODER_WEIGHT_KINDS + ("Wq2", "Wk2", "Wv2", "Wo2")  # ki
 
 
 def encoder_weight_seed(base: int, block: int, kind: int, head: int) -> int:
-    """Seed of one encoder weight tensor (include/qgemm.h, encoder.hip)."""
+    """Seed of one encoder weight tensor (include/qgemm.h, transformer.hip)."""
     return (base * 1000003 + block * 4099 + kind * 131 + head) & 0xFFFFFFFFFFFFFFFF
 
 

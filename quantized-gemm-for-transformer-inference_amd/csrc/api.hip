@@ -372,18 +372,18 @@ int qgemm_add_layernorm_rows(const float *A, const float *B, float *Y, int64_t r
 int qgemm_encoder_create(int d_model, int n_heads, int d_ff, int n_blocks, int max_seq, uint64_t seed,
                          void **encoder) {
     if (!encoder) return err(hipErrorInvalidValue);
-    Encoder *E = nullptr;
-    hipError_t e = encoder_create(d_model, n_heads, d_ff, n_blocks, max_seq, seed, &E);
+    Stack *E = nullptr;
+    hipError_t e = stack_create(d_model, n_heads, d_ff, n_blocks, max_seq, 0, seed, /*cross=*/false, false, false, &E);
     *encoder = E;
     return err(e);
 }
 
 int qgemm_encoder_forward(void *encoder, const float *X, float *Y, int seq, void *stream) {
-    return err(encoder_forward(static_cast<Encoder *>(encoder), X, Y, seq, static_cast<hipStream_t>(stream)));
+    return err(encoder_forward(static_cast<Stack *>(encoder), X, Y, seq, static_cast<hipStream_t>(stream)));
 }
 
 int qgemm_encoder_destroy(void *encoder) {
-    encoder_destroy(static_cast<Encoder *>(encoder));
+    stack_destroy(static_cast<Stack *>(encoder));
     return 0;
 }
 
@@ -429,9 +429,9 @@ int qgemm_decoder_create_ex(int d_model, int n_heads, int d_ff, int n_blocks, in
     *decoder = nullptr;
     if (flags & ~(QGEMM_DECODER_CAUSAL | QGEMM_DECODER_KV_CACHE)) return err(hipErrorInvalidValue);
     if ((flags & QGEMM_DECODER_KV_CACHE) && !(flags & QGEMM_DECODER_CAUSAL)) return err(hipErrorInvalidValue);
-    Decoder *D = nullptr;
-    hipError_t e = decoder_create(d_model, n_heads, d_ff, n_blocks, max_seq, max_enc_seq, seed,
-                                  (flags & QGEMM_DECODER_CAUSAL) != 0, (flags & QGEMM_DECODER_KV_CACHE) != 0, &D);
+    Stack *D = nullptr;
+    hipError_t e = stack_create(d_model, n_heads, d_ff, n_blocks, max_seq, max_enc_seq, seed, /*cross=*/true,
+                                (flags & QGEMM_DECODER_CAUSAL) != 0, (flags & QGEMM_DECODER_KV_CACHE) != 0, &D);
     *decoder = D;
     return err(e);
 }
@@ -443,20 +443,20 @@ int qgemm_decoder_create(int d_model, int n_heads, int d_ff, int n_blocks, int m
 
 int qgemm_decoder_forward(void *decoder, const float *X, const float *enc_out, float *Y, int seq, int enc_seq,
                           void *stream) {
-    return err(decoder_forward(static_cast<Decoder *>(decoder), X, enc_out, Y, seq, enc_seq,
+    return err(decoder_forward(static_cast<Stack *>(decoder), X, enc_out, Y, seq, enc_seq,
                                static_cast<hipStream_t>(stream)));
 }
 
 int qgemm_decoder_begin(void *decoder, const float *enc_out, int enc_seq, void *stream) {
-    return err(decoder_begin(static_cast<Decoder *>(decoder), enc_out, enc_seq, static_cast<hipStream_t>(stream)));
+    return err(decoder_begin(static_cast<Stack *>(decoder), enc_out, enc_seq, static_cast<hipStream_t>(stream)));
 }
 
 int qgemm_decoder_step(void *decoder, const float *X, float *Y, int pos, int n, void *stream) {
-    return err(decoder_step(static_cast<Decoder *>(decoder), X, Y, pos, n, static_cast<hipStream_t>(stream)));
+    return err(decoder_step(static_cast<Stack *>(decoder), X, Y, pos, n, static_cast<hipStream_t>(stream)));
 }
 
 int qgemm_decoder_destroy(void *decoder) {
-    decoder_destroy(static_cast<Decoder *>(decoder));
+    stack_destroy(static_cast<Stack *>(decoder));
     return 0;
 }
 

@@ -14,11 +14,10 @@
 //   * both products are v_mfma_f32_16x16x4_f32 chains from +0 over k ascending, zero-padded to a
 //     multiple of 4, then fl(res + 0) when k % 32 != 0 -- the reference's op_matmul_kernel chain
 //     (op_mm.cuh:37-39) with its zero-padded last 32-wide tile, exactly as gemm_f32.hip;
-//   * softmax as softmax_rows_kernel: products fl(s * scale), max seeded by the first element with a
-//     strict >, correctly rounded fp32 exp of fl(x - max), ONE sequential fp32 sum in column order,
-//     then fl(e / sum).
+//   * softmax as softmax_rows_kernel: max and exp by the contract at softmax_row_max (qgemm_internal.h), ONE
+//     sequential fp32 sum in column order, then fl(e / sum).
 // Envelope: d_k <= 64, seq_kv <= 512, any seq_q (S tile 32 x 512 fp32 = 64 KiB of LDS, Q tile and K / V
-// staged through LDS in 256-key chunks: 155 KiB in all); outside it launch_attention (encoder.hip) runs the
+// staged through LDS in 256-key chunks: 155 KiB in all); outside it launch_attention (attention_launch.hip) runs the
 // three kernels.
 // kCausal: query row i sees keys 0 .. L_i - 1, L_i = min(seq_kv, i + q_pos0 + 1).  The softmax of
 // row i is softmax_rows_kernel's on a row of width L_i and P is +0 from column L_i on; P V still runs over all of
@@ -196,6 +195,8 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
         if (rl >= rows) break;
         float *srow = S + rl * kSStride;
         const int li = limit(rl);  // the row's softmax width: nothing at or past it reaches the result
+        // the max keeps its own text (softmax_row_max's, spelled out: through the helper hipcc orders this kernel's
+        // register initialisation differently); the contract of both steps is at the helper (qgemm_internal.h)
         const float seed = __fmul_rn(srow[0], scale);
         float cand = -INFINITY;
         for (int c = lane + 1; c < li; c += 64) {
@@ -208,8 +209,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
             cand = (o > cand) ? o : cand;
         }
         const float mx = (cand > seed) ? cand : seed;
-        for (int c = lane, cu = upto(li); c < cu; c += 64)
-            srow[c] = (float)exp((double)__fsub_rn(__fmul_rn(srow[c], scale), mx));
+        for (int c = lane, cu = upto(li); c < cu; c += 64) srow[c] = softmax_exp(srow[c], scale, mx);
     }
     __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): this wave's exps are in LDS
     __builtin_amdgcn_wave_barrier();

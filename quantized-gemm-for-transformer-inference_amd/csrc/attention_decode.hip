@@ -9,9 +9,9 @@
 // attention_fused_kernel (its header comment):
 //   * a score is the fmaf chain from +0 over k ascending, d_k zero-padded to 32: Q and K are staged with zeros past
 //     d_k, so the padded steps are fmaf(+0, +0, res) = fl(res + 0) (the f32 MFMA of gemm_f32.hip computes this chain);
-//   * softmax as softmax_rows_kernel: fl(s * scale), max seeded by element 0 with a strict >, (float)exp((double)
-//     fl(x - max)), ONE sequential fp32 sum in column order (hopping lane to lane, 16 elements per lane, wrapping from
-//     lane 63 to lane 0 every 1024 elements), __fdiv_rn;
+//   * softmax as softmax_rows_kernel: max and exp by the contract at softmax_row_max (qgemm_internal.h), ONE
+//     sequential fp32 sum in column order (hopping lane to lane, 16 elements per lane, wrapping from lane 63 to lane 0
+//     every 1024 elements), __fdiv_rn;
 //   * P V is the fmaf chain from +0 over ALL seq_kv keys ascending, then fl(acc + 0) when seq_kv % 32 != 0 (the zero
 //     padding of the reference's last 32-wide tile).
 // Both serial chains (the row sum, each column's P V) run along the keys, so a row cannot be split across workgroups:
@@ -150,16 +150,7 @@ __global__ __launch_bounds__(kDecThreads) void attention_decode_kernel(
 
     // ---- softmax of the row over its first L columns, in place in S
     const float seed = __fmul_rn(S[0], scale);
-    float cand = -INFINITY;
-    for (int c = t + 1; c < L; c += kDecThreads) {
-        const float x = __fmul_rn(S[c], scale);  // op_multiply(QK_T, scale_factor)
-        cand = (x > cand) ? x : cand;
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const float o = __shfl_xor(cand, off, 64);
-        cand = (o > cand) ? o : cand;
-    }
+    float cand = softmax_row_max(S, t + 1, L, kDecThreads, scale);
     if (lane == 0) red[wave] = cand;
     __syncthreads();  // (also: every thread has read S[0] before the exps overwrite it)
 #pragma unroll
@@ -168,7 +159,7 @@ __global__ __launch_bounds__(kDecThreads) void attention_decode_kernel(
         cand = (o > cand) ? o : cand;
     }
     const float mx = (cand > seed) ? cand : seed;
-    for (int c = t; c < L; c += kDecThreads) S[c] = (float)exp((double)__fsub_rn(__fmul_rn(S[c], scale), mx));
+    for (int c = t; c < L; c += kDecThreads) S[c] = softmax_exp(S[c], scale, mx);
     __syncthreads();
     // the ONE sequential sum, in wave 0: lane l holds elements 1024 p + 16 l .. + 15 of pass p in registers and the
     // running sum hops from lane to lane (hop_left); after step t of a pass the chain through lane t - 1's block

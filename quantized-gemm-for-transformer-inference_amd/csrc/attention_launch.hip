@@ -1,0 +1,46 @@
+// attention_launch.hip -- which of the three attention launches a shape takes, for the transformer stack
+// (transformer.hip) and the public qgemm_attention* entry points (api.hip): the decode launch for a few query rows
+// (attention_decode.hip), one fused launch where it fits (attention.hip), else the three kernels it fuses, through
+// `scores` -- the same bits on every path.  Host code only; it is a file of its own because it calls the fp32 GEMM
+// launchers, which the programs that compile attention.hip's text alone do not link.
+#include "qgemm_internal.h"
+
+namespace qgemm {
+
+const char *attention_plan_name(int seq_q, int seq_kv, int dk) {
+    if (attention_decode_ok(seq_q, seq_kv, dk)) return "attention_decode_kernel";
+    return attention_fused_ok(seq_kv, dk) ? "attention_fused_kernel" : "three_launches";
+}
+
+// scores only where some call can reach the three launches: never inside the fused envelope, and never with at most
+// kAttnDecodeMaxQ query rows inside the decode envelope (a call of fewer rows or keys needs none either way)
+bool attention_needs_scores(int max_q, int max_kv, int dk) {
+    return !attention_fused_ok(max_kv, dk) && !attention_decode_ok(max_q, max_kv, dk);
+}
+
+// q_pos0: kNoMask or the causal mask's offset (qgemm_internal.h)
+hipError_t launch_attention(const float *Q, int64_t ldq, const float *K, int64_t ldk, const float *V, int64_t ldv,
+                            float *O, int64_t ldo, int seq_q, int seq_kv, int n_heads, int dk, float scale, int q_pos0,
+                            float *scores, hipStream_t stream) {
+    hipError_t e =
+        launch_attention_decode(Q, ldq, K, ldk, V, ldv, O, ldo, seq_q, seq_kv, n_heads, dk, scale, q_pos0, stream);
+    if (e != hipErrorNotSupported) return e;
+    e = launch_attention_fused(Q, ldq, K, ldk, V, ldv, O, ldo, seq_q, seq_kv, n_heads, dk, scale, q_pos0, stream);
+    if (e != hipErrorNotSupported) return e;
+    if (seq_q == 0) return hipSuccess;
+    if (!scores) return hipErrorInvalidValue;
+    // fp32 op_mm with the transposed view of K, softmax in place, fp32 op_mm into the head's columns of O
+    const int64_t sbs = (int64_t)seq_q * seq_kv;
+    if ((e = launch_mm_f32_batched(Q, ldq, 1, dk, K, 1, ldk, dk, scores, seq_kv, 1, sbs, seq_q, seq_kv, dk, n_heads,
+                                   stream)))
+        return e;
+    // (under the mask every score is still computed: the softmax reads only each row's visible columns)
+    e = q_pos0 == kNoMask
+            ? launch_softmax_rows(scores, scores, (int64_t)n_heads * seq_q, seq_kv, scale, stream)
+            : launch_softmax_rows_causal(scores, scores, (int64_t)n_heads * seq_q, seq_kv, scale, seq_q, q_pos0, stream);
+    if (e) return e;
+    return launch_mm_f32_batched(scores, seq_kv, 1, sbs, V, ldv, 1, dk, O, ldo, 1, dk, seq_q, dk, seq_kv, n_heads,
+                                 stream);
+}
+
+}  // namespace qgemm

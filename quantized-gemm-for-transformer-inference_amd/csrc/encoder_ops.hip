@@ -115,23 +115,11 @@ __global__ __launch_bounds__(64 * kRowWaves) void softmax_rows_kernel(const floa
     const float *s = S + row * w_all;
     float *p = P + row * w_all;
     float *st = stage + wv * ((w_all + 3) & ~3);  // 16-B aligned row stage
-    // max: seed = first element, then "if (x > max) max = x" (op_softmax.cuh:13-18) -- NaN never wins
+    // max and exp: the contract at softmax_row_max (qgemm_internal.h)
     const float seed = __fmul_rn(s[0], scale);
-    float cand = -INFINITY;
-    for (int c = lane + 1; c < w; c += 64) {
-        const float x = __fmul_rn(s[c], scale);  // op_multiply(QK_T, scale_factor) (attention.cuh:65)
-        cand = (x > cand) ? x : cand;
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const float o = __shfl_xor(cand, off, 64);
-        cand = (o > cand) ? o : cand;
-    }
+    const float cand = softmax_row_max(s, lane + 1, w, 64, scale);
     const float mx = (cand > seed) ? cand : seed;
-    for (int c = lane; c < w; c += 64) {
-        const float d = __fsub_rn(__fmul_rn(s[c], scale), mx);
-        st[c] = (float)exp((double)d);  // correctly rounded fp32 exp
-    }
+    for (int c = lane; c < w; c += 64) st[c] = softmax_exp(s[c], scale, mx);
     __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): this wave's LDS writes done (one wave per row)
     __builtin_amdgcn_wave_barrier();
     const float sum = seq_sum(st, w);   // op_softmax.cuh:20-24, in column order

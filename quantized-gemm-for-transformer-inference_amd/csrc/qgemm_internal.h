@@ -108,6 +108,33 @@ __device__ __forceinline__ float hop_left(float s) {
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(s), 0x13C /* wave_ror:1 */, 0xf, 0xf, true));
 }
 
+// The softmax's max and exp steps (op_multiply by `scale` + op_softmax, attention.cuh:65-68, op_softmax.cuh:13-24), the
+// numerics contract of softmax_rows_kernel, attention_fused_kernel and attention_decode_kernel, whose results are
+// bit-identical because they share it:
+//   * every score enters as fl(s * scale);
+//   * the maximum is seeded by element 0 and updated by "if (x > max) max = x" with a strict >, so a NaN never wins
+//     and a NaN seed sticks;
+//   * the exponential is the correctly rounded fp32 exp of fl(fl(s * scale) - max): fl32(exp((double)x)).
+// softmax_row_max: this lane's candidates row[first], row[first + stride], .. below w, from -inf, reduced over the 64
+// lanes of the wave.  `first` skips element 0: the caller combines the result with its seed fl(row[0] * scale),
+// (cand > seed) ? cand : seed -- after combining the waves' results the same way where a row spans several.
+__device__ __forceinline__ float softmax_row_max(const float *row, int first, int w, int stride, float scale) {
+    float cand = -INFINITY;
+    for (int c = first; c < w; c += stride) {
+        const float x = __fmul_rn(row[c], scale);  // op_multiply(QK_T, scale_factor) (attention.cuh:65)
+        cand = (x > cand) ? x : cand;
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const float o = __shfl_xor(cand, off, 64);
+        cand = (o > cand) ? o : cand;
+    }
+    return cand;
+}
+__device__ __forceinline__ float softmax_exp(float s, float scale, float mx) {
+    return (float)exp((double)__fsub_rn(__fmul_rn(s, scale), mx));
+}
+
 // Counter-based generator shared with oracle_uniform_at (oracle/qgemm_oracle.c).
 __host__ __device__ inline uint64_t mix64(uint64_t z) {
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
@@ -238,8 +265,11 @@ bool attention_decode_ok(int seq_q, int seq_kv, int dk);
 hipError_t launch_attention_decode(const float *Q, int64_t ldq, const float *K, int64_t ldk, const float *V, int64_t ldv,
                                    float *O, int64_t ldo, int seq_q, int seq_kv, int n_heads, int dk, float scale,
                                    int q_pos0, hipStream_t stream);
+// Attention dispatch (attention_launch.hip).
 // the kernel launch_attention takes for a shape (qgemm_attention_plan): a static string
 const char *attention_plan_name(int seq_q, int seq_kv, int dk);
+// whether a call of at most max_q query rows and max_kv keys can reach the three launches, and so needs `scores`
+bool attention_needs_scores(int max_q, int max_kv, int dk);
 // The decode launch for seq_q <= 8, else the fused launch where it fits, else launch_mm_f32_batched + launch_softmax_rows[_causal] + launch_mm_f32_batched
 // through scores (n_heads x seq_q x seq_kv floats; may be nullptr inside the other two envelopes; seq_kv <= 4096).
 hipError_t launch_attention(const float *Q, int64_t ldq, const float *K, int64_t ldk, const float *V, int64_t ldv,
@@ -278,27 +308,25 @@ hipError_t outlier_linear_prepare(const float *X, int64_t xsh, int m, int k, flo
                                   hipStream_t s);
 hipError_t outlier_linear_finish(const float *X, int64_t xsh, int m, int n, int k, void *scratch, PackedView vb,
                                  const float *bias, bool relu, float *Y, int64_t ysh, hipStream_t s);
-// The encoder counterpart (encoder.hip).
-struct Encoder;
+// The transformer stack (transformer.hip): an encoder is a stack without cross-attention, a decoder one with it.
+// encoder_forward refuses a stack with cross-attention and decoder_* one without (hipErrorInvalidValue).
+struct Stack;
 uint64_t encoder_weight_seed(uint64_t base, int block, int kind, int head);
 float encoder_init_bound(int n);
-hipError_t encoder_create(int d_model, int n_heads, int d_ff, int n_blocks, int max_seq, uint64_t seed, Encoder **out);
-hipError_t encoder_forward(Encoder *E, const float *X, float *Y, int seq, hipStream_t s);
-void encoder_destroy(Encoder *E);
+// max_enc_seq, causal and kv_cache count only with cross
+hipError_t stack_create(int d_model, int n_heads, int d_ff, int n_blocks, int max_seq, int max_enc_seq, uint64_t seed,
+                        bool cross, bool causal, bool kv_cache, Stack **out);
+void stack_destroy(Stack *S);
+hipError_t encoder_forward(Stack *S, const float *X, float *Y, int seq, hipStream_t s);
+hipError_t decoder_begin(Stack *S, const float *enc_out, int enc_seq, hipStream_t s);
+hipError_t decoder_step(Stack *S, const float *X, float *Y, int pos, int n, hipStream_t s);
+hipError_t decoder_forward(Stack *S, const float *X, const float *enc_out, float *Y, int seq, int enc_seq,
+                           hipStream_t s);
 // draws a k x n fp32 weight into tmp (col_seeds[c] fills columns [c*cols_per_seed, (c+1)*cols_per_seed), one
 // reference tensor each, uniform [-bound, bound)) and packs it as B into a fresh allocation; tmp holds
 // k * n + k * cols_per_seed floats
 hipError_t encoder_make_packed(int k, int n, const std::vector<uint64_t> &col_seeds, int cols_per_seed, float bound,
                                void **packed, float *tmp, hipStream_t s);
-// The decoder counterpart (decoder.hip).
-struct Decoder;
-hipError_t decoder_create(int d_model, int n_heads, int d_ff, int n_blocks, int max_seq, int max_enc_seq, uint64_t seed,
-                          bool causal, bool kv_cache, Decoder **out);
-hipError_t decoder_begin(Decoder *D, const float *enc_out, int enc_seq, hipStream_t s);
-hipError_t decoder_step(Decoder *D, const float *X, float *Y, int pos, int n, hipStream_t s);
-hipError_t decoder_forward(Decoder *D, const float *X, const float *enc_out, float *Y, int seq, int enc_seq,
-                           hipStream_t s);
-void decoder_destroy(Decoder *D);
 const char *gemm_config_name();
 // Quantization-error statistics on the device (error_stats.hip); scratch = error_stats_scratch_bytes().
 size_t error_stats_scratch_bytes();

@@ -1,0 +1,359 @@
+// transformer.hip -- the counterparts of the reference's Encoder (transformer.cu:14-77; SURVEY.md s8f f1, BASELINE
+// config 5) and Decoder (transformer.cu:79-168) with their GEMM call sites on the int8 quantized path: ONE stack of
+// blocks, an encoder without and a decoder with the cross-attention third (DESIGN.md "Encoder", "Decoder").  Per block:
+//   1. self-attention on the block input            transformer.cu:37-59 / :93-126
+//      [Q | K | V] = quantized_mm(in, [Wq | Wk | Wv])   attention.cuh:54-56 -- ONE GEMM over all heads (per-column
+//                                                       absmax makes this bit-identical to per-head GEMMs)
+//      heads = attention(Q, K, V)                       attention.cuh:58-69 -- fp32 (activation x activation): bit-exact
+//                                                       op_mm<float> (sequential-k fmaf), batched over heads
+//      t = quantized_mm(heads, W_O), x1 = LN(t + heads) transformer.cu:52-59
+//   2. cross-attention (decoder)                    transformer.cu:128-150
+//      Q2 = quantized_mm(x1, Wq2), [K2 | V2] = quantized_mm(enc_out, [Wk2 | Wv2]),
+//      heads2 = attention(Q2, K2, V2) with seq queries and enc_seq keys, t = quantized_mm(heads2, W_O2),
+//      x2 = LN(t + heads2)
+//   3. FFN                                          transformer.cu:62-75 / :152-167, linear.cuh:50-54
+//      out = LN(relu(x W1 + b1) W2 + b2 + multiHeadOut), bias and relu fused into the GEMMs; multiHeadOut is the last
+//      attention's: heads2 in a decoder, heads in an encoder
+// Softmax and add + layernorm: encoder_ops.hip.  The attention launches: attention_launch.hip.
+//
+// Decisions where the reference cannot run as written:
+//   * arity (transformer.cu:37 calls forward(X, X, out); attention.cuh:47 takes (X, out)): self attention on the block
+//     input.  The decoder's attn.forward(output, enc_output, out) (:132): its first argument is read as the source of
+//     the queries, its second as the source of the keys and values -- the only reading in which enc_output is used;
+//   * d_ff (transformer.cu:62 sizes ffnOut {h, d_model}): the FFN hidden is {seq, d_ff};
+//   * weights are drawn ONCE per stack (the reference re-draws them on every call, :34, :53, :63): they are packed
+//     once (the LLM.int8() weight cache, s8f f2) -- seeded, reproducible.  W_O is redrawn at :144, so the
+//     cross-attention's output projection W_O2 is a tensor of its own;
+//   * heads are written straight into their column slice of multiHeadOut (no host round trip, :43-50); the residual
+//     adds multiHeadOut, as the reference does (:58, :74);
+//   * enc_out is quantized ONCE per forward and its packed form serves every block's [K2 | V2] projection: its
+//     per-row absmax scales do not depend on the weight, so this is bit-identical to quantizing it per block.
+//
+// Incremental decoding (QGEMM_DECODER_KV_CACHE with QGEMM_DECODER_CAUSAL).  Every block owns a
+// self-attention cache -- its own [Q | K | V] buffer of max_seq x 3 d_model, so the QKV GEMM of a step writes rows
+// pos .. straight into it -- and a cross cache [K2 | V2] of max_enc_seq x 2 d_model.
+//   decoder_begin  packs enc_out once, runs every block's [K2 | V2] projection into its cross cache, records enc_seq
+//                  and sets the filled length to 0;
+//   decoder_step   forward's steps and helpers on the n rows at positions pos .. pos + n - 1: the QKV projection into
+//                  cache rows pos .., the masked attention of those n query rows against cache rows 0 .. pos + n - 1
+//                  (q_pos0 = pos), W_O, add + layernorm, Wq2, the unmasked attention on the cross cache, W_O2, add +
+//                  layernorm, the FFN.  No [K2 | V2] GEMM and no enc_out pack.
+// The result is rows pos .. pos + n - 1 of the causal forward on the whole prefix, bit for bit.  The argument: (1)
+// every step but the attention is row-local -- the pack's scales are per row, the int8 GEMM accumulates exactly and
+// dequantizes per element, add + layernorm works on one row -- so a cache row holds what forward computes for that
+// row, whichever call wrote it; (2) the masked attention has the prefix property: row i reads K rows below its limit
+// alone, and the V rows past it enter as fmaf(+0, v, acc), which changes nothing WHILE THE CACHED V IS FINITE and no
+// P V accumulator is -0 (the conditions of forward(X[:n]) == forward(X)[:n] itself; a step's key
+// sequence ends at its own last row, so there is no V row past the last limit at all).  A non-finite V
+// row written by an earlier, longer sequence is never read either: rows pos + n .. are outside the call's seq_kv.
+// pos is a host argument; the decoder keeps a host-side filled length, updated at enqueue time: 0 <= pos <= filled,
+// then filled = pos + n (an earlier pos rewinds: speculative decoding, beam search).  begin and step allocate nothing
+// and do not synchronize; they share the stack's scratch buffers with forward, so a stack does one thing at a time.
+// forward on a cached decoder neither reads nor writes the caches.
+#include <cmath>
+#include <new>
+#include <vector>
+
+#include "qgemm_internal.h"
+
+namespace qgemm {
+
+namespace {
+
+// every tensor of a block its own seed stream; 8 .. 11 are the cross-attention's
+enum WeightKind { kWq = 0, kWk = 1, kWv = 2, kWo = 3, kW1 = 4, kB1 = 5, kW2 = 6, kB2 = 7,
+                  kWq2 = 8, kWk2 = 9, kWv2 = 10, kWo2 = 11 };
+
+}  // namespace
+
+// Seed of one weight tensor: every tensor its own counter stream (documented for the oracle).
+uint64_t encoder_weight_seed(uint64_t base, int block, int kind, int head) {
+    return base * 1000003ULL + (uint64_t)block * 4099ULL + (uint64_t)kind * 131ULL + (uint64_t)head;
+}
+
+// fl32(1 / sqrt(n)): the reference's "float max = 1.0f / std::sqrt(n)" with an int n (double sqrt).
+float encoder_init_bound(int n) { return (float)(1.0 / std::sqrt((double)n)); }
+
+struct Block {
+    void *wqkv = nullptr, *wo = nullptr, *w1 = nullptr, *w2 = nullptr;  // packed (W^T int8 + Cw)
+    void *wq2 = nullptr, *wkv2 = nullptr, *wo2 = nullptr;               // cross
+    float *b1 = nullptr, *b2 = nullptr;
+    float *qkv_cache = nullptr, *kv2_cache = nullptr;  // kv_cache: max_seq x 3d and max_enc_seq x 2d
+};
+
+struct Stack {
+    int d_model = 0, n_heads = 0, d_ff = 0, n_blocks = 0, max_seq = 0, max_enc_seq = 0;
+    bool cross = false;     // the blocks have the cross-attention third: a decoder
+    bool causal = false;    // the self-attention masks keys past the query's own row (QGEMM_DECODER_CAUSAL)
+    bool kv_cache = false;  // the blocks own caches for decoder_begin / decoder_step (QGEMM_DECODER_KV_CACHE)
+    int enc_seq = 0;        // of the sequence begun (0: no decoder_begin yet)
+    int filled = 0;         // cache rows 0 .. filled - 1 hold the sequence so far (host side, at enqueue time)
+    std::vector<Block> blocks;
+    float *qkv = nullptr, *scores = nullptr, *heads = nullptr, *t = nullptr, *ffn = nullptr, *x = nullptr;
+    float *xa = nullptr, *xb = nullptr;
+    float *q2 = nullptr, *kv2 = nullptr, *heads2 = nullptr;  // cross
+    char *ws = nullptr;  // [split-K scratch][packed activations][cross: packed enc_out]
+    size_t scratch_bytes = 0, act_bytes = 0;
+};
+
+namespace {
+
+hipError_t alloc(void **p, size_t bytes) { return hipMalloc(p, bytes ? bytes : 16); }
+
+template <typename T>
+hipError_t alloc_f(T **p, size_t count) {
+    return alloc(reinterpret_cast<void **>(p), count * sizeof(T));
+}
+
+}  // namespace
+
+// draw a K x N fp32 weight (uniform [-bound, bound), reference init formula) and pack it as B
+hipError_t encoder_make_packed(int k, int n, const std::vector<uint64_t> &col_seeds, int cols_per_seed, float bound,
+                               void **packed, float *tmp, hipStream_t s) {
+    // col_seeds[c] fills columns [c*cols_per_seed, (c+1)*cols_per_seed) -- one reference tensor each
+    hipError_t e;
+    float *one = tmp + (size_t)k * n;  // k x cols_per_seed staging
+    for (size_t c = 0; c < col_seeds.size(); ++c) {
+        if ((e = launch_fill_uniform(one, (int64_t)k * cols_per_seed, col_seeds[c], -bound, bound, s)) != hipSuccess)
+            return e;
+        if ((e = hipMemcpy2DAsync(tmp + c * cols_per_seed, sizeof(float) * n, one, sizeof(float) * cols_per_seed,
+                                  sizeof(float) * cols_per_seed, k, hipMemcpyDeviceToDevice, s)) != hipSuccess)
+            return e;
+    }
+    if ((e = alloc(packed, packed_bytes(n, k))) != hipSuccess) return e;
+    // B = W (k x n, row-major): reduction vectors are its columns -> pack_cols path
+    return launch_pack_cols(tmp, n, k, n, 127.0f, packed_view(*packed, n, k), s);
+}
+
+namespace {
+
+// the packed activations of the next linear (one buffer, reused by every linear in stream order) ...
+PackedView act_view(Stack &S, int seq, int k) { return packed_view(S.ws + S.scratch_bytes, seq, k); }
+// ... and the packed encoder output, written once per forward or begin and read by every block
+PackedView enc_view(Stack &S, int enc_seq) {
+    return packed_view(S.ws + S.scratch_bytes + S.act_bytes, enc_seq, S.d_model);
+}
+
+// y = quantized_mm(packed rows va, packed weight) [+ bias] [relu]
+hipError_t gemm(Stack &S, const PackedView &va, int rows, int k, const void *wpacked, int n, float *y,
+                const float *bias, bool relu, hipStream_t s) {
+    const float inv_r2 = 1.0f / (127.0f * 127.0f);
+    return launch_gemm_dequant(va, packed_view(wpacked, n, k), y, n, 1, rows, n, inv_r2, S.ws, S.scratch_bytes, s, bias,
+                               relu, /*tickets_zeroed=*/true);
+}
+
+// x == nullptr: the activations are already packed in act_view (by the add+layernorm that made them)
+hipError_t linear(Stack &S, const float *x, int seq, int k, const void *wpacked, int n, float *y, const float *bias,
+                  bool relu, hipStream_t s) {
+    // pack the activations (Cx per row: op_absmax(X), X_int8), then the GEMM with the fused epilogue
+    const PackedView va = act_view(S, seq, k);
+    const hipError_t e = x ? launch_pack_rows(x, k, 1, seq, k, 127.0f, va, s) : hipSuccess;
+    if (e != hipSuccess) return e;
+    return gemm(S, va, seq, k, wpacked, n, y, bias, relu, s);
+}
+
+}  // namespace
+
+void stack_destroy(Stack *S) {
+    if (!S) return;
+    for (auto &b : S->blocks)
+        for (void *p : {b.wqkv, b.wo, b.wq2, b.wkv2, b.wo2, b.w1, b.w2, (void *)b.b1, (void *)b.b2,
+                        (void *)b.qkv_cache, (void *)b.kv2_cache})
+            (void)hipFree(p);
+    for (void *p : {(void *)S->qkv, (void *)S->scores, (void *)S->heads, (void *)S->t, (void *)S->ffn, (void *)S->x,
+                    (void *)S->q2, (void *)S->kv2, (void *)S->heads2, (void *)S->xa, (void *)S->xb, (void *)S->ws})
+        (void)hipFree(p);
+    delete S;
+}
+
+hipError_t stack_create(int d_model, int n_heads, int d_ff, int n_blocks, int max_seq, int max_enc_seq, uint64_t seed,
+                        bool cross, bool causal, bool kv_cache, Stack **out) {
+    *out = nullptr;
+    if (kv_cache && !causal) return hipErrorInvalidValue;
+    if (d_model < 2 || n_heads < 1 || d_model % n_heads || d_ff < 2 || n_blocks < 1 || max_seq < 1 || max_seq > 4096 ||
+        (cross && (max_enc_seq < 1 || max_enc_seq > 4096)) || d_model > 4096)
+        return hipErrorInvalidValue;
+    Stack *S = new (std::nothrow) Stack;
+    if (!S) return hipErrorOutOfMemory;
+    S->d_model = d_model;
+    S->n_heads = n_heads;
+    S->d_ff = d_ff;
+    S->n_blocks = n_blocks;
+    S->max_seq = max_seq;
+    S->max_enc_seq = cross ? max_enc_seq : 0;
+    S->cross = cross;
+    S->causal = causal;
+    S->kv_cache = kv_cache;
+    S->blocks.resize(n_blocks);
+    const int d = d_model, dk = d_model / n_heads;
+    const size_t Sq = (size_t)max_seq, Se = (size_t)S->max_enc_seq;
+    hipError_t e = hipSuccess;
+    auto fail = [&](hipError_t err) {
+        stack_destroy(S);
+        return err;
+    };
+    // scores only where some forward or step can reach the three launches (both attentions share them); else they
+    // stay nullptr, which launch_attention refuses on that path
+    const int max_kv = std::max(max_seq, S->max_enc_seq);
+    if (attention_needs_scores(max_seq, max_kv, dk) && (e = alloc_f(&S->scores, (size_t)n_heads * Sq * (size_t)max_kv)))
+        return fail(e);
+    if ((e = alloc_f(&S->qkv, Sq * 3 * d)) || (e = alloc_f(&S->heads, Sq * d)) ||
+        (e = alloc_f(&S->t, Sq * d)) || (e = alloc_f(&S->ffn, Sq * d_ff)) || (e = alloc_f(&S->x, Sq * d)) ||
+        (e = alloc_f(&S->xa, Sq * d)) || (e = alloc_f(&S->xb, Sq * d)))
+        return fail(e);
+    if (cross && ((e = alloc_f(&S->q2, Sq * d)) || (e = alloc_f(&S->kv2, Se * 2 * d)) || (e = alloc_f(&S->heads2, Sq * d))))
+        return fail(e);
+    // workspace: split-K scratch for the largest of the linear shapes + the packed activations (+ the packed enc_out)
+    const int shapes[5][3] = {{max_seq, 3 * d, d}, {max_seq, d, d}, {max_seq, d_ff, d}, {max_seq, d, d_ff},
+                              {S->max_enc_seq, 2 * d, d}};  // (m, n, k); the last one exists only with cross
+    size_t scratch = 0;
+    for (int i = 0; i < (cross ? 5 : 4); ++i)
+        scratch = std::max(scratch, gemm_scratch_bytes(shapes[i][0], shapes[i][1], shapes[i][2]));
+    const size_t act = std::max(packed_bytes(max_seq, d), packed_bytes(max_seq, d_ff));
+    S->scratch_bytes = (scratch + 255) & ~(size_t)255;
+    S->act_bytes = (act + 255) & ~(size_t)255;
+    const size_t ws_bytes = S->scratch_bytes + S->act_bytes + (cross ? packed_bytes(max_enc_seq, d) : 0);
+    if ((e = alloc(reinterpret_cast<void **>(&S->ws), ws_bytes))) return fail(e);
+    if ((e = hipMemset(S->ws, 0, S->scratch_bytes))) return fail(e);  // split-K tickets start at zero
+
+    // weights, drawn once with the reference's init bounds (attention.cuh:37-41, linear.cuh:34-39,
+    // transformer.cu:53, :120, :144) and packed
+    const size_t maxk = std::max(d, d_ff), maxn = std::max(3 * d, d_ff);
+    float *tmp = nullptr;
+    if ((e = alloc_f(&tmp, maxk * maxn + maxk * maxn))) return fail(e);
+    hipStream_t s = nullptr;
+    for (int i = 0; i < n_blocks && e == hipSuccess; ++i) {
+        Block &B = S->blocks[i];
+        auto head_seeds = [&](int first, int last) {
+            std::vector<uint64_t> v;
+            for (int kind = first; kind <= last; ++kind)
+                for (int h = 0; h < n_heads; ++h) v.push_back(encoder_weight_seed(seed, i, kind, h));
+            return v;
+        };
+        const float bk = encoder_init_bound(dk), bd = encoder_init_bound(d), bf = encoder_init_bound(d_ff);
+        if ((e = encoder_make_packed(d, 3 * d, head_seeds(kWq, kWv), dk, bk, &B.wqkv, tmp, s))) break;
+        if ((e = encoder_make_packed(d, d, {encoder_weight_seed(seed, i, kWo, 0)}, d, 1.0f, &B.wo, tmp, s))) break;
+        if (cross) {
+            if ((e = encoder_make_packed(d, d, head_seeds(kWq2, kWq2), dk, bk, &B.wq2, tmp, s))) break;
+            if ((e = encoder_make_packed(d, 2 * d, head_seeds(kWk2, kWv2), dk, bk, &B.wkv2, tmp, s))) break;
+            if ((e = encoder_make_packed(d, d, {encoder_weight_seed(seed, i, kWo2, 0)}, d, 1.0f, &B.wo2, tmp, s))) break;
+        }
+        if ((e = encoder_make_packed(d, d_ff, {encoder_weight_seed(seed, i, kW1, 0)}, d_ff, bd, &B.w1, tmp, s))) break;
+        if ((e = encoder_make_packed(d_ff, d, {encoder_weight_seed(seed, i, kW2, 0)}, d, bf, &B.w2, tmp, s))) break;
+        if ((e = alloc_f(&B.b1, d_ff)) || (e = alloc_f(&B.b2, d))) break;
+        if (kv_cache && ((e = alloc_f(&B.qkv_cache, Sq * 3 * d)) || (e = alloc_f(&B.kv2_cache, Se * 2 * d)))) break;
+        if ((e = launch_fill_uniform(B.b1, d_ff, encoder_weight_seed(seed, i, kB1, 0), -bd, bd, s))) break;
+        if ((e = launch_fill_uniform(B.b2, d, encoder_weight_seed(seed, i, kB2, 0), -bf, bf, s))) break;
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    (void)hipFree(tmp);
+    if (e != hipSuccess) return fail(e);
+    *out = S;
+    return hipSuccess;
+}
+
+namespace {
+
+// One pass over the blocks on `rows` rows, for forward (cached = false: the rows are the whole sequence, [Q | K | V]
+// and [K2 | V2] live in the stack's scratch buffers, [K2 | V2] is projected here from the packed enc_out) and for a
+// step (cached = true: the rows sit at positions pos .., [Q | K | V] rows pos .. are written into the block's cache
+// and attend to cache rows 0 .. pos + rows - 1, [K2 | V2] is the block's cross cache).
+hipError_t run_blocks(Stack *S, const float *X, float *Y, int rows, int enc_seq, bool cached, int pos, hipStream_t s) {
+    const int d = S->d_model, H = S->n_heads, dk = d / H;
+    const int seq = rows;
+    const float scale = (float)(1.0 / std::sqrt((double)dk));  // attention.cuh:64
+    const float *in = X;
+    bool in_packed = false;  // the previous block's last add+layernorm packed its output already
+    hipError_t e;
+    float *mho = S->cross ? S->heads2 : S->heads;  // the multiHeadOut that the FFN's residual adds: the last attention's
+    for (int i = 0; i < S->n_blocks; ++i) {
+        const Block &B = S->blocks[i];
+        const bool last = i == S->n_blocks - 1;
+        float *out = last ? Y : (i % 2 ? S->xb : S->xa);
+        // ---- self-attention on the block input: [Q | K | V] = in @ [Wq | Wk | Wv] over all heads
+        float *qkv = cached ? B.qkv_cache : S->qkv;               // row 0 of [Q | K | V]
+        float *qrows = qkv + (size_t)(cached ? pos : 0) * 3 * d;  // the rows this call projects
+        if ((e = linear(*S, in_packed ? nullptr : in, seq, d, B.wqkv, 3 * d, qrows, nullptr, false, s))) return e;
+        // S_h = Q_h K_h^T, P_h = softmax(S_h * 1/sqrt(d_k)), heads[:, h*d_v..] = P_h V_h, Q, K and V the thirds of qkv
+        // (causal: row i sees rows 0 .. i, so row i of the forward depends on rows 0 .. i of X alone)
+        if ((e = launch_attention(qrows, 3 * d, qkv + d, 3 * d, qkv + 2 * d, 3 * d, S->heads, d, seq,
+                                  cached ? pos + seq : seq, H, dk, scale, cached ? pos : (S->causal ? 0 : kNoMask),
+                                  S->scores, s)))
+            return e;
+        // output = multiHeadOut @ W_O; x1 = LN(output + multiHeadOut), packed by the same launch: the next linear
+        // quantizes nothing itself
+        if ((e = linear(*S, S->heads, seq, d, B.wo, d, S->t, nullptr, false, s))) return e;
+        if ((e = launch_add_layernorm_rows_pack(S->t, S->heads, S->x, seq, d, 127.0f, act_view(*S, seq, d), s)))
+            return e;
+        if (S->cross) {
+            // ---- cross-attention: queries from x1, keys and values from enc_out
+            if ((e = linear(*S, nullptr, seq, d, B.wq2, d, S->q2, nullptr, false, s))) return e;
+            float *kv2 = cached ? B.kv2_cache : S->kv2;
+            if (!cached && (e = gemm(*S, enc_view(*S, enc_seq), enc_seq, d, B.wkv2, 2 * d, kv2, nullptr, false, s)))
+                return e;
+            if ((e = launch_attention(S->q2, d, kv2, 2 * d, kv2 + d, 2 * d, mho, d, seq, enc_seq, H, dk, scale, kNoMask,
+                                      S->scores, s)))
+                return e;
+            if ((e = linear(*S, mho, seq, d, B.wo2, d, S->t, nullptr, false, s))) return e;
+            // x2 = LN(t + heads2), packed for the FFN's first linear
+            if ((e = launch_add_layernorm_rows_pack(S->t, mho, S->x, seq, d, 127.0f, act_view(*S, seq, d), s)))
+                return e;
+        }
+        // ---- FFN: relu(x W1 + b1) W2 + b2; LN(ffn + multiHeadOut)
+        if ((e = linear(*S, nullptr, seq, d, B.w1, S->d_ff, S->ffn, B.b1, true, s))) return e;
+        if ((e = linear(*S, S->ffn, seq, S->d_ff, B.w2, d, S->t, B.b2, false, s))) return e;
+        e = last ? launch_add_layernorm_rows(S->t, mho, out, seq, d, s)
+                 : launch_add_layernorm_rows_pack(S->t, mho, out, seq, d, 127.0f, act_view(*S, seq, d), s);
+        if (e) return e;
+        in = out;
+        in_packed = !last;
+    }
+    return hipSuccess;
+}
+
+// Cx and the int8 rows of enc_out, once for every block's [K2 | V2] projection
+hipError_t pack_enc(Stack *S, const float *enc_out, int enc_seq, hipStream_t s) {
+    return launch_pack_rows(enc_out, S->d_model, 1, enc_seq, S->d_model, 127.0f, enc_view(*S, enc_seq), s);
+}
+
+}  // namespace
+
+hipError_t encoder_forward(Stack *S, const float *X, float *Y, int seq, hipStream_t s) {
+    if (!S || S->cross || !X || !Y || seq < 1 || seq > S->max_seq) return hipErrorInvalidValue;
+    return run_blocks(S, X, Y, seq, 0, /*cached=*/false, 0, s);
+}
+
+hipError_t decoder_forward(Stack *S, const float *X, const float *enc_out, float *Y, int seq, int enc_seq,
+                           hipStream_t s) {
+    if (!S || !S->cross || !X || !enc_out || !Y || seq < 1 || seq > S->max_seq || enc_seq < 1 ||
+        enc_seq > S->max_enc_seq)
+        return hipErrorInvalidValue;
+    const hipError_t e = pack_enc(S, enc_out, enc_seq, s);
+    if (e) return e;
+    return run_blocks(S, X, Y, seq, enc_seq, /*cached=*/false, 0, s);
+}
+
+hipError_t decoder_begin(Stack *S, const float *enc_out, int enc_seq, hipStream_t s) {
+    if (!S || !S->cross || !S->kv_cache || !enc_out || enc_seq < 1 || enc_seq > S->max_enc_seq)
+        return hipErrorInvalidValue;
+    const int d = S->d_model;
+    hipError_t e = pack_enc(S, enc_out, enc_seq, s);
+    if (e) return e;
+    for (const Block &B : S->blocks)
+        if ((e = gemm(*S, enc_view(*S, enc_seq), enc_seq, d, B.wkv2, 2 * d, B.kv2_cache, nullptr, false, s))) return e;
+    S->enc_seq = enc_seq;
+    S->filled = 0;
+    return hipSuccess;
+}
+
+hipError_t decoder_step(Stack *S, const float *X, float *Y, int pos, int n, hipStream_t s) {
+    if (!S || !S->cross || !S->kv_cache || S->enc_seq < 1 || !X || !Y || n < 1 || pos < 0 || pos > S->filled ||
+        n > S->max_seq - pos)
+        return hipErrorInvalidValue;
+    const hipError_t e = run_blocks(S, X, Y, n, S->enc_seq, /*cached=*/true, pos, s);
+    if (e) return e;
+    S->filled = pos + n;
+    return hipSuccess;
+}
+
+}  // namespace qgemm

@@ -209,3 +209,41 @@ def test_decoder_and_encoder_on_two_streams(qg, oracle, device):
         for obj in (dec, enc):
             if obj is not None:
                 obj.close()
+
+
+def test_encoder_and_decoder_handles_are_not_interchangeable(qg, oracle, device):
+    """Encoder and decoder handles are the same kind of object inside the library (a stack of blocks without / with
+    cross-attention).  Through the raw entry points: qgemm_decoder_forward / _begin / _step on an encoder's handle and
+    qgemm_encoder_forward on a decoder's return the invalid-value code and write nothing; the matching calls still work
+    on the same handles afterwards.  The decoder has its caches, so begin and step are refused for the handle alone."""
+    d, H, dff, blocks, seq = 32, 2, 32, 1, 8
+    L = qg.load()
+    enc = qg.Encoder(d, H, dff, blocks, max_seq=seq, seed=61)
+    dec = qg.Decoder(d, H, dff, blocks, max_seq=seq, max_enc_seq=seq, seed=61, causal=True, kv_cache=True)
+    try:
+        X, E = _dev(oracle.uniform((seq, d), 62), device), _dev(oracle.uniform((seq, d), 63), device)
+        Y = torch.full((seq, d), -7.25, device=device)
+        stream = qg._stream(device)
+        refused = [
+            ("decoder_forward on an encoder",
+             lambda: L.qgemm_decoder_forward(enc._h, X.data_ptr(), E.data_ptr(), Y.data_ptr(), seq, seq, stream)),
+            ("decoder_begin on an encoder", lambda: L.qgemm_decoder_begin(enc._h, E.data_ptr(), seq, stream)),
+            ("decoder_step on an encoder",
+             lambda: L.qgemm_decoder_step(enc._h, X.data_ptr(), Y.data_ptr(), 0, 1, stream)),
+            ("encoder_forward on a decoder",
+             lambda: L.qgemm_encoder_forward(dec._h, X.data_ptr(), Y.data_ptr(), seq, stream)),
+        ]
+        for what, call in refused:
+            assert call() == qg.HIP_ERROR_INVALID_VALUE, what
+            torch.cuda.synchronize()
+            assert bool((Y == -7.25).all()), f"{what} wrote to Y"
+        assert_bits_equal(enc.forward(X).cpu().numpy(),
+                          oracle.encoder_forward(oracle.uniform((seq, d), 62), d, H, dff, blocks, 61),
+                          "encoder forward after the refused calls")
+        full = dec.forward(X, E)
+        dec.begin(E)
+        rows = torch.cat([dec.step(X[:5]), dec.step(X[5:])])
+        assert torch.equal(rows.view(torch.int32), full.view(torch.int32)), "decoder begin + steps after the refusals"
+    finally:
+        enc.close()
+        dec.close()
