@@ -268,6 +268,65 @@ QGEMM_API int qgemm_decoder_begin(void *decoder, const float *enc_out, int enc_s
 QGEMM_API int qgemm_decoder_step(void *decoder, const float *X, float *Y, int pos, int n, void *stream);
 QGEMM_API int qgemm_decoder_destroy(void *decoder);
 
+/* ---- Batched incremental decoding: many sequences per decoder step --------------------
+ * qgemm_attention_decode_batched: the decode launch of qgemm_attention / qgemm_attention_causal for up to
+ * QGEMM_DECODE_MAX_BATCH independent sequences in ONE launch.  Q and O hold n_seqs * rows_per_seq rows (row strides
+ * q / o_stride_h, unit inner stride), rows b * rows_per_seq .. + rows_per_seq - 1 are sequence b's.  K and V are
+ * stacks of slabs: sequence b reads rows 0 .. seq_kv[b] - 1 (row stride k / v_stride_h) of the slab that starts at
+ * K + kv_slot[b] * k_stride_seq (V likewise; strides in floats).  kv_slot, seq_kv and q_pos0 are HOST arrays of n_seqs
+ * ints, read when the call is enqueued: they travel in the kernel's arguments, so nothing is copied to the device,
+ * allocated or synchronized, and a captured graph replays the values of the capture.  kv_slot == NULL means slabs
+ * 0, 1, 2, ..; q_pos0 == NULL means no mask.
+ * Contract: for every b, rows b * rows_per_seq .. of O are BIT FOR BIT what qgemm_attention (q_pos0 == NULL) or
+ * qgemm_attention_causal with q_pos0[b] gives on those query rows and the seq_kv[b] rows of slab kv_slot[b].  Two
+ * sequences may share a slab.  O must not overlap Q, K or V (not checked).
+ * hipErrorInvalidValue before any launch: a null Q / K / V / O / seq_kv, n_seqs < 0 or > 64, rows_per_seq < 1 or > 8,
+ * d_k < 1 or > 64, n_heads < 1, any seq_kv[b] < 1 or > 4096, any q_pos0[b] < 0, any kv_slot[b] < 0; n_seqs == 0
+ * returns 0. */
+enum { QGEMM_DECODE_MAX_BATCH = 64 };
+QGEMM_API int qgemm_attention_decode_batched(const float *Q, int64_t q_stride_h,
+                                   const float *K, int64_t k_stride_h, int64_t k_stride_seq,
+                                   const float *V, int64_t v_stride_h, int64_t v_stride_seq,
+                                   float *O, int64_t o_stride_h, int n_seqs, int rows_per_seq,
+                                   const int *kv_slot, const int *seq_kv, const int *q_pos0,
+                                   int n_heads, int d_k, float scale, void *stream);
+/* Cache slots: ONE decoder (one copy of the packed weights) that holds n_slots (1 .. 64) independent sequences.
+ * flags must be exactly QGEMM_DECODER_CAUSAL | QGEMM_DECODER_KV_CACHE.  Every block's self cache is one allocation of
+ * n_slots x max_seq x 3 d_model floats ([Q | K | V] rows per slot, as before) and its cross cache one of n_slots x
+ * max_enc_seq x 2 d_model; enc_seq and the filled length are host state per slot.  n_slots == 1 allocates and behaves
+ * exactly as qgemm_decoder_create_ex with those flags, and every decoder created with the cache flag has slot 0:
+ * qgemm_decoder_begin / qgemm_decoder_step ARE begin_slot(0) / step_slot(0).  With n_slots > 1 the decoder's scratch
+ * buffers hold max(max_seq, 8 * n_slots) rows.
+ *   begin_slot  qgemm_decoder_begin on one slot: the slot's cross cache, its enc_seq, filled = 0.
+ *   step_slot   qgemm_decoder_step on one slot (the QKV GEMM writes the slot's cache rows directly).
+ *   step_batch  one step of n_seqs (1 .. n_slots) DIFFERENT slots, rows_per_seq (1 .. 8) rows each.  X and Y are
+ *               (n_seqs * rows_per_seq) x d_model, contiguous; rows b * r .. b * r + r - 1 are the new rows of slot
+ *               slots[b] at positions pos[b] .. pos[b] + r - 1 (slots and pos: host arrays, read at enqueue time).
+ *               Row for row Y is BIT FOR BIT what step_slot(slots[b], .., pos[b], r) gives for that sequence alone, and
+ *               so the rows of the causal forward on that sequence's prefix: every step but the attention is row-local
+ *               (per-row quantization scales, exact int32 accumulation, per-element dequantization, one-row layernorm),
+ *               and the attention of all sequences is one qgemm_attention_decode_batched launch over the cache slabs.
+ *               On success filled[slots[b]] = pos[b] + r; an earlier pos rewinds that sequence alone.  Needs
+ *               d_model / n_heads <= 64.  The Q third of the cache rows it writes is unspecified.
+ *   copy_slot   forks a sequence: rows 0 .. filled - 1 of every block's self cache and rows 0 .. enc_seq - 1 of its
+ *               cross cache, device to device in stream order; dst takes src's enc_seq and filled length.
+ *   slot_state  the host state of a slot (enc_seq 0: not begun); enc_seq / filled may be NULL.  No GPU call.
+ * None of these allocates or synchronizes; they share the decoder's scratch in stream order with forward, so a decoder
+ * still does one thing at a time.  forward on a slotted decoder touches no cache.
+ * hipErrorInvalidValue before any launch and without moving any filled length: a decoder without the cache flag, a
+ * null pointer, a slot out of range or not begun (begin_slot: out of range), the same slot twice in one step_batch,
+ * pos[b] < 0, pos[b] > filled, pos[b] + r > max_seq, n_seqs or rows_per_seq out of range, d_k > 64 (step_batch);
+ * copy_slot with dst == src or a source not begun; create_slots with other flags, n_slots < 1 or > 64 or a null
+ * handle (the handle is left NULL). */
+QGEMM_API int qgemm_decoder_create_slots(int d_model, int n_heads, int d_ff, int n_blocks, int max_seq, int max_enc_seq,
+                               uint64_t seed, int flags, int n_slots, void **decoder);
+QGEMM_API int qgemm_decoder_begin_slot(void *decoder, int slot, const float *enc_out, int enc_seq, void *stream);
+QGEMM_API int qgemm_decoder_step_slot(void *decoder, int slot, const float *X, float *Y, int pos, int n, void *stream);
+QGEMM_API int qgemm_decoder_step_batch(void *decoder, int n_seqs, const int *slots, const int *pos, int rows_per_seq,
+                             const float *X, float *Y, void *stream);
+QGEMM_API int qgemm_decoder_copy_slot(void *decoder, int dst_slot, int src_slot, void *stream);
+QGEMM_API int qgemm_decoder_slot_state(void *decoder, int slot, int *enc_seq, int *filled);
+
 /* ---- LLM.int8() outlier decomposition ------------------------------------------
  * Feature columns k of A (= rows of B) holding an element with NOT(|x| <= threshold) (the reference's
  * AbsCompareLTEConstFunc, op_elemwise.cuh:293-306; NaN counts as an outlier) are multiplied in fp32,

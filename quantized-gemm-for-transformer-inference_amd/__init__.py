@@ -73,6 +73,13 @@ EXPORTED_SYMBOLS = (
     "qgemm_decoder_begin",
     "qgemm_decoder_step",
     "qgemm_decoder_destroy",
+    "qgemm_attention_decode_batched",
+    "qgemm_decoder_create_slots",
+    "qgemm_decoder_begin_slot",
+    "qgemm_decoder_step_slot",
+    "qgemm_decoder_step_batch",
+    "qgemm_decoder_copy_slot",
+    "qgemm_decoder_slot_state",
     "qgemm_mm_outlier_workspace_size",
     "qgemm_mm_outlier",
     "qgemm_outlier_count",
@@ -109,6 +116,7 @@ HIP_ERROR_INVALID_VALUE = 1
 QGEMM_F32, QGEMM_BF16 = 0, 1  # element-type tags of the _dt entry points (include/qgemm.h)
 QGEMM_DECODER_CAUSAL = 1       # qgemm_decoder_create_ex flag: causal mask on the self-attention
 QGEMM_DECODER_KV_CACHE = 8     # ... and per-block key / value caches for begin() / step() (with CAUSAL only)
+QGEMM_DECODE_MAX_BATCH = 64    # sequences per attention_decode_batched / step_batch call, cache slots per decoder
 
 _lock = threading.Lock()
 _lib = None
@@ -212,6 +220,23 @@ def load() -> ctypes.CDLL:
         L.qgemm_attention_plan.restype = i32
         L.qgemm_decoder_destroy.argtypes = [vp]
         L.qgemm_decoder_destroy.restype = i32
+        ip = ctypes.POINTER(i32)
+        L.qgemm_attention_decode_batched.argtypes = [vp, i64, vp, i64, i64, vp, i64, i64, vp, i64, i32, i32, ip, ip, ip,
+                                                     i32, i32, f32, vp]
+        L.qgemm_attention_decode_batched.restype = i32
+        L.qgemm_decoder_create_slots.argtypes = [i32, i32, i32, i32, i32, i32, ctypes.c_uint64, i32, i32,
+                                                 ctypes.POINTER(vp)]
+        L.qgemm_decoder_create_slots.restype = i32
+        L.qgemm_decoder_begin_slot.argtypes = [vp, i32, vp, i32, vp]
+        L.qgemm_decoder_begin_slot.restype = i32
+        L.qgemm_decoder_step_slot.argtypes = [vp, i32, vp, vp, i32, i32, vp]
+        L.qgemm_decoder_step_slot.restype = i32
+        L.qgemm_decoder_step_batch.argtypes = [vp, i32, ip, ip, i32, vp, vp, vp]
+        L.qgemm_decoder_step_batch.restype = i32
+        L.qgemm_decoder_copy_slot.argtypes = [vp, i32, i32, vp]
+        L.qgemm_decoder_copy_slot.restype = i32
+        L.qgemm_decoder_slot_state.argtypes = [vp, i32, ip, ip]
+        L.qgemm_decoder_slot_state.restype = i32
         L.qgemm_mm_outlier_workspace_size.argtypes = [i32, i32, i32]
         L.qgemm_mm_outlier_workspace_size.restype = sz
         L.qgemm_mm_outlier.argtypes = [vp, vp, vp, i32, i32, i32, f32, vp, sz, vp]
@@ -908,6 +933,58 @@ def attention(Q, K, V, n_heads: int, scale=None, O=None, causal: bool = False, q
     return O
 
 
+def _int_array(values, n: int, name: str):
+    """A host int array of n entries for the C-ABI (None stays NULL)."""
+    if values is None:
+        return None
+    values = [int(v) for v in values]
+    assert len(values) == n, f"{name}: one entry per sequence"
+    return (ctypes.c_int * max(1, n))(*values)
+
+
+def attention_decode_batched(Q, K, V, n_heads: int, seq_kv, q_pos0=None, kv_slot=None, rows_per_seq: int = 1,
+                             scale=None, O=None):
+    """The decode attention launch for up to 64 independent sequences at once (qgemm_attention_decode_batched).
+    Q: (n_seqs * rows_per_seq) x d, sequence b's query rows at b * rows_per_seq ..; K and V: [slabs, rows, d] fp32
+    device tensors or views with unit inner stride; sequence b attends to rows 0 .. seq_kv[b] - 1 of slab kv_slot[b]
+    (left out: slab b).  q_pos0 (one per sequence) masks as attention(causal=True, q_pos0=q_pos0[b]); left out there
+    is no mask.  seq_kv, q_pos0 and kv_slot are host sequences of ints, read at the call.  Rows b * rows_per_seq .. of
+    the result equal attention() on that sequence's views bit for bit."""
+    import math
+    import torch
+    _require_device_f32(Q, "Q")
+    assert Q.stride(1) == 1 or Q.shape[1] == 1, "Q must have unit inner stride"
+    for t, nm in ((K, "K"), (V, "V")):
+        assert isinstance(t, torch.Tensor) and t.dim() == 3 and t.is_cuda and t.dtype == torch.float32, \
+            f"{nm}: a 3-D float32 device tensor [slabs, rows, d]"
+        assert t.stride(2) == 1 or t.shape[2] == 1, f"{nm} must have unit inner stride"
+    rows, d = Q.shape
+    assert K.shape[2] == d and V.shape[2] == d, "K and V: [slabs, rows, d], d as Q"
+    assert rows_per_seq >= 1 and rows % rows_per_seq == 0, "Q holds rows_per_seq rows per sequence"
+    n_seqs = rows // rows_per_seq
+    assert n_heads >= 1 and d % n_heads == 0, "d % n_heads == 0"
+    dk = d // n_heads
+    seq_kv = [int(v) for v in seq_kv]
+    slots = list(range(n_seqs)) if kv_slot is None else [int(v) for v in kv_slot]
+    assert len(seq_kv) == n_seqs and len(slots) == n_seqs, "seq_kv and kv_slot: one entry per sequence"
+    for b in range(n_seqs):  # the slabs and rows the call reads exist
+        assert 0 <= slots[b] < min(K.shape[0], V.shape[0]), f"kv_slot[{b}] names no slab of K / V"
+        assert seq_kv[b] <= min(K.shape[1], V.shape[1]), f"seq_kv[{b}] exceeds the slab's rows"
+    if scale is None:
+        scale = ctypes.c_float(1.0 / math.sqrt(float(dk))).value  # attention.cuh:64
+    if O is None:
+        O = torch.empty((rows, d), dtype=torch.float32, device=Q.device)
+    _require_device_f32(O, "O")
+    assert O.shape == (rows, d) and (O.stride(1) == 1 or d == 1), "O: as Q, with unit inner stride"
+    _check("qgemm_attention_decode_batched",
+           load().qgemm_attention_decode_batched(
+               Q.data_ptr(), Q.stride(0), K.data_ptr(), K.stride(1), K.stride(0), V.data_ptr(), V.stride(1),
+               V.stride(0), O.data_ptr(), O.stride(0), n_seqs, rows_per_seq, _int_array(kv_slot, n_seqs, "kv_slot"),
+               _int_array(seq_kv, n_seqs, "seq_kv"), _int_array(q_pos0, n_seqs, "q_pos0"), n_heads, dk, float(scale),
+               _stream(Q.device)))
+    return O
+
+
 def attention_plan(seq_q: int, seq_kv: int, n_heads: int, d_k: int) -> str:
     """The launch attention() takes for a shape (qgemm_attention_plan): a name that begins "attention_decode",
     "attention_fused" or "three_launches".  Needs no GPU; raises QGemmError for dimensions attention() refuses."""
@@ -922,16 +999,25 @@ class Decoder:
     QGEMM_DECODER_CAUSAL): the self-attention is masked, row i sees rows 0 .. i, and forward(X[:n]) equals
     forward(X)[:n] bit for bit.  kv_cache=True (QGEMM_DECODER_KV_CACHE, with causal=True only): begin(enc_out) starts a
     sequence and step(X_new) returns the output rows of the new input rows alone -- the rows forward would give for them
-    on the whole prefix, bit for bit -- from per-block key / value caches."""
+    on the whole prefix, bit for bit -- from per-block key / value caches.  n_slots > 1
+    (qgemm_decoder_create_slots): the caches hold that many independent sequences on one copy of the weights;
+    begin_slot / step_slot drive one of them, step_batch advances many in one step, copy_slot forks one (DESIGN.md s17);
+    begin / step are slot 0's."""
 
     def __init__(self, d_model: int, n_heads: int, d_ff: int, n_blocks: int, max_seq: int, max_enc_seq: int,
-                 seed: int = 0, causal: bool = False, kv_cache: bool = False):
+                 seed: int = 0, causal: bool = False, kv_cache: bool = False, n_slots: int = 1):
         self.d_model, self.n_heads, self.d_ff, self.n_blocks, self.max_seq, self.max_enc_seq, self.seed = (
             d_model, n_heads, d_ff, n_blocks, max_seq, max_enc_seq, seed)
-        self.causal, self.kv_cache = bool(causal), bool(kv_cache)
-        self.filled = None   # mirrors the decoder's filled length: None before begin()
+        self.causal, self.kv_cache, self.n_slots = bool(causal), bool(kv_cache), int(n_slots)
         h = ctypes.c_void_p()
-        if causal or kv_cache:
+        if n_slots != 1:
+            # cache slots (qgemm_decoder_create_slots): n_slots sequences on one copy of the weights
+            assert causal and kv_cache, "n_slots belongs to causal=True, kv_cache=True"
+            _check("qgemm_decoder_create_slots",
+                   load().qgemm_decoder_create_slots(d_model, n_heads, d_ff, n_blocks, max_seq, max_enc_seq, seed,
+                                                     QGEMM_DECODER_CAUSAL | QGEMM_DECODER_KV_CACHE, n_slots,
+                                                     ctypes.byref(h)))
+        elif causal or kv_cache:
             flags = (QGEMM_DECODER_CAUSAL if causal else 0) | (QGEMM_DECODER_KV_CACHE if kv_cache else 0)
             _check("qgemm_decoder_create_ex",
                    load().qgemm_decoder_create_ex(d_model, n_heads, d_ff, n_blocks, max_seq, max_enc_seq, seed,
@@ -953,13 +1039,26 @@ class Decoder:
                                                                     _stream(X.device)))
         return Y
 
+    def slot_filled(self, slot: int):
+        """The filled length of a cache slot as the decoder keeps it (qgemm_decoder_slot_state): None before the
+        slot's begin (and on a decoder without caches)."""
+        enc_seq, filled = ctypes.c_int(), ctypes.c_int()
+        if not getattr(self, "_h", None) or load().qgemm_decoder_slot_state(self._h, slot, ctypes.byref(enc_seq),
+                                                                            ctypes.byref(filled)):
+            return None
+        return filled.value if enc_seq.value > 0 else None
+
+    @property
+    def filled(self):
+        """Slot 0's filled length -- the sequence begin() / step() drive: None before begin()."""
+        return self.slot_filled(0)
+
     def begin(self, enc_out):
         """Start a sequence (qgemm_decoder_begin): every block's [K2 | V2] of enc_out into its cross cache."""
         _require_device_f32(enc_out, "enc_out")
         assert enc_out.is_contiguous() and enc_out.shape[1] == self.d_model
         _check("qgemm_decoder_begin", load().qgemm_decoder_begin(self._h, enc_out.data_ptr(), enc_out.shape[0],
                                                                 _stream(enc_out.device)))
-        self.filled = 0
 
     def step(self, X_new, pos=None, Y=None):
         """The output rows of the input rows X_new (n x d_model) at positions pos .. pos + n - 1
@@ -968,15 +1067,61 @@ class Decoder:
         _require_device_f32(X_new, "X_new")
         assert X_new.is_contiguous() and X_new.shape[1] == self.d_model
         if pos is None:
-            assert self.filled is not None, "step() follows begin()"
             pos = self.filled
+            assert pos is not None, "step() follows begin()"
         Y = torch.empty_like(X_new) if Y is None else Y
         _require_device_f32(Y, "Y")
         assert Y.is_contiguous() and Y.shape == X_new.shape
         _check("qgemm_decoder_step", load().qgemm_decoder_step(self._h, X_new.data_ptr(), Y.data_ptr(), pos,
                                                               X_new.shape[0], _stream(X_new.device)))
-        self.filled = pos + X_new.shape[0]
         return Y
+
+    def begin_slot(self, slot: int, enc_out):
+        """begin() for one cache slot (qgemm_decoder_begin_slot); slot 0 is begin()'s."""
+        _require_device_f32(enc_out, "enc_out")
+        assert enc_out.is_contiguous() and enc_out.shape[1] == self.d_model
+        _check("qgemm_decoder_begin_slot", load().qgemm_decoder_begin_slot(self._h, slot, enc_out.data_ptr(),
+                                                                          enc_out.shape[0], _stream(enc_out.device)))
+
+    def step_slot(self, slot: int, X_new, pos=None, Y=None):
+        """step() for one cache slot (qgemm_decoder_step_slot); pos defaults to the slot's filled length."""
+        import torch
+        _require_device_f32(X_new, "X_new")
+        assert X_new.is_contiguous() and X_new.shape[1] == self.d_model
+        if pos is None:
+            pos = self.slot_filled(slot)
+            assert pos is not None, "step_slot() follows begin_slot()"
+        Y = torch.empty_like(X_new) if Y is None else Y
+        _require_device_f32(Y, "Y")
+        assert Y.is_contiguous() and Y.shape == X_new.shape
+        _check("qgemm_decoder_step_slot", load().qgemm_decoder_step_slot(self._h, slot, X_new.data_ptr(), Y.data_ptr(),
+                                                                        pos, X_new.shape[0], _stream(X_new.device)))
+        return Y
+
+    def step_batch(self, slots, X_new, pos=None, rows_per_seq: int = 1, Y=None):
+        """One step of len(slots) sequences (qgemm_decoder_step_batch): rows b * rows_per_seq .. of X_new are the new
+        rows of slot slots[b] at positions pos[b] .. (pos defaults to every slot's filled length); the rows of Y are,
+        bit for bit, what step_slot gives for each sequence alone."""
+        import torch
+        _require_device_f32(X_new, "X_new")
+        slots = [int(v) for v in slots]
+        n = len(slots)
+        assert X_new.is_contiguous() and X_new.shape == (n * rows_per_seq, self.d_model), \
+            "X_new: (len(slots) * rows_per_seq) x d_model, contiguous"
+        if pos is None:
+            pos = [self.slot_filled(v) for v in slots]
+            assert None not in pos, "step_batch() follows every slot's begin_slot()"
+        Y = torch.empty_like(X_new) if Y is None else Y
+        _require_device_f32(Y, "Y")
+        assert Y.is_contiguous() and Y.shape == X_new.shape
+        _check("qgemm_decoder_step_batch",
+               load().qgemm_decoder_step_batch(self._h, n, _int_array(slots, n, "slots"), _int_array(pos, n, "pos"),
+                                               rows_per_seq, X_new.data_ptr(), Y.data_ptr(), _stream(X_new.device)))
+        return Y
+
+    def copy_slot(self, dst: int, src: int):
+        """Fork a sequence (qgemm_decoder_copy_slot): slot dst continues slot src's sequence on its own."""
+        _check("qgemm_decoder_copy_slot", load().qgemm_decoder_copy_slot(self._h, dst, src, _stream()))
 
     def close(self):
         if getattr(self, "_h", None):

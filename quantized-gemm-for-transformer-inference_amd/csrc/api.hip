@@ -448,11 +448,58 @@ int qgemm_decoder_forward(void *decoder, const float *X, const float *enc_out, f
 }
 
 int qgemm_decoder_begin(void *decoder, const float *enc_out, int enc_seq, void *stream) {
-    return err(decoder_begin(static_cast<Stack *>(decoder), enc_out, enc_seq, static_cast<hipStream_t>(stream)));
+    return qgemm_decoder_begin_slot(decoder, 0, enc_out, enc_seq, stream);
 }
 
 int qgemm_decoder_step(void *decoder, const float *X, float *Y, int pos, int n, void *stream) {
-    return err(decoder_step(static_cast<Stack *>(decoder), X, Y, pos, n, static_cast<hipStream_t>(stream)));
+    return qgemm_decoder_step_slot(decoder, 0, X, Y, pos, n, stream);
+}
+
+int qgemm_attention_decode_batched(const float *Q, int64_t q_stride_h, const float *K, int64_t k_stride_h,
+                                   int64_t k_stride_seq, const float *V, int64_t v_stride_h, int64_t v_stride_seq,
+                                   float *O, int64_t o_stride_h, int n_seqs, int rows_per_seq, const int *kv_slot,
+                                   const int *seq_kv, const int *q_pos0, int n_heads, int d_k, float scale,
+                                   void *stream) {
+    static_assert(QGEMM_DECODE_MAX_BATCH == kDecodeMaxBatch, "the header's cap is the table's size");
+    return err(launch_attention_batched(Q, q_stride_h, K, k_stride_h, k_stride_seq, V, v_stride_h, v_stride_seq, O,
+                                        o_stride_h, n_seqs, rows_per_seq, kv_slot, seq_kv, q_pos0, n_heads, d_k, scale,
+                                        static_cast<hipStream_t>(stream)));
+}
+
+int qgemm_decoder_create_slots(int d_model, int n_heads, int d_ff, int n_blocks, int max_seq, int max_enc_seq,
+                               uint64_t seed, int flags, int n_slots, void **decoder) {
+    if (!decoder) return err(hipErrorInvalidValue);
+    *decoder = nullptr;
+    if (flags != (QGEMM_DECODER_CAUSAL | QGEMM_DECODER_KV_CACHE) || n_slots < 1 || n_slots > QGEMM_DECODE_MAX_BATCH)
+        return err(hipErrorInvalidValue);
+    Stack *D = nullptr;
+    hipError_t e = stack_create(d_model, n_heads, d_ff, n_blocks, max_seq, max_enc_seq, seed, /*cross=*/true, true, true,
+                                &D, n_slots);
+    *decoder = D;
+    return err(e);
+}
+
+int qgemm_decoder_begin_slot(void *decoder, int slot, const float *enc_out, int enc_seq, void *stream) {
+    return err(decoder_begin_slot(static_cast<Stack *>(decoder), slot, enc_out, enc_seq,
+                                  static_cast<hipStream_t>(stream)));
+}
+
+int qgemm_decoder_step_slot(void *decoder, int slot, const float *X, float *Y, int pos, int n, void *stream) {
+    return err(decoder_step_slot(static_cast<Stack *>(decoder), slot, X, Y, pos, n, static_cast<hipStream_t>(stream)));
+}
+
+int qgemm_decoder_step_batch(void *decoder, int n_seqs, const int *slots, const int *pos, int rows_per_seq,
+                             const float *X, float *Y, void *stream) {
+    return err(decoder_step_batch(static_cast<Stack *>(decoder), n_seqs, slots, pos, rows_per_seq, X, Y,
+                                  static_cast<hipStream_t>(stream)));
+}
+
+int qgemm_decoder_copy_slot(void *decoder, int dst_slot, int src_slot, void *stream) {
+    return err(decoder_copy_slot(static_cast<Stack *>(decoder), dst_slot, src_slot, static_cast<hipStream_t>(stream)));
+}
+
+int qgemm_decoder_slot_state(void *decoder, int slot, int *enc_seq, int *filled) {
+    return err(decoder_slot_state(static_cast<Stack *>(decoder), slot, enc_seq, filled));
 }
 
 int qgemm_decoder_destroy(void *decoder) {

@@ -23,6 +23,15 @@
 // LDS: the score row (16 KiB) + one K / V chunk (34 KiB) + the query row: 50.3 KiB, room for three workgroups per CU;
 // the two chunks held in registers (176 VGPRs) make it two.  A decoding step launches heads x rows <= 128 workgroups
 // for 256 CUs, so a workgroup's own latency, not the occupancy, sets the launch time.
+// The batched launch runs the same workgroup for up to 64 independent sequences (grid z = the
+// sequence): each sequence has its own K / V slab, key count and mask offset, read from a table in the kernel
+// arguments.  It is the SAME kernel template, instantiated with DecodeMany instead of DecodeOne: one text of the
+// arithmetic.  (The body as a __device__ function inlined into two kernels was tried first: the compiler then
+// transformed the chunk loops differently and the single-sequence launch measured 0.2 % slower at 4096 keys; as one
+// kernel template the single-sequence instantiation compiles to the instruction stream it had before, register
+// numbers aside.)
+#include <type_traits>
+
 #include "qgemm_internal.h"
 
 namespace qgemm {
@@ -37,16 +46,47 @@ constexpr int kDecChunk = 128;    // keys per staged K / V chunk
 constexpr int kDecStride = 68;    // chunk row stride (floats): a thread-per-key b128 read is conflict-free
 constexpr int kDecPer = kDecChunk * 16 / kDecThreads;  // float4 pieces of a chunk per thread
 
-template <bool kCausal>
+// The sequences of a launch, the kernel's last argument (by value).  DecodeOne: the single-sequence launch, grid
+// (heads, query rows).  DecodeMany: up to kDecodeMaxBatch independent sequences, grid (heads, rows per sequence,
+// sequences): sequence b's query / output rows are b * rows_per_seq .. of Q / O, its K / V rows the slab at
+// K / V + kv_slot[b] * k / v_stride_seq, with seq_kv[b] keys and mask offset q_pos0[b] (uniform per workgroup: scalar
+// loads from the kernel arguments, nothing in device memory).
+struct DecodeOne {
+    int seq_kv, q_pos0;
+};
+struct DecodeMany {
+    int64_t k_stride_seq, v_stride_seq;
+    int rows_per_seq;
+    DecodeBatchTable tab;
+};
+
+// ONE kernel text for both launches (the batched decode kernel of DESIGN.md s17 is
+// attention_decode_kernel<kCausal, DecodeMany>): the sequence's parameters are resolved at the top, everything below
+// is the work of one (head, query row) of one sequence.
+template <bool kCausal, typename Seqs>
 __global__ __launch_bounds__(kDecThreads) void attention_decode_kernel(
     const float *__restrict__ Q, int64_t ldq, const float *__restrict__ K, int64_t ldk, const float *__restrict__ V,
-    int64_t ldv, float *__restrict__ O, int64_t ldo, int dk, int seq_kv, float scale, int q_pos0) {
+    int64_t ldv, float *__restrict__ O, int64_t ldo, int dk, float scale, Seqs seqs) {
     __shared__ __attribute__((aligned(16))) float S[kDecMaxSeq];
     __shared__ __attribute__((aligned(16))) float KV[kDecChunk * kDecStride];
     __shared__ __attribute__((aligned(16))) float Qs[kDecMaxDk];
     __shared__ float red[kDecThreads / 64 + 1];
     // grid (heads, query rows): with a multiple of 8 heads the rows of a head share an XCD and its L2
     const int h = blockIdx.x, qi = blockIdx.y;
+    int seq_kv, q_pos0;
+    if constexpr (std::is_same<Seqs, DecodeMany>::value) {
+        const int b = blockIdx.z;
+        const int64_t row0 = (int64_t)b * seqs.rows_per_seq, slab = seqs.tab.kv_slot[b];
+        Q += row0 * ldq;
+        O += row0 * ldo;
+        K += slab * seqs.k_stride_seq;
+        V += slab * seqs.v_stride_seq;
+        seq_kv = seqs.tab.seq_kv[b];
+        q_pos0 = seqs.tab.q_pos0[b];
+    } else {
+        seq_kv = seqs.seq_kv;
+        q_pos0 = seqs.q_pos0;
+    }
     const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const float *Qb = Q + qi * ldq + (int64_t)h * dk, *Kb = K + (int64_t)h * dk, *Vb = V + (int64_t)h * dk;
     const int seq = seq_kv;
@@ -256,11 +296,35 @@ hipError_t launch_attention_decode(const float *Q, int64_t ldq, const float *K, 
     if (seq_q == 0) return hipSuccess;
     const dim3 grid((unsigned)n_heads, (unsigned)seq_q);
     if (q_pos0 == kNoMask)
-        attention_decode_kernel<false><<<grid, kDecThreads, 0, stream>>>(Q, ldq, K, ldk, V, ldv, O, ldo, dk, seq_kv,
-                                                                         scale, 0);
+        attention_decode_kernel<false, DecodeOne><<<grid, kDecThreads, 0, stream>>>(Q, ldq, K, ldk, V, ldv, O, ldo, dk,
+                                                                                    scale, DecodeOne{seq_kv, 0});
     else  // past seq_kv - 1 the mask hides nothing: clamped, so the kernel's row limit cannot overflow
-        attention_decode_kernel<true><<<grid, kDecThreads, 0, stream>>>(Q, ldq, K, ldk, V, ldv, O, ldo, dk, seq_kv,
-                                                                        scale, q_pos0 < seq_kv ? q_pos0 : seq_kv);
+        attention_decode_kernel<true, DecodeOne><<<grid, kDecThreads, 0, stream>>>(
+            Q, ldq, K, ldk, V, ldv, O, ldo, dk, scale, DecodeOne{seq_kv, q_pos0 < seq_kv ? q_pos0 : seq_kv});
+    return hipGetLastError();
+}
+
+// tab: checked and clamped by launch_attention_batched (attention_launch.hip); the envelope is tested again here,
+// where the kernel's LDS arrays and grid are sized
+hipError_t launch_attention_decode_batched(const float *Q, int64_t ldq, const float *K, int64_t ldk, int64_t k_stride_seq,
+                                           const float *V, int64_t ldv, int64_t v_stride_seq, float *O, int64_t ldo,
+                                           int n_seqs, int rows_per_seq, const DecodeBatchTable &tab, bool causal,
+                                           int n_heads, int dk, float scale, hipStream_t stream) {
+    if (n_seqs < 1 || n_seqs > kDecodeMaxBatch || rows_per_seq < 1 || rows_per_seq > kAttnDecodeMaxQ || dk < 1 ||
+        dk > kDecMaxDk || n_heads < 1)
+        return hipErrorInvalidValue;
+    for (int b = 0; b < n_seqs; ++b)
+        if (tab.seq_kv[b] < 1 || tab.seq_kv[b] > kDecMaxSeq || tab.kv_slot[b] < 0 || tab.q_pos0[b] < 0 ||
+            tab.q_pos0[b] > tab.seq_kv[b])
+            return hipErrorInvalidValue;
+    const dim3 grid((unsigned)n_heads, (unsigned)rows_per_seq, (unsigned)n_seqs);
+    const DecodeMany many{k_stride_seq, v_stride_seq, rows_per_seq, tab};
+    if (causal)
+        attention_decode_kernel<true, DecodeMany><<<grid, kDecThreads, 0, stream>>>(Q, ldq, K, ldk, V, ldv, O, ldo, dk,
+                                                                                    scale, many);
+    else
+        attention_decode_kernel<false, DecodeMany><<<grid, kDecThreads, 0, stream>>>(Q, ldq, K, ldk, V, ldv, O, ldo, dk,
+                                                                                     scale, many);
     return hipGetLastError();
 }
 

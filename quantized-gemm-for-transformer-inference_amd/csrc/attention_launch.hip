@@ -43,4 +43,30 @@ hipError_t launch_attention(const float *Q, int64_t ldq, const float *K, int64_t
                                  stream);
 }
 
+// The decode launch over a batch of sequences (attention_decode.hip, DecodeMany): the host arrays are read HERE, into
+// the table that travels in the kernel arguments -- nothing is copied to the device, allocated or synchronized, and a
+// captured graph replays the values of the capture.  kv_slot == nullptr: slab b for sequence b; q_pos0 == nullptr: no
+// mask.  Every check comes before the launch.
+hipError_t launch_attention_batched(const float *Q, int64_t ldq, const float *K, int64_t ldk, int64_t k_stride_seq,
+                                    const float *V, int64_t ldv, int64_t v_stride_seq, float *O, int64_t ldo, int n_seqs,
+                                    int rows_per_seq, const int *kv_slot, const int *seq_kv, const int *q_pos0,
+                                    int n_heads, int dk, float scale, hipStream_t stream) {
+    if (!Q || !K || !V || !O || !seq_kv || n_seqs < 0 || n_seqs > kDecodeMaxBatch || n_heads < 1 ||
+        !attention_decode_ok(rows_per_seq, 1, dk) || rows_per_seq < 1 || dk < 1)
+        return hipErrorInvalidValue;
+    DecodeBatchTable tab = {};  // entries past n_seqs are never read; zeroed so the arguments are defined bytes
+    for (int b = 0; b < n_seqs; ++b) {
+        if (seq_kv[b] < 1 || !attention_decode_ok(rows_per_seq, seq_kv[b], dk) || (q_pos0 && q_pos0[b] < 0) ||
+            (kv_slot && kv_slot[b] < 0))
+            return hipErrorInvalidValue;
+        tab.kv_slot[b] = kv_slot ? kv_slot[b] : b;
+        tab.seq_kv[b] = seq_kv[b];
+        // past seq_kv - 1 the mask hides nothing: clamped, so the kernel's row limit cannot overflow
+        tab.q_pos0[b] = q_pos0 ? (q_pos0[b] < seq_kv[b] ? q_pos0[b] : seq_kv[b]) : 0;
+    }
+    if (n_seqs == 0) return hipSuccess;
+    return launch_attention_decode_batched(Q, ldq, K, ldk, k_stride_seq, V, ldv, v_stride_seq, O, ldo, n_seqs,
+                                           rows_per_seq, tab, q_pos0 != nullptr, n_heads, dk, scale, stream);
+}
+
 }  // namespace qgemm

@@ -265,7 +265,27 @@ bool attention_decode_ok(int seq_q, int seq_kv, int dk);
 hipError_t launch_attention_decode(const float *Q, int64_t ldq, const float *K, int64_t ldk, const float *V, int64_t ldv,
                                    float *O, int64_t ldo, int seq_q, int seq_kv, int n_heads, int dk, float scale,
                                    int q_pos0, hipStream_t stream);
+// The decode launch for a batch of independent sequences (attention_decode_kernel<., DecodeMany>): grid
+// (heads, rows per sequence, sequences); sequence b's query / output rows are b * rows_per_seq .., its K / V rows the
+// slab at K / V + kv_slot[b] * k / v_stride_seq, seq_kv[b] keys, mask offset q_pos0[b].  The table is a kernel argument
+// passed by value (768 bytes): filled on the host at enqueue time, never in device memory.
+constexpr int kDecodeMaxBatch = 64;
+struct DecodeBatchTable {
+    int kv_slot[kDecodeMaxBatch], seq_kv[kDecodeMaxBatch], q_pos0[kDecodeMaxBatch];
+};
+// tab already checked and clamped (q_pos0[b] <= seq_kv[b]); causal = false ignores q_pos0
+hipError_t launch_attention_decode_batched(const float *Q, int64_t ldq, const float *K, int64_t ldk, int64_t k_stride_seq,
+                                           const float *V, int64_t ldv, int64_t v_stride_seq, float *O, int64_t ldo,
+                                           int n_seqs, int rows_per_seq, const DecodeBatchTable &tab, bool causal,
+                                           int n_heads, int dk, float scale, hipStream_t stream);
 // Attention dispatch (attention_launch.hip).
+// the batched decode launch from host arrays of n_seqs entries (kv_slot nullptr: 0, 1, 2, ..; q_pos0 nullptr: no mask):
+// hipErrorInvalidValue before any launch outside n_seqs <= 64, 1 <= rows_per_seq <= 8, 1 <= d_k <= 64,
+// 1 <= seq_kv[b] <= 4096, q_pos0[b] >= 0, kv_slot[b] >= 0; n_seqs == 0 launches nothing
+hipError_t launch_attention_batched(const float *Q, int64_t ldq, const float *K, int64_t ldk, int64_t k_stride_seq,
+                                    const float *V, int64_t ldv, int64_t v_stride_seq, float *O, int64_t ldo, int n_seqs,
+                                    int rows_per_seq, const int *kv_slot, const int *seq_kv, const int *q_pos0,
+                                    int n_heads, int dk, float scale, hipStream_t stream);
 // the kernel launch_attention takes for a shape (qgemm_attention_plan): a static string
 const char *attention_plan_name(int seq_q, int seq_kv, int dk);
 // whether a call of at most max_q query rows and max_kv keys can reach the three launches, and so needs `scores`
@@ -313,13 +333,20 @@ hipError_t outlier_linear_finish(const float *X, int64_t xsh, int m, int n, int 
 struct Stack;
 uint64_t encoder_weight_seed(uint64_t base, int block, int kind, int head);
 float encoder_init_bound(int n);
-// max_enc_seq, causal and kv_cache count only with cross
+// max_enc_seq, causal and kv_cache count only with cross; n_slots (1 .. kDecodeMaxBatch, > 1 only with kv_cache) is
+// the number of sequences the caches hold
 hipError_t stack_create(int d_model, int n_heads, int d_ff, int n_blocks, int max_seq, int max_enc_seq, uint64_t seed,
-                        bool cross, bool causal, bool kv_cache, Stack **out);
+                        bool cross, bool causal, bool kv_cache, Stack **out, int n_slots = 1);
 void stack_destroy(Stack *S);
 hipError_t encoder_forward(Stack *S, const float *X, float *Y, int seq, hipStream_t s);
-hipError_t decoder_begin(Stack *S, const float *enc_out, int enc_seq, hipStream_t s);
-hipError_t decoder_step(Stack *S, const float *X, float *Y, int pos, int n, hipStream_t s);
+// begin / step of one cache slot (qgemm_decoder_begin / qgemm_decoder_step are slot 0's)
+hipError_t decoder_begin_slot(Stack *S, int slot, const float *enc_out, int enc_seq, hipStream_t s);
+hipError_t decoder_step_slot(Stack *S, int slot, const float *X, float *Y, int pos, int n, hipStream_t s);
+// one step of n_seqs sequences, rows_per_seq rows each: rows b * r .. of X / Y at positions pos[b] .. of slot slots[b]
+hipError_t decoder_step_batch(Stack *S, int n_seqs, const int *slots, const int *pos, int rows_per_seq, const float *X,
+                              float *Y, hipStream_t s);
+hipError_t decoder_copy_slot(Stack *S, int dst, int src, hipStream_t s);
+hipError_t decoder_slot_state(const Stack *S, int slot, int *enc_seq, int *filled);
 hipError_t decoder_forward(Stack *S, const float *X, const float *enc_out, float *Y, int seq, int enc_seq,
                            hipStream_t s);
 // draws a k x n fp32 weight into tmp (col_seeds[c] fills columns [c*cols_per_seed, (c+1)*cols_per_seed), one

@@ -50,6 +50,23 @@
 // then filled = pos + n (an earlier pos rewinds: speculative decoding, beam search).  begin and step allocate nothing
 // and do not synchronize; they share the stack's scratch buffers with forward, so a stack does one thing at a time.
 // forward on a cached decoder neither reads nor writes the caches.
+//
+// Cache slots and batched steps (qgemm_decoder_create_slots).  The caches hold n_slots sequences: every
+// block's self cache is n_slots slabs of max_seq x 3 d_model, its cross cache n_slots slabs of max_enc_seq x 2 d_model,
+// and enc_seq / filled are kept per slot; the weights exist once.  decoder_begin_slot / decoder_step_slot are begin /
+// step with the cache pointers offset to the slot's slabs (slot 0: the calls above, unchanged).
+//   decoder_step_batch  one step of n_seqs different slots, r = 1 .. 8 rows each, M = n_seqs * r rows through the
+//                       same chain: the QKV GEMM of all rows into the stack's qkv scratch, scatter_kv_kernel copies
+//                       each row's [K | V] into row pos[b] + i of its slot's slab, the batched decode launch
+//                       (attention_decode.hip) reads Q from the scratch and K / V from the slabs with seq_kv[b] =
+//                       pos[b] + r and q_pos0[b] = pos[b]; W_O, add + layernorm, Wq2; the batched launch again,
+//                       unmasked, on the cross slabs with seq_kv[b] = the slot's enc_seq; W_O2, the FFN.
+// Row b * r + i of its output is, bit for bit, row i of decoder_step_slot(slots[b], pos[b], r) alone: by argument (1)
+// every step but the attention gives a row the same bits whatever other rows share the launch (M = n_seqs * r or
+// M = r), and the batched attention launch runs, per (head, row, sequence), the single launch's workgroup on the same
+// operands -- the K / V rows of the slab are the same values whether a GEMM or the scatter stored them.
+// The scratch buffers, the packed activations and the split-K scratch hold max(max_seq, 8 * n_slots) rows with more
+// than one slot.  decoder_copy_slot forks a sequence with stream-ordered device-to-device copies of the rows in use.
 #include <cmath>
 #include <new>
 #include <vector>
@@ -78,7 +95,8 @@ struct Block {
     void *wqkv = nullptr, *wo = nullptr, *w1 = nullptr, *w2 = nullptr;  // packed (W^T int8 + Cw)
     void *wq2 = nullptr, *wkv2 = nullptr, *wo2 = nullptr;               // cross
     float *b1 = nullptr, *b2 = nullptr;
-    float *qkv_cache = nullptr, *kv2_cache = nullptr;  // kv_cache: max_seq x 3d and max_enc_seq x 2d
+    // kv_cache: n_slots slabs of max_seq x 3d ([Q | K | V] rows) and n_slots slabs of max_enc_seq x 2d ([K2 | V2])
+    float *qkv_cache = nullptr, *kv2_cache = nullptr;
 };
 
 struct Stack {
@@ -86,8 +104,11 @@ struct Stack {
     bool cross = false;     // the blocks have the cross-attention third: a decoder
     bool causal = false;    // the self-attention masks keys past the query's own row (QGEMM_DECODER_CAUSAL)
     bool kv_cache = false;  // the blocks own caches for decoder_begin / decoder_step (QGEMM_DECODER_KV_CACHE)
-    int enc_seq = 0;        // of the sequence begun (0: no decoder_begin yet)
-    int filled = 0;         // cache rows 0 .. filled - 1 hold the sequence so far (host side, at enqueue time)
+    int n_slots = 1;        // sequences the caches hold side by side (qgemm_decoder_create_slots)
+    int scratch_rows = 0;   // rows the scratch buffers hold: max_seq, or 8 rows of every slot if that is more
+    // per slot, host side, updated at enqueue time: enc_seq of the sequence begun (0: no begin yet) and the filled
+    // length (cache rows 0 .. filled - 1 hold the sequence so far)
+    std::vector<int> enc_seq, filled;
     std::vector<Block> blocks;
     float *qkv = nullptr, *scores = nullptr, *heads = nullptr, *t = nullptr, *ffn = nullptr, *x = nullptr;
     float *xa = nullptr, *xb = nullptr;
@@ -167,9 +188,10 @@ void stack_destroy(Stack *S) {
 }
 
 hipError_t stack_create(int d_model, int n_heads, int d_ff, int n_blocks, int max_seq, int max_enc_seq, uint64_t seed,
-                        bool cross, bool causal, bool kv_cache, Stack **out) {
+                        bool cross, bool causal, bool kv_cache, Stack **out, int n_slots) {
     *out = nullptr;
     if (kv_cache && !causal) return hipErrorInvalidValue;
+    if (n_slots < 1 || n_slots > kDecodeMaxBatch || (n_slots > 1 && !(cross && kv_cache))) return hipErrorInvalidValue;
     if (d_model < 2 || n_heads < 1 || d_model % n_heads || d_ff < 2 || n_blocks < 1 || max_seq < 1 || max_seq > 4096 ||
         (cross && (max_enc_seq < 1 || max_enc_seq > 4096)) || d_model > 4096)
         return hipErrorInvalidValue;
@@ -184,9 +206,15 @@ hipError_t stack_create(int d_model, int n_heads, int d_ff, int n_blocks, int ma
     S->cross = cross;
     S->causal = causal;
     S->kv_cache = kv_cache;
+    S->n_slots = n_slots;
+    // a batched step runs up to 8 rows of every slot through the scratch buffers (one slot: a step's rows fit max_seq)
+    S->scratch_rows = n_slots > 1 ? std::max(max_seq, 8 * n_slots) : max_seq;
+    S->enc_seq.assign(n_slots, 0);
+    S->filled.assign(n_slots, 0);
     S->blocks.resize(n_blocks);
     const int d = d_model, dk = d_model / n_heads;
-    const size_t Sq = (size_t)max_seq, Se = (size_t)S->max_enc_seq;
+    const int rows = S->scratch_rows;
+    const size_t Sq = (size_t)rows, Se = (size_t)S->max_enc_seq;
     hipError_t e = hipSuccess;
     auto fail = [&](hipError_t err) {
         stack_destroy(S);
@@ -195,7 +223,8 @@ hipError_t stack_create(int d_model, int n_heads, int d_ff, int n_blocks, int ma
     // scores only where some forward or step can reach the three launches (both attentions share them); else they
     // stay nullptr, which launch_attention refuses on that path
     const int max_kv = std::max(max_seq, S->max_enc_seq);
-    if (attention_needs_scores(max_seq, max_kv, dk) && (e = alloc_f(&S->scores, (size_t)n_heads * Sq * (size_t)max_kv)))
+    if (attention_needs_scores(max_seq, max_kv, dk) &&
+        (e = alloc_f(&S->scores, (size_t)n_heads * (size_t)max_seq * (size_t)max_kv)))
         return fail(e);
     if ((e = alloc_f(&S->qkv, Sq * 3 * d)) || (e = alloc_f(&S->heads, Sq * d)) ||
         (e = alloc_f(&S->t, Sq * d)) || (e = alloc_f(&S->ffn, Sq * d_ff)) || (e = alloc_f(&S->x, Sq * d)) ||
@@ -204,12 +233,12 @@ hipError_t stack_create(int d_model, int n_heads, int d_ff, int n_blocks, int ma
     if (cross && ((e = alloc_f(&S->q2, Sq * d)) || (e = alloc_f(&S->kv2, Se * 2 * d)) || (e = alloc_f(&S->heads2, Sq * d))))
         return fail(e);
     // workspace: split-K scratch for the largest of the linear shapes + the packed activations (+ the packed enc_out)
-    const int shapes[5][3] = {{max_seq, 3 * d, d}, {max_seq, d, d}, {max_seq, d_ff, d}, {max_seq, d, d_ff},
+    const int shapes[5][3] = {{rows, 3 * d, d}, {rows, d, d}, {rows, d_ff, d}, {rows, d, d_ff},
                               {S->max_enc_seq, 2 * d, d}};  // (m, n, k); the last one exists only with cross
     size_t scratch = 0;
     for (int i = 0; i < (cross ? 5 : 4); ++i)
         scratch = std::max(scratch, gemm_scratch_bytes(shapes[i][0], shapes[i][1], shapes[i][2]));
-    const size_t act = std::max(packed_bytes(max_seq, d), packed_bytes(max_seq, d_ff));
+    const size_t act = std::max(packed_bytes(rows, d), packed_bytes(rows, d_ff));
     S->scratch_bytes = (scratch + 255) & ~(size_t)255;
     S->act_bytes = (act + 255) & ~(size_t)255;
     const size_t ws_bytes = S->scratch_bytes + S->act_bytes + (cross ? packed_bytes(max_enc_seq, d) : 0);
@@ -241,7 +270,9 @@ hipError_t stack_create(int d_model, int n_heads, int d_ff, int n_blocks, int ma
         if ((e = encoder_make_packed(d, d_ff, {encoder_weight_seed(seed, i, kW1, 0)}, d_ff, bd, &B.w1, tmp, s))) break;
         if ((e = encoder_make_packed(d_ff, d, {encoder_weight_seed(seed, i, kW2, 0)}, d, bf, &B.w2, tmp, s))) break;
         if ((e = alloc_f(&B.b1, d_ff)) || (e = alloc_f(&B.b2, d))) break;
-        if (kv_cache && ((e = alloc_f(&B.qkv_cache, Sq * 3 * d)) || (e = alloc_f(&B.kv2_cache, Se * 2 * d)))) break;
+        if (kv_cache && ((e = alloc_f(&B.qkv_cache, (size_t)n_slots * max_seq * 3 * d)) ||
+                         (e = alloc_f(&B.kv2_cache, (size_t)n_slots * Se * 2 * d))))
+            break;
         if ((e = launch_fill_uniform(B.b1, d_ff, encoder_weight_seed(seed, i, kB1, 0), -bd, bd, s))) break;
         if ((e = launch_fill_uniform(B.b2, d, encoder_weight_seed(seed, i, kB2, 0), -bf, bf, s))) break;
     }
@@ -254,13 +285,52 @@ hipError_t stack_create(int d_model, int n_heads, int d_ff, int n_blocks, int ma
 
 namespace {
 
+// The new [K | V] of a batched step into the caches: block (i, b) copies columns d .. 3d - 1 of row b * r + i of the
+// step's [Q | K | V] scratch into row pos[b] + i of slab slot[b] (tab.q_pos0 = pos, tab.kv_slot = slot), as float4
+// where d % 4 == 0 (then every row and third of both buffers is 16-byte aligned), else float by float.  The Q third of
+// those cache rows is not written.
+__global__ __launch_bounds__(256) void scatter_kv_kernel(const float *__restrict__ qkv, float *__restrict__ cache,
+                                                         int64_t slab_rows, int d, DecodeBatchTable tab) {
+    const int i = blockIdx.x, b = blockIdx.y;
+    const float *src = qkv + ((int64_t)b * gridDim.x + i) * 3 * d + d;
+    float *dst = cache + ((int64_t)tab.kv_slot[b] * slab_rows + tab.q_pos0[b] + i) * 3 * d + d;
+    if ((d & 3) == 0) {
+        for (int c = threadIdx.x; c < d / 2; c += blockDim.x)
+            reinterpret_cast<float4 *>(dst)[c] = reinterpret_cast<const float4 *>(src)[c];
+    } else {
+        for (int c = threadIdx.x; c < 2 * d; c += blockDim.x) dst[c] = src[c];
+    }
+}
+
+// slab_rows: rows of one slab of `cache`; the destination rows are checked to lie inside their slabs
+hipError_t launch_scatter_kv(const float *qkv, float *cache, int64_t slab_rows, int d, int n_seqs, int rows_per_seq,
+                             const DecodeBatchTable &tab, hipStream_t s) {
+    if (!qkv || !cache || d < 1 || n_seqs < 1 || n_seqs > kDecodeMaxBatch || rows_per_seq < 1) return hipErrorInvalidValue;
+    for (int b = 0; b < n_seqs; ++b)  // every destination row inside its slab
+        if (tab.kv_slot[b] < 0 || tab.q_pos0[b] < 0 || tab.q_pos0[b] > slab_rows - rows_per_seq)
+            return hipErrorInvalidValue;
+    scatter_kv_kernel<<<dim3((unsigned)rows_per_seq, (unsigned)n_seqs), 256, 0, s>>>(qkv, cache, slab_rows, d, tab);
+    return hipGetLastError();
+}
+
+// A batched step's sequences (decoder_step_batch): the tables of its two attention launches
+struct BatchStep {
+    int n_seqs, rows_per_seq;
+    DecodeBatchTable self;   // kv_slot = the slot, seq_kv = pos + rows_per_seq, q_pos0 = pos
+    DecodeBatchTable cross;  // kv_slot = the slot, seq_kv = the slot's enc_seq, no mask
+};
+
 // One pass over the blocks on `rows` rows, for forward (cached = false: the rows are the whole sequence, [Q | K | V]
-// and [K2 | V2] live in the stack's scratch buffers, [K2 | V2] is projected here from the packed enc_out) and for a
-// step (cached = true: the rows sit at positions pos .., [Q | K | V] rows pos .. are written into the block's cache
-// and attend to cache rows 0 .. pos + rows - 1, [K2 | V2] is the block's cross cache).
-hipError_t run_blocks(Stack *S, const float *X, float *Y, int rows, int enc_seq, bool cached, int pos, hipStream_t s) {
+// and [K2 | V2] live in the stack's scratch buffers, [K2 | V2] is projected here from the packed enc_out), for a
+// step of one slot (cached = true: the rows sit at positions pos .., [Q | K | V] rows pos .. are written into the
+// block's cache slab `slot` and attend to its rows 0 .. pos + rows - 1, [K2 | V2] is the slot's cross cache) and for
+// a step of many (batch != nullptr, with cached: rows = n_seqs * rows_per_seq, [Q | K | V] of all rows into the
+// scratch, their [K | V] scattered into the slots' slabs, both attentions one batched launch over the slabs).
+hipError_t run_blocks(Stack *S, const float *X, float *Y, int rows, int enc_seq, bool cached, int slot, int pos,
+                      const BatchStep *batch, hipStream_t s) {
     const int d = S->d_model, H = S->n_heads, dk = d / H;
     const int seq = rows;
+    const int64_t self_slab = (int64_t)S->max_seq * 3 * d, cross_slab = (int64_t)S->max_enc_seq * 2 * d;  // floats
     const float scale = (float)(1.0 / std::sqrt((double)dk));  // attention.cuh:64
     const float *in = X;
     bool in_packed = false;  // the previous block's last add+layernorm packed its output already
@@ -271,14 +341,25 @@ hipError_t run_blocks(Stack *S, const float *X, float *Y, int rows, int enc_seq,
         const bool last = i == S->n_blocks - 1;
         float *out = last ? Y : (i % 2 ? S->xb : S->xa);
         // ---- self-attention on the block input: [Q | K | V] = in @ [Wq | Wk | Wv] over all heads
-        float *qkv = cached ? B.qkv_cache : S->qkv;               // row 0 of [Q | K | V]
-        float *qrows = qkv + (size_t)(cached ? pos : 0) * 3 * d;  // the rows this call projects
+        const bool to_cache = cached && !batch;                                 // the GEMM writes the cache rows itself
+        float *qkv = to_cache ? B.qkv_cache + slot * self_slab : S->qkv;        // row 0 of [Q | K | V]
+        float *qrows = qkv + (size_t)(to_cache ? pos : 0) * 3 * d;              // the rows this call projects
         if ((e = linear(*S, in_packed ? nullptr : in, seq, d, B.wqkv, 3 * d, qrows, nullptr, false, s))) return e;
         // S_h = Q_h K_h^T, P_h = softmax(S_h * 1/sqrt(d_k)), heads[:, h*d_v..] = P_h V_h, Q, K and V the thirds of qkv
         // (causal: row i sees rows 0 .. i, so row i of the forward depends on rows 0 .. i of X alone)
-        if ((e = launch_attention(qrows, 3 * d, qkv + d, 3 * d, qkv + 2 * d, 3 * d, S->heads, d, seq,
-                                  cached ? pos + seq : seq, H, dk, scale, cached ? pos : (S->causal ? 0 : kNoMask),
-                                  S->scores, s)))
+        if (batch) {
+            // sequence b's rows see its slot's cache rows 0 .. pos[b] + r - 1, the last r of them scattered here
+            if ((e = launch_scatter_kv(qkv, B.qkv_cache, S->max_seq, d, batch->n_seqs, batch->rows_per_seq, batch->self,
+                                       s)))
+                return e;
+            if ((e = launch_attention_decode_batched(qkv, 3 * d, B.qkv_cache + d, 3 * d, self_slab,
+                                                     B.qkv_cache + 2 * d, 3 * d, self_slab, S->heads, d, batch->n_seqs,
+                                                     batch->rows_per_seq, batch->self, /*causal=*/true, H, dk, scale,
+                                                     s)))
+                return e;
+        } else if ((e = launch_attention(qrows, 3 * d, qkv + d, 3 * d, qkv + 2 * d, 3 * d, S->heads, d, seq,
+                                         cached ? pos + seq : seq, H, dk, scale,
+                                         cached ? pos : (S->causal ? 0 : kNoMask), S->scores, s)))
             return e;
         // output = multiHeadOut @ W_O; x1 = LN(output + multiHeadOut), packed by the same launch: the next linear
         // quantizes nothing itself
@@ -288,11 +369,16 @@ hipError_t run_blocks(Stack *S, const float *X, float *Y, int rows, int enc_seq,
         if (S->cross) {
             // ---- cross-attention: queries from x1, keys and values from enc_out
             if ((e = linear(*S, nullptr, seq, d, B.wq2, d, S->q2, nullptr, false, s))) return e;
-            float *kv2 = cached ? B.kv2_cache : S->kv2;
+            float *kv2 = cached ? B.kv2_cache + slot * cross_slab : S->kv2;
             if (!cached && (e = gemm(*S, enc_view(*S, enc_seq), enc_seq, d, B.wkv2, 2 * d, kv2, nullptr, false, s)))
                 return e;
-            if ((e = launch_attention(S->q2, d, kv2, 2 * d, kv2 + d, 2 * d, mho, d, seq, enc_seq, H, dk, scale, kNoMask,
-                                      S->scores, s)))
+            if (batch) {
+                if ((e = launch_attention_decode_batched(S->q2, d, B.kv2_cache, 2 * d, cross_slab, B.kv2_cache + d, 2 * d,
+                                                         cross_slab, mho, d, batch->n_seqs, batch->rows_per_seq,
+                                                         batch->cross, /*causal=*/false, H, dk, scale, s)))
+                    return e;
+            } else if ((e = launch_attention(S->q2, d, kv2, 2 * d, kv2 + d, 2 * d, mho, d, seq, enc_seq, H, dk, scale,
+                                             kNoMask, S->scores, s)))
                 return e;
             if ((e = linear(*S, mho, seq, d, B.wo2, d, S->t, nullptr, false, s))) return e;
             // x2 = LN(t + heads2), packed for the FFN's first linear
@@ -320,7 +406,7 @@ hipError_t pack_enc(Stack *S, const float *enc_out, int enc_seq, hipStream_t s) 
 
 hipError_t encoder_forward(Stack *S, const float *X, float *Y, int seq, hipStream_t s) {
     if (!S || S->cross || !X || !Y || seq < 1 || seq > S->max_seq) return hipErrorInvalidValue;
-    return run_blocks(S, X, Y, seq, 0, /*cached=*/false, 0, s);
+    return run_blocks(S, X, Y, seq, 0, /*cached=*/false, 0, 0, nullptr, s);
 }
 
 hipError_t decoder_forward(Stack *S, const float *X, const float *enc_out, float *Y, int seq, int enc_seq,
@@ -330,29 +416,91 @@ hipError_t decoder_forward(Stack *S, const float *X, const float *enc_out, float
         return hipErrorInvalidValue;
     const hipError_t e = pack_enc(S, enc_out, enc_seq, s);
     if (e) return e;
-    return run_blocks(S, X, Y, seq, enc_seq, /*cached=*/false, 0, s);
+    return run_blocks(S, X, Y, seq, enc_seq, /*cached=*/false, 0, 0, nullptr, s);
 }
 
-hipError_t decoder_begin(Stack *S, const float *enc_out, int enc_seq, hipStream_t s) {
-    if (!S || !S->cross || !S->kv_cache || !enc_out || enc_seq < 1 || enc_seq > S->max_enc_seq)
+hipError_t decoder_begin_slot(Stack *S, int slot, const float *enc_out, int enc_seq, hipStream_t s) {
+    if (!S || !S->cross || !S->kv_cache || slot < 0 || slot >= S->n_slots || !enc_out || enc_seq < 1 ||
+        enc_seq > S->max_enc_seq)
         return hipErrorInvalidValue;
     const int d = S->d_model;
     hipError_t e = pack_enc(S, enc_out, enc_seq, s);
     if (e) return e;
     for (const Block &B : S->blocks)
-        if ((e = gemm(*S, enc_view(*S, enc_seq), enc_seq, d, B.wkv2, 2 * d, B.kv2_cache, nullptr, false, s))) return e;
-    S->enc_seq = enc_seq;
-    S->filled = 0;
+        if ((e = gemm(*S, enc_view(*S, enc_seq), enc_seq, d, B.wkv2, 2 * d,
+                      B.kv2_cache + (int64_t)slot * S->max_enc_seq * 2 * d, nullptr, false, s)))
+            return e;
+    S->enc_seq[slot] = enc_seq;
+    S->filled[slot] = 0;
     return hipSuccess;
 }
 
-hipError_t decoder_step(Stack *S, const float *X, float *Y, int pos, int n, hipStream_t s) {
-    if (!S || !S->cross || !S->kv_cache || S->enc_seq < 1 || !X || !Y || n < 1 || pos < 0 || pos > S->filled ||
-        n > S->max_seq - pos)
+hipError_t decoder_step_slot(Stack *S, int slot, const float *X, float *Y, int pos, int n, hipStream_t s) {
+    if (!S || !S->cross || !S->kv_cache || slot < 0 || slot >= S->n_slots || S->enc_seq[slot] < 1 || !X || !Y || n < 1 ||
+        pos < 0 || pos > S->filled[slot] || n > S->max_seq - pos)
         return hipErrorInvalidValue;
-    const hipError_t e = run_blocks(S, X, Y, n, S->enc_seq, /*cached=*/true, pos, s);
+    const hipError_t e = run_blocks(S, X, Y, n, S->enc_seq[slot], /*cached=*/true, slot, pos, nullptr, s);
     if (e) return e;
-    S->filled = pos + n;
+    S->filled[slot] = pos + n;
+    return hipSuccess;
+}
+
+hipError_t decoder_step_batch(Stack *S, int n_seqs, const int *slots, const int *pos, int rows_per_seq, const float *X,
+                              float *Y, hipStream_t s) {
+    if (!S || !S->cross || !S->kv_cache || !slots || !pos || !X || !Y || n_seqs < 1 || n_seqs > S->n_slots ||
+        rows_per_seq < 1 || rows_per_seq > 8)
+        return hipErrorInvalidValue;
+    const int r = rows_per_seq;
+    if (!attention_decode_ok(r, 1, S->d_model / S->n_heads)) return hipErrorInvalidValue;  // d_k > 64: no batched launch
+    BatchStep bs = {};
+    bs.n_seqs = n_seqs;
+    bs.rows_per_seq = r;
+    uint64_t seen = 0;  // n_slots <= 64
+    for (int b = 0; b < n_seqs; ++b) {
+        const int sl = slots[b];
+        if (sl < 0 || sl >= S->n_slots || S->enc_seq[sl] < 1 || (seen >> sl & 1) || pos[b] < 0 ||
+            pos[b] > S->filled[sl] || r > S->max_seq - pos[b])
+            return hipErrorInvalidValue;
+        seen |= (uint64_t)1 << sl;
+        bs.self.kv_slot[b] = bs.cross.kv_slot[b] = sl;
+        bs.self.seq_kv[b] = pos[b] + r;
+        bs.self.q_pos0[b] = pos[b];
+        bs.cross.seq_kv[b] = S->enc_seq[sl];
+    }
+    // (n_seqs * r <= scratch_rows: n_seqs <= n_slots, and r <= max_seq with one slot)
+    const hipError_t e = run_blocks(S, X, Y, n_seqs * r, 0, /*cached=*/true, 0, 0, &bs, s);
+    if (e) return e;
+    for (int b = 0; b < n_seqs; ++b) S->filled[slots[b]] = pos[b] + r;
+    return hipSuccess;
+}
+
+// rows 0 .. filled - 1 of every block's self cache and rows 0 .. enc_seq - 1 of its cross cache, device to device in
+// stream order: dst then continues src's sequence on its own (beam search)
+hipError_t decoder_copy_slot(Stack *S, int dst, int src, hipStream_t s) {
+    if (!S || !S->cross || !S->kv_cache || dst < 0 || dst >= S->n_slots || src < 0 || src >= S->n_slots || dst == src ||
+        S->enc_seq[src] < 1)
+        return hipErrorInvalidValue;
+    const int64_t d = S->d_model, self_slab = S->max_seq * 3 * d, cross_slab = S->max_enc_seq * 2 * d;
+    const size_t self_bytes = sizeof(float) * (size_t)S->filled[src] * 3 * d;
+    const size_t cross_bytes = sizeof(float) * (size_t)S->enc_seq[src] * 2 * d;
+    hipError_t e;
+    for (const Block &B : S->blocks) {
+        if (self_bytes && (e = hipMemcpyAsync(B.qkv_cache + dst * self_slab, B.qkv_cache + src * self_slab, self_bytes,
+                                              hipMemcpyDeviceToDevice, s)))
+            return e;
+        if ((e = hipMemcpyAsync(B.kv2_cache + dst * cross_slab, B.kv2_cache + src * cross_slab, cross_bytes,
+                                hipMemcpyDeviceToDevice, s)))
+            return e;
+    }
+    S->enc_seq[dst] = S->enc_seq[src];
+    S->filled[dst] = S->filled[src];
+    return hipSuccess;
+}
+
+hipError_t decoder_slot_state(const Stack *S, int slot, int *enc_seq, int *filled) {
+    if (!S || !S->cross || !S->kv_cache || slot < 0 || slot >= S->n_slots) return hipErrorInvalidValue;
+    if (enc_seq) *enc_seq = S->enc_seq[slot];
+    if (filled) *filled = S->filled[slot];
     return hipSuccess;
 }
 
