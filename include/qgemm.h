@@ -112,10 +112,36 @@ QGEMM_API int qgemm_mm_packed_i32(const void *packed_a, const void *packed_b, in
                         void *stream);
 
 /* The reference's UNQUANTIZED op_mm<float,float> (op_mm.cuh:49-65), bit-exact: sequential-k fmaf from +0.
- * Used for the reference's error metric (timing_quantize.cu:67-70) and its unquantized timing line. */
+ * Used for the reference's error metric (timing_quantize.cu:67-70) and its unquantized timing line.
+ * Strides are in floats; row-major, column-major and transposed views of A, B and C all work.  The stride
+ * envelope: the kernels reach an element of a block's tile (at most 128 x 128 outputs, 32 k) by a 32-bit byte
+ * offset, so
+ *   - the stride of every dimension longer than one element is >= 0, and
+ *   - (R - 1) * stride_h + (W - 1) * stride_w < 2^29 - 1 floats (2^31 bytes) for the tile's extent R x W of each
+ *     matrix: A min(m, TM) x min(k, 32), B min(k, 32) x min(n, TN), C min(m, TM) x min(n, TN), with TM x TN the
+ *     tile of the kernel the call takes (qgemm_mm_fp32_plan names it: 128x128, 64x64, 32x64 or 16x32).
+ * How many rows or k steps the matrices have beyond one tile does not matter: tiles start at 64-bit addresses.
+ * hipErrorInvalidValue before any launch: a null pointer, m < 0, n < 0, k < 1, or strides outside that envelope
+ * (C is then untouched; never zeros in place of products).  m == 0 or n == 0 returns 0. */
 QGEMM_API int qgemm_mm_fp32(const float *A, int64_t a_stride_h, int64_t a_stride_w,
                   const float *B, int64_t b_stride_h, int64_t b_stride_w,
                   float *C, int64_t c_stride_h, int64_t c_stride_w, int m, int n, int k, void *stream);
+/* Diagnostics: the kernel qgemm_mm_fp32 takes for a call, and each of the two batched GEMMs of qgemm_attention's
+ * three launches (batch = heads; batch strides in floats).  It takes all the selection reads: the dimensions, the
+ * batch, the strides of A and B and their batch strides, and A and B themselves for their 16-byte alignment only --
+ * they are never dereferenced, and any integer with the same low four bits serves.  Returns 0 and, when kernel is
+ * non-NULL, a static string in *kernel, one of
+ *   mm_f32_dma_128x128_bkc  mm_f32_dma_64x64_bkc  mm_f32_dma_32x64_bkc    LDS-DMA ring, B k-contiguous (a B^T view)
+ *   mm_f32_dma_128x128_bnc  mm_f32_dma_64x64_bnc  mm_f32_dma_32x64_bnc    LDS-DMA ring, B n-contiguous (row-major)
+ *   mm_f32_mfma_128x128     mm_f32_mfma_64x64     mm_f32_mfma_16x32       register staging, any strides
+ * (family, then the block's tile TM x TN).  The ring serves 16-byte aligned bases with k % 4 == 0, unit
+ * a_stride_w, a_stride_h % 4 == 0, batch strides % 4 == 0 and B either k-contiguous with b_stride_w % 4 == 0 or
+ * row-major with b_stride_h % 4 == 0 and n % 4 == 0; the tile is the largest that still fills the GPU.  Every kernel
+ * gives the same bits.  The query does not judge the stride envelope above: the call does.
+ * hipErrorInvalidValue: m, n, k or batch < 1.  Needs no GPU. */
+QGEMM_API int qgemm_mm_fp32_plan(int m, int n, int k, int batch, const void *A, int64_t a_stride_h,
+                       int64_t a_stride_w, int64_t a_batch_stride, const void *B, int64_t b_stride_h,
+                       int64_t b_stride_w, int64_t b_batch_stride, const char **kernel);
 
 /* ---- The encoder counterpart (transformer.cu:14-77, BASELINE config 5) ----------
  * Linear layer on the quantized path (linear.cuh:50-54): Y = quantized_mm(X, W) [+ b] [relu], where
@@ -186,7 +212,8 @@ QGEMM_API int qgemm_encoder_destroy(void *encoder);
  * qgemm_attention_plan below.  The workspace rules do not change with it.)
  * The call allocates nothing and makes no host synchronization.
  * hipErrorInvalidValue before any launch: a null Q / K / V / O, seq_q < 0, seq_kv < 1, n_heads < 1, d_k < 1,
- * seq_kv > 4096 (qgemm_softmax_rows' row limit) or a short workspace; seq_q == 0 returns 0. */
+ * seq_kv > 4096 (qgemm_softmax_rows' row limit), a short workspace or, on the three launches only, a row stride
+ * outside qgemm_mm_fp32's stride envelope (negative, or 127 rows of it reaching 2^31 bytes); seq_q == 0 returns 0. */
 QGEMM_API size_t qgemm_attention_workspace_size(int seq_q, int seq_kv, int n_heads, int d_k);
 QGEMM_API int qgemm_attention(const float *Q, int64_t q_stride_h, const float *K, int64_t k_stride_h,
                     const float *V, int64_t v_stride_h, float *O, int64_t o_stride_h,

@@ -48,6 +48,7 @@ EXPORTED_SYMBOLS = (
     "qgemm_mm_packed",
     "qgemm_mm_packed_i32",
     "qgemm_mm_fp32",
+    "qgemm_mm_fp32_plan",
     "qgemm_error_stats",
     "qgemm_linear_workspace_size",
     "qgemm_linear",
@@ -169,6 +170,9 @@ def load() -> ctypes.CDLL:
         L.qgemm_mm_packed_i32.restype = i32
         L.qgemm_mm_fp32.argtypes = [vp, i64, i64, vp, i64, i64, vp, i64, i64, i32, i32, i32, vp]
         L.qgemm_mm_fp32.restype = i32
+        L.qgemm_mm_fp32_plan.argtypes = [i32, i32, i32, i32, vp, i64, i64, i64, vp, i64, i64, i64,
+                                         ctypes.POINTER(ctypes.c_char_p)]
+        L.qgemm_mm_fp32_plan.restype = i32
         L.qgemm_error_stats.argtypes = [vp, vp, i64, i32, vp, vp]
         L.qgemm_error_stats.restype = i32
         L.qgemm_linear_workspace_size.argtypes = [i32, i32, i32]
@@ -662,7 +666,9 @@ def mm_packed_i32(pa: Packed, pb: Packed):
 
 
 def mm_fp32(A, B, C=None):
-    """The reference's unquantized op_mm<float,float> (op_mm.cuh:49-65), bit-exact, on the GPU."""
+    """The reference's unquantized op_mm<float,float> (op_mm.cuh:49-65), bit-exact, on the GPU.  Any views of A, B and
+    C inside qgemm_mm_fp32's stride envelope (include/qgemm.h: no negative stride, a tile's offsets below 2^31 bytes);
+    QGemmError outside it.  mm_fp32_plan names the kernel a call takes."""
     import torch
     _require_device_f32(A, "A")
     _require_device_f32(B, "B")
@@ -675,6 +681,19 @@ def mm_fp32(A, B, C=None):
                                                 B.stride(1), C.data_ptr(), C.stride(0), C.stride(1), M, N, K,
                                                 _stream(A.device)))
     return C
+
+
+def mm_fp32_plan(m: int, n: int, k: int, a_stride, b_stride, batch: int = 1, a_batch_stride: int = 0,
+                 b_batch_stride: int = 0, a_ptr: int = 0, b_ptr: int = 0) -> str:
+    """The kernel mm_fp32 -- or one batched GEMM of attention's three launches -- takes for a call
+    (qgemm_mm_fp32_plan): "mm_f32_dma_<tile>_bkc" / "_bnc" or "mm_f32_mfma_<tile>".  a_stride and b_stride are
+    (stride_h, stride_w) in floats, as torch's Tensor.stride(); a_ptr and b_ptr are read for their 16-byte alignment
+    only (Tensor.data_ptr(); 0 stands for an aligned base).  Needs no GPU; raises QGemmError for dimensions < 1."""
+    name = ctypes.c_char_p()
+    _check("qgemm_mm_fp32_plan",
+           load().qgemm_mm_fp32_plan(m, n, k, batch, a_ptr, a_stride[0], a_stride[1], a_batch_stride, b_ptr,
+                                     b_stride[0], b_stride[1], b_batch_stride, ctypes.byref(name)))
+    return name.value.decode()
 
 
 def error_stats(C, O, reference_order: bool = False) -> dict:

@@ -598,6 +598,16 @@ int qgemm_gemm_plan(int m, int n, int k, int *tile, const char **kernel) {
     return gemm_plan_info(m, n, round_up(k, kKPad), tile, kernel);
 }
 
+int qgemm_mm_fp32_plan(int m, int n, int k, int batch, const void *A, int64_t a_stride_h, int64_t a_stride_w,
+                       int64_t a_batch_stride, const void *B, int64_t b_stride_h, int64_t b_stride_w,
+                       int64_t b_batch_stride, const char **kernel) {
+    if (m < 1 || n < 1 || k < 1 || batch < 1) return (int)hipErrorInvalidValue;
+    const MmF32Plan p = mm_f32_plan(m, n, k, batch, a_stride_h, a_stride_w, a_batch_stride, mm_f32_al16(A), b_stride_h,
+                                    b_stride_w, b_batch_stride, mm_f32_al16(B));
+    if (kernel) *kernel = p.name;
+    return 0;
+}
+
 int qgemm_attention_plan(int seq_q, int seq_kv, int n_heads, int d_k, const char **kernel) {
     if (seq_q < 0 || seq_kv < 1 || seq_kv > 4096 || n_heads < 1 || d_k < 1) return (int)hipErrorInvalidValue;
     if (kernel) *kernel = attention_plan_name(seq_q, seq_kv, d_k);

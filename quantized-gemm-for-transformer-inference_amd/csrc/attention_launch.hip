@@ -31,6 +31,15 @@ hipError_t launch_attention(const float *Q, int64_t ldq, const float *K, int64_t
     if (!scores) return hipErrorInvalidValue;
     // fp32 op_mm with the transposed view of K, softmax in place, fp32 op_mm into the head's columns of O
     const int64_t sbs = (int64_t)seq_q * seq_kv;
+    // The fp32 GEMMs address a tile by 32-bit offsets (mm_f32_strides_ok): a row stride of Q, K, V or O that a tile
+    // cannot hold, or a negative one, is refused here for both GEMMs, before the first launch.  (The decode and fused
+    // kernels above index through 64-bit pointers and have no such limit.)
+    const MmF32Plan qk = mm_f32_plan(seq_q, seq_kv, dk, n_heads, ldq, 1, dk, mm_f32_al16(Q), 1, ldk, dk, mm_f32_al16(K));
+    const MmF32Plan pv =
+        mm_f32_plan(seq_q, dk, seq_kv, n_heads, seq_kv, 1, sbs, mm_f32_al16(scores), ldv, 1, dk, mm_f32_al16(V));
+    if (!mm_f32_strides_ok(qk, ldq, 1, 1, ldk, seq_kv, 1, seq_q, seq_kv, dk) ||
+        !mm_f32_strides_ok(pv, seq_kv, 1, ldv, 1, ldo, 1, seq_q, dk, seq_kv))
+        return hipErrorInvalidValue;
     if ((e = launch_mm_f32_batched(Q, ldq, 1, dk, K, 1, ldk, dk, scores, seq_kv, 1, sbs, seq_q, seq_kv, dk, n_heads,
                                    stream)))
         return e;

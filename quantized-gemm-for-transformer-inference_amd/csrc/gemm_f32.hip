@@ -333,17 +333,12 @@ hipError_t launch_mm_f32(const float *A, int64_t ash, int64_t asw, const float *
     return launch_mm_f32_batched(A, ash, asw, 0, B, bsh, bsw, 0, C, csh, csw, 0, m, n, k, 1, stream);
 }
 
-hipError_t launch_mm_f32_batched(const float *A, int64_t ash, int64_t asw, int64_t a_bs, const float *B, int64_t bsh,
-                                 int64_t bsw, int64_t b_bs, float *C, int64_t csh, int64_t csw, int64_t c_bs, int m,
-                                 int n, int k, int batch, hipStream_t stream) {
-#define QG_F32(FM, FN, WGM, WGN, TK) \
-    launch_cfg<FM, FN, WGM, WGN, TK>(A, ash, asw, a_bs, B, bsh, bsw, b_bs, C, csh, csw, c_bs, m, n, k, batch, stream)
-#define QG_DMA(FM, FN, WGM, WGN, TK, NS) \
-    launch_dma<FM, FN, WGM, WGN, TK, NS>(A, ash, a_bs, B, bkc ? bsw : bsh, bkc, b_bs, C, csh, csw, c_bs, m, n, k, batch, stream)
+// THE selection rule: the launch below and qgemm_mm_fp32_plan both call it, and nothing else chooses a kernel.
+MmF32Plan mm_f32_plan(int m, int n, int k, int batch, int64_t ash, int64_t asw, int64_t a_bs, bool a_al16, int64_t bsh,
+                      int64_t bsw, int64_t b_bs, bool b_al16) {
     // 16-B aligned operands: the LDS-DMA ring
     const bool bkc = bsh == 1 && bsw != 1;
-    auto al16 = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    const bool fast = asw == 1 && ash % 4 == 0 && k % 4 == 0 && al16(A) && al16(B) && a_bs % 4 == 0 && b_bs % 4 == 0 &&
+    const bool fast = asw == 1 && ash % 4 == 0 && k % 4 == 0 && a_al16 && b_al16 && a_bs % 4 == 0 && b_bs % 4 == 0 &&
                       (bkc ? bsw % 4 == 0 : (bsw == 1 && bsh % 4 == 0 && n % 4 == 0)) && ash >= 0 && bsh >= 0 && bsw >= 0;
     // the largest tile that still gives every SIMD two waves (4 x 256 CUs x 2); k is never split:
     // every output is one sequential chain
@@ -351,19 +346,64 @@ hipError_t launch_mm_f32_batched(const float *A, int64_t ash, int64_t asw, int64
         return (int64_t)((m + tm - 1) / tm) * ((n + tn - 1) / tn) * batch * wpb;
     };
     constexpr int64_t kWant = 2048;
+    const int tile = waves(128, 128, 4) >= kWant ? 128 : waves(64, 64, 4) >= kWant ? 64 : 0;
     if (fast) {
-        if (waves(128, 128, 4) >= kWant)
+        if (tile == 128) return {true, bkc, 128, 128, bkc ? "mm_f32_dma_128x128_bkc" : "mm_f32_dma_128x128_bnc"};
+        // attention QK^T: 12 us (was 17.9 on the f32 VALU)
+        if (tile == 64) return {true, bkc, 64, 64, bkc ? "mm_f32_dma_64x64_bkc" : "mm_f32_dma_64x64_bnc"};
+        // attention PV (k = 512, 128 blocks): 10.4-11.5 us (was 34.3)
+        return {true, bkc, 32, 64, bkc ? "mm_f32_dma_32x64_bkc" : "mm_f32_dma_32x64_bnc"};
+    }
+    if (tile == 128) return {false, false, 128, 128, "mm_f32_mfma_128x128"};
+    if (tile == 64) return {false, false, 64, 64, "mm_f32_mfma_64x64"};
+    // (a 32 x 32 single-wave step between the last two could never be chosen: ceil(m / 32) <= 2 ceil(m / 64), so it
+    // wants 2048 waves only where the 64-tile plan, asked first, has them too)
+    return {false, false, 16, 32, "mm_f32_mfma_16x32"};
+}
+
+// The stride envelope (include/qgemm.h, qgemm_mm_fp32).  Both kernels address an element of a block's tile by a
+// 32-bit byte offset from the tile's first element, against a buffer descriptor of 0x7fffffff bytes: an offset past
+// it reads as zero and drops a store, and a negative stride wraps to such an offset.  So no stride that is stepped is
+// negative, and the last element a tile of plan p touches -- (rows - 1) row strides and (cols - 1) column strides
+// in, over at most one 32-wide k tile for A and B (the k tiles advance the 64-bit base) -- ends below 2^31 bytes.
+bool mm_f32_strides_ok(const MmF32Plan &p, int64_t ash, int64_t asw, int64_t bsh, int64_t bsw, int64_t csh,
+                       int64_t csw, int m, int n, int k) {
+    constexpr int64_t kMaxElems = 0x7fffffff / 4;  // whole floats inside the descriptor
+    const int64_t rows = m < p.tm ? m : p.tm, cols = n < p.tn ? n : p.tn, kk = k < 32 ? k : 32;
+    // elements from the tile's first to the last along one dimension; -1 = refused.  A dimension of one element
+    // never steps, so its stride is not looked at (torch gives such dimensions arbitrary strides).
+    auto span = [&](int64_t stride, int64_t count) -> int64_t {
+        if (count <= 1) return 0;
+        return stride < 0 || stride > kMaxElems ? -1 : (count - 1) * stride;  // count <= 128: below 2^37
+    };
+    auto ok = [&](int64_t s0, int64_t n0, int64_t s1, int64_t n1) {
+        const int64_t d0 = span(s0, n0), d1 = span(s1, n1);
+        return d0 >= 0 && d1 >= 0 && d0 + d1 < kMaxElems;
+    };
+    return ok(ash, rows, asw, kk) && ok(bsw, cols, bsh, kk) && ok(csh, rows, csw, cols);
+}
+
+hipError_t launch_mm_f32_batched(const float *A, int64_t ash, int64_t asw, int64_t a_bs, const float *B, int64_t bsh,
+                                 int64_t bsw, int64_t b_bs, float *C, int64_t csh, int64_t csw, int64_t c_bs, int m,
+                                 int n, int k, int batch, hipStream_t stream) {
+#define QG_F32(FM, FN, WGM, WGN, TK) \
+    launch_cfg<FM, FN, WGM, WGN, TK>(A, ash, asw, a_bs, B, bsh, bsw, b_bs, C, csh, csw, c_bs, m, n, k, batch, stream)
+#define QG_DMA(FM, FN, WGM, WGN, TK, NS) \
+    launch_dma<FM, FN, WGM, WGN, TK, NS>(A, ash, a_bs, B, p.bkc ? bsw : bsh, p.bkc, b_bs, C, csh, csw, c_bs, m, n, k, batch, stream)
+    const MmF32Plan p = mm_f32_plan(m, n, k, batch, ash, asw, a_bs, mm_f32_al16(A), bsh, bsw, b_bs, mm_f32_al16(B));
+    if (!mm_f32_strides_ok(p, ash, asw, bsh, bsw, csh, csw, m, n, k)) return hipErrorInvalidValue;
+    // (FM, FN, WGM, WGN): the tile is WGM * FM * 16 x WGN * FN * 16, the plan's tm x tn
+    if (p.dma) {
+        if (p.tm == 128)
             QG_DMA(4, 4, 2, 2, 32, 3);
-        else if (waves(64, 64, 4) >= kWant)
-            QG_DMA(2, 2, 2, 2, 32, 3);  // attention QK^T: 12 us (was 17.9 on the f32 VALU)
+        else if (p.tm == 64)
+            QG_DMA(2, 2, 2, 2, 32, 3);
         else
-            QG_DMA(1, 2, 2, 2, 32, 4);  // attention PV (k = 512, 128 blocks): 10.4-11.5 us (was 34.3)
-    } else if (waves(128, 128, 4) >= kWant) {
+            QG_DMA(1, 2, 2, 2, 32, 4);
+    } else if (p.tm == 128) {
         QG_F32(4, 4, 2, 2, 32);
-    } else if (waves(64, 64, 4) >= kWant) {
+    } else if (p.tm == 64) {
         QG_F32(2, 2, 2, 2, 32);
-    } else if (waves(32, 32, 1) >= kWant) {
-        QG_F32(2, 2, 1, 1, 32);
     } else {
         QG_F32(1, 2, 1, 1, 32);
     }

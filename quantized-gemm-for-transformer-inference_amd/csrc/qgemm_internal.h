@@ -242,6 +242,21 @@ hipError_t launch_gemm_i32(const PackedView &a, const PackedView &b, int32_t *Ac
                            hipStream_t stream);
 hipError_t launch_mm_f32(const float *A, int64_t ash, int64_t asw, const float *B, int64_t bsh, int64_t bsw, float *C,
                          int64_t csh, int64_t csw, int m, int n, int k, hipStream_t stream);
+// The fp32 GEMM's kernel for one call (gemm_f32.hip): the family (LDS-DMA ring or register staging), for the ring
+// whether B is k-contiguous, the block's tile, and the stable name qgemm_mm_fp32_plan reports.
+struct MmF32Plan {
+    bool dma, bkc;
+    int tm, tn;
+    const char *name;
+};
+inline bool mm_f32_al16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+// the one selection rule, read by the launch and by the query; a_al16 / b_al16: the bases are 16-byte aligned
+MmF32Plan mm_f32_plan(int m, int n, int k, int batch, int64_t ash, int64_t asw, int64_t a_bs, bool a_al16, int64_t bsh,
+                      int64_t bsw, int64_t b_bs, bool b_al16);
+// whether plan p's 32-bit tile offsets hold these strides (the envelope at qgemm_mm_fp32, include/qgemm.h);
+// launch_mm_f32_batched returns hipErrorInvalidValue before its launch where they do not
+bool mm_f32_strides_ok(const MmF32Plan &p, int64_t ash, int64_t asw, int64_t bsh, int64_t bsw, int64_t csh,
+                       int64_t csw, int m, int n, int k);
 // batch of independent GEMMs (blockIdx.z), operand i at base + i * batch stride (attention heads)
 hipError_t launch_mm_f32_batched(const float *A, int64_t ash, int64_t asw, int64_t a_bs, const float *B, int64_t bsh,
                                  int64_t bsw, int64_t b_bs, float *C, int64_t csh, int64_t csw, int64_t c_bs, int m,
