@@ -6,6 +6,8 @@ The product path (the HIP library) never imports this module.
 
 Every function here restates a step of the reference's ``op_quantized_mm``
 (/root/reference/src/ops/op_mm.cuh:67-101); the citations live in the C source.
+``build_ref()`` compiles the reference's own operators for gfx950 (oracle/ref/), which
+tests/test_gpu_reference_pin.py runs against these restatements.
 """
 from __future__ import annotations
 
@@ -38,6 +40,26 @@ def build() -> str:
     return _LIB_PATH
 
 
+REF_DRIVER = os.path.join(_HERE, "_ref", "ref_driver")
+
+
+def build_ref():
+    """`make -C oracle ref`: the reference's own operators compiled for gfx950 behind oracle/ref/ref_driver.hip, into
+    oracle/_ref/ (never committed).  The reference tree is named by QGEMM_REFERENCE_DIR (oracle/Makefile holds the
+    default and the flags).  Without that tree, or without hipcc, nothing is built and the recipe says so; returns the
+    driver's path, or None."""
+    import shutil
+    if shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"):
+        print("oracle: no hipcc: ref_driver not built, skipped")
+        return None
+    # test infrastructure for one GPU module, which skips by name without the binary: a reference tree that is
+    # there but does not compile must not take the product's build down with it
+    if subprocess.run(["make", "-s", "-C", _HERE, "ref"]).returncode != 0:
+        print("oracle: `make -C oracle ref` FAILED (see above): tests/test_gpu_reference_pin.py will skip")
+        return None
+    return REF_DRIVER if os.path.exists(REF_DRIVER) else None
+
+
 def lib():
     global _lib
     with _lock:
@@ -68,6 +90,10 @@ def lib():
                                              ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]
             L.oracle_softmax_rows.argtypes = [_f32p, _f32p, _c_i64, _c_int, _c_f]
             L.oracle_add_layernorm_rows.argtypes = [_f32p, _f32p, _f32p, _c_i64, _c_int]
+            L.oracle_softmax_args.argtypes = [_f32p, _f32p, _c_i64, _c_int, _c_f]
+            L.oracle_softmax_rows_table.argtypes = [_f32p, _f32p, _f32p, _c_i64, _c_int, _c_f]
+            L.oracle_add_layernorm_args.argtypes = [_f32p, _f32p, _f32p, _c_i64, _c_int]
+            L.oracle_add_layernorm_rows_table.argtypes = [_f32p, _f32p, _f32p, _f32p, _c_i64, _c_int]
             L.oracle_linear.argtypes = [_f32p, _f32p, ctypes.c_void_p, _c_int, _f32p, _c_int, _c_int, _c_int]
             L.oracle_encoder_weight_seed.restype = _c_u64
             L.oracle_encoder_weight_seed.argtypes = [_c_u64, _c_int, _c_int, _c_int]
@@ -215,6 +241,40 @@ def add_layernorm_rows(A, B):
     A, B = _c(A, np.float32), _c(B, np.float32)
     Y = np.empty_like(A)
     lib().oracle_add_layernorm_rows(A, B, Y, A.size // A.shape[-1], A.shape[-1])
+    return Y
+
+
+def softmax_args(S, scale: float = 1.0):
+    """The arguments softmax_rows hands to exp: fl(fl(s * scale) - max), in S's layout."""
+    S = _c(S, np.float32)
+    A = np.empty_like(S)
+    lib().oracle_softmax_args(S, A, S.size // S.shape[-1], S.shape[-1], float(scale))
+    return A
+
+
+def softmax_rows_table(S, E, scale: float = 1.0):
+    """softmax_rows with exp read from the table E (one value per argument of softmax_args): every step but exp."""
+    S, E = _c(S, np.float32), _c(E, np.float32)
+    assert E.shape == S.shape
+    P = np.empty_like(S)
+    lib().oracle_softmax_rows_table(S, E, P, S.size // S.shape[-1], S.shape[-1], float(scale))
+    return P
+
+
+def add_layernorm_args(A, B):
+    """The arguments add_layernorm_rows squares: fl(fl(a + b) - mean), in A's layout."""
+    A, B = _c(A, np.float32), _c(B, np.float32)
+    D = np.empty_like(A)
+    lib().oracle_add_layernorm_args(A, B, D, A.size // A.shape[-1], A.shape[-1])
+    return D
+
+
+def add_layernorm_rows_table(A, B, Sq):
+    """add_layernorm_rows with pow(d, 2) read from the table Sq (one value per argument of add_layernorm_args)."""
+    A, B, Sq = _c(A, np.float32), _c(B, np.float32), _c(Sq, np.float32)
+    assert A.shape == B.shape == Sq.shape
+    Y = np.empty_like(A)
+    lib().oracle_add_layernorm_rows_table(A, B, Sq, Y, A.size // A.shape[-1], A.shape[-1])
     return Y
 
 

@@ -9,11 +9,11 @@
  * It restates, element for element, the arithmetic of
  *   /root/reference/src/ops/op_mm.cuh:67-101  op_quantized_mm<float>(X, W, O, range)
  * as the reference's ten kernel launches perform it (citations per function below).
- * The reference itself cannot be built here (its headers need cuda_runtime.h /
- * curand.h, which this image lacks), so this restatement is pinned by the reference's
- * own fixture (test_quantize.cu:38-62, outputs recorded in SURVEY.md s4 KAT-1) and by
- * an independent pure-Python literal restatement (oracle/literal.py).  See DESIGN.md
- * "Oracle".
+ * It is pinned to the reference's own kernels compiled by hipcc for gfx950 (oracle/ref/,
+ * `make ref`; recorded run in tests/golden/reference_pin.npz, held by
+ * tests/test_reference_pin_host.py), to the reference's fixture (test_quantize.cu:38-62,
+ * KAT-1) and to an independent pure-Python literal restatement (oracle/literal.py).
+ * See DESIGN.md "Oracle".
  *
  * Semantics:
  *   Cx[i] = seed X[i,0], then for k>=1: if |X[i,k]| > acc: acc = |X[i,k]|      (quirk)
@@ -357,21 +357,28 @@ static void mm_f32_strided(const float *A, int64_t ash, int64_t asw, const float
 
 /* op_multiply(S, scale) (attention.cuh:65) then op_softmax (op_softmax.cuh:6-29) per row:
  * max seeded with the first element, strict '>'; exp as the correctly rounded fp32 exp
- * fl32(exp((double)x)); sum in column order; divide. */
-void oracle_softmax_rows(const float *S, float *P, int64_t rows, int w, float scale)
+ * fl32(exp((double)x)); sum in column order; divide.
+ * E, when given, holds the value to use for exp of every argument fl(s*scale) - max (rows x w, the arguments being
+ * what oracle_softmax_args writes): the reference pin's hook, which makes every other step comparable with a
+ * reference build whatever its math library.  Args, when given, receives those arguments and P is not written. */
+static void softmax_rows_impl(const float *S, float *P, int64_t rows, int w, float scale, const float *E, float *Args)
 {
 #pragma omp parallel for schedule(static)
     for (int64_t r = 0; r < rows; ++r) {
         const float *s = S + r * w;
-        float *p = P + r * w;
         float mx = s[0] * scale;
         for (int c = 1; c < w; ++c) {
             float x = s[c] * scale;
             if (x > mx) mx = x;
         }
+        if (Args) {
+            for (int c = 0; c < w; ++c) Args[r * w + c] = s[c] * scale - mx;
+            continue;
+        }
+        float *p = P + r * w;
         float sum = 0.0f;
         for (int c = 0; c < w; ++c) {
-            float e = (float)exp((double)(s[c] * scale - mx));
+            float e = E ? E[r * w + c] : (float)exp((double)(s[c] * scale - mx));
             p[c] = e;
             sum += p[c];
         }
@@ -379,25 +386,65 @@ void oracle_softmax_rows(const float *S, float *P, int64_t rows, int w, float sc
     }
 }
 
+void oracle_softmax_rows(const float *S, float *P, int64_t rows, int w, float scale)
+{
+    softmax_rows_impl(S, P, rows, w, scale, NULL, NULL);
+}
+
+/* The arguments of exp, in S's layout. */
+void oracle_softmax_args(const float *S, float *Args, int64_t rows, int w, float scale)
+{
+    softmax_rows_impl(S, NULL, rows, w, scale, NULL, Args);
+}
+
+/* oracle_softmax_rows with exp read from the table E.  P must not alias E. */
+void oracle_softmax_rows_table(const float *S, const float *E, float *P, int64_t rows, int w, float scale)
+{
+    softmax_rows_impl(S, P, rows, w, scale, E, NULL);
+}
+
 /* op_add(A, B) (transformer.cu:58) then op_layernorm as written (op_layernorm.cuh:6-33):
  * mean = sum/w, var = sum of pow(y-mean, 2) with CUDA's float pow(float,int) = fl(d*d), / w,
- * out = (y - mean) / var. */
-void oracle_add_layernorm_rows(const float *A, const float *B, float *Y, int64_t rows, int w)
+ * out = (y - mean) / var.
+ * Sq, when given, holds the value to use for pow(d, 2) of every d = y - mean (rows x w, what
+ * oracle_add_layernorm_args writes): the reference pin's hook.  Args, when given, receives d and Y is not written. */
+static void add_layernorm_rows_impl(const float *A, const float *B, float *Y, int64_t rows, int w, const float *Sq,
+                                    float *Args)
 {
 #pragma omp parallel for schedule(static)
     for (int64_t r = 0; r < rows; ++r) {
         const float *a = A + r * w, *b = B + r * w;
-        float *y = Y + r * w;
         float mean = 0.0f, var = 0.0f;
         for (int c = 0; c < w; ++c) mean += a[c] + b[c];
         mean = mean / (float)w;
+        if (Args) {
+            for (int c = 0; c < w; ++c) Args[r * w + c] = (a[c] + b[c]) - mean;
+            continue;
+        }
+        float *y = Y + r * w;
         for (int c = 0; c < w; ++c) {
             float d = (a[c] + b[c]) - mean;
-            var += d * d;
+            var += Sq ? Sq[r * w + c] : d * d;
         }
         var = var / (float)w;
         for (int c = 0; c < w; ++c) y[c] = ((a[c] + b[c]) - mean) / var;
     }
+}
+
+void oracle_add_layernorm_rows(const float *A, const float *B, float *Y, int64_t rows, int w)
+{
+    add_layernorm_rows_impl(A, B, Y, rows, w, NULL, NULL);
+}
+
+void oracle_add_layernorm_args(const float *A, const float *B, float *Args, int64_t rows, int w)
+{
+    add_layernorm_rows_impl(A, B, NULL, rows, w, NULL, Args);
+}
+
+/* oracle_add_layernorm_rows with pow(d, 2) read from the table Sq.  Y must not alias Sq. */
+void oracle_add_layernorm_rows_table(const float *A, const float *B, const float *Sq, float *Y, int64_t rows, int w)
+{
+    add_layernorm_rows_impl(A, B, Y, rows, w, Sq, NULL);
 }
 
 /* LinearLayer.forward on the quantized path (linear.cuh:50-54, + op_relu): y = fl(O + b[j]),

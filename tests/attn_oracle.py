@@ -25,8 +25,18 @@ def default_scale(dk: int) -> float:
     return init_bound(dk)  # attention.cuh:64, the same expression
 
 
-def attention_ref(Q, K, V, n_heads: int, scale: float) -> np.ndarray:
-    """Per head h (columns h*d_k ..): softmax(Q_h K_h^T * scale) V_h with the reference's op_mm<float> chains."""
+def attention_scores(Q, K, n_heads: int):
+    """S_h = Q_h K_h^T per head, the reference's op_mm<float> chain: what attention_ref hands to its softmax."""
+    Q, K = (np.asarray(a, dtype=np.float32) for a in (Q, K))
+    dk = Q.shape[1] // n_heads
+    heads = [slice(h * dk, (h + 1) * dk) for h in range(n_heads)]
+    return [O.mm_fp32(np.ascontiguousarray(Q[:, c]), np.ascontiguousarray(K[:, c].T)) for c in heads]
+
+
+def attention_ref(Q, K, V, n_heads: int, scale: float, exp_tables=None) -> np.ndarray:
+    """Per head h (columns h*d_k ..): softmax(Q_h K_h^T * scale) V_h with the reference's op_mm<float> chains.
+    exp_tables, when given, holds per head the value to use for exp of every O.softmax_args(S_h, scale) (the
+    reference pin's hook, O.softmax_rows_table); otherwise exp is the oracle's own."""
     Q, K, V = (np.asarray(a, dtype=np.float32) for a in (Q, K, V))
     seq_q, d = Q.shape
     assert d % n_heads == 0 and K.shape == V.shape and K.shape[1] == d
@@ -35,7 +45,7 @@ def attention_ref(Q, K, V, n_heads: int, scale: float) -> np.ndarray:
     for h in range(n_heads):
         c = slice(h * dk, (h + 1) * dk)
         S = O.mm_fp32(np.ascontiguousarray(Q[:, c]), np.ascontiguousarray(K[:, c].T))
-        P = O.softmax_rows(S, scale)
+        P = O.softmax_rows(S, scale) if exp_tables is None else O.softmax_rows_table(S, exp_tables[h], scale)
         out[:, c] = O.mm_fp32(P, np.ascontiguousarray(V[:, c]))
     return out
 
