@@ -10,6 +10,9 @@
 //   build/maskpack_lab [m n k rounds]
 // NOTE (round 6): written against the round-5 outlier.hip (per-stream accumulator slots, flags_acc); it does not build
 // against the current tree, whose fast path keeps no state between calls (git show bd71824:quantized-gemm-for-transformer-inference_amd/csrc/outlier.hip).
+// NOTE (one scan): the flags kernel, its fused index, outlier_scan and flags_acc that this harness names no longer exist
+// in any form: outlier_colmask_kernel<VEC> is the only scan, on the fallback too, and outlier_column_list
+// (qgemm_internal.h) the only list builder.  What "flags" means below is that round-5 launch.
 #include <cstdio>
 #include <cstdlib>
 #include <vector>

@@ -534,7 +534,7 @@ int qgemm_mm_outlier(const float *A, const float *B, float *C, int m, int n, int
     // the int8 part on the outlier-free operands (their scales no longer see the outliers)
     const int rc = op_mm_quantize_ws(Xm, k, 1, Wm, n, 1, C, n, 1, m, n, k, kDefaultRange, ws2, ws.end, stream);
     if (rc) return rc;
-    return err(outlier_finish(A, k, B, n, m, n, k, scratch, C, n, s));
+    return err(outlier_finish(A, k, B, n, nullptr, nullptr, false, m, n, k, scratch, C, n, s));
 }
 
 // [outlier scratch without the W' slot (count and column list first)][the prepacked chain's workspace]
@@ -562,19 +562,19 @@ int qgemm_linear_outlier(const float *X, int64_t x_stride_h, int m, int k, const
         if (e != hipErrorNotSupported) return err(e);
     }
     float *Xm = nullptr;
-    hipError_t e = outlier_linear_prepare(X, x_stride_h, m, k, threshold, scratch, &Xm, s);
+    hipError_t e = outlier_prepare(X, x_stride_h, nullptr, 0, m, n, k, threshold, scratch, &Xm, nullptr, s);
     if (e != hipSuccess) return err(e);
     // the int8 part on X' and the cached weight, without bias: the chain is added first
     if ((e = launch_pack_rows(Xm, k, 1, m, k, kDefaultRange, va, s)) != hipSuccess) return err(e);
     const float inv_r2 = 1.0f / (kDefaultRange * kDefaultRange);
     e = launch_gemm_dequant(va, vb, Y, y_stride_h, 1, m, n, inv_r2, ws2, ws.scratch_bytes, s);
     if (e != hipSuccess) return err(e);
-    return err(outlier_linear_finish(X, x_stride_h, m, n, k, scratch, vb, bias, relu != 0, Y, y_stride_h, s));
+    return err(outlier_finish(X, x_stride_h, nullptr, 0, &vb, bias, relu != 0, m, n, k, scratch, Y, y_stride_h, s));
 }
 
 int qgemm_outlier_count(int k, const void *workspace, int *count) {
     if (!workspace || !count || k < 1) return err(hipErrorInvalidValue);
-    return outlier_count_slot(k, workspace, count);
+    return outlier_count_slot(workspace, count);
 }
 
 int qgemm_set_gemm_events(void *start_event, void *stop_event) {

@@ -92,13 +92,6 @@ constexpr bool outlier_q(int e) { return e == kEpiOutlierQ || e == kEpiOutlierQB
 constexpr bool outlier_epi(int e) { return e == kEpiOutlier || outlier_q(e); }
 constexpr bool has_bias(int e) { return e == kEpiBias || e == kEpiBiasRelu || e == kEpiOutlierQBias || e == kEpiOutlierQBiasRelu; }
 constexpr bool has_relu(int e) { return e == kEpiBiasRelu || e == kEpiOutlierQBiasRelu; }
-// fl(1 / range) of the prepacked weight's dequantization: qgemm_linear_outlier takes weights packed with range 127
-constexpr float kInvRange127 = 1.0f / 127.0f;
-// Wd of one cached weight byte: two separate roundings (-ffp-contract=off)
-__device__ __forceinline__ float dequant_w(int8_t q, float cw) {
-    return __fmul_rn(__fmul_rn((float)(int)q, cw), kInvRange127);
-}
-
 
 template <int kEpi>
 __device__ __forceinline__ float epi_extra(float o, const float *sB, int jl) {

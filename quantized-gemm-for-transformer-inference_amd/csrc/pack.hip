@@ -221,59 +221,16 @@ __device__ __forceinline__ void zero_words_block0(uint32_t *words, int n) {
 
 // ------------------------------------------------------------------------------------------------
 // LLM.int8() decomposition inside the pack (outlier.hip builds the mask): feature k of X is an outlier
-// column when bit k of `bits` is set.  The int8 chain runs on X' / W' = X / W with those columns /
+// column when bit k of the mask is set (OutlierMask, qgemm_internal.h).  The int8 chain runs on X' / W' = X / W with those columns /
 // rows zeroed, so the packs treat them as +0 (absmax candidates, the signed seed and the quantized
 // bytes alike, exactly as packing the zeroed copies).  The fp32 part reads the original values from X and W
 // themselves (gemm_i8_fm<kEpiOutlier>), so nothing is written here but the column index.  The mask comes from the
-// flags launch as nparts partial masks (outlier.hip outlier_colmask_kernel: partial[p][w] for row split p, every word
-// written by it each call, so no state lives on between calls; nparts = 2 at K = 4096): word w = OR over p.  Each
+// column-mask launch as nparts partial masks (outlier.hip outlier_colmask_kernel: partial[p][w] for row split p, every
+// word written by it each call, so no state lives on between calls; nparts = 2 at K = 4096): word w = OR over p.  Each
 // thread reads exactly the words of its own elements, issued ahead of its data: an X-row lane's chunk l + 64 j
 // (columns 4 (l + 64 j) .. +3) is nibble l & 7 of word (l >> 3) + 8 j, a W-strip thread's rows 4 q + e + 1024 i
 // are bits of word (4 q + 1024 i) >> 5.  Workgroup 0 also builds the column count and the ascending list for the
-// GEMM (idx[0], idx[1 ..]).
-struct OutlierMask {
-    const uint32_t *partial;  // nparts x nwords partial mask words (bit 0 of word 0: column 0, the absmax seed)
-    int nwords, nparts;
-    int *idx;                 // out: [count][columns ascending]
-    // mask words w[j] (0 where w[j] >= nwords): the ORs of their nparts partial words -- every load of split 0 issued
-    // before any is waited for (nparts is 1 or 2 on the shapes the benchmarks run)
-    template <int NW>
-    __device__ __forceinline__ void words(const int (&w)[NW], uint32_t (&out)[NW]) const {
-#pragma unroll
-        for (int j = 0; j < NW; ++j) out[j] = w[j] < nwords ? partial[w[j]] : 0u;
-        for (int p = 1; p < nparts; ++p)
-#pragma unroll
-            for (int j = 0; j < NW; ++j) out[j] |= w[j] < nwords ? partial[p * nwords + w[j]] : 0u;
-    }
-    __device__ __forceinline__ uint32_t word(int w) const {
-        const int ws[1] = {w};
-        uint32_t x[1];
-        words(ws, x);
-        return x[0];
-    }
-};
-// workgroup 0 of the masked pack: idx[0] = the outlier columns, idx[1 ..] = them ascending (nwords <= blockDim)
-__device__ __forceinline__ void outlier_column_list(const OutlierMask &om, int *wsum /* LDS, blockDim / 64 */) {
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, nwave = blockDim.x >> 6;
-    const uint32_t word = t < om.nwords ? om.word(t) : 0u;
-    const int pc = __popc(word);
-    int x = pc;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int v = __shfl_up(x, off, 64);
-        if (lane >= off) x += v;
-    }
-    if (lane == 63) wsum[wave] = x;
-    __syncthreads();
-    int below = x - pc, total = 0;
-    for (int j = 0; j < nwave; ++j) {
-        below += j < wave ? wsum[j] : 0;
-        total += wsum[j];
-    }
-    int j = 0;
-    for (uint32_t b = word; b; b &= b - 1, ++j) om.idx[1 + below + j] = 32 * t + __builtin_ctz(b);
-    if (t == 0) om.idx[0] = total;
-}
+// GEMM (idx[0], idx[1 ..]; outlier_column_list, nwords <= 128 <= blockDim here).
 
 // ------------------------------------------------------------------------------------------------
 // pack_rows, vector path: rows of `len` elements at src + r*sh, unit inner stride, 16-B aligned rows, read in the

@@ -101,6 +101,13 @@ __device__ __forceinline__ float dequantize(int acc, float outer, float inv_r2) 
     return __fmul_rn(__fmul_rn((float)acc, outer), inv_r2);
 }
 
+// fl(1 / range) of the prepacked weight's dequantization: qgemm_linear_outlier takes weights packed with range 127
+constexpr float kInvRange127 = 1.0f / 127.0f;
+// Wd of one cached weight byte: two separate roundings (-ffp-contract=off)
+__device__ __forceinline__ float dequant_w(int8_t q, float cw) {
+    return __fmul_rn(__fmul_rn((float)(int)q, cw), kInvRange127);
+}
+
 // The running value of the lane to the LEFT (DPP wave_ror:1: lane l reads lane l - 1, lane 0 reads lane 63),
 // for sequential fp32 sums that hop from lane to lane (encoder_ops.hip lane_chain_sum, attention.hip).  With
 // old = 0 and bound_ctrl set, hipcc folds the move into the consuming v_add_f32 (v_add_f32_dpp).
@@ -160,6 +167,68 @@ __device__ __forceinline__ uint32_t pk_bf16(float lo, float hi) {
     return r;
 }
 
+// ---- the outlier column mask (outlier.hip writes it, pack.hip and outlier.hip read it) -------------
+// outlier_colmask_kernel writes the mask as nparts partial masks (partial[p][w] for row split p, every word written
+// each call, so no state lives on between calls; nparts = 2 at K = 4096): word w = OR over p, bit c of word w = feature
+// column 32 w + c.  The partial words come from an earlier launch in the stream: plain loads.
+struct OutlierMask {
+    const uint32_t *partial;  // nparts x nwords partial mask words (bit 0 of word 0: column 0, the absmax seed)
+    int nwords, nparts;
+    int *idx;                 // out: [count][columns ascending]
+    // mask words w[j] (0 where w[j] >= nwords): the ORs of their nparts partial words -- every load of split 0 issued
+    // before any is waited for (nparts is 1 or 2 on the shapes the benchmarks run)
+    template <int NW>
+    __device__ __forceinline__ void words(const int (&w)[NW], uint32_t (&out)[NW]) const {
+#pragma unroll
+        for (int j = 0; j < NW; ++j) out[j] = w[j] < nwords ? partial[w[j]] : 0u;
+        for (int p = 1; p < nparts; ++p)
+#pragma unroll
+            for (int j = 0; j < NW; ++j) out[j] |= w[j] < nwords ? partial[p * nwords + w[j]] : 0u;
+    }
+    __device__ __forceinline__ uint32_t word(int w) const {
+        const int ws[1] = {w};
+        uint32_t x[1];
+        words(ws, x);
+        return x[0];
+    }
+};
+// The one list builder, run by ONE workgroup (workgroup 0 of the masked packs, or outlier_index_kernel): idx[0] = the
+// number of outlier columns, idx[1 ..] = them ascending -- a wave scan of the words' popcounts + the wave sums in
+// wsum (LDS, blockDim / 64 ints).  kAnyWords = false: nwords <= blockDim, one pass, nothing else written (the packs).
+// kAnyWords = true: passes of blockDim words over a running base, and bits[w] = mask word w for every w < nwords.
+template <bool kAnyWords = false>
+__device__ __forceinline__ void outlier_column_list(const OutlierMask &om, int *wsum, uint32_t *bits = nullptr) {
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, nwave = blockDim.x >> 6;
+    int w0 = 0, total = 0;  // uniform: every thread makes every pass (the barriers)
+    do {
+        const int w = w0 + t;
+        const uint32_t word = w < om.nwords ? om.word(w) : 0u;
+        const int pc = __popc(word);
+        int x = pc;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const int v = __shfl_up(x, off, 64);
+            if (lane >= off) x += v;
+        }
+        if (lane == 63) wsum[wave] = x;
+        __syncthreads();
+        int below = x - pc, sum = 0;
+        for (int j = 0; j < nwave; ++j) {
+            below += j < wave ? wsum[j] : 0;
+            sum += wsum[j];
+        }
+        if constexpr (kAnyWords) below += total;  // the columns of the passes before this one
+        total += sum;
+        int j = 0;
+        for (uint32_t b = word; b; b &= b - 1, ++j) om.idx[1 + below + j] = 32 * w + __builtin_ctz(b);
+        if constexpr (kAnyWords) {
+            if (w < om.nwords) bits[w] = word;
+            __syncthreads();  // wsum is rewritten by the next pass
+        }
+    } while (kAnyWords && (w0 += blockDim.x) < om.nwords);
+    if (t == 0) om.idx[0] = total;
+}
+
 // ---- launchers (defined in the .hip files) ------------------------------------------------------
 hipError_t launch_pack_rows(const float *src, int64_t sh, int64_t sw, int rows, int len, float range,
                             PackedView out, hipStream_t stream);
@@ -191,7 +260,7 @@ hipError_t launch_pack_single_pass_kind(const float *x, int64_t xsh, int m, int 
                                         int64_t wsh, int n, PackedView outw, float range, hipStream_t stream, int kind,
                                         uint32_t *zero_words = nullptr, int nzero = 0);
 // The single-pass pack (8-column W strips) of the LLM.int8() decomposition's int8 part: outlier columns
-// of X / rows of W packed as +0 (the mask = OR of the flags launch's nparts x nwords partial words partial[p][w],
+// of X / rows of W packed as +0 (the mask = OR of the column-mask launch's nparts x nwords partial words partial[p][w],
 // bit c of word w = column 32 w + c); workgroup 0 writes idx[0] = the outlier count, idx[1 ..] = the columns
 // ascending.  hipErrorNotSupported outside the single pass's envelope (K % 4 == 0 too) or for nparts > 16 (nothing
 // launched).
@@ -321,28 +390,27 @@ hipError_t launch_add_layernorm_rows(const float *A, const float *B, float *Y, i
 hipError_t launch_add_layernorm_rows_pack(const float *A, const float *B, float *Y, int64_t rows, int w, float range,
                                           PackedView out, hipStream_t stream);
 // LLM.int8() outlier decomposition (outlier.hip).
+// The scratch of a call with an fp32 W (qgemm_mm_outlier), and of one on a PREPACKED weight (qgemm_linear_outlier):
+// the same without the W' slot.
 size_t outlier_scratch_bytes(int m, int n, int k);
-hipError_t outlier_prepare(const float *X, int64_t xsh, const float *W, int64_t wsh, int m, int n, int k, float t,
-                           void *scratch, float **Xm, float **Wm, hipStream_t s);
-hipError_t outlier_finish(const float *X, int64_t xsh, const float *W, int64_t wsh, int m, int n, int k, void *scratch,
-                          float *O, int64_t osh, hipStream_t s);
-int outlier_count_slot(int k, const void *scratch, int *count_host);
-// fast path (flags, indices, masked single-pass pack, GEMM with the fp32 chain in its epilogue) into the
-// packed views va / vb; hipErrorNotSupported (nothing launched) outside its envelope (row-major operands)
+size_t outlier_linear_scratch_bytes(int m, int k);
+int outlier_count_slot(const void *scratch, int *count_host);
+// Fast paths into the packed views va / vb; hipErrorNotSupported (nothing launched) outside their envelopes.
+// outlier_fast (row-major fp32 operands): column mask, masked single-pass pack, the 256-tile GEMM with the fp32 chain
+// in its epilogue.  outlier_linear_fast: column mask, masked X-only pack into va, the 256-tile GEMM with the chain on
+// vb's dequantized rows (+ bias / relu) in its epilogue.
 hipError_t outlier_fast(const float *X, const float *W, float *O, int m, int n, int k, float t, void *scratch,
                         PackedView va, PackedView vb, float range, hipStream_t s);
-// The decomposition on a PREPACKED weight (qgemm_linear_outlier): the scratch is outlier_scratch_bytes without the
-// W' slot.  outlier_linear_fast: column mask, masked X-only pack into va, the 256-tile GEMM with the chain on vb's
-// dequantized rows (+ bias / relu) in its epilogue; hipErrorNotSupported (nothing launched) outside its envelope.
-// Fallback: outlier_linear_prepare (index + X' into the scratch), the caller's plain chain on X' without bias, then
-// outlier_linear_finish (the chain on vb's dequantized rows added to Y, then bias / relu).
-size_t outlier_linear_scratch_bytes(int m, int k);
 hipError_t outlier_linear_fast(const float *X, int64_t xsh, int m, int n, int k, float t, void *scratch, PackedView va,
                                PackedView vb, const float *bias, bool relu, float *Y, int64_t ysh, hipStream_t s);
-hipError_t outlier_linear_prepare(const float *X, int64_t xsh, int m, int k, float t, void *scratch, float **Xm,
-                                  hipStream_t s);
-hipError_t outlier_linear_finish(const float *X, int64_t xsh, int m, int n, int k, void *scratch, PackedView vb,
-                                 const float *bias, bool relu, float *Y, int64_t ysh, hipStream_t s);
+// Fallback: outlier_prepare (column mask, index, X' and -- where W != nullptr -- W' into the scratch; Wm may be
+// nullptr without a W), the caller's plain chain on them without bias, then outlier_finish: the chain on W's rows
+// (W != nullptr) or on the packed weight vb's dequantized rows added to O, then bias / relu.
+hipError_t outlier_prepare(const float *X, int64_t xsh, const float *W, int64_t wsh, int m, int n, int k, float t,
+                           void *scratch, float **Xm, float **Wm, hipStream_t s);
+hipError_t outlier_finish(const float *X, int64_t xsh, const float *W, int64_t wsh, const PackedView *vb,
+                          const float *bias, bool relu, int m, int n, int k, void *scratch, float *O, int64_t osh,
+                          hipStream_t s);
 // The transformer stack (transformer.hip): an encoder is a stack without cross-attention, a decoder one with it.
 // encoder_forward refuses a stack with cross-attention and decoder_* one without (hipErrorInvalidValue).
 struct Stack;

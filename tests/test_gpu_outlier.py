@@ -27,15 +27,54 @@ def _with_outliers(oracle, M, N, K, cols, seed):
     return X.astype(np.float32), W
 
 
-# (72, 40, 33000): K > 32 768 = past the flags launch's accumulator -- its partial-word path, 64-row chunks
+# (72, 40, 33000): 1032 mask words = two passes of the fallback's one-workgroup index kernel (1024 words per pass):
+# columns on both sides of that pass edge (32767 | 32768), of a 256-word boundary (8191 | 8192), and the first and last
 @pytest.mark.parametrize("M,N,K,cols", [(300, 200, 512, [3, 77, 400]), (2048, 1024, 4096, list(range(5, 4096, 257))),
-                                        (64, 96, 130, [0, 129]), (72, 40, 33000, [0, 31, 32767, 32768, 32999])])
+                                        (64, 96, 130, [0, 129]),
+                                        (72, 40, 33000, [0, 31, 8191, 8192, 32767, 32768, 32999])])
 def test_outlier_decomposition_bit_exact(qg, oracle, device, M, N, K, cols):
     X, W = _with_outliers(oracle, M, N, K, cols, 5)
     C, cnt = qg.mm_outlier(_dev(X, device), _dev(W, device), 6.0)
     want, wcnt = oracle.mm_outlier(X, W, 6.0)
     assert cnt == wcnt == len(cols)
     assert_bits_equal(C.cpu().numpy(), want, f"outlier decomposition {M}x{N}x{K}")
+
+
+def _planted(oracle, M, N, K, points, seed):
+    """Inputs below 1 everywhere but at the hand-placed (row, col) points: |x| = 7, 8, .. with alternating signs, or NaN
+    where the point carries one."""
+    X, W = oracle.inputs(M, N, K, seed)
+    assert np.abs(X).max() < 1
+    for i, (r, c, *v) in enumerate(points):
+        X[r, c] = v[0] if v else (7.0 + i % 6) * (-1) ** i
+    return X, W
+
+
+def test_outlier_row_splits_are_ored_on_the_scalar_scan(qg, oracle, device):
+    """K % 4 != 0: the column-mask kernel's scalar loads (and the fallback).  M = 700 is 6 row splits of 128 rows, the
+    last of 60; every outlier column has its one outlier in one split only -- rows 0 and 127 of the first, row 128
+    (the second's first), rows 640 and 699 of the last -- and columns 0, 31 | 32 (a word edge), 64 and 129 (the last
+    word's last column, K = 130).  A scan that drops a split, or a word's last columns, loses a column."""
+    M, N, K = 700, 40, 130
+    points = [(0, 0), (127, 31), (128, 32), (640, 64), (699, 129)]
+    X, W = _planted(oracle, M, N, K, points, 15)
+    C, cnt = qg.mm_outlier(_dev(X, device), _dev(W, device), 6.0)
+    want, wcnt = oracle.mm_outlier(X, W, 6.0)
+    assert cnt == wcnt == len(points)
+    assert_bits_equal(C.cpu().numpy(), want, f"outlier row splits {M}x{N}x{K}")
+
+
+# M > 65 535: more rows than a grid's y extent.  (65600, 24, 36) has 257 256-tiles, K % 4 == 0 and N % 8 == 0: the fast
+# path (the GEMM's epilogue adds the chain).  (65600, 24, 38), K % 4 != 0, takes the fallback, whose correction kernel
+# strides the rows over 65 535 blocks.
+@pytest.mark.parametrize("M,N,K", [(65600, 24, 36), (65600, 24, 38)])
+def test_outlier_more_than_65535_rows(qg, oracle, device, M, N, K):
+    points = [(0, 0), (M - 1, K - 1), (40000, 17, np.nan)]
+    X, W = _planted(oracle, M, N, K, points, 16)
+    C, cnt = qg.mm_outlier(_dev(X, device), _dev(W, device), 6.0)
+    want, wcnt = oracle.mm_outlier(X, W, 6.0)
+    assert cnt == wcnt == len(points)
+    assert_bits_equal(C.cpu().numpy(), want, f"outlier {M}x{N}x{K}")
 
 
 # shapes on the fast path (>= 160 256-tiles, row-major, K % 4 == 0, K <= 4096, N % 8 == 0): the masked
@@ -133,11 +172,11 @@ def test_decomposition_reduces_quantization_error(qg, oracle, device):
 
 
 def test_outlier_graph_capture_and_repeat(qg, oracle, device):
-    """qgemm_mm_outlier makes no allocation and no host sync (the outlier count stays on the device; the flags
-    launch's counters and accumulator live in the workspace and a kernel zeroes them at the start of every call), so
-    the four fast-path launches (zero state, flags, masked pack, GEMM with the chain) can be captured in a HIP graph
-    -- here as the FIRST call on its stream -- and replayed; and 20 eager calls on one workspace give the same bits
-    every time (race screen of the accumulator / count / column-list hand-offs)."""
+    """qgemm_mm_outlier makes no allocation and no host sync (the outlier count stays on the device; the column-mask
+    launch writes every partial mask word of the workspace every call, so nothing is zeroed and nothing lives on
+    between calls), so the three fast-path launches (column mask, masked pack, GEMM with the chain) can be captured in
+    a HIP graph -- here as the FIRST call on its stream -- and replayed; and 20 eager calls on one workspace give the
+    same bits every time (race screen of the mask / count / column-list hand-offs between the launches)."""
     import torch
     M, N, K = 2560, 4096, 512
     X, W = _with_outliers(oracle, M, N, K, [0, 5, 77, 300, 511], 12)
@@ -211,7 +250,7 @@ def test_outlier_fast_path_at_the_benched_shape(qg, oracle, device, ncols):
 
 def test_outlier_unaligned_workspace_bit_exact(qg, oracle, device):
     """A caller workspace that is only 4-B aligned: the fast path keeps nothing wider than an int in it (the count,
-    the column list, the flags counters and mask words), so it runs there, bit-exact."""
+    the column list and the mask words), so it runs there, bit-exact."""
     M, N, K = 2560, 4096, 256
     X, W = _with_outliers(oracle, M, N, K, [1, 100, 255], 14)
     want, wcnt = oracle.mm_outlier(X, W, 6.0)
@@ -245,8 +284,8 @@ def _outlier_case(qg, oracle, device, M, N, K, cols, seed):
 
 @pytest.mark.parametrize("M,N,K", [(2560, 4096, 512), (300, 200, 516)])  # fast path; materialising fallback
 def test_outlier_concurrent_streams_bit_exact(qg, oracle, device, M, N, K):
-    """the flags launch's state (counters, mask accumulator) belongs to the call, in its workspace -- not
-    to a library slot keyed by the stream handle.  Two streams run outlier calls at the same time, each with its own
+    """what the scan launches hand on (partial mask words, mask, count, column list) belongs to the call,
+    in its workspace -- not to a library slot keyed by the stream handle.  Two streams run outlier calls at the same time, each with its own
     workspace and its own outlier columns; every output bit-exact."""
     L = qg.load()
     cases = [_outlier_case(qg, oracle, device, M, N, K, cols, 21 + i)

@@ -97,7 +97,7 @@ FAST = [(2560, 4096, 128, [0, 31, 32, 127]),               # the seed column, ma
         (512, 16384, 256, [3, 100, 255])]                  # >= 64-KiB output rows: the LDS-image stores
 FALLBACK = [(300, 200, 512, [3, 77, 400]),                 # small tiles
             (64, 96, 130, [0, 129]),                       # K % 4 != 0
-            (72, 40, 33000, [0, 31, 32767, 32768, 32999])]  # K > 4096, past the flags accumulator
+            (72, 40, 33000, [0, 31, 32767, 32768, 32999])]  # K > 4096: 1032 mask words, two passes of the index kernel
 SPLIT = (128, 512, 4096, [5, 2048, 4095])                  # 64-tiles, split-K
 
 
@@ -188,6 +188,22 @@ def test_fallback_misaligned_base(qg, oracle, device):
     Y, cnt = qg.linear_outlier(Xv, qg.pack_b(_dev(W, device)), 6.0)
     assert cnt == len(cols)
     assert_bits_equal(Y.cpu().numpy(), want, "linear_outlier, misaligned X base")
+
+
+@pytest.mark.parametrize("M,N,K", [(65600, 24, 36), (65600, 24, 38)])  # fast path; K % 4 != 0: the fallback
+def test_more_than_65535_rows_bias_relu(qg, oracle, device, M, N, K):
+    """More rows than a grid's y extent, with bias + relu: the fallback's correction kernel strides the rows over
+    65 535 blocks.  Outliers in the first and the last row and a NaN between them, everything else below 1."""
+    assert _on_fast_plan(qg, M, N, K) == (K % 4 == 0), _plan(qg, M, N, K)
+    X, W = oracle.inputs(M, N, K, 16)
+    X[0, 0], X[M - 1, K - 1], X[40000, 17] = 7.5, -11.0, np.nan
+    b = oracle.uniform((N,), 80, -0.5, 0.5)
+    want, wcnt = _compose(oracle, X, W, 6.0, b, True)
+    assert wcnt == 3
+    Y, cnt = qg.linear_outlier(_dev(X, device), qg.pack_b(_dev(W, device)), 6.0, bias=_dev(b, device), relu=True)
+    assert cnt == 3
+    assert np.isnan(want[40000]).all() and (want == 0).any() and (want > 0).any()
+    assert_bits_equal(Y.cpu().numpy(), want, f"linear_outlier {M}x{N}x{K}, bias + relu")
 
 
 @pytest.mark.parametrize("M,N,K", [(2560, 4096, 128), (300, 200, 516)])  # fast path; fallback

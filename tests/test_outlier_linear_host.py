@@ -23,7 +23,7 @@ def test_workspace_size_is_zero_for_invalid_dims(qg, m, n, k):
     assert qg.load().qgemm_linear_outlier_workspace_size(m, n, k) == 0
 
 
-# fast-path shapes, 64- / 32-tile plans, a split-K plan, K past the flags accumulator, K % 4 != 0, empty M / N
+# fast-path shapes, 64- / 32-tile plans, a split-K plan, K past one pass of the index kernel, K % 4 != 0, empty M / N
 @pytest.mark.parametrize("m,n,k", [(4096, 4096, 4096), (2560, 4096, 128), (300, 200, 512), (64, 96, 130),
                                    (72, 40, 33000), (2048, 4096, 16384), (512, 1024, 4096), (1, 1, 1), (0, 8, 8),
                                    (8, 0, 8)])
