@@ -354,6 +354,72 @@ QGEMM_API int qgemm_decoder_step_batch(void *decoder, int n_seqs, const int *slo
 QGEMM_API int qgemm_decoder_copy_slot(void *decoder, int dst_slot, int src_slot, void *stream);
 QGEMM_API int qgemm_decoder_slot_state(void *decoder, int slot, int *enc_seq, int *filled);
 
+/* ---- Batched variable-length forward: packed sequences in one attention launch ---------
+ * qgemm_attention_varlen: qgemm_attention / qgemm_attention_causal for up to QGEMM_VARLEN_MAX_SEQS independent
+ * sequences of DIFFERENT lengths in one call.  Sequence b has seq_q[b] query rows that start at row q_row0[b] of Q --
+ * and its output rows at the same row q_row0[b] of O -- and seq_kv[b] keys that start at row kv_row0[b] of K and V
+ * (row strides *_stride_h in floats, unit inner stride, head h at columns h*d_k ..).  q_pos0[b] is its mask offset;
+ * q_pos0 == NULL means no mask for any sequence.  All five arrays are HOST arrays of n_seqs entries, read when the
+ * call is enqueued: they travel in the kernel's arguments, so nothing is copied to the device, allocated or
+ * synchronized, and a captured graph replays the values of the capture.
+ * Where d_k <= 64 and EVERY seq_kv[b] <= 512 the call is ONE launch of the fused kernel over a table of sequences:
+ * sum_b ceil(seq_q[b] / 32) * n_heads workgroups, none for a sequence with seq_q[b] == 0.  Otherwise it runs the
+ * sequences one after another in order, each as qgemm_attention[_causal] would (decode, fused or three launches
+ * through `workspace`).  qgemm_attention_varlen_plan names the path: "attention_fused_kernel<many>" or
+ * "per_sequence"; it needs no GPU.  qgemm_attention_varlen_workspace_size is the largest
+ * qgemm_attention_workspace_size over the sequences: 0 exactly when one table launch serves the call.
+ * Contract: for every b, rows q_row0[b] .. q_row0[b] + seq_q[b] - 1 of O are BIT FOR BIT what
+ * qgemm_attention (q_pos0 == NULL) or qgemm_attention_causal with q_pos0[b] gives on
+ * (Q + q_row0[b] * q_stride_h, K + kv_row0[b] * k_stride_h, V + kv_row0[b] * v_stride_h, O + q_row0[b] * o_stride_h,
+ * seq_q[b], seq_kv[b]); no other row of O is written.  Sequences may share rows of Q, K and V.  Output rows that two
+ * sequences share are the caller's error and are not checked; O must not overlap Q, K or V (not checked).
+ * hipErrorInvalidValue before any launch: a null Q / K / V / O / q_row0 / seq_q / kv_row0 / seq_kv, n_seqs < 0 or
+ * > 64, a negative row offset, seq_q[b] < 0, seq_kv[b] < 1 or > 4096, q_pos0[b] < 0, n_heads < 1, d_k < 1, a workspace
+ * smaller than qgemm_attention_varlen_workspace_size (which is 0 for arguments the call refuses); n_seqs == 0
+ * returns 0 without a launch.  (On the three launches alone a row stride outside qgemm_mm_fp32's stride envelope is
+ * refused when its sequence is reached, as by qgemm_attention.) */
+enum { QGEMM_VARLEN_MAX_SEQS = 64 };
+QGEMM_API size_t qgemm_attention_varlen_workspace_size(int n_seqs, const int *seq_q, const int *seq_kv, int n_heads,
+                                             int d_k);
+QGEMM_API int qgemm_attention_varlen(const float *Q, int64_t q_stride_h, const float *K, int64_t k_stride_h,
+                           const float *V, int64_t v_stride_h, float *O, int64_t o_stride_h, int n_seqs,
+                           const int64_t *q_row0, const int *seq_q, const int64_t *kv_row0, const int *seq_kv,
+                           const int *q_pos0 /* NULL: no mask */, int n_heads, int d_k, float scale,
+                           void *workspace, size_t ws_bytes, void *stream);
+QGEMM_API int qgemm_attention_varlen_plan(int n_seqs, const int *seq_q, const int *seq_kv, int n_heads, int d_k,
+                                const char **kernel);
+/* The stacks on many sequences at once.  Every step of a block but the attention is row-local (per-row quantization
+ * scales, exact int32 accumulation, per-element dequantization, one-row add + layernorm), so the rows of all
+ * sequences run through one pass of the blocks as ONE matrix, and the attention goes through qgemm_attention_varlen.
+ *   create_rows    qgemm_encoder_create / qgemm_decoder_create_slots with a ROW BUDGET: the scratch buffers, the packed
+ *                  activations and the split-K scratch hold max(what those calls give, max_rows) rows (max_rows == 0:
+ *                  exactly those calls).  The scores of the per-sequence path stay sized by max_seq.  Refused:
+ *                  max_rows < 0, and a max_rows with round_up(max_rows, 256) * round_up(max(3 d_model, d_ff), 128)
+ *                  > 2^31 - 1 -- below that no element index of a row-local kernel (pack, GEMM epilogue, add +
+ *                  layernorm) on the widest activation buffer or its packed image leaves 32 bits.
+ *   forward_batch  X, Y: the n_seqs (1 .. 64) sequences' rows packed one after another, sum seq_lens rows x d_model,
+ *                  contiguous; 1 <= seq_lens[b] <= max_seq, sum <= the row budget.  Sequence b's rows of Y are BIT FOR
+ *                  BIT qgemm_encoder_forward's on its rows of X alone.
+ *   step_varlen    step_batch without its limits of 8 and of equal rows: sequence b appends n_rows[b] >= 1 rows (rows
+ *                  sum_{b' < b} n_rows[b'] .. of X and Y) at positions pos[b] .. of slot slots[b] -- a prefill of many
+ *                  slots in one pass, or prefills mixed with single decoding rows.  Row for row Y is BIT FOR BIT what
+ *                  step_slot(slots[b], .., pos[b], n_rows[b]) gives for that sequence alone.  On success
+ *                  filled[slots[b]] = pos[b] + n_rows[b].  Past 512 keys (or d_k > 64) the attention runs sequence by
+ *                  sequence.  The Q third of the cache rows it writes is unspecified.
+ * Neither allocates or synchronizes; seq_lens, slots, pos and n_rows are host arrays read at enqueue time.
+ * hipErrorInvalidValue before any launch and without moving any filled length: a null pointer, n_seqs < 1 or > 64
+ * (step_varlen: > n_slots), a length < 1 or > max_seq, more rows than the budget, an encoder handed to step_varlen or
+ * a decoder to forward_batch; for step_varlen also step_batch's: a slot out of range, not begun or named twice,
+ * pos[b] < 0, pos[b] > filled, pos[b] + n_rows[b] > max_seq. */
+QGEMM_API int qgemm_encoder_create_rows(int d_model, int n_heads, int d_ff, int n_blocks, int max_seq, int max_rows,
+                              uint64_t seed, void **encoder);
+QGEMM_API int qgemm_encoder_forward_batch(void *encoder, const float *X, float *Y, int n_seqs, const int *seq_lens,
+                                void *stream);
+QGEMM_API int qgemm_decoder_create_rows(int d_model, int n_heads, int d_ff, int n_blocks, int max_seq, int max_enc_seq,
+                              uint64_t seed, int flags, int n_slots, int max_rows, void **decoder);
+QGEMM_API int qgemm_decoder_step_varlen(void *decoder, int n_seqs, const int *slots, const int *pos, const int *n_rows,
+                              const float *X, float *Y, void *stream);
+
 /* ---- LLM.int8() outlier decomposition ------------------------------------------
  * Feature columns k of A (= rows of B) holding an element with NOT(|x| <= threshold) (the reference's
  * AbsCompareLTEConstFunc, op_elemwise.cuh:293-306; NaN counts as an outlier) are multiplied in fp32,

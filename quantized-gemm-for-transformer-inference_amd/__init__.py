@@ -81,6 +81,13 @@ EXPORTED_SYMBOLS = (
     "qgemm_decoder_step_batch",
     "qgemm_decoder_copy_slot",
     "qgemm_decoder_slot_state",
+    "qgemm_attention_varlen_workspace_size",
+    "qgemm_attention_varlen",
+    "qgemm_attention_varlen_plan",
+    "qgemm_encoder_create_rows",
+    "qgemm_encoder_forward_batch",
+    "qgemm_decoder_create_rows",
+    "qgemm_decoder_step_varlen",
     "qgemm_mm_outlier_workspace_size",
     "qgemm_mm_outlier",
     "qgemm_outlier_count",
@@ -118,6 +125,7 @@ QGEMM_F32, QGEMM_BF16 = 0, 1  # element-type tags of the _dt entry points (inclu
 QGEMM_DECODER_CAUSAL = 1       # qgemm_decoder_create_ex flag: causal mask on the self-attention
 QGEMM_DECODER_KV_CACHE = 8     # ... and per-block key / value caches for begin() / step() (with CAUSAL only)
 QGEMM_DECODE_MAX_BATCH = 64    # sequences per attention_decode_batched / step_batch call, cache slots per decoder
+QGEMM_VARLEN_MAX_SEQS = 64     # sequences per attention_varlen / forward_batch / step_varlen call
 
 _lock = threading.Lock()
 _lib = None
@@ -241,6 +249,23 @@ def load() -> ctypes.CDLL:
         L.qgemm_decoder_copy_slot.restype = i32
         L.qgemm_decoder_slot_state.argtypes = [vp, i32, ip, ip]
         L.qgemm_decoder_slot_state.restype = i32
+        lp = ctypes.POINTER(i64)
+        L.qgemm_attention_varlen_workspace_size.argtypes = [i32, ip, ip, i32, i32]
+        L.qgemm_attention_varlen_workspace_size.restype = sz
+        L.qgemm_attention_varlen.argtypes = [vp, i64, vp, i64, vp, i64, vp, i64, i32, lp, ip, lp, ip, ip, i32, i32, f32,
+                                             vp, sz, vp]
+        L.qgemm_attention_varlen.restype = i32
+        L.qgemm_attention_varlen_plan.argtypes = [i32, ip, ip, i32, i32, ctypes.POINTER(ctypes.c_char_p)]
+        L.qgemm_attention_varlen_plan.restype = i32
+        L.qgemm_encoder_create_rows.argtypes = [i32, i32, i32, i32, i32, i32, ctypes.c_uint64, ctypes.POINTER(vp)]
+        L.qgemm_encoder_create_rows.restype = i32
+        L.qgemm_encoder_forward_batch.argtypes = [vp, vp, vp, i32, ip, vp]
+        L.qgemm_encoder_forward_batch.restype = i32
+        L.qgemm_decoder_create_rows.argtypes = [i32, i32, i32, i32, i32, i32, ctypes.c_uint64, i32, i32, i32,
+                                                ctypes.POINTER(vp)]
+        L.qgemm_decoder_create_rows.restype = i32
+        L.qgemm_decoder_step_varlen.argtypes = [vp, i32, ip, ip, ip, vp, vp, vp]
+        L.qgemm_decoder_step_varlen.restype = i32
         L.qgemm_mm_outlier_workspace_size.argtypes = [i32, i32, i32]
         L.qgemm_mm_outlier_workspace_size.restype = sz
         L.qgemm_mm_outlier.argtypes = [vp, vp, vp, i32, i32, i32, f32, vp, sz, vp]
@@ -874,15 +899,40 @@ def encoder_weight_seed(base: int, block: int, kind: int, head: int) -> int:
 
 
 class Encoder:
-    """transformer.cu:14-77's Encoder with its linears on the quantized path."""
+    """transformer.cu:14-77's Encoder with its linears on the quantized path.  max_rows
+    (qgemm_encoder_create_rows): the rows forward_batch may run at once, max_seq where left out."""
 
-    def __init__(self, d_model: int, n_heads: int, d_ff: int, n_blocks: int, max_seq: int, seed: int = 0):
+    def __init__(self, d_model: int, n_heads: int, d_ff: int, n_blocks: int, max_seq: int, seed: int = 0,
+                 max_rows=None):
         self.d_model, self.n_heads, self.d_ff, self.n_blocks, self.max_seq, self.seed = (
             d_model, n_heads, d_ff, n_blocks, max_seq, seed)
+        self.max_rows = max_rows
         h = ctypes.c_void_p()
-        _check("qgemm_encoder_create", load().qgemm_encoder_create(d_model, n_heads, d_ff, n_blocks, max_seq, seed,
-                                                                  ctypes.byref(h)))
+        if max_rows is None:
+            _check("qgemm_encoder_create", load().qgemm_encoder_create(d_model, n_heads, d_ff, n_blocks, max_seq, seed,
+                                                                      ctypes.byref(h)))
+        else:
+            _check("qgemm_encoder_create_rows",
+                   load().qgemm_encoder_create_rows(d_model, n_heads, d_ff, n_blocks, max_seq, int(max_rows), seed,
+                                                    ctypes.byref(h)))
         self._h = h
+
+    def forward_batch(self, X, seq_lens, Y=None):
+        """forward on len(seq_lens) sequences at once (qgemm_encoder_forward_batch): X holds their rows packed one
+        after another, sum(seq_lens) x d_model; the rows of each sequence in Y are, bit for bit, forward's on that
+        sequence alone."""
+        import torch
+        _require_device_f32(X, "X")
+        seq_lens = [int(v) for v in seq_lens]
+        assert X.is_contiguous() and X.shape == (sum(seq_lens), self.d_model), "X: sum(seq_lens) x d_model, contiguous"
+        Y = torch.empty_like(X) if Y is None else Y
+        _require_device_f32(Y, "Y")
+        assert Y.is_contiguous() and Y.shape == X.shape
+        n = len(seq_lens)
+        _check("qgemm_encoder_forward_batch",
+               load().qgemm_encoder_forward_batch(self._h, X.data_ptr(), Y.data_ptr(), n,
+                                                  _int_array(seq_lens, n, "seq_lens"), _stream(X.device)))
+        return Y
 
     def forward(self, X, Y=None):
         import torch
@@ -1004,6 +1054,78 @@ def attention_decode_batched(Q, K, V, n_heads: int, seq_kv, q_pos0=None, kv_slot
     return O
 
 
+def _int64_array(values, n: int, name: str):
+    values = [int(v) for v in values]
+    assert len(values) == n, f"{name}: one entry per sequence"
+    return (ctypes.c_int64 * max(1, n))(*values)
+
+
+def _prefix_sums(counts):
+    out, acc = [], 0
+    for c in counts:
+        out.append(acc)
+        acc += int(c)
+    return out
+
+
+def attention_varlen(Q, K, V, n_heads: int, seq_q, seq_kv, q_row0=None, kv_row0=None, q_pos0=None, scale=None, O=None):
+    """attention() for up to 64 independent sequences of different lengths in one call (qgemm_attention_varlen).
+    Sequence b has seq_q[b] query rows from row q_row0[b] of Q -- and of O -- and seq_kv[b] keys from row kv_row0[b]
+    of K and V; the row offsets default to the packed layout (prefix sums of seq_q / seq_kv).  q_pos0 (one per
+    sequence) masks as attention(causal=True, q_pos0=q_pos0[b]); left out there is no mask.  All of them are host
+    sequences of ints, read at the call.  One launch where d_k <= 64 and every seq_kv[b] <= 512, else sequence by
+    sequence (attention_varlen_plan); each sequence's rows of the result equal attention() on its views bit for bit,
+    and no other row of O is written (a fresh O is zero-filled)."""
+    import math
+    import torch
+    for t, nm in ((Q, "Q"), (K, "K"), (V, "V")):
+        _require_device_f32(t, nm)
+        assert t.dim() == 2 and (t.stride(1) == 1 or t.shape[1] == 1), f"{nm} must be 2-D with unit inner stride"
+    d = Q.shape[1]
+    assert K.shape[1] == d and V.shape[1] == d, "K and V: d columns as Q"
+    assert n_heads >= 1 and d % n_heads == 0, "d % n_heads == 0"
+    dk = d // n_heads
+    seq_q, seq_kv = [int(v) for v in seq_q], [int(v) for v in seq_kv]
+    n = len(seq_q)
+    assert len(seq_kv) == n, "seq_q and seq_kv: one entry per sequence"
+    q_row0 = _prefix_sums(seq_q) if q_row0 is None else [int(v) for v in q_row0]
+    kv_row0 = _prefix_sums(seq_kv) if kv_row0 is None else [int(v) for v in kv_row0]
+    assert len(q_row0) == n and len(kv_row0) == n, "q_row0 and kv_row0: one entry per sequence"
+    if O is None:
+        O = torch.zeros((Q.shape[0], d), dtype=torch.float32, device=Q.device)
+    _require_device_f32(O, "O")
+    assert O.dim() == 2 and O.shape[1] == d and (O.stride(1) == 1 or d == 1), "O: d columns, unit inner stride"
+    for b in range(n):  # the rows the call reads and writes exist
+        if q_row0[b] >= 0 and seq_q[b] >= 0:
+            assert q_row0[b] + seq_q[b] <= min(Q.shape[0], O.shape[0]), f"sequence {b}'s query rows exceed Q / O"
+        if kv_row0[b] >= 0 and seq_kv[b] >= 0:
+            assert kv_row0[b] + seq_kv[b] <= min(K.shape[0], V.shape[0]), f"sequence {b}'s keys exceed K / V"
+    if scale is None:
+        scale = ctypes.c_float(1.0 / math.sqrt(float(dk))).value  # attention.cuh:64
+    L = load()
+    sq, skv = _int_array(seq_q, n, "seq_q"), _int_array(seq_kv, n, "seq_kv")
+    need = L.qgemm_attention_varlen_workspace_size(n, sq, skv, n_heads, dk)
+    ws = torch.empty(need, dtype=torch.uint8, device=Q.device) if need else None
+    _check("qgemm_attention_varlen",
+           L.qgemm_attention_varlen(Q.data_ptr(), Q.stride(0), K.data_ptr(), K.stride(0), V.data_ptr(), V.stride(0),
+                                    O.data_ptr(), O.stride(0), n, _int64_array(q_row0, n, "q_row0"), sq,
+                                    _int64_array(kv_row0, n, "kv_row0"), skv, _int_array(q_pos0, n, "q_pos0"), n_heads,
+                                    dk, float(scale), ws.data_ptr() if need else None, need, _stream(Q.device)))
+    return O
+
+
+def attention_varlen_plan(seq_q, seq_kv, n_heads: int, d_k: int) -> str:
+    """The path attention_varlen() takes (qgemm_attention_varlen_plan): "attention_fused_kernel<many>", one launch over
+    the table of sequences, or "per_sequence".  Needs no GPU; raises QGemmError for arguments the call refuses."""
+    seq_q, seq_kv = [int(v) for v in seq_q], [int(v) for v in seq_kv]
+    n = len(seq_q)
+    name = ctypes.c_char_p()
+    _check("qgemm_attention_varlen_plan",
+           load().qgemm_attention_varlen_plan(n, _int_array(seq_q, n, "seq_q"), _int_array(seq_kv, n, "seq_kv"), n_heads,
+                                              d_k, ctypes.byref(name)))
+    return name.value.decode()
+
+
 def attention_plan(seq_q: int, seq_kv: int, n_heads: int, d_k: int) -> str:
     """The launch attention() takes for a shape (qgemm_attention_plan): a name that begins "attention_decode",
     "attention_fused" or "three_launches".  Needs no GPU; raises QGemmError for dimensions attention() refuses."""
@@ -1021,15 +1143,24 @@ class Decoder:
     on the whole prefix, bit for bit -- from per-block key / value caches.  n_slots > 1
     (qgemm_decoder_create_slots): the caches hold that many independent sequences on one copy of the weights;
     begin_slot / step_slot drive one of them, step_batch advances many in one step, copy_slot forks one (DESIGN.md s17);
-    begin / step are slot 0's."""
+    begin / step are slot 0's.  max_rows (qgemm_decoder_create_rows; a keyword, ahead of n_slots only so that n_slots
+    stays the last parameter): the rows step_varlen may run at once."""
 
     def __init__(self, d_model: int, n_heads: int, d_ff: int, n_blocks: int, max_seq: int, max_enc_seq: int,
-                 seed: int = 0, causal: bool = False, kv_cache: bool = False, n_slots: int = 1):
+                 seed: int = 0, causal: bool = False, kv_cache: bool = False, max_rows=None, n_slots: int = 1):
         self.d_model, self.n_heads, self.d_ff, self.n_blocks, self.max_seq, self.max_enc_seq, self.seed = (
             d_model, n_heads, d_ff, n_blocks, max_seq, max_enc_seq, seed)
         self.causal, self.kv_cache, self.n_slots = bool(causal), bool(kv_cache), int(n_slots)
+        self.max_rows = max_rows
         h = ctypes.c_void_p()
-        if n_slots != 1:
+        if max_rows is not None:
+            # a row budget for step_varlen (qgemm_decoder_create_rows): create_slots with larger scratch buffers
+            assert causal and kv_cache, "max_rows belongs to causal=True, kv_cache=True"
+            _check("qgemm_decoder_create_rows",
+                   load().qgemm_decoder_create_rows(d_model, n_heads, d_ff, n_blocks, max_seq, max_enc_seq, seed,
+                                                    QGEMM_DECODER_CAUSAL | QGEMM_DECODER_KV_CACHE, n_slots,
+                                                    int(max_rows), ctypes.byref(h)))
+        elif n_slots != 1:
             # cache slots (qgemm_decoder_create_slots): n_slots sequences on one copy of the weights
             assert causal and kv_cache, "n_slots belongs to causal=True, kv_cache=True"
             _check("qgemm_decoder_create_slots",
@@ -1136,6 +1267,30 @@ class Decoder:
         _check("qgemm_decoder_step_batch",
                load().qgemm_decoder_step_batch(self._h, n, _int_array(slots, n, "slots"), _int_array(pos, n, "pos"),
                                                rows_per_seq, X_new.data_ptr(), Y.data_ptr(), _stream(X_new.device)))
+        return Y
+
+    def step_varlen(self, slots, X_new, n_rows, pos=None, Y=None):
+        """One step of len(slots) sequences with their own row counts (qgemm_decoder_step_varlen): X_new holds the new
+        rows packed one after another, n_rows[b] >= 1 of them for slot slots[b] at positions pos[b] .. (pos defaults to
+        every slot's filled length) -- a prefill of many slots, or prefills mixed with decoding rows.  The rows of Y
+        are, bit for bit, what step_slot gives for each sequence alone."""
+        import torch
+        _require_device_f32(X_new, "X_new")
+        slots, n_rows = [int(v) for v in slots], [int(v) for v in n_rows]
+        n = len(slots)
+        assert len(n_rows) == n, "n_rows: one entry per slot"
+        assert X_new.is_contiguous() and X_new.shape == (sum(n_rows), self.d_model), \
+            "X_new: sum(n_rows) x d_model, contiguous"
+        if pos is None:
+            pos = [self.slot_filled(v) for v in slots]
+            assert None not in pos, "step_varlen() follows every slot's begin_slot()"
+        Y = torch.empty_like(X_new) if Y is None else Y
+        _require_device_f32(Y, "Y")
+        assert Y.is_contiguous() and Y.shape == X_new.shape
+        _check("qgemm_decoder_step_varlen",
+               load().qgemm_decoder_step_varlen(self._h, n, _int_array(slots, n, "slots"), _int_array(pos, n, "pos"),
+                                                _int_array(n_rows, n, "n_rows"), X_new.data_ptr(), Y.data_ptr(),
+                                                _stream(X_new.device)))
         return Y
 
     def copy_slot(self, dst: int, src: int):

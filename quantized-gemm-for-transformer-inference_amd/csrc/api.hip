@@ -6,6 +6,7 @@
 //   pack A  (Cx + X_int8)          -- op_mm.cuh:76-77, 82-83, 86-87
 //   pack B  (Cw + W_int8^T)        -- op_mm.cuh:78-79, 84-85, 88-89
 //   MFMA GEMM + dequant epilogue   -- op_mm.cuh:92-99
+#include <algorithm>
 #include <map>
 #include <mutex>
 #include <thread>
@@ -369,13 +370,25 @@ int qgemm_add_layernorm_rows(const float *A, const float *B, float *Y, int64_t r
     return err(launch_add_layernorm_rows(A, B, Y, rows, w, static_cast<hipStream_t>(stream)));
 }
 
-int qgemm_encoder_create(int d_model, int n_heads, int d_ff, int n_blocks, int max_seq, uint64_t seed,
-                         void **encoder) {
+int qgemm_encoder_create_rows(int d_model, int n_heads, int d_ff, int n_blocks, int max_seq, int max_rows,
+                              uint64_t seed, void **encoder) {
     if (!encoder) return err(hipErrorInvalidValue);
     Stack *E = nullptr;
-    hipError_t e = stack_create(d_model, n_heads, d_ff, n_blocks, max_seq, 0, seed, /*cross=*/false, false, false, &E);
+    hipError_t e = stack_create(d_model, n_heads, d_ff, n_blocks, max_seq, 0, seed, /*cross=*/false, false, false, &E, 1,
+                                max_rows);
     *encoder = E;
     return err(e);
+}
+
+int qgemm_encoder_create(int d_model, int n_heads, int d_ff, int n_blocks, int max_seq, uint64_t seed,
+                         void **encoder) {
+    return qgemm_encoder_create_rows(d_model, n_heads, d_ff, n_blocks, max_seq, 0, seed, encoder);
+}
+
+int qgemm_encoder_forward_batch(void *encoder, const float *X, float *Y, int n_seqs, const int *seq_lens,
+                                void *stream) {
+    return err(encoder_forward_batch(static_cast<Stack *>(encoder), X, Y, n_seqs, seq_lens,
+                                     static_cast<hipStream_t>(stream)));
 }
 
 int qgemm_encoder_forward(void *encoder, const float *X, float *Y, int seq, void *stream) {
@@ -423,6 +436,43 @@ int qgemm_attention_causal(const float *Q, int64_t q_stride_h, const float *K, i
                            scale, q_pos0, workspace, ws_bytes, stream);
 }
 
+// the largest single-call workspace over the sequences: 0 exactly when one table launch serves the call
+size_t qgemm_attention_varlen_workspace_size(int n_seqs, const int *seq_q, const int *seq_kv, int n_heads, int d_k) {
+    if (n_seqs < 0 || n_seqs > QGEMM_VARLEN_MAX_SEQS || !seq_q || !seq_kv) return 0;
+    size_t need = 0;
+    for (int b = 0; b < n_seqs; ++b)
+        need = std::max(need, qgemm_attention_workspace_size(seq_q[b], seq_kv[b], n_heads, d_k));
+    return need;
+}
+
+int qgemm_attention_varlen(const float *Q, int64_t q_stride_h, const float *K, int64_t k_stride_h, const float *V,
+                           int64_t v_stride_h, float *O, int64_t o_stride_h, int n_seqs, const int64_t *q_row0,
+                           const int *seq_q, const int64_t *kv_row0, const int *seq_kv, const int *q_pos0, int n_heads,
+                           int d_k, float scale, void *workspace, size_t ws_bytes, void *stream) {
+    static_assert(QGEMM_VARLEN_MAX_SEQS == kVarlenMaxSeqs, "the header's cap is the table's size");
+    if (!Q || !K || !V || !O || !q_row0 || !seq_q || !kv_row0 || !seq_kv || n_seqs < 0 ||
+        n_seqs > QGEMM_VARLEN_MAX_SEQS || n_heads < 1 || d_k < 1)
+        return err(hipErrorInvalidValue);
+    for (int b = 0; b < n_seqs; ++b)  // the sizes the workspace query reads, before it reads them
+        if (seq_q[b] < 0 || seq_kv[b] < 1 || seq_kv[b] > 4096) return err(hipErrorInvalidValue);
+    const size_t need = qgemm_attention_varlen_workspace_size(n_seqs, seq_q, seq_kv, n_heads, d_k);
+    if (need && (!workspace || ws_bytes < need)) return err(hipErrorInvalidValue);
+    return err(launch_attention_varlen(Q, q_stride_h, K, k_stride_h, V, v_stride_h, O, o_stride_h, n_seqs, q_row0, seq_q,
+                                       kv_row0, seq_kv, q_pos0, n_heads, d_k, scale,
+                                       need ? static_cast<float *>(workspace) : nullptr,
+                                       static_cast<hipStream_t>(stream)));
+}
+
+int qgemm_attention_varlen_plan(int n_seqs, const int *seq_q, const int *seq_kv, int n_heads, int d_k,
+                                const char **kernel) {
+    if (n_seqs < 0 || n_seqs > QGEMM_VARLEN_MAX_SEQS || !seq_q || !seq_kv || n_heads < 1 || d_k < 1)
+        return err(hipErrorInvalidValue);
+    for (int b = 0; b < n_seqs; ++b)
+        if (seq_q[b] < 0 || seq_kv[b] < 1 || seq_kv[b] > 4096) return err(hipErrorInvalidValue);
+    if (kernel) *kernel = attention_varlen_plan_name(n_seqs, seq_kv, d_k);
+    return 0;
+}
+
 int qgemm_decoder_create_ex(int d_model, int n_heads, int d_ff, int n_blocks, int max_seq, int max_enc_seq,
                             uint64_t seed, int flags, void **decoder) {
     if (!decoder) return err(hipErrorInvalidValue);
@@ -466,17 +516,29 @@ int qgemm_attention_decode_batched(const float *Q, int64_t q_stride_h, const flo
                                         static_cast<hipStream_t>(stream)));
 }
 
-int qgemm_decoder_create_slots(int d_model, int n_heads, int d_ff, int n_blocks, int max_seq, int max_enc_seq,
-                               uint64_t seed, int flags, int n_slots, void **decoder) {
+int qgemm_decoder_create_rows(int d_model, int n_heads, int d_ff, int n_blocks, int max_seq, int max_enc_seq,
+                              uint64_t seed, int flags, int n_slots, int max_rows, void **decoder) {
     if (!decoder) return err(hipErrorInvalidValue);
     *decoder = nullptr;
     if (flags != (QGEMM_DECODER_CAUSAL | QGEMM_DECODER_KV_CACHE) || n_slots < 1 || n_slots > QGEMM_DECODE_MAX_BATCH)
         return err(hipErrorInvalidValue);
     Stack *D = nullptr;
     hipError_t e = stack_create(d_model, n_heads, d_ff, n_blocks, max_seq, max_enc_seq, seed, /*cross=*/true, true, true,
-                                &D, n_slots);
+                                &D, n_slots, max_rows);
     *decoder = D;
     return err(e);
+}
+
+int qgemm_decoder_create_slots(int d_model, int n_heads, int d_ff, int n_blocks, int max_seq, int max_enc_seq,
+                               uint64_t seed, int flags, int n_slots, void **decoder) {
+    return qgemm_decoder_create_rows(d_model, n_heads, d_ff, n_blocks, max_seq, max_enc_seq, seed, flags, n_slots, 0,
+                                     decoder);
+}
+
+int qgemm_decoder_step_varlen(void *decoder, int n_seqs, const int *slots, const int *pos, const int *n_rows,
+                              const float *X, float *Y, void *stream) {
+    return err(decoder_step_varlen(static_cast<Stack *>(decoder), n_seqs, slots, pos, n_rows, X, Y,
+                                   static_cast<hipStream_t>(stream)));
 }
 
 int qgemm_decoder_begin_slot(void *decoder, int slot, const float *enc_out, int enc_seq, void *stream) {

@@ -19,6 +19,9 @@
 // Envelope: d_k <= 64, seq_kv <= 512, any seq_q (S tile 32 x 512 fp32 = 64 KiB of LDS, Q tile and K / V
 // staged through LDS in 256-key chunks: 155 KiB in all); outside it launch_attention (attention_launch.hip) runs the
 // three kernels.
+// The same kernel runs up to 64 independent sequences of their own lengths in one launch (FusedMany below, DESIGN.md
+// s19): a workgroup finds its (sequence, head, query tile) in a table in the kernel arguments and offsets its four
+// base pointers; everything after that is the single launch's workgroup.
 // kCausal: query row i sees keys 0 .. L_i - 1, L_i = min(seq_kv, i + q_pos0 + 1).  The softmax of
 // row i is softmax_rows_kernel's on a row of width L_i and P is +0 from column L_i on; P V still runs over all of
 // seq_kv (a masked key contributes fmaf(+0, v, acc), so 0 * inf is NaN as without a mask).  Q K^T tiles that lie
@@ -33,6 +36,7 @@ namespace {
 
 constexpr int kAttnMaxSeq = 512;
 constexpr int kAttnMaxDk = 64;
+constexpr int kFusedTQ = 32;               // query rows per workgroup of the library's tile configuration
 constexpr int kSStride = kAttnMaxSeq + 4;  // S row stride (floats): consecutive rows 4 banks apart
 constexpr int kKStride = 68;               // K chunk [key][d_k]: B-fragment reads (16 keys x 4 k) conflict-free
 constexpr int kVStride = 80;               // V chunk [key][d_k]: B-fragment reads (4 keys x 16 cols) conflict-free
@@ -54,10 +58,29 @@ struct AttnTile {
 
 typedef float v4f __attribute__((ext_vector_type(4)));
 
-template <int kTQ, int kChunk, int kThreads, bool kCausal>
+// The sequences of a launch, the kernel's last argument (by value), as DecodeOne / DecodeMany of
+// attention_decode.hip.  FusedOne: the single-sequence launch, grid (query tiles, heads).  FusedMany:
+// up to kVarlenMaxSeqs independent sequences of their own lengths, a one-dimensional grid of
+// sum_b ceil(seq_q[b] / kTQ) * n_heads workgroups.  Work item w (after the XCD remap) belongs to the sequence b with
+// item0[b] <= w < item0[b + 1]; inside it the items run head by head, a head's query tiles one after another, so the
+// tiles of one (sequence, head) are contiguous and share an XCD's L2 like a head's tiles in the single launch.
+// Sequence b's query and output rows start at row q_row0[b] of Q and O, its keys at row kv_row0[b] of K and V.
+// Everything is uniform per workgroup: scalar loads from the kernel arguments, nothing in device memory.
+// The single sequence's seq_q, seq_kv and q_pos0 stay plain kernel arguments, where they were before there was a table,
+// and FusedOne is empty: carried inside a by-value struct they reached the kernel through other loads, and hipcc
+// ordered this kernel's setup differently (it is sensitive to that, see the softmax max).  FusedMany overwrites the
+// three from its table, and the launcher passes zeros for them.
+struct FusedOne {};
+struct FusedMany {
+    int n_seqs;
+    FusedSeqTable tab;
+};
+static_assert(sizeof(FusedMany) + 80 < 4096, "the table travels in the kernel arguments");
+
+template <int kTQ, int kChunk, int kThreads, bool kCausal, typename Seqs>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))) void attention_fused_kernel(
     const float *__restrict__ Q, int64_t ldq, const float *__restrict__ K, int64_t ldk, const float *__restrict__ V,
-    int64_t ldv, float *__restrict__ O, int64_t ldo, int dk, int seq_q, int seq_kv, float scale, int q_pos0) {
+    int64_t ldv, float *__restrict__ O, int64_t ldo, int dk, int seq_q, int seq_kv, float scale, int q_pos0, Seqs seqs) {
     using T = AttnTile<kTQ, kChunk, kThreads>;
     constexpr int kAttnThreads = kThreads, kRF = T::kRowFrags;
     __shared__ __attribute__((aligned(16))) float S[kTQ * kSStride];
@@ -68,7 +91,31 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
     const int nwg = gridDim.x * gridDim.y, lin = blockIdx.y * gridDim.x + blockIdx.x;
     const int xq = nwg >> 3, xr = nwg & 7, xc = lin & 7;
     const int logical = (xc < xr ? xc * (xq + 1) : xr * (xq + 1) + (xc - xr) * xq) + (lin >> 3);
-    const int h = logical / gridDim.x, q0 = (logical - h * gridDim.x) * kTQ;
+    int h, q0;
+    if constexpr (std::is_same<Seqs, FusedMany>::value) {
+        // the last sequence whose first work item is at or below `logical` (an empty sequence shares its first item
+        // with the next one and is passed over): a wave-uniform binary search, at most 6 scalar loads
+        int b = 0, hi = seqs.n_seqs;
+        while (hi - b > 1) {
+            const int mid = (b + hi) >> 1;
+            if (seqs.tab.item0[mid] <= logical) b = mid;
+            else hi = mid;
+        }
+        seq_q = seqs.tab.seq_q[b];
+        seq_kv = seqs.tab.seq_kv[b];
+        q_pos0 = seqs.tab.q_pos0[b];
+        const int tiles = (seq_q + kTQ - 1) / kTQ, local = logical - seqs.tab.item0[b];
+        h = local / tiles;
+        q0 = (local - h * tiles) * kTQ;
+        const int64_t qr = seqs.tab.q_row0[b], kr = seqs.tab.kv_row0[b];
+        Q += qr * ldq;
+        O += qr * ldo;
+        K += kr * ldk;
+        V += kr * ldv;
+    } else {
+        h = logical / gridDim.x;
+        q0 = (logical - h * gridDim.x) * kTQ;
+    }
     const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const float *Qb = Q + (int64_t)h * dk, *Kb = K + (int64_t)h * dk, *Vb = V + (int64_t)h * dk;
     const int lr = lane & 15, lk = lane >> 4;  // MFMA operand lane: row lr of the fragment, k offset lk
@@ -320,15 +367,45 @@ hipError_t launch_attention_fused(const float *Q, int64_t ldq, const float *K, i
     if (n_heads < 1 || dk < 1 || seq_q < 0 || seq_kv < 1 || q_pos0 < kNoMask) return hipErrorInvalidValue;
     if (!attention_fused_ok(seq_kv, dk)) return hipErrorNotSupported;
     if (seq_q == 0) return hipSuccess;
-    constexpr int kTQ = 32;
+    constexpr int kTQ = kFusedTQ;
     const dim3 grid((unsigned)((seq_q + kTQ - 1) / kTQ), (unsigned)n_heads);
     if (q_pos0 == kNoMask)
-        attention_fused_kernel<kTQ, 256, 1024, false><<<grid, 1024, 0, stream>>>(Q, ldq, K, ldk, V, ldv, O, ldo, dk,
-                                                                                  seq_q, seq_kv, scale, 0);
+        attention_fused_kernel<kTQ, 256, 1024, false, FusedOne><<<grid, 1024, 0, stream>>>(
+            Q, ldq, K, ldk, V, ldv, O, ldo, dk, seq_q, seq_kv, scale, 0, FusedOne{});
     else  // past seq_kv - 1 the mask hides nothing: clamped, so the kernel's row limits cannot overflow
-        attention_fused_kernel<kTQ, 256, 1024, true><<<grid, 1024, 0, stream>>>(Q, ldq, K, ldk, V, ldv, O, ldo, dk,
-                                                                                 seq_q, seq_kv, scale,
-                                                                                 q_pos0 < seq_kv ? q_pos0 : seq_kv);
+        attention_fused_kernel<kTQ, 256, 1024, true, FusedOne><<<grid, 1024, 0, stream>>>(
+            Q, ldq, K, ldk, V, ldv, O, ldo, dk, seq_q, seq_kv, scale, q_pos0 < seq_kv ? q_pos0 : seq_kv, FusedOne{});
+    return hipGetLastError();
+}
+
+// tab.q_row0, kv_row0, seq_q, seq_kv and q_pos0 (clamped to seq_kv) come checked from launch_attention_varlen
+// (attention_launch.hip); the work map item0 is built HERE, where the tile height is known, and the envelope and the
+// ranges are tested again, where the kernel's LDS arrays and grid are sized
+hipError_t launch_attention_fused_many(const float *Q, int64_t ldq, const float *K, int64_t ldk, const float *V,
+                                       int64_t ldv, float *O, int64_t ldo, int n_seqs, const FusedSeqTable &tab,
+                                       bool causal, int n_heads, int dk, float scale, hipStream_t stream) {
+    if (n_seqs < 1 || n_seqs > kVarlenMaxSeqs || n_heads < 1 || dk < 1 || dk > kAttnMaxDk) return hipErrorInvalidValue;
+    FusedMany many;
+    many.n_seqs = n_seqs;
+    many.tab = tab;
+    int64_t items = 0;
+    for (int b = 0; b < n_seqs; ++b) {
+        if (tab.seq_q[b] < 0 || tab.seq_kv[b] < 1 || tab.seq_kv[b] > kAttnMaxSeq || tab.q_row0[b] < 0 ||
+            tab.kv_row0[b] < 0 || tab.q_pos0[b] < 0 || tab.q_pos0[b] > tab.seq_kv[b])
+            return hipErrorInvalidValue;
+        many.tab.item0[b] = (int)items;
+        items += (int64_t)((tab.seq_q[b] + kFusedTQ - 1) / kFusedTQ) * n_heads;
+        if (items > INT32_MAX) return hipErrorInvalidValue;
+    }
+    for (int b = n_seqs; b <= kVarlenMaxSeqs; ++b) many.tab.item0[b] = (int)items;
+    if (items == 0) return hipSuccess;
+    const dim3 grid((unsigned)items);
+    if (causal)
+        attention_fused_kernel<kFusedTQ, 256, 1024, true, FusedMany><<<grid, 1024, 0, stream>>>(
+            Q, ldq, K, ldk, V, ldv, O, ldo, dk, 0, 0, scale, 0, many);
+    else
+        attention_fused_kernel<kFusedTQ, 256, 1024, false, FusedMany><<<grid, 1024, 0, stream>>>(
+            Q, ldq, K, ldk, V, ldv, O, ldo, dk, 0, 0, scale, 0, many);
     return hipGetLastError();
 }
 

@@ -52,6 +52,56 @@ hipError_t launch_attention(const float *Q, int64_t ldq, const float *K, int64_t
                                  stream);
 }
 
+// one table launch serves a call exactly when every sequence lies inside the fused envelope (no sequence: vacuously)
+static bool varlen_fused_ok(int n_seqs, const int *seq_kv, int dk) {
+    for (int b = 0; b < n_seqs; ++b)
+        if (!attention_fused_ok(seq_kv[b], dk)) return false;
+    return attention_fused_ok(1, dk);
+}
+
+const char *attention_varlen_plan_name(int n_seqs, const int *seq_kv, int dk) {
+    return varlen_fused_ok(n_seqs, seq_kv, dk) ? "attention_fused_kernel<many>" : "per_sequence";
+}
+
+// The fused launch over a table of sequences (attention.hip, FusedMany): the host arrays are read HERE, into the table
+// that travels in the kernel arguments -- nothing is copied to the device, allocated or synchronized, and a captured
+// graph replays the values of the capture.  Every check comes before the first launch, on either path.  Rows of O
+// that two sequences share are the caller's error (not checked); Q, K and V rows may be shared.
+hipError_t launch_attention_varlen(const float *Q, int64_t ldq, const float *K, int64_t ldk, const float *V, int64_t ldv,
+                                   float *O, int64_t ldo, int n_seqs, const int64_t *q_row0, const int *seq_q,
+                                   const int64_t *kv_row0, const int *seq_kv, const int *q_pos0, int n_heads, int dk,
+                                   float scale, float *scores, hipStream_t stream) {
+    if (!Q || !K || !V || !O || !q_row0 || !seq_q || !kv_row0 || !seq_kv || n_seqs < 0 || n_seqs > kVarlenMaxSeqs ||
+        n_heads < 1 || dk < 1)
+        return hipErrorInvalidValue;
+    FusedSeqTable tab = {};  // entries past n_seqs are never read; zeroed so the arguments are defined bytes
+    bool need_scores = false;
+    for (int b = 0; b < n_seqs; ++b) {
+        if (q_row0[b] < 0 || kv_row0[b] < 0 || seq_q[b] < 0 || seq_kv[b] < 1 || seq_kv[b] > 4096 ||
+            (q_pos0 && q_pos0[b] < 0))
+            return hipErrorInvalidValue;
+        tab.q_row0[b] = q_row0[b];
+        tab.kv_row0[b] = kv_row0[b];
+        tab.seq_q[b] = seq_q[b];
+        tab.seq_kv[b] = seq_kv[b];
+        // past seq_kv - 1 the mask hides nothing: clamped, so the kernel's row limits cannot overflow
+        tab.q_pos0[b] = q_pos0 ? (q_pos0[b] < seq_kv[b] ? q_pos0[b] : seq_kv[b]) : 0;
+        need_scores = need_scores || (seq_q[b] > 0 && attention_needs_scores(seq_q[b], seq_kv[b], dk));
+    }
+    if (n_seqs == 0) return hipSuccess;
+    if (varlen_fused_ok(n_seqs, seq_kv, dk))
+        return launch_attention_fused_many(Q, ldq, K, ldk, V, ldv, O, ldo, n_seqs, tab, q_pos0 != nullptr, n_heads, dk,
+                                           scale, stream);
+    if (need_scores && !scores) return hipErrorInvalidValue;
+    for (int b = 0; b < n_seqs; ++b) {
+        const hipError_t e = launch_attention(Q + q_row0[b] * ldq, ldq, K + kv_row0[b] * ldk, ldk, V + kv_row0[b] * ldv,
+                                              ldv, O + q_row0[b] * ldo, ldo, seq_q[b], seq_kv[b], n_heads, dk, scale,
+                                              q_pos0 ? q_pos0[b] : kNoMask, scores, stream);
+        if (e) return e;
+    }
+    return hipSuccess;
+}
+
 // The decode launch over a batch of sequences (attention_decode.hip, DecodeMany): the host arrays are read HERE, into
 // the table that travels in the kernel arguments -- nothing is copied to the device, allocated or synchronized, and a
 // captured graph replays the values of the capture.  kv_slot == nullptr: slab b for sequence b; q_pos0 == nullptr: no

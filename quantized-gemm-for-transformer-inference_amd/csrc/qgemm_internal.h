@@ -362,7 +362,32 @@ hipError_t launch_attention_decode_batched(const float *Q, int64_t ldq, const fl
                                            const float *V, int64_t ldv, int64_t v_stride_seq, float *O, int64_t ldo,
                                            int n_seqs, int rows_per_seq, const DecodeBatchTable &tab, bool causal,
                                            int n_heads, int dk, float scale, hipStream_t stream);
+// The fused launch over a table of independent sequences of their own lengths (attention_fused_kernel<., FusedMany>,
+// DESIGN.md s19): sequence b has seq_q[b] query / output rows from row q_row0[b] of Q / O, seq_kv[b] keys from row
+// kv_row0[b] of K / V and mask offset q_pos0[b]; item0 is the work map, the first workgroup of each sequence, filled
+// by launch_attention_fused_many.  A kernel argument passed by value (2056 bytes): filled on the host at enqueue time,
+// never in device memory.
+constexpr int kVarlenMaxSeqs = 64;
+struct FusedSeqTable {
+    int64_t q_row0[kVarlenMaxSeqs], kv_row0[kVarlenMaxSeqs];
+    int seq_q[kVarlenMaxSeqs], seq_kv[kVarlenMaxSeqs], q_pos0[kVarlenMaxSeqs], item0[kVarlenMaxSeqs + 1];
+};
+// tab already checked and clamped (every seq_kv[b] <= 512, q_pos0[b] <= seq_kv[b]); causal = false ignores q_pos0;
+// sequences with seq_q[b] == 0 get no workgroup
+hipError_t launch_attention_fused_many(const float *Q, int64_t ldq, const float *K, int64_t ldk, const float *V,
+                                       int64_t ldv, float *O, int64_t ldo, int n_seqs, const FusedSeqTable &tab,
+                                       bool causal, int n_heads, int dk, float scale, hipStream_t stream);
 // Attention dispatch (attention_launch.hip).
+// Many sequences of different lengths from host arrays of n_seqs entries (q_pos0 nullptr: no mask), read at enqueue
+// time: ONE launch_attention_fused_many where d_k <= 64 and every seq_kv[b] <= 512, else launch_attention sequence by
+// sequence in order through `scores` (the largest n_heads x seq_q[b] x seq_kv[b] floats of a sequence outside the
+// fused envelope).  hipErrorInvalidValue before any launch outside 0 <= n_seqs <= 64, row offsets >= 0, seq_q[b] >= 0,
+// 1 <= seq_kv[b] <= 4096, q_pos0[b] >= 0, n_heads, d_k >= 1.  Sequence b's rows of O are launch_attention's on its views.
+const char *attention_varlen_plan_name(int n_seqs, const int *seq_kv, int dk);
+hipError_t launch_attention_varlen(const float *Q, int64_t ldq, const float *K, int64_t ldk, const float *V, int64_t ldv,
+                                   float *O, int64_t ldo, int n_seqs, const int64_t *q_row0, const int *seq_q,
+                                   const int64_t *kv_row0, const int *seq_kv, const int *q_pos0, int n_heads, int dk,
+                                   float scale, float *scores, hipStream_t stream);
 // the batched decode launch from host arrays of n_seqs entries (kv_slot nullptr: 0, 1, 2, ..; q_pos0 nullptr: no mask):
 // hipErrorInvalidValue before any launch outside n_seqs <= 64, 1 <= rows_per_seq <= 8, 1 <= d_k <= 64,
 // 1 <= seq_kv[b] <= 4096, q_pos0[b] >= 0, kv_slot[b] >= 0; n_seqs == 0 launches nothing
@@ -417,9 +442,10 @@ struct Stack;
 uint64_t encoder_weight_seed(uint64_t base, int block, int kind, int head);
 float encoder_init_bound(int n);
 // max_enc_seq, causal and kv_cache count only with cross; n_slots (1 .. kDecodeMaxBatch, > 1 only with kv_cache) is
-// the number of sequences the caches hold
+// the number of sequences the caches hold; max_rows (0: none) raises the rows the scratch buffers hold
+// for encoder_forward_batch / decoder_step_varlen, refused where a row-local index could leave int32
 hipError_t stack_create(int d_model, int n_heads, int d_ff, int n_blocks, int max_seq, int max_enc_seq, uint64_t seed,
-                        bool cross, bool causal, bool kv_cache, Stack **out, int n_slots = 1);
+                        bool cross, bool causal, bool kv_cache, Stack **out, int n_slots = 1, int max_rows = 0);
 void stack_destroy(Stack *S);
 hipError_t encoder_forward(Stack *S, const float *X, float *Y, int seq, hipStream_t s);
 // begin / step of one cache slot (qgemm_decoder_begin / qgemm_decoder_step are slot 0's)
@@ -428,6 +454,11 @@ hipError_t decoder_step_slot(Stack *S, int slot, const float *X, float *Y, int p
 // one step of n_seqs sequences, rows_per_seq rows each: rows b * r .. of X / Y at positions pos[b] .. of slot slots[b]
 hipError_t decoder_step_batch(Stack *S, int n_seqs, const int *slots, const int *pos, int rows_per_seq, const float *X,
                               float *Y, hipStream_t s);
+// n_seqs sequences of seq_lens[b] rows, packed one after another in X / Y: each one's rows are encoder_forward's
+hipError_t encoder_forward_batch(Stack *S, const float *X, float *Y, int n_seqs, const int *seq_lens, hipStream_t s);
+// step_batch with n_rows[b] >= 1 rows per sequence, rows packed one after another: each one's rows are step_slot's
+hipError_t decoder_step_varlen(Stack *S, int n_seqs, const int *slots, const int *pos, const int *n_rows, const float *X,
+                               float *Y, hipStream_t s);
 hipError_t decoder_copy_slot(Stack *S, int dst, int src, hipStream_t s);
 hipError_t decoder_slot_state(const Stack *S, int slot, int *enc_seq, int *filled);
 hipError_t decoder_forward(Stack *S, const float *X, const float *enc_out, float *Y, int seq, int enc_seq,

@@ -67,7 +67,18 @@
 // operands -- the K / V rows of the slab are the same values whether a GEMM or the scatter stored them.
 // The scratch buffers, the packed activations and the split-K scratch hold max(max_seq, 8 * n_slots) rows with more
 // than one slot.  decoder_copy_slot forks a sequence with stream-ordered device-to-device copies of the rows in use.
+//
+// Many sequences of different lengths at once (qgemm_*_create_rows).  By argument (1) the rows of B
+// sequences can run through one pass of the blocks as ONE matrix; the attention alone must know where a sequence ends,
+// and launch_attention_varlen (attention_launch.hip) does: one launch of the fused kernel over a table of sequences
+// where every one has at most 512 keys, else sequence by sequence.
+//   encoder_forward_batch  forward on sequences packed one after another: keys and queries in the qkv scratch;
+//   decoder_step_varlen    step_batch with n_rows[b] >= 1 rows per sequence (a prefill of many slots, or prefills mixed
+//                          with decoding rows): the scatter takes per-sequence row counts, keys in the slabs.
+// Each sequence's rows are forward's / step_slot's on it alone, bit for bit.  The scratch buffers hold
+// max(the above, max_rows) rows; the scores stay sized by max_seq (the per-sequence path runs one sequence at a time).
 #include <cmath>
+#include <cstdint>
 #include <new>
 #include <vector>
 
@@ -105,7 +116,7 @@ struct Stack {
     bool causal = false;    // the self-attention masks keys past the query's own row (QGEMM_DECODER_CAUSAL)
     bool kv_cache = false;  // the blocks own caches for decoder_begin / decoder_step (QGEMM_DECODER_KV_CACHE)
     int n_slots = 1;        // sequences the caches hold side by side (qgemm_decoder_create_slots)
-    int scratch_rows = 0;   // rows the scratch buffers hold: max_seq, or 8 rows of every slot if that is more
+    int scratch_rows = 0;   // rows the scratch buffers hold: max_seq, 8 rows of every slot or max_rows, the largest
     // per slot, host side, updated at enqueue time: enc_seq of the sequence begun (0: no begin yet) and the filled
     // length (cache rows 0 .. filled - 1 hold the sequence so far)
     std::vector<int> enc_seq, filled;
@@ -188,8 +199,15 @@ void stack_destroy(Stack *S) {
 }
 
 hipError_t stack_create(int d_model, int n_heads, int d_ff, int n_blocks, int max_seq, int max_enc_seq, uint64_t seed,
-                        bool cross, bool causal, bool kv_cache, Stack **out, int n_slots) {
+                        bool cross, bool causal, bool kv_cache, Stack **out, int n_slots, int max_rows) {
     *out = nullptr;
+    // max_rows: the row-local kernels (pack, GEMM epilogue, add + layernorm) address an activation buffer of
+    // scratch_rows x 3 d_model or x d_ff floats and its packed image of rows padded to 256 x columns padded to 128;
+    // with that padded product inside int32 no element index leaves its type, whichever type a kernel forms it in
+    if (max_rows < 0) return hipErrorInvalidValue;
+    if (max_rows > 0 && d_model >= 2 && d_ff >= 2 &&
+        (((int64_t)max_rows + 255) & ~(int64_t)255) * (((int64_t)std::max(3 * (int64_t)d_model, (int64_t)d_ff) + 127) & ~(int64_t)127) > INT32_MAX)
+        return hipErrorInvalidValue;
     if (kv_cache && !causal) return hipErrorInvalidValue;
     if (n_slots < 1 || n_slots > kDecodeMaxBatch || (n_slots > 1 && !(cross && kv_cache))) return hipErrorInvalidValue;
     if (d_model < 2 || n_heads < 1 || d_model % n_heads || d_ff < 2 || n_blocks < 1 || max_seq < 1 || max_seq > 4096 ||
@@ -208,7 +226,8 @@ hipError_t stack_create(int d_model, int n_heads, int d_ff, int n_blocks, int ma
     S->kv_cache = kv_cache;
     S->n_slots = n_slots;
     // a batched step runs up to 8 rows of every slot through the scratch buffers (one slot: a step's rows fit max_seq)
-    S->scratch_rows = n_slots > 1 ? std::max(max_seq, 8 * n_slots) : max_seq;
+    // and a batched forward or a varlen step its row budget (qgemm_*_create_rows)
+    S->scratch_rows = std::max(n_slots > 1 ? std::max(max_seq, 8 * n_slots) : max_seq, max_rows);
     S->enc_seq.assign(n_slots, 0);
     S->filled.assign(n_slots, 0);
     S->blocks.resize(n_blocks);
@@ -285,15 +304,21 @@ hipError_t stack_create(int d_model, int n_heads, int d_ff, int n_blocks, int ma
 
 namespace {
 
-// The new [K | V] of a batched step into the caches: block (i, b) copies columns d .. 3d - 1 of row b * r + i of the
-// step's [Q | K | V] scratch into row pos[b] + i of slab slot[b] (tab.q_pos0 = pos, tab.kv_slot = slot), as float4
-// where d % 4 == 0 (then every row and third of both buffers is 16-byte aligned), else float by float.  The Q third of
-// those cache rows is not written.
+// The new [K | V] of a batched or varlen step into the caches: block (i, b) with i < tab.n_rows[b] copies columns
+// d .. 3d - 1 of row tab.row0[b] + i of the step's [Q | K | V] scratch into row tab.pos[b] + i of slab tab.slot[b], as
+// float4 where d % 4 == 0 (then every row and third of both buffers is 16-byte aligned), else float by float.  The Q
+// third of those cache rows is not written.  The grid's x extent is the largest row count; a batched step has the same
+// count for every sequence, so no block of it is idle.
+struct ScatterTable {
+    int slot[kDecodeMaxBatch], pos[kDecodeMaxBatch], row0[kDecodeMaxBatch], n_rows[kDecodeMaxBatch];
+};
+
 __global__ __launch_bounds__(256) void scatter_kv_kernel(const float *__restrict__ qkv, float *__restrict__ cache,
-                                                         int64_t slab_rows, int d, DecodeBatchTable tab) {
+                                                         int64_t slab_rows, int d, ScatterTable tab) {
     const int i = blockIdx.x, b = blockIdx.y;
-    const float *src = qkv + ((int64_t)b * gridDim.x + i) * 3 * d + d;
-    float *dst = cache + ((int64_t)tab.kv_slot[b] * slab_rows + tab.q_pos0[b] + i) * 3 * d + d;
+    if (i >= tab.n_rows[b]) return;
+    const float *src = qkv + ((int64_t)tab.row0[b] + i) * 3 * d + d;
+    float *dst = cache + ((int64_t)tab.slot[b] * slab_rows + tab.pos[b] + i) * 3 * d + d;
     if ((d & 3) == 0) {
         for (int c = threadIdx.x; c < d / 2; c += blockDim.x)
             reinterpret_cast<float4 *>(dst)[c] = reinterpret_cast<const float4 *>(src)[c];
@@ -302,14 +327,19 @@ __global__ __launch_bounds__(256) void scatter_kv_kernel(const float *__restrict
     }
 }
 
-// slab_rows: rows of one slab of `cache`; the destination rows are checked to lie inside their slabs
-hipError_t launch_scatter_kv(const float *qkv, float *cache, int64_t slab_rows, int d, int n_seqs, int rows_per_seq,
-                             const DecodeBatchTable &tab, hipStream_t s) {
-    if (!qkv || !cache || d < 1 || n_seqs < 1 || n_seqs > kDecodeMaxBatch || rows_per_seq < 1) return hipErrorInvalidValue;
-    for (int b = 0; b < n_seqs; ++b)  // every destination row inside its slab
-        if (tab.kv_slot[b] < 0 || tab.q_pos0[b] < 0 || tab.q_pos0[b] > slab_rows - rows_per_seq)
+// slab_rows: rows of one slab of `cache`, n_slabs of them; scratch_rows: rows of `qkv`.  Every source row is checked
+// to lie inside the scratch and every destination row inside its slab
+hipError_t launch_scatter_kv(const float *qkv, int64_t scratch_rows, float *cache, int64_t slab_rows, int n_slabs, int d,
+                             int n_seqs, const ScatterTable &tab, hipStream_t s) {
+    if (!qkv || !cache || d < 1 || n_seqs < 1 || n_seqs > kDecodeMaxBatch) return hipErrorInvalidValue;
+    int max_n = 0;
+    for (int b = 0; b < n_seqs; ++b) {
+        if (tab.slot[b] < 0 || tab.slot[b] >= n_slabs || tab.n_rows[b] < 1 || tab.pos[b] < 0 ||
+            tab.pos[b] > slab_rows - tab.n_rows[b] || tab.row0[b] < 0 || tab.row0[b] > scratch_rows - tab.n_rows[b])
             return hipErrorInvalidValue;
-    scatter_kv_kernel<<<dim3((unsigned)rows_per_seq, (unsigned)n_seqs), 256, 0, s>>>(qkv, cache, slab_rows, d, tab);
+        max_n = std::max(max_n, tab.n_rows[b]);
+    }
+    scatter_kv_kernel<<<dim3((unsigned)max_n, (unsigned)n_seqs), 256, 0, s>>>(qkv, cache, slab_rows, d, tab);
     return hipGetLastError();
 }
 
@@ -318,6 +348,19 @@ struct BatchStep {
     int n_seqs, rows_per_seq;
     DecodeBatchTable self;   // kv_slot = the slot, seq_kv = pos + rows_per_seq, q_pos0 = pos
     DecodeBatchTable cross;  // kv_slot = the slot, seq_kv = the slot's enc_seq, no mask
+    ScatterTable scatter;    // slot, pos, row0 = b * rows_per_seq, n_rows = rows_per_seq
+};
+
+// The sequences of a batched forward (encoder_forward_batch) or a varlen step (decoder_step_varlen), DESIGN.md s19:
+// sequence b's rows are row0[b] .. row0[b] + n_rows[b] - 1 of every row buffer (prefix sums: packed one after another).
+// Forward: its keys are its own rows of the [Q | K | V] scratch (self_kv_row0 = row0, self_seq_kv = n_rows, no mask in
+// an encoder).  Step: its keys are rows 0 .. pos + n - 1 of its slot's slab (self_kv_row0 = slot * max_seq, self_pos0 =
+// pos), the cross keys the slot's cross slab (cross_kv_row0 = slot * max_enc_seq, cross_seq_kv = its enc_seq).
+struct VarlenStep {
+    int n_seqs;
+    int64_t row0[kVarlenMaxSeqs], self_kv_row0[kVarlenMaxSeqs], cross_kv_row0[kVarlenMaxSeqs];
+    int n_rows[kVarlenMaxSeqs], self_seq_kv[kVarlenMaxSeqs], self_pos0[kVarlenMaxSeqs], cross_seq_kv[kVarlenMaxSeqs];
+    ScatterTable scatter;  // a step's: slot, pos, row0, n_rows
 };
 
 // One pass over the blocks on `rows` rows, for forward (cached = false: the rows are the whole sequence, [Q | K | V]
@@ -326,8 +369,12 @@ struct BatchStep {
 // block's cache slab `slot` and attend to its rows 0 .. pos + rows - 1, [K2 | V2] is the slot's cross cache) and for
 // a step of many (batch != nullptr, with cached: rows = n_seqs * rows_per_seq, [Q | K | V] of all rows into the
 // scratch, their [K | V] scattered into the slots' slabs, both attentions one batched launch over the slabs).
+// var != nullptr (without batch): the rows are those of var->n_seqs sequences of their own lengths, one after another;
+// every row-local step runs on all of them at once and both attentions go through launch_attention_varlen -- a
+// batched forward (cached = false: keys in the scratch) or a varlen step (cached = true: [K | V] scattered into the
+// slabs as in a batched step, keys in the slabs).
 hipError_t run_blocks(Stack *S, const float *X, float *Y, int rows, int enc_seq, bool cached, int slot, int pos,
-                      const BatchStep *batch, hipStream_t s) {
+                      const BatchStep *batch, hipStream_t s, const VarlenStep *var = nullptr) {
     const int d = S->d_model, H = S->n_heads, dk = d / H;
     const int seq = rows;
     const int64_t self_slab = (int64_t)S->max_seq * 3 * d, cross_slab = (int64_t)S->max_enc_seq * 2 * d;  // floats
@@ -341,7 +388,7 @@ hipError_t run_blocks(Stack *S, const float *X, float *Y, int rows, int enc_seq,
         const bool last = i == S->n_blocks - 1;
         float *out = last ? Y : (i % 2 ? S->xb : S->xa);
         // ---- self-attention on the block input: [Q | K | V] = in @ [Wq | Wk | Wv] over all heads
-        const bool to_cache = cached && !batch;                                 // the GEMM writes the cache rows itself
+        const bool to_cache = cached && !batch && !var;                         // the GEMM writes the cache rows itself
         float *qkv = to_cache ? B.qkv_cache + slot * self_slab : S->qkv;        // row 0 of [Q | K | V]
         float *qrows = qkv + (size_t)(to_cache ? pos : 0) * 3 * d;              // the rows this call projects
         if ((e = linear(*S, in_packed ? nullptr : in, seq, d, B.wqkv, 3 * d, qrows, nullptr, false, s))) return e;
@@ -349,13 +396,25 @@ hipError_t run_blocks(Stack *S, const float *X, float *Y, int rows, int enc_seq,
         // (causal: row i sees rows 0 .. i, so row i of the forward depends on rows 0 .. i of X alone)
         if (batch) {
             // sequence b's rows see its slot's cache rows 0 .. pos[b] + r - 1, the last r of them scattered here
-            if ((e = launch_scatter_kv(qkv, B.qkv_cache, S->max_seq, d, batch->n_seqs, batch->rows_per_seq, batch->self,
-                                       s)))
+            if ((e = launch_scatter_kv(qkv, S->scratch_rows, B.qkv_cache, S->max_seq, S->n_slots, d, batch->n_seqs,
+                                       batch->scatter, s)))
                 return e;
             if ((e = launch_attention_decode_batched(qkv, 3 * d, B.qkv_cache + d, 3 * d, self_slab,
                                                      B.qkv_cache + 2 * d, 3 * d, self_slab, S->heads, d, batch->n_seqs,
                                                      batch->rows_per_seq, batch->self, /*causal=*/true, H, dk, scale,
                                                      s)))
+                return e;
+        } else if (var) {
+            // a step's sequences see their slots' cache rows, the new ones scattered here; a forward's their own rows
+            // of the scratch
+            if (cached && (e = launch_scatter_kv(qkv, S->scratch_rows, B.qkv_cache, S->max_seq, S->n_slots, d,
+                                                 var->n_seqs, var->scatter, s)))
+                return e;
+            const float *kv = cached ? B.qkv_cache : qkv;
+            if ((e = launch_attention_varlen(qkv, 3 * d, kv + d, 3 * d, kv + 2 * d, 3 * d, S->heads, d, var->n_seqs,
+                                             var->row0, var->n_rows, var->self_kv_row0, var->self_seq_kv,
+                                             cached || S->causal ? var->self_pos0 : nullptr, H, dk, scale, S->scores,
+                                             s)))
                 return e;
         } else if ((e = launch_attention(qrows, 3 * d, qkv + d, 3 * d, qkv + 2 * d, 3 * d, S->heads, d, seq,
                                          cached ? pos + seq : seq, H, dk, scale,
@@ -376,6 +435,11 @@ hipError_t run_blocks(Stack *S, const float *X, float *Y, int rows, int enc_seq,
                 if ((e = launch_attention_decode_batched(S->q2, d, B.kv2_cache, 2 * d, cross_slab, B.kv2_cache + d, 2 * d,
                                                          cross_slab, mho, d, batch->n_seqs, batch->rows_per_seq,
                                                          batch->cross, /*causal=*/false, H, dk, scale, s)))
+                    return e;
+            } else if (var) {
+                if ((e = launch_attention_varlen(S->q2, d, B.kv2_cache, 2 * d, B.kv2_cache + d, 2 * d, mho, d, var->n_seqs,
+                                                 var->row0, var->n_rows, var->cross_kv_row0, var->cross_seq_kv, nullptr,
+                                                 H, dk, scale, S->scores, s)))
                     return e;
             } else if ((e = launch_attention(S->q2, d, kv2, 2 * d, kv2 + d, 2 * d, mho, d, seq, enc_seq, H, dk, scale,
                                              kNoMask, S->scores, s)))
@@ -407,6 +471,23 @@ hipError_t pack_enc(Stack *S, const float *enc_out, int enc_seq, hipStream_t s) 
 hipError_t encoder_forward(Stack *S, const float *X, float *Y, int seq, hipStream_t s) {
     if (!S || S->cross || !X || !Y || seq < 1 || seq > S->max_seq) return hipErrorInvalidValue;
     return run_blocks(S, X, Y, seq, 0, /*cached=*/false, 0, 0, nullptr, s);
+}
+
+// X and Y: the sequences' rows packed one after another.  Every row-local step of run_blocks sees one matrix of
+// sum seq_lens rows; the self-attention alone knows where a sequence ends
+hipError_t encoder_forward_batch(Stack *S, const float *X, float *Y, int n_seqs, const int *seq_lens, hipStream_t s) {
+    if (!S || S->cross || !X || !Y || !seq_lens || n_seqs < 1 || n_seqs > kVarlenMaxSeqs) return hipErrorInvalidValue;
+    VarlenStep vs = {};
+    vs.n_seqs = n_seqs;
+    int64_t rows = 0;
+    for (int b = 0; b < n_seqs; ++b) {
+        if (seq_lens[b] < 1 || seq_lens[b] > S->max_seq) return hipErrorInvalidValue;
+        vs.row0[b] = vs.self_kv_row0[b] = rows;
+        vs.n_rows[b] = vs.self_seq_kv[b] = seq_lens[b];
+        rows += seq_lens[b];
+    }
+    if (rows > S->scratch_rows) return hipErrorInvalidValue;
+    return run_blocks(S, X, Y, (int)rows, 0, /*cached=*/false, 0, 0, nullptr, s, &vs);
 }
 
 hipError_t decoder_forward(Stack *S, const float *X, const float *enc_out, float *Y, int seq, int enc_seq,
@@ -466,11 +547,51 @@ hipError_t decoder_step_batch(Stack *S, int n_seqs, const int *slots, const int 
         bs.self.seq_kv[b] = pos[b] + r;
         bs.self.q_pos0[b] = pos[b];
         bs.cross.seq_kv[b] = S->enc_seq[sl];
+        bs.scatter.slot[b] = sl;
+        bs.scatter.pos[b] = pos[b];
+        bs.scatter.row0[b] = b * r;
+        bs.scatter.n_rows[b] = r;
     }
     // (n_seqs * r <= scratch_rows: n_seqs <= n_slots, and r <= max_seq with one slot)
     const hipError_t e = run_blocks(S, X, Y, n_seqs * r, 0, /*cached=*/true, 0, 0, &bs, s);
     if (e) return e;
     for (int b = 0; b < n_seqs; ++b) S->filled[slots[b]] = pos[b] + r;
+    return hipSuccess;
+}
+
+// step_batch without its 8-row, equal-rows limits: sequence b appends n_rows[b] rows (rows sum_{b' < b} n_rows[b'] ..
+// of X / Y) at pos[b] of slot slots[b].  Every check comes before the first launch; `filled` is updated at enqueue.
+hipError_t decoder_step_varlen(Stack *S, int n_seqs, const int *slots, const int *pos, const int *n_rows, const float *X,
+                               float *Y, hipStream_t s) {
+    if (!S || !S->cross || !S->kv_cache || !slots || !pos || !n_rows || !X || !Y || n_seqs < 1 || n_seqs > S->n_slots)
+        return hipErrorInvalidValue;
+    VarlenStep vs = {};
+    vs.n_seqs = n_seqs;
+    uint64_t seen = 0;  // n_slots <= 64
+    int64_t rows = 0;
+    for (int b = 0; b < n_seqs; ++b) {
+        const int sl = slots[b], n = n_rows[b];
+        if (sl < 0 || sl >= S->n_slots || S->enc_seq[sl] < 1 || (seen >> sl & 1) || n < 1 || pos[b] < 0 ||
+            pos[b] > S->filled[sl] || n > S->max_seq - pos[b])
+            return hipErrorInvalidValue;
+        seen |= (uint64_t)1 << sl;
+        vs.row0[b] = rows;
+        vs.n_rows[b] = n;
+        vs.self_kv_row0[b] = (int64_t)sl * S->max_seq;
+        vs.self_seq_kv[b] = pos[b] + n;
+        vs.self_pos0[b] = pos[b];
+        vs.cross_kv_row0[b] = (int64_t)sl * S->max_enc_seq;
+        vs.cross_seq_kv[b] = S->enc_seq[sl];
+        vs.scatter.slot[b] = sl;
+        vs.scatter.pos[b] = pos[b];
+        vs.scatter.row0[b] = (int)rows;
+        vs.scatter.n_rows[b] = n;
+        rows += n;
+        if (rows > S->scratch_rows) return hipErrorInvalidValue;
+    }
+    const hipError_t e = run_blocks(S, X, Y, (int)rows, 0, /*cached=*/true, 0, 0, nullptr, s, &vs);
+    if (e) return e;
+    for (int b = 0; b < n_seqs; ++b) S->filled[slots[b]] = pos[b] + n_rows[b];
     return hipSuccess;
 }
 
