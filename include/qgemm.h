@@ -420,6 +420,83 @@ QGEMM_API int qgemm_decoder_create_rows(int d_model, int n_heads, int d_ff, int 
 QGEMM_API int qgemm_decoder_step_varlen(void *decoder, int n_seqs, const int *slots, const int *pos, const int *n_rows,
                               const float *X, float *Y, void *stream);
 
+/* ---- The output end: argmax, token embedding, vocabulary head, greedy generation --------
+ * None of the entry points below allocates (qgemm_head_create / _destroy apart), synchronizes or copies anything to
+ * the device: host arrays travel in kernel arguments, so each call can be captured in a graph, which then replays the
+ * values of the capture.  Invalid arguments return hipErrorInvalidValue before any launch.
+ *
+ * qgemm_argmax_rows: row-wise argmax with the reference's op_argmax semantics for an [h x 1] index output
+ * (op_reduction.cuh:41-54, 174-182).  S: rows of w floats, unit inner stride, row stride s_stride_h >= w floats;
+ * idx: int32[rows]; val: float[rows] or NULL.  Per row the reference's chain:
+ *   best = 0; for i = 1 .. w-1: if (S[i] > S[best]) best = i;     idx = best, val = the bits of S[best]
+ * so among equal maxima the lowest index wins (+0 and -0 are equal), a NaN at i >= 1 never wins, and a NaN at column 0
+ * is never beaten (idx 0, val that NaN).  The reference's functor also writes the running maximum back into its input;
+ * here S is const and is not touched.  Nothing outside a row's w floats is read; 16-byte loads wherever base and
+ * stride allow, a scalar head and tail otherwise.
+ * With many rows it is one launch, one workgroup per row.  With fewer than 256 rows a wide row is split over `parts`
+ * workgroups (each at least 4096 columns, about 512 workgroups in all, parts <= 64) whose partial winners go through
+ * `workspace` to a second, combining launch; the result does not depend on the plan.  parts is chosen from rows and w
+ * alone: qgemm_argmax_rows_plan reports it (parts == 1 for rows >= 256, else parts * rows < 768; needs no GPU; part p
+ * covers columns p * chunk .. with chunk = ceil(w / parts) rounded up to a multiple of 4), and
+ * qgemm_argmax_rows_workspace_size is 8 * rows * parts bytes, 0 for parts == 1 (workspace may then be NULL) and for
+ * arguments the call refuses.
+ * hipErrorInvalidValue: a null S / idx, rows < 0, w < 1 or > 2^24, s_stride_h < w, a short or null workspace with
+ * parts > 1; rows == 0 returns 0 and touches nothing. */
+QGEMM_API size_t qgemm_argmax_rows_workspace_size(int64_t rows, int w);
+QGEMM_API int qgemm_argmax_rows_plan(int64_t rows, int w, int *parts);
+QGEMM_API int qgemm_argmax_rows(const float *S, int64_t s_stride_h, int64_t rows, int w, int32_t *idx, float *val,
+                      void *workspace, size_t ws_bytes, void *stream);
+/* qgemm_embed_rows: Y[r] = E[tokens[r]], or fl(E[tokens[r]] + P[p_r]) -- one fp32 add -- with a position table P
+ * (max_pos x d_model).  E: vocab x d_model; Y: (n_seqs * rows_per_seq) x d_model; E, P and Y have their own row
+ * strides in floats (>= d_model) and unit inner stride.  tokens: int32[n_seqs * rows_per_seq] in DEVICE memory.
+ * Positions follow step_batch's layout: row r belongs to sequence b = r / rows_per_seq and has position
+ * p_r = pos[b] + r % rows_per_seq; pos is a HOST array of n_seqs <= 64 ints, read at enqueue time (not read when
+ * P == NULL, and may then be NULL).
+ * A token outside [0, vocab) cannot be seen by the host: its row of Y is d_model quiet NaNs (0x7fc00000), nothing of E
+ * or P is read for it, and every other row stays right -- the error shows downstream and nothing faults.
+ * hipErrorInvalidValue: a null E / tokens / Y, vocab < 1, d_model < 1, a row stride below d_model, n_seqs < 0 or > 64,
+ * rows_per_seq < 1; with P: a null pos, max_pos < 1, pos[b] < 0 or pos[b] + rows_per_seq > max_pos.  n_seqs == 0
+ * returns 0. */
+QGEMM_API int qgemm_embed_rows(const float *E, int64_t e_stride_h, int vocab, int d_model, const int32_t *tokens,
+                     const float *P, int64_t p_stride_h, int max_pos, const int *pos, int n_seqs, int rows_per_seq,
+                     float *Y, int64_t y_stride_h, void *stream);
+/* The head object.  It BORROWS (the caller keeps them alive): packed_w, a d_model x vocab weight packed by
+ * qgemm_pack_b with range 127 (a tied head is the pack of E's transposed view: the pack takes strided views); bias
+ * (vocab floats) or NULL; E (vocab x d_model) or NULL; P (max_pos x d_model) or NULL (P needs E).  It OWNS, allocated at
+ * creation: a logits buffer of max_rows x vocab floats, two blocks of max_rows x d_model rows, and the workspaces of
+ * qgemm_linear and qgemm_argmax_rows for every row count up to max_rows.  One head does one thing at a time (its
+ * buffers are used in stream order).
+ *   logits       qgemm_linear(H, packed_w, bias, no relu) into the caller's `logits` (rows x vocab, row stride
+ *                l_stride_h), bit for bit.  H: rows x d_model, row stride h_stride_h, rows <= max_rows.
+ *   next_tokens  logits into the owned buffer, then qgemm_argmax_rows over the vocabulary: tokens int32[rows], device.
+ *   embed        qgemm_embed_rows on the head's tables (needs E).
+ * hipErrorInvalidValue: a null handle or pointer, d_model / vocab / max_rows < 1, vocab > 2^24, a row stride below its
+ * row, rows < 0 or > max_rows, embed on a head without E, and what qgemm_embed_rows refuses. */
+QGEMM_API int qgemm_head_create(const void *packed_w, int d_model, int vocab, const float *bias, const float *E,
+                      int64_t e_stride_h, const float *P, int64_t p_stride_h, int max_pos, int max_rows, void **head);
+QGEMM_API int qgemm_head_logits(void *head, const float *H, int64_t h_stride_h, int rows, float *logits,
+                      int64_t l_stride_h, void *stream);
+QGEMM_API int qgemm_head_next_tokens(void *head, const float *H, int64_t h_stride_h, int rows, int32_t *tokens,
+                           void *stream);
+QGEMM_API int qgemm_head_embed(void *head, const int32_t *tokens, const int *pos, int n_seqs, int rows_per_seq, float *Y,
+                     int64_t y_stride_h, void *stream);
+QGEMM_API int qgemm_head_destroy(void *head);
+/* Greedy decoding of n_seqs cache slots for n_new tokens, enqueued in ONE call with no host round trip.  With
+ * tok_0 = tokens_in (int32[n_seqs], device), for t = 0 .. n_new - 1:
+ *   X = head embed(tok_t, pos + t);  H = step_batch(slots, X, pos + t);  tok_{t+1} = head next_tokens(H)
+ * tok_{t+1} is row t of tokens_out (int32[n_new x n_seqs], device), and step t + 1's embed reads that row on the
+ * device.  So the tokens are, bit for bit, those of the same loop driven through qgemm_head_embed,
+ * qgemm_decoder_step_batch and qgemm_head_next_tokens.  pos: a host array of n_seqs ints, or NULL for the slots' filled
+ * lengths; an earlier pos rewinds, as in step_batch.  On success filled[slots[b]] = pos[b] + n_new.  It does not stop
+ * at an end token: the caller trims the output.  The head's row buffers and the decoder's scratch are used in stream
+ * order.
+ * hipErrorInvalidValue before any launch and without moving any filled length: a null pointer, a decoder without
+ * caches, a head without E or of another d_model, n_seqs < 1, > n_slots or > the head's max_rows, n_new < 0, a slot out
+ * of range, not begun or named twice, pos[b] < 0, pos[b] > filled, pos[b] + n_new > max_seq (or > the head's max_pos
+ * with a P), d_model / n_heads > 64 (step_batch).  n_new == 0 returns 0. */
+QGEMM_API int qgemm_decoder_generate(void *decoder, void *head, int n_seqs, const int *slots, const int32_t *tokens_in,
+                           int n_new, const int *pos, int32_t *tokens_out, void *stream);
+
 /* ---- LLM.int8() outlier decomposition ------------------------------------------
  * Feature columns k of A (= rows of B) holding an element with NOT(|x| <= threshold) (the reference's
  * AbsCompareLTEConstFunc, op_elemwise.cuh:293-306; NaN counts as an outlier) are multiplied in fp32,

@@ -88,6 +88,16 @@ EXPORTED_SYMBOLS = (
     "qgemm_encoder_forward_batch",
     "qgemm_decoder_create_rows",
     "qgemm_decoder_step_varlen",
+    "qgemm_argmax_rows_workspace_size",
+    "qgemm_argmax_rows_plan",
+    "qgemm_argmax_rows",
+    "qgemm_embed_rows",
+    "qgemm_head_create",
+    "qgemm_head_logits",
+    "qgemm_head_next_tokens",
+    "qgemm_head_embed",
+    "qgemm_head_destroy",
+    "qgemm_decoder_generate",
     "qgemm_mm_outlier_workspace_size",
     "qgemm_mm_outlier",
     "qgemm_outlier_count",
@@ -266,6 +276,26 @@ def load() -> ctypes.CDLL:
         L.qgemm_decoder_create_rows.restype = i32
         L.qgemm_decoder_step_varlen.argtypes = [vp, i32, ip, ip, ip, vp, vp, vp]
         L.qgemm_decoder_step_varlen.restype = i32
+        L.qgemm_argmax_rows_workspace_size.argtypes = [i64, i32]
+        L.qgemm_argmax_rows_workspace_size.restype = sz
+        L.qgemm_argmax_rows_plan.argtypes = [i64, i32, ip]
+        L.qgemm_argmax_rows_plan.restype = i32
+        L.qgemm_argmax_rows.argtypes = [vp, i64, i64, i32, vp, vp, vp, sz, vp]
+        L.qgemm_argmax_rows.restype = i32
+        L.qgemm_embed_rows.argtypes = [vp, i64, i32, i32, vp, vp, i64, i32, ip, i32, i32, vp, i64, vp]
+        L.qgemm_embed_rows.restype = i32
+        L.qgemm_head_create.argtypes = [vp, i32, i32, vp, vp, i64, vp, i64, i32, i32, ctypes.POINTER(vp)]
+        L.qgemm_head_create.restype = i32
+        L.qgemm_head_logits.argtypes = [vp, vp, i64, i32, vp, i64, vp]
+        L.qgemm_head_logits.restype = i32
+        L.qgemm_head_next_tokens.argtypes = [vp, vp, i64, i32, vp, vp]
+        L.qgemm_head_next_tokens.restype = i32
+        L.qgemm_head_embed.argtypes = [vp, vp, ip, i32, i32, vp, i64, vp]
+        L.qgemm_head_embed.restype = i32
+        L.qgemm_head_destroy.argtypes = [vp]
+        L.qgemm_head_destroy.restype = i32
+        L.qgemm_decoder_generate.argtypes = [vp, vp, i32, ip, vp, i32, ip, vp, vp]
+        L.qgemm_decoder_generate.restype = i32
         L.qgemm_mm_outlier_workspace_size.argtypes = [i32, i32, i32]
         L.qgemm_mm_outlier_workspace_size.restype = sz
         L.qgemm_mm_outlier.argtypes = [vp, vp, vp, i32, i32, i32, f32, vp, sz, vp]
@@ -1293,6 +1323,25 @@ class Decoder:
                                                 _stream(X_new.device)))
         return Y
 
+    def generate(self, head, slots, tokens_in, n_new: int, pos=None, tokens_out=None):
+        """Greedy decoding of the cache slots `slots` for n_new tokens in one enqueued call (qgemm_decoder_generate):
+        per step head.embed of the last tokens, step_batch, head.next_tokens, the tokens staying on the device.
+        tokens_in: int32[len(slots)] on the device; returns tokens_out, int32[n_new x len(slots)] on the device, row t
+        the tokens chosen at step t.  pos defaults to every slot's filled length, an earlier pos rewinds.  It does not
+        stop at an end token."""
+        import torch
+        slots = [int(v) for v in slots]
+        n = len(slots)
+        _require_device_i32(tokens_in, "tokens_in", n)
+        if tokens_out is None:
+            tokens_out = torch.empty((n_new, n), dtype=torch.int32, device=tokens_in.device)
+        _require_device_i32(tokens_out, "tokens_out", n_new * n)
+        _check("qgemm_decoder_generate",
+               load().qgemm_decoder_generate(self._h, head._h, n, _int_array(slots, n, "slots"), tokens_in.data_ptr(),
+                                             n_new, _int_array(pos, n, "pos"), tokens_out.data_ptr(),
+                                             _stream(tokens_in.device)))
+        return tokens_out
+
     def copy_slot(self, dst: int, src: int):
         """Fork a sequence (qgemm_decoder_copy_slot): slot dst continues slot src's sequence on its own."""
         _check("qgemm_decoder_copy_slot", load().qgemm_decoder_copy_slot(self._h, dst, src, _stream()))
@@ -1300,6 +1349,161 @@ class Decoder:
     def close(self):
         if getattr(self, "_h", None):
             load().qgemm_decoder_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _require_device_i32(t, name, count: int):
+    import torch
+    assert isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and t.is_contiguous(), \
+        f"{name}: a contiguous int32 device tensor"
+    assert t.numel() == count, f"{name}: {count} entries"
+
+
+def _require_rows_f32(t, name, cols=None):
+    """A 2-D fp32 device tensor or view with unit inner stride and a row stride of at least its width."""
+    _require_device_f32(t, name)
+    assert t.stride(1) == 1 or t.shape[1] == 1, f"{name} must have unit inner stride"
+    assert t.shape[0] <= 1 or t.stride(0) >= t.shape[1], f"{name}: the row stride covers a row"
+    assert cols is None or t.shape[1] == cols, f"{name}: {cols} columns"
+    return max(t.stride(0), t.shape[1])  # a one-row view may report any row stride
+
+
+def argmax_rows_plan(rows: int, w: int) -> int:
+    """The number of workgroups argmax_rows() gives each row (qgemm_argmax_rows_plan): 1, or more for few, wide rows.
+    Needs no GPU; raises QGemmError for rows < 0, w < 1 or w > 2**24."""
+    parts = ctypes.c_int()
+    _check("qgemm_argmax_rows_plan", load().qgemm_argmax_rows_plan(rows, w, ctypes.byref(parts)))
+    return parts.value
+
+
+def argmax_rows(S, idx=None, val=None):
+    """Row-wise argmax of a 2-D fp32 device tensor or view with unit inner stride (qgemm_argmax_rows), the reference's
+    op_argmax chain: the lowest index among equal maxima, a NaN past column 0 never wins, a NaN at column 0 is never
+    beaten.  Returns (idx, val): int32 indices and the winners' values, bit for bit.  S is not written."""
+    import torch
+    stride = _require_rows_f32(S, "S")
+    rows, w = S.shape
+    if idx is None:
+        idx = torch.empty(rows, dtype=torch.int32, device=S.device)
+    if val is None:
+        val = torch.empty(rows, dtype=torch.float32, device=S.device)
+    _require_device_i32(idx, "idx", rows)
+    assert val.is_cuda and val.dtype == torch.float32 and val.is_contiguous() and val.numel() == rows, "val: as idx"
+    L = load()
+    need = L.qgemm_argmax_rows_workspace_size(rows, w)
+    ws = torch.empty(need, dtype=torch.uint8, device=S.device) if need else None
+    _check("qgemm_argmax_rows", L.qgemm_argmax_rows(S.data_ptr(), stride, rows, w, idx.data_ptr(), val.data_ptr(),
+                                                    ws.data_ptr() if need else None, need, _stream(S.device)))
+    return idx, val
+
+
+def embed_rows(E, tokens, P=None, pos=None, rows_per_seq: int = 1, Y=None):
+    """Y[r] = E[tokens[r]] (+ P[pos[r // rows_per_seq] + r % rows_per_seq], one fp32 add): the token embedding gather
+    (qgemm_embed_rows).  tokens: int32 on the device, rows_per_seq per sequence; pos: one host int per sequence.  E, P
+    and Y may be row-strided views.  A token outside the vocabulary gives a row of quiet NaNs."""
+    import torch
+    es = _require_rows_f32(E, "E")
+    vocab, d = E.shape
+    assert isinstance(tokens, torch.Tensor), "tokens: an int32 device tensor"
+    rows = tokens.numel()
+    _require_device_i32(tokens, "tokens", rows)
+    assert rows_per_seq >= 1 and rows % rows_per_seq == 0, "tokens holds rows_per_seq entries per sequence"
+    n = rows // rows_per_seq
+    ps = 0
+    if P is not None:
+        ps = _require_rows_f32(P, "P", d)
+        assert pos is not None, "a position table needs pos"
+    if Y is None:
+        Y = torch.empty((rows, d), dtype=torch.float32, device=E.device)
+    ys = _require_rows_f32(Y, "Y", d)
+    assert Y.shape[0] == rows
+    _check("qgemm_embed_rows",
+           load().qgemm_embed_rows(E.data_ptr(), es, vocab, d, tokens.data_ptr(), None if P is None else P.data_ptr(),
+                                   ps, 0 if P is None else P.shape[0],
+                                   _int_array(pos if P is not None else None, n, "pos"), n, rows_per_seq, Y.data_ptr(),
+                                   ys, _stream(E.device)))
+    return Y
+
+
+class Head:
+    """The vocabulary head (qgemm_head_*): logits() is linear(H, pw, bias) onto the vocabulary, next_tokens() its
+    row-wise argmax, embed() the token (+ position) embedding that feeds the next decoder step -- what
+    Decoder.generate() chains on the device.  pw: a d_model x vocab weight packed by pack_b (a tied head:
+    pack_b(E.t())); bias, E (vocab x d_model) and P (max_pos x d_model) are optional.  The head keeps references to
+    them and owns its logits buffer, row buffers and workspaces for up to max_rows rows."""
+
+    def __init__(self, pw: Packed, vocab: int, bias=None, E=None, P=None, max_rows: int = 64):
+        import torch
+        assert pw.rows == vocab, "pw: d_model x vocab, packed by pack_b"
+        assert pw.range == DEFAULT_RANGE, f"the head needs a weight packed with range {DEFAULT_RANGE}"
+        self.d_model, self.vocab, self.max_rows = pw.k, vocab, int(max_rows)
+        es = ps = 0
+        if bias is not None:
+            assert bias.is_cuda and bias.dtype == torch.float32 and bias.is_contiguous() and bias.numel() == vocab
+        if E is not None:
+            es = _require_rows_f32(E, "E", self.d_model)
+            assert E.shape[0] == vocab, "E: vocab x d_model"
+        if P is not None:
+            assert E is not None, "a position table belongs to an embedding table"
+            ps = _require_rows_f32(P, "P", self.d_model)
+        self._keep = (pw, bias, E, P)  # borrowed by the C object
+        self.has_positions = P is not None
+        h = ctypes.c_void_p()
+        _check("qgemm_head_create",
+               load().qgemm_head_create(pw.buf.data_ptr(), self.d_model, vocab, None if bias is None else bias.data_ptr(),
+                                        None if E is None else E.data_ptr(), es, None if P is None else P.data_ptr(),
+                                        ps, 0 if P is None else P.shape[0], self.max_rows, ctypes.byref(h)))
+        self._h = h
+
+    def logits(self, H, out=None):
+        """linear(H, pw, bias) without relu, bit for bit (qgemm_head_logits): rows x vocab, fp32."""
+        import torch
+        hs = _require_rows_f32(H, "H", self.d_model)
+        if out is None:
+            out = torch.empty((H.shape[0], self.vocab), dtype=torch.float32, device=H.device)
+        os_ = _require_rows_f32(out, "out", self.vocab)
+        assert out.shape[0] == H.shape[0]
+        _check("qgemm_head_logits", load().qgemm_head_logits(self._h, H.data_ptr(), hs, H.shape[0], out.data_ptr(), os_,
+                                                            _stream(H.device)))
+        return out
+
+    def next_tokens(self, H, tokens=None):
+        """The argmax over the vocabulary of every row's logits (qgemm_head_next_tokens): int32 on the device."""
+        import torch
+        hs = _require_rows_f32(H, "H", self.d_model)
+        if tokens is None:
+            tokens = torch.empty(H.shape[0], dtype=torch.int32, device=H.device)
+        _require_device_i32(tokens, "tokens", H.shape[0])
+        _check("qgemm_head_next_tokens", load().qgemm_head_next_tokens(self._h, H.data_ptr(), hs, H.shape[0],
+                                                                      tokens.data_ptr(), _stream(H.device)))
+        return tokens
+
+    def embed(self, tokens, pos=None, rows_per_seq: int = 1, Y=None):
+        """embed_rows on the head's tables (qgemm_head_embed); pos is needed with a position table."""
+        import torch
+        assert isinstance(tokens, torch.Tensor), "tokens: an int32 device tensor"
+        rows = tokens.numel()
+        _require_device_i32(tokens, "tokens", rows)
+        assert rows_per_seq >= 1 and rows % rows_per_seq == 0, "tokens holds rows_per_seq entries per sequence"
+        n = rows // rows_per_seq
+        assert pos is not None or not self.has_positions, "a head with a position table needs pos"
+        if Y is None:
+            Y = torch.empty((rows, self.d_model), dtype=torch.float32, device=tokens.device)
+        ys = _require_rows_f32(Y, "Y", self.d_model)
+        assert Y.shape[0] == rows
+        _check("qgemm_head_embed", load().qgemm_head_embed(self._h, tokens.data_ptr(), _int_array(pos, n, "pos"), n,
+                                                          rows_per_seq, Y.data_ptr(), ys, _stream(tokens.device)))
+        return Y
+
+    def close(self):
+        if getattr(self, "_h", None):
+            load().qgemm_head_destroy(self._h)
             self._h = None
 
     def __del__(self):

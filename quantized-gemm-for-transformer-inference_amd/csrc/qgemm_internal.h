@@ -461,6 +461,9 @@ hipError_t decoder_step_varlen(Stack *S, int n_seqs, const int *slots, const int
                                float *Y, hipStream_t s);
 hipError_t decoder_copy_slot(Stack *S, int dst, int src, hipStream_t s);
 hipError_t decoder_slot_state(const Stack *S, int slot, int *enc_seq, int *filled);
+// what a caller that drives step_batch must know to check its arguments before the first launch (head.hip's generate):
+// hipErrorInvalidValue for a stack without caches
+hipError_t decoder_limits(const Stack *S, int *d_model, int *d_k, int *max_seq, int *n_slots);
 hipError_t decoder_forward(Stack *S, const float *X, const float *enc_out, float *Y, int seq, int enc_seq,
                            hipStream_t s);
 // draws a k x n fp32 weight into tmp (col_seeds[c] fills columns [c*cols_per_seed, (c+1)*cols_per_seed), one

@@ -625,4 +625,13 @@ hipError_t decoder_slot_state(const Stack *S, int slot, int *enc_seq, int *fille
     return hipSuccess;
 }
 
+hipError_t decoder_limits(const Stack *S, int *d_model, int *d_k, int *max_seq, int *n_slots) {
+    if (!S || !S->cross || !S->kv_cache) return hipErrorInvalidValue;
+    *d_model = S->d_model;
+    *d_k = S->d_model / S->n_heads;
+    *max_seq = S->max_seq;
+    *n_slots = S->n_slots;
+    return hipSuccess;
+}
+
 }  // namespace qgemm
