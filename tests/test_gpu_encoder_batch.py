@@ -183,6 +183,11 @@ def test_every_error_case(qg, device):
         assert f(enc._h, X.data_ptr(), Y.data_ptr(), 64, _ints([40] * 64), None) == 0      # 2560 rows, 64 sequences
         torch.cuda.synchronize()
         assert bool(torch.isfinite(Y[:2560]).all()) and bool(torch.isnan(Y[2560:]).all())
+        got = Y[:2560].cpu().numpy()
+        for b in (0, 31, 63):                                                              # first, middle, last
+            one = _nan((40, d), device)
+            enc.forward(X[40 * b:40 * b + 40], Y=one)
+            assert_bits_equal(got[40 * b:40 * b + 40], one.cpu().numpy(), f"sequence {b} of 64 against forward")
         with pytest.raises(qg.QGemmError):
             qg.Encoder(*DIMS, max_seq=40, seed=SEED, max_rows=-1)
     finally:
