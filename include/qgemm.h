@@ -497,6 +497,70 @@ QGEMM_API int qgemm_head_destroy(void *head);
 QGEMM_API int qgemm_decoder_generate(void *decoder, void *head, int n_seqs, const int *slots, const int32_t *tokens_in,
                            int n_new, const int *pos, int32_t *tokens_out, void *stream);
 
+/* ---- Sampled token choice: top-k / top-p at a temperature, seeded draws, end-token hold ----
+ * Like the entry points above, none of these allocates, synchronizes or copies anything to the device, and each can be
+ * captured; invalid arguments return hipErrorInvalidValue before any launch.
+ *
+ * qgemm_sample_rows draws one column per row of S (rows of w floats, unit inner stride, row stride s_stride_h >= w;
+ * S is const and untouched, nothing outside a row's w floats is read).  The rules for one row, every step one IEEE
+ * fp32 operation, so that a restatement predicts each token exactly:
+ *  1. Candidates are the columns with S[i] > -inf: a NaN or a -inf is never one (-inf is how a caller bans a token).
+ *     Their order is the argmax's: greater value first, among == values (+0 equals -0) the lower index first.
+ *     k' = min(top_k, candidates); the list t_0 .. t_{k'-1} holds the first k' columns in that order, v_j = S[t_j]
+ *     (own bits).  k' == 0: the token is 0 (what qgemm_argmax_rows gives such a row) and n_kept = 0.
+ *  2. temperature == 0 means greedy: top_k is taken as 1 and inv_t = 1.  Otherwise inv_t = 1.0f / temperature, one fp32
+ *     division on the host.
+ *  3. p_0 .. p_{k'-1} is qgemm_softmax_rows on the row v_0 .. v_{k'-1} with scale = inv_t, bit for bit: fl(v * inv_t),
+ *     a maximum seeded by element 0 and moved by a strict >, the correctly rounded exp of fl(x - max), one sum from +0
+ *     in list order, one division.
+ *  4. c_j = fl(c_{j-1} + p_j) with c_{-1} = +0, one after another in list order.
+ *  5. Nucleus: thr = fl(top_p * c_{k'-1}); n = 1 + the first j with c_j >= thr; n = k' where no j qualifies (NaNs).
+ *     top_p acts inside the top_k list.
+ *  6. Draw: u = (z >> 40) * 2^-24 with key = mix64(seed + G), z = mix64(key + (counter + 1) * G), G = 0x9E3779B97F4A7C15
+ *     and mix64 the generator of qgemm_fill_uniform (element `counter` of its [0, 1) fill with this seed);
+ *     r = fl(u * c_{n-1}); the token is t_j for the first j < n with c_j > r, j = 0 where there is none.  On finite rows
+ *     there always is one (u <= 1 - 2^-24); a row holding +inf has every p NaN and gives its lowest-index +inf.
+ *  7. Hold: with prev != NULL and eos >= 0, a row with prev[r] == eos gets the token eos whatever was drawn.
+ * So top_k = 1 (or temperature 0) gives qgemm_argmax_rows' index on every row whose column 0 is not a NaN.
+ * Row r's counter is counters[r] where counters != NULL -- a HOST array of rows <= 64 entries, read at enqueue time and
+ * passed in the kernel arguments -- else counter0 + ((uint64_t)r << 32).  A captured call replays the counters of
+ * its capture, and with them its draws: a device-resident counter is out of scope.
+ * idx: int32[rows], the tokens.  top_idx (int32) and top_prob (float), both or neither, rows x top_k: the list and the
+ * bits of its p, -1 and +0 at and past position k'.  n_kept: int32[rows] or NULL, n (0 where k' == 0).  prev:
+ * int32[rows] on the device or NULL.
+ * Few, wide rows are split as the argmax splits them: `parts` column ranges of at least 4096 columns per row (parts
+ * from rows, w and top_k alone, at most 64; qgemm_sample_rows_plan reports it and needs no GPU), whose top_k best go
+ * through `workspace` (qgemm_sample_rows_workspace_size: 8 * rows * parts * top_k bytes, 8-byte aligned; 0 for
+ * parts == 1, where workspace may be NULL, and for arguments the call refuses) to a second launch.  The result does not
+ * depend on the plan.
+ * hipErrorInvalidValue: a null S / idx, rows < 0, w < 1 or > 2^24, s_stride_h < w, top_k < 1 or > 1024, top_p outside
+ * (0, 1] or NaN, temperature < 0, infinite or NaN, one of top_idx / top_prob without the other, counters with
+ * rows > 64, a short, misaligned or null workspace with parts > 1; rows == 0 returns 0 and touches nothing. */
+QGEMM_API int qgemm_sample_rows_plan(int64_t rows, int w, int top_k, int *parts);
+QGEMM_API size_t qgemm_sample_rows_workspace_size(int64_t rows, int w, int top_k);
+QGEMM_API int qgemm_sample_rows(const float *S, int64_t s_stride_h, int64_t rows, int w, int top_k, float top_p,
+                      float temperature, uint64_t seed, uint64_t counter0, const uint64_t *counters,
+                      const int32_t *prev, int eos, int32_t *idx, int32_t *top_idx, float *top_prob, int32_t *n_kept,
+                      void *workspace, size_t ws_bytes, void *stream);
+/* qgemm_head_next_tokens with qgemm_sample_rows in the argmax's place: logits into the head's buffer, then one draw per
+ * row from them (the sampling arguments as above) into tokens, int32[rows] on the device.  The head owns a sampling
+ * workspace for top_k = 1024 and every row count up to max_rows.  Refused before the logits are launched: what
+ * qgemm_head_next_tokens and qgemm_sample_rows refuse. */
+QGEMM_API int qgemm_head_sample_tokens(void *head, const float *H, int64_t h_stride_h, int rows, int top_k, float top_p,
+                             float temperature, uint64_t seed, uint64_t counter0, const uint64_t *counters,
+                             const int32_t *prev, int eos, int32_t *tokens, void *stream);
+/* qgemm_decoder_generate with qgemm_head_sample_tokens in qgemm_head_next_tokens' place.  Sequence b draws at step t
+ * with the counter ((uint64_t)stream_b << 32) + pos[b] + t, stream_b = streams ? streams[b] : slots[b] (streams: a HOST
+ * array of n_seqs uint32, or NULL), and prev is the row of tokens fed at that step.  Because the counter is the
+ * position, a sequence's tokens depend neither on its batch neighbours nor on how n_new is split over calls, and a
+ * rewind (or a replayed graph) repeats its draws.  With eos >= 0 a sequence that has produced eos keeps producing it;
+ * its steps still run, so filled[slots[b]] = pos[b] + n_new as in the greedy call.  eos < 0: no end token.
+ * hipErrorInvalidValue before any launch: what qgemm_decoder_generate and qgemm_sample_rows refuse. */
+QGEMM_API int qgemm_decoder_generate_sampled(void *decoder, void *head, int n_seqs, const int *slots,
+                                   const int32_t *tokens_in, int n_new, const int *pos, int top_k, float top_p,
+                                   float temperature, uint64_t seed, const uint32_t *streams, int eos,
+                                   int32_t *tokens_out, void *stream);
+
 /* ---- LLM.int8() outlier decomposition ------------------------------------------
  * Feature columns k of A (= rows of B) holding an element with NOT(|x| <= threshold) (the reference's
  * AbsCompareLTEConstFunc, op_elemwise.cuh:293-306; NaN counts as an outlier) are multiplied in fp32,

@@ -98,6 +98,11 @@ EXPORTED_SYMBOLS = (
     "qgemm_head_embed",
     "qgemm_head_destroy",
     "qgemm_decoder_generate",
+    "qgemm_sample_rows_plan",
+    "qgemm_sample_rows_workspace_size",
+    "qgemm_sample_rows",
+    "qgemm_head_sample_tokens",
+    "qgemm_decoder_generate_sampled",
     "qgemm_mm_outlier_workspace_size",
     "qgemm_mm_outlier",
     "qgemm_outlier_count",
@@ -296,6 +301,20 @@ def load() -> ctypes.CDLL:
         L.qgemm_head_destroy.restype = i32
         L.qgemm_decoder_generate.argtypes = [vp, vp, i32, ip, vp, i32, ip, vp, vp]
         L.qgemm_decoder_generate.restype = i32
+        u64 = ctypes.c_uint64
+        L.qgemm_sample_rows_plan.argtypes = [i64, i32, i32, ip]
+        L.qgemm_sample_rows_plan.restype = i32
+        L.qgemm_sample_rows_workspace_size.argtypes = [i64, i32, i32]
+        L.qgemm_sample_rows_workspace_size.restype = sz
+        L.qgemm_sample_rows.argtypes = [vp, i64, i64, i32, i32, f32, f32, u64, u64, ctypes.POINTER(u64), vp, i32, vp,
+                                        vp, vp, vp, vp, sz, vp]
+        L.qgemm_sample_rows.restype = i32
+        L.qgemm_head_sample_tokens.argtypes = [vp, vp, i64, i32, i32, f32, f32, u64, u64, ctypes.POINTER(u64), vp, i32,
+                                               vp, vp]
+        L.qgemm_head_sample_tokens.restype = i32
+        L.qgemm_decoder_generate_sampled.argtypes = [vp, vp, i32, ip, vp, i32, ip, i32, f32, f32, u64,
+                                                     ctypes.POINTER(ctypes.c_uint32), i32, vp, vp]
+        L.qgemm_decoder_generate_sampled.restype = i32
         L.qgemm_mm_outlier_workspace_size.argtypes = [i32, i32, i32]
         L.qgemm_mm_outlier_workspace_size.restype = sz
         L.qgemm_mm_outlier.argtypes = [vp, vp, vp, i32, i32, i32, f32, vp, sz, vp]
@@ -1342,6 +1361,27 @@ class Decoder:
                                              _stream(tokens_in.device)))
         return tokens_out
 
+    def generate_sampled(self, head, slots, tokens_in, n_new: int, top_k: int, top_p: float = 1.0,
+                         temperature: float = 1.0, seed: int = 0, streams=None, eos=None, pos=None, tokens_out=None):
+        """generate() with head.sample_tokens in head.next_tokens' place (qgemm_decoder_generate_sampled): sequence b
+        draws at step t with the counter (streams[b] << 32) + pos[b] + t (streams defaults to the slots), so its tokens
+        depend neither on its batch neighbours nor on how n_new is split over calls, and a rewind repeats its draws.
+        With an end token eos, a sequence that has produced it keeps producing it while its steps run on."""
+        import torch
+        slots = [int(v) for v in slots]
+        n = len(slots)
+        _require_device_i32(tokens_in, "tokens_in", n)
+        if tokens_out is None:
+            tokens_out = torch.empty((n_new, n), dtype=torch.int32, device=tokens_in.device)
+        _require_device_i32(tokens_out, "tokens_out", n_new * n)
+        _check("qgemm_decoder_generate_sampled",
+               load().qgemm_decoder_generate_sampled(self._h, head._h, n, _int_array(slots, n, "slots"),
+                                                     tokens_in.data_ptr(), n_new, _int_array(pos, n, "pos"), top_k,
+                                                     top_p, temperature, seed, _uint_array(streams, n, "streams", 32),
+                                                     -1 if eos is None else int(eos), tokens_out.data_ptr(),
+                                                     _stream(tokens_in.device)))
+        return tokens_out
+
     def copy_slot(self, dst: int, src: int):
         """Fork a sequence (qgemm_decoder_copy_slot): slot dst continues slot src's sequence on its own."""
         _check("qgemm_decoder_copy_slot", load().qgemm_decoder_copy_slot(self._h, dst, src, _stream()))
@@ -1401,6 +1441,56 @@ def argmax_rows(S, idx=None, val=None):
     _check("qgemm_argmax_rows", L.qgemm_argmax_rows(S.data_ptr(), stride, rows, w, idx.data_ptr(), val.data_ptr(),
                                                     ws.data_ptr() if need else None, need, _stream(S.device)))
     return idx, val
+
+
+def _uint_array(values, n: int, name: str, bits: int):
+    """A host array of n unsigned 32- or 64-bit entries for the C-ABI (None stays NULL)."""
+    if values is None:
+        return None
+    values = [int(v) for v in values]
+    assert len(values) == n and all(0 <= v < 1 << bits for v in values), f"{name}: {n} unsigned {bits}-bit entries"
+    return ((ctypes.c_uint32 if bits == 32 else ctypes.c_uint64) * max(1, n))(*values)
+
+
+def sample_rows_plan(rows: int, w: int, top_k: int) -> int:
+    """The number of workgroups sample_rows() gives each row in its first launch (qgemm_sample_rows_plan): 1, or more
+    for few, wide rows.  Needs no GPU; raises QGemmError for rows < 0, w outside 1 .. 2**24 or top_k outside 1 .. 1024."""
+    parts = ctypes.c_int()
+    _check("qgemm_sample_rows_plan", load().qgemm_sample_rows_plan(rows, w, top_k, ctypes.byref(parts)))
+    return parts.value
+
+
+def sample_rows(S, top_k: int, top_p: float = 1.0, temperature: float = 1.0, seed: int = 0, counter0: int = 0,
+                counters=None, prev=None, eos=None, idx=None, return_top: bool = False):
+    """One seeded draw per row of a 2-D fp32 device tensor or view with unit inner stride (qgemm_sample_rows): the top_k
+    best columns in argmax_rows' order (NaN and -inf never among them), their softmax_rows at scale 1 / temperature, the
+    nucleus top_p inside that list, and the draw of counter counters[r] (host ints, at most 64 rows) or
+    counter0 + (r << 32).  temperature 0 is greedy.  With prev (int32 on the device) and eos, a row whose prev is eos
+    gets eos.  Returns idx (int32 tokens), or with return_top (idx, top_idx, top_prob, n_kept): the sorted list, its
+    probabilities bit for bit (-1 / +0 past the candidates) and the length of the nucleus.  S is not written."""
+    import torch
+    stride = _require_rows_f32(S, "S")
+    rows, w = S.shape
+    if idx is None:
+        idx = torch.empty(rows, dtype=torch.int32, device=S.device)
+    _require_device_i32(idx, "idx", rows)
+    if prev is not None:
+        _require_device_i32(prev, "prev", rows)
+    top_idx = top_prob = n_kept = None
+    if return_top:
+        top_idx = torch.empty((rows, top_k), dtype=torch.int32, device=S.device)
+        top_prob = torch.empty((rows, top_k), dtype=torch.float32, device=S.device)
+        n_kept = torch.empty(rows, dtype=torch.int32, device=S.device)
+    L = load()
+    need = L.qgemm_sample_rows_workspace_size(rows, w, top_k)
+    ws = torch.empty(need, dtype=torch.uint8, device=S.device) if need else None
+    ptr = lambda t: None if t is None else t.data_ptr()
+    _check("qgemm_sample_rows",
+           L.qgemm_sample_rows(S.data_ptr(), stride, rows, w, top_k, top_p, temperature, seed, counter0,
+                               _uint_array(counters, rows, "counters", 64), ptr(prev), -1 if eos is None else int(eos),
+                               idx.data_ptr(), ptr(top_idx), ptr(top_prob), ptr(n_kept), ptr(ws), need,
+                               _stream(S.device)))
+    return (idx, top_idx, top_prob, n_kept) if return_top else idx
 
 
 def embed_rows(E, tokens, P=None, pos=None, rows_per_seq: int = 1, Y=None):
@@ -1482,6 +1572,25 @@ class Head:
         _require_device_i32(tokens, "tokens", H.shape[0])
         _check("qgemm_head_next_tokens", load().qgemm_head_next_tokens(self._h, H.data_ptr(), hs, H.shape[0],
                                                                       tokens.data_ptr(), _stream(H.device)))
+        return tokens
+
+    def sample_tokens(self, H, top_k: int, top_p: float = 1.0, temperature: float = 1.0, seed: int = 0,
+                      counter0: int = 0, counters=None, prev=None, eos=None, tokens=None):
+        """One draw per row from the row's logits (qgemm_head_sample_tokens): sample_rows in next_tokens' argmax's
+        place, with its arguments; int32 on the device."""
+        import torch
+        hs = _require_rows_f32(H, "H", self.d_model)
+        rows = H.shape[0]
+        if tokens is None:
+            tokens = torch.empty(rows, dtype=torch.int32, device=H.device)
+        _require_device_i32(tokens, "tokens", rows)
+        if prev is not None:
+            _require_device_i32(prev, "prev", rows)
+        _check("qgemm_head_sample_tokens",
+               load().qgemm_head_sample_tokens(self._h, H.data_ptr(), hs, rows, top_k, top_p, temperature, seed,
+                                               counter0, _uint_array(counters, rows, "counters", 64),
+                                               None if prev is None else prev.data_ptr(),
+                                               -1 if eos is None else int(eos), tokens.data_ptr(), _stream(H.device)))
         return tokens
 
     def embed(self, tokens, pos=None, rows_per_seq: int = 1, Y=None):

@@ -1,6 +1,7 @@
 // head.hip -- the output end of the model: row-wise argmax over fp32 rows of any width, the token
 // embedding gather, the vocabulary head object (logits = qgemm_linear, next token = argmax of the logits) and the
-// greedy generation loop over a slotted decoder, enqueued in one call with the tokens staying on the device.
+// greedy generation loop over a slotted decoder, enqueued in one call with the tokens staying on the device -- and the
+// sampled counterparts of the last two (s21): the token chosen by launch_sample_rows (sample.hip) in argmax's place.
 //
 // The reference stops before this point (transformer.cu ends at "TODO:: MLP & op_softmax"); its op_argmax
 // (op_reduction.cuh:41-54, 174-182: MaxAccumFunc over the columns of a row) fixes the selection's semantics:
@@ -248,16 +249,16 @@ hipError_t launch_embed_rows(const float *E, int64_t es, int vocab, int d, const
 
 // ---- the head object ------------------------------------------------------------------------------------------
 // Borrowed: the packed weight, the bias and the tables.  Owned: the logits, two blocks of max_rows x d_model rows
-// (generate's input and hidden rows) and the workspaces of qgemm_linear and the argmax, sized at creation for every
-// row count up to max_rows.
+// (generate's input and hidden rows) and the workspaces of qgemm_linear, the argmax and the sampling (top_k = 1024),
+// sized at creation for every row count up to max_rows.
 struct Head {
     int d_model = 0, vocab = 0, max_pos = 0, max_rows = 0;
     const void *pw = nullptr;
     const float *bias = nullptr, *E = nullptr, *P = nullptr;
     int64_t es = 0, ps = 0;
     float *logits = nullptr, *rows = nullptr;
-    void *lin_ws = nullptr, *arg_ws = nullptr;
-    size_t lin_bytes = 0, arg_bytes = 0;
+    void *lin_ws = nullptr, *arg_ws = nullptr, *smp_ws = nullptr;
+    size_t lin_bytes = 0, arg_bytes = 0, smp_bytes = 0;
 };
 
 void head_free(Head *h) {
@@ -266,6 +267,7 @@ void head_free(Head *h) {
     (void)hipFree(h->rows);
     (void)hipFree(h->lin_ws);
     (void)hipFree(h->arg_ws);
+    (void)hipFree(h->smp_ws);
     delete h;
 }
 
@@ -283,11 +285,93 @@ hipError_t head_next_tokens(Head *h, const float *H, int64_t hs, int rows, int *
     return launch_argmax_rows(h->logits, h->vocab, rows, h->vocab, tokens, nullptr, h->arg_ws, h->arg_bytes, s);
 }
 
+// the sampling arguments of qgemm_sample_rows, checked before the logits are launched
+struct SampleArgs {
+    int top_k;
+    float top_p, temperature;
+    uint64_t seed, counter0;
+    const uint64_t *counters;
+    const int *prev;
+    int eos;
+};
+
+hipError_t head_sample_check(const Head *h, int rows, const SampleArgs &a) {
+    if (!h || rows < 0 || rows > h->max_rows) return hipErrorInvalidValue;
+    return sample_check(rows, h->vocab, a.top_k, a.top_p, a.temperature, a.counters != nullptr);
+}
+
+hipError_t head_sample_tokens(Head *h, const float *H, int64_t hs, int rows, const SampleArgs &a, int *tokens,
+                              hipStream_t s) {
+    if (!tokens || head_sample_check(h, rows, a) != hipSuccess) return hipErrorInvalidValue;
+    const hipError_t e = head_logits(h, H, hs, rows, h->logits, h->vocab, s);
+    if (e != hipSuccess) return e;
+    return launch_sample_rows(h->logits, h->vocab, rows, h->vocab, a.top_k, a.top_p, a.temperature, a.seed, a.counter0,
+                              a.counters, a.prev, a.eos, tokens, nullptr, nullptr, nullptr, h->smp_ws, h->smp_bytes, s);
+}
+
 hipError_t head_embed(Head *h, const int *tokens, const int *pos, int n_seqs, int rows_per_seq, float *Y, int64_t ys,
                       hipStream_t s) {
     if (!h || !h->E) return hipErrorInvalidValue;
     return launch_embed_rows(h->E, h->es, h->vocab, h->d_model, tokens, h->P, h->ps, h->max_pos, pos, n_seqs,
                              rows_per_seq, Y, ys, s);
+}
+
+// Decoding, greedy (sample == nullptr) or sampled: every check first, then n_new x (embed, step_batch, logits, token
+// choice) on the stream.  Step t + 1's embed reads row t of tokens_out on the device; the host only advances the
+// positions it passes along.  Sampled, sequence b draws at step t with the counter (stream_b << 32) + pos_b + t, filled
+// on the host into the sample launch's arguments, and prev is the row of tokens fed at that step: a sequence that has
+// produced eos keeps producing it while its steps run on.
+int generate_steps(void *decoder, void *head, int n_seqs, const int *slots, const int32_t *tokens_in, int n_new,
+                   const int *pos, const SampleArgs *sample, const uint32_t *streams, int32_t *tokens_out,
+                   void *stream) {
+    Stack *S = static_cast<Stack *>(decoder);
+    Head *h = static_cast<Head *>(head);
+    int d_model, d_k, max_seq, n_slots;
+    if (!h || !h->E || !slots || !tokens_in || n_new < 0 || decoder_limits(S, &d_model, &d_k, &max_seq, &n_slots))
+        return (int)hipErrorInvalidValue;
+    if (n_seqs < 1 || n_seqs > n_slots || n_seqs > h->max_rows || n_seqs > kEmbedMaxSeqs || d_model != h->d_model ||
+        d_k > 64 || (n_new > 0 && !tokens_out))
+        return (int)hipErrorInvalidValue;
+    uint64_t counters[kEmbedMaxSeqs];
+    SampleArgs a = {};
+    if (sample) {
+        a = *sample;
+        a.counters = counters;
+        if (head_sample_check(h, n_seqs, a) != hipSuccess) return (int)hipErrorInvalidValue;
+    }
+    int at[kEmbedMaxSeqs];
+    uint64_t seen = 0;  // n_slots <= 64
+    for (int b = 0; b < n_seqs; ++b) {
+        int enc_seq, filled;
+        if (decoder_slot_state(S, slots[b], &enc_seq, &filled) || enc_seq < 1 || (seen >> slots[b] & 1))
+            return (int)hipErrorInvalidValue;
+        seen |= (uint64_t)1 << slots[b];
+        at[b] = pos ? pos[b] : filled;
+        if (at[b] < 0 || at[b] > filled || n_new > max_seq - at[b] || (h->P && n_new > h->max_pos - at[b]))
+            return (int)hipErrorInvalidValue;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    float *X = h->rows, *Y = h->rows + (size_t)h->max_rows * h->d_model;
+    const int32_t *tok = tokens_in;
+    for (int t = 0; t < n_new; ++t) {
+        int32_t *next = tokens_out + (size_t)t * n_seqs;
+        hipError_t e;
+        if ((e = head_embed(h, tok, at, n_seqs, 1, X, d_model, s)) != hipSuccess ||
+            (e = decoder_step_batch(S, n_seqs, slots, at, 1, X, Y, s)) != hipSuccess)
+            return (int)e;
+        if (sample) {
+            for (int b = 0; b < n_seqs; ++b)
+                counters[b] = ((uint64_t)(streams ? streams[b] : (uint32_t)slots[b]) << 32) + (uint64_t)at[b];
+            a.prev = tok;
+            e = head_sample_tokens(h, Y, d_model, n_seqs, a, next, s);
+        } else {
+            e = head_next_tokens(h, Y, d_model, n_seqs, next, s);
+        }
+        if (e != hipSuccess) return (int)e;
+        tok = next;
+        for (int b = 0; b < n_seqs; ++b) ++at[b];
+    }
+    return 0;
 }
 
 }  // namespace
@@ -342,12 +426,14 @@ int qgemm_head_create(const void *packed_w, int d_model, int vocab, const float 
     for (int m = 1; m <= max_rows; ++m) {  // neither size is monotonic in the row count
         h->lin_bytes = std::max(h->lin_bytes, qgemm_linear_workspace_size(m, vocab, d_model));
         h->arg_bytes = std::max(h->arg_bytes, argmax_ws_bytes(m, vocab));
+        h->smp_bytes = std::max(h->smp_bytes, sample_ws_bytes(m, vocab, 1024));
     }
     hipError_t e;
     if ((e = hipMalloc(&h->logits, sizeof(float) * (size_t)max_rows * vocab)) != hipSuccess ||
         (e = hipMalloc(&h->rows, sizeof(float) * 2 * (size_t)max_rows * d_model)) != hipSuccess ||
         (e = hipMalloc(&h->lin_ws, std::max<size_t>(h->lin_bytes, 16))) != hipSuccess ||
-        (e = hipMalloc(&h->arg_ws, std::max<size_t>(h->arg_bytes, 16))) != hipSuccess) {
+        (e = hipMalloc(&h->arg_ws, std::max<size_t>(h->arg_bytes, 16))) != hipSuccess ||
+        (e = hipMalloc(&h->smp_ws, std::max<size_t>(h->smp_bytes, 16))) != hipSuccess) {
         head_free(h);
         return (int)e;
     }
@@ -371,48 +457,30 @@ int qgemm_head_next_tokens(void *head, const float *H, int64_t h_stride_h, int r
                                  static_cast<hipStream_t>(stream));
 }
 
+int qgemm_head_sample_tokens(void *head, const float *H, int64_t h_stride_h, int rows, int top_k, float top_p,
+                             float temperature, uint64_t seed, uint64_t counter0, const uint64_t *counters,
+                             const int32_t *prev, int eos, int32_t *tokens, void *stream) {
+    const SampleArgs a = {top_k, top_p, temperature, seed, counter0, counters, prev, eos};
+    return (int)head_sample_tokens(static_cast<Head *>(head), H, h_stride_h, rows, a, tokens,
+                                   static_cast<hipStream_t>(stream));
+}
+
 int qgemm_head_embed(void *head, const int32_t *tokens, const int *pos, int n_seqs, int rows_per_seq, float *Y,
                      int64_t y_stride_h, void *stream) {
     return (int)head_embed(static_cast<Head *>(head), tokens, pos, n_seqs, rows_per_seq, Y, y_stride_h,
                            static_cast<hipStream_t>(stream));
 }
 
-// Greedy decoding: every check first, then n_new x (embed, step_batch, logits, argmax) on the stream.  Step t + 1's
-// embed reads row t of tokens_out on the device; the host only advances the positions it passes along.
 int qgemm_decoder_generate(void *decoder, void *head, int n_seqs, const int *slots, const int32_t *tokens_in,
                            int n_new, const int *pos, int32_t *tokens_out, void *stream) {
-    Stack *S = static_cast<Stack *>(decoder);
-    Head *h = static_cast<Head *>(head);
-    int d_model, d_k, max_seq, n_slots;
-    if (!h || !h->E || !slots || !tokens_in || n_new < 0 || decoder_limits(S, &d_model, &d_k, &max_seq, &n_slots))
-        return (int)hipErrorInvalidValue;
-    if (n_seqs < 1 || n_seqs > n_slots || n_seqs > h->max_rows || n_seqs > kEmbedMaxSeqs || d_model != h->d_model ||
-        d_k > 64 || (n_new > 0 && !tokens_out))
-        return (int)hipErrorInvalidValue;
-    int at[kEmbedMaxSeqs];
-    uint64_t seen = 0;  // n_slots <= 64
-    for (int b = 0; b < n_seqs; ++b) {
-        int enc_seq, filled;
-        if (decoder_slot_state(S, slots[b], &enc_seq, &filled) || enc_seq < 1 || (seen >> slots[b] & 1))
-            return (int)hipErrorInvalidValue;
-        seen |= (uint64_t)1 << slots[b];
-        at[b] = pos ? pos[b] : filled;
-        if (at[b] < 0 || at[b] > filled || n_new > max_seq - at[b] || (h->P && n_new > h->max_pos - at[b]))
-            return (int)hipErrorInvalidValue;
-    }
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    float *X = h->rows, *Y = h->rows + (size_t)h->max_rows * h->d_model;
-    const int32_t *tok = tokens_in;
-    for (int t = 0; t < n_new; ++t) {
-        hipError_t e;
-        if ((e = head_embed(h, tok, at, n_seqs, 1, X, d_model, s)) != hipSuccess ||
-            (e = decoder_step_batch(S, n_seqs, slots, at, 1, X, Y, s)) != hipSuccess ||
-            (e = head_next_tokens(h, Y, d_model, n_seqs, tokens_out + (size_t)t * n_seqs, s)) != hipSuccess)
-            return (int)e;
-        tok = tokens_out + (size_t)t * n_seqs;
-        for (int b = 0; b < n_seqs; ++b) ++at[b];
-    }
-    return 0;
+    return generate_steps(decoder, head, n_seqs, slots, tokens_in, n_new, pos, nullptr, nullptr, tokens_out, stream);
+}
+
+int qgemm_decoder_generate_sampled(void *decoder, void *head, int n_seqs, const int *slots, const int32_t *tokens_in,
+                                   int n_new, const int *pos, int top_k, float top_p, float temperature, uint64_t seed,
+                                   const uint32_t *streams, int eos, int32_t *tokens_out, void *stream) {
+    const SampleArgs a = {top_k, top_p, temperature, seed, 0, nullptr, nullptr, eos};
+    return generate_steps(decoder, head, n_seqs, slots, tokens_in, n_new, pos, &a, streams, tokens_out, stream);
 }
 
 }  // extern "C"

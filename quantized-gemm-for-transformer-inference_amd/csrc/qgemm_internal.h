@@ -472,6 +472,17 @@ hipError_t decoder_forward(Stack *S, const float *X, const float *enc_out, float
 hipError_t encoder_make_packed(int k, int n, const std::vector<uint64_t> &col_seeds, int cols_per_seed, float bound,
                                void **packed, float *tmp, hipStream_t s);
 const char *gemm_config_name();
+// Sampled token choice (sample.hip; the contract is at qgemm_sample_rows in include/qgemm.h).
+// sample_plan: the parts a row is cut into and a part's columns, from rows, w and top_k alone; false outside
+// rows >= 0, 1 <= w <= 2^24, 1 <= top_k <= 1024.  sample_check: every limit of the contract that needs no pointer.
+// launch_sample_rows checks everything before its first launch; counters (host, <= 64 entries) travel by value.
+bool sample_plan(int64_t rows, int w, int top_k, int *parts, int *chunk);
+size_t sample_ws_bytes(int64_t rows, int w, int top_k);
+hipError_t sample_check(int64_t rows, int w, int top_k, float top_p, float temperature, bool has_counters);
+hipError_t launch_sample_rows(const float *S, int64_t stride, int64_t rows, int w, int top_k, float top_p,
+                              float temperature, uint64_t seed, uint64_t counter0, const uint64_t *counters,
+                              const int *prev, int eos, int *idx, int *top_idx, float *top_prob, int *n_kept, void *ws,
+                              size_t ws_bytes, hipStream_t s);
 // Quantization-error statistics on the device (error_stats.hip); scratch = error_stats_scratch_bytes().
 size_t error_stats_scratch_bytes();
 hipError_t launch_error_stats(const float *C, const float *O, int64_t n, bool reference_order, double *stats,
