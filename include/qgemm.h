@@ -561,6 +561,110 @@ QGEMM_API int qgemm_decoder_generate_sampled(void *decoder, void *head, int n_se
                                    float temperature, uint64_t seed, const uint32_t *streams, int eos,
                                    int32_t *tokens_out, void *stream);
 
+/* ---- Beam search: log-sum-exp rows, beam step, cache gather, device loop -----------------
+ * Like the entry points above, none of these allocates, synchronizes or copies anything to the device, and each can be
+ * captured; host arrays travel in kernel arguments; invalid arguments return hipErrorInvalidValue before any launch and
+ * without moving host state.
+ *
+ * qgemm_logsumexp_rows: mx[r], logz[r] (float[rows], device) for every row of S (rows of w floats, unit inner stride,
+ * row stride s_stride_h >= w, 1 <= w <= 2^24; S is const, nothing outside a row's w floats is read).  The rules for one
+ * row, every step one IEEE fp32 operation:
+ *  1. Candidates are the columns with S[i] > -inf (qgemm_sample_rows' rule 1: never a NaN or a -inf).
+ *  2. m is the greatest candidate in the argmax's order (among == values the lowest index); mx[r] holds its bits.
+ *  3. e_i = fl32(exp((double)fl(S[i] - m))) for a candidate (qgemm_softmax_rows' exp at scale 1), +0 for any other column.
+ *  4. The sum: e padded with +0 to P, the least power of two >= max(w, 1024); y_i = fl(x_2i + x_2i+1) level by level;
+ *     the sum is the root of that perfect binary tree.  (fl(x + +0) == x for every e, so all-padding subtrees are
+ *     identities; the tree does not depend on the launch plan.)
+ *  5. logz[r] = fl32(log((double)sum)).
+ * A row without a candidate gives mx = logz = -inf; a row holding +inf gives logz = NaN (fl(inf - inf)).  The
+ * log-probability of column i is then fl(fl(S[i] - mx) - logz).
+ * With fewer than 256 rows a wide row is split by whole 1024-column blocks over `parts` workgroups (each at least 4
+ * blocks, about 512 workgroups in all, parts <= 64: qgemm_logsumexp_rows_plan reports it, from rows and w alone, no GPU
+ * needed) whose maxima and block sums go through `workspace` (qgemm_logsumexp_rows_workspace_size:
+ * 8 * rows * parts + 4 * rows * ceil(w / 1024) bytes, 8-byte aligned; 0 for parts == 1, where workspace may be NULL, and
+ * for arguments the call refuses) to a finishing launch; the result does not depend on the plan.
+ * hipErrorInvalidValue: a null S / mx / logz, rows < 0, w < 1 or > 2^24, s_stride_h < w, a short, misaligned or null
+ * workspace with parts > 1; rows == 0 returns 0 and touches nothing. */
+QGEMM_API int qgemm_logsumexp_rows_plan(int64_t rows, int w, int *parts);
+QGEMM_API size_t qgemm_logsumexp_rows_workspace_size(int64_t rows, int w);
+QGEMM_API int qgemm_logsumexp_rows(const float *S, int64_t s_stride_h, int64_t rows, int w, float *mx, float *logz,
+                         void *workspace, size_t ws_bytes, void *stream);
+/* qgemm_beam_step: one step of beam search on the logits S, rows = n_groups * beams rows (row g * beams + b is beam b of
+ * group g; 1 <= beams <= 8, rows <= 64).  scores_in: float[rows] on the device, or NULL for the start (beam 0 of every
+ * group has +0, the others are dead); prev: int32[rows] on the device or NULL; eos < 0: no end token.
+ *  1. A beam whose score is not > -inf is dead and contributes no candidate.
+ *  2. A beam with eos >= 0, prev != NULL and prev[r] == eos is finished: it contributes exactly one candidate, token
+ *     eos at rank j = 0 with its score unchanged; its logits are not used.
+ *  3. Any other beam is live: its first k' = min(beams, candidates) columns t_j in the argmax's order (qgemm_sample_rows'
+ *     rule 1), v_j = S[t_j], lp_j = fl(fl(v_j - mx_r) - logz_r) with qgemm_logsumexp_rows' (mx_r, logz_r), and
+ *     c_j = fl(scores_in[r] + lp_j).
+ *  4. Of a group's candidates those with c > -inf are ordered by greater c first, among == values (+0 equals -0) the
+ *     lower b * beams + j first.  Place i < beams of the group gets parents[g * beams + i] = b (the index inside the
+ *     group), tokens[g * beams + i] = t and scores_out[g * beams + i] = the bits of c.
+ *  5. Places past the number of candidates get parent i, token 0 and score -inf: dead beams.
+ * Every fl step is monotone in v, so this is the selection over all beams * w columns of the group under that tie rule;
+ * beams == 1 gives qgemm_argmax_rows' index on every row whose column 0 is not a NaN.  parents / tokens: int32[rows],
+ * scores_out: float[rows], device.  The workspace (qgemm_beam_step_workspace_size, 8-byte aligned) holds the row lists
+ * of a split selection (qgemm_sample_rows' plan at top_k = beams), the log-sum-exp's workspace, mx, logz and the
+ * candidates; qgemm_beam_step_plan reports the parts of the selection and of the log-sum-exp (either pointer may be
+ * NULL) and needs no GPU.  The result does not depend on the plan.
+ * hipErrorInvalidValue: a null S / parents / tokens / scores_out, n_groups < 0, beams < 1 or > 8, n_groups * beams > 64,
+ * w < 1 or > 2^24, s_stride_h < w, a short, misaligned or null workspace; n_groups == 0 returns 0. */
+QGEMM_API int qgemm_beam_step_plan(int n_groups, int beams, int w, int *select_parts, int *lse_parts);
+QGEMM_API size_t qgemm_beam_step_workspace_size(int n_groups, int beams, int w);
+QGEMM_API int qgemm_beam_step(const float *S, int64_t s_stride_h, int n_groups, int beams, int w, const float *scores_in,
+                    const int32_t *prev, int eos, int32_t *parents, int32_t *tokens, float *scores_out, void *workspace,
+                    size_t ws_bytes, void *stream);
+/* qgemm_head_next_tokens with qgemm_beam_step in the argmax's place: logits of the n_groups * beams rows of H into the
+ * head's buffer, then the step on them.  The head owns a beam workspace for every beams <= 8 and every row count up to
+ * max_rows.  Refused before the logits are launched: what qgemm_head_next_tokens and qgemm_beam_step refuse. */
+QGEMM_API int qgemm_head_beam_step(void *head, const float *H, int64_t h_stride_h, int n_groups, int beams,
+                         const float *scores_in, const int32_t *prev, int eos, int32_t *parents, int32_t *tokens,
+                         float *scores_out, void *stream);
+/* qgemm_decoder_gather_slots reorders KV caches by a permutation that exists only on the device: destination slot
+ * dst_slots[g * beams + i] takes, for every block, the K and V thirds (the 2 d_model contiguous floats at offset d_model
+ * of each 3 d_model row) of self-cache rows 0 .. n_rows[g] - 1 of slot src_slots[g * beams + parents[g * beams + i]].
+ * dst_slots, src_slots (n_groups * beams entries) and n_rows (n_groups) are HOST arrays read at enqueue time; parents is
+ * int32[n_groups * beams] on the DEVICE, read by the kernel.  The Q third, rows at or past n_rows[g], the cross caches
+ * and every other slot are not written.  On success filled[dst] = n_rows[g].  A parent outside [0, beams) cannot be
+ * seen by the host: that destination's rows get quiet NaNs (0x7fc00000), nothing is read through the bad index and
+ * nothing faults (qgemm_embed_rows' convention).  A copy into a second set of slots is the design: a source may be named
+ * by many destinations, never a destination.
+ * hipErrorInvalidValue: a decoder without caches, a null pointer, n_groups < 1, beams < 1 or > 8, n_groups * beams > 64,
+ * a slot out of range or not begun, a destination named twice, a slot in both lists, n_rows[g] < 0, above max_seq or
+ * above the filled length of any source slot of the group, enc_seq differing among a group's slots. */
+QGEMM_API int qgemm_decoder_gather_slots(void *decoder, int n_groups, int beams, const int *dst_slots,
+                               const int *src_slots, const int32_t *parents, const int *n_rows, void *stream);
+/* A cache slot as it is, for inspection: block `block`'s self slab of slot `slot` (max_seq x 3 d_model floats, rows
+ * [Q | K | V]) into self_rows and its cross slab (max_enc_seq x 2 d_model, rows [K2 | V2]) into cross_rows, device to
+ * device in stream order; either may be NULL.  Rows at or past the filled length / enc_seq, and the Q thirds that
+ * step_batch and gather_slots do not write, hold whatever was there.  hipErrorInvalidValue: a decoder without caches,
+ * a block or slot out of range. */
+QGEMM_API int qgemm_decoder_read_slot(void *decoder, int block, int slot, float *self_rows, float *cross_rows,
+                            void *stream);
+/* Beam search of n_groups sequences with `beams` beams each for n_new tokens, enqueued in ONE call with no host round
+ * trip.  Two sets of rows = n_groups * beams distinct cache slots, slots_a and slots_b (rows <= 32, rows <= the head's
+ * max_rows): every slot begun, slots_b[r] with the enc_seq of slots_a[r], equal inside a group, and the cross caches of
+ * a group's slots equal (the caller's job: qgemm_decoder_copy_slot).  The beams' self caches are in set A.  With
+ * tok_0 = tokens_in (int32[rows], device), sc_0 = scores_in (float[rows], device, or NULL for the start) and
+ * cur = A for even t, B for odd t:
+ *   X = head embed(tok_t, pos + t);  H = step_batch(cur, X, pos + t);
+ *   (par_t, tok_{t+1}, sc_{t+1}) = head beam_step(H, sc_t, prev = tok_t, eos);
+ *   gather_slots(other <- cur, par_t, pos + t + 1)                       -- after the last step too
+ * par_t, tok_{t+1} and sc_{t+1} are row t of parents_out, tokens_out and scores_out ([n_new x rows], device).  pos: a
+ * host array of n_groups ints, or NULL for the filled length of the group's first set-A slot.  Afterwards the beams'
+ * caches are in set A for an even n_new and in set B for an odd one, and both sets report filled = pos + n_new.  A
+ * second call that passes the sets in their new roles, the last row of tokens_out as tokens_in and the last row of
+ * scores_out as scores_in continues the search: together they give, bit for bit, what one call gives.
+ * hipErrorInvalidValue before any launch and without moving any filled length: what qgemm_decoder_generate,
+ * qgemm_head_beam_step and qgemm_decoder_gather_slots refuse, rows > 32, 2 * rows > n_slots, a slot named twice in or
+ * across the sets, enc_seq differing between slots_a[r] and slots_b[r] or inside a group, pos[g] < 0 or above the
+ * filled length of any set-A slot of the group.  n_new == 0 returns 0. */
+QGEMM_API int qgemm_decoder_generate_beam(void *decoder, void *head, int n_groups, int beams, const int *slots_a,
+                                const int *slots_b, const int32_t *tokens_in, int n_new, const int *pos,
+                                const float *scores_in, int eos, int32_t *tokens_out, int32_t *parents_out,
+                                float *scores_out, void *stream);
+
 /* ---- LLM.int8() outlier decomposition ------------------------------------------
  * Feature columns k of A (= rows of B) holding an element with NOT(|x| <= threshold) (the reference's
  * AbsCompareLTEConstFunc, op_elemwise.cuh:293-306; NaN counts as an outlier) are multiplied in fp32,

@@ -103,6 +103,16 @@ EXPORTED_SYMBOLS = (
     "qgemm_sample_rows",
     "qgemm_head_sample_tokens",
     "qgemm_decoder_generate_sampled",
+    "qgemm_logsumexp_rows_plan",
+    "qgemm_logsumexp_rows_workspace_size",
+    "qgemm_logsumexp_rows",
+    "qgemm_beam_step_plan",
+    "qgemm_beam_step_workspace_size",
+    "qgemm_beam_step",
+    "qgemm_head_beam_step",
+    "qgemm_decoder_gather_slots",
+    "qgemm_decoder_read_slot",
+    "qgemm_decoder_generate_beam",
     "qgemm_mm_outlier_workspace_size",
     "qgemm_mm_outlier",
     "qgemm_outlier_count",
@@ -315,6 +325,26 @@ def load() -> ctypes.CDLL:
         L.qgemm_decoder_generate_sampled.argtypes = [vp, vp, i32, ip, vp, i32, ip, i32, f32, f32, u64,
                                                      ctypes.POINTER(ctypes.c_uint32), i32, vp, vp]
         L.qgemm_decoder_generate_sampled.restype = i32
+        L.qgemm_logsumexp_rows_plan.argtypes = [i64, i32, ip]
+        L.qgemm_logsumexp_rows_plan.restype = i32
+        L.qgemm_logsumexp_rows_workspace_size.argtypes = [i64, i32]
+        L.qgemm_logsumexp_rows_workspace_size.restype = sz
+        L.qgemm_logsumexp_rows.argtypes = [vp, i64, i64, i32, vp, vp, vp, sz, vp]
+        L.qgemm_logsumexp_rows.restype = i32
+        L.qgemm_beam_step_plan.argtypes = [i32, i32, i32, ip, ip]
+        L.qgemm_beam_step_plan.restype = i32
+        L.qgemm_beam_step_workspace_size.argtypes = [i32, i32, i32]
+        L.qgemm_beam_step_workspace_size.restype = sz
+        L.qgemm_beam_step.argtypes = [vp, i64, i32, i32, i32, vp, vp, i32, vp, vp, vp, vp, sz, vp]
+        L.qgemm_beam_step.restype = i32
+        L.qgemm_head_beam_step.argtypes = [vp, vp, i64, i32, i32, vp, vp, i32, vp, vp, vp, vp]
+        L.qgemm_head_beam_step.restype = i32
+        L.qgemm_decoder_gather_slots.argtypes = [vp, i32, i32, ip, ip, vp, ip, vp]
+        L.qgemm_decoder_gather_slots.restype = i32
+        L.qgemm_decoder_read_slot.argtypes = [vp, i32, i32, vp, vp, vp]
+        L.qgemm_decoder_read_slot.restype = i32
+        L.qgemm_decoder_generate_beam.argtypes = [vp, vp, i32, i32, ip, ip, vp, i32, ip, vp, i32, vp, vp, vp, vp]
+        L.qgemm_decoder_generate_beam.restype = i32
         L.qgemm_mm_outlier_workspace_size.argtypes = [i32, i32, i32]
         L.qgemm_mm_outlier_workspace_size.restype = sz
         L.qgemm_mm_outlier.argtypes = [vp, vp, vp, i32, i32, i32, f32, vp, sz, vp]
@@ -1386,6 +1416,79 @@ class Decoder:
         """Fork a sequence (qgemm_decoder_copy_slot): slot dst continues slot src's sequence on its own."""
         _check("qgemm_decoder_copy_slot", load().qgemm_decoder_copy_slot(self._h, dst, src, _stream()))
 
+    def gather_slots(self, dst_slots, src_slots, parents, n_rows, beams: int):
+        """Reorder KV caches by a permutation on the device (qgemm_decoder_gather_slots): slot dst_slots[g * beams + i]
+        takes the K and V thirds of self-cache rows 0 .. n_rows[g] - 1 of slot src_slots[g * beams + parents[g * beams +
+        i]].  parents: int32 on the device; the slot lists and n_rows (one entry per group) are host values.  A parent
+        outside [0, beams) gives that destination rows of quiet NaNs."""
+        dst_slots, src_slots = [int(v) for v in dst_slots], [int(v) for v in src_slots]
+        rows = len(dst_slots)
+        assert beams >= 1 and rows % beams == 0 and len(src_slots) == rows, "beams slots per group in both lists"
+        _require_device_i32(parents, "parents", rows)
+        n = rows // beams
+        _check("qgemm_decoder_gather_slots",
+               load().qgemm_decoder_gather_slots(self._h, n, beams, _int_array(dst_slots, rows, "dst_slots"),
+                                                 _int_array(src_slots, rows, "src_slots"), parents.data_ptr(),
+                                                 _int_array(n_rows, n, "n_rows"), _stream(parents.device)))
+
+    def read_slot(self, block: int, slot: int):
+        """(self, cross): copies of block `block`'s cache slabs of one slot as they are (qgemm_decoder_read_slot),
+        max_seq x 3 d_model rows [Q | K | V] and max_enc_seq x 2 d_model rows [K2 | V2], for inspection."""
+        import torch
+        dev = torch.device("cuda", torch.cuda.current_device())
+        self_rows = torch.empty((self.max_seq, 3 * self.d_model), dtype=torch.float32, device=dev)
+        cross_rows = torch.empty((self.max_enc_seq, 2 * self.d_model), dtype=torch.float32, device=dev)
+        _check("qgemm_decoder_read_slot", load().qgemm_decoder_read_slot(self._h, block, slot, self_rows.data_ptr(),
+                                                                        cross_rows.data_ptr(), _stream(dev)))
+        return self_rows, cross_rows
+
+    def beam_fork(self, slot: int, slots_a, slots_b):
+        """Start a group's beams from the sequence in `slot` (copy_slot into every other slot of the two sets): they
+        then share its cross cache, which generate_beam needs, and its self cache so far."""
+        for dst in list(slots_a) + list(slots_b):
+            if int(dst) != int(slot):
+                self.copy_slot(int(dst), int(slot))
+
+    def generate_beam(self, head, slots_a, slots_b, tokens_in, n_new: int, beams: int, pos=None, scores_in=None,
+                      eos: int = -1, out=None):
+        """Beam search for n_new tokens in one enqueued call (qgemm_decoder_generate_beam): per step head.embed,
+        step_batch on the slot set that holds the beams, head.beam_step, gather_slots into the other set by the
+        parents just chosen.  slots_a / slots_b: two sets of n_groups * beams distinct begun slots (beam_fork makes
+        them); the beams' caches are in slots_a.  tokens_in: int32[rows] on the device, or [n_groups] (every beam of a
+        group then starts from the same token).  scores_in None: the start (beam 0 of each group alone is live).  pos:
+        one host int per group, default the filled length of the group's first slot.  Returns (tokens, parents,
+        scores), each n_new x rows on the device; afterwards the caches are in slots_a for an even n_new, else in
+        slots_b.  A second call with the sets in their new roles, tokens[-1] and scores[-1] continues bit for bit."""
+        import torch
+        slots_a, slots_b = [int(v) for v in slots_a], [int(v) for v in slots_b]
+        rows = len(slots_a)
+        assert beams >= 1 and rows % beams == 0 and len(slots_b) == rows, "beams slots per group in both sets"
+        n = rows // beams
+        assert isinstance(tokens_in, torch.Tensor), "tokens_in: an int32 device tensor"
+        if tokens_in.numel() == n and n != rows:
+            tokens_in = tokens_in.repeat_interleave(beams).contiguous()
+        _require_device_i32(tokens_in, "tokens_in", rows)
+        if scores_in is not None:
+            assert scores_in.is_cuda and scores_in.dtype == torch.float32 and scores_in.is_contiguous() and \
+                scores_in.numel() == rows, "scores_in: float32[rows] on the device"
+        if out is None:
+            out = (torch.empty((n_new, rows), dtype=torch.int32, device=tokens_in.device),
+                   torch.empty((n_new, rows), dtype=torch.int32, device=tokens_in.device),
+                   torch.empty((n_new, rows), dtype=torch.float32, device=tokens_in.device))
+        tokens, parents, scores = out
+        _require_device_i32(tokens, "tokens", n_new * rows)
+        _require_device_i32(parents, "parents", n_new * rows)
+        assert scores.is_cuda and scores.dtype == torch.float32 and scores.is_contiguous() and \
+            scores.numel() == n_new * rows, "scores: float32[n_new x rows] on the device"
+        _check("qgemm_decoder_generate_beam",
+               load().qgemm_decoder_generate_beam(self._h, head._h, n, beams, _int_array(slots_a, rows, "slots_a"),
+                                                  _int_array(slots_b, rows, "slots_b"), tokens_in.data_ptr(), n_new,
+                                                  _int_array(pos, n, "pos"),
+                                                  None if scores_in is None else scores_in.data_ptr(), int(eos),
+                                                  tokens.data_ptr(), parents.data_ptr(), scores.data_ptr(),
+                                                  _stream(tokens_in.device)))
+        return tokens, parents, scores
+
     def close(self):
         if getattr(self, "_h", None):
             load().qgemm_decoder_destroy(self._h)
@@ -1493,6 +1596,117 @@ def sample_rows(S, top_k: int, top_p: float = 1.0, temperature: float = 1.0, see
     return (idx, top_idx, top_prob, n_kept) if return_top else idx
 
 
+def logsumexp_rows_plan(rows: int, w: int) -> int:
+    """The number of workgroups logsumexp_rows() gives each row (qgemm_logsumexp_rows_plan): 1, or more for few, wide
+    rows, each a run of whole 1024-column blocks.  Needs no GPU; raises QGemmError for rows < 0 or w outside 1 .. 2**24."""
+    parts = ctypes.c_int()
+    _check("qgemm_logsumexp_rows_plan", load().qgemm_logsumexp_rows_plan(rows, w, ctypes.byref(parts)))
+    return parts.value
+
+
+def logsumexp_rows(S, mx=None, logz=None):
+    """(mx, logz) of every row of a 2-D fp32 device tensor or view with unit inner stride (qgemm_logsumexp_rows): mx the
+    greatest candidate (S[i] > -inf) in argmax_rows' order, logz = fl32(log(sum)) with the sum of the correctly rounded
+    exp(S[i] - mx) over the candidates taken by one fixed binary tree, so that every bit is predictable and independent
+    of the launch plan.  The log-probability of column i is fl(fl(S[i] - mx) - logz).  S is not written."""
+    import torch
+    stride = _require_rows_f32(S, "S")
+    rows, w = S.shape
+    if mx is None:
+        mx = torch.empty(rows, dtype=torch.float32, device=S.device)
+    if logz is None:
+        logz = torch.empty(rows, dtype=torch.float32, device=S.device)
+    for t, name in ((mx, "mx"), (logz, "logz")):
+        assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == rows, \
+            f"{name}: float32[rows] on the device"
+    L = load()
+    need = L.qgemm_logsumexp_rows_workspace_size(rows, w)
+    ws = torch.empty(need, dtype=torch.uint8, device=S.device) if need else None
+    _check("qgemm_logsumexp_rows", L.qgemm_logsumexp_rows(S.data_ptr(), stride, rows, w, mx.data_ptr(), logz.data_ptr(),
+                                                          ws.data_ptr() if need else None, need, _stream(S.device)))
+    return mx, logz
+
+
+def beam_step_plan(n_groups: int, beams: int, w: int) -> tuple:
+    """(select_parts, lse_parts) of beam_step() (qgemm_beam_step_plan): the workgroups a row gets in the selection's
+    first launch and in the log-sum-exp's.  Needs no GPU; raises QGemmError outside 1 <= beams <= 8,
+    n_groups * beams <= 64, 1 <= w <= 2**24."""
+    sp, lp = ctypes.c_int(), ctypes.c_int()
+    _check("qgemm_beam_step_plan", load().qgemm_beam_step_plan(n_groups, beams, w, ctypes.byref(sp), ctypes.byref(lp)))
+    return sp.value, lp.value
+
+
+def _beam_outputs(rows, device, out):
+    import torch
+    if out is None:
+        out = (torch.empty(rows, dtype=torch.int32, device=device), torch.empty(rows, dtype=torch.int32, device=device),
+               torch.empty(rows, dtype=torch.float32, device=device))
+    parents, tokens, scores = out
+    _require_device_i32(parents, "parents", rows)
+    _require_device_i32(tokens, "tokens", rows)
+    assert scores.is_cuda and scores.dtype == torch.float32 and scores.is_contiguous() and scores.numel() == rows, \
+        "scores: float32[rows] on the device"
+    return parents, tokens, scores
+
+
+def _beam_inputs(rows, scores_in, prev):
+    import torch
+    if scores_in is not None:
+        assert scores_in.is_cuda and scores_in.dtype == torch.float32 and scores_in.is_contiguous() and \
+            scores_in.numel() == rows, "scores_in: float32[rows] on the device"
+    if prev is not None:
+        _require_device_i32(prev, "prev", rows)
+    return (None if scores_in is None else scores_in.data_ptr()), (None if prev is None else prev.data_ptr())
+
+
+def beam_step(S, beams: int, scores_in=None, prev=None, eos: int = -1, out=None):
+    """One step of beam search on the logits S, a 2-D fp32 device tensor or view of n_groups * beams rows
+    (qgemm_beam_step): every live beam's best `beams` columns scored as fl(score + log-probability), finished beams
+    (prev == eos) held with their score, dead beams (score not > -inf) dropped, and the best `beams` candidates of every
+    group chosen -- greater score first, the lower beam * beams + rank among equal scores.  scores_in None: the start.
+    Returns (parents, tokens, scores): int32, int32 and float32 [rows] on the device."""
+    stride = _require_rows_f32(S, "S")
+    rows, w = S.shape
+    assert beams >= 1 and rows % beams == 0, "S: beams rows per group"
+    parents, tokens, scores = _beam_outputs(rows, S.device, out)
+    sc, pv = _beam_inputs(rows, scores_in, prev)
+    import torch
+    L = load()
+    need = L.qgemm_beam_step_workspace_size(rows // beams, beams, w)
+    ws = torch.empty(max(need, 8), dtype=torch.uint8, device=S.device)
+    _check("qgemm_beam_step", L.qgemm_beam_step(S.data_ptr(), stride, rows // beams, beams, w, sc, pv, int(eos),
+                                                parents.data_ptr(), tokens.data_ptr(), scores.data_ptr(), ws.data_ptr(),
+                                                need, _stream(S.device)))
+    return parents, tokens, scores
+
+
+def beam_hypotheses(tokens, parents, scores, eos: int = -1, beams=None):
+    """Backtrack a finished search on the host: tokens / parents / scores are generate_beam's outputs (n_new x rows;
+    several calls' outputs concatenated along the first axis are fine).  beams defaults to rows (one group).  Returns,
+    for every final place, (token list, score): the tokens along its parent chain, cut after the first eos; a dead
+    place (score -inf) has an empty list."""
+    import numpy as np
+    tok, par, sc = (np.asarray(a.cpu() if hasattr(a, "cpu") else a) for a in (tokens, parents, scores))
+    steps, rows = tok.shape
+    beams = rows if beams is None else int(beams)
+    assert rows % beams == 0, "beams rows per group"
+    out = []
+    for r in range(rows):
+        score = float(sc[-1, r]) if steps else 0.0
+        if not score > float("-inf"):
+            out.append(([], score))
+            continue
+        seq, at = [], r
+        for t in range(steps - 1, -1, -1):
+            seq.append(int(tok[t, at]))
+            at = at // beams * beams + int(par[t, at])
+        seq.reverse()
+        if eos >= 0 and eos in seq:
+            seq = seq[:seq.index(eos) + 1]
+        out.append((seq, score))
+    return out
+
+
 def embed_rows(E, tokens, P=None, pos=None, rows_per_seq: int = 1, Y=None):
     """Y[r] = E[tokens[r]] (+ P[pos[r // rows_per_seq] + r % rows_per_seq], one fp32 add): the token embedding gather
     (qgemm_embed_rows).  tokens: int32 on the device, rows_per_seq per sequence; pos: one host int per sequence.  E, P
@@ -1592,6 +1806,19 @@ class Head:
                                                None if prev is None else prev.data_ptr(),
                                                -1 if eos is None else int(eos), tokens.data_ptr(), _stream(H.device)))
         return tokens
+
+    def beam_step(self, H, beams: int, scores_in=None, prev=None, eos: int = -1, out=None):
+        """beam_step on the logits of H's rows (qgemm_head_beam_step): logits into the head's buffer, then the step,
+        with its arguments; returns (parents, tokens, scores) on the device."""
+        hs = _require_rows_f32(H, "H", self.d_model)
+        rows = H.shape[0]
+        assert beams >= 1 and rows % beams == 0, "H: beams rows per group"
+        parents, tokens, scores = _beam_outputs(rows, H.device, out)
+        sc, pv = _beam_inputs(rows, scores_in, prev)
+        _check("qgemm_head_beam_step",
+               load().qgemm_head_beam_step(self._h, H.data_ptr(), hs, rows // beams, beams, sc, pv, int(eos),
+                                           parents.data_ptr(), tokens.data_ptr(), scores.data_ptr(), _stream(H.device)))
+        return parents, tokens, scores
 
     def embed(self, tokens, pos=None, rows_per_seq: int = 1, Y=None):
         """embed_rows on the head's tables (qgemm_head_embed); pos is needed with a position table."""

@@ -560,6 +560,17 @@ int qgemm_decoder_copy_slot(void *decoder, int dst_slot, int src_slot, void *str
     return err(decoder_copy_slot(static_cast<Stack *>(decoder), dst_slot, src_slot, static_cast<hipStream_t>(stream)));
 }
 
+int qgemm_decoder_gather_slots(void *decoder, int n_groups, int beams, const int *dst_slots, const int *src_slots,
+                               const int32_t *parents, const int *n_rows, void *stream) {
+    return err(decoder_gather_slots(static_cast<Stack *>(decoder), n_groups, beams, dst_slots, src_slots, parents, n_rows,
+                                    static_cast<hipStream_t>(stream)));
+}
+
+int qgemm_decoder_read_slot(void *decoder, int block, int slot, float *self_rows, float *cross_rows, void *stream) {
+    return err(decoder_read_slot(static_cast<Stack *>(decoder), block, slot, self_rows, cross_rows,
+                                 static_cast<hipStream_t>(stream)));
+}
+
 int qgemm_decoder_slot_state(void *decoder, int slot, int *enc_seq, int *filled) {
     return err(decoder_slot_state(static_cast<Stack *>(decoder), slot, enc_seq, filled));
 }

@@ -1,7 +1,9 @@
 // head.hip -- the output end of the model: row-wise argmax over fp32 rows of any width, the token
 // embedding gather, the vocabulary head object (logits = qgemm_linear, next token = argmax of the logits) and the
 // greedy generation loop over a slotted decoder, enqueued in one call with the tokens staying on the device -- and the
-// sampled counterparts of the last two (s21): the token chosen by launch_sample_rows (sample.hip) in argmax's place.
+// sampled counterparts of the last two (s21): the token chosen by launch_sample_rows (sample.hip) in argmax's place --
+// and beam search (s22): the head's beam step (logits, then launch_beam_step, beam.hip) and the loop that alternates
+// two sets of cache slots, the caches reordered by decoder_gather_slots (transformer.hip) after every step.
 //
 // The reference stops before this point (transformer.cu ends at "TODO:: MLP & op_softmax"); its op_argmax
 // (op_reduction.cuh:41-54, 174-182: MaxAccumFunc over the columns of a row) fixes the selection's semantics:
@@ -249,16 +251,16 @@ hipError_t launch_embed_rows(const float *E, int64_t es, int vocab, int d, const
 
 // ---- the head object ------------------------------------------------------------------------------------------
 // Borrowed: the packed weight, the bias and the tables.  Owned: the logits, two blocks of max_rows x d_model rows
-// (generate's input and hidden rows) and the workspaces of qgemm_linear, the argmax and the sampling (top_k = 1024),
-// sized at creation for every row count up to max_rows.
+// (generate's input and hidden rows) and the workspaces of qgemm_linear, the argmax, the sampling (top_k = 1024) and
+// the beam step (every beams <= 8), sized at creation for every row count up to max_rows.
 struct Head {
     int d_model = 0, vocab = 0, max_pos = 0, max_rows = 0;
     const void *pw = nullptr;
     const float *bias = nullptr, *E = nullptr, *P = nullptr;
     int64_t es = 0, ps = 0;
     float *logits = nullptr, *rows = nullptr;
-    void *lin_ws = nullptr, *arg_ws = nullptr, *smp_ws = nullptr;
-    size_t lin_bytes = 0, arg_bytes = 0, smp_bytes = 0;
+    void *lin_ws = nullptr, *arg_ws = nullptr, *smp_ws = nullptr, *beam_ws = nullptr;
+    size_t lin_bytes = 0, arg_bytes = 0, smp_bytes = 0, beam_bytes = 0;
 };
 
 void head_free(Head *h) {
@@ -268,6 +270,7 @@ void head_free(Head *h) {
     (void)hipFree(h->lin_ws);
     (void)hipFree(h->arg_ws);
     (void)hipFree(h->smp_ws);
+    (void)hipFree(h->beam_ws);
     delete h;
 }
 
@@ -307,6 +310,25 @@ hipError_t head_sample_tokens(Head *h, const float *H, int64_t hs, int rows, con
     if (e != hipSuccess) return e;
     return launch_sample_rows(h->logits, h->vocab, rows, h->vocab, a.top_k, a.top_p, a.temperature, a.seed, a.counter0,
                               a.counters, a.prev, a.eos, tokens, nullptr, nullptr, nullptr, h->smp_ws, h->smp_bytes, s);
+}
+
+// what qgemm_beam_step refuses without looking at a pointer, and the head's row limit
+hipError_t head_beam_check(const Head *h, int n_groups, int beams) {
+    int sp, lp;
+    if (!h || !beam_step_plan(n_groups, beams, h->vocab, &sp, &lp) || n_groups * beams > h->max_rows)
+        return hipErrorInvalidValue;
+    return hipSuccess;
+}
+
+// logits into the owned buffer, then the beam step on them
+hipError_t head_beam_step(Head *h, const float *H, int64_t hs, int n_groups, int beams, const float *scores_in,
+                          const int *prev, int eos, int *parents, int *tokens, float *scores_out, hipStream_t s) {
+    if (!parents || !tokens || !scores_out || head_beam_check(h, n_groups, beams) != hipSuccess)
+        return hipErrorInvalidValue;
+    const hipError_t e = head_logits(h, H, hs, n_groups * beams, h->logits, h->vocab, s);
+    if (e != hipSuccess) return e;
+    return launch_beam_step(h->logits, h->vocab, n_groups, beams, h->vocab, scores_in, prev, eos, parents, tokens,
+                            scores_out, h->beam_ws, h->beam_bytes, s);
 }
 
 hipError_t head_embed(Head *h, const int *tokens, const int *pos, int n_seqs, int rows_per_seq, float *Y, int64_t ys,
@@ -374,6 +396,71 @@ int generate_steps(void *decoder, void *head, int n_seqs, const int *slots, cons
     return 0;
 }
 
+// Beam search over two sets of rows = n_groups * beams cache slots: every check first, then n_new x
+// (embed, step_batch on the set that holds the beams, the head's beam step, gather_slots into the other set by the
+// parents just chosen) on the stream.  Step t + 1 reads row t of the three outputs on the device; the host only
+// advances positions and swaps the sets' roles.
+constexpr int kBeamGenerateMaxRows = 32;  // two sets share the decoder's 64 slots
+
+int generate_beam_steps(void *decoder, void *head, int n_groups, int beams, const int *slots_a, const int *slots_b,
+                        const int32_t *tokens_in, int n_new, const int *pos, const float *scores_in, int eos,
+                        int32_t *tokens_out, int32_t *parents_out, float *scores_out, void *stream) {
+    Stack *S = static_cast<Stack *>(decoder);
+    Head *h = static_cast<Head *>(head);
+    int d_model, d_k, max_seq, n_slots;
+    if (!h || !h->E || !slots_a || !slots_b || !tokens_in || n_new < 0 ||
+        decoder_limits(S, &d_model, &d_k, &max_seq, &n_slots))
+        return (int)hipErrorInvalidValue;
+    if (n_groups < 1 || head_beam_check(h, n_groups, beams) != hipSuccess ||
+        n_groups * beams > kBeamGenerateMaxRows || 2 * n_groups * beams > n_slots || d_model != h->d_model ||
+        d_k > 64 || (n_new > 0 && (!tokens_out || !parents_out || !scores_out)))
+        return (int)hipErrorInvalidValue;
+    const int rows = n_groups * beams;
+    int at[kBeamGenerateMaxRows], next_rows[kBeamGenerateMaxRows];  // per row / per group
+    uint64_t seen = 0;                                              // n_slots <= 64
+    for (int g = 0; g < n_groups; ++g) {
+        int enc0 = 0, start = 0;
+        for (int q = 0; q < beams; ++q) {
+            const int r = g * beams + q;
+            int enc_a, enc_b, filled_a, filled_b;
+            if (decoder_slot_state(S, slots_a[r], &enc_a, &filled_a) ||
+                decoder_slot_state(S, slots_b[r], &enc_b, &filled_b) || enc_a < 1 || enc_b != enc_a ||
+                slots_a[r] == slots_b[r] || (seen >> slots_a[r] & 1) || (seen >> slots_b[r] & 1))
+                return (int)hipErrorInvalidValue;
+            seen |= (uint64_t)1 << slots_a[r] | (uint64_t)1 << slots_b[r];
+            if (q == 0) {
+                enc0 = enc_a;
+                start = pos ? pos[g] : filled_a;
+            }
+            if (enc_a != enc0 || start < 0 || start > filled_a || n_new > max_seq - start ||
+                (h->P && n_new > h->max_pos - start))
+                return (int)hipErrorInvalidValue;
+            at[r] = start;
+        }
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    float *X = h->rows, *Y = h->rows + (size_t)h->max_rows * h->d_model;
+    const int32_t *tok = tokens_in;
+    const float *sc = scores_in;
+    const int *cur = slots_a, *other = slots_b;
+    for (int t = 0; t < n_new; ++t) {
+        int32_t *next = tokens_out + (size_t)t * rows, *par = parents_out + (size_t)t * rows;
+        float *nsc = scores_out + (size_t)t * rows;
+        for (int g = 0; g < n_groups; ++g) next_rows[g] = at[g * beams] + 1;
+        hipError_t e;
+        if ((e = head_embed(h, tok, at, rows, 1, X, d_model, s)) != hipSuccess ||
+            (e = decoder_step_batch(S, rows, cur, at, 1, X, Y, s)) != hipSuccess ||
+            (e = head_beam_step(h, Y, d_model, n_groups, beams, sc, tok, eos, par, next, nsc, s)) != hipSuccess ||
+            (e = decoder_gather_slots(S, n_groups, beams, other, cur, par, next_rows, s)) != hipSuccess)
+            return (int)e;
+        tok = next;
+        sc = nsc;
+        std::swap(cur, other);
+        for (int r = 0; r < rows; ++r) ++at[r];
+    }
+    return 0;
+}
+
 }  // namespace
 
 }  // namespace qgemm
@@ -428,12 +515,16 @@ int qgemm_head_create(const void *packed_w, int d_model, int vocab, const float 
         h->arg_bytes = std::max(h->arg_bytes, argmax_ws_bytes(m, vocab));
         h->smp_bytes = std::max(h->smp_bytes, sample_ws_bytes(m, vocab, 1024));
     }
+    for (int beams = 1; beams <= 8; ++beams)
+        for (int groups = 1; groups * beams <= std::min(max_rows, 64); ++groups)
+            h->beam_bytes = std::max(h->beam_bytes, beam_step_ws_bytes(groups, beams, vocab));
     hipError_t e;
     if ((e = hipMalloc(&h->logits, sizeof(float) * (size_t)max_rows * vocab)) != hipSuccess ||
         (e = hipMalloc(&h->rows, sizeof(float) * 2 * (size_t)max_rows * d_model)) != hipSuccess ||
         (e = hipMalloc(&h->lin_ws, std::max<size_t>(h->lin_bytes, 16))) != hipSuccess ||
         (e = hipMalloc(&h->arg_ws, std::max<size_t>(h->arg_bytes, 16))) != hipSuccess ||
-        (e = hipMalloc(&h->smp_ws, std::max<size_t>(h->smp_bytes, 16))) != hipSuccess) {
+        (e = hipMalloc(&h->smp_ws, std::max<size_t>(h->smp_bytes, 16))) != hipSuccess ||
+        (e = hipMalloc(&h->beam_ws, std::max<size_t>(h->beam_bytes, 16))) != hipSuccess) {
         head_free(h);
         return (int)e;
     }
@@ -481,6 +572,21 @@ int qgemm_decoder_generate_sampled(void *decoder, void *head, int n_seqs, const 
                                    const uint32_t *streams, int eos, int32_t *tokens_out, void *stream) {
     const SampleArgs a = {top_k, top_p, temperature, seed, 0, nullptr, nullptr, eos};
     return generate_steps(decoder, head, n_seqs, slots, tokens_in, n_new, pos, &a, streams, tokens_out, stream);
+}
+
+int qgemm_head_beam_step(void *head, const float *H, int64_t h_stride_h, int n_groups, int beams,
+                         const float *scores_in, const int32_t *prev, int eos, int32_t *parents, int32_t *tokens,
+                         float *scores_out, void *stream) {
+    return (int)head_beam_step(static_cast<Head *>(head), H, h_stride_h, n_groups, beams, scores_in, prev, eos, parents,
+                               tokens, scores_out, static_cast<hipStream_t>(stream));
+}
+
+int qgemm_decoder_generate_beam(void *decoder, void *head, int n_groups, int beams, const int *slots_a,
+                                const int *slots_b, const int32_t *tokens_in, int n_new, const int *pos,
+                                const float *scores_in, int eos, int32_t *tokens_out, int32_t *parents_out,
+                                float *scores_out, void *stream) {
+    return generate_beam_steps(decoder, head, n_groups, beams, slots_a, slots_b, tokens_in, n_new, pos, scores_in, eos,
+                               tokens_out, parents_out, scores_out, stream);
 }
 
 }  // extern "C"

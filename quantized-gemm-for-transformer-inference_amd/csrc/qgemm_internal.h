@@ -461,6 +461,8 @@ hipError_t decoder_step_varlen(Stack *S, int n_seqs, const int *slots, const int
                                float *Y, hipStream_t s);
 hipError_t decoder_copy_slot(Stack *S, int dst, int src, hipStream_t s);
 hipError_t decoder_slot_state(const Stack *S, int slot, int *enc_seq, int *filled);
+// a slot's self slab (max_seq x 3 d_model) / cross slab (max_enc_seq x 2 d_model) of one block, copied out in stream order
+hipError_t decoder_read_slot(const Stack *S, int block, int slot, float *self_rows, float *cross_rows, hipStream_t s);
 // what a caller that drives step_batch must know to check its arguments before the first launch (head.hip's generate):
 // hipErrorInvalidValue for a stack without caches
 hipError_t decoder_limits(const Stack *S, int *d_model, int *d_k, int *max_seq, int *n_slots);
@@ -483,6 +485,26 @@ hipError_t launch_sample_rows(const float *S, int64_t stride, int64_t rows, int 
                               float temperature, uint64_t seed, uint64_t counter0, const uint64_t *counters,
                               const int *prev, int eos, int *idx, int *top_idx, float *top_prob, int *n_kept, void *ws,
                               size_t ws_bytes, hipStream_t s);
+// Beam search (beam.hip; the contracts are at qgemm_logsumexp_rows, qgemm_beam_step and
+// qgemm_decoder_gather_slots in include/qgemm.h).  The plans need rows, w and beams alone; every launch_* checks
+// everything before its first launch.
+bool logsumexp_plan(int64_t rows, int w, int *parts, int *bpp);
+size_t logsumexp_ws_bytes(int64_t rows, int w);
+hipError_t launch_logsumexp_rows(const float *S, int64_t stride, int64_t rows, int w, float *mx, float *logz, void *ws,
+                                 size_t ws_bytes, hipStream_t s);
+bool beam_step_plan(int n_groups, int beams, int w, int *select_parts, int *lse_parts);
+size_t beam_step_ws_bytes(int n_groups, int beams, int w);
+hipError_t launch_beam_step(const float *S, int64_t stride, int n_groups, int beams, int w, const float *scores_in,
+                            const int *prev, int eos, int *parents, int *tokens, float *scores_out, void *ws,
+                            size_t ws_bytes, hipStream_t s);
+// one cache (n_slabs slabs of slab_rows x 3 d floats): the [K | V] of rows 0 .. n_rows[g] - 1 of slab
+// src_slots[g * beams + parents[g * beams + q]] into slab dst_slots[g * beams + q]; parents on the device, the rest host
+hipError_t launch_gather_kv(float *cache, int64_t slab_rows, int n_slabs, int d, int n_groups, int beams,
+                            const int *dst_slots, const int *src_slots, const int *n_rows, const int *parents,
+                            hipStream_t s);
+// the decoder's side of it (transformer.hip): the checks on the slots' state, one launch_gather_kv per block, filled
+hipError_t decoder_gather_slots(Stack *S, int n_groups, int beams, const int *dst_slots, const int *src_slots,
+                                const int *parents, const int *n_rows, hipStream_t s);
 // Quantization-error statistics on the device (error_stats.hip); scratch = error_stats_scratch_bytes().
 size_t error_stats_scratch_bytes();
 hipError_t launch_error_stats(const float *C, const float *O, int64_t n, bool reference_order, double *stats,

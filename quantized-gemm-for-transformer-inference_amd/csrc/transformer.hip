@@ -618,10 +618,60 @@ hipError_t decoder_copy_slot(Stack *S, int dst, int src, hipStream_t s) {
     return hipSuccess;
 }
 
+// Beam search's reorder: destination dst_slots[g * beams + q] takes the [K | V] of self-cache rows
+// 0 .. n_rows[g] - 1 of source src_slots[g * beams + parents[g * beams + q]], parents read on the device by the copy
+// kernel (beam.hip), one launch per block.  Every check comes before the first launch; `filled` moves at enqueue.
+hipError_t decoder_gather_slots(Stack *S, int n_groups, int beams, const int *dst_slots, const int *src_slots,
+                                const int *parents, const int *n_rows, hipStream_t s) {
+    if (!S || !S->cross || !S->kv_cache || !dst_slots || !src_slots || !parents || !n_rows || n_groups < 1 ||
+        beams < 1 || beams > 8 || (int64_t)n_groups * beams > kDecodeMaxBatch)
+        return hipErrorInvalidValue;
+    uint64_t is_dst = 0, is_src = 0;  // n_slots <= 64
+    for (int g = 0; g < n_groups; ++g) {
+        if (n_rows[g] < 0 || n_rows[g] > S->max_seq) return hipErrorInvalidValue;
+        for (int q = 0; q < beams; ++q) {
+            const int ds = dst_slots[g * beams + q], ss = src_slots[g * beams + q];
+            if (ds < 0 || ds >= S->n_slots || ss < 0 || ss >= S->n_slots || S->enc_seq[ds] < 1 || S->enc_seq[ss] < 1 ||
+                (is_dst >> ds & 1) || n_rows[g] > S->filled[ss] ||
+                S->enc_seq[ds] != S->enc_seq[src_slots[g * beams]] || S->enc_seq[ss] != S->enc_seq[src_slots[g * beams]])
+                return hipErrorInvalidValue;
+            is_dst |= (uint64_t)1 << ds;
+            is_src |= (uint64_t)1 << ss;
+        }
+    }
+    if (is_dst & is_src) return hipErrorInvalidValue;
+    hipError_t e;
+    for (const Block &B : S->blocks)
+        if ((e = launch_gather_kv(B.qkv_cache, S->max_seq, S->n_slots, S->d_model, n_groups, beams, dst_slots, src_slots,
+                                  n_rows, parents, s)))
+            return e;
+    for (int g = 0; g < n_groups; ++g)
+        for (int q = 0; q < beams; ++q) S->filled[dst_slots[g * beams + q]] = n_rows[g];
+    return hipSuccess;
+}
+
 hipError_t decoder_slot_state(const Stack *S, int slot, int *enc_seq, int *filled) {
     if (!S || !S->cross || !S->kv_cache || slot < 0 || slot >= S->n_slots) return hipErrorInvalidValue;
     if (enc_seq) *enc_seq = S->enc_seq[slot];
     if (filled) *filled = S->filled[slot];
+    return hipSuccess;
+}
+
+// a slot's slabs as they are, device to device in stream order: block `block`'s self slab (max_seq x 3 d_model) into
+// self_rows and its cross slab (max_enc_seq x 2 d_model) into cross_rows, either may be nullptr.  For inspection:
+// what a reorder wrote and what it left alone cannot be seen through step's output alone.
+hipError_t decoder_read_slot(const Stack *S, int block, int slot, float *self_rows, float *cross_rows, hipStream_t s) {
+    if (!S || !S->cross || !S->kv_cache || block < 0 || block >= S->n_blocks || slot < 0 || slot >= S->n_slots)
+        return hipErrorInvalidValue;
+    const int64_t d = S->d_model, self_slab = S->max_seq * 3 * d, cross_slab = S->max_enc_seq * 2 * d;
+    const Block &B = S->blocks[block];
+    hipError_t e;
+    if (self_rows && (e = hipMemcpyAsync(self_rows, B.qkv_cache + slot * self_slab, sizeof(float) * self_slab,
+                                         hipMemcpyDeviceToDevice, s)))
+        return e;
+    if (cross_rows && (e = hipMemcpyAsync(cross_rows, B.kv2_cache + slot * cross_slab, sizeof(float) * cross_slab,
+                                          hipMemcpyDeviceToDevice, s)))
+        return e;
     return hipSuccess;
 }
 
