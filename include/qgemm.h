@@ -665,6 +665,93 @@ QGEMM_API int qgemm_decoder_generate_beam(void *decoder, void *head, int n_group
                                 const float *scores_in, int eos, int32_t *tokens_out, int32_t *parents_out,
                                 float *scores_out, void *stream);
 
+/* ---- Copy-free beam search: per-row KV cache indirection in decode attention ---------------
+ * A row table `row_slab` is a uint8 array in DEVICE memory, one row per sequence place, row stride row_slab_stride
+ * bytes (any stride that covers the entries read, any alignment): entry [s][j] names the slab whose row j holds the K
+ * and V of position j of the sequence at place s.  255 is the invalid entry (slabs <= 64).
+ *
+ * qgemm_attention_decode_indirect: qgemm_attention_decode_batched reading through such a table.  Same envelope and the
+ * same host arrays; tab_row[b] (NULL: b) is sequence b's table row, n_slabs the slabs K and V hold.
+ * Contract: BIT FOR BIT qgemm_attention_decode_batched on slabs in which row j of sequence b's slab is row j of slab
+ * row_slab[tab_row[b]][j], for j < seq_kv[b]; an entry >= n_slabs stands for a row of quiet NaNs (0x7fc00000) in the
+ * d_k columns of every head: nothing is loaded through such an entry, the kernel forms no address outside the
+ * n_slabs slabs whatever the table holds, and the call returns normally (qgemm_decoder_gather_slots' convention).
+ * Two sequences may share a table row.  Of the table the kernel reads the aligned 16-byte pieces that hold an entry
+ * 0 .. seq_kv[b] - 1 of a named row.  Nothing is copied to the device, allocated or synchronized.
+ * hipErrorInvalidValue before any launch: what qgemm_attention_decode_batched refuses, a null row_slab, n_slabs < 1 or
+ * > 64, row_slab_stride < any seq_kv[b], any tab_row[b] < 0; n_seqs == 0 returns 0. */
+QGEMM_API int qgemm_attention_decode_indirect(const float *Q, int64_t q_stride_h,
+                                    const float *K, int64_t k_stride_h, int64_t k_stride_seq,
+                                    const float *V, int64_t v_stride_h, int64_t v_stride_seq,
+                                    float *O, int64_t o_stride_h, int n_seqs, int rows_per_seq,
+                                    const uint8_t *row_slab, int64_t row_slab_stride, int n_slabs,
+                                    const int *tab_row, const int *seq_kv, const int *q_pos0,
+                                    int n_heads, int d_k, float scale, void *stream);
+/* qgemm_beam_reindex: beam search's reorder on any row table, IN PLACE:
+ *   row_slab[slots[g * beams + q]][j] = old row_slab[slots[g * beams + parents[g * beams + q]]][j],  j < n_rows[g].
+ * slots (n_groups * beams table rows) and n_rows (n_groups) are HOST arrays read at enqueue time; parents is
+ * int32[n_groups * beams] on the DEVICE.  The reorder is column-local (column j of a group's new rows depends on column
+ * j of its old rows alone), so one thread reads a column's `beams` entries and then writes them: one table, no
+ * barrier.  A parent outside [0, beams) gives that destination 255 in entries 0 .. n_rows[g] - 1.  Entries at or past
+ * n_rows[g] and every other row are not written.
+ * hipErrorInvalidValue before the launch: a null pointer, row_slab_stride < 1, n_groups < 1, beams < 1 or > 8,
+ * n_groups * beams > 64, a slot < 0 or > 63, a slot named twice, n_rows[g] < 0 or > row_slab_stride. */
+QGEMM_API int qgemm_beam_reindex(uint8_t *row_slab, int64_t row_slab_stride, int n_groups, int beams, const int *slots,
+                       const int32_t *parents, const int *n_rows, void *stream);
+/* The decoder's row table.  A decoder with n_slots > 1 owns ONE table of n_slots x max_seq bytes for all its blocks,
+ * allocated at creation (never in a step) and filled with the identity, own[s][j] = s.  The row index inside a slab is
+ * always the position: a sequence writes the row of position p into its OWN slab once, and only its descendants read
+ * it afterwards.  Per slot the decoder keeps a host flag, set by beam_begin and cleared by qgemm_decoder_begin_slot: the
+ * slot's slab does not hold its own sequence.  On a flagged slot qgemm_decoder_step_slot / _step_batch / _step_varlen,
+ * qgemm_decoder_copy_slot and qgemm_decoder_gather_slots as source and qgemm_decoder_generate* return
+ * hipErrorInvalidValue before any launch; no other call sequence sets the flag.
+ *   beam_begin          for every group g the slots slots[g * beams + q] get entries 0 .. pos[g] - 1 = src_slots[g], the
+ *                       slot that holds the group's prompt; their enc_seq becomes src's, filled = pos[g], the flag is
+ *                       set.  They need not have been begun.  No K / V row and no cross cache is copied: one launch.
+ *                       slots[g * beams] may be src_slots[g] itself.
+ *   step_batch_indirect qgemm_decoder_step_batch on flagged slots with the append: the new [K | V] into slot slots[b]'s
+ *                       own slab at rows pos[b] .. pos[b] + r - 1, own[slots[b]][those] = slots[b], the self-attention
+ *                       over own[slots[b]][0 .. pos[b] + r - 1] through qgemm_attention_decode_indirect, the
+ *                       cross-attention on the cross cache of slot cross_slots[b] (a group's beams share their prompt's;
+ *                       it may be named by many).  Row for row Y is BIT FOR BIT what step_batch gives on slots whose
+ *                       slabs hold the rows the table names: the same values in the same key order through one kernel text.
+ *   beam_reindex        qgemm_beam_reindex on the table rows of flagged slots; filled of group g's slots = n_rows[g].
+ *   read_beam_table     the table as it is, n_slots x max_seq bytes into `out` (device), in stream order: read_slot's sibling.
+ * None allocates or synchronizes; slots, src_slots, cross_slots, pos and n_rows are host arrays read at enqueue time.
+ * hipErrorInvalidValue before any launch and without moving any state: a decoder without a table (n_slots == 1, no
+ * caches), a null pointer, n_groups < 1, beams < 1 or > 8, n_groups * beams > 64, a slot out of range or named twice;
+ * beam_begin: a source not begun, pos[g] < 0 or above the rows of the source's slab that hold its own sequence (its
+ * filled length; for a flagged source, which can only be one that was place 0 of its own group, the pos of that begin,
+ * less what a step at an earlier position overwrote -- so the same begin may be enqueued again), a slot that is a source
+ * other than place 0 of a group whose source no other group names; step_batch_indirect: what step_batch refuses, a
+ * slot without the flag, a cross slot out of range, not begun or of another enc_seq; beam_reindex: a slot without the
+ * flag, n_rows[g] < 0 or above the filled length of any slot of the group. */
+QGEMM_API int qgemm_decoder_beam_begin(void *decoder, int n_groups, int beams, const int *slots, const int *src_slots,
+                             const int *pos, void *stream);
+QGEMM_API int qgemm_decoder_step_batch_indirect(void *decoder, int n_seqs, const int *slots, const int *cross_slots,
+                                      const int *pos, int rows_per_seq, const float *X, float *Y, void *stream);
+QGEMM_API int qgemm_decoder_beam_reindex(void *decoder, int n_groups, int beams, const int *slots,
+                               const int32_t *parents, const int *n_rows, void *stream);
+QGEMM_API int qgemm_decoder_read_beam_table(void *decoder, uint8_t *out, void *stream);
+/* qgemm_decoder_generate_beam's loop over ONE slot set, no K / V row copied.  slots: rows = n_groups * beams distinct
+ * slots begun by qgemm_decoder_beam_begin from src_slots (n_groups prompt slots, begun; they lend their cross caches).
+ * rows <= the head's max_rows and the decoder's slots, so up to 64.  Per step t:
+ *   X = head embed(tok_t, pos + t);  H = step_batch_indirect(slots, cross = the groups' src_slots, X, pos + t);
+ *   (par_t, tok_{t+1}, sc_{t+1}) = head beam_step(H, sc_t, prev = tok_t, eos);
+ *   beam_reindex(slots, par_t, n_rows = pos + t + 1)                      -- after the last step too
+ * Outputs, pos (NULL: the filled length of the group's first slot) and the continuation rule are
+ * qgemm_decoder_generate_beam's: every token, parent and score is BIT FOR BIT that call's, and a second call with the
+ * last row of tokens_out and scores_out continues bit for bit -- without another beam_begin.  It allocates nothing and
+ * does not synchronize, so it can be captured; a replay starts from the table of the capture's start only if
+ * beam_begin is enqueued again before it or captured with it (a search leaves the table reordered).
+ * hipErrorInvalidValue before any launch and without moving any filled length: what qgemm_decoder_generate_beam refuses
+ * where it applies, rows > max_rows or > n_slots, a slot named twice or without the flag, a prompt slot not begun or of
+ * another enc_seq, pos[g] < 0 or above the filled length of a slot of the group.  n_new == 0 returns 0. */
+QGEMM_API int qgemm_decoder_generate_beam_indirect(void *decoder, void *head, int n_groups, int beams, const int *slots,
+                                         const int *src_slots, const int32_t *tokens_in, int n_new, const int *pos,
+                                         const float *scores_in, int eos, int32_t *tokens_out, int32_t *parents_out,
+                                         float *scores_out, void *stream);
+
 /* ---- LLM.int8() outlier decomposition ------------------------------------------
  * Feature columns k of A (= rows of B) holding an element with NOT(|x| <= threshold) (the reference's
  * AbsCompareLTEConstFunc, op_elemwise.cuh:293-306; NaN counts as an outlier) are multiplied in fp32,

@@ -113,6 +113,13 @@ EXPORTED_SYMBOLS = (
     "qgemm_decoder_gather_slots",
     "qgemm_decoder_read_slot",
     "qgemm_decoder_generate_beam",
+    "qgemm_attention_decode_indirect",
+    "qgemm_beam_reindex",
+    "qgemm_decoder_beam_begin",
+    "qgemm_decoder_step_batch_indirect",
+    "qgemm_decoder_beam_reindex",
+    "qgemm_decoder_read_beam_table",
+    "qgemm_decoder_generate_beam_indirect",
     "qgemm_mm_outlier_workspace_size",
     "qgemm_mm_outlier",
     "qgemm_outlier_count",
@@ -345,6 +352,22 @@ def load() -> ctypes.CDLL:
         L.qgemm_decoder_read_slot.restype = i32
         L.qgemm_decoder_generate_beam.argtypes = [vp, vp, i32, i32, ip, ip, vp, i32, ip, vp, i32, vp, vp, vp, vp]
         L.qgemm_decoder_generate_beam.restype = i32
+        L.qgemm_attention_decode_indirect.argtypes = [vp, i64, vp, i64, i64, vp, i64, i64, vp, i64, i32, i32, vp, i64,
+                                                      i32, ip, ip, ip, i32, i32, f32, vp]
+        L.qgemm_attention_decode_indirect.restype = i32
+        L.qgemm_beam_reindex.argtypes = [vp, i64, i32, i32, ip, vp, ip, vp]
+        L.qgemm_beam_reindex.restype = i32
+        L.qgemm_decoder_beam_begin.argtypes = [vp, i32, i32, ip, ip, ip, vp]
+        L.qgemm_decoder_beam_begin.restype = i32
+        L.qgemm_decoder_step_batch_indirect.argtypes = [vp, i32, ip, ip, ip, i32, vp, vp, vp]
+        L.qgemm_decoder_step_batch_indirect.restype = i32
+        L.qgemm_decoder_beam_reindex.argtypes = [vp, i32, i32, ip, vp, ip, vp]
+        L.qgemm_decoder_beam_reindex.restype = i32
+        L.qgemm_decoder_read_beam_table.argtypes = [vp, vp, vp]
+        L.qgemm_decoder_read_beam_table.restype = i32
+        L.qgemm_decoder_generate_beam_indirect.argtypes = [vp, vp, i32, i32, ip, ip, vp, i32, ip, vp, i32, vp, vp, vp,
+                                                           vp]
+        L.qgemm_decoder_generate_beam_indirect.restype = i32
         L.qgemm_mm_outlier_workspace_size.argtypes = [i32, i32, i32]
         L.qgemm_mm_outlier_workspace_size.restype = sz
         L.qgemm_mm_outlier.argtypes = [vp, vp, vp, i32, i32, i32, f32, vp, sz, vp]
@@ -1133,6 +1156,82 @@ def attention_decode_batched(Q, K, V, n_heads: int, seq_kv, q_pos0=None, kv_slot
     return O
 
 
+def _require_row_table(t, name):
+    """A row table: a 2-D uint8 device tensor or view with unit inner stride (any row stride, any alignment)."""
+    import torch
+    assert isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8 and t.dim() == 2, \
+        f"{name}: a 2-D uint8 device tensor"
+    assert t.stride(1) == 1 or t.shape[1] == 1, f"{name} must have unit inner stride"
+    assert t.shape[0] <= 1 or t.stride(0) >= t.shape[1], f"{name}: the row stride covers a row"
+
+
+def attention_decode_indirect(Q, K, V, n_heads: int, row_slab, seq_kv, q_pos0=None, tab_row=None,
+                              rows_per_seq: int = 1, scale=None, O=None):
+    """attention_decode_batched through a per-row slab table (qgemm_attention_decode_indirect): K / V
+    row j of sequence b is row j of slab row_slab[tab_row[b]][j] (tab_row left out: row b).  row_slab: a 2-D uint8
+    device tensor or view [table rows, entries], unit inner stride, any row stride and alignment; an entry >= the
+    number of slabs stands for a row of quiet NaNs.  Bit for bit attention_decode_batched on slabs gathered that
+    way."""
+    import math
+    import torch
+    _require_device_f32(Q, "Q")
+    assert Q.stride(1) == 1 or Q.shape[1] == 1, "Q must have unit inner stride"
+    for t, nm in ((K, "K"), (V, "V")):
+        assert isinstance(t, torch.Tensor) and t.dim() == 3 and t.is_cuda and t.dtype == torch.float32, \
+            f"{nm}: a 3-D float32 device tensor [slabs, rows, d]"
+        assert t.stride(2) == 1 or t.shape[2] == 1, f"{nm} must have unit inner stride"
+    _require_row_table(row_slab, "row_slab")
+    rows, d = Q.shape
+    assert K.shape[2] == d and V.shape[2] == d, "K and V: [slabs, rows, d], d as Q"
+    assert rows_per_seq >= 1 and rows % rows_per_seq == 0, "Q holds rows_per_seq rows per sequence"
+    n_seqs = rows // rows_per_seq
+    assert n_heads >= 1 and d % n_heads == 0, "d % n_heads == 0"
+    dk = d // n_heads
+    seq_kv = [int(v) for v in seq_kv]
+    trows = list(range(n_seqs)) if tab_row is None else [int(v) for v in tab_row]
+    assert len(seq_kv) == n_seqs and len(trows) == n_seqs, "seq_kv and tab_row: one entry per sequence"
+    n_slabs = min(K.shape[0], V.shape[0])
+    for b in range(n_seqs):  # the table rows, entries and slab rows the call reads exist
+        assert 0 <= trows[b] < row_slab.shape[0], f"tab_row[{b}] names no row of the table"
+        assert seq_kv[b] <= min(K.shape[1], V.shape[1], row_slab.shape[1]), f"seq_kv[{b}] exceeds the slab's rows"
+    if scale is None:
+        scale = ctypes.c_float(1.0 / math.sqrt(float(dk))).value  # attention.cuh:64
+    if O is None:
+        O = torch.empty((rows, d), dtype=torch.float32, device=Q.device)
+    _require_device_f32(O, "O")
+    assert O.shape == (rows, d) and (O.stride(1) == 1 or d == 1), "O: as Q, with unit inner stride"
+    _check("qgemm_attention_decode_indirect",
+           load().qgemm_attention_decode_indirect(
+               Q.data_ptr(), Q.stride(0), K.data_ptr(), K.stride(1), K.stride(0), V.data_ptr(), V.stride(1),
+               V.stride(0), O.data_ptr(), O.stride(0), n_seqs, rows_per_seq, row_slab.data_ptr(),
+               row_slab.stride(0) if row_slab.shape[0] > 1 else row_slab.shape[1], n_slabs,
+               _int_array(tab_row, n_seqs, "tab_row"), _int_array(seq_kv, n_seqs, "seq_kv"),
+               _int_array(q_pos0, n_seqs, "q_pos0"), n_heads, dk, float(scale), _stream(Q.device)))
+    return O
+
+
+def beam_reindex(row_slab, slots, parents, n_rows, beams: int):
+    """Beam search's reorder on a row table, in place (qgemm_beam_reindex): row slots[g * beams + q] takes entries
+    0 .. n_rows[g] - 1 of the old row slots[g * beams + parents[g * beams + q]], 255 for a parent outside [0, beams).
+    row_slab: a 2-D uint8 device tensor or view; parents: int32 on the device; slots and n_rows: host values."""
+    _require_row_table(row_slab, "row_slab")
+    slots = [int(v) for v in slots]
+    rows = len(slots)
+    assert beams >= 1 and rows % beams == 0, "beams slots per group"
+    n = rows // beams
+    n_rows = [int(v) for v in n_rows]
+    assert len(n_rows) == n, "n_rows: one entry per group"
+    _require_device_i32(parents, "parents", rows)
+    assert all(0 <= v < row_slab.shape[0] for v in slots), "slots: rows of the table"
+    assert all(v <= row_slab.shape[1] for v in n_rows), "n_rows: inside a table row"
+    _check("qgemm_beam_reindex",
+           load().qgemm_beam_reindex(row_slab.data_ptr(),
+                                     row_slab.stride(0) if row_slab.shape[0] > 1 else row_slab.shape[1], n, beams,
+                                     _int_array(slots, rows, "slots"), parents.data_ptr(),
+                                     _int_array(n_rows, n, "n_rows"), _stream(row_slab.device)))
+    return row_slab
+
+
 def _int64_array(values, n: int, name: str):
     values = [int(v) for v in values]
     assert len(values) == n, f"{name}: one entry per sequence"
@@ -1223,7 +1322,9 @@ class Decoder:
     (qgemm_decoder_create_slots): the caches hold that many independent sequences on one copy of the weights;
     begin_slot / step_slot drive one of them, step_batch advances many in one step, copy_slot forks one (DESIGN.md s17);
     begin / step are slot 0's.  max_rows (qgemm_decoder_create_rows; a keyword, ahead of n_slots only so that n_slots
-    stays the last parameter): the rows step_varlen may run at once."""
+    stays the last parameter): the rows step_varlen may run at once.  With n_slots > 1 the decoder also
+    owns the row table of the copy-free beam search (beam_begin / step_batch_indirect / beam_reindex / beam_table /
+    generate_beam_indirect)."""
 
     def __init__(self, d_model: int, n_heads: int, d_ff: int, n_blocks: int, max_seq: int, max_enc_seq: int,
                  seed: int = 0, causal: bool = False, kv_cache: bool = False, max_rows=None, n_slots: int = 1):
@@ -1487,6 +1588,106 @@ class Decoder:
                                                   None if scores_in is None else scores_in.data_ptr(), int(eos),
                                                   tokens.data_ptr(), parents.data_ptr(), scores.data_ptr(),
                                                   _stream(tokens_in.device)))
+        return tokens, parents, scores
+
+    def beam_begin(self, slots, src_slots, pos, beams: int):
+        """Start the copy-free search's beams (qgemm_decoder_beam_begin): the slots slots[g * beams + q]
+        of group g get row-table entries 0 .. pos[g] - 1 = src_slots[g], the slot that holds the group's prompt, its
+        enc_seq and filled = pos[g].  Nothing is copied; the slots need not have been begun, and slots[g * beams] may
+        be src_slots[g].  pos None: every prompt's filled length."""
+        slots, src_slots = [int(v) for v in slots], [int(v) for v in src_slots]
+        rows, n = len(slots), len(src_slots)
+        assert beams >= 1 and rows == n * beams, "beams slots per group, one prompt slot per group"
+        if pos is None:
+            pos = [self.slot_filled(v) for v in src_slots]
+            assert None not in pos, "beam_begin() follows every prompt slot's begin_slot()"
+        _check("qgemm_decoder_beam_begin",
+               load().qgemm_decoder_beam_begin(self._h, n, beams, _int_array(slots, rows, "slots"),
+                                               _int_array(src_slots, n, "src_slots"), _int_array(pos, n, "pos"),
+                                               _stream()))
+
+    def step_batch_indirect(self, slots, cross_slots, X_new, pos=None, rows_per_seq: int = 1, Y=None):
+        """step_batch on slots begun by beam_begin (qgemm_decoder_step_batch_indirect): the new K / V rows go into each
+        slot's own slab, the row table names them, the self-attention reads through the table and the cross-attention
+        uses the cross cache of cross_slots[b] (a group's prompt slot)."""
+        import torch
+        _require_device_f32(X_new, "X_new")
+        slots, cross_slots = [int(v) for v in slots], [int(v) for v in cross_slots]
+        n = len(slots)
+        assert len(cross_slots) == n, "cross_slots: one entry per slot"
+        assert X_new.is_contiguous() and X_new.shape == (n * rows_per_seq, self.d_model), \
+            "X_new: (len(slots) * rows_per_seq) x d_model, contiguous"
+        if pos is None:
+            pos = [self.slot_filled(v) for v in slots]
+            assert None not in pos, "step_batch_indirect() follows beam_begin()"
+        Y = torch.empty_like(X_new) if Y is None else Y
+        _require_device_f32(Y, "Y")
+        assert Y.is_contiguous() and Y.shape == X_new.shape
+        _check("qgemm_decoder_step_batch_indirect",
+               load().qgemm_decoder_step_batch_indirect(self._h, n, _int_array(slots, n, "slots"),
+                                                        _int_array(cross_slots, n, "cross_slots"),
+                                                        _int_array(pos, n, "pos"), rows_per_seq, X_new.data_ptr(),
+                                                        Y.data_ptr(), _stream(X_new.device)))
+        return Y
+
+    def beam_reindex(self, slots, parents, n_rows, beams: int):
+        """The search's reorder on the decoder's row table, in place (qgemm_decoder_beam_reindex): slot
+        slots[g * beams + q] continues the hypothesis of slots[g * beams + parents[g * beams + q]] over its first
+        n_rows[g] positions.  parents: int32 on the device; only table bytes move."""
+        slots = [int(v) for v in slots]
+        rows = len(slots)
+        assert beams >= 1 and rows % beams == 0, "beams slots per group"
+        _require_device_i32(parents, "parents", rows)
+        n = rows // beams
+        _check("qgemm_decoder_beam_reindex",
+               load().qgemm_decoder_beam_reindex(self._h, n, beams, _int_array(slots, rows, "slots"),
+                                                 parents.data_ptr(), _int_array(n_rows, n, "n_rows"),
+                                                 _stream(parents.device)))
+
+    def beam_table(self):
+        """A copy of the decoder's row table as it is, uint8 [n_slots, max_seq] on the device
+        (qgemm_decoder_read_beam_table): entry [s][j] is the slot whose slab holds row j of slot s's sequence."""
+        import torch
+        dev = torch.device("cuda", torch.cuda.current_device())
+        out = torch.empty((self.n_slots, self.max_seq), dtype=torch.uint8, device=dev)
+        _check("qgemm_decoder_read_beam_table", load().qgemm_decoder_read_beam_table(self._h, out.data_ptr(),
+                                                                                    _stream(dev)))
+        return out
+
+    def generate_beam_indirect(self, head, slots, src_slots, tokens_in, n_new: int, beams: int, pos=None,
+                               scores_in=None, eos: int = -1, out=None):
+        """generate_beam over ONE slot set without copying a cache row (qgemm_decoder_generate_beam_indirect): per step
+        head.embed, step_batch_indirect (cross slots: the groups' prompt slots src_slots), head.beam_step, beam_reindex
+        by the parents just chosen.  slots: n_groups * beams slots begun by beam_begin from src_slots; up to 64 rows.
+        tokens_in, scores_in, pos, eos and the returned (tokens, parents, scores) are generate_beam's, bit for bit; a
+        second call with tokens[-1] and scores[-1] continues, without another beam_begin."""
+        import torch
+        slots, src_slots = [int(v) for v in slots], [int(v) for v in src_slots]
+        rows, n = len(slots), len(src_slots)
+        assert beams >= 1 and rows == n * beams, "beams slots per group, one prompt slot per group"
+        assert isinstance(tokens_in, torch.Tensor), "tokens_in: an int32 device tensor"
+        if tokens_in.numel() == n and n != rows:
+            tokens_in = tokens_in.repeat_interleave(beams).contiguous()
+        _require_device_i32(tokens_in, "tokens_in", rows)
+        if scores_in is not None:
+            assert scores_in.is_cuda and scores_in.dtype == torch.float32 and scores_in.is_contiguous() and \
+                scores_in.numel() == rows, "scores_in: float32[rows] on the device"
+        if out is None:
+            out = (torch.empty((n_new, rows), dtype=torch.int32, device=tokens_in.device),
+                   torch.empty((n_new, rows), dtype=torch.int32, device=tokens_in.device),
+                   torch.empty((n_new, rows), dtype=torch.float32, device=tokens_in.device))
+        tokens, parents, scores = out
+        _require_device_i32(tokens, "tokens", n_new * rows)
+        _require_device_i32(parents, "parents", n_new * rows)
+        assert scores.is_cuda and scores.dtype == torch.float32 and scores.is_contiguous() and \
+            scores.numel() == n_new * rows, "scores: float32[n_new x rows] on the device"
+        _check("qgemm_decoder_generate_beam_indirect",
+               load().qgemm_decoder_generate_beam_indirect(self._h, head._h, n, beams, _int_array(slots, rows, "slots"),
+                                                           _int_array(src_slots, n, "src_slots"), tokens_in.data_ptr(),
+                                                           n_new, _int_array(pos, n, "pos"),
+                                                           None if scores_in is None else scores_in.data_ptr(),
+                                                           int(eos), tokens.data_ptr(), parents.data_ptr(),
+                                                           scores.data_ptr(), _stream(tokens_in.device)))
         return tokens, parents, scores
 
     def close(self):

@@ -566,6 +566,38 @@ int qgemm_decoder_gather_slots(void *decoder, int n_groups, int beams, const int
                                     static_cast<hipStream_t>(stream)));
 }
 
+int qgemm_attention_decode_indirect(const float *Q, int64_t q_stride_h, const float *K, int64_t k_stride_h,
+                                    int64_t k_stride_seq, const float *V, int64_t v_stride_h, int64_t v_stride_seq,
+                                    float *O, int64_t o_stride_h, int n_seqs, int rows_per_seq, const uint8_t *row_slab,
+                                    int64_t row_slab_stride, int n_slabs, const int *tab_row, const int *seq_kv,
+                                    const int *q_pos0, int n_heads, int d_k, float scale, void *stream) {
+    return err(launch_attention_indirect(Q, q_stride_h, K, k_stride_h, k_stride_seq, V, v_stride_h, v_stride_seq, O,
+                                         o_stride_h, n_seqs, rows_per_seq, row_slab, row_slab_stride, n_slabs, tab_row,
+                                         seq_kv, q_pos0, n_heads, d_k, scale, static_cast<hipStream_t>(stream)));
+}
+
+int qgemm_decoder_beam_begin(void *decoder, int n_groups, int beams, const int *slots, const int *src_slots,
+                             const int *pos, void *stream) {
+    return err(decoder_beam_begin(static_cast<Stack *>(decoder), n_groups, beams, slots, src_slots, pos,
+                                  static_cast<hipStream_t>(stream)));
+}
+
+int qgemm_decoder_step_batch_indirect(void *decoder, int n_seqs, const int *slots, const int *cross_slots,
+                                      const int *pos, int rows_per_seq, const float *X, float *Y, void *stream) {
+    return err(decoder_step_batch_indirect(static_cast<Stack *>(decoder), n_seqs, slots, cross_slots, pos, rows_per_seq,
+                                           X, Y, static_cast<hipStream_t>(stream)));
+}
+
+int qgemm_decoder_beam_reindex(void *decoder, int n_groups, int beams, const int *slots, const int32_t *parents,
+                               const int *n_rows, void *stream) {
+    return err(decoder_beam_reindex(static_cast<Stack *>(decoder), n_groups, beams, slots, parents, n_rows,
+                                    static_cast<hipStream_t>(stream)));
+}
+
+int qgemm_decoder_read_beam_table(void *decoder, uint8_t *out, void *stream) {
+    return err(decoder_read_beam_table(static_cast<Stack *>(decoder), out, static_cast<hipStream_t>(stream)));
+}
+
 int qgemm_decoder_read_slot(void *decoder, int block, int slot, float *self_rows, float *cross_rows, void *stream) {
     return err(decoder_read_slot(static_cast<Stack *>(decoder), block, slot, self_rows, cross_rows,
                                  static_cast<hipStream_t>(stream)));

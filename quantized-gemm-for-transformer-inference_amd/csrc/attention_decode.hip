@@ -30,6 +30,12 @@
 // transformed the chunk loops differently and the single-sequence launch measured 0.2 % slower at 4096 keys; as one
 // kernel template the single-sequence instantiation compiles to the instruction stream it had before, register
 // numbers aside.)
+// The indirect launch is the batched one with a THIRD Seqs type, DecodeIndirect: every key position of
+// a sequence names the slab that holds its K / V row, through a byte table in device memory (beam search's copy-free
+// cache reorder).  The sequence's table row (<= 4096 bytes) is staged in LDS before the first fetch -- one 16-byte piece
+// per thread, one exposed latency per WORKGROUP -- so the byte in front of a K / V address is an LDS read issued with
+// the fetch, two chunks ahead of the data's use, not a second memory latency per chunk.  Only the address of a fetched
+// row and a NaN select in `put` differ; the arithmetic below is the one text.
 #include <type_traits>
 
 #include "qgemm_internal.h"
@@ -59,6 +65,15 @@ struct DecodeMany {
     int rows_per_seq;
     DecodeBatchTable tab;
 };
+// DecodeIndirect: DecodeMany's grid; K / V row j of sequence b is row j of slab row_slab[tab.kv_slot[b] * row_slab_stride
+// + j] (tab.kv_slot holds the sequence's TABLE ROW here), an entry >= n_slabs reads as a row of quiet NaNs.
+struct DecodeIndirect {
+    int64_t k_stride_seq, v_stride_seq;
+    int rows_per_seq, n_slabs;
+    const uint8_t *row_slab;
+    int64_t row_slab_stride;
+    DecodeBatchTable tab;
+};
 
 // ONE kernel text for both launches (the batched decode kernel of DESIGN.md s17 is
 // attention_decode_kernel<kCausal, DecodeMany>): the sequence's parameters are resolved at the top, everything below
@@ -74,7 +89,46 @@ __global__ __launch_bounds__(kDecThreads) void attention_decode_kernel(
     // grid (heads, query rows): with a multiple of 8 heads the rows of a head share an XCD and its L2
     const int h = blockIdx.x, qi = blockIdx.y;
     int seq_kv, q_pos0;
-    if constexpr (std::is_same<Seqs, DecodeMany>::value) {
+    constexpr bool kIndirect = std::is_same<Seqs, DecodeIndirect>::value;
+    // DecodeIndirect alone: the sequence's table row in LDS (own[j] = the slab of key j), the slabs' offsets in K and V
+    // in LDS (ko[e] / vo[e], e the table entry clamped to 63: an entry that names no slab gives the last slab's), the
+    // slab strides and count
+    const uint8_t *own = nullptr;
+    const int64_t *ko = nullptr, *vo = nullptr;
+    int64_t kss = 0, vss = 0;
+    int n_slabs = 0;
+    if constexpr (kIndirect) {
+        // The row starts at any byte: the aligned 16-byte pieces that hold an entry of it are copied as they lie (a
+        // piece that holds a byte of the row lies in that byte's page), and own points `off` bytes into the copy.
+        // A slab's offset is a 64-bit product; 64 of them per matrix are made here once, so that a fetched row costs two
+        // LDS reads in front of its address and no 64-bit multiply (as products per row the launch measured 20 % over
+        // the batched one at 2048 keys with the identity table).
+        __shared__ __attribute__((aligned(16))) uint8_t Own[kDecMaxSeq + 16];
+        __shared__ int64_t SlabOff[2][kDecodeMaxBatch];
+        const int b = blockIdx.z;
+        const int64_t row0 = (int64_t)b * seqs.rows_per_seq;
+        Q += row0 * ldq;
+        O += row0 * ldo;
+        seq_kv = seqs.tab.seq_kv[b];
+        q_pos0 = seqs.tab.q_pos0[b];
+        const uint8_t *tp = seqs.row_slab + seqs.tab.kv_slot[b] * seqs.row_slab_stride;
+        const int off = (int)(reinterpret_cast<uintptr_t>(tp) & 15);
+        // (4096 entries from an odd start span 257 pieces: the first thread takes the last one too)
+        for (int i = threadIdx.x; 16 * i < off + seq_kv; i += kDecThreads)
+            reinterpret_cast<uint4 *>(Own)[i] = reinterpret_cast<const uint4 *>(tp - off)[i];
+        if (threadIdx.x < 2 * kDecodeMaxBatch) {
+            const int e = min((int)threadIdx.x & (kDecodeMaxBatch - 1), seqs.n_slabs - 1);
+            SlabOff[threadIdx.x / kDecodeMaxBatch][threadIdx.x & (kDecodeMaxBatch - 1)] =
+                e * (threadIdx.x < kDecodeMaxBatch ? seqs.k_stride_seq : seqs.v_stride_seq);
+        }
+        __syncthreads();
+        own = Own + off;
+        ko = SlabOff[0];
+        vo = SlabOff[1];
+        kss = seqs.k_stride_seq;
+        vss = seqs.v_stride_seq;
+        n_slabs = seqs.n_slabs;
+    } else if constexpr (std::is_same<Seqs, DecodeMany>::value) {
         const int b = blockIdx.z;
         const int64_t row0 = (int64_t)b * seqs.rows_per_seq, slab = seqs.tab.kv_slot[b];
         Q += row0 * ldq;
@@ -104,22 +158,43 @@ __global__ __launch_bounds__(kDecThreads) void attention_decode_kernel(
     // right after issuing it, and the launch was bound by the exposed latency of each chunk: 139 us at 4096 keys.)
     // The 16-byte alignment test is made once per matrix: every row of a head is aligned when the head's first row is
     // and the row stride is a multiple of 4 floats; anything else (any stride, any d_k) takes the scalar loads.
-    auto aligned = [&](const float *base, int64_t ld) {
-        return (reinterpret_cast<uintptr_t>(base) & 15) == 0 && (ld & 3) == 0 && (dk & 3) == 0;
+    // (DecodeIndirect: ... and the slab stride is one too, every slab starting like the first)
+    auto aligned = [&](const float *base, int64_t ld, int64_t ss) {
+        return (reinterpret_cast<uintptr_t>(base) & 15) == 0 && (ld & 3) == 0 && (dk & 3) == 0 && (ss & 3) == 0;
     };
-    const bool vec_k = aligned(Kb, ldk), vec_v = aligned(Vb, ldv);  // workgroup-uniform
-    auto fetch = [&](float4 (&r)[kDecPer], const float *src, int64_t ld, int c0, bool vec) __attribute__((always_inline)) {
+    const bool vec_k = aligned(Kb, ldk, kss), vec_v = aligned(Vb, ldv, vss);  // workgroup-uniform
+    // DecodeIndirect: nxo[i] = the offset of the slab that holds this thread's row i of the chunk the NEXT fetch
+    // brings (so: the matrix's slab offsets), every table entry clamped into the slabs so that no entry forms an address
+    // outside them; `put` selects the NaNs.  They are read from LDS into registers of their own BEFORE the buffer that
+    // fetch refills is `put`: read inside the fetch, the compiler took the buffer's just-freed registers as the LDS
+    // reads' temporaries and then waited, between a chunk's loads, for loads still in flight into the OTHER buffer
+    // (s_waitcnt vmcnt(6) after the third load), which stalled every fetch on the chunk before it.
+    int64_t nxo[kDecPer];
+    auto slabs_of = [&](const int64_t *so, int c0) __attribute__((always_inline)) {
+#pragma unroll
+        for (int i = 0; i < kDecPer; ++i) {
+            const int row = (t + i * kDecThreads) >> 4;
+            nxo[i] = so[min((int)own[min(c0 + row, seq - 1)], kDecodeMaxBatch - 1)];
+        }
+    };
+    auto slab_at = [&](const float *src, const int64_t *so, int i) __attribute__((always_inline)) {
+        if constexpr (kIndirect) src += nxo[i];
+        return src;
+    };
+    auto fetch = [&](float4 (&r)[kDecPer], const float *src, int64_t ld, const int64_t *ss, int c0,
+                     bool vec) __attribute__((always_inline)) {
         if (vec) {
 #pragma unroll
             for (int i = 0; i < kDecPer; ++i) {
                 const int f = t + i * kDecThreads, row = f >> 4, c4 = f & 15;
-                r[i] = *reinterpret_cast<const float4 *>(src + min(c0 + row, seq - 1) * ld + 4 * min(c4, dk4 - 1));
+                r[i] = *reinterpret_cast<const float4 *>(slab_at(src, ss, i) + min(c0 + row, seq - 1) * ld +
+                                                         4 * min(c4, dk4 - 1));
             }
         } else {
 #pragma unroll
             for (int i = 0; i < kDecPer; ++i) {
                 const int f = t + i * kDecThreads, row = f >> 4, c4 = f & 15;
-                const float *p = src + min(c0 + row, seq - 1) * ld;
+                const float *p = slab_at(src, ss, i) + min(c0 + row, seq - 1) * ld;
                 r[i].x = p[min(4 * c4, dk - 1)];
                 r[i].y = p[min(4 * c4 + 1, dk - 1)];
                 r[i].z = p[min(4 * c4 + 2, dk - 1)];
@@ -132,11 +207,16 @@ __global__ __launch_bounds__(kDecThreads) void attention_decode_kernel(
         for (int i = 0; i < kDecPer; ++i) {
             const int f = t + i * kDecThreads, row = f >> 4, c4 = f & 15;
             const bool in = c0 + row < seq;
+            float4 x = r[i];
+            if constexpr (kIndirect) {  // an entry that names no slab: the row reads as quiet NaNs (under the zeros)
+                const float qn = __uint_as_float(0x7fc00000u);
+                if ((int)own[min(c0 + row, seq - 1)] >= n_slabs) x = make_float4(qn, qn, qn, qn);
+            }
             float4 v;
-            v.x = in && 4 * c4 < dk ? r[i].x : 0.0f;
-            v.y = in && 4 * c4 + 1 < dk ? r[i].y : 0.0f;
-            v.z = in && 4 * c4 + 2 < dk ? r[i].z : 0.0f;
-            v.w = in && 4 * c4 + 3 < dk ? r[i].w : 0.0f;
+            v.x = in && 4 * c4 < dk ? x.x : 0.0f;
+            v.y = in && 4 * c4 + 1 < dk ? x.y : 0.0f;
+            v.z = in && 4 * c4 + 2 < dk ? x.z : 0.0f;
+            v.w = in && 4 * c4 + 3 < dk ? x.w : 0.0f;
             *reinterpret_cast<float4 *>(KV + row * kDecStride + 4 * c4) = v;
         }
     };
@@ -146,11 +226,18 @@ __global__ __launch_bounds__(kDecThreads) void attention_decode_kernel(
     // workgroup, are in flight under every chunk's arithmetic, and the first two V chunks stream in under the softmax
     // and its sum chain
     auto fetch_g = [&](float4 (&r)[kDecPer], int g) __attribute__((always_inline)) {
-        if (g < nck) fetch(r, Kb, ldk, g * kDecChunk, vec_k);
-        else if (g < nck + ncv) fetch(r, Vb, ldv, (g - nck) * kDecChunk, vec_v);
+        if (g < nck) fetch(r, Kb, ldk, ko, g * kDecChunk, vec_k);
+        else if (g < nck + ncv) fetch(r, Vb, ldv, vo, (g - nck) * kDecChunk, vec_v);
+    };
+    // (DecodeIndirect) the slab offsets of chunk g of the stream into nxo
+    auto slabs_g = [&](int g) __attribute__((always_inline)) {
+        if (g < nck) slabs_of(ko, g * kDecChunk);
+        else if (g < nck + ncv) slabs_of(vo, (g - nck) * kDecChunk);
     };
     float4 pfa[kDecPer], pfb[kDecPer];
+    if constexpr (kIndirect) slabs_g(0);
     fetch_g(pfa, 0);
+    if constexpr (kIndirect) slabs_g(1);
     fetch_g(pfb, 1);
     if (t < kDecMaxDk) Qs[t] = t < dk ? Qb[t] : 0.0f;
 
@@ -158,6 +245,7 @@ __global__ __launch_bounds__(kDecThreads) void attention_decode_kernel(
     // reads, the query row as broadcast reads), over d_k zero-padded to 32
     const bool wide = dk > 32;
     auto k_step = [&](float4 (&pf)[kDecPer], int c) __attribute__((always_inline)) {
+        if constexpr (kIndirect) slabs_g(c + 2);
         if (c) __syncthreads();  // every thread is done with the previous chunk
         put(pf, c * kDecChunk);
         __syncthreads();
@@ -239,6 +327,7 @@ __global__ __launch_bounds__(kDecThreads) void attention_decode_kernel(
     // ---- O[i] = p V over every key: lane = output column, the accumulator carried across the chunks in key order
     float acc = 0.0f;
     auto v_step = [&](float4 (&pf)[kDecPer], int c) __attribute__((always_inline)) {
+        if constexpr (kIndirect) slabs_g(nck + c + 2);
         __syncthreads();  // P complete (c = 0) / the previous chunk consumed
         put(pf, c * kDecChunk);
         __syncthreads();
@@ -325,6 +414,31 @@ hipError_t launch_attention_decode_batched(const float *Q, int64_t ldq, const fl
     else
         attention_decode_kernel<false, DecodeMany><<<grid, kDecThreads, 0, stream>>>(Q, ldq, K, ldk, V, ldv, O, ldo, dk,
                                                                                      scale, many);
+    return hipGetLastError();
+}
+
+// tab (kv_slot = the table row) checked and clamped by launch_attention_indirect (attention_launch.hip); what sizes
+// the kernel's LDS arrays and grid, and what keeps every table read inside the table, is tested again here
+hipError_t launch_attention_decode_indirect(const float *Q, int64_t ldq, const float *K, int64_t ldk, int64_t k_stride_seq,
+                                            const float *V, int64_t ldv, int64_t v_stride_seq, float *O, int64_t ldo,
+                                            int n_seqs, int rows_per_seq, const uint8_t *row_slab,
+                                            int64_t row_slab_stride, int n_slabs, const DecodeBatchTable &tab,
+                                            bool causal, int n_heads, int dk, float scale, hipStream_t stream) {
+    if (n_seqs < 1 || n_seqs > kDecodeMaxBatch || rows_per_seq < 1 || rows_per_seq > kAttnDecodeMaxQ || dk < 1 ||
+        dk > kDecMaxDk || n_heads < 1 || !row_slab || n_slabs < 1 || n_slabs > kDecodeMaxBatch)
+        return hipErrorInvalidValue;
+    for (int b = 0; b < n_seqs; ++b)
+        if (tab.seq_kv[b] < 1 || tab.seq_kv[b] > kDecMaxSeq || tab.kv_slot[b] < 0 || tab.q_pos0[b] < 0 ||
+            tab.q_pos0[b] > tab.seq_kv[b] || row_slab_stride < tab.seq_kv[b])
+            return hipErrorInvalidValue;
+    const dim3 grid((unsigned)n_heads, (unsigned)rows_per_seq, (unsigned)n_seqs);
+    const DecodeIndirect ind{k_stride_seq, v_stride_seq, rows_per_seq, n_slabs, row_slab, row_slab_stride, tab};
+    if (causal)
+        attention_decode_kernel<true, DecodeIndirect><<<grid, kDecThreads, 0, stream>>>(Q, ldq, K, ldk, V, ldv, O, ldo,
+                                                                                        dk, scale, ind);
+    else
+        attention_decode_kernel<false, DecodeIndirect><<<grid, kDecThreads, 0, stream>>>(Q, ldq, K, ldk, V, ldv, O, ldo,
+                                                                                         dk, scale, ind);
     return hipGetLastError();
 }
 

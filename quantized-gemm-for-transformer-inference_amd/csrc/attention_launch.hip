@@ -128,4 +128,32 @@ hipError_t launch_attention_batched(const float *Q, int64_t ldq, const float *K,
                                            rows_per_seq, tab, q_pos0 != nullptr, n_heads, dk, scale, stream);
 }
 
+// The same launch through a per-row slab table in device memory (attention_decode.hip, DecodeIndirect).
+// The host arrays are read HERE as above; the table's bytes are read by the kernel.  tab_row == nullptr: table row b
+// for sequence b.  Every check comes before the launch: the batched launch's, and what keeps the kernel's table reads
+// inside the table's rows (a stride that covers seq_kv[b] entries) and its clamp meaningful (1 <= n_slabs <= 64).
+hipError_t launch_attention_indirect(const float *Q, int64_t ldq, const float *K, int64_t ldk, int64_t k_stride_seq,
+                                     const float *V, int64_t ldv, int64_t v_stride_seq, float *O, int64_t ldo, int n_seqs,
+                                     int rows_per_seq, const uint8_t *row_slab, int64_t row_slab_stride, int n_slabs,
+                                     const int *tab_row, const int *seq_kv, const int *q_pos0, int n_heads, int dk,
+                                     float scale, hipStream_t stream) {
+    if (!Q || !K || !V || !O || !seq_kv || !row_slab || n_seqs < 0 || n_seqs > kDecodeMaxBatch || n_heads < 1 ||
+        !attention_decode_ok(rows_per_seq, 1, dk) || rows_per_seq < 1 || dk < 1 || n_slabs < 1 ||
+        n_slabs > kDecodeMaxBatch)
+        return hipErrorInvalidValue;
+    DecodeBatchTable tab = {};  // kv_slot: the table row
+    for (int b = 0; b < n_seqs; ++b) {
+        if (seq_kv[b] < 1 || !attention_decode_ok(rows_per_seq, seq_kv[b], dk) || (q_pos0 && q_pos0[b] < 0) ||
+            (tab_row && tab_row[b] < 0) || row_slab_stride < seq_kv[b])
+            return hipErrorInvalidValue;
+        tab.kv_slot[b] = tab_row ? tab_row[b] : b;
+        tab.seq_kv[b] = seq_kv[b];
+        tab.q_pos0[b] = q_pos0 ? (q_pos0[b] < seq_kv[b] ? q_pos0[b] : seq_kv[b]) : 0;
+    }
+    if (n_seqs == 0) return hipSuccess;
+    return launch_attention_decode_indirect(Q, ldq, K, ldk, k_stride_seq, V, ldv, v_stride_seq, O, ldo, n_seqs,
+                                            rows_per_seq, row_slab, row_slab_stride, n_slabs, tab, q_pos0 != nullptr,
+                                            n_heads, dk, scale, stream);
+}
+
 }  // namespace qgemm

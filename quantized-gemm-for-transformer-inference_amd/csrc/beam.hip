@@ -411,6 +411,72 @@ __global__ __launch_bounds__(256) void gather_kv_kernel(float *cache, int64_t sl
         }
 }
 
+// ---- the row table of the copy-free search --------------------------------------------------------
+// own[s][j]: the slot whose slab holds, at row j, the K and V of position j of the sequence in slot s; one byte each.
+// 16 columns of a table row as they lie: one 16-byte access where the piece is whole and aligned, else byte by byte
+// (the table may start at any byte and have any row stride).  Nothing outside the cnt bytes is touched.
+__device__ __forceinline__ uint4 load_cols(const uint8_t *p, int cnt) {
+    if (cnt == 16 && (reinterpret_cast<uintptr_t>(p) & 15) == 0) return *reinterpret_cast<const uint4 *>(p);
+    uint32_t w[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int j = 0; j < 16; ++j)
+        if (j < cnt) w[j >> 2] |= (uint32_t)p[j] << (8 * (j & 3));
+    return make_uint4(w[0], w[1], w[2], w[3]);
+}
+__device__ __forceinline__ void store_cols(uint8_t *p, uint4 v, int cnt) {
+    if (cnt == 16 && (reinterpret_cast<uintptr_t>(p) & 15) == 0) {
+        *reinterpret_cast<uint4 *>(p) = v;
+        return;
+    }
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int j = 0; j < 16; ++j)
+        if (j < cnt) p[j] = (uint8_t)(w[j >> 2] >> (8 * (j & 3)));
+}
+
+// per place i = g * beams + q its table row, per group its column count: a kernel argument passed by value
+struct ReindexTable {
+    int slot[kBeamMaxRows], n_rows[kBeamMaxRows];
+};
+
+// The reorder, IN PLACE in the one table: thread (g, x) owns columns 16 x .. 16 x + 15 of group g's `beams` rows.  It
+// first reads all `beams` entries of each of its columns and then writes them, new[q][j] = old[parent[q]][j].  The
+// reorder is column-local -- new[.][j] of a group depends on old[.][j] of that group alone -- and no other thread
+// touches this thread's columns of these rows (the groups' rows are distinct: checked on the host), so there is no
+// second table, no barrier and no order to agree on.  A parent outside [0, beams) gives 255, the invalid entry.
+__global__ __launch_bounds__(64) void beam_reindex_kernel(uint8_t *own, int64_t stride, int beams,
+                                                          const int *__restrict__ parents, ReindexTable tab) {
+    const int g = blockIdx.y, c0 = 16 * (blockIdx.x * 64 + threadIdx.x), cnt = min(16, tab.n_rows[g] - c0);
+    if (cnt <= 0) return;
+    uint4 old[kBeamMax];
+#pragma unroll
+    for (int q = 0; q < kBeamMax; ++q)
+        if (q < beams) old[q] = load_cols(own + tab.slot[g * beams + q] * stride + c0, cnt);
+#pragma unroll
+    for (int q = 0; q < kBeamMax; ++q) {
+        if (q >= beams) break;
+        const int par = parents[g * beams + q];
+        uint4 v = make_uint4(~0u, ~0u, ~0u, ~0u);
+#pragma unroll
+        for (int p = 0; p < kBeamMax; ++p)
+            if (p < beams && p == par) v = old[p];
+        store_cols(own + tab.slot[g * beams + q] * stride + c0, v, cnt);
+    }
+}
+
+// entries first[i] .. first[i] + count[i] - 1 of table row slot[i] = value[i]: begin's prefix (the prompt's slot) and
+// a step's append (the slot itself).  By value, 1 KiB.
+struct FillTable {
+    int slot[kBeamMaxRows], first[kBeamMaxRows], count[kBeamMaxRows], value[kBeamMaxRows];
+};
+
+__global__ __launch_bounds__(256) void beam_fill_kernel(uint8_t *own, int64_t stride, FillTable tab) {
+    const int i = blockIdx.y, c0 = 16 * (blockIdx.x * blockDim.x + threadIdx.x), cnt = min(16, tab.count[i] - c0);
+    if (cnt <= 0) return;
+    const uint32_t w = 0x01010101u * (uint32_t)tab.value[i];
+    store_cols(own + tab.slot[i] * stride + tab.first[i] + c0, make_uint4(w, w, w, w), cnt);
+}
+
 // rows * beams <= 64 and 1 <= beams <= 8, from the counts alone
 bool beam_counts_ok(int n_groups, int beams) {
     return n_groups >= 0 && beams >= 1 && beams <= kBeamMax && (int64_t)n_groups * beams <= kBeamMaxRows;
@@ -561,11 +627,72 @@ hipError_t launch_gather_kv(float *cache, int64_t slab_rows, int n_slabs, int d,
     return hipGetLastError();
 }
 
+// The in-place reorder of a row table (beam_reindex_kernel).  Checked here: every table row inside the table, no row
+// named twice (so no two threads share a byte), every column count inside a row -- so no access leaves the named rows'
+// first `stride` bytes.
+hipError_t launch_beam_reindex(uint8_t *own, int64_t stride, int n_table_rows, int n_groups, int beams, const int *slots,
+                               const int *parents, const int *n_rows, hipStream_t s) {
+    if (!own || !slots || !parents || !n_rows || stride < 1 || n_table_rows < 1 || n_table_rows > kBeamMaxRows ||
+        n_groups < 1 || !beam_counts_ok(n_groups, beams))
+        return hipErrorInvalidValue;
+    ReindexTable tab = {};
+    uint64_t seen = 0;  // n_table_rows <= 64
+    int max_n = 0;
+    for (int g = 0; g < n_groups; ++g) {
+        if (n_rows[g] < 0 || n_rows[g] > stride) return hipErrorInvalidValue;
+        tab.n_rows[g] = n_rows[g];
+        max_n = std::max(max_n, n_rows[g]);
+        for (int q = 0; q < beams; ++q) {
+            const int sl = slots[g * beams + q];
+            if (sl < 0 || sl >= n_table_rows || (seen >> sl & 1)) return hipErrorInvalidValue;
+            seen |= (uint64_t)1 << sl;
+            tab.slot[g * beams + q] = sl;
+        }
+    }
+    if (max_n == 0) return hipSuccess;
+    const dim3 grid((unsigned)((max_n + 16 * 64 - 1) / (16 * 64)), (unsigned)n_groups);
+    beam_reindex_kernel<<<grid, 64, 0, s>>>(own, stride, beams, parents, tab);
+    return hipGetLastError();
+}
+
+// Constant runs into a row table (beam_fill_kernel): row slots[i] gets value[i] at entries first[i] .. + count[i] - 1.
+// Checked here: every row inside the table, every run inside a row, every value a byte.  Rows may repeat (the runs of
+// one call are the caller's to keep apart).
+hipError_t launch_beam_fill(uint8_t *own, int64_t stride, int n_table_rows, int n, const int *slots, const int *first,
+                            const int *count, const int *value, hipStream_t s) {
+    if (!own || !slots || !first || !count || !value || stride < 1 || n_table_rows < 1 ||
+        n_table_rows > kBeamMaxRows || n < 1 || n > kBeamMaxRows)
+        return hipErrorInvalidValue;
+    FillTable tab = {};
+    int max_n = 0;
+    for (int i = 0; i < n; ++i) {
+        if (slots[i] < 0 || slots[i] >= n_table_rows || first[i] < 0 || count[i] < 0 || first[i] > stride - count[i] ||
+            value[i] < 0 || value[i] > 255)
+            return hipErrorInvalidValue;
+        tab.slot[i] = slots[i];
+        tab.first[i] = first[i];
+        tab.count[i] = count[i];
+        tab.value[i] = value[i];
+        max_n = std::max(max_n, count[i]);
+    }
+    if (max_n == 0) return hipSuccess;
+    const int threads = max_n <= 16 * 64 ? 64 : 256;
+    const dim3 grid((unsigned)((max_n + 16 * threads - 1) / (16 * threads)), (unsigned)n);
+    beam_fill_kernel<<<grid, threads, 0, s>>>(own, stride, tab);
+    return hipGetLastError();
+}
+
 }  // namespace qgemm
 
 using namespace qgemm;
 
 extern "C" {
+
+int qgemm_beam_reindex(uint8_t *row_slab, int64_t row_slab_stride, int n_groups, int beams, const int *slots,
+                       const int32_t *parents, const int *n_rows, void *stream) {
+    return (int)launch_beam_reindex(row_slab, row_slab_stride, kBeamMaxRows, n_groups, beams, slots, parents, n_rows,
+                                    static_cast<hipStream_t>(stream));
+}
 
 int qgemm_logsumexp_rows_plan(int64_t rows, int w, int *parts) {
     int p, bpp;

@@ -365,7 +365,8 @@ int generate_steps(void *decoder, void *head, int n_seqs, const int *slots, cons
     uint64_t seen = 0;  // n_slots <= 64
     for (int b = 0; b < n_seqs; ++b) {
         int enc_seq, filled;
-        if (decoder_slot_state(S, slots[b], &enc_seq, &filled) || enc_seq < 1 || (seen >> slots[b] & 1))
+        if (decoder_slot_state(S, slots[b], &enc_seq, &filled) || enc_seq < 1 || decoder_slot_indirect(S, slots[b]) ||
+            (seen >> slots[b] & 1))
             return (int)hipErrorInvalidValue;
         seen |= (uint64_t)1 << slots[b];
         at[b] = pos ? pos[b] : filled;
@@ -425,7 +426,8 @@ int generate_beam_steps(void *decoder, void *head, int n_groups, int beams, cons
             int enc_a, enc_b, filled_a, filled_b;
             if (decoder_slot_state(S, slots_a[r], &enc_a, &filled_a) ||
                 decoder_slot_state(S, slots_b[r], &enc_b, &filled_b) || enc_a < 1 || enc_b != enc_a ||
-                slots_a[r] == slots_b[r] || (seen >> slots_a[r] & 1) || (seen >> slots_b[r] & 1))
+                slots_a[r] == slots_b[r] || (seen >> slots_a[r] & 1) || (seen >> slots_b[r] & 1) ||
+                decoder_slot_indirect(S, slots_a[r]) || decoder_slot_indirect(S, slots_b[r]))
                 return (int)hipErrorInvalidValue;
             seen |= (uint64_t)1 << slots_a[r] | (uint64_t)1 << slots_b[r];
             if (q == 0) {
@@ -456,6 +458,66 @@ int generate_beam_steps(void *decoder, void *head, int n_groups, int beams, cons
         tok = next;
         sc = nsc;
         std::swap(cur, other);
+        for (int r = 0; r < rows; ++r) ++at[r];
+    }
+    return 0;
+}
+
+// Beam search over ONE set of rows = n_groups * beams cache slots: every check first, then n_new x
+// (embed, step_batch_indirect with the groups' prompt slots as cross slots, the head's beam step, the in-place reindex
+// of the row table by the parents just chosen) on the stream.  No K / V row is copied; rows may fill the decoder's
+// slots and the head's max_rows (the copy path's cap of 32 belonged to its two sets).  What step_batch_indirect and
+// beam_reindex would refuse at step t is refused here, before the first launch.
+int generate_beam_indirect_steps(void *decoder, void *head, int n_groups, int beams, const int *slots,
+                                 const int *src_slots, const int32_t *tokens_in, int n_new, const int *pos,
+                                 const float *scores_in, int eos, int32_t *tokens_out, int32_t *parents_out,
+                                 float *scores_out, void *stream) {
+    Stack *S = static_cast<Stack *>(decoder);
+    Head *h = static_cast<Head *>(head);
+    int d_model, d_k, max_seq, n_slots;
+    if (!h || !h->E || !slots || !src_slots || !tokens_in || n_new < 0 ||
+        decoder_limits(S, &d_model, &d_k, &max_seq, &n_slots))
+        return (int)hipErrorInvalidValue;
+    if (n_groups < 1 || head_beam_check(h, n_groups, beams) != hipSuccess || n_groups * beams > kEmbedMaxSeqs ||
+        n_groups * beams > n_slots || d_model != h->d_model || d_k > 64 ||
+        (n_new > 0 && (!tokens_out || !parents_out || !scores_out)))
+        return (int)hipErrorInvalidValue;
+    const int rows = n_groups * beams;
+    int at[kEmbedMaxSeqs], cross[kEmbedMaxSeqs], next_rows[kEmbedMaxSeqs];  // per row, per row, per group
+    uint64_t seen = 0;                                                      // n_slots <= 64
+    for (int g = 0; g < n_groups; ++g) {
+        int enc_src, filled_src, start = 0;
+        if (decoder_slot_state(S, src_slots[g], &enc_src, &filled_src) || enc_src < 1) return (int)hipErrorInvalidValue;
+        for (int q = 0; q < beams; ++q) {
+            const int r = g * beams + q;
+            int enc, filled;
+            if (decoder_slot_state(S, slots[r], &enc, &filled) || !decoder_slot_indirect(S, slots[r]) ||
+                enc != enc_src || (seen >> slots[r] & 1))
+                return (int)hipErrorInvalidValue;
+            seen |= (uint64_t)1 << slots[r];
+            if (q == 0) start = pos ? pos[g] : filled;
+            if (start < 0 || start > filled || n_new > max_seq - start || (h->P && n_new > h->max_pos - start))
+                return (int)hipErrorInvalidValue;
+            at[r] = start;
+            cross[r] = src_slots[g];
+        }
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    float *X = h->rows, *Y = h->rows + (size_t)h->max_rows * h->d_model;
+    const int32_t *tok = tokens_in;
+    const float *sc = scores_in;
+    for (int t = 0; t < n_new; ++t) {
+        int32_t *next = tokens_out + (size_t)t * rows, *par = parents_out + (size_t)t * rows;
+        float *nsc = scores_out + (size_t)t * rows;
+        for (int g = 0; g < n_groups; ++g) next_rows[g] = at[g * beams] + 1;
+        hipError_t e;
+        if ((e = head_embed(h, tok, at, rows, 1, X, d_model, s)) != hipSuccess ||
+            (e = decoder_step_batch_indirect(S, rows, slots, cross, at, 1, X, Y, s)) != hipSuccess ||
+            (e = head_beam_step(h, Y, d_model, n_groups, beams, sc, tok, eos, par, next, nsc, s)) != hipSuccess ||
+            (e = decoder_beam_reindex(S, n_groups, beams, slots, par, next_rows, s)) != hipSuccess)
+            return (int)e;
+        tok = next;
+        sc = nsc;
         for (int r = 0; r < rows; ++r) ++at[r];
     }
     return 0;
@@ -587,6 +649,14 @@ int qgemm_decoder_generate_beam(void *decoder, void *head, int n_groups, int bea
                                 float *scores_out, void *stream) {
     return generate_beam_steps(decoder, head, n_groups, beams, slots_a, slots_b, tokens_in, n_new, pos, scores_in, eos,
                                tokens_out, parents_out, scores_out, stream);
+}
+
+int qgemm_decoder_generate_beam_indirect(void *decoder, void *head, int n_groups, int beams, const int *slots,
+                                         const int *src_slots, const int32_t *tokens_in, int n_new, const int *pos,
+                                         const float *scores_in, int eos, int32_t *tokens_out, int32_t *parents_out,
+                                         float *scores_out, void *stream) {
+    return generate_beam_indirect_steps(decoder, head, n_groups, beams, slots, src_slots, tokens_in, n_new, pos,
+                                        scores_in, eos, tokens_out, parents_out, scores_out, stream);
 }
 
 }  // extern "C"

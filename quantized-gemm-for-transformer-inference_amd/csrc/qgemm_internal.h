@@ -362,6 +362,15 @@ hipError_t launch_attention_decode_batched(const float *Q, int64_t ldq, const fl
                                            const float *V, int64_t ldv, int64_t v_stride_seq, float *O, int64_t ldo,
                                            int n_seqs, int rows_per_seq, const DecodeBatchTable &tab, bool causal,
                                            int n_heads, int dk, float scale, hipStream_t stream);
+// The batched launch through a per-row slab table (attention_decode_kernel<., DecodeIndirect>): K / V
+// row j of sequence b is row j of slab row_slab[tab.kv_slot[b] * row_slab_stride + j] -- tab.kv_slot holds the
+// sequence's table ROW here -- row_slab a uint8 array in device memory, any alignment; an entry >= n_slabs reads as a
+// row of quiet NaNs and forms no address outside the slabs.  tab already checked and clamped.
+hipError_t launch_attention_decode_indirect(const float *Q, int64_t ldq, const float *K, int64_t ldk, int64_t k_stride_seq,
+                                            const float *V, int64_t ldv, int64_t v_stride_seq, float *O, int64_t ldo,
+                                            int n_seqs, int rows_per_seq, const uint8_t *row_slab,
+                                            int64_t row_slab_stride, int n_slabs, const DecodeBatchTable &tab,
+                                            bool causal, int n_heads, int dk, float scale, hipStream_t stream);
 // The fused launch over a table of independent sequences of their own lengths (attention_fused_kernel<., FusedMany>,
 // DESIGN.md s19): sequence b has seq_q[b] query / output rows from row q_row0[b] of Q / O, seq_kv[b] keys from row
 // kv_row0[b] of K / V and mask offset q_pos0[b]; item0 is the work map, the first workgroup of each sequence, filled
@@ -395,6 +404,13 @@ hipError_t launch_attention_batched(const float *Q, int64_t ldq, const float *K,
                                     const float *V, int64_t ldv, int64_t v_stride_seq, float *O, int64_t ldo, int n_seqs,
                                     int rows_per_seq, const int *kv_slot, const int *seq_kv, const int *q_pos0,
                                     int n_heads, int dk, float scale, hipStream_t stream);
+// the indirect launch from host arrays (tab_row nullptr: 0, 1, 2, ..): launch_attention_batched's checks, and a null
+// table, n_slabs < 1 or > 64, row_slab_stride < seq_kv[b], tab_row[b] < 0
+hipError_t launch_attention_indirect(const float *Q, int64_t ldq, const float *K, int64_t ldk, int64_t k_stride_seq,
+                                     const float *V, int64_t ldv, int64_t v_stride_seq, float *O, int64_t ldo, int n_seqs,
+                                     int rows_per_seq, const uint8_t *row_slab, int64_t row_slab_stride, int n_slabs,
+                                     const int *tab_row, const int *seq_kv, const int *q_pos0, int n_heads, int dk,
+                                     float scale, hipStream_t stream);
 // the kernel launch_attention takes for a shape (qgemm_attention_plan): a static string
 const char *attention_plan_name(int seq_q, int seq_kv, int dk);
 // whether a call of at most max_q query rows and max_kv keys can reach the three launches, and so needs `scores`
@@ -505,6 +521,26 @@ hipError_t launch_gather_kv(float *cache, int64_t slab_rows, int n_slabs, int d,
 // the decoder's side of it (transformer.hip): the checks on the slots' state, one launch_gather_kv per block, filled
 hipError_t decoder_gather_slots(Stack *S, int n_groups, int beams, const int *dst_slots, const int *src_slots,
                                 const int *parents, const int *n_rows, hipStream_t s);
+// Copy-free beam search (the contracts are at qgemm_beam_reindex and qgemm_decoder_beam_begin in
+// include/qgemm.h).  The table kernels (beam.hip) work on a uint8 table of n_table_rows rows, `stride` bytes apart, and
+// take their slots, values and counts from host arrays in the kernel arguments; each checks that every byte it touches
+// lies in a named row's first `stride` bytes before its launch.
+//   reindex: own[slots[g * beams + q]][j] = old own[slots[g * beams + parents[g * beams + q]]][j], j < n_rows[g], in place
+//   fill:    own[slots[i]][first[i] .. first[i] + count[i] - 1] = value[i], i < n
+hipError_t launch_beam_reindex(uint8_t *own, int64_t stride, int n_table_rows, int n_groups, int beams, const int *slots,
+                               const int *parents, const int *n_rows, hipStream_t s);
+hipError_t launch_beam_fill(uint8_t *own, int64_t stride, int n_table_rows, int n, const int *slots, const int *first,
+                            const int *count, const int *value, hipStream_t s);
+// the decoder's side (transformer.hip): the state checks, the launches, enc_seq / filled / the slots' indirect flag
+hipError_t decoder_beam_begin(Stack *S, int n_groups, int beams, const int *slots, const int *src_slots, const int *pos,
+                              hipStream_t s);
+hipError_t decoder_step_batch_indirect(Stack *S, int n_seqs, const int *slots, const int *cross_slots, const int *pos,
+                                       int rows_per_seq, const float *X, float *Y, hipStream_t s);
+hipError_t decoder_beam_reindex(Stack *S, int n_groups, int beams, const int *slots, const int *parents,
+                                const int *n_rows, hipStream_t s);
+hipError_t decoder_read_beam_table(const Stack *S, uint8_t *out, hipStream_t s);
+// whether the slot was begun by decoder_beam_begin (its slab does not hold its own sequence); false out of range
+bool decoder_slot_indirect(const Stack *S, int slot);
 // Quantization-error statistics on the device (error_stats.hip); scratch = error_stats_scratch_bytes().
 size_t error_stats_scratch_bytes();
 hipError_t launch_error_stats(const float *C, const float *O, int64_t n, bool reference_order, double *stats,

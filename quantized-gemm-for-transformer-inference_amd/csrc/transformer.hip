@@ -120,6 +120,15 @@ struct Stack {
     // per slot, host side, updated at enqueue time: enc_seq of the sequence begun (0: no begin yet) and the filled
     // length (cache rows 0 .. filled - 1 hold the sequence so far)
     std::vector<int> enc_seq, filled;
+    // the copy-free beam search, n_slots > 1 only: ONE row table for all blocks, n_slots x max_seq bytes
+    // on the device, own[s][j] = the slot whose self slab holds row j of the sequence in slot s (the identity at
+    // creation), and per slot the host flag that beam_begin sets and begin_slot clears: the slot's slab does not hold
+    // its own sequence, so the plain calls refuse it.  own_rows (flagged slots): the leading rows of the slot's slab that
+    // still hold the plain sequence it had -- what beam_begin may name as a prompt again (a slot that is place 0 of its
+    // own group keeps its prompt rows: begin copies nothing and a step writes at or past its position)
+    uint8_t *own = nullptr;
+    std::vector<char> indirect;
+    std::vector<int> own_rows;
     std::vector<Block> blocks;
     float *qkv = nullptr, *scores = nullptr, *heads = nullptr, *t = nullptr, *ffn = nullptr, *x = nullptr;
     float *xa = nullptr, *xb = nullptr;
@@ -193,7 +202,8 @@ void stack_destroy(Stack *S) {
                         (void *)b.qkv_cache, (void *)b.kv2_cache})
             (void)hipFree(p);
     for (void *p : {(void *)S->qkv, (void *)S->scores, (void *)S->heads, (void *)S->t, (void *)S->ffn, (void *)S->x,
-                    (void *)S->q2, (void *)S->kv2, (void *)S->heads2, (void *)S->xa, (void *)S->xb, (void *)S->ws})
+                    (void *)S->q2, (void *)S->kv2, (void *)S->heads2, (void *)S->xa, (void *)S->xb, (void *)S->ws,
+                    (void *)S->own})
         (void)hipFree(p);
     delete S;
 }
@@ -230,6 +240,8 @@ hipError_t stack_create(int d_model, int n_heads, int d_ff, int n_blocks, int ma
     S->scratch_rows = std::max(n_slots > 1 ? std::max(max_seq, 8 * n_slots) : max_seq, max_rows);
     S->enc_seq.assign(n_slots, 0);
     S->filled.assign(n_slots, 0);
+    S->indirect.assign(n_slots, 0);
+    S->own_rows.assign(n_slots, 0);
     S->blocks.resize(n_blocks);
     const int d = d_model, dk = d_model / n_heads;
     const int rows = S->scratch_rows;
@@ -263,6 +275,13 @@ hipError_t stack_create(int d_model, int n_heads, int d_ff, int n_blocks, int ma
     const size_t ws_bytes = S->scratch_bytes + S->act_bytes + (cross ? packed_bytes(max_enc_seq, d) : 0);
     if ((e = alloc(reinterpret_cast<void **>(&S->ws), ws_bytes))) return fail(e);
     if ((e = hipMemset(S->ws, 0, S->scratch_bytes))) return fail(e);  // split-K tickets start at zero
+    if (n_slots > 1) {  // the row table, allocated here and never in a step: the identity
+        std::vector<uint8_t> ident((size_t)n_slots * max_seq);
+        for (int sl = 0; sl < n_slots; ++sl) std::fill_n(ident.begin() + (size_t)sl * max_seq, max_seq, (uint8_t)sl);
+        if ((e = alloc(reinterpret_cast<void **>(&S->own), ident.size())) ||
+            (e = hipMemcpy(S->own, ident.data(), ident.size(), hipMemcpyHostToDevice)))
+            return fail(e);
+    }
 
     // weights, drawn once with the reference's init bounds (attention.cuh:37-41, linear.cuh:34-39,
     // transformer.cu:53, :120, :144) and packed
@@ -346,8 +365,9 @@ hipError_t launch_scatter_kv(const float *qkv, int64_t scratch_rows, float *cach
 // A batched step's sequences (decoder_step_batch): the tables of its two attention launches
 struct BatchStep {
     int n_seqs, rows_per_seq;
-    DecodeBatchTable self;   // kv_slot = the slot, seq_kv = pos + rows_per_seq, q_pos0 = pos
-    DecodeBatchTable cross;  // kv_slot = the slot, seq_kv = the slot's enc_seq, no mask
+    bool indirect;           // the self-attention reads through the row table (decoder_step_batch_indirect)
+    DecodeBatchTable self;   // kv_slot = the slot (indirect: its table row), seq_kv = pos + rows_per_seq, q_pos0 = pos
+    DecodeBatchTable cross;  // kv_slot = the slot (indirect: cross_slots[b]), seq_kv = that slot's enc_seq, no mask
     ScatterTable scatter;    // slot, pos, row0 = b * rows_per_seq, n_rows = rows_per_seq
 };
 
@@ -399,11 +419,16 @@ hipError_t run_blocks(Stack *S, const float *X, float *Y, int rows, int enc_seq,
             if ((e = launch_scatter_kv(qkv, S->scratch_rows, B.qkv_cache, S->max_seq, S->n_slots, d, batch->n_seqs,
                                        batch->scatter, s)))
                 return e;
-            if ((e = launch_attention_decode_batched(qkv, 3 * d, B.qkv_cache + d, 3 * d, self_slab,
-                                                     B.qkv_cache + 2 * d, 3 * d, self_slab, S->heads, d, batch->n_seqs,
-                                                     batch->rows_per_seq, batch->self, /*causal=*/true, H, dk, scale,
-                                                     s)))
-                return e;
+            // (indirect: row j of the sequence is row j of slab own[slot][j], the new rows its own slab's)
+            e = batch->indirect
+                    ? launch_attention_decode_indirect(qkv, 3 * d, B.qkv_cache + d, 3 * d, self_slab, B.qkv_cache + 2 * d,
+                                                       3 * d, self_slab, S->heads, d, batch->n_seqs, batch->rows_per_seq,
+                                                       S->own, S->max_seq, S->n_slots, batch->self, /*causal=*/true, H,
+                                                       dk, scale, s)
+                    : launch_attention_decode_batched(qkv, 3 * d, B.qkv_cache + d, 3 * d, self_slab, B.qkv_cache + 2 * d,
+                                                      3 * d, self_slab, S->heads, d, batch->n_seqs, batch->rows_per_seq,
+                                                      batch->self, /*causal=*/true, H, dk, scale, s);
+            if (e) return e;
         } else if (var) {
             // a step's sequences see their slots' cache rows, the new ones scattered here; a forward's their own rows
             // of the scratch
@@ -513,12 +538,13 @@ hipError_t decoder_begin_slot(Stack *S, int slot, const float *enc_out, int enc_
             return e;
     S->enc_seq[slot] = enc_seq;
     S->filled[slot] = 0;
+    S->indirect[slot] = 0;  // the slab is the slot's own again (rows 0 .. filled - 1: none)
     return hipSuccess;
 }
 
 hipError_t decoder_step_slot(Stack *S, int slot, const float *X, float *Y, int pos, int n, hipStream_t s) {
-    if (!S || !S->cross || !S->kv_cache || slot < 0 || slot >= S->n_slots || S->enc_seq[slot] < 1 || !X || !Y || n < 1 ||
-        pos < 0 || pos > S->filled[slot] || n > S->max_seq - pos)
+    if (!S || !S->cross || !S->kv_cache || slot < 0 || slot >= S->n_slots || S->enc_seq[slot] < 1 ||
+        S->indirect[slot] || !X || !Y || n < 1 || pos < 0 || pos > S->filled[slot] || n > S->max_seq - pos)
         return hipErrorInvalidValue;
     const hipError_t e = run_blocks(S, X, Y, n, S->enc_seq[slot], /*cached=*/true, slot, pos, nullptr, s);
     if (e) return e;
@@ -539,7 +565,7 @@ hipError_t decoder_step_batch(Stack *S, int n_seqs, const int *slots, const int 
     uint64_t seen = 0;  // n_slots <= 64
     for (int b = 0; b < n_seqs; ++b) {
         const int sl = slots[b];
-        if (sl < 0 || sl >= S->n_slots || S->enc_seq[sl] < 1 || (seen >> sl & 1) || pos[b] < 0 ||
+        if (sl < 0 || sl >= S->n_slots || S->enc_seq[sl] < 1 || S->indirect[sl] || (seen >> sl & 1) || pos[b] < 0 ||
             pos[b] > S->filled[sl] || r > S->max_seq - pos[b])
             return hipErrorInvalidValue;
         seen |= (uint64_t)1 << sl;
@@ -571,7 +597,8 @@ hipError_t decoder_step_varlen(Stack *S, int n_seqs, const int *slots, const int
     int64_t rows = 0;
     for (int b = 0; b < n_seqs; ++b) {
         const int sl = slots[b], n = n_rows[b];
-        if (sl < 0 || sl >= S->n_slots || S->enc_seq[sl] < 1 || (seen >> sl & 1) || n < 1 || pos[b] < 0 ||
+        if (sl < 0 || sl >= S->n_slots || S->enc_seq[sl] < 1 || S->indirect[sl] || (seen >> sl & 1) || n < 1 ||
+            pos[b] < 0 ||
             pos[b] > S->filled[sl] || n > S->max_seq - pos[b])
             return hipErrorInvalidValue;
         seen |= (uint64_t)1 << sl;
@@ -599,7 +626,7 @@ hipError_t decoder_step_varlen(Stack *S, int n_seqs, const int *slots, const int
 // stream order: dst then continues src's sequence on its own (beam search)
 hipError_t decoder_copy_slot(Stack *S, int dst, int src, hipStream_t s) {
     if (!S || !S->cross || !S->kv_cache || dst < 0 || dst >= S->n_slots || src < 0 || src >= S->n_slots || dst == src ||
-        S->enc_seq[src] < 1)
+        S->enc_seq[src] < 1 || S->indirect[src])
         return hipErrorInvalidValue;
     const int64_t d = S->d_model, self_slab = S->max_seq * 3 * d, cross_slab = S->max_enc_seq * 2 * d;
     const size_t self_bytes = sizeof(float) * (size_t)S->filled[src] * 3 * d;
@@ -632,7 +659,7 @@ hipError_t decoder_gather_slots(Stack *S, int n_groups, int beams, const int *ds
         for (int q = 0; q < beams; ++q) {
             const int ds = dst_slots[g * beams + q], ss = src_slots[g * beams + q];
             if (ds < 0 || ds >= S->n_slots || ss < 0 || ss >= S->n_slots || S->enc_seq[ds] < 1 || S->enc_seq[ss] < 1 ||
-                (is_dst >> ds & 1) || n_rows[g] > S->filled[ss] ||
+                S->indirect[ss] || (is_dst >> ds & 1) || n_rows[g] > S->filled[ss] ||
                 S->enc_seq[ds] != S->enc_seq[src_slots[g * beams]] || S->enc_seq[ss] != S->enc_seq[src_slots[g * beams]])
                 return hipErrorInvalidValue;
             is_dst |= (uint64_t)1 << ds;
@@ -648,6 +675,131 @@ hipError_t decoder_gather_slots(Stack *S, int n_groups, int beams, const int *ds
     for (int g = 0; g < n_groups; ++g)
         for (int q = 0; q < beams; ++q) S->filled[dst_slots[g * beams + q]] = n_rows[g];
     return hipSuccess;
+}
+
+// ---- the copy-free beam search: the row table's three operations ----------------------------------
+namespace {
+
+bool has_table(const Stack *S) { return S && S->cross && S->kv_cache && S->own; }
+
+// rows = n_groups * beams places in all, within the table kernels' 64
+bool beam_places_ok(int n_groups, int beams) {
+    return n_groups >= 1 && beams >= 1 && beams <= 8 && (int64_t)n_groups * beams <= kDecodeMaxBatch;
+}
+
+// the leading rows of the slot's own slab that hold a plain sequence: what a prompt may lend
+int plain_rows(const Stack *S, int slot) { return S->indirect[slot] ? S->own_rows[slot] : S->filled[slot]; }
+
+}  // namespace
+
+// begin: entries 0 .. pos[g] - 1 of every slot of group g name src_slots[g], the slot that holds the group's prompt; no
+// K / V row and no cross cache is copied.  A destination may be its own group's source (place 0 only, and then no
+// other group may name that source): any other overlap of the lists would let a search write into a prompt.  Such a
+// slot keeps its prompt rows, so the same begin may be enqueued again (a captured search, a second search).
+hipError_t decoder_beam_begin(Stack *S, int n_groups, int beams, const int *slots, const int *src_slots, const int *pos,
+                              hipStream_t s) {
+    if (!has_table(S) || !slots || !src_slots || !pos || !beam_places_ok(n_groups, beams)) return hipErrorInvalidValue;
+    const int rows = n_groups * beams;
+    int first[kDecodeMaxBatch], count[kDecodeMaxBatch], value[kDecodeMaxBatch];
+    uint64_t seen = 0;  // n_slots <= 64
+    for (int g = 0; g < n_groups; ++g) {
+        const int src = src_slots[g];
+        if (src < 0 || src >= S->n_slots || S->enc_seq[src] < 1 || pos[g] < 0 || pos[g] > plain_rows(S, src))
+            return hipErrorInvalidValue;
+        for (int q = 0; q < beams; ++q) {
+            const int i = g * beams + q, sl = slots[i];
+            if (sl < 0 || sl >= S->n_slots || (seen >> sl & 1)) return hipErrorInvalidValue;
+            seen |= (uint64_t)1 << sl;
+            for (int g2 = 0; g2 < n_groups; ++g2)
+                if (sl == src_slots[g2] && !(g2 == g && q == 0)) return hipErrorInvalidValue;
+            first[i] = 0;
+            count[i] = pos[g];
+            value[i] = src;
+        }
+    }
+    const hipError_t e = launch_beam_fill(S->own, S->max_seq, S->n_slots, rows, slots, first, count, value, s);
+    if (e) return e;
+    for (int g = 0; g < n_groups; ++g)
+        for (int q = 0; q < beams; ++q) {
+            const int sl = slots[g * beams + q];
+            S->own_rows[sl] = sl == src_slots[g] ? pos[g] : 0;  // (rows at or past pos: the search's to overwrite)
+            S->enc_seq[sl] = S->enc_seq[src_slots[g]];
+            S->filled[sl] = pos[g];
+            S->indirect[sl] = 1;
+        }
+    return hipSuccess;
+}
+
+// step_batch on slots begun by beam_begin, with the append: the new [K | V] into the slot's own slab (the scatter),
+// own[slot][pos .. pos + r - 1] = slot (ONE launch per step: the table serves every block), the self-attention through
+// the table, the cross-attention on the slab of cross_slots[b] (a group's beams share their prompt's cross cache).
+hipError_t decoder_step_batch_indirect(Stack *S, int n_seqs, const int *slots, const int *cross_slots, const int *pos,
+                                       int rows_per_seq, const float *X, float *Y, hipStream_t s) {
+    if (!has_table(S) || !slots || !cross_slots || !pos || !X || !Y || n_seqs < 1 || n_seqs > S->n_slots ||
+        rows_per_seq < 1 || rows_per_seq > 8)
+        return hipErrorInvalidValue;
+    const int r = rows_per_seq;
+    if (!attention_decode_ok(r, 1, S->d_model / S->n_heads)) return hipErrorInvalidValue;
+    BatchStep bs = {};
+    bs.n_seqs = n_seqs;
+    bs.rows_per_seq = r;
+    bs.indirect = true;
+    int count[kDecodeMaxBatch];
+    uint64_t seen = 0;  // n_slots <= 64
+    for (int b = 0; b < n_seqs; ++b) {
+        const int sl = slots[b], cs = cross_slots[b];
+        if (sl < 0 || sl >= S->n_slots || !S->indirect[sl] || (seen >> sl & 1) || cs < 0 || cs >= S->n_slots ||
+            S->enc_seq[cs] < 1 || S->enc_seq[cs] != S->enc_seq[sl] || pos[b] < 0 || pos[b] > S->filled[sl] ||
+            r > S->max_seq - pos[b])
+            return hipErrorInvalidValue;
+        seen |= (uint64_t)1 << sl;
+        bs.self.kv_slot[b] = sl;
+        bs.self.seq_kv[b] = pos[b] + r;
+        bs.self.q_pos0[b] = pos[b];
+        bs.cross.kv_slot[b] = cs;
+        bs.cross.seq_kv[b] = S->enc_seq[cs];
+        bs.scatter.slot[b] = sl;
+        bs.scatter.pos[b] = pos[b];
+        bs.scatter.row0[b] = b * r;
+        bs.scatter.n_rows[b] = r;
+        count[b] = r;
+    }
+    hipError_t e = launch_beam_fill(S->own, S->max_seq, S->n_slots, n_seqs, slots, pos, count, slots, s);
+    if (e) return e;
+    if ((e = run_blocks(S, X, Y, n_seqs * r, 0, /*cached=*/true, 0, 0, &bs, s))) return e;
+    for (int b = 0; b < n_seqs; ++b) {
+        S->filled[slots[b]] = pos[b] + r;
+        S->own_rows[slots[b]] = std::min(S->own_rows[slots[b]], pos[b]);  // a rewind into the prompt overwrites it
+    }
+    return hipSuccess;
+}
+
+// reindex: the table rows of a group's slots reordered in place by the parents on the device (beam.hip)
+hipError_t decoder_beam_reindex(Stack *S, int n_groups, int beams, const int *slots, const int *parents,
+                                const int *n_rows, hipStream_t s) {
+    if (!has_table(S) || !slots || !parents || !n_rows || !beam_places_ok(n_groups, beams)) return hipErrorInvalidValue;
+    for (int g = 0; g < n_groups; ++g)
+        for (int q = 0; q < beams; ++q) {
+            const int sl = slots[g * beams + q];
+            // (any slot of the group may be a parent: the columns moved must be filled in all of them)
+            if (sl < 0 || sl >= S->n_slots || !S->indirect[sl] || n_rows[g] < 0 || n_rows[g] > S->filled[sl])
+                return hipErrorInvalidValue;
+        }
+    const hipError_t e = launch_beam_reindex(S->own, S->max_seq, S->n_slots, n_groups, beams, slots, parents, n_rows, s);
+    if (e) return e;  // (a slot named twice: refused there, before its launch)
+    for (int g = 0; g < n_groups; ++g)
+        for (int q = 0; q < beams; ++q) S->filled[slots[g * beams + q]] = n_rows[g];
+    return hipSuccess;
+}
+
+// the table as it is (n_slots x max_seq bytes), device to device in stream order: read_slot's sibling
+hipError_t decoder_read_beam_table(const Stack *S, uint8_t *out, hipStream_t s) {
+    if (!has_table(S) || !out) return hipErrorInvalidValue;
+    return hipMemcpyAsync(out, S->own, (size_t)S->n_slots * S->max_seq, hipMemcpyDeviceToDevice, s);
+}
+
+bool decoder_slot_indirect(const Stack *S, int slot) {
+    return S && slot >= 0 && slot < S->n_slots && slot < (int)S->indirect.size() && S->indirect[slot];
 }
 
 hipError_t decoder_slot_state(const Stack *S, int slot, int *enc_seq, int *filled) {
