@@ -160,8 +160,8 @@ QGEMM_API int qgemm_linear(const float *X, int64_t x_stride_h, int m, int k, con
  *   bf16 output: the fp32 value the fp32 entry point would store (after dequantize, + bias, relu) is rounded
  *                once, to nearest even: past the bf16 maximum it becomes +-inf, subnormals stay subnormal, -0
  *                stays -0, NaN stays NaN.
- * bias stays fp32, and weights are packed from fp32 with qgemm_pack_b (a bf16 checkpoint is widened once by
- * the caller, which is exact).  With every tag QGEMM_F32 a _dt entry point IS its fp32 counterpart (same
+ * bias stays fp32, and weights are packed from fp32 with qgemm_pack_b (a bf16 checkpoint goes in through
+ * qgemm_pack_b_window below, which widens it exactly).  With every tag QGEMM_F32 a _dt entry point IS its fp32 counterpart (same
  * launches, bit-identical results); an unknown tag returns hipErrorInvalidValue before any launch.
  * qgemm_linear_dt takes the workspace of qgemm_linear_workspace_size (it does not depend on the types). */
 enum { QGEMM_F32 = 0, QGEMM_BF16 = 1 };
@@ -751,6 +751,53 @@ QGEMM_API int qgemm_decoder_generate_beam_indirect(void *decoder, void *head, in
                                          const int *src_slots, const int32_t *tokens_in, int n_new, const int *pos,
                                          const float *scores_in, int eos, int32_t *tokens_out, int32_t *parents_out,
                                          float *scores_out, void *stream);
+
+/* ---- Caller-supplied weights -----------------------------------------------------------
+ * qgemm_pack_b_window packs B, a logical k x ncols tensor of QGEMM_F32 or QGEMM_BF16 elements with element strides
+ * b_stride_h (along k) and b_stride_w (along the columns) -- an [out, in] checkpoint tensor is passed as
+ * b_stride_h = 1, b_stride_w = k --, into columns col0 .. col0 + ncols - 1 of packed_b, a buffer of
+ * qgemm_packed_size(n_total, k) bytes that already holds a packed k x n_total weight.  Afterwards scale[col0 ..
+ * col0 + ncols - 1] and the q bytes of packed rows col0 .. col0 + ncols - 1 over all of k_pad are BIT FOR BIT what
+ * qgemm_pack_b writes for those columns of any k x n_total fp32 matrix whose columns col0 .. are B (bf16 widened
+ * exactly, as qgemm_pack_a_dt widens): the quantization of B is column-local.  No other byte of the scale and q
+ * regions changes, and the reserved region is left alone, so windows that cover 0 .. n_total - 1 reproduce
+ * qgemm_pack_b of the assembled matrix.  One launch in stream order; no allocation, no synchronization, no workspace.
+ * Windows need not be multiples of 16.  The source path follows from the layout: 16-byte loads along k where
+ * b_stride_h == 1 and the base and every column are 16-byte aligned, neighbouring columns side by side where
+ * b_stride_w == 1, element by element through both strides otherwise; qgemm_pack_b_window_plan names it (a static
+ * string; it launches nothing).
+ * hipErrorInvalidValue before any launch: a null pointer, an unknown dtype, a negative stride, k < 1 or > 16384,
+ * col0 < 0, ncols < 1, col0 + ncols > n_total. */
+QGEMM_API int qgemm_pack_b_window(const void *B, int b_dtype, int64_t b_stride_h, int64_t b_stride_w, int k, int n_total,
+                        int col0, int ncols, float range, void *packed_b, void *stream);
+QGEMM_API int qgemm_pack_b_window_plan(const void *B, int b_dtype, int64_t b_stride_h, int64_t b_stride_w, int k,
+                             int n_total, int col0, int ncols, const char **kernel);
+/* The weights of an encoder or decoder handle (`model`), one tensor at a time.  kind is the weight kind of
+ * qgemm_encoder_create / qgemm_decoder_create: 0, 1, 2 (Wq, Wk, Wv) and on a decoder 8, 9, 10 (Wq2, Wk2, Wv2) are one
+ * d_model x d_k tensor per head; 3 (W_O) and on a decoder 11 (W_O2) d_model x d_model, head 0; 4 (W1) d_model x d_ff;
+ * 6 (W2) d_ff x d_model; 5 and 7 the biases b1 and b2 as 1 x d_ff and 1 x d_model.  A tensor is rows x cols with y = x W:
+ * rows = in features.
+ * qgemm_model_weight_shape reports rows, cols and the number of heads that have such a tensor (each may be NULL); no
+ * GPU call.
+ * qgemm_model_set_weight loads W (element strides stride_h along the rows, stride_w along the columns; an [out, in]
+ * tensor: stride_h = 1, stride_w = rows) as tensor (block, kind, head): ONE qgemm_pack_b_window launch with range 127
+ * into the block's packed weight at the tensor's column offset (kind 1 of head h: column d_model + h * d_k of
+ * [Wq | Wk | Wv]); a bias is a strided copy, a bf16 one widened.  Afterwards the model behaves, bit for bit, as one whose
+ * seeded draw had produced those values: forward, forward_batch, step*, generate* and the beam calls keep their
+ * contracts with "the weights" meaning the current ones.  It allocates nothing and does not synchronize; it runs in
+ * stream order with the model's other work.  On a decoder with caches the cached keys and values are stale after it,
+ * so when it is enqueued EVERY slot goes back to "not begun" (enc_seq 0, filled length 0, the beam search's flag
+ * cleared): a step is refused until the slot's next begin.
+ * hipErrorInvalidValue before any launch and without touching a slot: a null pointer, a kind the model lacks (8 .. 11
+ * on an encoder), block or head out of range (head != 0 for a kind without heads), an unknown dtype, a negative stride.
+ * qgemm_model_packed_weight / qgemm_model_bias give READ-ONLY access for tests and tools: the packed buffer of block's
+ * weight `which` = 0 .. 6 (wqkv, wo, w1, w2 and on a decoder wq2, wkv2, wo2) with its n packed rows and k, and bias 5
+ * or 7 with its n floats -- device pointers owned by the model. */
+QGEMM_API int qgemm_model_weight_shape(void *model, int kind, int *rows, int *cols, int *heads);
+QGEMM_API int qgemm_model_set_weight(void *model, int block, int kind, int head, const void *W, int dtype, int64_t stride_h,
+                           int64_t stride_w, void *stream);
+QGEMM_API int qgemm_model_packed_weight(void *model, int block, int which, const void **packed, int *n, int *k);
+QGEMM_API int qgemm_model_bias(void *model, int block, int kind, const float **bias, int *n);
 
 /* ---- LLM.int8() outlier decomposition ------------------------------------------
  * Feature columns k of A (= rows of B) holding an element with NOT(|x| <= threshold) (the reference's

@@ -120,6 +120,12 @@ EXPORTED_SYMBOLS = (
     "qgemm_decoder_beam_reindex",
     "qgemm_decoder_read_beam_table",
     "qgemm_decoder_generate_beam_indirect",
+    "qgemm_pack_b_window",
+    "qgemm_pack_b_window_plan",
+    "qgemm_model_weight_shape",
+    "qgemm_model_set_weight",
+    "qgemm_model_packed_weight",
+    "qgemm_model_bias",
     "qgemm_mm_outlier_workspace_size",
     "qgemm_mm_outlier",
     "qgemm_outlier_count",
@@ -368,6 +374,18 @@ def load() -> ctypes.CDLL:
         L.qgemm_decoder_generate_beam_indirect.argtypes = [vp, vp, i32, i32, ip, ip, vp, i32, ip, vp, i32, vp, vp, vp,
                                                            vp]
         L.qgemm_decoder_generate_beam_indirect.restype = i32
+        L.qgemm_pack_b_window.argtypes = [vp, i32, i64, i64, i32, i32, i32, i32, f32, vp, vp]
+        L.qgemm_pack_b_window.restype = i32
+        L.qgemm_pack_b_window_plan.argtypes = [vp, i32, i64, i64, i32, i32, i32, i32, ctypes.POINTER(ctypes.c_char_p)]
+        L.qgemm_pack_b_window_plan.restype = i32
+        L.qgemm_model_weight_shape.argtypes = [vp, i32, ip, ip, ip]
+        L.qgemm_model_weight_shape.restype = i32
+        L.qgemm_model_set_weight.argtypes = [vp, i32, i32, i32, vp, i32, i64, i64, vp]
+        L.qgemm_model_set_weight.restype = i32
+        L.qgemm_model_packed_weight.argtypes = [vp, i32, i32, ctypes.POINTER(vp), ip, ip]
+        L.qgemm_model_packed_weight.restype = i32
+        L.qgemm_model_bias.argtypes = [vp, i32, i32, ctypes.POINTER(vp), ip]
+        L.qgemm_model_bias.restype = i32
         L.qgemm_mm_outlier_workspace_size.argtypes = [i32, i32, i32]
         L.qgemm_mm_outlier_workspace_size.restype = sz
         L.qgemm_mm_outlier.argtypes = [vp, vp, vp, i32, i32, i32, f32, vp, sz, vp]
@@ -761,6 +779,38 @@ def pack_b(B, range: float = DEFAULT_RANGE) -> Packed:  # noqa: A002
     return p
 
 
+def _window_source(B, layout: str, name: str):
+    """A weight tensor given as "kn" ([in, out]: rows along k) or "nk" ([out, in], a checkpoint's layout): its
+    element-type tag, k, the number of columns and the element strides along k and along the columns."""
+    tag = _require_device_act(B, name)
+    assert layout in ("kn", "nk"), 'layout is "kn" ([in, out]) or "nk" ([out, in])'
+    if layout == "kn":
+        return tag, B.shape[0], B.shape[1], B.stride(0), B.stride(1)
+    return tag, B.shape[1], B.shape[0], B.stride(1), B.stride(0)
+
+
+def pack_b_window(B, packed: Packed, col0: int, layout: str = "kn", range: float = DEFAULT_RANGE) -> Packed:  # noqa: A002
+    """Pack B -- fp32 or bf16, k x ncols as layout "kn" or ncols x k as "nk", any strides -- into columns col0 ..
+    col0 + ncols - 1 of `packed`, a packed k x n weight (qgemm_pack_b_window): those columns' scales and packed rows
+    become, bit for bit, what pack_b writes for them; no other scale or q byte changes.  One launch, in place."""
+    tag, K, ncols, sh, sw = _window_source(B, layout, "B")
+    assert K == packed.k, "B's k is the packed weight's"
+    _check("qgemm_pack_b_window",
+           load().qgemm_pack_b_window(B.data_ptr(), tag, sh, sw, K, packed.rows, int(col0), ncols, float(range),
+                                      packed.buf.data_ptr(), _stream(B.device)))
+    return packed
+
+
+def pack_b_window_plan(B, packed: Packed, col0: int, layout: str = "kn") -> str:
+    """The source path pack_b_window takes for this tensor (qgemm_pack_b_window_plan): nothing is launched."""
+    tag, K, ncols, sh, sw = _window_source(B, layout, "B")
+    name = ctypes.c_char_p()
+    _check("qgemm_pack_b_window_plan",
+           load().qgemm_pack_b_window_plan(B.data_ptr(), tag, sh, sw, K, packed.rows, int(col0), ncols,
+                                           ctypes.byref(name)))
+    return name.value.decode()
+
+
 def mm_packed(pa: Packed, pb: Packed, C=None, out_dtype=None):
     """int8 MFMA GEMM + fused dequantize (op_mm.cuh:92-99) on packed operands.  The output is fp32 unless a bf16 C
     or out_dtype=torch.bfloat16 is given: then each fp32 result is rounded once to bf16 (qgemm_mm_packed_dt)."""
@@ -1000,7 +1050,85 @@ def encoder_weight_seed(base: int, block: int, kind: int, head: int) -> int:
     return (base * 1000003 + block * 4099 + kind * 131 + head) & 0xFFFFFFFFFFFFFFFF
 
 
-class Encoder:
+# The weight kinds by name (include/qgemm.h): KIND_WQ .. KIND_WV and KIND_WQ2 .. KIND_WV2 are one tensor per head.
+(KIND_WQ, KIND_WK, KIND_WV, KIND_WO, KIND_W1, KIND_B1, KIND_W2, KIND_B2,
+ KIND_WQ2, KIND_WK2, KIND_WV2, KIND_WO2) = range(12)
+# packed_weight's `which`
+(WEIGHT_WQKV, WEIGHT_WO, WEIGHT_W1, WEIGHT_W2, WEIGHT_WQ2, WEIGHT_WKV2, WEIGHT_WO2) = range(7)
+
+
+class _DeviceView:
+    """Device memory owned by someone else, for torch.as_tensor: `owner` stays alive as long as the tensor does."""
+
+    def __init__(self, ptr: int, nbytes: int, owner):
+        self.owner = owner
+        self.__cuda_array_interface__ = {"shape": (nbytes,), "typestr": "|u1", "data": (ptr, False), "version": 2}
+
+
+class _ModelWeights:
+    """Caller-supplied weights of an Encoder or Decoder (qgemm_model_*).  A weight tensor is rows x
+    cols with y = x W, as layout "kn"; a checkpoint's [out, in] tensor is layout "nk".  fp32 or bf16, any strides."""
+
+    def weight_shape(self, kind: int) -> tuple:
+        """(rows, cols, heads) of a tensor of `kind`: heads > 1 tensors exist for the per-head kinds."""
+        shapes = self.__dict__.setdefault("_weight_shapes", {})   # fixed at creation: asked once per kind
+        if kind not in shapes:
+            r, c, h = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+            _check("qgemm_model_weight_shape",
+                   load().qgemm_model_weight_shape(self._h, kind, ctypes.byref(r), ctypes.byref(c), ctypes.byref(h)))
+            shapes[kind] = (r.value, c.value, h.value)
+        return shapes[kind]
+
+    def set_weight(self, block: int, kind: int, W, head=None, layout: str = "kn"):
+        """Load tensor (block, kind, head) from W (qgemm_model_set_weight): one window-pack launch into the block's
+        packed weight, or a copy for a bias (W: n elements, 1-D or 1 x n).  head=None: head 0 for a kind without
+        heads, and for a per-head kind W is [n_heads, rows, cols] ("kn") or [n_heads, cols, rows] ("nk") and every head
+        is loaded.  On a decoder with caches every slot goes back to "not begun"."""
+        import torch
+        assert isinstance(W, torch.Tensor) and W.is_cuda and W.dtype in (torch.float32, torch.bfloat16), \
+            "W must be a float32 or bfloat16 device tensor"
+        rows, cols, heads = self.weight_shape(kind)
+        if head is None and heads > 1:
+            assert W.dim() == 3 and W.shape[0] == heads, "head=None on a per-head kind takes [n_heads, ...]"
+            for h in range(heads):
+                self.set_weight(block, kind, W[h], head=h, layout=layout)
+            return
+        head = 0 if head is None else int(head)
+        if kind in (KIND_B1, KIND_B2):
+            W = W.reshape(1, -1) if W.dim() == 1 else W
+            layout = "kn"
+        tag, r, c, sh, sw = _window_source(W, layout, "W")
+        assert (r, c) == (rows, cols), f"kind {kind} is {rows} x {cols}"
+        _check("qgemm_model_set_weight",
+               load().qgemm_model_set_weight(self._h, block, kind, head, W.data_ptr(), tag, sh, sw, _stream(W.device)))
+
+    def load_weights(self, mapping, layout: str = "kn"):
+        """set_weight for every entry of a mapping keyed (block, kind) or (block, kind, head)."""
+        for key, W in mapping.items():
+            block, kind = key[0], key[1]
+            self.set_weight(block, kind, W, head=key[2] if len(key) > 2 else None, layout=layout)
+
+    def packed_weight(self, block: int, which: int) -> Packed:
+        """Block's packed weight `which` (WEIGHT_WQKV ..) as a NON-OWNING Packed view of the model's own buffer, for
+        tests and tools: read it, do not write it, and do not use it after close()."""
+        import torch
+        p, n, k = ctypes.c_void_p(), ctypes.c_int(), ctypes.c_int()
+        _check("qgemm_model_packed_weight",
+               load().qgemm_model_packed_weight(self._h, block, which, ctypes.byref(p), ctypes.byref(n), ctypes.byref(k)))
+        nbytes = load().qgemm_packed_size(n.value, k.value)
+        buf = torch.as_tensor(_DeviceView(p.value, nbytes, self), device=torch.device("cuda", torch.cuda.current_device()))
+        return Packed(buf, n.value, k.value, DEFAULT_RANGE)
+
+    def bias(self, block: int, kind: int):
+        """Block's bias KIND_B1 or KIND_B2: a copy, n floats on the device."""
+        import torch
+        p, n = ctypes.c_void_p(), ctypes.c_int()
+        _check("qgemm_model_bias", load().qgemm_model_bias(self._h, block, kind, ctypes.byref(p), ctypes.byref(n)))
+        dev = torch.device("cuda", torch.cuda.current_device())
+        return torch.as_tensor(_DeviceView(p.value, 4 * n.value, self), device=dev).view(torch.float32).clone()
+
+
+class Encoder(_ModelWeights):
     """transformer.cu:14-77's Encoder with its linears on the quantized path.  max_rows
     (qgemm_encoder_create_rows): the rows forward_batch may run at once, max_seq where left out."""
 
@@ -1312,7 +1440,7 @@ def attention_plan(seq_q: int, seq_kv: int, n_heads: int, d_k: int) -> str:
     return name.value.decode()
 
 
-class Decoder:
+class Decoder(_ModelWeights):
     """transformer.cu:79-168's Decoder with its linears on the quantized path: per block self-attention,
     cross-attention on the encoder's output, FFN (DESIGN.md "Decoder").  causal=True (qgemm_decoder_create_ex,
     QGEMM_DECODER_CAUSAL): the self-attention is masked, row i sees rows 0 .. i, and forward(X[:n]) equals

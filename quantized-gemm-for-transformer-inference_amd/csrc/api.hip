@@ -612,6 +612,39 @@ int qgemm_decoder_destroy(void *decoder) {
     return 0;
 }
 
+// ---- caller-supplied weights: every check sits with the launch it guards (weights.hip, transformer.hip)
+
+int qgemm_pack_b_window(const void *B, int b_dtype, int64_t b_stride_h, int64_t b_stride_w, int k, int n_total, int col0,
+                        int ncols, float range, void *packed_b, void *stream) {
+    return err(launch_pack_b_window(B, b_dtype, b_stride_h, b_stride_w, k, n_total, col0, ncols, range, packed_b,
+                                    static_cast<hipStream_t>(stream)));
+}
+
+int qgemm_pack_b_window_plan(const void *B, int b_dtype, int64_t b_stride_h, int64_t b_stride_w, int k, int n_total,
+                             int col0, int ncols, const char **kernel) {
+    if (!pack_b_window_ok(B, b_dtype, b_stride_h, b_stride_w, k, n_total, col0, ncols)) return (int)hipErrorInvalidValue;
+    if (kernel) *kernel = pack_b_window_path(B, b_dtype, b_stride_h, b_stride_w, ncols);
+    return 0;
+}
+
+int qgemm_model_weight_shape(void *model, int kind, int *rows, int *cols, int *heads) {
+    return err(stack_weight_shape(static_cast<Stack *>(model), kind, rows, cols, heads));
+}
+
+int qgemm_model_set_weight(void *model, int block, int kind, int head, const void *W, int dtype, int64_t stride_h,
+                           int64_t stride_w, void *stream) {
+    return err(stack_set_weight(static_cast<Stack *>(model), block, kind, head, W, dtype, stride_h, stride_w,
+                                static_cast<hipStream_t>(stream)));
+}
+
+int qgemm_model_packed_weight(void *model, int block, int which, const void **packed, int *n, int *k) {
+    return err(stack_packed_weight(static_cast<Stack *>(model), block, which, packed, n, k));
+}
+
+int qgemm_model_bias(void *model, int block, int kind, const float **bias, int *n) {
+    return err(stack_bias(static_cast<Stack *>(model), block, kind, bias, n));
+}
+
 size_t qgemm_mm_outlier_workspace_size(int m, int n, int k) {
     if (!dims_ok(m, n, k)) return 0;
     return align256(outlier_scratch_bytes(m, n, k)) + op_mm_quantize_workspace_size(m, n, k);

@@ -490,6 +490,24 @@ hipError_t decoder_forward(Stack *S, const float *X, const float *enc_out, float
 hipError_t encoder_make_packed(int k, int n, const std::vector<uint64_t> &col_seeds, int cols_per_seed, float bound,
                                void **packed, float *tmp, hipStream_t s);
 const char *gemm_config_name();
+// Caller-supplied weights (weights.hip, transformer.hip; the contracts are at qgemm_pack_b_window and
+// qgemm_model_set_weight in include/qgemm.h).  dtype: QGEMM_F32 = 0 / QGEMM_BF16 = 1; strides in elements.
+// launch_pack_b_window: the k x ncols tensor B into packed rows col0 .. col0 + ncols - 1 of the packed k x n_total
+// weight at packed_b, one launch, nothing else in its scale and q regions written; every check of pack_b_window_ok
+// and a null destination before the launch.  pack_b_window_path: the source path's stable name.
+bool pack_b_window_ok(const void *B, int dtype, int64_t sh, int64_t sw, int k, int n_total, int col0, int ncols);
+const char *pack_b_window_path(const void *B, int dtype, int64_t sh, int64_t sw, int ncols);
+hipError_t launch_pack_b_window(const void *B, int dtype, int64_t sh, int64_t sw, int k, int n_total, int col0,
+                                int ncols, float range, void *packed_b, hipStream_t stream);
+// dst[i] = src[i * sw] widened, i < n: a bias from a strided fp32 or bf16 row
+hipError_t launch_copy_row(const void *src, int dtype, int64_t sw, int n, float *dst, hipStream_t stream);
+// The stack's side (transformer.hip).  kind: 0 .. 7 and, with cross-attention, 8 .. 11 (encoder_weight_seed's);
+// which: 0 .. 6 = wqkv, wo, w1, w2 and, with cross-attention, wq2, wkv2, wo2.
+hipError_t stack_weight_shape(const Stack *S, int kind, int *rows, int *cols, int *heads);
+hipError_t stack_set_weight(Stack *S, int block, int kind, int head, const void *W, int dtype, int64_t sh, int64_t sw,
+                            hipStream_t s);
+hipError_t stack_packed_weight(const Stack *S, int block, int which, const void **packed, int *n, int *k);
+hipError_t stack_bias(const Stack *S, int block, int kind, const float **bias, int *n);
 // Sampled token choice (sample.hip; the contract is at qgemm_sample_rows in include/qgemm.h).
 // sample_plan: the parts a row is cut into and a part's columns, from rows, w and top_k alone; false outside
 // rows >= 0, 1 <= w <= 2^24, 1 <= top_k <= 1024.  sample_check: every limit of the contract that needs no pointer.

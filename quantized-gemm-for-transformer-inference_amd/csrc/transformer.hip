@@ -77,6 +77,10 @@
 //                          with decoding rows): the scatter takes per-sequence row counts, keys in the slabs.
 // Each sequence's rows are forward's / step_slot's on it alone, bit for bit.  The scratch buffers hold
 // max(the above, max_rows) rows; the scores stay sized by max_seq (the per-sequence path runs one sequence at a time).
+//
+// Caller-supplied weights (qgemm_model_set_weight).  The seeded draw stays what creation does; afterwards
+// stack_set_weight replaces one tensor at a time: launch_pack_b_window (weights.hip) packs it into its column window of
+// the block's packed weight, a bias is copied.  Every call above then runs on the current weights.
 #include <cmath>
 #include <cstdint>
 #include <new>
@@ -833,6 +837,100 @@ hipError_t decoder_limits(const Stack *S, int *d_model, int *d_k, int *max_seq, 
     *d_k = S->d_model / S->n_heads;
     *max_seq = S->max_seq;
     *n_slots = S->n_slots;
+    return hipSuccess;
+}
+
+// ---- caller-supplied weights -------------------------------------------------------------------------
+namespace {
+
+// Where weight tensor (kind, head) lives: the packed buffer of the block that holds it (k x n_total), its column
+// window there, or the bias it is.  false: a kind the stack lacks or a head out of range.
+struct WeightPlace {
+    void *packed = nullptr;
+    float *bias = nullptr;
+    int k = 0, n_total = 0, col0 = 0, ncols = 0;
+};
+
+bool weight_kind_ok(const Stack *S, int kind) { return kind >= kWq && kind <= (S->cross ? kWo2 : kB2); }
+bool weight_per_head(int kind) { return (kind >= kWq && kind <= kWv) || (kind >= kWq2 && kind <= kWv2); }
+
+bool weight_place(const Stack *S, const Block &B, int kind, int head, WeightPlace *p) {
+    const int d = S->d_model, dk = d / S->n_heads, ff = S->d_ff;
+    if (!weight_kind_ok(S, kind) || head < 0 || head >= (weight_per_head(kind) ? S->n_heads : 1)) return false;
+    switch (kind) {
+        case kWq: case kWk: case kWv: *p = {B.wqkv, nullptr, d, 3 * d, (kind - kWq) * d + head * dk, dk}; break;
+        case kWo: *p = {B.wo, nullptr, d, d, 0, d}; break;
+        case kW1: *p = {B.w1, nullptr, d, ff, 0, ff}; break;
+        case kB1: *p = {nullptr, B.b1, 1, ff, 0, ff}; break;
+        case kW2: *p = {B.w2, nullptr, ff, d, 0, d}; break;
+        case kB2: *p = {nullptr, B.b2, 1, d, 0, d}; break;
+        case kWq2: *p = {B.wq2, nullptr, d, d, head * dk, dk}; break;
+        case kWk2: case kWv2: *p = {B.wkv2, nullptr, d, 2 * d, (kind - kWk2) * d + head * dk, dk}; break;
+        default: *p = {B.wo2, nullptr, d, d, 0, d}; break;  // kWo2
+    }
+    return true;
+}
+
+}  // namespace
+
+// the logical shape of one tensor of `kind` and the heads that have one; no GPU call
+hipError_t stack_weight_shape(const Stack *S, int kind, int *rows, int *cols, int *heads) {
+    WeightPlace p;
+    if (!S || !weight_place(S, S->blocks[0], kind, 0, &p)) return hipErrorInvalidValue;
+    if (rows) *rows = p.k;
+    if (cols) *cols = p.ncols;
+    if (heads) *heads = weight_per_head(kind) ? S->n_heads : 1;
+    return hipSuccess;
+}
+
+// One tensor of the caller's into the block's packed weight (ONE launch_pack_b_window at its column window) or bias (a
+// strided, widening copy), in stream order with the stack's other work; nothing allocated, no synchronization.  The
+// result is the packed weight the seeded draw would have made had it drawn these values: the pack is column-local.
+// Cached keys and values were projected with the old weights, so on a stack with caches every slot goes back to "not
+// begun" when the call is enqueued: a step is refused until the slot's next begin.
+hipError_t stack_set_weight(Stack *S, int block, int kind, int head, const void *W, int dtype, int64_t sh, int64_t sw,
+                            hipStream_t s) {
+    WeightPlace p;
+    if (!S || block < 0 || block >= S->n_blocks || !W || (dtype != 0 && dtype != 1) || sh < 0 || sw < 0 ||
+        !weight_place(S, S->blocks[block], kind, head, &p))
+        return hipErrorInvalidValue;
+    const hipError_t e = p.bias ? launch_copy_row(W, dtype, sw, p.ncols, p.bias, s)
+                                : launch_pack_b_window(W, dtype, sh, sw, p.k, p.n_total, p.col0, p.ncols, 127.0f,
+                                                       p.packed, s);
+    if (e) return e;
+    if (S->kv_cache) {
+        S->enc_seq.assign(S->n_slots, 0);
+        S->filled.assign(S->n_slots, 0);
+        S->indirect.assign(S->n_slots, 0);
+        S->own_rows.assign(S->n_slots, 0);
+    }
+    return hipSuccess;
+}
+
+// read-only views for tests and tools: a block's packed weight (n packed rows of k) ...
+hipError_t stack_packed_weight(const Stack *S, int block, int which, const void **packed, int *n, int *k) {
+    if (!S || block < 0 || block >= S->n_blocks || which < 0 || which > (S->cross ? 6 : 3) || !packed)
+        return hipErrorInvalidValue;
+    const Block &B = S->blocks[block];
+    const int d = S->d_model, ff = S->d_ff;
+    const struct {
+        const void *p;
+        int n, k;
+    } w[7] = {{B.wqkv, 3 * d, d}, {B.wo, d, d}, {B.w1, ff, d}, {B.w2, d, ff}, {B.wq2, d, d}, {B.wkv2, 2 * d, d}, {B.wo2, d, d}};
+    *packed = w[which].p;
+    if (n) *n = w[which].n;
+    if (k) *k = w[which].k;
+    return hipSuccess;
+}
+
+// ... and a bias (kind 5 or 7), n floats on the device
+hipError_t stack_bias(const Stack *S, int block, int kind, const float **bias, int *n) {
+    WeightPlace p;
+    if (!S || block < 0 || block >= S->n_blocks || !bias || (kind != kB1 && kind != kB2) ||
+        !weight_place(S, S->blocks[block], kind, 0, &p))
+        return hipErrorInvalidValue;
+    *bias = p.bias;
+    if (n) *n = p.ncols;
     return hipSuccess;
 }
 
