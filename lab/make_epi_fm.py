@@ -24,9 +24,9 @@ b = src.index('// --------------------------------------------------------------
 k = src[a:b]
 reps = [
     ('template <int kEpi = kEpiNone, bool kI32 = false, int kSplit = kSplitNone, bool kNtC = !kI32, int kFirst64 = 30,\n'
-     '          bool kBf16 = false>\n'
+     '          bool kBf16 = false, bool kRowFinish = false, int kRfRest = 0, bool kRfLoop = true>\n'
      '__global__ __launch_bounds__(kFmThreads, 1) void gemm_i8_fm(GemmArgs p) {',
-     'template <int kMap, int kStore, int kAux, int kEpi = kEpiNone, bool kI32 = false, int kSplit = kSplitNone, bool kNtC = !kI32, int kFirst64 = 30, bool kBf16 = false>\n'
+     'template <int kMap, int kStore, int kAux, int kEpi = kEpiNone, bool kI32 = false, int kSplit = kSplitNone, bool kNtC = !kI32, int kFirst64 = 30, bool kBf16 = false, bool kRowFinish = false, int kRfRest = 0, bool kRfLoop = true>\n'
      '__global__ __launch_bounds__(kFmThreads, 1) void gemm_i8_fm_epi(GemmArgs p) {'),
     ("    group_tiles(tile, p.tiles_m, p.tiles_n, tm, tn, !outlier_epi(kEpi) && p.wide_rows ? 8 : 4);\n",
      """    if constexpr (kMap == 1 || kMap == 3) {  // XCD patches of 8 (2) tile-rows instead of 4

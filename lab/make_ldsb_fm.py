@@ -19,9 +19,9 @@ a = src.index('// kNtC: the paired full-tile output stores')
 b = src.index('// ------------------------------------------------------------------------------------------------\n// gemm_i8_small')
 k = src[a:b]
 k = k.replace('template <int kEpi = kEpiNone, bool kI32 = false, int kSplit = kSplitNone, bool kNtC = !kI32, int kFirst64 = 30,\n'
-              '          bool kBf16 = false>\n'
+              '          bool kBf16 = false, bool kRowFinish = false, int kRfRest = 0, bool kRfLoop = true>\n'
               '__global__ __launch_bounds__(kFmThreads, 1) void gemm_i8_fm(GemmArgs p) {',
-              'template <int kKnob, int kEpi = kEpiNone, bool kI32 = false, int kSplit = kSplitNone, bool kNtC = !kI32, int kFirst64 = 30, bool kBf16 = false>\n'
+              'template <int kKnob, int kEpi = kEpiNone, bool kI32 = false, int kSplit = kSplitNone, bool kNtC = !kI32, int kFirst64 = 30, bool kBf16 = false, bool kRowFinish = false, int kRfRest = 0, bool kRfLoop = true>\n'
               '__global__ __launch_bounds__(kFmThreads, 1) void gemm_i8_fm_ldsb(GemmArgs p) {')
 loop_a = k.index('    v4i a0[8], b0[8], a1[8], b1[8], a2[8], b2[8];')
 loop_b = k.index('    // the last MFMAs\' results are read by VALU below')

@@ -86,11 +86,18 @@ int gemm_plan_info(int m, int n, int k, int *tile, const char **kernel) {
         else if (g.tile == 64)
             *kernel = g.splits > 1 ? "gemm_i8_small<64> (64x64 tiles, LDS-DMA ring, split-K)"
                                    : "gemm_i8_small<64> (64x64 tiles, LDS-DMA ring)";
+        else if (g.splits > 1)
+            *kernel = "gemm_i8_fm<split-K> (256x256 tiles, 4 waves of 128x128, fragment-major operands "
+                      "straight to VGPRs, AGPR accumulators, ticket-first split-K: one int32 slab per tile)";
+        else if (round_up(k, BK) / 64 >= kRowFinishJ + 3)
+            // what launch_fm picks for this K when the output also qualifies (fp32, plain / bias / relu epilogue, rows
+            // below 64 KiB, unit column stride, 16-B aligned rows); other outputs of the shape run the form below
+            *kernel = "gemm_i8_fm<row-finish> (256x256 tiles, 4 waves of 128x128, fragment-major operands straight to "
+                      "VGPRs, AGPR accumulators, fused dequant epilogue; the last 4 k-blocks row group by row group, "
+                      "each group's stores under the next one's MFMAs)";
         else
-            *kernel = g.splits > 1 ? "gemm_i8_fm<split-K> (256x256 tiles, 4 waves of 128x128, fragment-major operands "
-                                     "straight to VGPRs, AGPR accumulators, ticket-first split-K: one int32 slab per tile)"
-                                   : "gemm_i8_fm (256x256 tiles, 4 waves of 128x128, fragment-major operands straight to "
-                                     "VGPRs, AGPR accumulators, fused dequant epilogue)";
+            *kernel = "gemm_i8_fm (256x256 tiles, 4 waves of 128x128, fragment-major operands straight to "
+                      "VGPRs, AGPR accumulators, fused dequant epilogue)";
     }
     return g.splits;
 }
@@ -145,6 +152,25 @@ static hipError_t launch_fm(const GemmArgs &p, dim3 grid, hipStream_t stream) {
         if (p.splits == 2)
             return launch_timed(grid, dim3(kFmThreads), stream, p, gemm_i8_fm<kEpi, false, kSplitFirst, true, 31, kBf16>);
         if (p.splits > 2) return hipErrorNotSupported;  // gemm_plan never makes one (tiles in [128, 160) -> S <= 2)
+        // unsplit fp32 output on the paired-store path with enough sub-steps: the row-finish form (gemm_i8_kernels.h
+        // kRowFinish: each row group's stores under the next one's MFMAs); ragged edge tiles of such a launch store
+        // through its guarded scalar path
+        if constexpr (!kBf16) {
+            if (!p.wide_rows && p.csw == 1 && p.csh % 4 == 0 && (reinterpret_cast<uintptr_t>(p.C) & 15) == 0 &&
+                p.k_pad / 64 >= kRowFinishJ + 3 && p.k_pad % BK == 0)
+            {
+                // the instantiation for this K: pre = the k-outer sub-steps that prefetch two ahead, rest = pre % 3
+                // (which rotating set the phase ends on), loop = whether pre holds a whole group of three.  k_pad is a
+                // multiple of 128 (shape_ok), so pre is even: 2 at the shortest K, then 4, 6, ...
+                const int pre = (int)(p.k_pad / 64) - kRowFinishJ - 2;
+                const int rest = pre % 3;
+                auto go = [&](auto kernel) { return launch_timed(grid, dim3(kFmThreads), stream, p, kernel); };
+                if (pre == 2) return go(gemm_i8_fm<kEpi, false, kSplitNone, true, 30, false, true, 2, false>);
+                if (rest == 0) return go(gemm_i8_fm<kEpi, false, kSplitNone, true, 30, false, true, 0, true>);
+                if (rest == 1) return go(gemm_i8_fm<kEpi, false, kSplitNone, true, 30, false, true, 1, true>);
+                return go(gemm_i8_fm<kEpi, false, kSplitNone, true, 30, false, true, 2, true>);
+            }
+        }
     }
     return launch_timed(grid, dim3(kFmThreads), stream, p, gemm_i8_fm<kEpi, false, kSplitNone, true, 30, kBf16>);
 }

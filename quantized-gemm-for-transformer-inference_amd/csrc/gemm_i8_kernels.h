@@ -9,6 +9,8 @@
 // The row-major kernels of rounds 1-2 (gemm_i8_v1/v3, the ping-pong gemm_i8_pp) live in lab/gemm_legacy.h.
 #pragma once
 
+#include <type_traits>
+
 #include "qgemm_internal.h"
 
 namespace qgemm {
@@ -201,6 +203,19 @@ constexpr int kFmThreads = 256;
 //                 block that is not running: the first arriver has already drawn its ticket.
 enum SplitMode { kSplitNone = 0, kSplitFirst = 2 };
 
+// kRowFinish: the last kRowFinishJ sub-steps of the K loop run ROW-GROUP-OUTER, so the wave's eight 16-row groups
+// finish one after the other and each group's dequantize and stores are issued between the next group's MFMAs: the
+// store stream starts under the last MFMAs instead of after them (integer sums: the same bits in any order).  The final
+// phase needs no rotating sets: the B fragments of its kRowFinishJ sub-steps stay in registers (Bh: 128 VGPRs, loaded
+// while the last two k-outer sub-steps drain the pipeline) and A streams through two buffers of kRowFinishJ fragments
+// (32 VGPRs) -- 160 registers in place of the sets' 192, which is why J is 4 (J = 5 would take 200).  Only for the
+// launches the host picks (gemm_i8.hip launch_fm): fp32 output by the paired stores, none / bias / relu epilogue,
+// unsplit, at least kRowFinishJ + 3 sub-steps.  The one synchronisation it adds is a raw barrier after the prologue's
+// LDS writes (scales, bias), in place of the __syncthreads() after the loop.  kRfRest = (nsub - kRowFinishJ - 2) % 3:
+// which rotating set the k-outer phase ends on, and kRfLoop = whether that phase holds a whole group of three
+// sub-steps, both fixed per instantiation (run-time branches around the MFMAs cost accumulator moves and spills).
+constexpr int kRowFinishJ = 4;
+
 // kNtC: the paired full-tile output stores (rows < 64 KiB) are nontemporal -- the 64-MiB tail streams past the
 // caches (lab/ds_lab.hip: dsPn 56.30 vs plain pairs 56.99 us at 4096^3).  The wide-row LDS-image stores are
 // nontemporal in every instantiation (qgemm_mm_packed_i32, the one kNtC = false caller, never sets wide_rows).
@@ -214,10 +229,13 @@ enum SplitMode { kSplitNone = 0, kSplitFirst = 2 };
 //   full tiles, wide rows: the wave's LDS image holds bf16 (8-B writes, rows of TSH dwords) and leaves as 256-B row
 //     segments, 4 rows per store instruction, in the per-tile rotated order;
 //   ragged tiles, odd strides or a base off 16 B: 2-B scalar stores.
+
 template <int kEpi = kEpiNone, bool kI32 = false, int kSplit = kSplitNone, bool kNtC = !kI32, int kFirst64 = 30,
-          bool kBf16 = false>
+          bool kBf16 = false, bool kRowFinish = false, int kRfRest = 0, bool kRfLoop = true>
 __global__ __launch_bounds__(kFmThreads, 1) void gemm_i8_fm(GemmArgs p) {
     static_assert(!(kI32 && kEpi != kEpiNone), "raw accumulators take no epilogue extras");
+    static_assert(!(kRowFinish && (kI32 || kSplit || kBf16 || outlier_epi(kEpi) || !kNtC)),
+                  "row finish: the unsplit fp32 plain / bias / relu launches");
     static_assert(!(kBf16 && (kI32 || outlier_epi(kEpi))), "bf16 output: the dequantized plain / bias / relu epilogues");
     static_assert(!(kI32 && kSplit), "raw accumulators are not split");
     static_assert(!(outlier_epi(kEpi) && kSplit), "the outlier epilogue runs on unsplit plans");
@@ -270,6 +288,9 @@ __global__ __launch_bounds__(kFmThreads, 1) void gemm_i8_fm(GemmArgs p) {
     // prologue, and they reach LDS before the k-loop.  (LDS-DMA here instead makes hipcc wait for vmcnt(0) before
     // the first MFMA: it orders the inline-asm MFMAs behind every pending LDS-DMA write.)
     const float sx = kI32 ? 0.0f : p.Cx[gi0 + tid], sw = kI32 ? 0.0f : p.Cw[gj0 + tid];
+    // kRowFinish: the tile's 256 bias values join the scale image (0 past n, as the epilogue below reads them)
+    float sb = 0.0f;
+    if constexpr (kRowFinish && has_bias(kEpi)) sb = gj0 + tid < p.n ? p.bias[gj0 + tid] : 0.0f;
     // kEpiOutlier: the outlier-column count (device-side) and the operands of the chain's first 8 columns for this
     // tile -- X[row][col_t] of its 256 rows, W[col_t][j] of its 256 columns, +0 / -0 past the count (see the
     // epilogue) -- gathered first and staged in LDS after the operand prologue is in flight, so the epilogue reads
@@ -341,6 +362,196 @@ __global__ __launch_bounds__(kFmThreads, 1) void gemm_i8_fm(GemmArgs p) {
             sO[t * OS + tid] = oxv[t];
             sO[(8 + t) * OS + tid] = owv[t];
         }
+    }
+    if constexpr (kRowFinish) {
+        constexpr int J = kRowFinishJ;
+        typedef float v2f __attribute__((ext_vector_type(2)));
+        typedef float v4f __attribute__((ext_vector_type(4)));
+        float *const sBias = sS + 2 * BM + 4;  // the wide-row image's place: a row-finish launch has no wide rows
+        if constexpr (has_bias(kEpi)) sBias[tid] = sb;
+        // the scale image is read from row group 0's epilogue on, under the other waves' MFMAs: every wave's LDS writes
+        // land (lgkmcnt only -- the 32 fragment loads above stay in flight) before any wave goes on
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        // the zeroed accumulators are in their AGPRs from here on (an empty statement with the tile as its tied operand
+        // is a use): without a loop in front of the first MFMAs hipcc zeroed each tile one instruction ahead of the
+        // inline-asm MFMA that reads it, inside the VALU-write-to-MFMA-read hazard window it cannot see
+#pragma unroll
+        for (int mi = 0; mi < 8; ++mi)
+#pragma unroll
+            for (int ni = 0; ni < 8; ++ni) asm volatile("" : "+a"(acc[mi][ni]));
+        asm volatile("s_nop 7" ::: "memory");
+        const int n1 = nloc - J;  // k-outer sub-steps [0, n1), then sub-steps n1 .. n1 + J - 1 row-group-outer (n1 >= 3)
+        const int c = lane & 15, kq = lane >> 4;
+        const int r0 = wm * 128, c0 = wn * 128;
+        const bool lo = c < 8;
+        const v2f inv2 = {p.inv_r2, p.inv_r2};
+        const v2f zero2 = {0.0f, 0.0f};
+        float *C = static_cast<float *>(p.C);
+        const bool pairs = p.csw == 1 && (p.csh % 4 == 0) && ((reinterpret_cast<uintptr_t>(p.C) & 15) == 0) &&
+                           gj0 + BN <= p.n && gi0 + BM <= p.m;
+        // the lane's first paired-store address: row (c & 7) of row group 0, tile pair 0
+        float *const Cl = C + (int64_t)(gi0 + r0 + (c & 7)) * p.csh + gj0 + c0 + (lo ? 0 : 16) + 4 * kq;
+        const float *const sCw = sS + BM + c0 + 4 * kq;
+        const float *const sBv = sBias + c0 + 4 * kq;
+        // half a tile's outputs (elements 2 h, 2 h + 1): O = fl(fl(float(acc) * (fl(Cx * Cw) + 0)) * inv_r2) on a packed
+        // pair, then the extras -- the epilogue below, operation for operation
+        auto half_out = [&](v4f &o, const v4i &a, float cx, const v4f &cw, const v4f &bv, int h) __attribute__((always_inline)) {
+            const v2f x = {cx, cx};
+            const v2f s = x * v2f{cw[2 * h], cw[2 * h + 1]} + zero2;
+            const v2f d = (v2f{(float)a[2 * h], (float)a[2 * h + 1]} * s) * inv2;
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                float v = d[e];
+                if constexpr (has_bias(kEpi)) v = __fadd_rn(v, bv[2 * h + e]);
+                if constexpr (has_relu(kEpi)) v = (v < 0.0f) ? 0.0f : v;
+                o[2 * h + e] = v;
+            }
+        };
+        // the drains and the final phase, once per residue of the set rotation (the registers a set occupies differ by
+        // residue; a shared copy would have to move 144 registers into place): (ca, cb) holds sub-step n1 - 2,
+        // (na, nb) sub-step n1 - 1 (in flight)
+        auto tail = [&](v4i (&ca)[8], v4i (&cb)[8], v4i (&na)[8], v4i (&nb)[8]) __attribute__((always_inline)) {
+            v4i Bh[J][8], Ab[2][J];
+            // Bh[t >> 3][t & 7]: B row group t & 7, sub-step n1 + (t >> 3)
+            auto ldB = [&](int t) __attribute__((always_inline)) {
+                Bh[t >> 3][t & 7] = __builtin_amdgcn_raw_buffer_load_b128(rsB, voff, ((t & 7) * nsub + n1 + (t >> 3)) * 1024, 0);
+            };
+            // A row group g, sub-step n1 + j (the J blocks are contiguous: one scalar offset, immediate steps)
+            auto ldA = [&](int buf, int g, int j) __attribute__((always_inline)) {
+                Ab[buf][j] = __builtin_amdgcn_raw_buffer_load_b128(rsA, voff + j * 1024, (g * nsub + n1) * 1024, 0);
+            };
+            // the two draining k-outer sub-steps: the loads they issue fill Bh (and A of row group 0) at the loop's pace
+            __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+            for (int mi = 0; mi < 8; ++mi) {
+#pragma unroll
+                for (int ni = 0; ni < 8; ++ni) {
+                    if (ni == 2) ldB(2 * mi);
+                    if (ni == 6) ldB(2 * mi + 1);
+                    mfma_agpr(acc[mi][ni], cb[ni], ca[mi]);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+#pragma unroll
+            for (int mi = 0; mi < 8; ++mi) {
+#pragma unroll
+                for (int ni = 0; ni < 8; ++ni) {
+                    if (ni == 2) ldB(16 + 2 * mi);
+                    if (ni == 4 && mi < J) ldA(0, 0, mi);
+                    if (ni == 6) ldB(16 + 2 * mi + 1);
+                    mfma_agpr(acc[mi][ni], nb[ni], na[mi]);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            __builtin_amdgcn_s_setprio(0);
+            // the epilogue of tile pair np of row group g in 8 pieces, one per MFMA of the next row group's sub-step np
+            // (a wave issues in order: VALU runs in an MFMA's shadow only when it stands between two MFMAs)
+            v4i ta, tb;
+            v4f o0, o1, w0, w1, bb0 = {}, bb1 = {};
+            float cxg = 0.0f, r0v[4], r1v[4];
+            auto piece = [&](int g, int np, int q) __attribute__((always_inline)) {
+                if (q == 0) {
+                    if (np == 0) cxg = sS[r0 + 16 * g + c];
+                    w0 = *reinterpret_cast<const v4f *>(sCw + 32 * np);
+                    w1 = *reinterpret_cast<const v4f *>(sCw + 32 * np + 16);
+                    if constexpr (has_bias(kEpi)) {
+                        bb0 = *reinterpret_cast<const v4f *>(sBv + 32 * np);
+                        bb1 = *reinterpret_cast<const v4f *>(sBv + 32 * np + 16);
+                    }
+                    // pin the accumulator reads HERE: hipcc otherwise copies an asm result to VGPRs right behind the
+                    // statement that wrote it last -- inside the MFMA-to-VALU hazard window it cannot see -- and an
+                    // empty statement with the tile as its tied operand is the "last writer" the copy then follows
+                    asm volatile("" : "+a"(acc[g][2 * np]));
+                    asm volatile("" : "+a"(acc[g][2 * np + 1]));
+                    ta = acc[g][2 * np];
+                    tb = acc[g][2 * np + 1];
+                } else if (q <= 2) {
+                    half_out(o0, ta, cxg, w0, bb0, q - 1);
+                } else if (q <= 4) {
+                    half_out(o1, tb, cxg, w1, bb1, q - 3);
+                } else if (q == 5) {
+                    // tiles 2 np and 2 np + 1 exchanged between lanes c and c ^ 8 (DPP row_ror:8), as below
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        r0v[e] = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(o0[e]), 0x128, 0xf, 0xf, false));
+                        r1v[e] = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(o1[e]), 0x128, 0xf, 0xf, false));
+                    }
+                } else {
+                    // after the exchange the lane holds columns jc .. jc + 3 of rows ra (x1) and ra + 8 (x2)
+                    v4f x;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) x[e] = q == 6 ? (lo ? o0[e] : r1v[e]) : (lo ? r0v[e] : o1[e]);
+                    const int rl = 16 * g + (q == 6 ? 0 : 8);
+                    if (pairs) {
+                        __builtin_nontemporal_store(x, reinterpret_cast<v4f *>(Cl + (int64_t)rl * p.csh + 32 * np));
+                    } else {
+                        // a ragged edge tile (block-uniform): the same values through guarded scalar stores
+                        const int64_t ra = gi0 + r0 + rl + (c & 7);
+                        const int jc = gj0 + c0 + 32 * np + (lo ? 0 : 16) + 4 * kq;
+                        if (ra < p.m) {
+#pragma unroll
+                            for (int e = 0; e < 4; ++e)
+                                if (jc + e < p.n) C[ra * p.csh + (int64_t)(jc + e) * p.csw] = x[e];
+                        }
+                    }
+                }
+            };
+            // the final phase.  Row group g: its J MFMA rows of 8, A from buffer g & 1; group g + 1's A loads go out
+            // first (before group g - 1's stores: a store waiting for the vector-memory queue must not hold them back).
+            // One straight line for full and ragged tiles alike -- only the store inside a piece branches: accumulators
+            // that meet at a join after MFMAs on both sides get moved and spilled.  MFMA-to-VALU distance: tile ni of
+            // group g - 1 was last written by MFMA 8 (J - 1) + ni of its group and is first read after MFMA 8 (ni >> 1)
+            // of group g: at least 8 MFMAs (>= 32 issue cycles) lie between, where the block after the last group
+            // waits 20
+#pragma unroll
+            for (int g = 0; g < 8; ++g) {
+                if (g < 7) {
+#pragma unroll
+                    for (int j = 0; j < J; ++j) ldA((g + 1) & 1, g + 1, j);
+                }
+#pragma unroll
+                for (int j = 0; j < J; ++j)
+#pragma unroll
+                    for (int ni = 0; ni < 8; ++ni) {
+                        mfma_agpr(acc[g][ni], Bh[j][ni], Ab[g & 1][j]);
+                        if (g > 0) piece(g - 1, j, ni);
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+            }
+            // the last group's results are read by VALU next; the asm statements hide the MFMAs from hipcc's padding
+            asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 3" ::: "memory");
+#pragma unroll
+            for (int np = 0; np < 4; ++np)
+#pragma unroll
+                for (int q = 0; q < 8; ++q) piece(7, np, q);
+        };
+        // sub-steps 0 .. n1 - 3 prefetch two ahead as the plain loop does (same body); the last two drain
+        int u = 0;
+        // kRfLoop: at least one group of three (the host's choice again: with a loop that may run zero times the
+        // accumulators meet at the join behind it, and hipcc permuted 292 of them there); the body is the plain loop's
+        if constexpr (kRfLoop) {
+            do {
+                substep(a0, b0, a2, b2, u + 2, true);
+                substep(a1, b1, a0, b0, u + 3, true);
+                substep(a2, b2, a1, b1, u + 4, true);
+                u += 3;
+            } while (u + 3 + kRfRest <= n1 - 2);
+        }
+        // kRfRest = (n1 - 2) % 3 prefetching sub-steps are left (the host's choice of instantiation: a run-time
+        // three-way branch here made hipcc move and spill accumulators): sets 0 and 1 hold sub-steps u, u + 1
+        if constexpr (kRfRest == 0) {
+            tail(a0, b0, a1, b1);
+        } else if constexpr (kRfRest == 1) {
+            substep(a0, b0, a2, b2, u + 2, true);
+            tail(a1, b1, a2, b2);
+        } else {
+            substep(a0, b0, a2, b2, u + 2, true);
+            substep(a1, b1, a0, b0, u + 3, true);
+            tail(a2, b2, a0, b0);
+        }
+        return;
     }
     int u = 0;
     for (; u + 3 <= nloc; u += 3) {
