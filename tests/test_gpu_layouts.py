@@ -66,7 +66,8 @@ OUT_LAYOUTS = {
     "rows_16380": lambda m, n: (16380, 1, 0),         # just below the switch: the paired stores
 }
 WIDE = ("rows_16384", "rows_16380")
-# the unsplit 256-tile plan at 160 full tiles, and the split-K one, for the two wide layouts
+# the unsplit 256-tile plan at 160 full tiles, and the split-K one, for the two wide layouts.  K = 128 (and PLAN_SHAPES'
+# K = 192) reaches gemm_i8_fm's plain form; the row-finish form's layouts are in test_gpu_row_finish_matrix.py
 WIDE_SHAPES = [((2560, 4096, 128), 256, 1, None), ((2048, 4096, 2048), 256, 2, None)]
 OUT_CASES = [(s, lay) for s in PLAN_SHAPES for lay in OUT_LAYOUTS if lay not in WIDE] + \
             [(s, lay) for s in WIDE_SHAPES for lay in WIDE]

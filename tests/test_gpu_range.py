@@ -179,7 +179,9 @@ def test_drop_in_range(qg, oracle, device, shape, path, r):
 
 
 # ---------------------------------------------------------------------------------- 3. every GEMM plan
-# (m, n, k), the plan qgemm_gemm_plan must report (tile, splits) and the 64-tile ring depth (test_gpu_bf16._assert_plan)
+# (m, n, k), the plan qgemm_gemm_plan must report (tile, splits) and the 64-tile ring depth (test_gpu_bf16._assert_plan).
+# The unsplit 256-tile shape has K = 192 (4 k-blocks) and so reaches gemm_i8_fm's plain form; the row-finish form that
+# the same plan takes from 8 k-blocks on has these axes in test_gpu_row_finish_matrix.py
 PLAN_SHAPES = [
     ((250, 1000, 200), 32, 1, None),
     ((130, 70, 640), 64, 1, 3),

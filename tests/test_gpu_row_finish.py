@@ -3,7 +3,8 @@
 The form runs the last 4 of a tile's 64-deep k-blocks row group by row group and stores each finished row group under
 the next one's MFMAs.  The launcher takes it for unsplit 256-tile plans with an fp32 output on the paired-store path
 (unit column stride, row stride a multiple of 4 floats, 16-B aligned base, rows below 64 KiB), a plain / bias /
-bias + relu epilogue and at least 7 k-blocks; everything else keeps the plain kernel.  The 256-tile plan runs unsplit
+bias + relu epilogue and k_pad / 64 >= 7 with k_pad a multiple of 128 -- hence at least 8 64-deep k-blocks, K >= 385;
+everything else keeps the plain kernel.  The 256-tile plan runs unsplit
 from 160 tiles on, so the smallest shape here is 2560 x 4096 (10 x 16 tiles).  Each case asserts its plan through
 qgemm_gemm_plan first, so none can pass by missing the kernel.
 
