@@ -868,6 +868,108 @@ QGEMM_API int qgemm_gemm_plan(int m, int n, int k, int *tile, const char **kerne
 /* Library identification: "qgemm <version> gfx950 <kernel config>". */
 QGEMM_API const char *qgemm_version(void);
 
+/* ---- The standard post-LN transformer block ---------------------------------------------
+ * The reference's block normalises with (y - mean) / var, adds the attention's multiHeadOut as every residual, has no
+ * projection biases and only relu.  QGEMM_ARCH_STANDARD is the block of "Attention Is All You Need" and of
+ * torch.nn.TransformerEncoderLayer / TransformerDecoderLayer with norm_first=False, every linear on the int8 path:
+ *   x1 = LN1(x  + SelfAttn(x) W_O + b_O)
+ *   x2 = LN2(x1 + CrossAttn(x1, enc) W_O2 + b_O2)        (decoder)
+ *   y  = LN3(x2 + act(x2 W1 + b1) W2 + b2)               act: relu or tanh-form GELU
+ *
+ * qgemm_layernorm_rows: Y = LN(A + B) on rows x w floats, contiguous rows, w <= 4096; B may be NULL (Y = LN(A)).
+ * gamma, beta: w floats.  Every step is ONE IEEE fp32 operation, no contraction and no fma:
+ *   v[c]  = fl(A[c] + B[c])                        (B == NULL: v[c] = A[c])
+ *   mean  = fl(rowsum(v) / fl32(w))
+ *   d[c]  = fl(v[c] - mean)
+ *   var   = fl(rowsum(fl(d[c] d[c])) / fl32(w))
+ *   rstd  = fl(1 / fl(sqrt(fl(var + eps))))
+ *   Y[c]  = fl(fl(fl(d[c] rstd) gamma[c]) + beta[c])
+ * rowsum -- the order is part of the contract, and it is NOT the reference's sequential chain (nothing pins it here,
+ * and that chain is what the reference architecture's add + layernorm spends its time on):
+ *   partial p[l], l = 0 .. 63, starts at +0 and adds, in increasing c, the elements whose float4 column c / 4 is
+ *   congruent to l modulo 64 (lane l reads float4 columns l, l + 64, ..);
+ *   then six butterfly steps p[l] = fl(p[l] + p[l ^ off]), off = 32, 16, 8, 4, 2, 1 (for every l at once: an fp32 add
+ *   is commutative, so the two lanes of a pair hold the same bits); every p[l] ends as the same value, the sum.
+ * The order depends on w alone: not on rows, not on the launch a shape takes -- 16-byte aligned rows of w % 4 == 0
+ * floats stay in registers through float4 loads, any other w or alignment fills the same registers float by float and
+ * gives the same bits.  eps is any float; with eps = 0 a constant row gives d = 0, rstd = inf, 0 inf = NaN.
+ * Y may be the same buffer as A or as B (the same rows): a row belongs to one wave, which reads all of it before it
+ * writes.  For that reason A, B and Y are not restrict-qualified inside the library; gamma and beta must not overlap Y.
+ * qgemm_layernorm_pack_a: the same, and Y's rows are also written packed into packed_a (qgemm_packed_size(rows, w)
+ * bytes) with the operations of qgemm_pack_a: the scale and q regions equal qgemm_pack_a(Y, range) byte for byte,
+ * padding rows and columns included.  Workspace-free: one launch, no allocation, no synchronization.
+ * hipErrorInvalidValue before any launch: a null A / gamma / beta / Y (/ packed_a), w < 1 or > 4096, rows < 0;
+ * rows == 0 returns 0. */
+QGEMM_API int qgemm_layernorm_rows(const float *A, const float *B_or_null, const float *gamma, const float *beta, float eps,
+                         float *Y, int64_t rows, int w, void *stream);
+QGEMM_API int qgemm_layernorm_pack_a(const float *A, const float *B_or_null, const float *gamma, const float *beta,
+                           float eps, float *Y, int64_t rows, int w, float range, void *packed_a, void *stream);
+
+/* qgemm_gelu_rows: the tanh-form GELU, elementwise on rows x w floats (unit inner stride, row strides in floats),
+ * written as x sigmoid(2u), u = sqrt(2/pi) (x + 0.044715 x^3) -- algebraically 0.5 x (1 + tanh(u)) -- so that it needs
+ * only the correctly rounded exp the softmax uses; every other step ONE IEEE fp32 operation:
+ *   t = fl(x C1)                         C1 = fl32(2 sqrt(2/pi)) = 0x3FCC422A
+ *   q = fl(fl(fl(x x) 0.044715f) + 1.0f)
+ *   z = fl(t q)
+ *   e = fl32(exp((double)(-z)))
+ *   g = fl(x / fl(1.0f + e))
+ * NaN and +-inf give what these operations give (-inf: NaN; a very negative x: x / inf = -0).  The erf form is not
+ * offered: its bits would hang on a library's double erf, and it differs from this form by at most 4.7e-4 absolute,
+ * far below one int8 step of a row whose absmax is of order 1.
+ * qgemm_gelu_pack_a: packed_a (qgemm_packed_size(m, k) bytes) = qgemm_pack_a(gelu_rows(X), range) byte for byte over the
+ * scale and q regions, the GELU'd matrix never written: the hidden layer of a GELU FFN is written once by the W1 GEMM
+ * and read once by this pack.  The signed first element of the GELU'd row seeds its absmax, as in qgemm_pack_a.
+ * k <= 16384; one launch, no workspace, no allocation, no synchronization.
+ * hipErrorInvalidValue before any launch: a null pointer, a negative stride, w < 1 / k < 1 or k > 16384, rows < 0 /
+ * m < 0; rows == 0 / m == 0 returns 0. */
+QGEMM_API int qgemm_gelu_rows(const float *X, int64_t x_stride_h, float *Y, int64_t y_stride_h, int64_t rows, int w,
+                    void *stream);
+QGEMM_API int qgemm_gelu_pack_a(const float *X, int64_t x_stride_h, int m, int k, float range, void *packed_a, void *stream);
+
+/* qgemm_model_create: the one creator that knows architectures.  desc->size = sizeof(qgemm_model_desc).
+ * arch = QGEMM_ARCH_REFERENCE creates exactly what the matching older creator creates -- cross = 0:
+ * qgemm_encoder_create_rows (flags, n_slots and max_enc_seq must be 0 / 0 or 1 / anything); cross = 1:
+ * qgemm_decoder_create_rows where n_slots > 1 or max_rows > 0 (flags must then be CAUSAL | KV_CACHE), else
+ * qgemm_decoder_create_ex -- with the same argument checks and the same seeded weights.  n_slots = 0 means 1.
+ * arch = QGEMM_ARCH_STANDARD: the block above.  The twelve matrices and b1, b2 are drawn exactly as on the reference
+ * architecture (same seeds, kinds and bounds); the new tensors are set to b = +0, gamma = 1, beta = +0:
+ *   kind 12, 13, 14  b_q, b_k, b_v     1 x d_model each (all heads side by side)
+ *   kind 15          b_o               1 x d_model
+ *   kind 16, 17      gamma1, beta1     1 x d_model        LN1
+ *   kind 18, 19      gamma3, beta3     1 x d_model        LN3, the FFN's
+ *   kind 20, 21, 22  b_q2, b_k2, b_v2  1 x d_model each   decoder
+ *   kind 23          b_o2              1 x d_model        decoder
+ *   kind 24, 25      gamma2, beta2     1 x d_model        decoder, LN2
+ * qgemm_model_set_weight, qgemm_model_weight_shape and qgemm_model_bias take them on a standard model (head 0; the
+ * strided widening row copy of kinds 5 and 7) and refuse them on a reference model as kinds the model lacks; 20 .. 25
+ * are refused on an encoder.  The fused biases live as one 3 d_model vector beside [Wq | Wk | Wv], one d_model vector
+ * beside Wq2 and one 2 d_model vector beside [Wk2 | Wv2], so the GEMM epilogue adds them with no launch of their own.
+ * activation = QGEMM_ACT_GELU_TANH (standard only): W1 runs without relu and the pack in front of W2 is
+ * qgemm_gelu_pack_a's.  ln_eps: the epsilon of every LN.
+ * The handle works with every qgemm_encoder_* (cross = 0) / qgemm_decoder_* (cross = 1) / qgemm_model_* call and with
+ * that family's destroy.  Every contract of those calls that rests on row-locality carries over: the new steps are
+ * row-local.  hipErrorInvalidValue: a null pointer, a wrong size, an unknown arch or activation, GELU on the reference
+ * architecture, GELU with d_ff > 16384 (qgemm_gelu_pack_a's limit), a negative or NaN ln_eps, and whatever the older
+ * creators refuse.
+ * qgemm_model_info reads the descriptor back (n_slots as created, 1 for 0). */
+#define QGEMM_ARCH_REFERENCE 0
+#define QGEMM_ARCH_STANDARD 1
+#define QGEMM_ACT_RELU 0
+#define QGEMM_ACT_GELU_TANH 1
+typedef struct {
+    uint32_t size; /* sizeof(qgemm_model_desc), for later growth */
+    int cross;     /* 0 encoder, 1 decoder */
+    int d_model, n_heads, d_ff, n_blocks, max_seq, max_enc_seq;
+    uint64_t seed;
+    int flags;             /* QGEMM_DECODER_* */
+    int n_slots, max_rows; /* 0: the defaults of the older creators */
+    int arch;              /* QGEMM_ARCH_* */
+    int activation;        /* QGEMM_ACT_* (standard only) */
+    float ln_eps;
+} qgemm_model_desc;
+QGEMM_API int qgemm_model_create(const qgemm_model_desc *desc, void **model);
+QGEMM_API int qgemm_model_info(void *model, qgemm_model_desc *desc);
+
 #ifdef __cplusplus
 }
 #endif

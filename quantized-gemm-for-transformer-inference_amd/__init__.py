@@ -136,6 +136,12 @@ EXPORTED_SYMBOLS = (
     "qgemm_fill_uniform",
     "qgemm_gemm_plan",
     "qgemm_version",
+    "qgemm_layernorm_rows",
+    "qgemm_layernorm_pack_a",
+    "qgemm_gelu_rows",
+    "qgemm_gelu_pack_a",
+    "qgemm_model_create",
+    "qgemm_model_info",
 )
 
 # Every symbol include/qgemm_dist.h declares (libqgemm_dist.so: M-shards + RCCL all-gather).
@@ -164,6 +170,19 @@ QGEMM_DECODER_CAUSAL = 1       # qgemm_decoder_create_ex flag: causal mask on th
 QGEMM_DECODER_KV_CACHE = 8     # ... and per-block key / value caches for begin() / step() (with CAUSAL only)
 QGEMM_DECODE_MAX_BATCH = 64    # sequences per attention_decode_batched / step_batch call, cache slots per decoder
 QGEMM_VARLEN_MAX_SEQS = 64     # sequences per attention_varlen / forward_batch / step_varlen call
+QGEMM_ARCH_REFERENCE, QGEMM_ARCH_STANDARD = 0, 1  # qgemm_model_create: the reference's block / the post-LN block
+QGEMM_ACT_RELU, QGEMM_ACT_GELU_TANH = 0, 1        # ... and the FFN's activation (GELU: standard only)
+ARCHS = {"reference": QGEMM_ARCH_REFERENCE, "standard": QGEMM_ARCH_STANDARD}
+ACTIVATIONS = {"relu": QGEMM_ACT_RELU, "gelu_tanh": QGEMM_ACT_GELU_TANH}
+
+
+class ModelDesc(ctypes.Structure):
+    """qgemm_model_desc (include/qgemm.h)."""
+    _fields_ = [("size", ctypes.c_uint32), ("cross", ctypes.c_int), ("d_model", ctypes.c_int),
+                ("n_heads", ctypes.c_int), ("d_ff", ctypes.c_int), ("n_blocks", ctypes.c_int),
+                ("max_seq", ctypes.c_int), ("max_enc_seq", ctypes.c_int), ("seed", ctypes.c_uint64),
+                ("flags", ctypes.c_int), ("n_slots", ctypes.c_int), ("max_rows", ctypes.c_int),
+                ("arch", ctypes.c_int), ("activation", ctypes.c_int), ("ln_eps", ctypes.c_float)]
 
 _lock = threading.Lock()
 _lib = None
@@ -406,6 +425,18 @@ def load() -> ctypes.CDLL:
         L.qgemm_gemm_plan.restype = i32
         L.qgemm_version.argtypes = []
         L.qgemm_version.restype = ctypes.c_char_p
+        L.qgemm_layernorm_rows.argtypes = [vp, vp, vp, vp, f32, vp, i64, i32, vp]
+        L.qgemm_layernorm_rows.restype = i32
+        L.qgemm_layernorm_pack_a.argtypes = [vp, vp, vp, vp, f32, vp, i64, i32, f32, vp, vp]
+        L.qgemm_layernorm_pack_a.restype = i32
+        L.qgemm_gelu_rows.argtypes = [vp, i64, vp, i64, i64, i32, vp]
+        L.qgemm_gelu_rows.restype = i32
+        L.qgemm_gelu_pack_a.argtypes = [vp, i64, i32, i32, f32, vp, vp]
+        L.qgemm_gelu_pack_a.restype = i32
+        L.qgemm_model_create.argtypes = [ctypes.POINTER(ModelDesc), ctypes.POINTER(vp)]
+        L.qgemm_model_create.restype = i32
+        L.qgemm_model_info.argtypes = [vp, ctypes.POINTER(ModelDesc)]
+        L.qgemm_model_info.restype = i32
         _lib = L
         return L
 
@@ -987,6 +1018,78 @@ def add_layernorm_rows(A, B, Y=None):
     return Y
 
 
+def _ln_args(A, B, gamma, beta, Y):
+    import torch
+    _require_device_f32(A, "A")
+    assert A.dim() == 2 and A.is_contiguous(), "A: rows x w, contiguous"
+    w = A.shape[1]
+    if B is not None:
+        _require_device_f32(B, "B")
+        assert B.shape == A.shape and B.is_contiguous(), "B: as A"
+    for t, nm in ((gamma, "gamma"), (beta, "beta")):
+        assert isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.numel() == w and \
+            t.is_contiguous(), f"{nm}: w float32 values on the device, contiguous"
+    Y = torch.empty_like(A) if Y is None else Y
+    _require_device_f32(Y, "Y")
+    assert Y.shape == A.shape and Y.is_contiguous(), "Y: as A"
+    return Y
+
+
+def layernorm_rows(A, B, gamma, beta, eps: float = 1e-5, Y=None):
+    """Y = LN(A + B) with gamma, beta and eps, the standard layer normalisation (qgemm_layernorm_rows, DESIGN.md s25);
+    B may be None, Y may be A or B."""
+    Y = _ln_args(A, B, gamma, beta, Y)
+    _check("qgemm_layernorm_rows",
+           load().qgemm_layernorm_rows(A.data_ptr(), 0 if B is None else B.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
+                                       float(eps), Y.data_ptr(), A.shape[0], A.shape[1], _stream(A.device)))
+    return Y
+
+
+def _packed_out(out, M: int, K: int, device):
+    """The buffer of a fused pack: a fresh one, or the caller's Packed of the same geometry."""
+    if out is None:
+        return _alloc_packed(M, K, device)
+    assert isinstance(out, Packed) and (out.rows, out.k) == (M, K), f"out: a Packed of {M} x {K}"
+    return out.buf
+
+
+def layernorm_pack_a(A, B, gamma, beta, eps: float = 1e-5, Y=None, range: float = DEFAULT_RANGE, out=None):  # noqa: A002
+    """layernorm_rows that also packs Y's rows for the next quantized linear (qgemm_layernorm_pack_a): returns
+    (Y, Packed), the Packed byte for byte pack_a(Y) (written into `out`'s buffer where given)."""
+    Y = _ln_args(A, B, gamma, beta, Y)
+    M, K = A.shape
+    buf = _packed_out(out, M, K, A.device)
+    _check("qgemm_layernorm_pack_a",
+           load().qgemm_layernorm_pack_a(A.data_ptr(), 0 if B is None else B.data_ptr(), gamma.data_ptr(),
+                                         beta.data_ptr(), float(eps), Y.data_ptr(), M, K, float(range), buf.data_ptr(),
+                                         _stream(A.device)))
+    return Y, Packed(buf, M, K, range)
+
+
+def gelu_rows(X, Y=None):
+    """The tanh-form GELU elementwise (qgemm_gelu_rows): X rows x w with unit inner stride, any row stride."""
+    import torch
+    _require_device_f32(X, "X")
+    assert X.dim() == 2 and X.stride(1) == 1, "X: rows x w, unit inner stride"
+    Y = torch.empty(X.shape, dtype=torch.float32, device=X.device) if Y is None else Y
+    _require_device_f32(Y, "Y")
+    assert Y.shape == X.shape and Y.stride(1) == 1
+    _check("qgemm_gelu_rows", load().qgemm_gelu_rows(X.data_ptr(), X.stride(0), Y.data_ptr(), Y.stride(0), X.shape[0],
+                                                    X.shape[1], _stream(X.device)))
+    return Y
+
+
+def gelu_pack_a(X, range: float = DEFAULT_RANGE, out=None) -> Packed:  # noqa: A002
+    """pack_a(gelu_rows(X)) in one launch, the GELU'd matrix never written (qgemm_gelu_pack_a); k <= 16384."""
+    _require_device_f32(X, "X")
+    assert X.dim() == 2 and X.stride(1) == 1, "X: m x k, unit inner stride"
+    M, K = X.shape
+    buf = _packed_out(out, M, K, X.device)
+    _check("qgemm_gelu_pack_a", load().qgemm_gelu_pack_a(X.data_ptr(), X.stride(0), M, K, float(range), buf.data_ptr(),
+                                                        _stream(X.device)))
+    return Packed(buf, M, K, range)
+
+
 def mm_outlier(A, B, threshold: float = 6.0, C=None):
     """LLM.int8() decomposition: outlier feature columns in fp32, the rest int8.
     Returns (C, number of outlier columns)."""
@@ -1053,6 +1156,11 @@ def encoder_weight_seed(base: int, block: int, kind: int, head: int) -> int:
 # The weight kinds by name (include/qgemm.h): KIND_WQ .. KIND_WV and KIND_WQ2 .. KIND_WV2 are one tensor per head.
 (KIND_WQ, KIND_WK, KIND_WV, KIND_WO, KIND_W1, KIND_B1, KIND_W2, KIND_B2,
  KIND_WQ2, KIND_WK2, KIND_WV2, KIND_WO2) = range(12)
+# The standard architecture's vectors (qgemm_model_create), 1 x d_model each, head 0; KIND_BQ2 .. on a
+# decoder only.  A reference-arch model refuses them.
+(KIND_BQ, KIND_BK, KIND_BV, KIND_BO, KIND_G1, KIND_BE1, KIND_G3, KIND_BE3,
+ KIND_BQ2, KIND_BK2, KIND_BV2, KIND_BO2, KIND_G2, KIND_BE2) = range(12, 26)
+_VECTOR_KINDS = (KIND_B1, KIND_B2) + tuple(range(KIND_BQ, KIND_BE2 + 1))
 # packed_weight's `which`
 (WEIGHT_WQKV, WEIGHT_WO, WEIGHT_W1, WEIGHT_W2, WEIGHT_WQ2, WEIGHT_WKV2, WEIGHT_WO2) = range(7)
 
@@ -1065,7 +1173,19 @@ class _DeviceView:
         self.__cuda_array_interface__ = {"shape": (nbytes,), "typestr": "|u1", "data": (ptr, False), "version": 2}
 
 
-class _ModelWeights:
+class _ArchKeywords(type):
+    """Encoder(..., arch=, activation=, ln_eps=) and the same on Decoder: keyword-only arguments of the class call,
+    set on the object before __init__ runs.  __init__ keeps its parameter list as it was (its last parameters stay
+    max_rows, and n_slots on a Decoder), so positional callers and tools that read that list see no change."""
+
+    def __call__(cls, *args, arch: str = "reference", activation: str = "relu", ln_eps: float = 1e-5, **kw):
+        self = cls.__new__(cls)
+        self.arch, self.activation, self.ln_eps = arch, activation, float(ln_eps)
+        self.__init__(*args, **kw)
+        return self
+
+
+class _ModelWeights(metaclass=_ArchKeywords):
     """Caller-supplied weights of an Encoder or Decoder (qgemm_model_*).  A weight tensor is rows x
     cols with y = x W, as layout "kn"; a checkpoint's [out, in] tensor is layout "nk".  fp32 or bf16, any strides."""
 
@@ -1094,7 +1214,7 @@ class _ModelWeights:
                 self.set_weight(block, kind, W[h], head=h, layout=layout)
             return
         head = 0 if head is None else int(head)
-        if kind in (KIND_B1, KIND_B2):
+        if kind in _VECTOR_KINDS:
             W = W.reshape(1, -1) if W.dim() == 1 else W
             layout = "kn"
         tag, r, c, sh, sw = _window_source(W, layout, "W")
@@ -1108,6 +1228,85 @@ class _ModelWeights:
             block, kind = key[0], key[1]
             self.set_weight(block, kind, W, head=key[2] if len(key) > 2 else None, layout=layout)
 
+    def _create_model(self, cross: bool, max_enc_seq: int, flags: int, n_slots: int, max_rows, arch: str,
+                      activation: str, ln_eps: float):
+        """qgemm_model_create: the creator that knows architectures (the older creators make reference-arch models)."""
+        assert arch in ARCHS, f"arch: one of {sorted(ARCHS)}"
+        assert activation in ACTIVATIONS, f"activation: one of {sorted(ACTIVATIONS)}"
+        desc = ModelDesc(ctypes.sizeof(ModelDesc), 1 if cross else 0, self.d_model, self.n_heads, self.d_ff,
+                         self.n_blocks, self.max_seq, max_enc_seq, self.seed, flags, n_slots,
+                         0 if max_rows is None else int(max_rows), ARCHS[arch], ACTIVATIONS[activation], float(ln_eps))
+        h = ctypes.c_void_p()
+        _check("qgemm_model_create", load().qgemm_model_create(ctypes.byref(desc), ctypes.byref(h)))
+        return h
+
+    def info(self) -> dict:
+        """The descriptor the model was created with (qgemm_model_info), as a dict."""
+        desc = ModelDesc()
+        _check("qgemm_model_info", load().qgemm_model_info(self._h, ctypes.byref(desc)))
+        return {name: getattr(desc, name) for name, _ in ModelDesc._fields_}
+
+    def load_torch_layer(self, block: int, layer):
+        """Load every tensor of `block` from a torch.nn.TransformerEncoderLayer (an Encoder) or TransformerDecoderLayer
+        (a Decoder) with norm_first=False: the set_weight calls for the q / k / v thirds of in_proj_weight head by head
+        (rows h d_k .. of a third are head h's [out, in] tensor), in_proj_bias, out_proj, linear1 / linear2 and the
+        norms; a decoder layer's multihead_attn is the cross-attention and its norm2 LN2, an encoder layer's norm2 is
+        the FFN's LN (kinds KIND_G3 / KIND_BE3).  Tensors are copied to the current device as they are (fp32 or bf16,
+        anything else as fp32).  ValueError: norm_first=True, a width, head count or epsilon that is not the model's, a
+        layer of the other kind, or a reference-arch model.  The layer's activation is not looked at: create the model
+        with the matching one."""
+        import torch
+        if self.arch != "standard":
+            raise ValueError("load_torch_layer needs a model created with arch='standard'")
+        cross = hasattr(layer, "multihead_attn")
+        if cross != isinstance(self, Decoder):
+            raise ValueError("an Encoder takes a TransformerEncoderLayer, a Decoder a TransformerDecoderLayer")
+        if getattr(layer, "norm_first", False):
+            raise ValueError("norm_first=True (pre-LN) is not the standard architecture's block")
+        d, H, dk = self.d_model, self.n_heads, self.d_model // self.n_heads
+        attns = [layer.self_attn] + ([layer.multihead_attn] if cross else [])
+        for a in attns:
+            if a.embed_dim != d or a.num_heads != H or a.in_proj_weight is None or a.in_proj_bias is None:
+                raise ValueError(f"attention of width {a.embed_dim} with {a.num_heads} heads (fused, biased in_proj) "
+                                 f"expected: the model has d_model {d}, {H} heads")
+        if (layer.linear1.in_features, layer.linear1.out_features) != (d, self.d_ff) or \
+                (layer.linear2.in_features, layer.linear2.out_features) != (self.d_ff, d):
+            raise ValueError(f"the layer's FFN is not {d} x {self.d_ff} x {d}")
+        norms = [layer.norm1, layer.norm2] + ([layer.norm3] if cross else [])
+        for n in norms:
+            if tuple(n.normalized_shape) != (d,) or n.weight is None or n.bias is None or \
+                    abs(n.eps - self.ln_eps) > 1e-12:
+                raise ValueError(f"the layer's norms must be affine LayerNorm({d}, eps={self.ln_eps})")
+        dev = torch.device("cuda", torch.cuda.current_device())
+
+        def dv(t):
+            t = t.detach()
+            return t.to(dev) if t.dtype in (torch.float32, torch.bfloat16) else t.to(dev, torch.float32)
+
+        def attn(a, wkinds, bkinds, wo, bo):
+            Wi, bi = dv(a.in_proj_weight), dv(a.in_proj_bias)
+            for j, (wk, bk) in enumerate(zip(wkinds, bkinds)):
+                for h in range(H):
+                    self.set_weight(block, wk, Wi[j * d + h * dk:j * d + (h + 1) * dk], head=h, layout="nk")
+                self.set_weight(block, bk, bi[j * d:(j + 1) * d])
+            self.set_weight(block, wo, dv(a.out_proj.weight), layout="nk")
+            self.set_weight(block, bo, dv(a.out_proj.bias))
+
+        attn(layer.self_attn, (KIND_WQ, KIND_WK, KIND_WV), (KIND_BQ, KIND_BK, KIND_BV), KIND_WO, KIND_BO)
+        self.set_weight(block, KIND_G1, dv(layer.norm1.weight))
+        self.set_weight(block, KIND_BE1, dv(layer.norm1.bias))
+        if cross:
+            attn(layer.multihead_attn, (KIND_WQ2, KIND_WK2, KIND_WV2), (KIND_BQ2, KIND_BK2, KIND_BV2), KIND_WO2, KIND_BO2)
+            self.set_weight(block, KIND_G2, dv(layer.norm2.weight))
+            self.set_weight(block, KIND_BE2, dv(layer.norm2.bias))
+        self.set_weight(block, KIND_W1, dv(layer.linear1.weight), layout="nk")
+        self.set_weight(block, KIND_B1, dv(layer.linear1.bias))
+        self.set_weight(block, KIND_W2, dv(layer.linear2.weight), layout="nk")
+        self.set_weight(block, KIND_B2, dv(layer.linear2.bias))
+        ffn_norm = layer.norm3 if cross else layer.norm2
+        self.set_weight(block, KIND_G3, dv(ffn_norm.weight))
+        self.set_weight(block, KIND_BE3, dv(ffn_norm.bias))
+
     def packed_weight(self, block: int, which: int) -> Packed:
         """Block's packed weight `which` (WEIGHT_WQKV ..) as a NON-OWNING Packed view of the model's own buffer, for
         tests and tools: read it, do not write it, and do not use it after close()."""
@@ -1120,7 +1319,8 @@ class _ModelWeights:
         return Packed(buf, n.value, k.value, DEFAULT_RANGE)
 
     def bias(self, block: int, kind: int):
-        """Block's bias KIND_B1 or KIND_B2: a copy, n floats on the device."""
+        """Block's bias KIND_B1 or KIND_B2, or on a standard model a vector of kinds KIND_BQ ..: a copy, n floats on
+        the device."""
         import torch
         p, n = ctypes.c_void_p(), ctypes.c_int()
         _check("qgemm_model_bias", load().qgemm_model_bias(self._h, block, kind, ctypes.byref(p), ctypes.byref(n)))
@@ -1130,7 +1330,12 @@ class _ModelWeights:
 
 class Encoder(_ModelWeights):
     """transformer.cu:14-77's Encoder with its linears on the quantized path.  max_rows
-    (qgemm_encoder_create_rows): the rows forward_batch may run at once, max_seq where left out."""
+    (qgemm_encoder_create_rows): the rows forward_batch may run at once, max_seq where left out.
+    arch="standard" (a keyword of the class call, as activation= and ln_eps= are; qgemm_model_create): the
+    textbook post-LN block instead -- biases on every
+    projection, block-input residuals, LayerNorm with gamma, beta and ln_eps, activation "relu" or "gelu_tanh" -- which
+    load_torch_layer fills from a torch.nn.TransformerEncoderLayer; the defaults give the reference's block through the
+    older creators."""
 
     def __init__(self, d_model: int, n_heads: int, d_ff: int, n_blocks: int, max_seq: int, seed: int = 0,
                  max_rows=None):
@@ -1138,7 +1343,10 @@ class Encoder(_ModelWeights):
             d_model, n_heads, d_ff, n_blocks, max_seq, seed)
         self.max_rows = max_rows
         h = ctypes.c_void_p()
-        if max_rows is None:
+        if self.arch != "reference" or self.activation != "relu":
+            # the post-LN block of torch.nn.TransformerEncoderLayer (qgemm_model_create)
+            h = self._create_model(False, 0, 0, 0, max_rows, self.arch, self.activation, self.ln_eps)
+        elif max_rows is None:
             _check("qgemm_encoder_create", load().qgemm_encoder_create(d_model, n_heads, d_ff, n_blocks, max_seq, seed,
                                                                       ctypes.byref(h)))
         else:
@@ -1452,7 +1660,9 @@ class Decoder(_ModelWeights):
     begin / step are slot 0's.  max_rows (qgemm_decoder_create_rows; a keyword, ahead of n_slots only so that n_slots
     stays the last parameter): the rows step_varlen may run at once.  With n_slots > 1 the decoder also
     owns the row table of the copy-free beam search (beam_begin / step_batch_indirect / beam_reindex / beam_table /
-    generate_beam_indirect)."""
+    generate_beam_indirect).  arch / activation / ln_eps: as on Encoder; every call above works on a
+    standard-arch decoder as it does on the reference's, and load_torch_layer fills a block from a
+    torch.nn.TransformerDecoderLayer."""
 
     def __init__(self, d_model: int, n_heads: int, d_ff: int, n_blocks: int, max_seq: int, max_enc_seq: int,
                  seed: int = 0, causal: bool = False, kv_cache: bool = False, max_rows=None, n_slots: int = 1):
@@ -1461,7 +1671,11 @@ class Decoder(_ModelWeights):
         self.causal, self.kv_cache, self.n_slots = bool(causal), bool(kv_cache), int(n_slots)
         self.max_rows = max_rows
         h = ctypes.c_void_p()
-        if max_rows is not None:
+        if self.arch != "reference" or self.activation != "relu":
+            # the post-LN block of torch.nn.TransformerDecoderLayer (qgemm_model_create)
+            flags = (QGEMM_DECODER_CAUSAL if causal else 0) | (QGEMM_DECODER_KV_CACHE if kv_cache else 0)
+            h = self._create_model(True, max_enc_seq, flags, n_slots, max_rows, self.arch, self.activation, self.ln_eps)
+        elif max_rows is not None:
             # a row budget for step_varlen (qgemm_decoder_create_rows): create_slots with larger scratch buffers
             assert causal and kv_cache, "max_rows belongs to causal=True, kv_cache=True"
             _check("qgemm_decoder_create_rows",

@@ -645,6 +645,74 @@ int qgemm_model_bias(void *model, int block, int kind, const float **bias, int *
     return err(stack_bias(static_cast<Stack *>(model), block, kind, bias, n));
 }
 
+// ---- the standard block ----
+
+int qgemm_layernorm_rows(const float *A, const float *B_or_null, const float *gamma, const float *beta, float eps,
+                         float *Y, int64_t rows, int w, void *stream) {
+    return err(launch_layernorm_rows(A, B_or_null, gamma, beta, eps, Y, rows, w, static_cast<hipStream_t>(stream)));
+}
+
+int qgemm_layernorm_pack_a(const float *A, const float *B_or_null, const float *gamma, const float *beta, float eps,
+                           float *Y, int64_t rows, int w, float range, void *packed_a, void *stream) {
+    if (!packed_a || rows < 0 || rows > INT32_MAX || w < 1 || w > 4096) return err(hipErrorInvalidValue);
+    return err(launch_layernorm_rows_pack(A, B_or_null, gamma, beta, eps, Y, rows, w, range,
+                                          packed_view(packed_a, (int)rows, w), static_cast<hipStream_t>(stream)));
+}
+
+int qgemm_gelu_rows(const float *X, int64_t x_stride_h, float *Y, int64_t y_stride_h, int64_t rows, int w,
+                    void *stream) {
+    return err(launch_gelu_rows(X, x_stride_h, Y, y_stride_h, rows, w, static_cast<hipStream_t>(stream)));
+}
+
+int qgemm_gelu_pack_a(const float *X, int64_t x_stride_h, int m, int k, float range, void *packed_a, void *stream) {
+    if (!packed_a || m < 0 || k < 1 || k > 16384) return err(hipErrorInvalidValue);
+    return err(launch_gelu_pack(X, x_stride_h, m, k, range, packed_view(packed_a, m, k),
+                                static_cast<hipStream_t>(stream)));
+}
+
+int qgemm_model_create(const qgemm_model_desc *desc, void **model) {
+    if (!model) return err(hipErrorInvalidValue);
+    *model = nullptr;
+    if (!desc || desc->size != sizeof(qgemm_model_desc)) return err(hipErrorInvalidValue);
+    const qgemm_model_desc &d = *desc;
+    if ((d.arch != QGEMM_ARCH_REFERENCE && d.arch != QGEMM_ARCH_STANDARD) ||
+        (d.activation != QGEMM_ACT_RELU && d.activation != QGEMM_ACT_GELU_TANH) ||
+        (d.arch == QGEMM_ARCH_REFERENCE && d.activation != QGEMM_ACT_RELU) || !(d.ln_eps >= 0.0f) ||
+        (d.cross != 0 && d.cross != 1) || d.n_slots < 0 || d.max_rows < 0)
+        return err(hipErrorInvalidValue);
+    const int n_slots = d.n_slots ? d.n_slots : 1;
+    bool causal = false, kv_cache = false;
+    if (!d.cross) {  // qgemm_encoder_create_rows
+        if (d.flags || n_slots != 1) return err(hipErrorInvalidValue);
+    } else if (n_slots > 1 || d.max_rows > 0) {  // qgemm_decoder_create_rows
+        if (d.flags != (QGEMM_DECODER_CAUSAL | QGEMM_DECODER_KV_CACHE) || n_slots > QGEMM_DECODE_MAX_BATCH)
+            return err(hipErrorInvalidValue);
+        causal = kv_cache = true;
+    } else {  // qgemm_decoder_create_ex
+        if (d.flags & ~(QGEMM_DECODER_CAUSAL | QGEMM_DECODER_KV_CACHE)) return err(hipErrorInvalidValue);
+        if ((d.flags & QGEMM_DECODER_KV_CACHE) && !(d.flags & QGEMM_DECODER_CAUSAL)) return err(hipErrorInvalidValue);
+        causal = (d.flags & QGEMM_DECODER_CAUSAL) != 0;
+        kv_cache = (d.flags & QGEMM_DECODER_KV_CACHE) != 0;
+    }
+    Stack *S = nullptr;
+    const hipError_t e = stack_create(d.d_model, d.n_heads, d.d_ff, d.n_blocks, d.max_seq, d.cross ? d.max_enc_seq : 0,
+                                      d.seed, d.cross != 0, causal, kv_cache, &S, n_slots, d.max_rows, d.arch,
+                                      d.activation, d.ln_eps);
+    *model = S;
+    return err(e);
+}
+
+int qgemm_model_info(void *model, qgemm_model_desc *desc) {
+    StackDesc sd;
+    if (!desc) return err(hipErrorInvalidValue);
+    const hipError_t e = stack_describe(static_cast<Stack *>(model), &sd);
+    if (e) return err(e);
+    *desc = qgemm_model_desc{(uint32_t)sizeof(qgemm_model_desc), sd.cross, sd.d_model, sd.n_heads, sd.d_ff, sd.n_blocks,
+                             sd.max_seq, sd.max_enc_seq, sd.seed, sd.flags, sd.n_slots, sd.max_rows, sd.arch,
+                             sd.activation, sd.ln_eps};
+    return 0;
+}
+
 size_t qgemm_mm_outlier_workspace_size(int m, int n, int k) {
     if (!dims_ok(m, n, k)) return 0;
     return align256(outlier_scratch_bytes(m, n, k)) + op_mm_quantize_workspace_size(m, n, k);

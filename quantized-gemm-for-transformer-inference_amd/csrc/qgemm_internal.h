@@ -461,7 +461,8 @@ float encoder_init_bound(int n);
 // the number of sequences the caches hold; max_rows (0: none) raises the rows the scratch buffers hold
 // for encoder_forward_batch / decoder_step_varlen, refused where a row-local index could leave int32
 hipError_t stack_create(int d_model, int n_heads, int d_ff, int n_blocks, int max_seq, int max_enc_seq, uint64_t seed,
-                        bool cross, bool causal, bool kv_cache, Stack **out, int n_slots = 1, int max_rows = 0);
+                        bool cross, bool causal, bool kv_cache, Stack **out, int n_slots = 1, int max_rows = 0,
+                        int arch = 0, int activation = 0, float ln_eps = 0.0f);
 void stack_destroy(Stack *S);
 hipError_t encoder_forward(Stack *S, const float *X, float *Y, int seq, hipStream_t s);
 // begin / step of one cache slot (qgemm_decoder_begin / qgemm_decoder_step are slot 0's)
@@ -572,5 +573,28 @@ struct GemmEvents {
 GemmEvents take_gemm_events();
 void set_gemm_events(hipEvent_t start, hipEvent_t stop);
 void set_gemm_event_mode(int mode);
+
+// The standard post-LN block (the contracts are at qgemm_layernorm_rows, qgemm_gelu_rows and
+// qgemm_model_create in include/qgemm.h).
+// norm.hip: Y = LN(A + B) with gamma, beta and eps (B may be nullptr; Y may be A or B), one wave per row, w <= 4096;
+// the pack variant also writes Y's rows packed, padding rows and columns included.  Every check before the launch.
+hipError_t launch_layernorm_rows(const float *A, const float *B, const float *gamma, const float *beta, float eps,
+                                 float *Y, int64_t rows, int w, hipStream_t stream);
+hipError_t launch_layernorm_rows_pack(const float *A, const float *B, const float *gamma, const float *beta, float eps,
+                                      float *Y, int64_t rows, int w, float range, PackedView out, hipStream_t stream);
+// gelu.hip: the tanh-form GELU elementwise (row strides in floats, unit inner stride), and fused into pack_rows of an
+// m x k matrix, k <= 16384: the packed view of the GELU'd matrix, which is never written
+hipError_t launch_gelu_rows(const float *X, int64_t xsh, float *Y, int64_t ysh, int64_t rows, int w, hipStream_t stream);
+hipError_t launch_gelu_pack(const float *X, int64_t xsh, int m, int k, float range, PackedView out, hipStream_t stream);
+// transformer.hip: the architecture of a stack (stack_create's arch: 0 the reference's block, 1 the standard one with
+// its new tensors allocated and set, b_* = +0, gamma = 1, beta = +0; activation: 0 relu, 1 tanh GELU, arch 1 only);
+// stack_describe reads back what creation was given.
+struct StackDesc {
+    int cross, d_model, n_heads, d_ff, n_blocks, max_seq, max_enc_seq;
+    uint64_t seed;
+    int flags, n_slots, max_rows, arch, activation;
+    float ln_eps;
+};
+hipError_t stack_describe(const Stack *S, StackDesc *out);
 
 }  // namespace qgemm

@@ -78,6 +78,15 @@
 // Each sequence's rows are forward's / step_slot's on it alone, bit for bit.  The scratch buffers hold
 // max(the above, max_rows) rows; the scores stay sized by max_seq (the per-sequence path runs one sequence at a time).
 //
+// The standard architecture (qgemm_model_create with QGEMM_ARCH_STANDARD): the textbook post-LN block
+// as a second architecture of the same stack.  run_blocks keeps its launches and their order and changes what some of
+// them are:   x1 = LN1(x + heads W_O + b_O), x2 = LN2(x1 + heads2 W_O2 + b_O2), y = LN3(x2 + act(x2 W1 + b1) W2 + b2)
+//   * the projections' biases ride in the GEMM epilogue ([b_q | b_k | b_v] beside [Wq | Wk | Wv], ..): no launch;
+//   * the three add + layernorm launches are norm.hip's (gamma, beta, eps; the residual is the sub-layer's input);
+//   * with GELU, W1 runs without relu and the pack_rows in front of W2 is gelu.hip's fused pack.
+// Every new step is row-local, so arguments (1) and (2) above, and with them every contract of the cached, batched and
+// varlen calls, hold as they do for the reference block.  The cross caches carry b_k2 | b_v2.
+//
 // Caller-supplied weights (qgemm_model_set_weight).  The seeded draw stays what creation does; afterwards
 // stack_set_weight replaces one tensor at a time: launch_pack_b_window (weights.hip) packs it into its column window of
 // the block's packed weight, a bias is copied.  Every call above then runs on the current weights.
@@ -94,7 +103,10 @@ namespace {
 
 // every tensor of a block its own seed stream; 8 .. 11 are the cross-attention's
 enum WeightKind { kWq = 0, kWk = 1, kWv = 2, kWo = 3, kW1 = 4, kB1 = 5, kW2 = 6, kB2 = 7,
-                  kWq2 = 8, kWk2 = 9, kWv2 = 10, kWo2 = 11 };
+                  kWq2 = 8, kWk2 = 9, kWv2 = 10, kWo2 = 11,
+                  // the standard architecture's, 1 x d_model each; 20 .. 25 are the cross-attention's
+                  kBq = 12, kBk = 13, kBv = 14, kBo = 15, kG1 = 16, kBe1 = 17, kG3 = 18, kBe3 = 19,
+                  kBq2 = 20, kBk2 = 21, kBv2 = 22, kBo2 = 23, kG2 = 24, kBe2 = 25 };
 
 }  // namespace
 
@@ -110,6 +122,12 @@ struct Block {
     void *wqkv = nullptr, *wo = nullptr, *w1 = nullptr, *w2 = nullptr;  // packed (W^T int8 + Cw)
     void *wq2 = nullptr, *wkv2 = nullptr, *wo2 = nullptr;               // cross
     float *b1 = nullptr, *b2 = nullptr;
+    // the standard architecture's vectors, ONE allocation `sp` (nullptr on a reference stack, and so is every pointer
+    // into it: a nullptr bias is the reference's GEMM call): [bqkv: 3d][bo][g1][be1][g3][be3] and with cross-attention
+    // [bq2][bkv2: 2d][bo2][g2][be2] -- the order of kinds 12 .. 25, the fused biases side by side as their fused
+    // weights' columns are
+    float *sp = nullptr, *bqkv = nullptr, *bo = nullptr, *g1 = nullptr, *be1 = nullptr, *g3 = nullptr, *be3 = nullptr;
+    float *bq2 = nullptr, *bkv2 = nullptr, *bo2 = nullptr, *g2 = nullptr, *be2 = nullptr;
     // kv_cache: n_slots slabs of max_seq x 3d ([Q | K | V] rows) and n_slots slabs of max_enc_seq x 2d ([K2 | V2])
     float *qkv_cache = nullptr, *kv2_cache = nullptr;
 };
@@ -120,6 +138,11 @@ struct Stack {
     bool causal = false;    // the self-attention masks keys past the query's own row (QGEMM_DECODER_CAUSAL)
     bool kv_cache = false;  // the blocks own caches for decoder_begin / decoder_step (QGEMM_DECODER_KV_CACHE)
     int n_slots = 1;        // sequences the caches hold side by side (qgemm_decoder_create_slots)
+    bool standard = false;  // the post-LN block with biases, block-input residuals and a real LayerNorm
+    bool gelu = false;      // standard: the FFN's activation is the tanh-form GELU, fused into the pack in front of W2
+    float ln_eps = 0.0f;    // standard: every LN's epsilon
+    uint64_t seed = 0;      // as created, for stack_describe
+    int max_rows = 0;
     int scratch_rows = 0;   // rows the scratch buffers hold: max_seq, 8 rows of every slot or max_rows, the largest
     // per slot, host side, updated at enqueue time: enc_seq of the sequence begun (0: no begin yet) and the filled
     // length (cache rows 0 .. filled - 1 hold the sequence so far)
@@ -202,7 +225,7 @@ hipError_t linear(Stack &S, const float *x, int seq, int k, const void *wpacked,
 void stack_destroy(Stack *S) {
     if (!S) return;
     for (auto &b : S->blocks)
-        for (void *p : {b.wqkv, b.wo, b.wq2, b.wkv2, b.wo2, b.w1, b.w2, (void *)b.b1, (void *)b.b2,
+        for (void *p : {b.wqkv, b.wo, b.wq2, b.wkv2, b.wo2, b.w1, b.w2, (void *)b.b1, (void *)b.b2, (void *)b.sp,
                         (void *)b.qkv_cache, (void *)b.kv2_cache})
             (void)hipFree(p);
     for (void *p : {(void *)S->qkv, (void *)S->scores, (void *)S->heads, (void *)S->t, (void *)S->ffn, (void *)S->x,
@@ -213,8 +236,12 @@ void stack_destroy(Stack *S) {
 }
 
 hipError_t stack_create(int d_model, int n_heads, int d_ff, int n_blocks, int max_seq, int max_enc_seq, uint64_t seed,
-                        bool cross, bool causal, bool kv_cache, Stack **out, int n_slots, int max_rows) {
+                        bool cross, bool causal, bool kv_cache, Stack **out, int n_slots, int max_rows, int arch,
+                        int activation, float ln_eps) {
     *out = nullptr;
+    if ((arch != 0 && arch != 1) || (activation != 0 && activation != 1) || (arch == 0 && activation != 0) ||
+        !(ln_eps >= 0.0f) || (activation == 1 && d_ff > 16384))  // (the GELU pack's row limit)
+        return hipErrorInvalidValue;
     // max_rows: the row-local kernels (pack, GEMM epilogue, add + layernorm) address an activation buffer of
     // scratch_rows x 3 d_model or x d_ff floats and its packed image of rows padded to 256 x columns padded to 128;
     // with that padded product inside int32 no element index leaves its type, whichever type a kernel forms it in
@@ -239,6 +266,11 @@ hipError_t stack_create(int d_model, int n_heads, int d_ff, int n_blocks, int ma
     S->causal = causal;
     S->kv_cache = kv_cache;
     S->n_slots = n_slots;
+    S->standard = arch == 1;
+    S->gelu = activation == 1;
+    S->ln_eps = ln_eps;
+    S->seed = seed;
+    S->max_rows = max_rows;
     // a batched step runs up to 8 rows of every slot through the scratch buffers (one slot: a step's rows fit max_seq)
     // and a batched forward or a varlen step its row budget (qgemm_*_create_rows)
     S->scratch_rows = std::max(n_slots > 1 ? std::max(max_seq, 8 * n_slots) : max_seq, max_rows);
@@ -317,6 +349,18 @@ hipError_t stack_create(int d_model, int n_heads, int d_ff, int n_blocks, int ma
             break;
         if ((e = launch_fill_uniform(B.b1, d_ff, encoder_weight_seed(seed, i, kB1, 0), -bd, bd, s))) break;
         if ((e = launch_fill_uniform(B.b2, d, encoder_weight_seed(seed, i, kB2, 0), -bf, bf, s))) break;
+        if (S->standard) {  // b = +0, gamma = 1, beta = +0: nothing drawn, so no new generator contract
+            const size_t nd = cross ? 16 : 8;  // vectors of d floats
+            if ((e = alloc_f(&B.sp, nd * d))) break;
+            float *p = B.sp;
+            auto take = [&](int n) { float *r = p; p += (size_t)n * d; return r; };
+            B.bqkv = take(3), B.bo = take(1), B.g1 = take(1), B.be1 = take(1), B.g3 = take(1), B.be3 = take(1);
+            if (cross) B.bq2 = take(1), B.bkv2 = take(2), B.bo2 = take(1), B.g2 = take(1), B.be2 = take(1);
+            std::vector<float> host(nd * d, 0.0f);
+            for (float *g : {B.g1, B.g3, B.g2})
+                if (g) std::fill_n(host.begin() + (g - B.sp), d, 1.0f);
+            if ((e = hipMemcpy(B.sp, host.data(), sizeof(float) * host.size(), hipMemcpyHostToDevice))) break;
+        }
     }
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     (void)hipFree(tmp);
@@ -415,7 +459,8 @@ hipError_t run_blocks(Stack *S, const float *X, float *Y, int rows, int enc_seq,
         const bool to_cache = cached && !batch && !var;                         // the GEMM writes the cache rows itself
         float *qkv = to_cache ? B.qkv_cache + slot * self_slab : S->qkv;        // row 0 of [Q | K | V]
         float *qrows = qkv + (size_t)(to_cache ? pos : 0) * 3 * d;              // the rows this call projects
-        if ((e = linear(*S, in_packed ? nullptr : in, seq, d, B.wqkv, 3 * d, qrows, nullptr, false, s))) return e;
+        // (B.bqkv and every other standard-only pointer is nullptr on a reference stack: the reference's call)
+        if ((e = linear(*S, in_packed ? nullptr : in, seq, d, B.wqkv, 3 * d, qrows, B.bqkv, false, s))) return e;
         // S_h = Q_h K_h^T, P_h = softmax(S_h * 1/sqrt(d_k)), heads[:, h*d_v..] = P_h V_h, Q, K and V the thirds of qkv
         // (causal: row i sees rows 0 .. i, so row i of the forward depends on rows 0 .. i of X alone)
         if (batch) {
@@ -451,14 +496,18 @@ hipError_t run_blocks(Stack *S, const float *X, float *Y, int rows, int enc_seq,
             return e;
         // output = multiHeadOut @ W_O; x1 = LN(output + multiHeadOut), packed by the same launch: the next linear
         // quantizes nothing itself
-        if ((e = linear(*S, S->heads, seq, d, B.wo, d, S->t, nullptr, false, s))) return e;
-        if ((e = launch_add_layernorm_rows_pack(S->t, S->heads, S->x, seq, d, 127.0f, act_view(*S, seq, d), s)))
+        // standard: x1 = LN1(in + heads W_O + b_O), the residual the block's input
+        if ((e = linear(*S, S->heads, seq, d, B.wo, d, S->t, B.bo, false, s))) return e;
+        if ((e = S->standard ? launch_layernorm_rows_pack(S->t, in, B.g1, B.be1, S->ln_eps, S->x, seq, d, 127.0f,
+                                                          act_view(*S, seq, d), s)
+                             : launch_add_layernorm_rows_pack(S->t, S->heads, S->x, seq, d, 127.0f,
+                                                              act_view(*S, seq, d), s)))
             return e;
         if (S->cross) {
             // ---- cross-attention: queries from x1, keys and values from enc_out
-            if ((e = linear(*S, nullptr, seq, d, B.wq2, d, S->q2, nullptr, false, s))) return e;
+            if ((e = linear(*S, nullptr, seq, d, B.wq2, d, S->q2, B.bq2, false, s))) return e;
             float *kv2 = cached ? B.kv2_cache + slot * cross_slab : S->kv2;
-            if (!cached && (e = gemm(*S, enc_view(*S, enc_seq), enc_seq, d, B.wkv2, 2 * d, kv2, nullptr, false, s)))
+            if (!cached && (e = gemm(*S, enc_view(*S, enc_seq), enc_seq, d, B.wkv2, 2 * d, kv2, B.bkv2, false, s)))
                 return e;
             if (batch) {
                 if ((e = launch_attention_decode_batched(S->q2, d, B.kv2_cache, 2 * d, cross_slab, B.kv2_cache + d, 2 * d,
@@ -473,10 +522,32 @@ hipError_t run_blocks(Stack *S, const float *X, float *Y, int rows, int enc_seq,
             } else if ((e = launch_attention(S->q2, d, kv2, 2 * d, kv2 + d, 2 * d, mho, d, seq, enc_seq, H, dk, scale,
                                              kNoMask, S->scores, s)))
                 return e;
-            if ((e = linear(*S, mho, seq, d, B.wo2, d, S->t, nullptr, false, s))) return e;
-            // x2 = LN(t + heads2), packed for the FFN's first linear
-            if ((e = launch_add_layernorm_rows_pack(S->t, mho, S->x, seq, d, 127.0f, act_view(*S, seq, d), s)))
+            if ((e = linear(*S, mho, seq, d, B.wo2, d, S->t, B.bo2, false, s))) return e;
+            // x2 = LN(t + heads2), packed for the FFN's first linear; standard: x2 = LN2(x1 + t), in place over x1
+            if ((e = S->standard ? launch_layernorm_rows_pack(S->t, S->x, B.g2, B.be2, S->ln_eps, S->x, seq, d, 127.0f,
+                                                              act_view(*S, seq, d), s)
+                                 : launch_add_layernorm_rows_pack(S->t, mho, S->x, seq, d, 127.0f,
+                                                                  act_view(*S, seq, d), s)))
                 return e;
+        }
+        if (S->standard) {
+            // ---- FFN: y = LN3(x + act(x W1 + b1) W2 + b2), x = S->x the FFN's own input.  GELU: W1 without relu, and
+            // the pack in front of W2 applies GELU as it quantizes -- the launch count is the relu path's
+            if ((e = linear(*S, nullptr, seq, d, B.w1, S->d_ff, S->ffn, B.b1, !S->gelu, s))) return e;
+            if (S->gelu) {
+                const PackedView va = act_view(*S, seq, S->d_ff);
+                if ((e = launch_gelu_pack(S->ffn, S->d_ff, seq, S->d_ff, 127.0f, va, s))) return e;
+                if ((e = gemm(*S, va, seq, S->d_ff, B.w2, d, S->t, B.b2, false, s))) return e;
+            } else if ((e = linear(*S, S->ffn, seq, S->d_ff, B.w2, d, S->t, B.b2, false, s))) {
+                return e;
+            }
+            e = last ? launch_layernorm_rows(S->t, S->x, B.g3, B.be3, S->ln_eps, out, seq, d, s)
+                     : launch_layernorm_rows_pack(S->t, S->x, B.g3, B.be3, S->ln_eps, out, seq, d, 127.0f,
+                                                  act_view(*S, seq, d), s);
+            if (e) return e;
+            in = out;
+            in_packed = !last;
+            continue;
         }
         // ---- FFN: relu(x W1 + b1) W2 + b2; LN(ffn + multiHeadOut)
         if ((e = linear(*S, nullptr, seq, d, B.w1, S->d_ff, S->ffn, B.b1, true, s))) return e;
@@ -538,7 +609,7 @@ hipError_t decoder_begin_slot(Stack *S, int slot, const float *enc_out, int enc_
     if (e) return e;
     for (const Block &B : S->blocks)
         if ((e = gemm(*S, enc_view(*S, enc_seq), enc_seq, d, B.wkv2, 2 * d,
-                      B.kv2_cache + (int64_t)slot * S->max_enc_seq * 2 * d, nullptr, false, s)))
+                      B.kv2_cache + (int64_t)slot * S->max_enc_seq * 2 * d, B.bkv2, false, s)))
             return e;
     S->enc_seq[slot] = enc_seq;
     S->filled[slot] = 0;
@@ -851,7 +922,10 @@ struct WeightPlace {
     int k = 0, n_total = 0, col0 = 0, ncols = 0;
 };
 
-bool weight_kind_ok(const Stack *S, int kind) { return kind >= kWq && kind <= (S->cross ? kWo2 : kB2); }
+bool weight_kind_ok(const Stack *S, int kind) {
+    if (kind >= kBq) return S->standard && kind <= (S->cross ? kBe2 : kBe3);  // a reference stack lacks them
+    return kind >= kWq && kind <= (S->cross ? kWo2 : kB2);
+}
 bool weight_per_head(int kind) { return (kind >= kWq && kind <= kWv) || (kind >= kWq2 && kind <= kWv2); }
 
 bool weight_place(const Stack *S, const Block &B, int kind, int head, WeightPlace *p) {
@@ -866,7 +940,9 @@ bool weight_place(const Stack *S, const Block &B, int kind, int head, WeightPlac
         case kB2: *p = {nullptr, B.b2, 1, d, 0, d}; break;
         case kWq2: *p = {B.wq2, nullptr, d, d, head * dk, dk}; break;
         case kWk2: case kWv2: *p = {B.wkv2, nullptr, d, 2 * d, (kind - kWk2) * d + head * dk, dk}; break;
-        default: *p = {B.wo2, nullptr, d, d, 0, d}; break;  // kWo2
+        case kWo2: *p = {B.wo2, nullptr, d, d, 0, d}; break;
+        // the standard architecture's vectors, 1 x d_model each: B.sp holds them in the order of their kinds
+        default: *p = {nullptr, B.sp + (size_t)(kind - kBq) * d, 1, d, 0, d}; break;
     }
     return true;
 }
@@ -923,14 +999,22 @@ hipError_t stack_packed_weight(const Stack *S, int block, int which, const void 
     return hipSuccess;
 }
 
-// ... and a bias (kind 5 or 7), n floats on the device
+// ... and a bias (kind 5 or 7) or a vector of the standard architecture (kinds 12 ..), n floats on the device
 hipError_t stack_bias(const Stack *S, int block, int kind, const float **bias, int *n) {
     WeightPlace p;
-    if (!S || block < 0 || block >= S->n_blocks || !bias || (kind != kB1 && kind != kB2) ||
-        !weight_place(S, S->blocks[block], kind, 0, &p))
+    if (!S || block < 0 || block >= S->n_blocks || !bias || !weight_place(S, S->blocks[block], kind, 0, &p) || !p.bias)
         return hipErrorInvalidValue;
     *bias = p.bias;
     if (n) *n = p.ncols;
+    return hipSuccess;
+}
+
+hipError_t stack_describe(const Stack *S, StackDesc *out) {
+    if (!S || !out) return hipErrorInvalidValue;
+    // (QGEMM_DECODER_CAUSAL = 1, QGEMM_DECODER_KV_CACHE = 8, include/qgemm.h)
+    *out = StackDesc{S->cross, S->d_model, S->n_heads, S->d_ff, S->n_blocks, S->max_seq, S->max_enc_seq, S->seed,
+                     (S->causal ? 1 : 0) | (S->kv_cache ? 8 : 0), S->n_slots, S->max_rows, S->standard ? 1 : 0,
+                     S->gelu ? 1 : 0, S->ln_eps};
     return hipSuccess;
 }
 
