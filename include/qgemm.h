@@ -950,7 +950,7 @@ QGEMM_API int qgemm_gelu_pack_a(const float *X, int64_t x_stride_h, int m, int k
  * that family's destroy.  Every contract of those calls that rests on row-locality carries over: the new steps are
  * row-local.  hipErrorInvalidValue: a null pointer, a wrong size, an unknown arch or activation, GELU on the reference
  * architecture, GELU with d_ff > 16384 (qgemm_gelu_pack_a's limit), a negative or NaN ln_eps, and whatever the older
- * creators refuse.
+ * creators refuse.  arch also takes the pre-LN modifier bits QGEMM_ARCH_NORM_FIRST / QGEMM_ARCH_FINAL_NORM (below).
  * qgemm_model_info reads the descriptor back (n_slots as created, 1 for 0). */
 #define QGEMM_ARCH_REFERENCE 0
 #define QGEMM_ARCH_STANDARD 1
@@ -969,6 +969,45 @@ typedef struct {
 } qgemm_model_desc;
 QGEMM_API int qgemm_model_create(const qgemm_model_desc *desc, void **model);
 QGEMM_API int qgemm_model_info(void *model, qgemm_model_desc *desc);
+
+/* ---- Pre-LN blocks: norm-first stacks, a final norm, fused add + LN + pack -----------------
+ * The block of GPT-2, Whisper, mBART, ViT and torch.nn.Transformer*Layer(norm_first=True): every sub-layer normalises
+ * its own input and adds its output to the un-normalised residual stream (an encoder lacks the middle line):
+ *   x = x + SelfAttn(LN1(x)) W_O + b_O
+ *   x = x + CrossAttn(LN2(x), enc) W_O2 + b_O2
+ *   x = x + act(LN3(x) W1 + b1) W2 + b2
+ *   after the last block:  y = LNf(x)  (QGEMM_ARCH_FINAL_NORM)   or   y = x
+ * It is QGEMM_ARCH_STANDARD with two modifier bits on qgemm_model_desc.arch, which does not grow:
+ *   arch = QGEMM_ARCH_STANDARD | QGEMM_ARCH_NORM_FIRST [| QGEMM_ARCH_FINAL_NORM]
+ * hipErrorInvalidValue: any other bit above the low byte, NORM_FIRST on the reference architecture, FINAL_NORM without
+ * NORM_FIRST.  qgemm_model_info returns arch as given.  Kinds 12 .. 25 keep their meaning: gamma1 / beta1 belong to the
+ * LN in front of the self-attention, gamma2 / beta2 to the one in front of the cross-attention, gamma3 / beta3 to the
+ * one in front of the FFN.  A FINAL_NORM model has two more vectors, addressed with block = 0, head = 0:
+ *   kind 26, 27      gamma_f, beta_f   1 x d_model        LNf; created as gamma = 1, beta = +0
+ * with the copy path of kinds 5 and 7; every other model refuses them, and so does any other block index.  Setting
+ * them resets the cache slots as every kind does.  Cross keys and values come from enc_out as given.  Each sub-layer
+ * boundary is ONE launch of qgemm_prenorm_pack_a's kernel (block 0 begins with LN1 of X, which is never written), so a
+ * pre-LN block has the launch count of the post-LN block; the last boundary is qgemm_layernorm_rows with gamma_f,
+ * beta_f, or qgemm_add_rows.  Every new step is row-local, so every contract of the cached, batched, varlen and
+ * generate calls that rests on row-locality carries over.
+ *
+ * qgemm_prenorm_pack_a: the norm-first form of qgemm_layernorm_pack_a's kernel.  On rows x w floats, contiguous rows:
+ *   S[c] = v[c] = fl(A[c] + B[c])      one fp32 add; B == NULL: S[c] = A[c]; S == NULL: the store is skipped
+ *   packed_a    = the scale and q regions qgemm_layernorm_pack_a writes for the same A, B, gamma, beta, eps and range,
+ *                 byte for byte, padding rows and columns included: the pack of LN(v) by qgemm_layernorm_rows'
+ *                 contract (every arithmetic step and both sums' order); the normalised fp32 row is never stored.
+ * S may be A or B (the same rows): a wave reads its whole row before it writes, and A, B and S are not restrict-
+ * qualified inside the library; gamma and beta must not overlap S.  w <= 4096.  16-byte aligned base pointers (S
+ * included) with w % 4 == 0 stay in registers through float4 loads and stores, anything else goes float by float and
+ * gives the same bits.  One launch, no workspace, no allocation, no synchronization.
+ * hipErrorInvalidValue before any launch: a null A / gamma / beta / packed_a, w < 1 or > 4096, rows < 0; rows == 0
+ * returns 0.
+ * qgemm_add_rows: S = fl(A + B) alone, the same rows, paths and aliasing rules; a null A / B / S is refused. */
+#define QGEMM_ARCH_NORM_FIRST 0x100 /* with QGEMM_ARCH_STANDARD only */
+#define QGEMM_ARCH_FINAL_NORM 0x200 /* with QGEMM_ARCH_NORM_FIRST only */
+QGEMM_API int qgemm_prenorm_pack_a(const float *A, const float *B_or_null, const float *gamma, const float *beta, float eps,
+                         float *S_or_null, int64_t rows, int w, float range, void *packed_a, void *stream);
+QGEMM_API int qgemm_add_rows(const float *A, const float *B, float *S, int64_t rows, int w, void *stream);
 
 #ifdef __cplusplus
 }

@@ -142,6 +142,8 @@ EXPORTED_SYMBOLS = (
     "qgemm_gelu_pack_a",
     "qgemm_model_create",
     "qgemm_model_info",
+    "qgemm_prenorm_pack_a",
+    "qgemm_add_rows",
 )
 
 # Every symbol include/qgemm_dist.h declares (libqgemm_dist.so: M-shards + RCCL all-gather).
@@ -172,6 +174,7 @@ QGEMM_DECODE_MAX_BATCH = 64    # sequences per attention_decode_batched / step_b
 QGEMM_VARLEN_MAX_SEQS = 64     # sequences per attention_varlen / forward_batch / step_varlen call
 QGEMM_ARCH_REFERENCE, QGEMM_ARCH_STANDARD = 0, 1  # qgemm_model_create: the reference's block / the post-LN block
 QGEMM_ACT_RELU, QGEMM_ACT_GELU_TANH = 0, 1        # ... and the FFN's activation (GELU: standard only)
+QGEMM_ARCH_NORM_FIRST, QGEMM_ARCH_FINAL_NORM = 0x100, 0x200  # modifier bits on arch: the pre-LN block
 ARCHS = {"reference": QGEMM_ARCH_REFERENCE, "standard": QGEMM_ARCH_STANDARD}
 ACTIVATIONS = {"relu": QGEMM_ACT_RELU, "gelu_tanh": QGEMM_ACT_GELU_TANH}
 
@@ -437,6 +440,10 @@ def load() -> ctypes.CDLL:
         L.qgemm_model_create.restype = i32
         L.qgemm_model_info.argtypes = [vp, ctypes.POINTER(ModelDesc)]
         L.qgemm_model_info.restype = i32
+        L.qgemm_prenorm_pack_a.argtypes = [vp, vp, vp, vp, f32, vp, i64, i32, f32, vp, vp]
+        L.qgemm_prenorm_pack_a.restype = i32
+        L.qgemm_add_rows.argtypes = [vp, vp, vp, i64, i32, vp]
+        L.qgemm_add_rows.restype = i32
         _lib = L
         return L
 
@@ -1066,6 +1073,35 @@ def layernorm_pack_a(A, B, gamma, beta, eps: float = 1e-5, Y=None, range: float 
     return Y, Packed(buf, M, K, range)
 
 
+def prenorm_pack_a(A, B, gamma, beta, eps: float = 1e-5, S=None, range: float = DEFAULT_RANGE, out=None):  # noqa: A002
+    """The pre-LN boundary in one launch (qgemm_prenorm_pack_a): S = A + B, the updated residual stream
+    (B may be None: S = A; S=None: not stored; S may be A or B), and LN(A + B) written only packed.  Returns
+    (S, Packed), the Packed byte for byte layernorm_pack_a's for the same arguments."""
+    _ln_args(A, B, gamma, beta, A if S is None else S)
+    M, K = A.shape
+    buf = _packed_out(out, M, K, A.device)
+    _check("qgemm_prenorm_pack_a",
+           load().qgemm_prenorm_pack_a(A.data_ptr(), 0 if B is None else B.data_ptr(), gamma.data_ptr(),
+                                       beta.data_ptr(), float(eps), 0 if S is None else S.data_ptr(), M, K,
+                                       float(range), buf.data_ptr(), _stream(A.device)))
+    return S, Packed(buf, M, K, range)
+
+
+def add_rows(A, B, S=None):
+    """S = A + B on rows x w floats (qgemm_add_rows): the last boundary of a pre-LN model without a final norm.  S may
+    be A or B."""
+    import torch
+    for t, nm in ((A, "A"), (B, "B")):
+        _require_device_f32(t, nm)
+    assert A.dim() == 2 and A.is_contiguous() and B.shape == A.shape and B.is_contiguous(), "A, B: rows x w, contiguous"
+    S = torch.empty_like(A) if S is None else S
+    _require_device_f32(S, "S")
+    assert S.shape == A.shape and S.is_contiguous(), "S: as A"
+    _check("qgemm_add_rows", load().qgemm_add_rows(A.data_ptr(), B.data_ptr(), S.data_ptr(), A.shape[0], A.shape[1],
+                                                  _stream(A.device)))
+    return S
+
+
 def gelu_rows(X, Y=None):
     """The tanh-form GELU elementwise (qgemm_gelu_rows): X rows x w with unit inner stride, any row stride."""
     import torch
@@ -1160,7 +1196,9 @@ def encoder_weight_seed(base: int, block: int, kind: int, head: int) -> int:
 # decoder only.  A reference-arch model refuses them.
 (KIND_BQ, KIND_BK, KIND_BV, KIND_BO, KIND_G1, KIND_BE1, KIND_G3, KIND_BE3,
  KIND_BQ2, KIND_BK2, KIND_BV2, KIND_BO2, KIND_G2, KIND_BE2) = range(12, 26)
-_VECTOR_KINDS = (KIND_B1, KIND_B2) + tuple(range(KIND_BQ, KIND_BE2 + 1))
+# The final norm of a pre-LN model created with final_norm=True: block 0, head 0; refused elsewhere.
+KIND_GF, KIND_BEF = 26, 27
+_VECTOR_KINDS = (KIND_B1, KIND_B2) + tuple(range(KIND_BQ, KIND_BEF + 1))
 # packed_weight's `which`
 (WEIGHT_WQKV, WEIGHT_WO, WEIGHT_W1, WEIGHT_W2, WEIGHT_WQ2, WEIGHT_WKV2, WEIGHT_WO2) = range(7)
 
@@ -1174,13 +1212,18 @@ class _DeviceView:
 
 
 class _ArchKeywords(type):
-    """Encoder(..., arch=, activation=, ln_eps=) and the same on Decoder: keyword-only arguments of the class call,
-    set on the object before __init__ runs.  __init__ keeps its parameter list as it was (its last parameters stay
+    """Encoder(..., arch=, activation=, ln_eps=, norm_first=, final_norm=) and the same on Decoder: keyword-only
+    arguments of the class call, set on the object before __init__ runs.  norm_first (arch="standard" only): the pre-LN
+    block; final_norm (with norm_first only): a LayerNorm behind the last block.  __init__ keeps its parameter list as it was (its last parameters stay
     max_rows, and n_slots on a Decoder), so positional callers and tools that read that list see no change."""
 
-    def __call__(cls, *args, arch: str = "reference", activation: str = "relu", ln_eps: float = 1e-5, **kw):
+    def __call__(cls, *args, arch: str = "reference", activation: str = "relu", ln_eps: float = 1e-5,
+                 norm_first: bool = False, final_norm: bool = False, **kw):
+        assert not norm_first or arch != "reference", "norm_first needs arch='standard'"
+        assert norm_first or not final_norm, "final_norm needs norm_first=True"
         self = cls.__new__(cls)
         self.arch, self.activation, self.ln_eps = arch, activation, float(ln_eps)
+        self.norm_first, self.final_norm = bool(norm_first), bool(final_norm)
         self.__init__(*args, **kw)
         return self
 
@@ -1235,7 +1278,9 @@ class _ModelWeights(metaclass=_ArchKeywords):
         assert activation in ACTIVATIONS, f"activation: one of {sorted(ACTIVATIONS)}"
         desc = ModelDesc(ctypes.sizeof(ModelDesc), 1 if cross else 0, self.d_model, self.n_heads, self.d_ff,
                          self.n_blocks, self.max_seq, max_enc_seq, self.seed, flags, n_slots,
-                         0 if max_rows is None else int(max_rows), ARCHS[arch], ACTIVATIONS[activation], float(ln_eps))
+                         0 if max_rows is None else int(max_rows),
+                         ARCHS[arch] | (QGEMM_ARCH_NORM_FIRST if self.norm_first else 0) |
+                         (QGEMM_ARCH_FINAL_NORM if self.final_norm else 0), ACTIVATIONS[activation], float(ln_eps))
         h = ctypes.c_void_p()
         _check("qgemm_model_create", load().qgemm_model_create(ctypes.byref(desc), ctypes.byref(h)))
         return h
@@ -1248,11 +1293,12 @@ class _ModelWeights(metaclass=_ArchKeywords):
 
     def load_torch_layer(self, block: int, layer):
         """Load every tensor of `block` from a torch.nn.TransformerEncoderLayer (an Encoder) or TransformerDecoderLayer
-        (a Decoder) with norm_first=False: the set_weight calls for the q / k / v thirds of in_proj_weight head by head
+        (a Decoder) whose norm_first is the model's: the set_weight calls for the q / k / v thirds of in_proj_weight head by head
         (rows h d_k .. of a third are head h's [out, in] tensor), in_proj_bias, out_proj, linear1 / linear2 and the
         norms; a decoder layer's multihead_attn is the cross-attention and its norm2 LN2, an encoder layer's norm2 is
-        the FFN's LN (kinds KIND_G3 / KIND_BE3).  Tensors are copied to the current device as they are (fp32 or bf16,
-        anything else as fp32).  ValueError: norm_first=True, a width, head count or epsilon that is not the model's, a
+        the FFN's LN (kinds KIND_G3 / KIND_BE3) -- on a pre-LN layer the same norms stand in front of their sub-layers.
+        Tensors are copied to the current device as they are (fp32 or bf16,
+        anything else as fp32).  ValueError: a norm_first that is not the model's, a width, head count or epsilon that is not the model's, a
         layer of the other kind, or a reference-arch model.  The layer's activation is not looked at: create the model
         with the matching one."""
         import torch
@@ -1261,8 +1307,9 @@ class _ModelWeights(metaclass=_ArchKeywords):
         cross = hasattr(layer, "multihead_attn")
         if cross != isinstance(self, Decoder):
             raise ValueError("an Encoder takes a TransformerEncoderLayer, a Decoder a TransformerDecoderLayer")
-        if getattr(layer, "norm_first", False):
-            raise ValueError("norm_first=True (pre-LN) is not the standard architecture's block")
+        if bool(getattr(layer, "norm_first", False)) != getattr(self, "norm_first", False):
+            raise ValueError(f"the layer has norm_first={bool(getattr(layer, 'norm_first', False))}, the model "
+                             f"norm_first={getattr(self, 'norm_first', False)}")
         d, H, dk = self.d_model, self.n_heads, self.d_model // self.n_heads
         attns = [layer.self_attn] + ([layer.multihead_attn] if cross else [])
         for a in attns:
@@ -1307,6 +1354,21 @@ class _ModelWeights(metaclass=_ArchKeywords):
         self.set_weight(block, KIND_G3, dv(ffn_norm.weight))
         self.set_weight(block, KIND_BE3, dv(ffn_norm.bias))
 
+    def load_torch_final_norm(self, ln):
+        """Load the norm behind the last block (kinds KIND_GF / KIND_BEF) from an affine
+        torch.nn.LayerNorm(d_model, eps=ln_eps): the `norm` of a torch.nn.TransformerEncoder / TransformerDecoder.
+        ValueError: any other module, or a model created without final_norm=True."""
+        import torch
+        if not getattr(self, "final_norm", False):
+            raise ValueError("load_torch_final_norm needs a model created with final_norm=True")
+        if not isinstance(ln, torch.nn.LayerNorm) or tuple(ln.normalized_shape) != (self.d_model,) or \
+                ln.weight is None or ln.bias is None or abs(ln.eps - self.ln_eps) > 1e-12:
+            raise ValueError(f"the final norm must be an affine LayerNorm({self.d_model}, eps={self.ln_eps})")
+        dev = torch.device("cuda", torch.cuda.current_device())
+        for kind, t in ((KIND_GF, ln.weight), (KIND_BEF, ln.bias)):
+            t = t.detach()
+            self.set_weight(0, kind, t.to(dev) if t.dtype in (torch.float32, torch.bfloat16) else t.to(dev, torch.float32))
+
     def packed_weight(self, block: int, which: int) -> Packed:
         """Block's packed weight `which` (WEIGHT_WQKV ..) as a NON-OWNING Packed view of the model's own buffer, for
         tests and tools: read it, do not write it, and do not use it after close()."""
@@ -1335,7 +1397,9 @@ class Encoder(_ModelWeights):
     textbook post-LN block instead -- biases on every
     projection, block-input residuals, LayerNorm with gamma, beta and ln_eps, activation "relu" or "gelu_tanh" -- which
     load_torch_layer fills from a torch.nn.TransformerEncoderLayer; the defaults give the reference's block through the
-    older creators."""
+    older creators.  norm_first=True (with arch="standard"): the pre-LN block of norm_first=True layers, and
+    final_norm=True (with norm_first): a LayerNorm behind the last block, loaded by load_torch_final_norm (DESIGN.md
+    s26)."""
 
     def __init__(self, d_model: int, n_heads: int, d_ff: int, n_blocks: int, max_seq: int, seed: int = 0,
                  max_rows=None):

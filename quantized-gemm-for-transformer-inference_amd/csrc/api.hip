@@ -659,6 +659,17 @@ int qgemm_layernorm_pack_a(const float *A, const float *B_or_null, const float *
                                           packed_view(packed_a, (int)rows, w), static_cast<hipStream_t>(stream)));
 }
 
+int qgemm_prenorm_pack_a(const float *A, const float *B_or_null, const float *gamma, const float *beta, float eps,
+                         float *S_or_null, int64_t rows, int w, float range, void *packed_a, void *stream) {
+    if (!packed_a || rows < 0 || rows > INT32_MAX || w < 1 || w > 4096) return err(hipErrorInvalidValue);
+    return err(launch_prenorm_pack(A, B_or_null, gamma, beta, eps, S_or_null, rows, w, range,
+                                   packed_view(packed_a, (int)rows, w), static_cast<hipStream_t>(stream)));
+}
+
+int qgemm_add_rows(const float *A, const float *B, float *S, int64_t rows, int w, void *stream) {
+    return err(launch_add_rows(A, B, S, rows, w, static_cast<hipStream_t>(stream)));
+}
+
 int qgemm_gelu_rows(const float *X, int64_t x_stride_h, float *Y, int64_t y_stride_h, int64_t rows, int w,
                     void *stream) {
     return err(launch_gelu_rows(X, x_stride_h, Y, y_stride_h, rows, w, static_cast<hipStream_t>(stream)));
@@ -675,9 +686,8 @@ int qgemm_model_create(const qgemm_model_desc *desc, void **model) {
     *model = nullptr;
     if (!desc || desc->size != sizeof(qgemm_model_desc)) return err(hipErrorInvalidValue);
     const qgemm_model_desc &d = *desc;
-    if ((d.arch != QGEMM_ARCH_REFERENCE && d.arch != QGEMM_ARCH_STANDARD) ||
-        (d.activation != QGEMM_ACT_RELU && d.activation != QGEMM_ACT_GELU_TANH) ||
-        (d.arch == QGEMM_ARCH_REFERENCE && d.activation != QGEMM_ACT_RELU) || !(d.ln_eps >= 0.0f) ||
+    if (!stack_arch_ok(d.arch) || (d.activation != QGEMM_ACT_RELU && d.activation != QGEMM_ACT_GELU_TANH) ||
+        ((d.arch & 0xff) == QGEMM_ARCH_REFERENCE && d.activation != QGEMM_ACT_RELU) || !(d.ln_eps >= 0.0f) ||
         (d.cross != 0 && d.cross != 1) || d.n_slots < 0 || d.max_rows < 0)
         return err(hipErrorInvalidValue);
     const int n_slots = d.n_slots ? d.n_slots : 1;

@@ -19,6 +19,11 @@
 // kPack: the row is also quantized for the next linear with the operations of pack_rows (absmax_candidate,
 // absmax_finish, inv_divide, quant_i8): the packed bytes are those of packing Y afterwards; rows [rows, rows_pad) get
 // zero bytes and a zero scale, columns [w, k_pad) zero bytes (as add_layernorm_rows_vec_kernel<true, .>).
+// kForm: what the row's wave writes.  kFormPost, the post-LN block's: Y = LN(v).  kFormPre, the pre-LN
+// boundary's: S = v, the updated residual stream, stored BEFORE the mean is subtracted (S == nullptr: not stored), then
+// LN(v) exactly as above, written only as packed int8 + scale -- the normalised fp32 row is never stored.  kFormAdd: S
+// = v and nothing else, the last boundary of a pre-LN model without a final norm.  S takes Y's place in the argument
+// list and Y's rules: it may be A or B.
 #include "qgemm_internal.h"
 
 namespace qgemm {
@@ -60,7 +65,22 @@ __device__ __forceinline__ float4 load4(const float *row, int j, int w, float pa
     }
 }
 
-template <bool kPack, int kV, bool kVec>
+// v into elements c .. c + 3 of a row of w floats (c < w)
+template <bool kVec>
+__device__ __forceinline__ void store4(float *row, int c, int w, float4 v) {
+    if constexpr (kVec) {
+        *reinterpret_cast<float4 *>(row + c) = v;
+    } else {
+        row[c] = v.x;
+        if (c + 1 < w) row[c + 1] = v.y;
+        if (c + 2 < w) row[c + 2] = v.z;
+        if (c + 3 < w) row[c + 3] = v.w;
+    }
+}
+
+enum { kFormPost = 0, kFormPre = 1, kFormAdd = 2 };
+
+template <bool kPack, int kV, bool kVec, int kForm = kFormPost>
 __global__ __launch_bounds__(64 * kRowWaves) void layernorm_rows_kernel(const float *A, const float *B,
                                                                        const float *__restrict__ gamma,
                                                                        const float *__restrict__ beta, float eps,
@@ -75,8 +95,9 @@ __global__ __launch_bounds__(64 * kRowWaves) void layernorm_rows_kernel(const fl
         return;
     }
     if (row >= rows) return;
+    static_assert(kForm == kFormPost || kPack == (kForm == kFormPre), "pre-LN packs and only packs; the add packs nothing");
     const float *a = A + row * w, *b = B ? B + row * w : nullptr;
-    float *y = Y + row * w;
+    float *y = Y ? Y + row * w : nullptr;  // (nullptr: kFormPre without a stream to write)
     const int w4 = (w + 3) >> 2;  // float4 columns that hold an element
     // past the row: -0, the identity of the sums (x + -0 == x for every x, -0 and NaN included)
     float4 x[kV];
@@ -89,6 +110,14 @@ __global__ __launch_bounds__(64 * kRowWaves) void layernorm_rows_kernel(const fl
             x[i] = make_float4(__fadd_rn(x[i].x, bv.x), __fadd_rn(x[i].y, bv.y), __fadd_rn(x[i].z, bv.z),
                                __fadd_rn(x[i].w, bv.w));
         }
+    }
+    if constexpr (kForm != kFormPost) {  // the residual stream: every load of the row has been issued above
+        if (y) {
+#pragma unroll
+            for (int i = 0; i < kV; ++i)
+                if (lane + 64 * i < w4) store4<kVec>(y, 4 * (lane + 64 * i), w, x[i]);
+        }
+        if constexpr (kForm == kFormAdd) return;
     }
     const float fw = (float)w;
     const float mean = __fdiv_rn(lane_sum<kV>(x), fw);
@@ -116,14 +145,7 @@ __global__ __launch_bounds__(64 * kRowWaves) void layernorm_rows_kernel(const fl
             v.y = __fadd_rn(__fmul_rn(__fmul_rn(x[i].y, rstd), g.y), be.y);
             v.z = __fadd_rn(__fmul_rn(__fmul_rn(x[i].z, rstd), g.z), be.z);
             v.w = __fadd_rn(__fmul_rn(__fmul_rn(x[i].w, rstd), g.w), be.w);
-            if constexpr (kVec) {
-                *reinterpret_cast<float4 *>(y + c) = v;
-            } else {
-                y[c] = v.x;
-                if (c + 1 < w) y[c + 1] = v.y;
-                if (c + 2 < w) y[c + 2] = v.z;
-                if (c + 3 < w) y[c + 3] = v.w;
-            }
+            if constexpr (kForm == kFormPost) store4<kVec>(y, c, w, v);
             x[i] = v;
             if constexpr (kPack) {
                 if (c > 0) cand = fmaxf(cand, absmax_candidate(v.x));  // element 0 is the seed, no candidate
@@ -155,32 +177,32 @@ __global__ __launch_bounds__(64 * kRowWaves) void layernorm_rows_kernel(const fl
 
 bool al16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-template <bool kPack, bool kVec>
+template <bool kPack, bool kVec, int kForm>
 hipError_t launch_ln(const float *A, const float *B, const float *gamma, const float *beta, float eps, float *Y,
                      int64_t rows, int w, int8_t *q, float *qscale, int64_t k_pad, int64_t rows_pad, float range,
                      int64_t grid_rows, hipStream_t stream) {
     const unsigned grid = (unsigned)((grid_rows + kRowWaves - 1) / kRowWaves);
     if (w <= 1024)
-        layernorm_rows_kernel<kPack, 4, kVec><<<grid, 64 * kRowWaves, 0, stream>>>(A, B, gamma, beta, eps, Y, rows, w, q,
-                                                                                  qscale, k_pad, rows_pad, range);
+        layernorm_rows_kernel<kPack, 4, kVec, kForm>
+            <<<grid, 64 * kRowWaves, 0, stream>>>(A, B, gamma, beta, eps, Y, rows, w, q, qscale, k_pad, rows_pad, range);
     else if (w <= 2048)
-        layernorm_rows_kernel<kPack, 8, kVec><<<grid, 64 * kRowWaves, 0, stream>>>(A, B, gamma, beta, eps, Y, rows, w, q,
-                                                                                  qscale, k_pad, rows_pad, range);
+        layernorm_rows_kernel<kPack, 8, kVec, kForm>
+            <<<grid, 64 * kRowWaves, 0, stream>>>(A, B, gamma, beta, eps, Y, rows, w, q, qscale, k_pad, rows_pad, range);
     else
-        layernorm_rows_kernel<kPack, 16, kVec><<<grid, 64 * kRowWaves, 0, stream>>>(A, B, gamma, beta, eps, Y, rows, w,
-                                                                                   q, qscale, k_pad, rows_pad, range);
+        layernorm_rows_kernel<kPack, 16, kVec, kForm>
+            <<<grid, 64 * kRowWaves, 0, stream>>>(A, B, gamma, beta, eps, Y, rows, w, q, qscale, k_pad, rows_pad, range);
     return hipGetLastError();
 }
 
-template <bool kPack>
+template <bool kPack, int kForm = kFormPost>
 hipError_t launch_ln_any(const float *A, const float *B, const float *gamma, const float *beta, float eps, float *Y,
                          int64_t rows, int w, int8_t *q, float *qscale, int64_t k_pad, int64_t rows_pad, float range,
                          int64_t grid_rows, hipStream_t stream) {
     const bool vec = w % 4 == 0 && al16(A) && al16(B) && al16(gamma) && al16(beta) && al16(Y);
-    return vec ? launch_ln<kPack, true>(A, B, gamma, beta, eps, Y, rows, w, q, qscale, k_pad, rows_pad, range, grid_rows,
-                                        stream)
-               : launch_ln<kPack, false>(A, B, gamma, beta, eps, Y, rows, w, q, qscale, k_pad, rows_pad, range, grid_rows,
-                                         stream);
+    return vec ? launch_ln<kPack, true, kForm>(A, B, gamma, beta, eps, Y, rows, w, q, qscale, k_pad, rows_pad, range,
+                                               grid_rows, stream)
+               : launch_ln<kPack, false, kForm>(A, B, gamma, beta, eps, Y, rows, w, q, qscale, k_pad, rows_pad, range,
+                                                grid_rows, stream);
 }
 
 }  // namespace
@@ -199,6 +221,24 @@ hipError_t launch_layernorm_rows_pack(const float *A, const float *B, const floa
     if (!out.q || out.k_pad < w || out.rows_pad < rows) return hipErrorInvalidValue;
     return launch_ln_any<true>(A, B, gamma, beta, eps, Y, rows, w, out.q, out.scale, out.k_pad, out.rows_pad, range,
                                out.rows_pad, stream);
+}
+
+// the pre-LN boundary: S = A + B (S == nullptr: not stored), LN(S) written packed alone
+hipError_t launch_prenorm_pack(const float *A, const float *B, const float *gamma, const float *beta, float eps,
+                               float *S, int64_t rows, int w, float range, PackedView out, hipStream_t stream) {
+    if (!A || !gamma || !beta || w < 1 || w > kMaxRowLen || rows < 0) return hipErrorInvalidValue;
+    if (rows == 0) return hipSuccess;
+    if (!out.q || out.k_pad < w || out.rows_pad < rows) return hipErrorInvalidValue;
+    return launch_ln_any<true, kFormPre>(A, B, gamma, beta, eps, S, rows, w, out.q, out.scale, out.k_pad, out.rows_pad,
+                                         range, out.rows_pad, stream);
+}
+
+// S = A + B, the same rows and paths without a norm
+hipError_t launch_add_rows(const float *A, const float *B, float *S, int64_t rows, int w, hipStream_t stream) {
+    if (!A || !B || !S || w < 1 || w > kMaxRowLen || rows < 0) return hipErrorInvalidValue;
+    if (rows == 0) return hipSuccess;
+    return launch_ln_any<false, kFormAdd>(A, B, nullptr, nullptr, 0.0f, S, rows, w, nullptr, nullptr, 0, 0, 0.0f, rows,
+                                          stream);
 }
 
 }  // namespace qgemm

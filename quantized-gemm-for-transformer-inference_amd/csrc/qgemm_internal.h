@@ -582,13 +582,21 @@ hipError_t launch_layernorm_rows(const float *A, const float *B, const float *ga
                                  float *Y, int64_t rows, int w, hipStream_t stream);
 hipError_t launch_layernorm_rows_pack(const float *A, const float *B, const float *gamma, const float *beta, float eps,
                                       float *Y, int64_t rows, int w, float range, PackedView out, hipStream_t stream);
+// The pre-LN boundary (the contract is at qgemm_prenorm_pack_a in include/qgemm.h), the same kernel's
+// norm-first form: S = A + B (B may be nullptr: S = A; S may be nullptr: not stored; S may be A or B), LN(S) written
+// only packed.  launch_add_rows: S = A + B alone.
+hipError_t launch_prenorm_pack(const float *A, const float *B, const float *gamma, const float *beta, float eps,
+                               float *S, int64_t rows, int w, float range, PackedView out, hipStream_t stream);
+hipError_t launch_add_rows(const float *A, const float *B, float *S, int64_t rows, int w, hipStream_t stream);
 // gelu.hip: the tanh-form GELU elementwise (row strides in floats, unit inner stride), and fused into pack_rows of an
 // m x k matrix, k <= 16384: the packed view of the GELU'd matrix, which is never written
 hipError_t launch_gelu_rows(const float *X, int64_t xsh, float *Y, int64_t ysh, int64_t rows, int w, hipStream_t stream);
 hipError_t launch_gelu_pack(const float *X, int64_t xsh, int m, int k, float range, PackedView out, hipStream_t stream);
 // transformer.hip: the architecture of a stack (stack_create's arch: 0 the reference's block, 1 the standard one with
-// its new tensors allocated and set, b_* = +0, gamma = 1, beta = +0; activation: 0 relu, 1 tanh GELU, arch 1 only);
+// its new tensors allocated and set, b_* = +0, gamma = 1, beta = +0; activation: 0 relu, 1 tanh GELU, arch 1 only;
+// arch 0x101 the pre-LN block and 0x301 the pre-LN block with a final norm, QGEMM_ARCH_NORM_FIRST / _FINAL_NORM);
 // stack_describe reads back what creation was given.
+bool stack_arch_ok(int arch);
 struct StackDesc {
     int cross, d_model, n_heads, d_ff, n_blocks, max_seq, max_enc_seq;
     uint64_t seed;

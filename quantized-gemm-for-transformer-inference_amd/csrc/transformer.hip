@@ -87,6 +87,15 @@
 // Every new step is row-local, so arguments (1) and (2) above, and with them every contract of the cached, batched and
 // varlen calls, hold as they do for the reference block.  The cross caches carry b_k2 | b_v2.
 //
+// The pre-LN block (arch = STANDARD | NORM_FIRST [| FINAL_NORM]): the standard block's launches with the
+// norms moved in front of their sub-layers:   x += SelfAttn(LN1(x)) W_O + b_O, x += CrossAttn(LN2(x), enc) W_O2 + b_O2,
+// x += act(LN3(x) W1 + b1) W2 + b2, and behind the last block y = LNf(x) or y = x
+//   * every sub-layer boundary is ONE launch of norm.hip's norm-first form: stream += t, the next LN, its pack; the
+//     normalised rows exist only packed, the stream lives in S->x (the caller's X is read, never written);
+//   * block 0 begins with LN1 + pack of X in place of pack_rows(X); the last boundary is the post-LN kernel with gamma_f,
+//     beta_f (kinds 26, 27, the stack's own allocation) or launch_add_rows.
+// Row-local again, so the same arguments hold; enc_out enters the cross-attention as given.
+//
 // Caller-supplied weights (qgemm_model_set_weight).  The seeded draw stays what creation does; afterwards
 // stack_set_weight replaces one tensor at a time: launch_pack_b_window (weights.hip) packs it into its column window of
 // the block's packed weight, a bias is copied.  Every call above then runs on the current weights.
@@ -106,9 +115,23 @@ enum WeightKind { kWq = 0, kWk = 1, kWv = 2, kWo = 3, kW1 = 4, kB1 = 5, kW2 = 6,
                   kWq2 = 8, kWk2 = 9, kWv2 = 10, kWo2 = 11,
                   // the standard architecture's, 1 x d_model each; 20 .. 25 are the cross-attention's
                   kBq = 12, kBk = 13, kBv = 14, kBo = 15, kG1 = 16, kBe1 = 17, kG3 = 18, kBe3 = 19,
-                  kBq2 = 20, kBk2 = 21, kBv2 = 22, kBo2 = 23, kG2 = 24, kBe2 = 25 };
+                  kBq2 = 20, kBk2 = 21, kBv2 = 22, kBo2 = 23, kG2 = 24, kBe2 = 25,
+                  // the final norm of a pre-LN stack, 1 x d_model each, block 0's
+                  kGf = 26, kBef = 27 };
+
+// QGEMM_ARCH_NORM_FIRST / QGEMM_ARCH_FINAL_NORM (include/qgemm.h): modifier bits above the architecture's low byte
+constexpr int kArchNormFirst = 0x100, kArchFinalNorm = 0x200;
 
 }  // namespace
+
+// arch as qgemm_model_create takes it: the reference's block or the standard one in the low byte; above it NORM_FIRST
+// on the standard block alone and FINAL_NORM with NORM_FIRST alone, and no other bit
+bool stack_arch_ok(int arch) {
+    const int base = arch & 0xff, mods = arch & ~0xff;
+    if ((base != 0 && base != 1) || (mods & ~(kArchNormFirst | kArchFinalNorm))) return false;
+    if ((mods & kArchNormFirst) && base != 1) return false;
+    return !(mods & kArchFinalNorm) || (mods & kArchNormFirst);
+}
 
 // Seed of one weight tensor: every tensor its own counter stream (documented for the oracle).
 uint64_t encoder_weight_seed(uint64_t base, int block, int kind, int head) {
@@ -141,6 +164,11 @@ struct Stack {
     bool standard = false;  // the post-LN block with biases, block-input residuals and a real LayerNorm
     bool gelu = false;      // standard: the FFN's activation is the tanh-form GELU, fused into the pack in front of W2
     float ln_eps = 0.0f;    // standard: every LN's epsilon
+    // standard: the pre-LN block -- every sub-layer normalises its own input and adds its output to
+    // the un-normalised stream -- and whether LNf follows the last block; fn = [gamma_f][beta_f], final_norm only
+    bool norm_first = false, final_norm = false;
+    int arch = 0;           // as created, for stack_describe
+    float *fn = nullptr;
     uint64_t seed = 0;      // as created, for stack_describe
     int max_rows = 0;
     int scratch_rows = 0;   // rows the scratch buffers hold: max_seq, 8 rows of every slot or max_rows, the largest
@@ -230,7 +258,7 @@ void stack_destroy(Stack *S) {
             (void)hipFree(p);
     for (void *p : {(void *)S->qkv, (void *)S->scores, (void *)S->heads, (void *)S->t, (void *)S->ffn, (void *)S->x,
                     (void *)S->q2, (void *)S->kv2, (void *)S->heads2, (void *)S->xa, (void *)S->xb, (void *)S->ws,
-                    (void *)S->own})
+                    (void *)S->own, (void *)S->fn})
         (void)hipFree(p);
     delete S;
 }
@@ -239,7 +267,7 @@ hipError_t stack_create(int d_model, int n_heads, int d_ff, int n_blocks, int ma
                         bool cross, bool causal, bool kv_cache, Stack **out, int n_slots, int max_rows, int arch,
                         int activation, float ln_eps) {
     *out = nullptr;
-    if ((arch != 0 && arch != 1) || (activation != 0 && activation != 1) || (arch == 0 && activation != 0) ||
+    if (!stack_arch_ok(arch) || (activation != 0 && activation != 1) || ((arch & 0xff) == 0 && activation != 0) ||
         !(ln_eps >= 0.0f) || (activation == 1 && d_ff > 16384))  // (the GELU pack's row limit)
         return hipErrorInvalidValue;
     // max_rows: the row-local kernels (pack, GEMM epilogue, add + layernorm) address an activation buffer of
@@ -266,7 +294,10 @@ hipError_t stack_create(int d_model, int n_heads, int d_ff, int n_blocks, int ma
     S->causal = causal;
     S->kv_cache = kv_cache;
     S->n_slots = n_slots;
-    S->standard = arch == 1;
+    S->standard = (arch & 0xff) == 1;
+    S->norm_first = (arch & kArchNormFirst) != 0;
+    S->final_norm = (arch & kArchFinalNorm) != 0;
+    S->arch = arch;
     S->gelu = activation == 1;
     S->ln_eps = ln_eps;
     S->seed = seed;
@@ -362,6 +393,12 @@ hipError_t stack_create(int d_model, int n_heads, int d_ff, int n_blocks, int ma
             if ((e = hipMemcpy(B.sp, host.data(), sizeof(float) * host.size(), hipMemcpyHostToDevice))) break;
         }
     }
+    if (e == hipSuccess && S->final_norm) {  // gamma_f = 1, beta_f = +0
+        std::vector<float> host(2 * (size_t)d, 0.0f);
+        std::fill_n(host.begin(), d, 1.0f);
+        if (!(e = alloc_f(&S->fn, host.size())))
+            e = hipMemcpy(S->fn, host.data(), sizeof(float) * host.size(), hipMemcpyHostToDevice);
+    }
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     (void)hipFree(tmp);
     if (e != hipSuccess) return fail(e);
@@ -451,6 +488,23 @@ hipError_t run_blocks(Stack *S, const float *X, float *Y, int rows, int enc_seq,
     bool in_packed = false;  // the previous block's last add+layernorm packed its output already
     hipError_t e;
     float *mho = S->cross ? S->heads2 : S->heads;  // the multiHeadOut that the FFN's residual adds: the last attention's
+    // pre-LN: `res` is the residual stream -- the caller's X, never written, until the first add stores
+    // S->x, then S->x in place -- and every sub-layer boundary ONE launch: stream += t, the next sub-layer's LN of the
+    // new stream, its pack.  The normalised rows exist only packed: the QKV, Wq2 and W1 GEMMs read them from act_view.
+    const float *res = X;
+    auto pre_boundary = [&](const float *g, const float *be) {
+        const hipError_t err = launch_prenorm_pack(res, S->t, g, be, S->ln_eps, S->x, seq, d, 127.0f,
+                                                   act_view(*S, seq, d), s);
+        res = S->x;
+        return err;
+    };
+    if (S->norm_first) {  // LN1 of block 0 on X as it is: no add, nothing to store
+        const Block &B0 = S->blocks[0];
+        if ((e = launch_prenorm_pack(X, nullptr, B0.g1, B0.be1, S->ln_eps, nullptr, seq, d, 127.0f, act_view(*S, seq, d),
+                                     s)))
+            return e;
+        in_packed = true;
+    }
     for (int i = 0; i < S->n_blocks; ++i) {
         const Block &B = S->blocks[i];
         const bool last = i == S->n_blocks - 1;
@@ -497,11 +551,13 @@ hipError_t run_blocks(Stack *S, const float *X, float *Y, int rows, int enc_seq,
         // output = multiHeadOut @ W_O; x1 = LN(output + multiHeadOut), packed by the same launch: the next linear
         // quantizes nothing itself
         // standard: x1 = LN1(in + heads W_O + b_O), the residual the block's input
+        // pre-LN: stream += heads W_O + b_O, then the LN in front of the next sub-layer (LN2, or LN3 in an encoder)
         if ((e = linear(*S, S->heads, seq, d, B.wo, d, S->t, B.bo, false, s))) return e;
-        if ((e = S->standard ? launch_layernorm_rows_pack(S->t, in, B.g1, B.be1, S->ln_eps, S->x, seq, d, 127.0f,
-                                                          act_view(*S, seq, d), s)
-                             : launch_add_layernorm_rows_pack(S->t, S->heads, S->x, seq, d, 127.0f,
-                                                              act_view(*S, seq, d), s)))
+        if ((e = S->norm_first ? pre_boundary(S->cross ? B.g2 : B.g3, S->cross ? B.be2 : B.be3)
+                 : S->standard ? launch_layernorm_rows_pack(S->t, in, B.g1, B.be1, S->ln_eps, S->x, seq, d, 127.0f,
+                                                            act_view(*S, seq, d), s)
+                               : launch_add_layernorm_rows_pack(S->t, S->heads, S->x, seq, d, 127.0f,
+                                                                act_view(*S, seq, d), s)))
             return e;
         if (S->cross) {
             // ---- cross-attention: queries from x1, keys and values from enc_out
@@ -523,11 +579,13 @@ hipError_t run_blocks(Stack *S, const float *X, float *Y, int rows, int enc_seq,
                                              kNoMask, S->scores, s)))
                 return e;
             if ((e = linear(*S, mho, seq, d, B.wo2, d, S->t, B.bo2, false, s))) return e;
-            // x2 = LN(t + heads2), packed for the FFN's first linear; standard: x2 = LN2(x1 + t), in place over x1
-            if ((e = S->standard ? launch_layernorm_rows_pack(S->t, S->x, B.g2, B.be2, S->ln_eps, S->x, seq, d, 127.0f,
-                                                              act_view(*S, seq, d), s)
-                                 : launch_add_layernorm_rows_pack(S->t, mho, S->x, seq, d, 127.0f,
-                                                                  act_view(*S, seq, d), s)))
+            // x2 = LN(t + heads2), packed for the FFN's first linear; standard: x2 = LN2(x1 + t), in place over x1;
+            // pre-LN: stream += t, then LN3
+            if ((e = S->norm_first ? pre_boundary(B.g3, B.be3)
+                     : S->standard ? launch_layernorm_rows_pack(S->t, S->x, B.g2, B.be2, S->ln_eps, S->x, seq, d, 127.0f,
+                                                                act_view(*S, seq, d), s)
+                                   : launch_add_layernorm_rows_pack(S->t, mho, S->x, seq, d, 127.0f,
+                                                                    act_view(*S, seq, d), s)))
                 return e;
         }
         if (S->standard) {
@@ -540,6 +598,15 @@ hipError_t run_blocks(Stack *S, const float *X, float *Y, int rows, int enc_seq,
                 if ((e = gemm(*S, va, seq, S->d_ff, B.w2, d, S->t, B.b2, false, s))) return e;
             } else if ((e = linear(*S, S->ffn, seq, S->d_ff, B.w2, d, S->t, B.b2, false, s))) {
                 return e;
+            }
+            if (S->norm_first) {
+                // stream += t, then the next block's LN1 and its pack; behind the last block Y = LNf(stream + t), the
+                // post-LN kernel as it is, or Y = stream + t
+                e = !last           ? pre_boundary(S->blocks[i + 1].g1, S->blocks[i + 1].be1)
+                    : S->final_norm ? launch_layernorm_rows(res, S->t, S->fn, S->fn + d, S->ln_eps, Y, seq, d, s)
+                                    : launch_add_rows(res, S->t, Y, seq, d, s);
+                if (e) return e;
+                continue;  // (in_packed stays true)
             }
             e = last ? launch_layernorm_rows(S->t, S->x, B.g3, B.be3, S->ln_eps, out, seq, d, s)
                      : launch_layernorm_rows_pack(S->t, S->x, B.g3, B.be3, S->ln_eps, out, seq, d, 127.0f,
@@ -923,6 +990,7 @@ struct WeightPlace {
 };
 
 bool weight_kind_ok(const Stack *S, int kind) {
+    if (kind >= kGf) return S->final_norm && kind <= kBef;  // the final norm of a pre-LN stack that has one
     if (kind >= kBq) return S->standard && kind <= (S->cross ? kBe2 : kBe3);  // a reference stack lacks them
     return kind >= kWq && kind <= (S->cross ? kWo2 : kB2);
 }
@@ -941,6 +1009,7 @@ bool weight_place(const Stack *S, const Block &B, int kind, int head, WeightPlac
         case kWq2: *p = {B.wq2, nullptr, d, d, head * dk, dk}; break;
         case kWk2: case kWv2: *p = {B.wkv2, nullptr, d, 2 * d, (kind - kWk2) * d + head * dk, dk}; break;
         case kWo2: *p = {B.wo2, nullptr, d, d, 0, d}; break;
+        case kGf: case kBef: *p = {nullptr, S->fn + (size_t)(kind - kGf) * d, 1, d, 0, d}; break;  // the stack's own
         // the standard architecture's vectors, 1 x d_model each: B.sp holds them in the order of their kinds
         default: *p = {nullptr, B.sp + (size_t)(kind - kBq) * d, 1, d, 0, d}; break;
     }
@@ -968,7 +1037,7 @@ hipError_t stack_set_weight(Stack *S, int block, int kind, int head, const void 
                             hipStream_t s) {
     WeightPlace p;
     if (!S || block < 0 || block >= S->n_blocks || !W || (dtype != 0 && dtype != 1) || sh < 0 || sw < 0 ||
-        !weight_place(S, S->blocks[block], kind, head, &p))
+        (kind >= kGf && block != 0) || !weight_place(S, S->blocks[block], kind, head, &p))
         return hipErrorInvalidValue;
     const hipError_t e = p.bias ? launch_copy_row(W, dtype, sw, p.ncols, p.bias, s)
                                 : launch_pack_b_window(W, dtype, sh, sw, p.k, p.n_total, p.col0, p.ncols, 127.0f,
@@ -999,10 +1068,12 @@ hipError_t stack_packed_weight(const Stack *S, int block, int which, const void 
     return hipSuccess;
 }
 
-// ... and a bias (kind 5 or 7) or a vector of the standard architecture (kinds 12 ..), n floats on the device
+// ... and a bias (kind 5 or 7) or a vector of the standard architecture (kinds 12 ..; the final norm's 26, 27 are
+// block 0's), n floats on the device
 hipError_t stack_bias(const Stack *S, int block, int kind, const float **bias, int *n) {
     WeightPlace p;
-    if (!S || block < 0 || block >= S->n_blocks || !bias || !weight_place(S, S->blocks[block], kind, 0, &p) || !p.bias)
+    if (!S || block < 0 || block >= S->n_blocks || !bias || (kind >= kGf && block != 0) ||
+        !weight_place(S, S->blocks[block], kind, 0, &p) || !p.bias)
         return hipErrorInvalidValue;
     *bias = p.bias;
     if (n) *n = p.ncols;
@@ -1013,7 +1084,7 @@ hipError_t stack_describe(const Stack *S, StackDesc *out) {
     if (!S || !out) return hipErrorInvalidValue;
     // (QGEMM_DECODER_CAUSAL = 1, QGEMM_DECODER_KV_CACHE = 8, include/qgemm.h)
     *out = StackDesc{S->cross, S->d_model, S->n_heads, S->d_ff, S->n_blocks, S->max_seq, S->max_enc_seq, S->seed,
-                     (S->causal ? 1 : 0) | (S->kv_cache ? 8 : 0), S->n_slots, S->max_rows, S->standard ? 1 : 0,
+                     (S->causal ? 1 : 0) | (S->kv_cache ? 8 : 0), S->n_slots, S->max_rows, S->arch,
                      S->gelu ? 1 : 0, S->ln_eps};
     return hipSuccess;
 }
