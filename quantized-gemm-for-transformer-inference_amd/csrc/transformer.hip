@@ -1,20 +1,43 @@
 // transformer.hip -- the counterparts of the reference's Encoder (transformer.cu:14-77; SURVEY.md s8f f1, BASELINE
 // config 5) and Decoder (transformer.cu:79-168) with their GEMM call sites on the int8 quantized path: ONE stack of
-// blocks, an encoder without and a decoder with the cross-attention third (DESIGN.md "Encoder", "Decoder").  Per block:
-//   1. self-attention on the block input            transformer.cu:37-59 / :93-126
-//      [Q | K | V] = quantized_mm(in, [Wq | Wk | Wv])   attention.cuh:54-56 -- ONE GEMM over all heads (per-column
-//                                                       absmax makes this bit-identical to per-head GEMMs)
-//      heads = attention(Q, K, V)                       attention.cuh:58-69 -- fp32 (activation x activation): bit-exact
-//                                                       op_mm<float> (sequential-k fmaf), batched over heads
-//      t = quantized_mm(heads, W_O), x1 = LN(t + heads) transformer.cu:52-59
-//   2. cross-attention (decoder)                    transformer.cu:128-150
-//      Q2 = quantized_mm(x1, Wq2), [K2 | V2] = quantized_mm(enc_out, [Wk2 | Wv2]),
-//      heads2 = attention(Q2, K2, V2) with seq queries and enc_seq keys, t = quantized_mm(heads2, W_O2),
-//      x2 = LN(t + heads2)
-//   3. FFN                                          transformer.cu:62-75 / :152-167, linear.cuh:50-54
-//      out = LN(relu(x W1 + b1) W2 + b2 + multiHeadOut), bias and relu fused into the GEMMs; multiHeadOut is the last
-//      attention's: heads2 in a decoder, heads in an encoder
-// Softmax and add + layernorm: encoder_ops.hip.  The attention launches: attention_launch.hip.
+// blocks, an encoder without and a decoder with the cross-attention third (DESIGN.md "Encoder", "Decoder").  One
+// function, run_blocks, makes every pass over the blocks; what kind of pass it is and which architecture the blocks
+// have are each decided in one place.  Softmax and add + layernorm: encoder_ops.hip.  LayerNorm with gamma and beta
+// and the norm-first form: norm.hip.  The GELU pack: gelu.hip.  The attention launches: attention_launch.hip.
+//
+// THE BLOCK, once and in order (run_blocks).  Every linear is pack_rows + the int8 GEMM with bias (and relu) in its
+// epilogue; a boundary packs its own output, so the linear behind it quantizes nothing itself.
+//   [Q | K | V] = in @ [Wq | Wk | Wv]    attention.cuh:54-56 -- ONE GEMM over all heads (per-column absmax makes this
+//                                        bit-identical to per-head GEMMs); where it writes: qkv_rows
+//   heads = attention(Q, K, V)           attention.cuh:58-69 -- fp32 (activation x activation): bit-exact op_mm<float>
+//                                        (sequential-k fmaf), batched over heads: self_attention
+//   t = heads @ W_O                      transformer.cu:52-59
+//   boundary after W_O
+//   decoder:  Q2 = x @ Wq2, [K2 | V2] = enc_out @ [Wk2 | Wv2], heads2 = attention(Q2, K2, V2) with the rows as queries
+//             and enc_seq keys, unmasked: cross_attention; t = heads2 @ W_O2          transformer.cu:128-150
+//             boundary after W_O2
+//   t = act(x W1 + b1) W2 + b2           transformer.cu:62-75 / :152-167, linear.cuh:50-54.  relu in W1's epilogue; with
+//                                        GELU W1 runs without relu and the pack in front of W2 is gelu.hip's fused one
+//   boundary after W2
+//
+// THE BOUNDARIES.  The architecture (qgemm_model_create's arch) is what stands between the
+// sub-layers, ONE launch each; every other launch above is the same for all three.
+//                    reference                       post-LN (STANDARD)                pre-LN (STANDARD | NORM_FIRST)
+//   after W_O        x = LN(t + heads), packed       x = LN1(in + t), packed           stream += t; LN2 (encoder: LN3), packed
+//   after W_O2       x = LN(t + heads2), packed      x = LN2(x + t), in place, packed  stream += t; LN3, packed
+//   after W2         out = LN(t + mho), packed       out = LN3(x + t), packed          stream += t; next block's LN1, packed
+//   after W2, last   Y = LN(t + mho)                 Y = LN3(x + t)                    Y = LNf(stream + t), or stream + t
+//   reference: the LN without gamma and beta, the residual the last attention's multiHeadOut as in the reference (:58,
+//     :74) -- mho = heads2 in a decoder, heads in an encoder; no projection has a bias (nullptr: the reference's call);
+//   post-LN: the textbook block, x1 = LN1(x + heads W_O + b_O), x2 = LN2(x1 + heads2 W_O2 + b_O2), y = LN3(x2 + FFN(x2)).
+//     The projections' biases ride in the GEMM epilogue ([b_q | b_k | b_v] beside [Wq | Wk | Wv], ..): no launch; the
+//     cross caches carry b_k2 | b_v2;
+//   pre-LN: x += SelfAttn(LN1(x)) W_O + b_O, x += CrossAttn(LN2(x), enc) W_O2 + b_O2, x += act(LN3(x) W1 + b1) W2 + b2
+//     and y = LNf(x) [FINAL_NORM] or y = x.  Every boundary is norm.hip's norm-first form: stream += t, the NEXT
+//     sub-layer's LN, its pack; the normalised rows exist only packed, the stream lives in S->x (the caller's X is read,
+//     never written).  Block 0 begins with LN1 + pack of X in place of pack_rows(X) (run_blocks' prologue); the last
+//     boundary is the post-LN kernel with gamma_f, beta_f (kinds 26, 27, the stack's own allocation) or
+//     launch_add_rows.  enc_out enters the cross-attention as given.
 //
 // Decisions where the reference cannot run as written:
 //   * arity (transformer.cu:37 calls forward(X, X, out); attention.cuh:47 takes (X, out)): self attention on the block
@@ -29,72 +52,57 @@
 //   * enc_out is quantized ONCE per forward and its packed form serves every block's [K2 | V2] projection: its
 //     per-row absmax scales do not depend on the weight, so this is bit-identical to quantizing it per block.
 //
-// Incremental decoding (QGEMM_DECODER_KV_CACHE with QGEMM_DECODER_CAUSAL).  Every block owns a
-// self-attention cache -- its own [Q | K | V] buffer of max_seq x 3 d_model, so the QKV GEMM of a step writes rows
-// pos .. straight into it -- and a cross cache [K2 | V2] of max_enc_seq x 2 d_model.
-//   decoder_begin  packs enc_out once, runs every block's [K2 | V2] projection into its cross cache, records enc_seq
-//                  and sets the filled length to 0;
-//   decoder_step   forward's steps and helpers on the n rows at positions pos .. pos + n - 1: the QKV projection into
-//                  cache rows pos .., the masked attention of those n query rows against cache rows 0 .. pos + n - 1
-//                  (q_pos0 = pos), W_O, add + layernorm, Wq2, the unmasked attention on the cross cache, W_O2, add +
-//                  layernorm, the FFN.  No [K2 | V2] GEMM and no enc_out pack.
-// The result is rows pos .. pos + n - 1 of the causal forward on the whole prefix, bit for bit.  The argument: (1)
-// every step but the attention is row-local -- the pack's scales are per row, the int8 GEMM accumulates exactly and
-// dequantizes per element, add + layernorm works on one row -- so a cache row holds what forward computes for that
-// row, whichever call wrote it; (2) the masked attention has the prefix property: row i reads K rows below its limit
-// alone, and the V rows past it enter as fmaf(+0, v, acc), which changes nothing WHILE THE CACHED V IS FINITE and no
-// P V accumulator is -0 (the conditions of forward(X[:n]) == forward(X)[:n] itself; a step's key
-// sequence ends at its own last row, so there is no V row past the last limit at all).  A non-finite V
-// row written by an earlier, longer sequence is never read either: rows pos + n .. are outside the call's seq_kv.
-// pos is a host argument; the decoder keeps a host-side filled length, updated at enqueue time: 0 <= pos <= filled,
-// then filled = pos + n (an earlier pos rewinds: speculative decoding, beam search).  begin and step allocate nothing
-// and do not synchronize; they share the stack's scratch buffers with forward, so a stack does one thing at a time.
-// forward on a cached decoder neither reads nor writes the caches.
-//
-// Cache slots and batched steps (qgemm_decoder_create_slots).  The caches hold n_slots sequences: every
-// block's self cache is n_slots slabs of max_seq x 3 d_model, its cross cache n_slots slabs of max_enc_seq x 2 d_model,
-// and enc_seq / filled are kept per slot; the weights exist once.  decoder_begin_slot / decoder_step_slot are begin /
-// step with the cache pointers offset to the slot's slabs (slot 0: the calls above, unchanged).
-//   decoder_step_batch  one step of n_seqs different slots, r = 1 .. 8 rows each, M = n_seqs * r rows through the
-//                       same chain: the QKV GEMM of all rows into the stack's qkv scratch, scatter_kv_kernel copies
-//                       each row's [K | V] into row pos[b] + i of its slot's slab, the batched decode launch
-//                       (attention_decode.hip) reads Q from the scratch and K / V from the slabs with seq_kv[b] =
-//                       pos[b] + r and q_pos0[b] = pos[b]; W_O, add + layernorm, Wq2; the batched launch again,
-//                       unmasked, on the cross slabs with seq_kv[b] = the slot's enc_seq; W_O2, the FFN.
-// Row b * r + i of its output is, bit for bit, row i of decoder_step_slot(slots[b], pos[b], r) alone: by argument (1)
-// every step but the attention gives a row the same bits whatever other rows share the launch (M = n_seqs * r or
-// M = r), and the batched attention launch runs, per (head, row, sequence), the single launch's workgroup on the same
-// operands -- the K / V rows of the slab are the same values whether a GEMM or the scatter stored them.
-// The scratch buffers, the packed activations and the split-K scratch hold max(max_seq, 8 * n_slots) rows with more
-// than one slot.  decoder_copy_slot forks a sequence with stream-ordered device-to-device copies of the rows in use.
-//
-// Many sequences of different lengths at once (qgemm_*_create_rows).  By argument (1) the rows of B
-// sequences can run through one pass of the blocks as ONE matrix; the attention alone must know where a sequence ends,
-// and launch_attention_varlen (attention_launch.hip) does: one launch of the fused kernel over a table of sequences
-// where every one has at most 512 keys, else sequence by sequence.
-//   encoder_forward_batch  forward on sequences packed one after another: keys and queries in the qkv scratch;
-//   decoder_step_varlen    step_batch with n_rows[b] >= 1 rows per sequence (a prefill of many slots, or prefills mixed
-//                          with decoding rows): the scatter takes per-sequence row counts, keys in the slabs.
-// Each sequence's rows are forward's / step_slot's on it alone, bit for bit.  The scratch buffers hold
-// max(the above, max_rows) rows; the scores stay sized by max_seq (the per-sequence path runs one sequence at a time).
-//
-// The standard architecture (qgemm_model_create with QGEMM_ARCH_STANDARD): the textbook post-LN block
-// as a second architecture of the same stack.  run_blocks keeps its launches and their order and changes what some of
-// them are:   x1 = LN1(x + heads W_O + b_O), x2 = LN2(x1 + heads2 W_O2 + b_O2), y = LN3(x2 + act(x2 W1 + b1) W2 + b2)
-//   * the projections' biases ride in the GEMM epilogue ([b_q | b_k | b_v] beside [Wq | Wk | Wv], ..): no launch;
-//   * the three add + layernorm launches are norm.hip's (gamma, beta, eps; the residual is the sub-layer's input);
-//   * with GELU, W1 runs without relu and the pack_rows in front of W2 is gelu.hip's fused pack.
-// Every new step is row-local, so arguments (1) and (2) above, and with them every contract of the cached, batched and
-// varlen calls, hold as they do for the reference block.  The cross caches carry b_k2 | b_v2.
-//
-// The pre-LN block (arch = STANDARD | NORM_FIRST [| FINAL_NORM]): the standard block's launches with the
-// norms moved in front of their sub-layers:   x += SelfAttn(LN1(x)) W_O + b_O, x += CrossAttn(LN2(x), enc) W_O2 + b_O2,
-// x += act(LN3(x) W1 + b1) W2 + b2, and behind the last block y = LNf(x) or y = x
-//   * every sub-layer boundary is ONE launch of norm.hip's norm-first form: stream += t, the next LN, its pack; the
-//     normalised rows exist only packed, the stream lives in S->x (the caller's X is read, never written);
-//   * block 0 begins with LN1 + pack of X in place of pack_rows(X); the last boundary is the post-LN kernel with gamma_f,
-//     beta_f (kinds 26, 27, the stack's own allocation) or launch_add_rows.
-// Row-local again, so the same arguments hold; enc_out enters the cross-attention as given.
+// PASS KINDS.  The entry point says in a Pass which of five kinds its call is; qkv_rows, self_attention and
+// cross_attention alone read the kind.  Caches (QGEMM_DECODER_KV_CACHE with QGEMM_DECODER_CAUSAL):
+// every block owns n_slots self slabs of max_seq x 3 d_model ([Q | K | V] rows) and n_slots cross slabs of max_enc_seq
+// x 2 d_model ([K2 | V2]); enc_seq and the filled length are kept per slot on the host; the weights exist once.
+// decoder_begin_slot packs enc_out once, runs every block's [K2 | V2] projection into the slot's cross slab, records
+// enc_seq and sets filled to 0: no step runs a [K2 | V2] GEMM or an enc_out pack.
+//   Forward        encoder_forward, decoder_forward: the rows are a whole sequence.  [Q | K | V] and [K2 | V2] live in
+//                  the stack's scratch, [K2 | V2] is projected from the packed enc_out; the mask is the stack's causal
+//                  flag.  On a cached decoder it neither reads nor writes the caches.
+//   Slot           decoder_step_slot (qgemm_decoder_step: slot 0): n rows at positions pos .. pos + n - 1.  The QKV GEMM
+//                  writes cache rows pos .. of the slot's slab itself; those n query rows attend, masked with q_pos0 =
+//                  pos, to cache rows 0 .. pos + n - 1; the cross-attention reads the slot's cross slab.
+//   Batch          decoder_step_batch: r = 1 .. 8 rows of each of n_seqs different slots, M = n_seqs * r rows.  The QKV
+//                  GEMM of all rows into the qkv scratch, scatter_kv_kernel copies each row's [K | V] into row pos[b] + i
+//                  of its slot's slab, the batched decode launch (attention_decode.hip) reads Q from the scratch and K / V
+//                  from the slabs with seq_kv[b] = pos[b] + r and q_pos0[b] = pos[b]; the batched launch again, unmasked,
+//                  on the cross slabs with seq_kv[b] = the slot's enc_seq.
+//   BatchIndirect  decoder_step_batch_indirect (the copy-free beam search): Batch, the self-attention
+//                  reading row j of a sequence from slab own[slot][j] of the stack's row table, the cross-attention the
+//                  slab of cross_slots[b].
+//   Varlen         n_seqs sequences of their own lengths packed one after another (qgemm_*_create_rows);
+//                  both attentions go through launch_attention_varlen (attention_launch.hip): one launch of the fused
+//                  kernel over a table of sequences where every one has at most 512 keys, else sequence by sequence.
+//                  encoder_forward_batch: keys and queries in the qkv scratch.  decoder_step_varlen: Batch with n_rows[b]
+//                  >= 1 rows per sequence (a prefill of many slots, or prefills mixed with decoding rows): the scatter
+//                  takes per-sequence row counts, keys in the slabs.
+// Why every kind gives the same bits:
+//   (1) row-locality.  Every step but the attention is row-local -- the pack's scales are per row, the int8 GEMM
+//       accumulates exactly and dequantizes per element, every boundary of every architecture and the GELU pack work on
+//       one row -- so a row gets the same bits whatever other rows share the launch, and a cache row holds what forward
+//       computes for that row, whichever call wrote it;
+//   (2) the prefix property.  The masked attention's row i reads K rows below its limit alone, and the V rows past it
+//       enter as fmaf(+0, v, acc), which changes nothing WHILE THE CACHED V IS FINITE and no P V accumulator is -0
+//       (the conditions of forward(X[:n]) == forward(X)[:n] itself; a step's key sequence ends at its
+//       own last row, so there is no V row past the last limit at all).  A non-finite V row written by an earlier,
+//       longer sequence is never read either: rows pos + n .. are outside the call's seq_kv.
+//   Slot: by (1) and (2) the result is rows pos .. pos + n - 1 of the causal forward on the whole prefix, bit for bit.
+//   Batch: row b * r + i is, bit for bit, row i of decoder_step_slot(slots[b], pos[b], r) alone: by (1) every step but
+//     the attention gives a row the same bits with M = n_seqs * r or M = r, and the batched attention launch runs, per
+//     (head, row, sequence), the single launch's workgroup on the same operands -- the K / V rows of the slab are the
+//     same values whether a GEMM or the scatter stored them.
+//   BatchIndirect: the same workgroup again, its K / V rows the same values read from the slabs the table names.
+//   Varlen: by (1) the rows of B sequences run through the blocks as ONE matrix; the attention alone must know where a
+//     sequence ends.  Each sequence's rows are forward's / step_slot's on it alone, bit for bit.
+// pos is a host argument; the filled length is updated at enqueue time: 0 <= pos <= filled, then filled = pos + n (an
+// earlier pos rewinds: speculative decoding, beam search).  The step entry points share one admission check per slot
+// (admit), and every check comes before the first launch.  begin and the steps allocate nothing and do not
+// synchronize; they share the stack's scratch buffers with forward, so a stack does one thing at a time.  The scratch
+// buffers, the packed activations and the split-K scratch hold max(max_seq, 8 * n_slots with more than one slot,
+// max_rows) rows; the scores stay sized by max_seq (the per-sequence varlen path runs one sequence at a time).
+// decoder_copy_slot forks a sequence with stream-ordered device-to-device copies of the rows in use.
 //
 // Caller-supplied weights (qgemm_model_set_weight).  The seeded draw stays what creation does; afterwards
 // stack_set_weight replaces one tensor at a time: launch_pack_b_window (weights.hip) packs it into its column window of
@@ -447,183 +455,210 @@ hipError_t launch_scatter_kv(const float *qkv, int64_t scratch_rows, float *cach
     return hipGetLastError();
 }
 
-// A batched step's sequences (decoder_step_batch): the tables of its two attention launches
-struct BatchStep {
-    int n_seqs, rows_per_seq;
-    bool indirect;           // the self-attention reads through the row table (decoder_step_batch_indirect)
-    DecodeBatchTable self;   // kv_slot = the slot (indirect: its table row), seq_kv = pos + rows_per_seq, q_pos0 = pos
-    DecodeBatchTable cross;  // kv_slot = the slot (indirect: cross_slots[b]), seq_kv = that slot's enc_seq, no mask
-    ScatterTable scatter;    // slot, pos, row0 = b * rows_per_seq, n_rows = rows_per_seq
-};
+// ---- one pass over the blocks ----------------------------------------------------------------------------------------
+// Which pass this is (the header's "Pass kinds") and the tables that kind reads.  The entry point builds it, after its
+// checks, by aggregate initialisation, and the block loop only reads it.  What the entry point does not name is zero,
+// and must be: the launchers check whole table entries, and e.g. a cross table's q_pos0 is never set.
+//   Forward        the rows are ONE whole sequence; [Q | K | V] and [K2 | V2] live in the stack's scratch
+//   Slot           the rows sit at positions pos .. of ONE cache slot
+//   Batch          rows_per_seq rows of each of n_seqs slots
+//   BatchIndirect  Batch, the self-attention reading through the row table
+//   Varlen         n_seqs sequences of their own row counts, packed one after another
+enum class PassKind { Forward, Slot, Batch, BatchIndirect, Varlen };
 
-// The sequences of a batched forward (encoder_forward_batch) or a varlen step (decoder_step_varlen), DESIGN.md s19:
-// sequence b's rows are row0[b] .. row0[b] + n_rows[b] - 1 of every row buffer (prefix sums: packed one after another).
-// Forward: its keys are its own rows of the [Q | K | V] scratch (self_kv_row0 = row0, self_seq_kv = n_rows, no mask in
-// an encoder).  Step: its keys are rows 0 .. pos + n - 1 of its slot's slab (self_kv_row0 = slot * max_seq, self_pos0 =
-// pos), the cross keys the slot's cross slab (cross_kv_row0 = slot * max_enc_seq, cross_seq_kv = its enc_seq).
-struct VarlenStep {
-    int n_seqs;
+struct Pass {
+    PassKind kind;
+    int rows;                  // rows of X and Y, all sequences together
+    int n_seqs, rows_per_seq;  // (rows_per_seq: 0 in a Varlen pass)
+    int enc_seq;               // Forward (decoder), Slot: the cross-attention's keys
+    int slot, pos;             // Slot
+    // Batch, BatchIndirect -- self: kv_slot = the slot (indirect: its table row), seq_kv = pos + rows_per_seq, q_pos0 =
+    // pos; cross: kv_slot = the slot (indirect: cross_slots[b]), seq_kv = that slot's enc_seq, no mask
+    DecodeBatchTable self, cross;
+    ScatterTable scatter;      // the kinds whose new [K | V] go from the scratch into the slabs: slot, pos, row0, n_rows
+    // Varlen: sequence b's rows are row0[b] .. row0[b] + n_rows[b] - 1 of every row buffer (prefix sums).
+    // A batched forward: its keys are its own rows of the [Q | K | V] scratch (self_kv_row0 = row0, self_seq_kv =
+    // n_rows, self_pos0 = 0).  A step (kv_in_slabs): its keys are rows 0 .. pos + n - 1 of its slot's slab (self_kv_row0
+    // = slot * max_seq, self_pos0 = pos), the cross keys the slot's cross slab (cross_kv_row0 = slot * max_enc_seq,
+    // cross_seq_kv = its enc_seq)
+    bool kv_in_slabs;
     int64_t row0[kVarlenMaxSeqs], self_kv_row0[kVarlenMaxSeqs], cross_kv_row0[kVarlenMaxSeqs];
     int n_rows[kVarlenMaxSeqs], self_seq_kv[kVarlenMaxSeqs], self_pos0[kVarlenMaxSeqs], cross_seq_kv[kVarlenMaxSeqs];
-    ScatterTable scatter;  // a step's: slot, pos, row0, n_rows
 };
 
-// One pass over the blocks on `rows` rows, for forward (cached = false: the rows are the whole sequence, [Q | K | V]
-// and [K2 | V2] live in the stack's scratch buffers, [K2 | V2] is projected here from the packed enc_out), for a
-// step of one slot (cached = true: the rows sit at positions pos .., [Q | K | V] rows pos .. are written into the
-// block's cache slab `slot` and attend to its rows 0 .. pos + rows - 1, [K2 | V2] is the slot's cross cache) and for
-// a step of many (batch != nullptr, with cached: rows = n_seqs * rows_per_seq, [Q | K | V] of all rows into the
-// scratch, their [K | V] scattered into the slots' slabs, both attentions one batched launch over the slabs).
-// var != nullptr (without batch): the rows are those of var->n_seqs sequences of their own lengths, one after another;
-// every row-local step runs on all of them at once and both attentions go through launch_attention_varlen -- a
-// batched forward (cached = false: keys in the scratch) or a varlen step (cached = true: [K | V] scattered into the
-// slabs as in a batched step, keys in the slabs).
-hipError_t run_blocks(Stack *S, const float *X, float *Y, int rows, int enc_seq, bool cached, int slot, int pos,
-                      const BatchStep *batch, hipStream_t s, const VarlenStep *var = nullptr) {
-    const int d = S->d_model, H = S->n_heads, dk = d / H;
-    const int seq = rows;
-    const int64_t self_slab = (int64_t)S->max_seq * 3 * d, cross_slab = (int64_t)S->max_enc_seq * 2 * d;  // floats
-    const float scale = (float)(1.0 / std::sqrt((double)dk));  // attention.cuh:64
-    const float *in = X;
-    bool in_packed = false;  // the previous block's last add+layernorm packed its output already
+// 1 / sqrt(d_k), attention.cuh:64
+float attention_scale(const Stack &S) { return (float)(1.0 / std::sqrt((double)(S.d_model / S.n_heads))); }
+
+// Where the QKV GEMM writes the pass's rows: a single-slot step projects straight into cache rows pos .. of the slot's
+// slab, every other kind into the [Q | K | V] scratch
+float *qkv_rows(const Stack &S, const Block &B, const Pass &p) {
+    return p.kind == PassKind::Slot ? B.qkv_cache + ((int64_t)p.slot * S.max_seq + p.pos) * 3 * S.d_model : S.qkv;
+}
+
+// sequence b's rows see its slot's cache rows 0 .. pos[b] + n - 1, the last n of them copied here from the scratch
+hipError_t scatter_new_kv(Stack &S, const Block &B, const Pass &p, hipStream_t s) {
+    return launch_scatter_kv(S.qkv, S.scratch_rows, B.qkv_cache, S.max_seq, S.n_slots, S.d_model, p.n_seqs, p.scatter, s);
+}
+
+// S_h = Q_h K_h^T, P_h = softmax(S_h * 1/sqrt(d_k)), heads[:, h*d_v..] = P_h V_h, Q, K and V the thirds of the rows that
+// the QKV GEMM wrote (causal: row i sees rows 0 .. i, so row i of the forward depends on rows 0 .. i of X alone)
+hipError_t self_attention(Stack &S, const Block &B, const Pass &p, hipStream_t s) {
+    const int d = S.d_model, H = S.n_heads, dk = d / H;
+    const int64_t slab = (int64_t)S.max_seq * 3 * d;  // floats
+    const float scale = attention_scale(S);
+    const float *cache = B.qkv_cache;  // [Q | K | V] rows of slab 0 (the step kinds)
+    switch (p.kind) {
+        case PassKind::Forward:
+            return launch_attention(S.qkv, 3 * d, S.qkv + d, 3 * d, S.qkv + 2 * d, 3 * d, S.heads, d, p.rows, p.rows, H, dk,
+                                    scale, S.causal ? 0 : kNoMask, S.scores, s);
+        case PassKind::Slot:  // the rows at pos .. against the slot's rows 0 .. pos + rows - 1
+            cache += p.slot * slab;
+            return launch_attention(qkv_rows(S, B, p), 3 * d, cache + d, 3 * d, cache + 2 * d, 3 * d, S.heads, d, p.rows,
+                                    p.pos + p.rows, H, dk, scale, p.pos, S.scores, s);
+        case PassKind::Batch:
+            if (const hipError_t e = scatter_new_kv(S, B, p, s)) return e;
+            return launch_attention_decode_batched(S.qkv, 3 * d, cache + d, 3 * d, slab, cache + 2 * d, 3 * d, slab, S.heads,
+                                                   d, p.n_seqs, p.rows_per_seq, p.self, /*causal=*/true, H, dk, scale, s);
+        case PassKind::BatchIndirect:  // row j of the sequence is row j of slab own[slot][j], the new rows its own slab's
+            if (const hipError_t e = scatter_new_kv(S, B, p, s)) return e;
+            return launch_attention_decode_indirect(S.qkv, 3 * d, cache + d, 3 * d, slab, cache + 2 * d, 3 * d, slab, S.heads,
+                                                    d, p.n_seqs, p.rows_per_seq, S.own, S.max_seq, S.n_slots, p.self,
+                                                    /*causal=*/true, H, dk, scale, s);
+        case PassKind::Varlen:  // a step's keys are in the slabs, a forward's its own rows of the scratch
+            if (!p.kv_in_slabs) cache = S.qkv;
+            else if (const hipError_t e = scatter_new_kv(S, B, p, s)) return e;
+            return launch_attention_varlen(S.qkv, 3 * d, cache + d, 3 * d, cache + 2 * d, 3 * d, S.heads, d, p.n_seqs, p.row0,
+                                           p.n_rows, p.self_kv_row0, p.self_seq_kv,
+                                           p.kv_in_slabs || S.causal ? p.self_pos0 : nullptr, H, dk, scale, S.scores, s);
+    }
+    return hipErrorInvalidValue;
+}
+
+// heads2 = attention(Q2, K2, V2), unmasked: the queries in S.q2, [K2 | V2] projected here from the packed enc_out for a
+// forward, the slots' cross slabs (filled by begin) for every step
+hipError_t cross_attention(Stack &S, const Block &B, const Pass &p, hipStream_t s) {
+    const int d = S.d_model, H = S.n_heads, dk = d / H;
+    const int64_t slab = (int64_t)S.max_enc_seq * 2 * d;  // floats
+    const float scale = attention_scale(S);
+    const float *kv2 = B.kv2_cache;  // slab 0 (the step kinds)
+    switch (p.kind) {
+        case PassKind::Forward:
+            if (const hipError_t e = gemm(S, enc_view(S, p.enc_seq), p.enc_seq, d, B.wkv2, 2 * d, S.kv2, B.bkv2, false, s))
+                return e;
+            return launch_attention(S.q2, d, S.kv2, 2 * d, S.kv2 + d, 2 * d, S.heads2, d, p.rows, p.enc_seq, H, dk, scale,
+                                    kNoMask, S.scores, s);
+        case PassKind::Slot:
+            kv2 += p.slot * slab;
+            return launch_attention(S.q2, d, kv2, 2 * d, kv2 + d, 2 * d, S.heads2, d, p.rows, p.enc_seq, H, dk, scale,
+                                    kNoMask, S.scores, s);
+        case PassKind::Batch:
+        case PassKind::BatchIndirect:
+            return launch_attention_decode_batched(S.q2, d, kv2, 2 * d, slab, kv2 + d, 2 * d, slab, S.heads2, d, p.n_seqs,
+                                                   p.rows_per_seq, p.cross, /*causal=*/false, H, dk, scale, s);
+        case PassKind::Varlen:
+            return launch_attention_varlen(S.q2, d, kv2, 2 * d, kv2 + d, 2 * d, S.heads2, d, p.n_seqs, p.row0, p.n_rows,
+                                           p.cross_kv_row0, p.cross_seq_kv, nullptr, H, dk, scale, S.scores, s);
+    }
+    return hipErrorInvalidValue;
+}
+
+// ---- the sub-layer boundaries: the residual, the LayerNorm and the pack in front of the next linear, ONE launch each,
+// per architecture (the header's table).  t = S.t is the sub-layer's output, what W_O, W_O2 or W2 just wrote
+enum Boundary { kAfterWo, kAfterWo2, kAfterW2 };
+
+// What the block loop carries: the fp32 rows the next QKV linear reads (a post-LN block's LN1 adds them too), or that
+// they are packed in act_view already.  res is the pre-LN boundary's own: the residual stream -- the caller's X, never
+// written, until the first boundary stores S.x, then S.x in place
+struct Carry { const float *in; bool packed; const float *res; };
+
+// where a reference or post-LN block's last boundary writes, and what that makes of the carry: Y unpacked behind the
+// last block, else xa / xb in turn, packed for the next block
+float *block_out(Stack &S, int i, float *Y, Carry &c) {
+    c.packed = i != S.n_blocks - 1;
+    float *out = c.packed ? (i % 2 ? S.xb : S.xa) : Y;
+    c.in = out;
+    return out;
+}
+
+// the reference block: x = LN(t + multiHeadOut), multiHeadOut the last attention's -- heads2 in a decoder, also behind W2
+hipError_t boundary_reference(Stack &S, int i, Boundary where, int rows, Carry &c, float *Y, hipStream_t s) {
+    const int d = S.d_model;
+    const float *mho = where == kAfterWo || !S.cross ? S.heads : S.heads2;
+    if (where != kAfterW2) return launch_add_layernorm_rows_pack(S.t, mho, S.x, rows, d, 127.0f, act_view(S, rows, d), s);
+    float *out = block_out(S, i, Y, c);
+    return c.packed ? launch_add_layernorm_rows_pack(S.t, mho, out, rows, d, 127.0f, act_view(S, rows, d), s)
+                    : launch_add_layernorm_rows(S.t, mho, out, rows, d, s);
+}
+
+// post-LN: x1 = LN1(in + t), x2 = LN2(x1 + t) in place over x1, y = LN3(x + t) with x the FFN's own input
+hipError_t boundary_post_ln(Stack &S, int i, Boundary where, int rows, Carry &c, float *Y, hipStream_t s) {
+    const int d = S.d_model;
+    const Block &B = S.blocks[i];
+    const PackedView va = act_view(S, rows, d);
+    if (where == kAfterWo) return launch_layernorm_rows_pack(S.t, c.in, B.g1, B.be1, S.ln_eps, S.x, rows, d, 127.0f, va, s);
+    if (where == kAfterWo2) return launch_layernorm_rows_pack(S.t, S.x, B.g2, B.be2, S.ln_eps, S.x, rows, d, 127.0f, va, s);
+    float *out = block_out(S, i, Y, c);
+    return c.packed ? launch_layernorm_rows_pack(S.t, S.x, B.g3, B.be3, S.ln_eps, out, rows, d, 127.0f, va, s)
+                    : launch_layernorm_rows(S.t, S.x, B.g3, B.be3, S.ln_eps, out, rows, d, s);
+}
+
+// pre-LN: stream += t, the LN in front of the NEXT sub-layer -- LN2, LN3 (after W_O too in an encoder),
+// the next block's LN1 -- and its pack.  The normalised rows exist only packed: the QKV, Wq2 and W1 GEMMs read them from
+// act_view.  Behind the last block Y = LNf(stream + t), the post-LN kernel as it is, or Y = stream + t
+hipError_t boundary_pre_ln(Stack &S, int i, Boundary where, int rows, Carry &c, float *Y, hipStream_t s) {
+    const int d = S.d_model;
+    const float *res = c.res;
+    if (where == kAfterW2 && i == S.n_blocks - 1)
+        return S.final_norm ? launch_layernorm_rows(res, S.t, S.fn, S.fn + d, S.ln_eps, Y, rows, d, s)
+                            : launch_add_rows(res, S.t, Y, rows, d, s);
+    const Block &B = S.blocks[where == kAfterW2 ? i + 1 : i];
+    const bool ln2 = where == kAfterWo && S.cross;
+    const float *g = where == kAfterW2 ? B.g1 : ln2 ? B.g2 : B.g3, *be = where == kAfterW2 ? B.be1 : ln2 ? B.be2 : B.be3;
+    c.res = S.x;
+    return launch_prenorm_pack(res, S.t, g, be, S.ln_eps, S.x, rows, d, 127.0f, act_view(S, rows, d), s);
+}
+
+// One pass over the blocks on the p.rows rows of X into Y: the block of the header, once and in order.  The pass kind is
+// the attention helpers' and qkv_rows' business, the architecture the boundaries'; every other launch is row-local and
+// the same for all of them.  (B.bqkv and every other standard-only pointer is nullptr on a reference stack: the
+// reference's GEMM call)
+hipError_t run_blocks(Stack *S, const Pass &p, const float *X, float *Y, hipStream_t s) {
+    const int d = S->d_model, rows = p.rows;
+    const auto boundary = S->norm_first ? boundary_pre_ln : S->standard ? boundary_post_ln : boundary_reference;
+    Carry c = {X, false, X};
     hipError_t e;
-    float *mho = S->cross ? S->heads2 : S->heads;  // the multiHeadOut that the FFN's residual adds: the last attention's
-    // pre-LN: `res` is the residual stream -- the caller's X, never written, until the first add stores
-    // S->x, then S->x in place -- and every sub-layer boundary ONE launch: stream += t, the next sub-layer's LN of the
-    // new stream, its pack.  The normalised rows exist only packed: the QKV, Wq2 and W1 GEMMs read them from act_view.
-    const float *res = X;
-    auto pre_boundary = [&](const float *g, const float *be) {
-        const hipError_t err = launch_prenorm_pack(res, S->t, g, be, S->ln_eps, S->x, seq, d, 127.0f,
-                                                   act_view(*S, seq, d), s);
-        res = S->x;
-        return err;
-    };
     if (S->norm_first) {  // LN1 of block 0 on X as it is: no add, nothing to store
-        const Block &B0 = S->blocks[0];
-        if ((e = launch_prenorm_pack(X, nullptr, B0.g1, B0.be1, S->ln_eps, nullptr, seq, d, 127.0f, act_view(*S, seq, d),
-                                     s)))
+        if ((e = launch_prenorm_pack(X, nullptr, S->blocks[0].g1, S->blocks[0].be1, S->ln_eps, nullptr, rows, d, 127.0f,
+                                     act_view(*S, rows, d), s)))
             return e;
-        in_packed = true;
+        c.packed = true;
     }
     for (int i = 0; i < S->n_blocks; ++i) {
         const Block &B = S->blocks[i];
-        const bool last = i == S->n_blocks - 1;
-        float *out = last ? Y : (i % 2 ? S->xb : S->xa);
-        // ---- self-attention on the block input: [Q | K | V] = in @ [Wq | Wk | Wv] over all heads
-        const bool to_cache = cached && !batch && !var;                         // the GEMM writes the cache rows itself
-        float *qkv = to_cache ? B.qkv_cache + slot * self_slab : S->qkv;        // row 0 of [Q | K | V]
-        float *qrows = qkv + (size_t)(to_cache ? pos : 0) * 3 * d;              // the rows this call projects
-        // (B.bqkv and every other standard-only pointer is nullptr on a reference stack: the reference's call)
-        if ((e = linear(*S, in_packed ? nullptr : in, seq, d, B.wqkv, 3 * d, qrows, B.bqkv, false, s))) return e;
-        // S_h = Q_h K_h^T, P_h = softmax(S_h * 1/sqrt(d_k)), heads[:, h*d_v..] = P_h V_h, Q, K and V the thirds of qkv
-        // (causal: row i sees rows 0 .. i, so row i of the forward depends on rows 0 .. i of X alone)
-        if (batch) {
-            // sequence b's rows see its slot's cache rows 0 .. pos[b] + r - 1, the last r of them scattered here
-            if ((e = launch_scatter_kv(qkv, S->scratch_rows, B.qkv_cache, S->max_seq, S->n_slots, d, batch->n_seqs,
-                                       batch->scatter, s)))
-                return e;
-            // (indirect: row j of the sequence is row j of slab own[slot][j], the new rows its own slab's)
-            e = batch->indirect
-                    ? launch_attention_decode_indirect(qkv, 3 * d, B.qkv_cache + d, 3 * d, self_slab, B.qkv_cache + 2 * d,
-                                                       3 * d, self_slab, S->heads, d, batch->n_seqs, batch->rows_per_seq,
-                                                       S->own, S->max_seq, S->n_slots, batch->self, /*causal=*/true, H,
-                                                       dk, scale, s)
-                    : launch_attention_decode_batched(qkv, 3 * d, B.qkv_cache + d, 3 * d, self_slab, B.qkv_cache + 2 * d,
-                                                      3 * d, self_slab, S->heads, d, batch->n_seqs, batch->rows_per_seq,
-                                                      batch->self, /*causal=*/true, H, dk, scale, s);
-            if (e) return e;
-        } else if (var) {
-            // a step's sequences see their slots' cache rows, the new ones scattered here; a forward's their own rows
-            // of the scratch
-            if (cached && (e = launch_scatter_kv(qkv, S->scratch_rows, B.qkv_cache, S->max_seq, S->n_slots, d,
-                                                 var->n_seqs, var->scatter, s)))
-                return e;
-            const float *kv = cached ? B.qkv_cache : qkv;
-            if ((e = launch_attention_varlen(qkv, 3 * d, kv + d, 3 * d, kv + 2 * d, 3 * d, S->heads, d, var->n_seqs,
-                                             var->row0, var->n_rows, var->self_kv_row0, var->self_seq_kv,
-                                             cached || S->causal ? var->self_pos0 : nullptr, H, dk, scale, S->scores,
-                                             s)))
-                return e;
-        } else if ((e = launch_attention(qrows, 3 * d, qkv + d, 3 * d, qkv + 2 * d, 3 * d, S->heads, d, seq,
-                                         cached ? pos + seq : seq, H, dk, scale,
-                                         cached ? pos : (S->causal ? 0 : kNoMask), S->scores, s)))
+        // ---- self-attention on the block input: [Q | K | V] = in @ [Wq | Wk | Wv] over all heads, t = heads @ W_O
+        if ((e = linear(*S, c.packed ? nullptr : c.in, rows, d, B.wqkv, 3 * d, qkv_rows(*S, B, p), B.bqkv, false, s)))
             return e;
-        // output = multiHeadOut @ W_O; x1 = LN(output + multiHeadOut), packed by the same launch: the next linear
-        // quantizes nothing itself
-        // standard: x1 = LN1(in + heads W_O + b_O), the residual the block's input
-        // pre-LN: stream += heads W_O + b_O, then the LN in front of the next sub-layer (LN2, or LN3 in an encoder)
-        if ((e = linear(*S, S->heads, seq, d, B.wo, d, S->t, B.bo, false, s))) return e;
-        if ((e = S->norm_first ? pre_boundary(S->cross ? B.g2 : B.g3, S->cross ? B.be2 : B.be3)
-                 : S->standard ? launch_layernorm_rows_pack(S->t, in, B.g1, B.be1, S->ln_eps, S->x, seq, d, 127.0f,
-                                                            act_view(*S, seq, d), s)
-                               : launch_add_layernorm_rows_pack(S->t, S->heads, S->x, seq, d, 127.0f,
-                                                                act_view(*S, seq, d), s)))
-            return e;
+        if ((e = self_attention(*S, B, p, s))) return e;
+        if ((e = linear(*S, S->heads, rows, d, B.wo, d, S->t, B.bo, false, s))) return e;
+        if ((e = boundary(*S, i, kAfterWo, rows, c, Y, s))) return e;
         if (S->cross) {
-            // ---- cross-attention: queries from x1, keys and values from enc_out
-            if ((e = linear(*S, nullptr, seq, d, B.wq2, d, S->q2, B.bq2, false, s))) return e;
-            float *kv2 = cached ? B.kv2_cache + slot * cross_slab : S->kv2;
-            if (!cached && (e = gemm(*S, enc_view(*S, enc_seq), enc_seq, d, B.wkv2, 2 * d, kv2, B.bkv2, false, s)))
-                return e;
-            if (batch) {
-                if ((e = launch_attention_decode_batched(S->q2, d, B.kv2_cache, 2 * d, cross_slab, B.kv2_cache + d, 2 * d,
-                                                         cross_slab, mho, d, batch->n_seqs, batch->rows_per_seq,
-                                                         batch->cross, /*causal=*/false, H, dk, scale, s)))
-                    return e;
-            } else if (var) {
-                if ((e = launch_attention_varlen(S->q2, d, B.kv2_cache, 2 * d, B.kv2_cache + d, 2 * d, mho, d, var->n_seqs,
-                                                 var->row0, var->n_rows, var->cross_kv_row0, var->cross_seq_kv, nullptr,
-                                                 H, dk, scale, S->scores, s)))
-                    return e;
-            } else if ((e = launch_attention(S->q2, d, kv2, 2 * d, kv2 + d, 2 * d, mho, d, seq, enc_seq, H, dk, scale,
-                                             kNoMask, S->scores, s)))
-                return e;
-            if ((e = linear(*S, mho, seq, d, B.wo2, d, S->t, B.bo2, false, s))) return e;
-            // x2 = LN(t + heads2), packed for the FFN's first linear; standard: x2 = LN2(x1 + t), in place over x1;
-            // pre-LN: stream += t, then LN3
-            if ((e = S->norm_first ? pre_boundary(B.g3, B.be3)
-                     : S->standard ? launch_layernorm_rows_pack(S->t, S->x, B.g2, B.be2, S->ln_eps, S->x, seq, d, 127.0f,
-                                                                act_view(*S, seq, d), s)
-                                   : launch_add_layernorm_rows_pack(S->t, mho, S->x, seq, d, 127.0f,
-                                                                    act_view(*S, seq, d), s)))
-                return e;
+            // ---- cross-attention: queries from the boundary's packed rows, keys and values from enc_out
+            if ((e = linear(*S, nullptr, rows, d, B.wq2, d, S->q2, B.bq2, false, s))) return e;
+            if ((e = cross_attention(*S, B, p, s))) return e;
+            if ((e = linear(*S, S->heads2, rows, d, B.wo2, d, S->t, B.bo2, false, s))) return e;
+            if ((e = boundary(*S, i, kAfterWo2, rows, c, Y, s))) return e;
         }
-        if (S->standard) {
-            // ---- FFN: y = LN3(x + act(x W1 + b1) W2 + b2), x = S->x the FFN's own input.  GELU: W1 without relu, and
-            // the pack in front of W2 applies GELU as it quantizes -- the launch count is the relu path's
-            if ((e = linear(*S, nullptr, seq, d, B.w1, S->d_ff, S->ffn, B.b1, !S->gelu, s))) return e;
-            if (S->gelu) {
-                const PackedView va = act_view(*S, seq, S->d_ff);
-                if ((e = launch_gelu_pack(S->ffn, S->d_ff, seq, S->d_ff, 127.0f, va, s))) return e;
-                if ((e = gemm(*S, va, seq, S->d_ff, B.w2, d, S->t, B.b2, false, s))) return e;
-            } else if ((e = linear(*S, S->ffn, seq, S->d_ff, B.w2, d, S->t, B.b2, false, s))) {
-                return e;
-            }
-            if (S->norm_first) {
-                // stream += t, then the next block's LN1 and its pack; behind the last block Y = LNf(stream + t), the
-                // post-LN kernel as it is, or Y = stream + t
-                e = !last           ? pre_boundary(S->blocks[i + 1].g1, S->blocks[i + 1].be1)
-                    : S->final_norm ? launch_layernorm_rows(res, S->t, S->fn, S->fn + d, S->ln_eps, Y, seq, d, s)
-                                    : launch_add_rows(res, S->t, Y, seq, d, s);
-                if (e) return e;
-                continue;  // (in_packed stays true)
-            }
-            e = last ? launch_layernorm_rows(S->t, S->x, B.g3, B.be3, S->ln_eps, out, seq, d, s)
-                     : launch_layernorm_rows_pack(S->t, S->x, B.g3, B.be3, S->ln_eps, out, seq, d, 127.0f,
-                                                  act_view(*S, seq, d), s);
-            if (e) return e;
-            in = out;
-            in_packed = !last;
-            continue;
+        // ---- FFN: t = act(x W1 + b1) W2 + b2, bias and relu fused into the GEMMs.  GELU: W1 without relu, and the pack
+        // in front of W2 applies GELU as it quantizes -- the launch count is the relu path's
+        if ((e = linear(*S, nullptr, rows, d, B.w1, S->d_ff, S->ffn, B.b1, !S->gelu, s))) return e;
+        if (S->gelu) {
+            const PackedView va = act_view(*S, rows, S->d_ff);
+            if ((e = launch_gelu_pack(S->ffn, S->d_ff, rows, S->d_ff, 127.0f, va, s))) return e;
+            if ((e = gemm(*S, va, rows, S->d_ff, B.w2, d, S->t, B.b2, false, s))) return e;
+        } else if ((e = linear(*S, S->ffn, rows, S->d_ff, B.w2, d, S->t, B.b2, false, s))) {
+            return e;
         }
-        // ---- FFN: relu(x W1 + b1) W2 + b2; LN(ffn + multiHeadOut)
-        if ((e = linear(*S, nullptr, seq, d, B.w1, S->d_ff, S->ffn, B.b1, true, s))) return e;
-        if ((e = linear(*S, S->ffn, seq, S->d_ff, B.w2, d, S->t, B.b2, false, s))) return e;
-        e = last ? launch_add_layernorm_rows(S->t, mho, out, seq, d, s)
-                 : launch_add_layernorm_rows_pack(S->t, mho, out, seq, d, 127.0f, act_view(*S, seq, d), s);
-        if (e) return e;
-        in = out;
-        in_packed = !last;
+        if ((e = boundary(*S, i, kAfterW2, rows, c, Y, s))) return e;
     }
     return hipSuccess;
 }
@@ -633,28 +668,50 @@ hipError_t pack_enc(Stack *S, const float *enc_out, int enc_seq, hipStream_t s) 
     return launch_pack_rows(enc_out, S->d_model, 1, enc_seq, S->d_model, 127.0f, enc_view(*S, enc_seq), s);
 }
 
+// ---- what the step entry points share --------------------------------------------------------------------------------
+// May slot sl take n rows at pos in this step?  In range, begun, its slab its own sequence's or (indirect) a beam's as
+// the call needs it, not named before in this call (seen, a bit per slot: n_slots <= 64), 0 <= pos <= filled, and room
+// for the rows.  Every entry point runs it for all its sequences before its first launch
+bool admit(const Stack *S, int sl, bool indirect, uint64_t &seen, int pos, int n) {
+    if (sl < 0 || sl >= S->n_slots || S->enc_seq[sl] < 1 || (S->indirect[sl] != 0) != indirect || (seen >> sl & 1) ||
+        n < 1 || pos < 0 || pos > S->filled[sl] || n > S->max_seq - pos)
+        return false;
+    seen |= (uint64_t)1 << sl;
+    return true;
+}
+
+// sequence b's n new [K | V] rows: from rows row0 .. of the scratch to rows pos .. of slab sl
+void scatter_entry(ScatterTable &t, int b, int sl, int pos, int row0, int n) {
+    t.slot[b] = sl, t.pos[b] = pos, t.row0[b] = row0, t.n_rows[b] = n;
+}
+
+// the filled lengths behind an enqueued step: every sequence's pos + its rows (an earlier pos rewinds)
+void set_filled(Stack *S, int n_seqs, const ScatterTable &t) {
+    for (int b = 0; b < n_seqs; ++b) S->filled[t.slot[b]] = t.pos[b] + t.n_rows[b];
+}
+
 }  // namespace
 
 hipError_t encoder_forward(Stack *S, const float *X, float *Y, int seq, hipStream_t s) {
     if (!S || S->cross || !X || !Y || seq < 1 || seq > S->max_seq) return hipErrorInvalidValue;
-    return run_blocks(S, X, Y, seq, 0, /*cached=*/false, 0, 0, nullptr, s);
+    return run_blocks(S, Pass{PassKind::Forward, seq, 1, seq}, X, Y, s);
 }
 
 // X and Y: the sequences' rows packed one after another.  Every row-local step of run_blocks sees one matrix of
 // sum seq_lens rows; the self-attention alone knows where a sequence ends
 hipError_t encoder_forward_batch(Stack *S, const float *X, float *Y, int n_seqs, const int *seq_lens, hipStream_t s) {
     if (!S || S->cross || !X || !Y || !seq_lens || n_seqs < 1 || n_seqs > kVarlenMaxSeqs) return hipErrorInvalidValue;
-    VarlenStep vs = {};
-    vs.n_seqs = n_seqs;
+    Pass p = {PassKind::Varlen, 0, n_seqs};  // (kv_in_slabs = false: a sequence's keys are its own rows of the scratch)
     int64_t rows = 0;
     for (int b = 0; b < n_seqs; ++b) {
         if (seq_lens[b] < 1 || seq_lens[b] > S->max_seq) return hipErrorInvalidValue;
-        vs.row0[b] = vs.self_kv_row0[b] = rows;
-        vs.n_rows[b] = vs.self_seq_kv[b] = seq_lens[b];
+        p.row0[b] = p.self_kv_row0[b] = rows;
+        p.n_rows[b] = p.self_seq_kv[b] = seq_lens[b];
         rows += seq_lens[b];
     }
     if (rows > S->scratch_rows) return hipErrorInvalidValue;
-    return run_blocks(S, X, Y, (int)rows, 0, /*cached=*/false, 0, 0, nullptr, s, &vs);
+    p.rows = (int)rows;
+    return run_blocks(S, p, X, Y, s);
 }
 
 hipError_t decoder_forward(Stack *S, const float *X, const float *enc_out, float *Y, int seq, int enc_seq,
@@ -664,7 +721,7 @@ hipError_t decoder_forward(Stack *S, const float *X, const float *enc_out, float
         return hipErrorInvalidValue;
     const hipError_t e = pack_enc(S, enc_out, enc_seq, s);
     if (e) return e;
-    return run_blocks(S, X, Y, seq, enc_seq, /*cached=*/false, 0, 0, nullptr, s);
+    return run_blocks(S, Pass{PassKind::Forward, seq, 1, seq, enc_seq}, X, Y, s);
 }
 
 hipError_t decoder_begin_slot(Stack *S, int slot, const float *enc_out, int enc_seq, hipStream_t s) {
@@ -685,10 +742,10 @@ hipError_t decoder_begin_slot(Stack *S, int slot, const float *enc_out, int enc_
 }
 
 hipError_t decoder_step_slot(Stack *S, int slot, const float *X, float *Y, int pos, int n, hipStream_t s) {
-    if (!S || !S->cross || !S->kv_cache || slot < 0 || slot >= S->n_slots || S->enc_seq[slot] < 1 ||
-        S->indirect[slot] || !X || !Y || n < 1 || pos < 0 || pos > S->filled[slot] || n > S->max_seq - pos)
+    uint64_t seen = 0;
+    if (!S || !S->cross || !S->kv_cache || !X || !Y || !admit(S, slot, /*indirect=*/false, seen, pos, n))
         return hipErrorInvalidValue;
-    const hipError_t e = run_blocks(S, X, Y, n, S->enc_seq[slot], /*cached=*/true, slot, pos, nullptr, s);
+    const hipError_t e = run_blocks(S, Pass{PassKind::Slot, n, 1, n, S->enc_seq[slot], slot, pos}, X, Y, s);
     if (e) return e;
     S->filled[slot] = pos + n;
     return hipSuccess;
@@ -701,29 +758,21 @@ hipError_t decoder_step_batch(Stack *S, int n_seqs, const int *slots, const int 
         return hipErrorInvalidValue;
     const int r = rows_per_seq;
     if (!attention_decode_ok(r, 1, S->d_model / S->n_heads)) return hipErrorInvalidValue;  // d_k > 64: no batched launch
-    BatchStep bs = {};
-    bs.n_seqs = n_seqs;
-    bs.rows_per_seq = r;
-    uint64_t seen = 0;  // n_slots <= 64
+    // (n_seqs * r <= scratch_rows: n_seqs <= n_slots, and r <= max_seq with one slot)
+    Pass p = {PassKind::Batch, n_seqs * r, n_seqs, r};
+    uint64_t seen = 0;
     for (int b = 0; b < n_seqs; ++b) {
         const int sl = slots[b];
-        if (sl < 0 || sl >= S->n_slots || S->enc_seq[sl] < 1 || S->indirect[sl] || (seen >> sl & 1) || pos[b] < 0 ||
-            pos[b] > S->filled[sl] || r > S->max_seq - pos[b])
-            return hipErrorInvalidValue;
-        seen |= (uint64_t)1 << sl;
-        bs.self.kv_slot[b] = bs.cross.kv_slot[b] = sl;
-        bs.self.seq_kv[b] = pos[b] + r;
-        bs.self.q_pos0[b] = pos[b];
-        bs.cross.seq_kv[b] = S->enc_seq[sl];
-        bs.scatter.slot[b] = sl;
-        bs.scatter.pos[b] = pos[b];
-        bs.scatter.row0[b] = b * r;
-        bs.scatter.n_rows[b] = r;
+        if (!admit(S, sl, /*indirect=*/false, seen, pos[b], r)) return hipErrorInvalidValue;
+        p.self.kv_slot[b] = p.cross.kv_slot[b] = sl;
+        p.self.seq_kv[b] = pos[b] + r;
+        p.self.q_pos0[b] = pos[b];
+        p.cross.seq_kv[b] = S->enc_seq[sl];
+        scatter_entry(p.scatter, b, sl, pos[b], b * r, r);
     }
-    // (n_seqs * r <= scratch_rows: n_seqs <= n_slots, and r <= max_seq with one slot)
-    const hipError_t e = run_blocks(S, X, Y, n_seqs * r, 0, /*cached=*/true, 0, 0, &bs, s);
+    const hipError_t e = run_blocks(S, p, X, Y, s);
     if (e) return e;
-    for (int b = 0; b < n_seqs; ++b) S->filled[slots[b]] = pos[b] + r;
+    set_filled(S, n_seqs, p.scatter);
     return hipSuccess;
 }
 
@@ -733,34 +782,28 @@ hipError_t decoder_step_varlen(Stack *S, int n_seqs, const int *slots, const int
                                float *Y, hipStream_t s) {
     if (!S || !S->cross || !S->kv_cache || !slots || !pos || !n_rows || !X || !Y || n_seqs < 1 || n_seqs > S->n_slots)
         return hipErrorInvalidValue;
-    VarlenStep vs = {};
-    vs.n_seqs = n_seqs;
-    uint64_t seen = 0;  // n_slots <= 64
+    Pass p = {PassKind::Varlen, 0, n_seqs};
+    p.kv_in_slabs = true;
+    uint64_t seen = 0;
     int64_t rows = 0;
     for (int b = 0; b < n_seqs; ++b) {
         const int sl = slots[b], n = n_rows[b];
-        if (sl < 0 || sl >= S->n_slots || S->enc_seq[sl] < 1 || S->indirect[sl] || (seen >> sl & 1) || n < 1 ||
-            pos[b] < 0 ||
-            pos[b] > S->filled[sl] || n > S->max_seq - pos[b])
-            return hipErrorInvalidValue;
-        seen |= (uint64_t)1 << sl;
-        vs.row0[b] = rows;
-        vs.n_rows[b] = n;
-        vs.self_kv_row0[b] = (int64_t)sl * S->max_seq;
-        vs.self_seq_kv[b] = pos[b] + n;
-        vs.self_pos0[b] = pos[b];
-        vs.cross_kv_row0[b] = (int64_t)sl * S->max_enc_seq;
-        vs.cross_seq_kv[b] = S->enc_seq[sl];
-        vs.scatter.slot[b] = sl;
-        vs.scatter.pos[b] = pos[b];
-        vs.scatter.row0[b] = (int)rows;
-        vs.scatter.n_rows[b] = n;
+        if (!admit(S, sl, /*indirect=*/false, seen, pos[b], n)) return hipErrorInvalidValue;
+        p.row0[b] = rows;
+        p.n_rows[b] = n;
+        p.self_kv_row0[b] = (int64_t)sl * S->max_seq;
+        p.self_seq_kv[b] = pos[b] + n;
+        p.self_pos0[b] = pos[b];
+        p.cross_kv_row0[b] = (int64_t)sl * S->max_enc_seq;
+        p.cross_seq_kv[b] = S->enc_seq[sl];
+        scatter_entry(p.scatter, b, sl, pos[b], (int)rows, n);
         rows += n;
         if (rows > S->scratch_rows) return hipErrorInvalidValue;
     }
-    const hipError_t e = run_blocks(S, X, Y, (int)rows, 0, /*cached=*/true, 0, 0, nullptr, s, &vs);
+    p.rows = (int)rows;
+    const hipError_t e = run_blocks(S, p, X, Y, s);
     if (e) return e;
-    for (int b = 0; b < n_seqs; ++b) S->filled[slots[b]] = pos[b] + n_rows[b];
+    set_filled(S, n_seqs, p.scatter);
     return hipSuccess;
 }
 
@@ -882,37 +925,27 @@ hipError_t decoder_step_batch_indirect(Stack *S, int n_seqs, const int *slots, c
         return hipErrorInvalidValue;
     const int r = rows_per_seq;
     if (!attention_decode_ok(r, 1, S->d_model / S->n_heads)) return hipErrorInvalidValue;
-    BatchStep bs = {};
-    bs.n_seqs = n_seqs;
-    bs.rows_per_seq = r;
-    bs.indirect = true;
-    int count[kDecodeMaxBatch];
-    uint64_t seen = 0;  // n_slots <= 64
+    Pass p = {PassKind::BatchIndirect, n_seqs * r, n_seqs, r};
+    uint64_t seen = 0;
     for (int b = 0; b < n_seqs; ++b) {
         const int sl = slots[b], cs = cross_slots[b];
-        if (sl < 0 || sl >= S->n_slots || !S->indirect[sl] || (seen >> sl & 1) || cs < 0 || cs >= S->n_slots ||
-            S->enc_seq[cs] < 1 || S->enc_seq[cs] != S->enc_seq[sl] || pos[b] < 0 || pos[b] > S->filled[sl] ||
-            r > S->max_seq - pos[b])
+        // (a beam's slot carries its prompt's enc_seq, so "begun" is the cross slot's: begun, and the same enc_seq)
+        if (!admit(S, sl, /*indirect=*/true, seen, pos[b], r) || cs < 0 || cs >= S->n_slots || S->enc_seq[cs] < 1 ||
+            S->enc_seq[cs] != S->enc_seq[sl])
             return hipErrorInvalidValue;
-        seen |= (uint64_t)1 << sl;
-        bs.self.kv_slot[b] = sl;
-        bs.self.seq_kv[b] = pos[b] + r;
-        bs.self.q_pos0[b] = pos[b];
-        bs.cross.kv_slot[b] = cs;
-        bs.cross.seq_kv[b] = S->enc_seq[cs];
-        bs.scatter.slot[b] = sl;
-        bs.scatter.pos[b] = pos[b];
-        bs.scatter.row0[b] = b * r;
-        bs.scatter.n_rows[b] = r;
-        count[b] = r;
+        p.self.kv_slot[b] = sl;
+        p.self.seq_kv[b] = pos[b] + r;
+        p.self.q_pos0[b] = pos[b];
+        p.cross.kv_slot[b] = cs;
+        p.cross.seq_kv[b] = S->enc_seq[cs];
+        scatter_entry(p.scatter, b, sl, pos[b], b * r, r);
     }
-    hipError_t e = launch_beam_fill(S->own, S->max_seq, S->n_slots, n_seqs, slots, pos, count, slots, s);
+    hipError_t e = launch_beam_fill(S->own, S->max_seq, S->n_slots, n_seqs, slots, pos, p.scatter.n_rows, slots, s);
     if (e) return e;
-    if ((e = run_blocks(S, X, Y, n_seqs * r, 0, /*cached=*/true, 0, 0, &bs, s))) return e;
-    for (int b = 0; b < n_seqs; ++b) {
-        S->filled[slots[b]] = pos[b] + r;
+    if ((e = run_blocks(S, p, X, Y, s))) return e;
+    set_filled(S, n_seqs, p.scatter);
+    for (int b = 0; b < n_seqs; ++b)
         S->own_rows[slots[b]] = std::min(S->own_rows[slots[b]], pos[b]);  // a rewind into the prompt overwrites it
-    }
     return hipSuccess;
 }
 

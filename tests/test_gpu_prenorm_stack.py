@@ -202,6 +202,29 @@ def test_step_varlen_mixes_a_prefill_and_a_decoding_row(qg, oracle, device):
     assert_bits_equal(got[4:], _slot_expected(2, 4)[-1:], "the decoding row")
 
 
+def test_indirect_beam_steps_equal_each_beams_own_forward(qg, oracle, device):
+    """The copy-free beam search's calls on a pre-LN stack with the final norm: a 2-row prompt in slot 0, beam_begin of
+    two beams on it, step_batch_indirect, beam_reindex (both beams continue beam 1), step_batch_indirect again.  Every
+    output row is the last row of the causal forward on that beam's own prefix."""
+    X, enc = _slot_seq(0)
+    new1, new2 = O.uniform((2, D), 71), O.uniform((2, D), 72)
+    dec = _decoder(qg, n_slots=3)
+    try:
+        _load(dec, _weights(True), device)
+        dec.begin_slot(0, _dev(enc, device))
+        dec.step_slot(0, _dev(X[:2], device))
+        dec.beam_begin([0, 1], [0], [2], 2)
+        y1 = dec.step_batch_indirect([0, 1], [0, 0], _dev(new1, device), pos=[2, 2], Y=_nan((2, D), device)).cpu().numpy()
+        dec.beam_reindex([0, 1], torch.tensor([1, 1], dtype=torch.int32, device=device), [3], 2)
+        y2 = dec.step_batch_indirect([0, 1], [0, 0], _dev(new2, device), pos=[3, 3], Y=_nan((2, D), device)).cpu().numpy()
+    finally:
+        dec.close()
+    for q in range(2):
+        for got, prefix in ((y1, [X[:2], new1[q:q + 1]]), (y2, [X[:2], new1[1:2], new2[q:q + 1]])):
+            want = PO.decoder_forward_pre(np.concatenate(prefix), enc, _weights(True), D, H, BLOCKS, True)
+            assert_bits_equal(got[q:q + 1], want[-1:], f"beam {q} at position {len(want) - 1}")
+
+
 def test_forward_batch_of_three_lengths(qg, oracle, device):
     X = _inputs()[0]
     W = _weights(False)
