@@ -1009,6 +1009,72 @@ QGEMM_API int qgemm_prenorm_pack_a(const float *A, const float *B_or_null, const
                          float *S_or_null, int64_t rows, int w, float range, void *packed_a, void *stream);
 QGEMM_API int qgemm_add_rows(const float *A, const float *B, float *S, int64_t rows, int w, void *stream);
 
+/* ---- Decoder-only stacks and rotary position embeddings -------------------------------------
+ * Two more modifier bits on qgemm_model_desc.arch, which does not grow; any bit above them is refused.
+ *
+ * QGEMM_ARCH_DECODER_ONLY: a model of the decoder family (cross = 1 only; with cross = 0 it is refused) whose blocks
+ * lack the cross-attention third -- self-attention, the boundary, FFN, the boundary: the encoder's block, under the
+ * decoder's causal mask and with its caches (GPT-2, OPT).  Valid on every base architecture.  max_enc_seq must be 0;
+ * every other check of the decoder creators applies (flags, n_slots, max_rows).  The weights are the ENCODER's: the
+ * same kinds, heads, bounds and seeds, so with flags = 0 qgemm_decoder_forward gives, bit for bit, qgemm_encoder_forward
+ * of an encoder with the same sizes, seed and arch bits; kinds 8 .. 11 and 20 .. 25 are refused as on an encoder, and
+ * a pre-LN block's second norm is gamma3 / beta3.  No cross weights, scratch or slabs exist.  The handle takes every
+ * qgemm_decoder_* and qgemm_model_* call and the decoder's destroy:
+ *   qgemm_decoder_forward              enc_out must be NULL and enc_seq 0 (anything else: hipErrorInvalidValue)
+ *   qgemm_decoder_begin / begin_slot   the same arguments; NO launch: the slot becomes "begun" with filled = 0 and
+ *                                      its indirect flag cleared
+ *   step, step_slot, step_batch, step_varlen, generate, generate_sampled, generate_beam, generate_beam_indirect,
+ *   beam_begin, beam_reindex           the same contracts, without the cross launches
+ *   copy_slot, gather_slots            the self slabs only
+ *   step_batch_indirect                cross_slots is checked as before (in range, begun) and otherwise unused
+ *   read_slot                          cross_rows must be NULL
+ *   slot_state                         *enc_seq is 0 whether or not the slot is begun: ask qgemm_decoder_slot_begun
+ * qgemm_decoder_slot_begun (any decoder with caches): *begun = 1 between the slot's begin (or a copy / beam_begin that
+ * made it a sequence) and the next qgemm_model_set_weight, else 0; with cross-attention that is enc_seq >= 1.
+ *
+ * QGEMM_ARCH_ROPE: rotary position embeddings on the self-attention's Q and K (GPT-NeoX, Llama: the half-split
+ * "rotate_half" pairing, not the interleaved one).  Valid on QGEMM_ARCH_STANDARD only (post-LN or pre-LN; encoder,
+ * decoder or decoder-only) and where d_k = d_model / n_heads is even.  The model owns two tables, addressed with
+ * block = 0, head = 0, which exist on ROPE models only (every other model refuses the kinds):
+ *   kind 28, 29      rope_cos, rope_sin   max_seq x d_k / 2 each
+ * filled at creation on the host in double precision,
+ *   inv_i = pow(10000.0, -2.0 i / d_k),  cos[p][i] = (float)cos((double)p inv_i),  sin[p][i] = (float)sin((double)p inv_i)
+ * qgemm_model_set_weight replaces a table (another theta, a scaled table) by the strided widening copy of the bias
+ * kinds, one copy per table row, and resets the cache slots as every kind does; qgemm_model_weight_shape reports
+ * max_seq x d_k / 2; qgemm_model_bias refuses the kinds, qgemm_model_rope_tables returns non-owning device pointers
+ * (rows = max_seq, half = d_k / 2; rows / half may be NULL).  In every block ONE qgemm_rope_rows[_varlen] launch
+ * follows the QKV GEMM: the Q and K thirds of the call's new rows (2 n_heads groups of d_k at stride 3 d_model), each
+ * row at its absolute position -- 0 .. for a forward and for every sequence of a batched forward, pos .. for a step.
+ * V is not touched, the caches hold rotated K, and the cross-attention is never rotated.  The rotation is row-local
+ * and depends on the row's own position alone, so every contract that rests on row-locality and the prefix property
+ * carries over.
+ *
+ * qgemm_rope_rows: in place on `rows` rows of `groups` consecutive groups of d_k floats, rows stride_h floats apart;
+ * row r stands at position p = pos0 + r.  With h = d_k / 2, c = cos[p h + i], s = sin[p h + i], i < h, per group:
+ *   a = x[i], b = x[i + h]               both read before either is written
+ *   x[i]     = fl(fl(a c) - fl(b s))
+ *   x[i + h] = fl(fl(b c) + fl(a s))
+ * Every step is ONE IEEE fp32 operation: no contraction, no fma.  NaN and +-inf give what these operations give.  No
+ * trigonometry runs on the device: cos and sin are the caller's tables of table_rows x h floats.  Where d_k % 8 == 0
+ * and X, stride_h and both tables are 16-byte aligned a thread moves one float4 of the low half and the matching one
+ * of the high half, else one pair; both give the same bits.  One launch, no workspace, no allocation, no
+ * synchronization; capturable.
+ * qgemm_rope_rows_varlen: n_seqs <= 64 sequences in one launch; sequence b is rows row0[b] .. row0[b] + n_rows[b] - 1
+ * of X at positions pos0[b] ..; the three arrays are HOST arrays read at enqueue time (they travel in the kernel
+ * arguments).  Rows between the sequences are not touched; sequences must not overlap.
+ * hipErrorInvalidValue before any launch: a null pointer; d_k odd or < 2; groups < 1; stride_h < groups d_k (a
+ * negative one included) or groups d_k past int32; rows < 0 or n_rows[b] < 0; row0[b] < 0; n_seqs < 1 or > 64; table_rows < 1; any position
+ * < 0 or >= table_rows (pos0 itself, and pos0 + rows - 1).  rows == 0 (every n_rows[b] == 0) returns 0. */
+#define QGEMM_ARCH_DECODER_ONLY 0x400 /* with cross = 1 only; max_enc_seq = 0 */
+#define QGEMM_ARCH_ROPE 0x800         /* with QGEMM_ARCH_STANDARD only; d_model / n_heads even */
+QGEMM_API int qgemm_decoder_slot_begun(void *decoder, int slot, int *begun);
+QGEMM_API int qgemm_model_rope_tables(void *model, const float **cos, const float **sin, int *rows, int *half);
+QGEMM_API int qgemm_rope_rows(float *X, int64_t stride_h, int64_t rows, int groups, int d_k, const float *cos,
+                    const float *sin, int table_rows, int pos0, void *stream);
+QGEMM_API int qgemm_rope_rows_varlen(float *X, int64_t stride_h, int groups, int d_k, const float *cos, const float *sin,
+                           int table_rows, int n_seqs, const int64_t *row0, const int *n_rows, const int *pos0,
+                           void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -144,6 +144,10 @@ EXPORTED_SYMBOLS = (
     "qgemm_model_info",
     "qgemm_prenorm_pack_a",
     "qgemm_add_rows",
+    "qgemm_decoder_slot_begun",
+    "qgemm_model_rope_tables",
+    "qgemm_rope_rows",
+    "qgemm_rope_rows_varlen",
 )
 
 # Every symbol include/qgemm_dist.h declares (libqgemm_dist.so: M-shards + RCCL all-gather).
@@ -175,6 +179,8 @@ QGEMM_VARLEN_MAX_SEQS = 64     # sequences per attention_varlen / forward_batch 
 QGEMM_ARCH_REFERENCE, QGEMM_ARCH_STANDARD = 0, 1  # qgemm_model_create: the reference's block / the post-LN block
 QGEMM_ACT_RELU, QGEMM_ACT_GELU_TANH = 0, 1        # ... and the FFN's activation (GELU: standard only)
 QGEMM_ARCH_NORM_FIRST, QGEMM_ARCH_FINAL_NORM = 0x100, 0x200  # modifier bits on arch: the pre-LN block
+# ... a decoder without the cross-attention third / rotary embeddings on Q and K
+QGEMM_ARCH_DECODER_ONLY, QGEMM_ARCH_ROPE = 0x400, 0x800
 ARCHS = {"reference": QGEMM_ARCH_REFERENCE, "standard": QGEMM_ARCH_STANDARD}
 ACTIVATIONS = {"relu": QGEMM_ACT_RELU, "gelu_tanh": QGEMM_ACT_GELU_TANH}
 
@@ -444,6 +450,14 @@ def load() -> ctypes.CDLL:
         L.qgemm_prenorm_pack_a.restype = i32
         L.qgemm_add_rows.argtypes = [vp, vp, vp, i64, i32, vp]
         L.qgemm_add_rows.restype = i32
+        L.qgemm_decoder_slot_begun.argtypes = [vp, i32, ip]
+        L.qgemm_decoder_slot_begun.restype = i32
+        L.qgemm_model_rope_tables.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ip, ip]
+        L.qgemm_model_rope_tables.restype = i32
+        L.qgemm_rope_rows.argtypes = [vp, i64, i64, i32, i32, vp, vp, i32, i32, vp]
+        L.qgemm_rope_rows.restype = i32
+        L.qgemm_rope_rows_varlen.argtypes = [vp, i64, i32, i32, vp, vp, i32, i32, lp, ip, ip, vp]
+        L.qgemm_rope_rows_varlen.restype = i32
         _lib = L
         return L
 
@@ -1126,6 +1140,39 @@ def gelu_pack_a(X, range: float = DEFAULT_RANGE, out=None) -> Packed:  # noqa: A
     return Packed(buf, M, K, range)
 
 
+def _rope_args(X, groups: int, d_k: int, cos, sin):
+    _require_device_f32(X, "X")
+    _require_device_f32(cos, "cos")
+    _require_device_f32(sin, "sin")
+    assert X.dim() == 2 and X.stride(1) == 1 and X.shape[1] == groups * d_k, "X: rows x groups * d_k, unit inner stride"
+    assert cos.is_contiguous() and sin.is_contiguous() and cos.dim() == 2 and cos.shape == sin.shape and \
+        2 * cos.shape[1] == d_k, "cos, sin: table_rows x d_k / 2, contiguous"
+    return cos.shape[0]
+
+
+def rope_rows(X, groups: int, d_k: int, cos, sin, pos0: int = 0):
+    """Rotary position embedding IN PLACE on the rows of X (qgemm_rope_rows): rows x groups * d_k floats, any row
+    stride; row r of every group is rotated (half-split pairing) by position pos0 + r of the tables cos, sin
+    (table_rows x d_k / 2).  Returns X."""
+    table_rows = _rope_args(X, groups, d_k, cos, sin)
+    _check("qgemm_rope_rows", load().qgemm_rope_rows(X.data_ptr(), X.stride(0), X.shape[0], groups, d_k, cos.data_ptr(),
+                                                    sin.data_ptr(), table_rows, int(pos0), _stream(X.device)))
+    return X
+
+
+def rope_rows_varlen(X, groups: int, d_k: int, cos, sin, row0, n_rows, pos0):
+    """rope_rows on len(n_rows) <= 64 sequences in one launch (qgemm_rope_rows_varlen): sequence b is rows row0[b] ..
+    row0[b] + n_rows[b] - 1 of X at positions pos0[b] ..; rows between the sequences are not touched.  Returns X."""
+    table_rows = _rope_args(X, groups, d_k, cos, sin)
+    n = len(n_rows)
+    assert all(0 <= int(r) and int(r) + int(c) <= X.shape[0] for r, c in zip(row0, n_rows)), "a sequence leaves X"
+    _check("qgemm_rope_rows_varlen",
+           load().qgemm_rope_rows_varlen(X.data_ptr(), X.stride(0), groups, d_k, cos.data_ptr(), sin.data_ptr(),
+                                         table_rows, n, _int64_array(row0, n, "row0"), _int_array(n_rows, n, "n_rows"),
+                                         _int_array(pos0, n, "pos0"), _stream(X.device)))
+    return X
+
+
 def mm_outlier(A, B, threshold: float = 6.0, C=None):
     """LLM.int8() decomposition: outlier feature columns in fp32, the rest int8.
     Returns (C, number of outlier columns)."""
@@ -1198,6 +1245,8 @@ def encoder_weight_seed(base: int, block: int, kind: int, head: int) -> int:
  KIND_BQ2, KIND_BK2, KIND_BV2, KIND_BO2, KIND_G2, KIND_BE2) = range(12, 26)
 # The final norm of a pre-LN model created with final_norm=True: block 0, head 0; refused elsewhere.
 KIND_GF, KIND_BEF = 26, 27
+# The rotary tables of a model created with rope=True: max_seq x d_k / 2 each, block 0, head 0.
+KIND_ROPE_COS, KIND_ROPE_SIN = 28, 29
 _VECTOR_KINDS = (KIND_B1, KIND_B2) + tuple(range(KIND_BQ, KIND_BEF + 1))
 # packed_weight's `which`
 (WEIGHT_WQKV, WEIGHT_WO, WEIGHT_W1, WEIGHT_W2, WEIGHT_WQ2, WEIGHT_WKV2, WEIGHT_WO2) = range(7)
@@ -1212,18 +1261,27 @@ class _DeviceView:
 
 
 class _ArchKeywords(type):
-    """Encoder(..., arch=, activation=, ln_eps=, norm_first=, final_norm=) and the same on Decoder: keyword-only
-    arguments of the class call, set on the object before __init__ runs.  norm_first (arch="standard" only): the pre-LN
+    """Encoder(..., arch=, activation=, ln_eps=, norm_first=, final_norm=, rope=) and the same on Decoder, which also takes
+    decoder_only=: keyword-only arguments of the class call, set on the object before __init__ runs.  decoder_only
+    (Decoder, with max_enc_seq = 0): the blocks lack the cross-attention; rope (arch="standard" only): rotary
+    embeddings on Q and K.  norm_first (arch="standard" only): the pre-LN
     block; final_norm (with norm_first only): a LayerNorm behind the last block.  __init__ keeps its parameter list as it was (its last parameters stay
     max_rows, and n_slots on a Decoder), so positional callers and tools that read that list see no change."""
 
     def __call__(cls, *args, arch: str = "reference", activation: str = "relu", ln_eps: float = 1e-5,
-                 norm_first: bool = False, final_norm: bool = False, **kw):
+                 norm_first: bool = False, final_norm: bool = False, decoder_only: bool = False, rope: bool = False,
+                 **kw):
         assert not norm_first or arch != "reference", "norm_first needs arch='standard'"
         assert norm_first or not final_norm, "final_norm needs norm_first=True"
+        assert not rope or arch != "reference", "rope needs arch='standard'"
+        if decoder_only:  # (Decoder's parameters: d_model, n_heads, d_ff, n_blocks, max_seq, max_enc_seq, ..)
+            assert cls.__name__ == "Decoder", "decoder_only belongs to Decoder"
+            max_enc_seq = kw["max_enc_seq"] if "max_enc_seq" in kw else (args[5] if len(args) > 5 else None)
+            assert max_enc_seq == 0, "decoder_only needs max_enc_seq = 0"
         self = cls.__new__(cls)
         self.arch, self.activation, self.ln_eps = arch, activation, float(ln_eps)
         self.norm_first, self.final_norm = bool(norm_first), bool(final_norm)
+        self.decoder_only, self.rope = bool(decoder_only), bool(rope)
         self.__init__(*args, **kw)
         return self
 
@@ -1280,7 +1338,9 @@ class _ModelWeights(metaclass=_ArchKeywords):
                          self.n_blocks, self.max_seq, max_enc_seq, self.seed, flags, n_slots,
                          0 if max_rows is None else int(max_rows),
                          ARCHS[arch] | (QGEMM_ARCH_NORM_FIRST if self.norm_first else 0) |
-                         (QGEMM_ARCH_FINAL_NORM if self.final_norm else 0), ACTIVATIONS[activation], float(ln_eps))
+                         (QGEMM_ARCH_FINAL_NORM if self.final_norm else 0) |
+                         (QGEMM_ARCH_DECODER_ONLY if getattr(self, "decoder_only", False) else 0) |
+                         (QGEMM_ARCH_ROPE if getattr(self, "rope", False) else 0), ACTIVATIONS[activation], float(ln_eps))
         h = ctypes.c_void_p()
         _check("qgemm_model_create", load().qgemm_model_create(ctypes.byref(desc), ctypes.byref(h)))
         return h
@@ -1305,8 +1365,9 @@ class _ModelWeights(metaclass=_ArchKeywords):
         if self.arch != "standard":
             raise ValueError("load_torch_layer needs a model created with arch='standard'")
         cross = hasattr(layer, "multihead_attn")
-        if cross != isinstance(self, Decoder):
-            raise ValueError("an Encoder takes a TransformerEncoderLayer, a Decoder a TransformerDecoderLayer")
+        if cross != (isinstance(self, Decoder) and not getattr(self, "decoder_only", False)):
+            raise ValueError("an Encoder or a decoder-only Decoder takes a TransformerEncoderLayer, a Decoder with "
+                             "cross-attention a TransformerDecoderLayer")
         if bool(getattr(layer, "norm_first", False)) != getattr(self, "norm_first", False):
             raise ValueError(f"the layer has norm_first={bool(getattr(layer, 'norm_first', False))}, the model "
                              f"norm_first={getattr(self, 'norm_first', False)}")
@@ -1388,6 +1449,18 @@ class _ModelWeights(metaclass=_ArchKeywords):
         _check("qgemm_model_bias", load().qgemm_model_bias(self._h, block, kind, ctypes.byref(p), ctypes.byref(n)))
         dev = torch.device("cuda", torch.cuda.current_device())
         return torch.as_tensor(_DeviceView(p.value, 4 * n.value, self), device=dev).view(torch.float32).clone()
+
+    def rope_tables(self):
+        """(cos, sin) of a model created with rope=True (qgemm_model_rope_tables): copies, max_seq x d_k / 2 floats each
+        on the device -- what set_weight(0, KIND_ROPE_COS / KIND_ROPE_SIN, ..) replaces."""
+        import torch
+        c, s, rows, half = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_int(), ctypes.c_int()
+        _check("qgemm_model_rope_tables", load().qgemm_model_rope_tables(self._h, ctypes.byref(c), ctypes.byref(s),
+                                                                        ctypes.byref(rows), ctypes.byref(half)))
+        dev = torch.device("cuda", torch.cuda.current_device())
+        nbytes = 4 * rows.value * half.value
+        return tuple(torch.as_tensor(_DeviceView(p.value, nbytes, self), device=dev).view(torch.float32)
+                     .reshape(rows.value, half.value).clone() for p in (c, s))
 
 
 class Encoder(_ModelWeights):
@@ -1735,8 +1808,9 @@ class Decoder(_ModelWeights):
         self.causal, self.kv_cache, self.n_slots = bool(causal), bool(kv_cache), int(n_slots)
         self.max_rows = max_rows
         h = ctypes.c_void_p()
-        if self.arch != "reference" or self.activation != "relu":
-            # the post-LN block of torch.nn.TransformerDecoderLayer (qgemm_model_create)
+        if self.arch != "reference" or self.activation != "relu" or getattr(self, "decoder_only", False):
+            # the post-LN block of torch.nn.TransformerDecoderLayer (qgemm_model_create); a decoder-only
+            # model of any architecture
             flags = (QGEMM_DECODER_CAUSAL if causal else 0) | (QGEMM_DECODER_KV_CACHE if kv_cache else 0)
             h = self._create_model(True, max_enc_seq, flags, n_slots, max_rows, self.arch, self.activation, self.ln_eps)
         elif max_rows is not None:
@@ -1763,38 +1837,48 @@ class Decoder(_ModelWeights):
                                                                       max_enc_seq, seed, ctypes.byref(h)))
         self._h = h
 
-    def forward(self, X, enc_out, Y=None):
+    def _enc_args(self, enc_out):
+        """(pointer, rows) of the encoder output a forward or a begin passes on: None on a decoder-only model alone."""
+        if getattr(self, "decoder_only", False):
+            assert enc_out is None, "a decoder-only model takes no enc_out"
+            return None, 0
+        assert enc_out is not None, "enc_out: the encoder's output rows"
+        _require_device_f32(enc_out, "enc_out")
+        assert enc_out.is_contiguous() and enc_out.shape[1] == self.d_model
+        return enc_out.data_ptr(), enc_out.shape[0]
+
+    def forward(self, X, enc_out=None, Y=None):
         import torch
         _require_device_f32(X, "X")
-        _require_device_f32(enc_out, "enc_out")
         assert X.is_contiguous() and X.shape[1] == self.d_model
-        assert enc_out.is_contiguous() and enc_out.shape[1] == self.d_model
+        enc_ptr, enc_seq = self._enc_args(enc_out)
         Y = torch.empty_like(X) if Y is None else Y
-        _check("qgemm_decoder_forward", load().qgemm_decoder_forward(self._h, X.data_ptr(), enc_out.data_ptr(),
-                                                                    Y.data_ptr(), X.shape[0], enc_out.shape[0],
-                                                                    _stream(X.device)))
+        _check("qgemm_decoder_forward", load().qgemm_decoder_forward(self._h, X.data_ptr(), enc_ptr, Y.data_ptr(),
+                                                                    X.shape[0], enc_seq, _stream(X.device)))
         return Y
 
     def slot_filled(self, slot: int):
         """The filled length of a cache slot as the decoder keeps it (qgemm_decoder_slot_state): None before the
         slot's begin (and on a decoder without caches)."""
-        enc_seq, filled = ctypes.c_int(), ctypes.c_int()
+        enc_seq, filled, begun = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
         if not getattr(self, "_h", None) or load().qgemm_decoder_slot_state(self._h, slot, ctypes.byref(enc_seq),
                                                                             ctypes.byref(filled)):
             return None
-        return filled.value if enc_seq.value > 0 else None
+        if load().qgemm_decoder_slot_begun(self._h, slot, ctypes.byref(begun)):
+            return None
+        return filled.value if begun.value else None
 
     @property
     def filled(self):
         """Slot 0's filled length -- the sequence begin() / step() drive: None before begin()."""
         return self.slot_filled(0)
 
-    def begin(self, enc_out):
-        """Start a sequence (qgemm_decoder_begin): every block's [K2 | V2] of enc_out into its cross cache."""
-        _require_device_f32(enc_out, "enc_out")
-        assert enc_out.is_contiguous() and enc_out.shape[1] == self.d_model
-        _check("qgemm_decoder_begin", load().qgemm_decoder_begin(self._h, enc_out.data_ptr(), enc_out.shape[0],
-                                                                _stream(enc_out.device)))
+    def begin(self, enc_out=None):
+        """Start a sequence (qgemm_decoder_begin): every block's [K2 | V2] of enc_out into its cross cache.  A
+        decoder-only model takes no enc_out and launches nothing."""
+        enc_ptr, enc_seq = self._enc_args(enc_out)
+        _check("qgemm_decoder_begin", load().qgemm_decoder_begin(self._h, enc_ptr, enc_seq,
+                                                                _stream(None if enc_out is None else enc_out.device)))
 
     def step(self, X_new, pos=None, Y=None):
         """The output rows of the input rows X_new (n x d_model) at positions pos .. pos + n - 1
@@ -1812,12 +1896,12 @@ class Decoder(_ModelWeights):
                                                               X_new.shape[0], _stream(X_new.device)))
         return Y
 
-    def begin_slot(self, slot: int, enc_out):
+    def begin_slot(self, slot: int, enc_out=None):
         """begin() for one cache slot (qgemm_decoder_begin_slot); slot 0 is begin()'s."""
-        _require_device_f32(enc_out, "enc_out")
-        assert enc_out.is_contiguous() and enc_out.shape[1] == self.d_model
-        _check("qgemm_decoder_begin_slot", load().qgemm_decoder_begin_slot(self._h, slot, enc_out.data_ptr(),
-                                                                          enc_out.shape[0], _stream(enc_out.device)))
+        enc_ptr, enc_seq = self._enc_args(enc_out)
+        _check("qgemm_decoder_begin_slot",
+               load().qgemm_decoder_begin_slot(self._h, slot, enc_ptr, enc_seq,
+                                               _stream(None if enc_out is None else enc_out.device)))
 
     def step_slot(self, slot: int, X_new, pos=None, Y=None):
         """step() for one cache slot (qgemm_decoder_step_slot); pos defaults to the slot's filled length."""
@@ -1945,8 +2029,10 @@ class Decoder(_ModelWeights):
         dev = torch.device("cuda", torch.cuda.current_device())
         self_rows = torch.empty((self.max_seq, 3 * self.d_model), dtype=torch.float32, device=dev)
         cross_rows = torch.empty((self.max_enc_seq, 2 * self.d_model), dtype=torch.float32, device=dev)
+        # (decoder-only: no cross slab, 0 rows back)
+        cross_ptr = None if getattr(self, "decoder_only", False) else cross_rows.data_ptr()
         _check("qgemm_decoder_read_slot", load().qgemm_decoder_read_slot(self._h, block, slot, self_rows.data_ptr(),
-                                                                        cross_rows.data_ptr(), _stream(dev)))
+                                                                        cross_ptr, _stream(dev)))
         return self_rows, cross_rows
 
     def beam_fork(self, slot: int, slots_a, slots_b):

@@ -607,6 +607,15 @@ int qgemm_decoder_slot_state(void *decoder, int slot, int *enc_seq, int *filled)
     return err(decoder_slot_state(static_cast<Stack *>(decoder), slot, enc_seq, filled));
 }
 
+int qgemm_decoder_slot_begun(void *decoder, int slot, int *begun) {
+    int enc_seq;
+    if (!begun) return err(hipErrorInvalidValue);
+    const hipError_t e = decoder_slot_state(static_cast<Stack *>(decoder), slot, &enc_seq, nullptr);
+    if (e) return err(e);
+    *begun = decoder_slot_begun(static_cast<Stack *>(decoder), slot) ? 1 : 0;
+    return 0;
+}
+
 int qgemm_decoder_destroy(void *decoder) {
     stack_destroy(static_cast<Stack *>(decoder));
     return 0;
@@ -643,6 +652,25 @@ int qgemm_model_packed_weight(void *model, int block, int which, const void **pa
 
 int qgemm_model_bias(void *model, int block, int kind, const float **bias, int *n) {
     return err(stack_bias(static_cast<Stack *>(model), block, kind, bias, n));
+}
+
+int qgemm_model_rope_tables(void *model, const float **cos, const float **sin, int *rows, int *half) {
+    return err(stack_rope_tables(static_cast<Stack *>(model), cos, sin, rows, half));
+}
+
+// ---- rotary position embeddings: every check sits with the launch it guards (rope.hip)
+
+int qgemm_rope_rows(float *X, int64_t stride_h, int64_t rows, int groups, int d_k, const float *cos, const float *sin,
+                    int table_rows, int pos0, void *stream) {
+    return err(launch_rope_rows(X, stride_h, rows, groups, d_k, cos, sin, table_rows, pos0,
+                                static_cast<hipStream_t>(stream)));
+}
+
+int qgemm_rope_rows_varlen(float *X, int64_t stride_h, int groups, int d_k, const float *cos, const float *sin,
+                           int table_rows, int n_seqs, const int64_t *row0, const int *n_rows, const int *pos0,
+                           void *stream) {
+    return err(launch_rope_rows_varlen(X, stride_h, groups, d_k, cos, sin, table_rows, n_seqs, row0, n_rows, pos0,
+                                       static_cast<hipStream_t>(stream)));
 }
 
 // ---- the standard block ----
@@ -686,9 +714,9 @@ int qgemm_model_create(const qgemm_model_desc *desc, void **model) {
     *model = nullptr;
     if (!desc || desc->size != sizeof(qgemm_model_desc)) return err(hipErrorInvalidValue);
     const qgemm_model_desc &d = *desc;
-    if (!stack_arch_ok(d.arch) || (d.activation != QGEMM_ACT_RELU && d.activation != QGEMM_ACT_GELU_TANH) ||
+    if ((d.cross != 0 && d.cross != 1) || !stack_arch_ok(d.arch, d.cross != 0) || (d.activation != QGEMM_ACT_RELU && d.activation != QGEMM_ACT_GELU_TANH) ||
         ((d.arch & 0xff) == QGEMM_ARCH_REFERENCE && d.activation != QGEMM_ACT_RELU) || !(d.ln_eps >= 0.0f) ||
-        (d.cross != 0 && d.cross != 1) || d.n_slots < 0 || d.max_rows < 0)
+        d.n_slots < 0 || d.max_rows < 0)
         return err(hipErrorInvalidValue);
     const int n_slots = d.n_slots ? d.n_slots : 1;
     bool causal = false, kv_cache = false;

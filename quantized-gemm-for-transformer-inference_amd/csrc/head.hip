@@ -364,8 +364,9 @@ int generate_steps(void *decoder, void *head, int n_seqs, const int *slots, cons
     int at[kEmbedMaxSeqs];
     uint64_t seen = 0;  // n_slots <= 64
     for (int b = 0; b < n_seqs; ++b) {
-        int enc_seq, filled;
-        if (decoder_slot_state(S, slots[b], &enc_seq, &filled) || enc_seq < 1 || decoder_slot_indirect(S, slots[b]) ||
+        int filled;
+        if (decoder_slot_state(S, slots[b], nullptr, &filled) || !decoder_slot_begun(S, slots[b]) ||
+            decoder_slot_indirect(S, slots[b]) ||
             (seen >> slots[b] & 1))
             return (int)hipErrorInvalidValue;
         seen |= (uint64_t)1 << slots[b];
@@ -425,7 +426,8 @@ int generate_beam_steps(void *decoder, void *head, int n_groups, int beams, cons
             const int r = g * beams + q;
             int enc_a, enc_b, filled_a, filled_b;
             if (decoder_slot_state(S, slots_a[r], &enc_a, &filled_a) ||
-                decoder_slot_state(S, slots_b[r], &enc_b, &filled_b) || enc_a < 1 || enc_b != enc_a ||
+                decoder_slot_state(S, slots_b[r], &enc_b, &filled_b) || !decoder_slot_begun(S, slots_a[r]) ||
+                !decoder_slot_begun(S, slots_b[r]) || enc_b != enc_a ||
                 slots_a[r] == slots_b[r] || (seen >> slots_a[r] & 1) || (seen >> slots_b[r] & 1) ||
                 decoder_slot_indirect(S, slots_a[r]) || decoder_slot_indirect(S, slots_b[r]))
                 return (int)hipErrorInvalidValue;
@@ -487,7 +489,8 @@ int generate_beam_indirect_steps(void *decoder, void *head, int n_groups, int be
     uint64_t seen = 0;                                                      // n_slots <= 64
     for (int g = 0; g < n_groups; ++g) {
         int enc_src, filled_src, start = 0;
-        if (decoder_slot_state(S, src_slots[g], &enc_src, &filled_src) || enc_src < 1) return (int)hipErrorInvalidValue;
+        if (decoder_slot_state(S, src_slots[g], &enc_src, &filled_src) || !decoder_slot_begun(S, src_slots[g]))
+            return (int)hipErrorInvalidValue;
         for (int q = 0; q < beams; ++q) {
             const int r = g * beams + q;
             int enc, filled;

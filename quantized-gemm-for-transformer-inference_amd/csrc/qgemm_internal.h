@@ -452,8 +452,11 @@ hipError_t outlier_prepare(const float *X, int64_t xsh, const float *W, int64_t 
 hipError_t outlier_finish(const float *X, int64_t xsh, const float *W, int64_t wsh, const PackedView *vb,
                           const float *bias, bool relu, int m, int n, int k, void *scratch, float *O, int64_t osh,
                           hipStream_t s);
-// The transformer stack (transformer.hip): an encoder is a stack without cross-attention, a decoder one with it.
-// encoder_forward refuses a stack with cross-attention and decoder_* one without (hipErrorInvalidValue).
+// The transformer stack (transformer.hip): an encoder is a stack without cross-attention, a decoder one with it, a
+// decoder-only stack (arch bit QGEMM_ARCH_DECODER_ONLY) a handle of the decoder family whose blocks
+// are the encoder's.  encoder_forward refuses a handle of the decoder family and decoder_* an encoder
+// (hipErrorInvalidValue).  stack_create's `decoder` names the family; without cross-attention enc_out is nullptr and
+// enc_seq 0 in decoder_forward / decoder_begin_slot, and begin launches nothing.
 struct Stack;
 uint64_t encoder_weight_seed(uint64_t base, int block, int kind, int head);
 float encoder_init_bound(int n);
@@ -461,7 +464,7 @@ float encoder_init_bound(int n);
 // the number of sequences the caches hold; max_rows (0: none) raises the rows the scratch buffers hold
 // for encoder_forward_batch / decoder_step_varlen, refused where a row-local index could leave int32
 hipError_t stack_create(int d_model, int n_heads, int d_ff, int n_blocks, int max_seq, int max_enc_seq, uint64_t seed,
-                        bool cross, bool causal, bool kv_cache, Stack **out, int n_slots = 1, int max_rows = 0,
+                        bool decoder, bool causal, bool kv_cache, Stack **out, int n_slots = 1, int max_rows = 0,
                         int arch = 0, int activation = 0, float ln_eps = 0.0f);
 void stack_destroy(Stack *S);
 hipError_t encoder_forward(Stack *S, const float *X, float *Y, int seq, hipStream_t s);
@@ -478,6 +481,8 @@ hipError_t decoder_step_varlen(Stack *S, int n_seqs, const int *slots, const int
                                float *Y, hipStream_t s);
 hipError_t decoder_copy_slot(Stack *S, int dst, int src, hipStream_t s);
 hipError_t decoder_slot_state(const Stack *S, int slot, int *enc_seq, int *filled);
+// whether the slot's sequence was begun (begin_slot, copy_slot, beam_begin) and no set_weight came since
+bool decoder_slot_begun(const Stack *S, int slot);
 // a slot's self slab (max_seq x 3 d_model) / cross slab (max_enc_seq x 2 d_model) of one block, copied out in stream order
 hipError_t decoder_read_slot(const Stack *S, int block, int slot, float *self_rows, float *cross_rows, hipStream_t s);
 // what a caller that drives step_batch must know to check its arguments before the first launch (head.hip's generate):
@@ -509,6 +514,14 @@ hipError_t stack_set_weight(Stack *S, int block, int kind, int head, const void 
                             hipStream_t s);
 hipError_t stack_packed_weight(const Stack *S, int block, int which, const void **packed, int *n, int *k);
 hipError_t stack_bias(const Stack *S, int block, int kind, const float **bias, int *n);
+hipError_t stack_rope_tables(const Stack *S, const float **cos_t, const float **sin_t, int *rows, int *half);
+// Rotary position embeddings (rope.hip; the contract is at qgemm_rope_rows in include/qgemm.h): every
+// check before the one launch; row0 / n_rows / pos0 are host arrays of n_seqs <= kVarlenMaxSeqs entries
+hipError_t launch_rope_rows(float *X, int64_t stride, int64_t rows, int groups, int dk, const float *cos_t,
+                            const float *sin_t, int table_rows, int pos0, hipStream_t s);
+hipError_t launch_rope_rows_varlen(float *X, int64_t stride, int groups, int dk, const float *cos_t, const float *sin_t,
+                                   int table_rows, int n_seqs, const int64_t *row0, const int *n_rows, const int *pos0,
+                                   hipStream_t s);
 // Sampled token choice (sample.hip; the contract is at qgemm_sample_rows in include/qgemm.h).
 // sample_plan: the parts a row is cut into and a part's columns, from rows, w and top_k alone; false outside
 // rows >= 0, 1 <= w <= 2^24, 1 <= top_k <= 1024.  sample_check: every limit of the contract that needs no pointer.
@@ -594,9 +607,10 @@ hipError_t launch_gelu_rows(const float *X, int64_t xsh, float *Y, int64_t ysh, 
 hipError_t launch_gelu_pack(const float *X, int64_t xsh, int m, int k, float range, PackedView out, hipStream_t stream);
 // transformer.hip: the architecture of a stack (stack_create's arch: 0 the reference's block, 1 the standard one with
 // its new tensors allocated and set, b_* = +0, gamma = 1, beta = +0; activation: 0 relu, 1 tanh GELU, arch 1 only;
-// arch 0x101 the pre-LN block and 0x301 the pre-LN block with a final norm, QGEMM_ARCH_NORM_FIRST / _FINAL_NORM);
+// arch 0x101 the pre-LN block and 0x301 the pre-LN block with a final norm, QGEMM_ARCH_NORM_FIRST / _FINAL_NORM;
+// 0x400 QGEMM_ARCH_DECODER_ONLY with cross alone, 0x800 QGEMM_ARCH_ROPE on the standard block alone);
 // stack_describe reads back what creation was given.
-bool stack_arch_ok(int arch);
+bool stack_arch_ok(int arch, bool cross);
 struct StackDesc {
     int cross, d_model, n_heads, d_ff, n_blocks, max_seq, max_enc_seq;
     uint64_t seed;

@@ -4,6 +4,10 @@
 // function, run_blocks, makes every pass over the blocks; what kind of pass it is and which architecture the blocks
 // have are each decided in one place.  Softmax and add + layernorm: encoder_ops.hip.  LayerNorm with gamma and beta
 // and the norm-first form: norm.hip.  The GELU pack: gelu.hip.  The attention launches: attention_launch.hip.
+// A decoder-only stack (QGEMM_ARCH_DECODER_ONLY) is a handle of the decoder family (S->decoder: what
+// the entry points' guards ask) whose blocks lack the cross-attention third (S->cross: what run_blocks, the weights and
+// the allocations ask): the encoder's blocks with the decoder's mask, caches and calls.  QGEMM_ARCH_ROPE adds ONE
+// launch per block, rope.hip's rotation of Q and K behind the QKV GEMM (rotate_qk).
 //
 // THE BLOCK, once and in order (run_blocks).  Every linear is pack_rows + the int8 GEMM with bias (and relu) in its
 // epilogue; a boundary packs its own output, so the linear behind it quantizes nothing itself.
@@ -125,19 +129,25 @@ enum WeightKind { kWq = 0, kWk = 1, kWv = 2, kWo = 3, kW1 = 4, kB1 = 5, kW2 = 6,
                   kBq = 12, kBk = 13, kBv = 14, kBo = 15, kG1 = 16, kBe1 = 17, kG3 = 18, kBe3 = 19,
                   kBq2 = 20, kBk2 = 21, kBv2 = 22, kBo2 = 23, kG2 = 24, kBe2 = 25,
                   // the final norm of a pre-LN stack, 1 x d_model each, block 0's
-                  kGf = 26, kBef = 27 };
+                  kGf = 26, kBef = 27,
+                  // the rotary tables of a ROPE stack, max_seq x d_k / 2 each, block 0's
+                  kRopeCos = 28, kRopeSin = 29 };
 
-// QGEMM_ARCH_NORM_FIRST / QGEMM_ARCH_FINAL_NORM (include/qgemm.h): modifier bits above the architecture's low byte
-constexpr int kArchNormFirst = 0x100, kArchFinalNorm = 0x200;
+// QGEMM_ARCH_NORM_FIRST / _FINAL_NORM / _DECODER_ONLY / _ROPE (include/qgemm.h): modifier bits above the
+// architecture's low byte
+constexpr int kArchNormFirst = 0x100, kArchFinalNorm = 0x200, kArchDecoderOnly = 0x400, kArchRope = 0x800;
 
 }  // namespace
 
 // arch as qgemm_model_create takes it: the reference's block or the standard one in the low byte; above it NORM_FIRST
-// on the standard block alone and FINAL_NORM with NORM_FIRST alone, and no other bit
-bool stack_arch_ok(int arch) {
+// and ROPE on the standard block alone, FINAL_NORM with NORM_FIRST alone, DECODER_ONLY on a descriptor of the decoder
+// family (cross = 1) alone, and no other bit
+bool stack_arch_ok(int arch, bool cross) {
     const int base = arch & 0xff, mods = arch & ~0xff;
-    if ((base != 0 && base != 1) || (mods & ~(kArchNormFirst | kArchFinalNorm))) return false;
-    if ((mods & kArchNormFirst) && base != 1) return false;
+    if ((base != 0 && base != 1) || (mods & ~(kArchNormFirst | kArchFinalNorm | kArchDecoderOnly | kArchRope)))
+        return false;
+    if ((mods & (kArchNormFirst | kArchRope)) && base != 1) return false;
+    if ((mods & kArchDecoderOnly) && !cross) return false;
     return !(mods & kArchFinalNorm) || (mods & kArchNormFirst);
 }
 
@@ -165,7 +175,10 @@ struct Block {
 
 struct Stack {
     int d_model = 0, n_heads = 0, d_ff = 0, n_blocks = 0, max_seq = 0, max_enc_seq = 0;
-    bool cross = false;     // the blocks have the cross-attention third: a decoder
+    bool decoder = false;   // the decoder family: the handle the decoder_* entry points take, with or without cross
+    bool cross = false;     // the blocks have the cross-attention third (a decoder-only stack: decoder without cross)
+    bool rope = false;      // Q and K are rotated by their rows' positions behind the QKV GEMM
+    float *rope_t = nullptr;  // rope: [cos: max_seq x d_k / 2][sin: the same], kinds 28 and 29
     bool causal = false;    // the self-attention masks keys past the query's own row (QGEMM_DECODER_CAUSAL)
     bool kv_cache = false;  // the blocks own caches for decoder_begin / decoder_step (QGEMM_DECODER_KV_CACHE)
     int n_slots = 1;        // sequences the caches hold side by side (qgemm_decoder_create_slots)
@@ -180,8 +193,9 @@ struct Stack {
     uint64_t seed = 0;      // as created, for stack_describe
     int max_rows = 0;
     int scratch_rows = 0;   // rows the scratch buffers hold: max_seq, 8 rows of every slot or max_rows, the largest
-    // per slot, host side, updated at enqueue time: enc_seq of the sequence begun (0: no begin yet) and the filled
-    // length (cache rows 0 .. filled - 1 hold the sequence so far)
+    // per slot, host side, updated at enqueue time: whether a sequence was begun, its enc_seq (0 without cross) and the
+    // filled length (cache rows 0 .. filled - 1 hold the sequence so far)
+    std::vector<char> begun;
     std::vector<int> enc_seq, filled;
     // the copy-free beam search, n_slots > 1 only: ONE row table for all blocks, n_slots x max_seq bytes
     // on the device, own[s][j] = the slot whose self slab holds row j of the sequence in slot s (the identity at
@@ -266,16 +280,21 @@ void stack_destroy(Stack *S) {
             (void)hipFree(p);
     for (void *p : {(void *)S->qkv, (void *)S->scores, (void *)S->heads, (void *)S->t, (void *)S->ffn, (void *)S->x,
                     (void *)S->q2, (void *)S->kv2, (void *)S->heads2, (void *)S->xa, (void *)S->xb, (void *)S->ws,
-                    (void *)S->own, (void *)S->fn})
+                    (void *)S->own, (void *)S->fn, (void *)S->rope_t})
         (void)hipFree(p);
     delete S;
 }
 
 hipError_t stack_create(int d_model, int n_heads, int d_ff, int n_blocks, int max_seq, int max_enc_seq, uint64_t seed,
-                        bool cross, bool causal, bool kv_cache, Stack **out, int n_slots, int max_rows, int arch,
+                        bool decoder, bool causal, bool kv_cache, Stack **out, int n_slots, int max_rows, int arch,
                         int activation, float ln_eps) {
     *out = nullptr;
-    if (!stack_arch_ok(arch) || (activation != 0 && activation != 1) || ((arch & 0xff) == 0 && activation != 0) ||
+    // decoder: the family the handle belongs to; cross: whether its blocks have the cross-attention third.  A
+    // decoder-only stack is of the decoder family, has the encoder's blocks and no encoder output to size anything by
+    const bool cross = decoder && !(arch & kArchDecoderOnly);
+    if (decoder && !cross && max_enc_seq != 0) return hipErrorInvalidValue;
+    if ((arch & kArchRope) && (n_heads < 1 || d_model % n_heads || (d_model / n_heads) % 2)) return hipErrorInvalidValue;
+    if (!stack_arch_ok(arch, decoder) || (activation != 0 && activation != 1) || ((arch & 0xff) == 0 && activation != 0) ||
         !(ln_eps >= 0.0f) || (activation == 1 && d_ff > 16384))  // (the GELU pack's row limit)
         return hipErrorInvalidValue;
     // max_rows: the row-local kernels (pack, GEMM epilogue, add + layernorm) address an activation buffer of
@@ -286,7 +305,7 @@ hipError_t stack_create(int d_model, int n_heads, int d_ff, int n_blocks, int ma
         (((int64_t)max_rows + 255) & ~(int64_t)255) * (((int64_t)std::max(3 * (int64_t)d_model, (int64_t)d_ff) + 127) & ~(int64_t)127) > INT32_MAX)
         return hipErrorInvalidValue;
     if (kv_cache && !causal) return hipErrorInvalidValue;
-    if (n_slots < 1 || n_slots > kDecodeMaxBatch || (n_slots > 1 && !(cross && kv_cache))) return hipErrorInvalidValue;
+    if (n_slots < 1 || n_slots > kDecodeMaxBatch || (n_slots > 1 && !(decoder && kv_cache))) return hipErrorInvalidValue;
     if (d_model < 2 || n_heads < 1 || d_model % n_heads || d_ff < 2 || n_blocks < 1 || max_seq < 1 || max_seq > 4096 ||
         (cross && (max_enc_seq < 1 || max_enc_seq > 4096)) || d_model > 4096)
         return hipErrorInvalidValue;
@@ -298,7 +317,9 @@ hipError_t stack_create(int d_model, int n_heads, int d_ff, int n_blocks, int ma
     S->n_blocks = n_blocks;
     S->max_seq = max_seq;
     S->max_enc_seq = cross ? max_enc_seq : 0;
+    S->decoder = decoder;
     S->cross = cross;
+    S->rope = (arch & kArchRope) != 0;
     S->causal = causal;
     S->kv_cache = kv_cache;
     S->n_slots = n_slots;
@@ -314,6 +335,7 @@ hipError_t stack_create(int d_model, int n_heads, int d_ff, int n_blocks, int ma
     // and a batched forward or a varlen step its row budget (qgemm_*_create_rows)
     S->scratch_rows = std::max(n_slots > 1 ? std::max(max_seq, 8 * n_slots) : max_seq, max_rows);
     S->enc_seq.assign(n_slots, 0);
+    S->begun.assign(n_slots, 0);
     S->filled.assign(n_slots, 0);
     S->indirect.assign(n_slots, 0);
     S->own_rows.assign(n_slots, 0);
@@ -384,7 +406,7 @@ hipError_t stack_create(int d_model, int n_heads, int d_ff, int n_blocks, int ma
         if ((e = encoder_make_packed(d_ff, d, {encoder_weight_seed(seed, i, kW2, 0)}, d, bf, &B.w2, tmp, s))) break;
         if ((e = alloc_f(&B.b1, d_ff)) || (e = alloc_f(&B.b2, d))) break;
         if (kv_cache && ((e = alloc_f(&B.qkv_cache, (size_t)n_slots * max_seq * 3 * d)) ||
-                         (e = alloc_f(&B.kv2_cache, (size_t)n_slots * Se * 2 * d))))
+                         (cross && (e = alloc_f(&B.kv2_cache, (size_t)n_slots * Se * 2 * d)))))
             break;
         if ((e = launch_fill_uniform(B.b1, d_ff, encoder_weight_seed(seed, i, kB1, 0), -bd, bd, s))) break;
         if ((e = launch_fill_uniform(B.b2, d, encoder_weight_seed(seed, i, kB2, 0), -bf, bf, s))) break;
@@ -406,6 +428,20 @@ hipError_t stack_create(int d_model, int n_heads, int d_ff, int n_blocks, int ma
         std::fill_n(host.begin(), d, 1.0f);
         if (!(e = alloc_f(&S->fn, host.size())))
             e = hipMemcpy(S->fn, host.data(), sizeof(float) * host.size(), hipMemcpyHostToDevice);
+    }
+    if (e == hipSuccess && S->rope) {  // theta = 10000, in double on the host; set_weight brings any other table
+        const int h = dk / 2;
+        std::vector<float> host(2 * (size_t)max_seq * h);
+        float *c = host.data(), *sn = c + (size_t)max_seq * h;
+        for (int i = 0; i < h; ++i) {
+            const double inv = std::pow(10000.0, -2.0 * i / dk);
+            for (int p = 0; p < max_seq; ++p) {
+                c[(size_t)p * h + i] = (float)std::cos((double)p * inv);
+                sn[(size_t)p * h + i] = (float)std::sin((double)p * inv);
+            }
+        }
+        if (!(e = alloc_f(&S->rope_t, host.size())))
+            e = hipMemcpy(S->rope_t, host.data(), sizeof(float) * host.size(), hipMemcpyHostToDevice);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     (void)hipFree(tmp);
@@ -500,6 +536,34 @@ hipError_t scatter_new_kv(Stack &S, const Block &B, const Pass &p, hipStream_t s
     return launch_scatter_kv(S.qkv, S.scratch_rows, B.qkv_cache, S.max_seq, S.n_slots, S.d_model, p.n_seqs, p.scatter, s);
 }
 
+// RoPE (rope.hip): the Q and K thirds of the pass's new rows, where the QKV GEMM wrote them, rotated in
+// place by each row's absolute position -- ONE launch: the thirds are adjacent, so a row is 2 n_heads groups of d_k
+// floats at stride 3 d_model; V is not touched.  Row-local and a function of the row's own position alone, so the
+// header's argument for the pass kinds carries over.  A forward's sequence starts at position 0, and so does every
+// sequence of a batched forward (self_pos0 = 0 there); a step's rows stand at pos ..
+hipError_t rotate_qk(Stack &S, const Block &B, const Pass &p, hipStream_t s) {
+    const int d = S.d_model, H = S.n_heads, dk = d / H;
+    const float *cos_t = S.rope_t, *sin_t = S.rope_t + (size_t)S.max_seq * (dk / 2);
+    float *rows = qkv_rows(S, B, p);
+    int64_t row0[kDecodeMaxBatch];
+    int n_rows[kDecodeMaxBatch];
+    switch (p.kind) {
+        case PassKind::Forward:
+        case PassKind::Slot:
+            return launch_rope_rows(rows, 3 * d, p.rows, 2 * H, dk, cos_t, sin_t, S.max_seq,
+                                    p.kind == PassKind::Slot ? p.pos : 0, s);
+        case PassKind::Batch:
+        case PassKind::BatchIndirect:
+            for (int b = 0; b < p.n_seqs; ++b) row0[b] = (int64_t)b * p.rows_per_seq, n_rows[b] = p.rows_per_seq;
+            return launch_rope_rows_varlen(rows, 3 * d, 2 * H, dk, cos_t, sin_t, S.max_seq, p.n_seqs, row0, n_rows,
+                                           p.self.q_pos0, s);
+        case PassKind::Varlen:
+            return launch_rope_rows_varlen(rows, 3 * d, 2 * H, dk, cos_t, sin_t, S.max_seq, p.n_seqs, p.row0, p.n_rows,
+                                           p.self_pos0, s);
+    }
+    return hipErrorInvalidValue;
+}
+
 // S_h = Q_h K_h^T, P_h = softmax(S_h * 1/sqrt(d_k)), heads[:, h*d_v..] = P_h V_h, Q, K and V the thirds of the rows that
 // the QKV GEMM wrote (causal: row i sees rows 0 .. i, so row i of the forward depends on rows 0 .. i of X alone)
 hipError_t self_attention(Stack &S, const Block &B, const Pass &p, hipStream_t s) {
@@ -507,6 +571,8 @@ hipError_t self_attention(Stack &S, const Block &B, const Pass &p, hipStream_t s
     const int64_t slab = (int64_t)S.max_seq * 3 * d;  // floats
     const float scale = attention_scale(S);
     const float *cache = B.qkv_cache;  // [Q | K | V] rows of slab 0 (the step kinds)
+    if (S.rope)  // before the scatter: the caches hold rotated K
+        if (const hipError_t e = rotate_qk(S, B, p, s)) return e;
     switch (p.kind) {
         case PassKind::Forward:
             return launch_attention(S.qkv, 3 * d, S.qkv + d, 3 * d, S.qkv + 2 * d, 3 * d, S.heads, d, p.rows, p.rows, H, dk,
@@ -668,12 +734,17 @@ hipError_t pack_enc(Stack *S, const float *enc_out, int enc_seq, hipStream_t s) 
     return launch_pack_rows(enc_out, S->d_model, 1, enc_seq, S->d_model, 127.0f, enc_view(*S, enc_seq), s);
 }
 
+// the encoder output a forward or a begin is given: enc_seq rows with cross-attention, nothing at all without it
+bool enc_out_ok(const Stack *S, const float *enc_out, int enc_seq) {
+    return S->cross ? enc_out && enc_seq >= 1 && enc_seq <= S->max_enc_seq : !enc_out && enc_seq == 0;
+}
+
 // ---- what the step entry points share --------------------------------------------------------------------------------
 // May slot sl take n rows at pos in this step?  In range, begun, its slab its own sequence's or (indirect) a beam's as
 // the call needs it, not named before in this call (seen, a bit per slot: n_slots <= 64), 0 <= pos <= filled, and room
 // for the rows.  Every entry point runs it for all its sequences before its first launch
 bool admit(const Stack *S, int sl, bool indirect, uint64_t &seen, int pos, int n) {
-    if (sl < 0 || sl >= S->n_slots || S->enc_seq[sl] < 1 || (S->indirect[sl] != 0) != indirect || (seen >> sl & 1) ||
+    if (sl < 0 || sl >= S->n_slots || !S->begun[sl] || (S->indirect[sl] != 0) != indirect || (seen >> sl & 1) ||
         n < 1 || pos < 0 || pos > S->filled[sl] || n > S->max_seq - pos)
         return false;
     seen |= (uint64_t)1 << sl;
@@ -693,14 +764,14 @@ void set_filled(Stack *S, int n_seqs, const ScatterTable &t) {
 }  // namespace
 
 hipError_t encoder_forward(Stack *S, const float *X, float *Y, int seq, hipStream_t s) {
-    if (!S || S->cross || !X || !Y || seq < 1 || seq > S->max_seq) return hipErrorInvalidValue;
+    if (!S || S->decoder || !X || !Y || seq < 1 || seq > S->max_seq) return hipErrorInvalidValue;
     return run_blocks(S, Pass{PassKind::Forward, seq, 1, seq}, X, Y, s);
 }
 
 // X and Y: the sequences' rows packed one after another.  Every row-local step of run_blocks sees one matrix of
 // sum seq_lens rows; the self-attention alone knows where a sequence ends
 hipError_t encoder_forward_batch(Stack *S, const float *X, float *Y, int n_seqs, const int *seq_lens, hipStream_t s) {
-    if (!S || S->cross || !X || !Y || !seq_lens || n_seqs < 1 || n_seqs > kVarlenMaxSeqs) return hipErrorInvalidValue;
+    if (!S || S->decoder || !X || !Y || !seq_lens || n_seqs < 1 || n_seqs > kVarlenMaxSeqs) return hipErrorInvalidValue;
     Pass p = {PassKind::Varlen, 0, n_seqs};  // (kv_in_slabs = false: a sequence's keys are its own rows of the scratch)
     int64_t rows = 0;
     for (int b = 0; b < n_seqs; ++b) {
@@ -716,25 +787,25 @@ hipError_t encoder_forward_batch(Stack *S, const float *X, float *Y, int n_seqs,
 
 hipError_t decoder_forward(Stack *S, const float *X, const float *enc_out, float *Y, int seq, int enc_seq,
                            hipStream_t s) {
-    if (!S || !S->cross || !X || !enc_out || !Y || seq < 1 || seq > S->max_seq || enc_seq < 1 ||
-        enc_seq > S->max_enc_seq)
+    if (!S || !S->decoder || !X || !Y || seq < 1 || seq > S->max_seq || !enc_out_ok(S, enc_out, enc_seq))
         return hipErrorInvalidValue;
-    const hipError_t e = pack_enc(S, enc_out, enc_seq, s);
-    if (e) return e;
+    if (S->cross)
+        if (const hipError_t e = pack_enc(S, enc_out, enc_seq, s)) return e;
     return run_blocks(S, Pass{PassKind::Forward, seq, 1, seq, enc_seq}, X, Y, s);
 }
 
+// (a decoder-only stack: no launch -- the slot is begun, empty and its own)
 hipError_t decoder_begin_slot(Stack *S, int slot, const float *enc_out, int enc_seq, hipStream_t s) {
-    if (!S || !S->cross || !S->kv_cache || slot < 0 || slot >= S->n_slots || !enc_out || enc_seq < 1 ||
-        enc_seq > S->max_enc_seq)
+    if (!S || !S->decoder || !S->kv_cache || slot < 0 || slot >= S->n_slots || !enc_out_ok(S, enc_out, enc_seq))
         return hipErrorInvalidValue;
     const int d = S->d_model;
-    hipError_t e = pack_enc(S, enc_out, enc_seq, s);
+    hipError_t e = S->cross ? pack_enc(S, enc_out, enc_seq, s) : hipSuccess;
     if (e) return e;
     for (const Block &B : S->blocks)
-        if ((e = gemm(*S, enc_view(*S, enc_seq), enc_seq, d, B.wkv2, 2 * d,
-                      B.kv2_cache + (int64_t)slot * S->max_enc_seq * 2 * d, B.bkv2, false, s)))
+        if (S->cross && (e = gemm(*S, enc_view(*S, enc_seq), enc_seq, d, B.wkv2, 2 * d,
+                                  B.kv2_cache + (int64_t)slot * S->max_enc_seq * 2 * d, B.bkv2, false, s)))
             return e;
+    S->begun[slot] = 1;
     S->enc_seq[slot] = enc_seq;
     S->filled[slot] = 0;
     S->indirect[slot] = 0;  // the slab is the slot's own again (rows 0 .. filled - 1: none)
@@ -743,7 +814,7 @@ hipError_t decoder_begin_slot(Stack *S, int slot, const float *enc_out, int enc_
 
 hipError_t decoder_step_slot(Stack *S, int slot, const float *X, float *Y, int pos, int n, hipStream_t s) {
     uint64_t seen = 0;
-    if (!S || !S->cross || !S->kv_cache || !X || !Y || !admit(S, slot, /*indirect=*/false, seen, pos, n))
+    if (!S || !S->decoder || !S->kv_cache || !X || !Y || !admit(S, slot, /*indirect=*/false, seen, pos, n))
         return hipErrorInvalidValue;
     const hipError_t e = run_blocks(S, Pass{PassKind::Slot, n, 1, n, S->enc_seq[slot], slot, pos}, X, Y, s);
     if (e) return e;
@@ -753,7 +824,7 @@ hipError_t decoder_step_slot(Stack *S, int slot, const float *X, float *Y, int p
 
 hipError_t decoder_step_batch(Stack *S, int n_seqs, const int *slots, const int *pos, int rows_per_seq, const float *X,
                               float *Y, hipStream_t s) {
-    if (!S || !S->cross || !S->kv_cache || !slots || !pos || !X || !Y || n_seqs < 1 || n_seqs > S->n_slots ||
+    if (!S || !S->decoder || !S->kv_cache || !slots || !pos || !X || !Y || n_seqs < 1 || n_seqs > S->n_slots ||
         rows_per_seq < 1 || rows_per_seq > 8)
         return hipErrorInvalidValue;
     const int r = rows_per_seq;
@@ -780,7 +851,7 @@ hipError_t decoder_step_batch(Stack *S, int n_seqs, const int *slots, const int 
 // of X / Y) at pos[b] of slot slots[b].  Every check comes before the first launch; `filled` is updated at enqueue.
 hipError_t decoder_step_varlen(Stack *S, int n_seqs, const int *slots, const int *pos, const int *n_rows, const float *X,
                                float *Y, hipStream_t s) {
-    if (!S || !S->cross || !S->kv_cache || !slots || !pos || !n_rows || !X || !Y || n_seqs < 1 || n_seqs > S->n_slots)
+    if (!S || !S->decoder || !S->kv_cache || !slots || !pos || !n_rows || !X || !Y || n_seqs < 1 || n_seqs > S->n_slots)
         return hipErrorInvalidValue;
     Pass p = {PassKind::Varlen, 0, n_seqs};
     p.kv_in_slabs = true;
@@ -810,8 +881,8 @@ hipError_t decoder_step_varlen(Stack *S, int n_seqs, const int *slots, const int
 // rows 0 .. filled - 1 of every block's self cache and rows 0 .. enc_seq - 1 of its cross cache, device to device in
 // stream order: dst then continues src's sequence on its own (beam search)
 hipError_t decoder_copy_slot(Stack *S, int dst, int src, hipStream_t s) {
-    if (!S || !S->cross || !S->kv_cache || dst < 0 || dst >= S->n_slots || src < 0 || src >= S->n_slots || dst == src ||
-        S->enc_seq[src] < 1 || S->indirect[src])
+    if (!S || !S->decoder || !S->kv_cache || dst < 0 || dst >= S->n_slots || src < 0 || src >= S->n_slots || dst == src ||
+        !S->begun[src] || S->indirect[src])
         return hipErrorInvalidValue;
     const int64_t d = S->d_model, self_slab = S->max_seq * 3 * d, cross_slab = S->max_enc_seq * 2 * d;
     const size_t self_bytes = sizeof(float) * (size_t)S->filled[src] * 3 * d;
@@ -821,11 +892,12 @@ hipError_t decoder_copy_slot(Stack *S, int dst, int src, hipStream_t s) {
         if (self_bytes && (e = hipMemcpyAsync(B.qkv_cache + dst * self_slab, B.qkv_cache + src * self_slab, self_bytes,
                                               hipMemcpyDeviceToDevice, s)))
             return e;
-        if ((e = hipMemcpyAsync(B.kv2_cache + dst * cross_slab, B.kv2_cache + src * cross_slab, cross_bytes,
-                                hipMemcpyDeviceToDevice, s)))
+        if (S->cross && (e = hipMemcpyAsync(B.kv2_cache + dst * cross_slab, B.kv2_cache + src * cross_slab, cross_bytes,
+                                            hipMemcpyDeviceToDevice, s)))
             return e;
     }
     S->enc_seq[dst] = S->enc_seq[src];
+    S->begun[dst] = 1;
     S->filled[dst] = S->filled[src];
     return hipSuccess;
 }
@@ -835,7 +907,7 @@ hipError_t decoder_copy_slot(Stack *S, int dst, int src, hipStream_t s) {
 // kernel (beam.hip), one launch per block.  Every check comes before the first launch; `filled` moves at enqueue.
 hipError_t decoder_gather_slots(Stack *S, int n_groups, int beams, const int *dst_slots, const int *src_slots,
                                 const int *parents, const int *n_rows, hipStream_t s) {
-    if (!S || !S->cross || !S->kv_cache || !dst_slots || !src_slots || !parents || !n_rows || n_groups < 1 ||
+    if (!S || !S->decoder || !S->kv_cache || !dst_slots || !src_slots || !parents || !n_rows || n_groups < 1 ||
         beams < 1 || beams > 8 || (int64_t)n_groups * beams > kDecodeMaxBatch)
         return hipErrorInvalidValue;
     uint64_t is_dst = 0, is_src = 0;  // n_slots <= 64
@@ -843,7 +915,7 @@ hipError_t decoder_gather_slots(Stack *S, int n_groups, int beams, const int *ds
         if (n_rows[g] < 0 || n_rows[g] > S->max_seq) return hipErrorInvalidValue;
         for (int q = 0; q < beams; ++q) {
             const int ds = dst_slots[g * beams + q], ss = src_slots[g * beams + q];
-            if (ds < 0 || ds >= S->n_slots || ss < 0 || ss >= S->n_slots || S->enc_seq[ds] < 1 || S->enc_seq[ss] < 1 ||
+            if (ds < 0 || ds >= S->n_slots || ss < 0 || ss >= S->n_slots || !S->begun[ds] || !S->begun[ss] ||
                 S->indirect[ss] || (is_dst >> ds & 1) || n_rows[g] > S->filled[ss] ||
                 S->enc_seq[ds] != S->enc_seq[src_slots[g * beams]] || S->enc_seq[ss] != S->enc_seq[src_slots[g * beams]])
                 return hipErrorInvalidValue;
@@ -865,7 +937,7 @@ hipError_t decoder_gather_slots(Stack *S, int n_groups, int beams, const int *ds
 // ---- the copy-free beam search: the row table's three operations ----------------------------------
 namespace {
 
-bool has_table(const Stack *S) { return S && S->cross && S->kv_cache && S->own; }
+bool has_table(const Stack *S) { return S && S->decoder && S->kv_cache && S->own; }
 
 // rows = n_groups * beams places in all, within the table kernels' 64
 bool beam_places_ok(int n_groups, int beams) {
@@ -889,7 +961,7 @@ hipError_t decoder_beam_begin(Stack *S, int n_groups, int beams, const int *slot
     uint64_t seen = 0;  // n_slots <= 64
     for (int g = 0; g < n_groups; ++g) {
         const int src = src_slots[g];
-        if (src < 0 || src >= S->n_slots || S->enc_seq[src] < 1 || pos[g] < 0 || pos[g] > plain_rows(S, src))
+        if (src < 0 || src >= S->n_slots || !S->begun[src] || pos[g] < 0 || pos[g] > plain_rows(S, src))
             return hipErrorInvalidValue;
         for (int q = 0; q < beams; ++q) {
             const int i = g * beams + q, sl = slots[i];
@@ -909,6 +981,7 @@ hipError_t decoder_beam_begin(Stack *S, int n_groups, int beams, const int *slot
             const int sl = slots[g * beams + q];
             S->own_rows[sl] = sl == src_slots[g] ? pos[g] : 0;  // (rows at or past pos: the search's to overwrite)
             S->enc_seq[sl] = S->enc_seq[src_slots[g]];
+            S->begun[sl] = 1;
             S->filled[sl] = pos[g];
             S->indirect[sl] = 1;
         }
@@ -930,7 +1003,7 @@ hipError_t decoder_step_batch_indirect(Stack *S, int n_seqs, const int *slots, c
     for (int b = 0; b < n_seqs; ++b) {
         const int sl = slots[b], cs = cross_slots[b];
         // (a beam's slot carries its prompt's enc_seq, so "begun" is the cross slot's: begun, and the same enc_seq)
-        if (!admit(S, sl, /*indirect=*/true, seen, pos[b], r) || cs < 0 || cs >= S->n_slots || S->enc_seq[cs] < 1 ||
+        if (!admit(S, sl, /*indirect=*/true, seen, pos[b], r) || cs < 0 || cs >= S->n_slots || !S->begun[cs] ||
             S->enc_seq[cs] != S->enc_seq[sl])
             return hipErrorInvalidValue;
         p.self.kv_slot[b] = sl;
@@ -978,17 +1051,23 @@ bool decoder_slot_indirect(const Stack *S, int slot) {
 }
 
 hipError_t decoder_slot_state(const Stack *S, int slot, int *enc_seq, int *filled) {
-    if (!S || !S->cross || !S->kv_cache || slot < 0 || slot >= S->n_slots) return hipErrorInvalidValue;
+    if (!S || !S->decoder || !S->kv_cache || slot < 0 || slot >= S->n_slots) return hipErrorInvalidValue;
     if (enc_seq) *enc_seq = S->enc_seq[slot];
     if (filled) *filled = S->filled[slot];
     return hipSuccess;
+}
+
+// whether the slot's sequence was begun (with cross-attention: enc_seq >= 1); false out of range
+bool decoder_slot_begun(const Stack *S, int slot) {
+    return S && S->decoder && S->kv_cache && slot >= 0 && slot < S->n_slots && S->begun[slot];
 }
 
 // a slot's slabs as they are, device to device in stream order: block `block`'s self slab (max_seq x 3 d_model) into
 // self_rows and its cross slab (max_enc_seq x 2 d_model) into cross_rows, either may be nullptr.  For inspection:
 // what a reorder wrote and what it left alone cannot be seen through step's output alone.
 hipError_t decoder_read_slot(const Stack *S, int block, int slot, float *self_rows, float *cross_rows, hipStream_t s) {
-    if (!S || !S->cross || !S->kv_cache || block < 0 || block >= S->n_blocks || slot < 0 || slot >= S->n_slots)
+    if (!S || !S->decoder || !S->kv_cache || block < 0 || block >= S->n_blocks || slot < 0 || slot >= S->n_slots ||
+        (cross_rows && !S->cross))
         return hipErrorInvalidValue;
     const int64_t d = S->d_model, self_slab = S->max_seq * 3 * d, cross_slab = S->max_enc_seq * 2 * d;
     const Block &B = S->blocks[block];
@@ -1003,7 +1082,7 @@ hipError_t decoder_read_slot(const Stack *S, int block, int slot, float *self_ro
 }
 
 hipError_t decoder_limits(const Stack *S, int *d_model, int *d_k, int *max_seq, int *n_slots) {
-    if (!S || !S->cross || !S->kv_cache) return hipErrorInvalidValue;
+    if (!S || !S->decoder || !S->kv_cache) return hipErrorInvalidValue;
     *d_model = S->d_model;
     *d_k = S->d_model / S->n_heads;
     *max_seq = S->max_seq;
@@ -1023,6 +1102,7 @@ struct WeightPlace {
 };
 
 bool weight_kind_ok(const Stack *S, int kind) {
+    if (kind >= kRopeCos) return S->rope && kind <= kRopeSin;  // the rotary tables of a stack that has them
     if (kind >= kGf) return S->final_norm && kind <= kBef;  // the final norm of a pre-LN stack that has one
     if (kind >= kBq) return S->standard && kind <= (S->cross ? kBe2 : kBe3);  // a reference stack lacks them
     return kind >= kWq && kind <= (S->cross ? kWo2 : kB2);
@@ -1043,6 +1123,9 @@ bool weight_place(const Stack *S, const Block &B, int kind, int head, WeightPlac
         case kWk2: case kWv2: *p = {B.wkv2, nullptr, d, 2 * d, (kind - kWk2) * d + head * dk, dk}; break;
         case kWo2: *p = {B.wo2, nullptr, d, d, 0, d}; break;
         case kGf: case kBef: *p = {nullptr, S->fn + (size_t)(kind - kGf) * d, 1, d, 0, d}; break;  // the stack's own
+        case kRopeCos: case kRopeSin:  // max_seq rows of d_k / 2 floats, row after row
+            *p = {nullptr, S->rope_t + (size_t)(kind - kRopeCos) * S->max_seq * (dk / 2), S->max_seq, dk / 2, 0, dk / 2};
+            break;
         // the standard architecture's vectors, 1 x d_model each: B.sp holds them in the order of their kinds
         default: *p = {nullptr, B.sp + (size_t)(kind - kBq) * d, 1, d, 0, d}; break;
     }
@@ -1072,12 +1155,19 @@ hipError_t stack_set_weight(Stack *S, int block, int kind, int head, const void 
     if (!S || block < 0 || block >= S->n_blocks || !W || (dtype != 0 && dtype != 1) || sh < 0 || sw < 0 ||
         (kind >= kGf && block != 0) || !weight_place(S, S->blocks[block], kind, head, &p))
         return hipErrorInvalidValue;
-    const hipError_t e = p.bias ? launch_copy_row(W, dtype, sw, p.ncols, p.bias, s)
-                                : launch_pack_b_window(W, dtype, sh, sw, p.k, p.n_total, p.col0, p.ncols, 127.0f,
-                                                       p.packed, s);
+    hipError_t e = hipSuccess;
+    if (p.bias) {  // a bias is one row; a rotary table max_seq of them, one copy each
+        const int64_t row_bytes = sh * (dtype == 1 ? 2 : 4);
+        for (int r = 0; r < p.k && !e; ++r)
+            e = launch_copy_row(static_cast<const char *>(W) + r * row_bytes, dtype, sw, p.ncols,
+                                p.bias + (size_t)r * p.ncols, s);
+    } else {
+        e = launch_pack_b_window(W, dtype, sh, sw, p.k, p.n_total, p.col0, p.ncols, 127.0f, p.packed, s);
+    }
     if (e) return e;
     if (S->kv_cache) {
         S->enc_seq.assign(S->n_slots, 0);
+        S->begun.assign(S->n_slots, 0);
         S->filled.assign(S->n_slots, 0);
         S->indirect.assign(S->n_slots, 0);
         S->own_rows.assign(S->n_slots, 0);
@@ -1105,7 +1195,7 @@ hipError_t stack_packed_weight(const Stack *S, int block, int which, const void 
 // block 0's), n floats on the device
 hipError_t stack_bias(const Stack *S, int block, int kind, const float **bias, int *n) {
     WeightPlace p;
-    if (!S || block < 0 || block >= S->n_blocks || !bias || (kind >= kGf && block != 0) ||
+    if (!S || block < 0 || block >= S->n_blocks || !bias || (kind >= kGf && block != 0) || kind >= kRopeCos ||
         !weight_place(S, S->blocks[block], kind, 0, &p) || !p.bias)
         return hipErrorInvalidValue;
     *bias = p.bias;
@@ -1113,10 +1203,21 @@ hipError_t stack_bias(const Stack *S, int block, int kind, const float **bias, i
     return hipSuccess;
 }
 
+// ... and the rotary tables (kinds 28, 29) of a ROPE stack: rows x half floats each, on the device
+hipError_t stack_rope_tables(const Stack *S, const float **cos_t, const float **sin_t, int *rows, int *half) {
+    if (!S || !S->rope || !cos_t || !sin_t) return hipErrorInvalidValue;
+    const int h = S->d_model / S->n_heads / 2;
+    *cos_t = S->rope_t;
+    *sin_t = S->rope_t + (size_t)S->max_seq * h;
+    if (rows) *rows = S->max_seq;
+    if (half) *half = h;
+    return hipSuccess;
+}
+
 hipError_t stack_describe(const Stack *S, StackDesc *out) {
     if (!S || !out) return hipErrorInvalidValue;
     // (QGEMM_DECODER_CAUSAL = 1, QGEMM_DECODER_KV_CACHE = 8, include/qgemm.h)
-    *out = StackDesc{S->cross, S->d_model, S->n_heads, S->d_ff, S->n_blocks, S->max_seq, S->max_enc_seq, S->seed,
+    *out = StackDesc{S->decoder, S->d_model, S->n_heads, S->d_ff, S->n_blocks, S->max_seq, S->max_enc_seq, S->seed,
                      (S->causal ? 1 : 0) | (S->kv_cache ? 8 : 0), S->n_slots, S->max_rows, S->arch,
                      S->gelu ? 1 : 0, S->ln_eps};
     return hipSuccess;
