@@ -7,7 +7,6 @@ search runs the causal decoder oracle on every live beam's whole prefix.
 """
 import numpy as np
 
-import causal_oracle
 import head_oracle
 from oracle import oracle as O
 
@@ -105,11 +104,14 @@ def beam_step_ref(S, beams, scores_in=None, prev=None, eos=-1):
     return parents, tokens, scores
 
 
-def generate_beam_ref(prefixes, encs, tokens_in, n_new, beams, E, W, bias, P, dims, seed, scores_in=None, eos=-1):
+def generate_beam_ref(prefixes, encs, tokens_in, n_new, beams, E, W, bias, P, dims, seed, scores_in=None, eos=-1,
+                      forward=None):
     """The whole search on whole prefixes: group g starts from prefixes[g] (rows x d_model, may be empty) with encoder
     output encs[g]; every live beam keeps its own input rows, the causal decoder oracle runs on all of them at every
     step, its last row goes through oracle.linear and beam_step_ref chooses.  tokens_in: one token per row.  Returns
-    (tokens, parents, scores), each n_new x rows, and the final input rows of every place (None for a dead one)."""
+    (tokens, parents, scores), each n_new x rows, and the final input rows of every place (None for a dead one).
+    forward: the model as a callable (X, enc) -> hidden rows, head_oracle.generate_ref's."""
+    model = head_oracle.model_forward(dims, seed, forward)
     n_groups = len(prefixes)
     rows = n_groups * beams
     d, vocab = dims[0], np.asarray(W).shape[1]
@@ -125,7 +127,7 @@ def generate_beam_ref(prefixes, encs, tokens_in, n_new, beams, E, W, bias, P, di
         for r in range(rows):
             X[r] = np.concatenate([X[r], head_oracle.embed_rows_ref(E, [int(tok[r])], P, [X[r].shape[0]])])
             if live[r] and not (eos >= 0 and int(tok[r]) == eos):
-                H = causal_oracle.decoder_forward_causal_ref(X[r], encs[r // beams], *dims, seed)[-1:]
+                H = model(X[r], encs[r // beams])[-1:]
                 logits[r] = O.linear(np.ascontiguousarray(H), W, bias)[0]
         par, ntok, nsc = beam_step_ref(logits, beams, sc, tok, eos)
         X = [X[r // beams * beams + int(par[r])] for r in range(rows)]

@@ -47,17 +47,27 @@ def embed_rows_ref(E, tokens, P=None, pos=None, rows_per_seq=1):
     return Y
 
 
-def generate_ref(prefix, enc, token_in, n_new, E, W, bias, P, dims, seed):
+def model_forward(dims, seed, forward=None):
+    """The model of a whole-search oracle as a callable (X, enc) -> hidden rows on the whole input rows of one
+    sequence: `forward` where given (any stack architecture: tests/stack_cases.py), else the reference block with
+    seeded weights, causal_oracle.decoder_forward_causal_ref(X, enc, *dims, seed)."""
+    if forward is not None:
+        return forward
+    return lambda X, enc: causal_oracle.decoder_forward_causal_ref(X, enc, *dims, seed)
+
+
+def generate_ref(prefix, enc, token_in, n_new, E, W, bias, P, dims, seed, forward=None):
     """Greedy decoding of ONE sequence: `prefix` (rows x d_model, may be empty) are the input rows already fed; then
     token by token the embedding of the last token is appended, the causal decoder runs on the WHOLE prefix
-    (causal_oracle.decoder_forward_causal_ref), its last row goes through oracle.linear onto the vocabulary and
-    argmax_rows_ref picks the next token.  Returns the n_new tokens."""
+    (model_forward: causal_oracle.decoder_forward_causal_ref unless `forward` is given), its last row goes through
+    oracle.linear onto the vocabulary and argmax_rows_ref picks the next token.  Returns the n_new tokens."""
+    model = model_forward(dims, seed, forward)
     X = np.ascontiguousarray(prefix, dtype=np.float32).reshape(-1, dims[0])
     out, tok = [], int(token_in)
     for _ in range(n_new):
         row = embed_rows_ref(E, [tok], P, [X.shape[0]])
         X = np.concatenate([X, row])
-        H = causal_oracle.decoder_forward_causal_ref(X, enc, *dims, seed)[-1:]
+        H = model(X, enc)[-1:]
         tok = int(argmax_rows_ref(O.linear(np.ascontiguousarray(H), W, bias))[0][0])
         out.append(tok)
     return out

@@ -7,7 +7,6 @@ loop; the draw is the oracle's oracle_uniform_at.
 """
 import numpy as np
 
-import causal_oracle
 import head_oracle
 from oracle import oracle as O
 
@@ -98,15 +97,16 @@ def sample_rows_ref(S, top_k, top_p=1.0, temperature=1.0, seed=0, counter0=0, co
 
 
 def generate_sampled_ref(prefix, enc, token_in, n_new, E, W, bias, P, dims, seed, top_k, top_p, temperature,
-                         sample_seed, stream, eos=None):
+                         sample_seed, stream, eos=None, forward=None):
     """head_oracle.generate_ref with sample_rows_ref in argmax_rows_ref's place: ONE sequence, the draw of the step that
-    feeds position q made with the counter (stream << 32) + q, the token fed as prev."""
+    feeds position q made with the counter (stream << 32) + q, the token fed as prev.  forward: as generate_ref's."""
+    model = head_oracle.model_forward(dims, seed, forward)
     X = np.ascontiguousarray(prefix, dtype=F32).reshape(-1, dims[0])
     out, tok = [], int(token_in)
     for _ in range(n_new):
         q = X.shape[0]
         X = np.concatenate([X, head_oracle.embed_rows_ref(E, [tok], P, [q])])
-        H = causal_oracle.decoder_forward_causal_ref(X, enc, *dims, seed)[-1:]
+        H = model(X, enc)[-1:]
         logits = O.linear(np.ascontiguousarray(H), W, bias)
         tok = int(sample_rows_ref(logits, top_k, top_p, temperature, sample_seed, counters=[(stream << 32) + q],
                                   prev=[tok], eos=eos)[0][0])
