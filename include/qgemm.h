@@ -1075,6 +1075,83 @@ QGEMM_API int qgemm_rope_rows_varlen(float *X, int64_t stride_h, int groups, int
                            int table_rows, int n_seqs, const int64_t *row0, const int *n_rows, const int *pos0,
                            void *stream);
 
+/* ---- Llama-style blocks: RMSNorm and the gated FFN -------------------------------------------
+ * Two more modifier bits on qgemm_model_desc.arch, which does not grow, valid on QGEMM_ARCH_STANDARD only; either
+ * combines with post-LN or pre-LN, with an encoder, a decoder or a decoder-only model, and with or without ROPE.  Bit
+ * 0x1000 is NOT a bit of arch and stays refused, as does every bit from 0x8000 up.  Grouped-query attention is not
+ * part of this: n_kv_heads = n_heads (the Llama-1 / Llama-2 7B and 13B shape).
+ *
+ * QGEMM_ARCH_RMSNORM: every norm of the model -- LN1, LN2, LN3 and the final norm -- is the root-mean-square norm of
+ * Llama, Mistral, Qwen, Gemma and T5, with gamma alone.  The beta kinds 17, 19, 25 and 27 do not exist on such a model:
+ * qgemm_model_set_weight, qgemm_model_weight_shape and qgemm_model_bias refuse them.  The gamma kinds keep their
+ * numbers and meaning; ln_eps is the norm's epsilon.  The launch counts do not change: every boundary is the same ONE
+ * launch, of the RMS form below.
+ *
+ * QGEMM_ARCH_GATED_FFN: the block's FFN is
+ *   t = (act(x W1 + b1) * (x W3 + b3)) W2 + b2          act: relu (ReGLU), tanh-form GELU (GEGLU) or SiLU (SwiGLU)
+ * with two more tensors per block, which every other model refuses as kinds it lacks:
+ *   kind 30          W3                d_model x d_ff     head 0; the UP projection.  Kind 4, W1, is the GATE, the
+ *                                                         activated one, and kind 6, W2, is down: Meta's w1 / w3 / w2,
+ *                                                         Hugging Face's gate_proj / up_proj / down_proj
+ *   kind 31          b3                1 x d_ff           created +0, with the copy path of kinds 5 and 7
+ * W3 is drawn at creation as the stream encoder_weight_seed(seed, block, 30, 0) with W1's bound.  The block's packed W1
+ * is [W1 | W3], d_model x 2 d_ff, and [b1 | b3] sits beside it, as [Wq | Wk | Wv] and its bias do: ONE GEMM produces
+ * gate and up, qgemm_model_set_weight(kind 30) is one qgemm_pack_b_window launch at column d_ff, and
+ * qgemm_model_packed_weight(block, 2) reports n = 2 d_ff.  Setting either kind resets the cache slots as every kind
+ * does.  The FFN stays three launches: the W1 GEMM, qgemm_glu_pack_a's kernel, the W2 GEMM; no fp32 matrix of the
+ * product is written.  d_ff <= 16384 (qgemm_glu_pack_a's limit); where the older creators bound max_rows by d_ff, a
+ * gated model is bound by 2 d_ff.
+ * QGEMM_ACT_SILU is valid together with QGEMM_ARCH_GATED_FFN only: an ungated SiLU FFN is no known model's.
+ * Every new step is row-local, so every contract of the cached, batched, varlen, generate and beam calls that rests
+ * on row-locality carries over.  qgemm_model_info returns arch and activation as given.
+ *
+ * qgemm_rmsnorm_rows: on rows x w floats, contiguous rows, w <= 4096, with the aliasing and alignment rules of
+ * qgemm_layernorm_rows.  Every step is ONE IEEE fp32 operation, no contraction and no fma:
+ *   v[c] = fl(A[c] + B[c])                      (B == NULL: v[c] = A[c])
+ *   ms   = fl(rowsum(fl(v[c] v[c])) / fl32(w))
+ *   r    = fl(1 / fl(sqrt(fl(ms + eps))))
+ *   Y[c] = fl(fl(v[c] r) gamma[c])
+ * rowsum is EXACTLY qgemm_layernorm_rows': lane l's partial over float4 columns l, l + 64, .. from +0, then six butterfly
+ * steps; the order depends on w alone, positions past the row do not change the sum, and the float-by-float path
+ * gives the float4 path's bits.  This is the order of Hugging Face's LlamaRMSNorm / T5LayerNorm: scale by the
+ * reciprocal root first, then by the weight.  With eps = 0 a zero row gives r = inf, 0 inf = NaN.
+ * qgemm_rmsnorm_pack_a: the same, and Y's rows also written packed: the scale and q regions equal qgemm_pack_a(Y, range)
+ * byte for byte, padding rows and columns included.
+ * qgemm_prenorm_rms_pack_a: the norm-first form, S = v stored before normalising (S == NULL: not stored; S may be A or
+ * B), the normalised row written only packed, byte for byte qgemm_rmsnorm_pack_a's.
+ * qgemm_add_rows serves an RMS model unchanged.  One launch each, no workspace, no allocation, no synchronization.
+ * hipErrorInvalidValue before any launch: a null A / gamma (/ Y / packed_a), w < 1 or > 4096, rows < 0; rows == 0
+ * returns 0.
+ *
+ * qgemm_glu_rows: a row of X holds 2w floats, the gate in columns 0 .. w - 1 and up in w .. 2w - 1 (unit inner stride,
+ * row strides in floats); Y is rows x w:
+ *   a    = act(X[c])        QGEMM_ACT_RELU:      (g < 0 ? 0 : g), the GEMM epilogue's relu
+ *                           QGEMM_ACT_GELU_TANH: qgemm_gelu_rows' five steps
+ *                           QGEMM_ACT_SILU:      e = fl32(exp((double)(-g))),  a = fl(g / fl(1.0f + e))
+ *   Y[c] = fl(a * X[w + c])
+ * NaN, +-inf and -0 give what these operations give; silu(-inf) is NaN.
+ * qgemm_glu_pack_a: packed_a (qgemm_packed_size(m, k) bytes) = qgemm_pack_a(glu_rows(X), range) byte for byte over the
+ * scale and q regions, the signed first element of the product row seeding its absmax as in qgemm_pack_a, padding rows
+ * and columns zeroed; the product matrix is never written.  k <= 16384; one launch, no workspace, no allocation, no
+ * synchronization; capturable.  16-byte aligned X with k % 4 == 0 and x_stride_h % 4 == 0 (or m == 1) loads float4s,
+ * anything else goes float by float and gives the same bits.
+ * hipErrorInvalidValue before any launch: a null pointer, an unknown activation, a negative stride, x_stride_h < 2k
+ * (2w) or y_stride_h < w with more than one row, w < 1 / k < 1 or k > 16384, rows < 0 / m < 0; rows == 0 / m == 0
+ * returns 0. */
+#define QGEMM_ARCH_RMSNORM 0x2000   /* with QGEMM_ARCH_STANDARD only */
+#define QGEMM_ARCH_GATED_FFN 0x4000 /* with QGEMM_ARCH_STANDARD only; d_ff <= 16384 */
+#define QGEMM_ACT_SILU 2            /* with QGEMM_ARCH_GATED_FFN only */
+QGEMM_API int qgemm_rmsnorm_rows(const float *A, const float *B_or_null, const float *gamma, float eps, float *Y,
+                       int64_t rows, int w, void *stream);
+QGEMM_API int qgemm_rmsnorm_pack_a(const float *A, const float *B_or_null, const float *gamma, float eps, float *Y,
+                         int64_t rows, int w, float range, void *packed_a, void *stream);
+QGEMM_API int qgemm_prenorm_rms_pack_a(const float *A, const float *B_or_null, const float *gamma, float eps,
+                             float *S_or_null, int64_t rows, int w, float range, void *packed_a, void *stream);
+QGEMM_API int qgemm_glu_rows(const float *X, int64_t x_stride_h, float *Y, int64_t y_stride_h, int64_t rows, int w,
+                   int activation, void *stream);
+QGEMM_API int qgemm_glu_pack_a(const float *X, int64_t x_stride_h, int m, int k, int activation, float range,
+                     void *packed_a, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -148,6 +148,11 @@ EXPORTED_SYMBOLS = (
     "qgemm_model_rope_tables",
     "qgemm_rope_rows",
     "qgemm_rope_rows_varlen",
+    "qgemm_rmsnorm_rows",
+    "qgemm_rmsnorm_pack_a",
+    "qgemm_prenorm_rms_pack_a",
+    "qgemm_glu_rows",
+    "qgemm_glu_pack_a",
 )
 
 # Every symbol include/qgemm_dist.h declares (libqgemm_dist.so: M-shards + RCCL all-gather).
@@ -181,8 +186,13 @@ QGEMM_ACT_RELU, QGEMM_ACT_GELU_TANH = 0, 1        # ... and the FFN's activation
 QGEMM_ARCH_NORM_FIRST, QGEMM_ARCH_FINAL_NORM = 0x100, 0x200  # modifier bits on arch: the pre-LN block
 # ... a decoder without the cross-attention third / rotary embeddings on Q and K
 QGEMM_ARCH_DECODER_ONLY, QGEMM_ARCH_ROPE = 0x400, 0x800
+# ... the RMS norm with gamma alone / the gated FFN (act(x W1) * (x W3)) W2 of Llama-style blocks;
+# 0x1000 is no bit of arch.  SiLU: with the gated FFN only
+QGEMM_ARCH_RMSNORM, QGEMM_ARCH_GATED_FFN = 0x2000, 0x4000
+QGEMM_ACT_SILU = 2
 ARCHS = {"reference": QGEMM_ARCH_REFERENCE, "standard": QGEMM_ARCH_STANDARD}
-ACTIVATIONS = {"relu": QGEMM_ACT_RELU, "gelu_tanh": QGEMM_ACT_GELU_TANH}
+ACTIVATIONS = {"relu": QGEMM_ACT_RELU, "gelu_tanh": QGEMM_ACT_GELU_TANH, "silu": QGEMM_ACT_SILU}
+NORMS = ("layer", "rms")
 
 
 class ModelDesc(ctypes.Structure):
@@ -458,6 +468,16 @@ def load() -> ctypes.CDLL:
         L.qgemm_rope_rows.restype = i32
         L.qgemm_rope_rows_varlen.argtypes = [vp, i64, i32, i32, vp, vp, i32, i32, lp, ip, ip, vp]
         L.qgemm_rope_rows_varlen.restype = i32
+        L.qgemm_rmsnorm_rows.argtypes = [vp, vp, vp, f32, vp, i64, i32, vp]
+        L.qgemm_rmsnorm_rows.restype = i32
+        L.qgemm_rmsnorm_pack_a.argtypes = [vp, vp, vp, f32, vp, i64, i32, f32, vp, vp]
+        L.qgemm_rmsnorm_pack_a.restype = i32
+        L.qgemm_prenorm_rms_pack_a.argtypes = [vp, vp, vp, f32, vp, i64, i32, f32, vp, vp]
+        L.qgemm_prenorm_rms_pack_a.restype = i32
+        L.qgemm_glu_rows.argtypes = [vp, i64, vp, i64, i64, i32, i32, vp]
+        L.qgemm_glu_rows.restype = i32
+        L.qgemm_glu_pack_a.argtypes = [vp, i64, i32, i32, i32, f32, vp, vp]
+        L.qgemm_glu_pack_a.restype = i32
         _lib = L
         return L
 
@@ -1140,6 +1160,71 @@ def gelu_pack_a(X, range: float = DEFAULT_RANGE, out=None) -> Packed:  # noqa: A
     return Packed(buf, M, K, range)
 
 
+def rmsnorm_rows(A, B, gamma, eps: float = 1e-5, Y=None):
+    """Y = RMSNorm(A + B) with gamma and eps, the root-mean-square norm of Llama-style blocks (qgemm_rmsnorm_rows,
+    DESIGN.md s28); B may be None, Y may be A or B."""
+    Y = _ln_args(A, B, gamma, gamma, Y)
+    _check("qgemm_rmsnorm_rows",
+           load().qgemm_rmsnorm_rows(A.data_ptr(), 0 if B is None else B.data_ptr(), gamma.data_ptr(), float(eps),
+                                     Y.data_ptr(), A.shape[0], A.shape[1], _stream(A.device)))
+    return Y
+
+
+def rmsnorm_pack_a(A, B, gamma, eps: float = 1e-5, Y=None, range: float = DEFAULT_RANGE, out=None):  # noqa: A002
+    """rmsnorm_rows that also packs Y's rows for the next quantized linear (qgemm_rmsnorm_pack_a): returns
+    (Y, Packed), the Packed byte for byte pack_a(Y) (written into `out`'s buffer where given)."""
+    Y = _ln_args(A, B, gamma, gamma, Y)
+    M, K = A.shape
+    buf = _packed_out(out, M, K, A.device)
+    _check("qgemm_rmsnorm_pack_a",
+           load().qgemm_rmsnorm_pack_a(A.data_ptr(), 0 if B is None else B.data_ptr(), gamma.data_ptr(), float(eps),
+                                       Y.data_ptr(), M, K, float(range), buf.data_ptr(), _stream(A.device)))
+    return Y, Packed(buf, M, K, range)
+
+
+def prenorm_rms_pack_a(A, B, gamma, eps: float = 1e-5, S=None, range: float = DEFAULT_RANGE, out=None):  # noqa: A002
+    """The pre-norm boundary of an RMS model in one launch (qgemm_prenorm_rms_pack_a): S = A + B (B may
+    be None: S = A; S=None: not stored; S may be A or B), and RMSNorm(A + B) written only packed.  Returns (S, Packed),
+    the Packed byte for byte rmsnorm_pack_a's for the same arguments."""
+    _ln_args(A, B, gamma, gamma, A if S is None else S)
+    M, K = A.shape
+    buf = _packed_out(out, M, K, A.device)
+    _check("qgemm_prenorm_rms_pack_a",
+           load().qgemm_prenorm_rms_pack_a(A.data_ptr(), 0 if B is None else B.data_ptr(), gamma.data_ptr(), float(eps),
+                                           0 if S is None else S.data_ptr(), M, K, float(range), buf.data_ptr(),
+                                           _stream(A.device)))
+    return S, Packed(buf, M, K, range)
+
+
+def _glu_args(X, activation):
+    _require_device_f32(X, "X")
+    assert X.dim() == 2 and X.stride(1) == 1 and X.shape[1] % 2 == 0, "X: rows x 2w ([gate | up]), unit inner stride"
+    assert activation in ACTIVATIONS, f"activation: one of {sorted(ACTIVATIONS)}"
+    return X.shape[0], X.shape[1] // 2, ACTIVATIONS[activation]
+
+
+def glu_rows(X, activation: str = "silu", Y=None):
+    """act(gate) * up elementwise (qgemm_glu_rows): X rows x 2w with the gate in its left half and up
+    in its right half, unit inner stride, any row stride; Y rows x w."""
+    import torch
+    rows, w, act = _glu_args(X, activation)
+    Y = torch.empty((rows, w), dtype=torch.float32, device=X.device) if Y is None else Y
+    _require_device_f32(Y, "Y")
+    assert Y.shape == (rows, w) and Y.stride(1) == 1
+    _check("qgemm_glu_rows", load().qgemm_glu_rows(X.data_ptr(), X.stride(0), Y.data_ptr(), Y.stride(0), rows, w, act,
+                                                  _stream(X.device)))
+    return Y
+
+
+def glu_pack_a(X, activation: str = "silu", range: float = DEFAULT_RANGE, out=None) -> Packed:  # noqa: A002
+    """pack_a(glu_rows(X)) in one launch, the product never written (qgemm_glu_pack_a); w <= 16384."""
+    M, K, act = _glu_args(X, activation)
+    buf = _packed_out(out, M, K, X.device)
+    _check("qgemm_glu_pack_a", load().qgemm_glu_pack_a(X.data_ptr(), X.stride(0), M, K, act, float(range),
+                                                      buf.data_ptr(), _stream(X.device)))
+    return Packed(buf, M, K, range)
+
+
 def _rope_args(X, groups: int, d_k: int, cos, sin):
     _require_device_f32(X, "X")
     _require_device_f32(cos, "cos")
@@ -1247,7 +1332,10 @@ def encoder_weight_seed(base: int, block: int, kind: int, head: int) -> int:
 KIND_GF, KIND_BEF = 26, 27
 # The rotary tables of a model created with rope=True: max_seq x d_k / 2 each, block 0, head 0.
 KIND_ROPE_COS, KIND_ROPE_SIN = 28, 29
-_VECTOR_KINDS = (KIND_B1, KIND_B2) + tuple(range(KIND_BQ, KIND_BEF + 1))
+# The up projection of a model created with gated_ffn=True and its bias: d_model x d_ff and 1 x d_ff,
+# every block's, head 0.  KIND_W1 is then the gate (HF gate_proj), KIND_W3 up (up_proj), KIND_W2 down (down_proj).
+KIND_W3, KIND_B3 = 30, 31
+_VECTOR_KINDS = (KIND_B1, KIND_B2, KIND_B3) + tuple(range(KIND_BQ, KIND_BEF + 1))
 # packed_weight's `which`
 (WEIGHT_WQKV, WEIGHT_WO, WEIGHT_W1, WEIGHT_W2, WEIGHT_WQ2, WEIGHT_WKV2, WEIGHT_WO2) = range(7)
 
@@ -1265,15 +1353,21 @@ class _ArchKeywords(type):
     decoder_only=: keyword-only arguments of the class call, set on the object before __init__ runs.  decoder_only
     (Decoder, with max_enc_seq = 0): the blocks lack the cross-attention; rope (arch="standard" only): rotary
     embeddings on Q and K.  norm_first (arch="standard" only): the pre-LN
-    block; final_norm (with norm_first only): a LayerNorm behind the last block.  __init__ keeps its parameter list as it was (its last parameters stay
+    block; final_norm (with norm_first only): a LayerNorm behind the last block.  norm="rms"
+    (arch="standard" only): every norm is the RMS norm with gamma alone; gated_ffn=True (arch="standard" only): the FFN
+    is (act(x W1 + b1) * (x W3 + b3)) W2 + b2, and activation="silu" is valid with it alone.  __init__ keeps its parameter list as it was (its last parameters stay
     max_rows, and n_slots on a Decoder), so positional callers and tools that read that list see no change."""
 
     def __call__(cls, *args, arch: str = "reference", activation: str = "relu", ln_eps: float = 1e-5,
                  norm_first: bool = False, final_norm: bool = False, decoder_only: bool = False, rope: bool = False,
-                 **kw):
+                 norm: str = "layer", gated_ffn: bool = False, **kw):
         assert not norm_first or arch != "reference", "norm_first needs arch='standard'"
         assert norm_first or not final_norm, "final_norm needs norm_first=True"
         assert not rope or arch != "reference", "rope needs arch='standard'"
+        assert norm in NORMS, f"norm: one of {NORMS}"
+        assert norm == "layer" or arch != "reference", "norm='rms' needs arch='standard'"
+        assert not gated_ffn or arch != "reference", "gated_ffn needs arch='standard'"
+        assert activation != "silu" or gated_ffn, "activation='silu' needs gated_ffn=True"
         if decoder_only:  # (Decoder's parameters: d_model, n_heads, d_ff, n_blocks, max_seq, max_enc_seq, ..)
             assert cls.__name__ == "Decoder", "decoder_only belongs to Decoder"
             max_enc_seq = kw["max_enc_seq"] if "max_enc_seq" in kw else (args[5] if len(args) > 5 else None)
@@ -1282,6 +1376,7 @@ class _ArchKeywords(type):
         self.arch, self.activation, self.ln_eps = arch, activation, float(ln_eps)
         self.norm_first, self.final_norm = bool(norm_first), bool(final_norm)
         self.decoder_only, self.rope = bool(decoder_only), bool(rope)
+        self.norm, self.gated_ffn = norm, bool(gated_ffn)
         self.__init__(*args, **kw)
         return self
 
@@ -1340,7 +1435,10 @@ class _ModelWeights(metaclass=_ArchKeywords):
                          ARCHS[arch] | (QGEMM_ARCH_NORM_FIRST if self.norm_first else 0) |
                          (QGEMM_ARCH_FINAL_NORM if self.final_norm else 0) |
                          (QGEMM_ARCH_DECODER_ONLY if getattr(self, "decoder_only", False) else 0) |
-                         (QGEMM_ARCH_ROPE if getattr(self, "rope", False) else 0), ACTIVATIONS[activation], float(ln_eps))
+                         (QGEMM_ARCH_ROPE if getattr(self, "rope", False) else 0) |
+                         (QGEMM_ARCH_RMSNORM if getattr(self, "norm", "layer") == "rms" else 0) |
+                         (QGEMM_ARCH_GATED_FFN if getattr(self, "gated_ffn", False) else 0),
+                         ACTIVATIONS[activation], float(ln_eps))
         h = ctypes.c_void_p()
         _check("qgemm_model_create", load().qgemm_model_create(ctypes.byref(desc), ctypes.byref(h)))
         return h
@@ -1364,6 +1462,8 @@ class _ModelWeights(metaclass=_ArchKeywords):
         import torch
         if self.arch != "standard":
             raise ValueError("load_torch_layer needs a model created with arch='standard'")
+        if getattr(self, "norm", "layer") != "layer" or getattr(self, "gated_ffn", False):
+            raise ValueError("torch.nn has no layer with an RMS norm or a gated FFN: load such a model with set_weight")
         cross = hasattr(layer, "multihead_attn")
         if cross != (isinstance(self, Decoder) and not getattr(self, "decoder_only", False)):
             raise ValueError("an Encoder or a decoder-only Decoder takes a TransformerEncoderLayer, a Decoder with "
@@ -1422,6 +1522,8 @@ class _ModelWeights(metaclass=_ArchKeywords):
         import torch
         if not getattr(self, "final_norm", False):
             raise ValueError("load_torch_final_norm needs a model created with final_norm=True")
+        if getattr(self, "norm", "layer") != "layer" or getattr(self, "gated_ffn", False):
+            raise ValueError("torch.nn has no layer with an RMS norm or a gated FFN: load such a model with set_weight")
         if not isinstance(ln, torch.nn.LayerNorm) or tuple(ln.normalized_shape) != (self.d_model,) or \
                 ln.weight is None or ln.bias is None or abs(ln.eps - self.ln_eps) > 1e-12:
             raise ValueError(f"the final norm must be an affine LayerNorm({self.d_model}, eps={self.ln_eps})")
@@ -1442,8 +1544,8 @@ class _ModelWeights(metaclass=_ArchKeywords):
         return Packed(buf, n.value, k.value, DEFAULT_RANGE)
 
     def bias(self, block: int, kind: int):
-        """Block's bias KIND_B1 or KIND_B2, or on a standard model a vector of kinds KIND_BQ ..: a copy, n floats on
-        the device."""
+        """Block's bias KIND_B1 or KIND_B2 (KIND_B3 on a gated model), or on a standard model a vector of kinds
+        KIND_BQ ..: a copy, n floats on the device."""
         import torch
         p, n = ctypes.c_void_p(), ctypes.c_int()
         _check("qgemm_model_bias", load().qgemm_model_bias(self._h, block, kind, ctypes.byref(p), ctypes.byref(n)))

@@ -709,14 +709,46 @@ int qgemm_gelu_pack_a(const float *X, int64_t x_stride_h, int m, int k, float ra
                                 static_cast<hipStream_t>(stream)));
 }
 
+// ---- Llama-style blocks: the RMS norm and the gated FFN's pack ----
+
+int qgemm_rmsnorm_rows(const float *A, const float *B_or_null, const float *gamma, float eps, float *Y, int64_t rows,
+                       int w, void *stream) {
+    return err(launch_rmsnorm_rows(A, B_or_null, gamma, eps, Y, rows, w, static_cast<hipStream_t>(stream)));
+}
+
+int qgemm_rmsnorm_pack_a(const float *A, const float *B_or_null, const float *gamma, float eps, float *Y, int64_t rows,
+                         int w, float range, void *packed_a, void *stream) {
+    if (!packed_a || rows < 0 || rows > INT32_MAX || w < 1 || w > 4096) return err(hipErrorInvalidValue);
+    return err(launch_rmsnorm_rows_pack(A, B_or_null, gamma, eps, Y, rows, w, range, packed_view(packed_a, (int)rows, w),
+                                        static_cast<hipStream_t>(stream)));
+}
+
+int qgemm_prenorm_rms_pack_a(const float *A, const float *B_or_null, const float *gamma, float eps, float *S_or_null,
+                             int64_t rows, int w, float range, void *packed_a, void *stream) {
+    if (!packed_a || rows < 0 || rows > INT32_MAX || w < 1 || w > 4096) return err(hipErrorInvalidValue);
+    return err(launch_prenorm_rms_pack(A, B_or_null, gamma, eps, S_or_null, rows, w, range,
+                                       packed_view(packed_a, (int)rows, w), static_cast<hipStream_t>(stream)));
+}
+
+int qgemm_glu_rows(const float *X, int64_t x_stride_h, float *Y, int64_t y_stride_h, int64_t rows, int w, int activation,
+                   void *stream) {
+    return err(launch_glu_rows(X, x_stride_h, Y, y_stride_h, rows, w, activation, static_cast<hipStream_t>(stream)));
+}
+
+int qgemm_glu_pack_a(const float *X, int64_t x_stride_h, int m, int k, int activation, float range, void *packed_a,
+                     void *stream) {
+    if (!packed_a || m < 0 || k < 1 || k > 16384) return err(hipErrorInvalidValue);
+    return err(launch_glu_pack(X, x_stride_h, m, k, activation, range, packed_view(packed_a, m, k),
+                               static_cast<hipStream_t>(stream)));
+}
+
 int qgemm_model_create(const qgemm_model_desc *desc, void **model) {
     if (!model) return err(hipErrorInvalidValue);
     *model = nullptr;
     if (!desc || desc->size != sizeof(qgemm_model_desc)) return err(hipErrorInvalidValue);
     const qgemm_model_desc &d = *desc;
-    if ((d.cross != 0 && d.cross != 1) || !stack_arch_ok(d.arch, d.cross != 0) || (d.activation != QGEMM_ACT_RELU && d.activation != QGEMM_ACT_GELU_TANH) ||
-        ((d.arch & 0xff) == QGEMM_ARCH_REFERENCE && d.activation != QGEMM_ACT_RELU) || !(d.ln_eps >= 0.0f) ||
-        d.n_slots < 0 || d.max_rows < 0)
+    if ((d.cross != 0 && d.cross != 1) || !stack_arch_ok(d.arch, d.cross != 0) ||
+        !stack_activation_ok(d.arch, d.activation, d.d_ff) || !(d.ln_eps >= 0.0f) || d.n_slots < 0 || d.max_rows < 0)
         return err(hipErrorInvalidValue);
     const int n_slots = d.n_slots ? d.n_slots : 1;
     bool causal = false, kv_cache = false;

@@ -8,13 +8,14 @@
 // the row (kV = 1, 4 or 16 of them: rows up to 1024, 4096 and 16384 floats), loads them once, applies GELU once and
 // keeps g in registers between the absmax and the quantization: a row of 16384 floats is 64 VGPRs per thread.  Holding
 // g costs registers; recomputing it in a second pass would cost the double-precision exp twice, and that exp is the
-// kernel's time.  The absmax is a maximum, exact in any order: wave_max, then the four waves' results
+// kernel's time.  gelu_tanh itself lives in activations.h, shared with glu.hip's gated pack.  The absmax is a maximum, exact in any order: wave_max, then the four waves' results
 // through LDS.  Then the operations of pack_rows: the signed seed g[0], candidates |g[c]|, c >= 1, inv_divide, quant_i8;
 // rows [m, rows_pad) zero bytes and a zero scale, columns [k, k_pad) zero bytes.
 //   kVec = true : 16-byte aligned rows of k % 4 == 0 floats, float4 loads;  false: any k, stride and alignment, the same
 //   registers filled float by float.
 #include <algorithm>
 
+#include "activations.h"
 #include "qgemm_internal.h"
 
 namespace qgemm {
@@ -23,14 +24,6 @@ namespace {
 
 constexpr int kBlock = 256;
 constexpr int kMaxK = 16384;
-
-__device__ __forceinline__ float gelu_tanh(float x) {
-    const float t = __fmul_rn(x, 1.59576912160573071176f);  // fl32(2 sqrt(2 / pi)) = 0x3FCC422A
-    const float q = __fadd_rn(__fmul_rn(__fmul_rn(x, x), 0.044715f), 1.0f);
-    const float z = __fmul_rn(t, q);
-    const float e = (float)exp((double)(-z));
-    return __fdiv_rn(x, __fadd_rn(1.0f, e));
-}
 
 __global__ __launch_bounds__(kBlock) void gelu_rows_kernel(const float *X, int64_t xsh, float *Y, int64_t ysh,
                                                            int64_t rows, int w) {

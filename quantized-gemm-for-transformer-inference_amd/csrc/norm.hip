@@ -24,6 +24,9 @@
 // LN(v) exactly as above, written only as packed int8 + scale -- the normalised fp32 row is never stored.  kFormAdd: S
 // = v and nothing else, the last boundary of a pre-LN model without a final norm.  S takes Y's place in the argument
 // list and Y's rules: it may be A or B.
+// kRms: the root-mean-square norm of Llama-style blocks (qgemm_rmsnorm_rows): no mean pass and no beta --
+//   ms = fl(sum(fl(v v)) / fl32(w)), r = fl(1 / fl(sqrt(fl(ms + eps)))), Y = fl(fl(v r) gamma)
+// -- the same loads, stores, sum order, pack and forms; beta is not read (nullptr).
 #include "qgemm_internal.h"
 
 namespace qgemm {
@@ -80,7 +83,7 @@ __device__ __forceinline__ void store4(float *row, int c, int w, float4 v) {
 
 enum { kFormPost = 0, kFormPre = 1, kFormAdd = 2 };
 
-template <bool kPack, int kV, bool kVec, int kForm = kFormPost>
+template <bool kPack, int kV, bool kVec, int kForm = kFormPost, bool kRms = false>
 __global__ __launch_bounds__(64 * kRowWaves) void layernorm_rows_kernel(const float *A, const float *B,
                                                                        const float *__restrict__ gamma,
                                                                        const float *__restrict__ beta, float eps,
@@ -120,13 +123,16 @@ __global__ __launch_bounds__(64 * kRowWaves) void layernorm_rows_kernel(const fl
         if constexpr (kForm == kFormAdd) return;
     }
     const float fw = (float)w;
-    const float mean = __fdiv_rn(lane_sum<kV>(x), fw);
+    // kRms: no mean -- x stays v, and below `var` is the mean square and `rstd` the scale r
+    [[maybe_unused]] float mean = 0.0f;
+    if constexpr (!kRms) mean = __fdiv_rn(lane_sum<kV>(x), fw);
     float4 sq[kV];
 #pragma unroll
     for (int i = 0; i < kV; ++i) {
         const int c = 4 * (lane + 64 * i);
-        x[i] = make_float4(__fsub_rn(x[i].x, mean), __fsub_rn(x[i].y, mean), __fsub_rn(x[i].z, mean),
-                           __fsub_rn(x[i].w, mean));  // d
+        if constexpr (!kRms)
+            x[i] = make_float4(__fsub_rn(x[i].x, mean), __fsub_rn(x[i].y, mean), __fsub_rn(x[i].z, mean),
+                               __fsub_rn(x[i].w, mean));  // d
         sq[i] = make_float4(c < w ? __fmul_rn(x[i].x, x[i].x) : -0.0f, c + 1 < w ? __fmul_rn(x[i].y, x[i].y) : -0.0f,
                             c + 2 < w ? __fmul_rn(x[i].z, x[i].z) : -0.0f, c + 3 < w ? __fmul_rn(x[i].w, x[i].w) : -0.0f);
     }
@@ -139,12 +145,18 @@ __global__ __launch_bounds__(64 * kRowWaves) void layernorm_rows_kernel(const fl
     for (int i = 0; i < kV; ++i) {
         const int j = lane + 64 * i, c = 4 * j;
         if (j < w4) {
-            const float4 g = load4<kVec>(gamma, j, w, 0.0f), be = load4<kVec>(beta, j, w, 0.0f);
+            const float4 g = load4<kVec>(gamma, j, w, 0.0f);
             float4 v;
-            v.x = __fadd_rn(__fmul_rn(__fmul_rn(x[i].x, rstd), g.x), be.x);
-            v.y = __fadd_rn(__fmul_rn(__fmul_rn(x[i].y, rstd), g.y), be.y);
-            v.z = __fadd_rn(__fmul_rn(__fmul_rn(x[i].z, rstd), g.z), be.z);
-            v.w = __fadd_rn(__fmul_rn(__fmul_rn(x[i].w, rstd), g.w), be.w);
+            if constexpr (kRms) {  // no beta: Y = fl(fl(v r) gamma)
+                v = make_float4(__fmul_rn(__fmul_rn(x[i].x, rstd), g.x), __fmul_rn(__fmul_rn(x[i].y, rstd), g.y),
+                                __fmul_rn(__fmul_rn(x[i].z, rstd), g.z), __fmul_rn(__fmul_rn(x[i].w, rstd), g.w));
+            } else {
+                const float4 be = load4<kVec>(beta, j, w, 0.0f);
+                v.x = __fadd_rn(__fmul_rn(__fmul_rn(x[i].x, rstd), g.x), be.x);
+                v.y = __fadd_rn(__fmul_rn(__fmul_rn(x[i].y, rstd), g.y), be.y);
+                v.z = __fadd_rn(__fmul_rn(__fmul_rn(x[i].z, rstd), g.z), be.z);
+                v.w = __fadd_rn(__fmul_rn(__fmul_rn(x[i].w, rstd), g.w), be.w);
+            }
             if constexpr (kForm == kFormPost) store4<kVec>(y, c, w, v);
             x[i] = v;
             if constexpr (kPack) {
@@ -177,31 +189,31 @@ __global__ __launch_bounds__(64 * kRowWaves) void layernorm_rows_kernel(const fl
 
 bool al16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-template <bool kPack, bool kVec, int kForm>
+template <bool kPack, bool kVec, int kForm, bool kRms>
 hipError_t launch_ln(const float *A, const float *B, const float *gamma, const float *beta, float eps, float *Y,
                      int64_t rows, int w, int8_t *q, float *qscale, int64_t k_pad, int64_t rows_pad, float range,
                      int64_t grid_rows, hipStream_t stream) {
     const unsigned grid = (unsigned)((grid_rows + kRowWaves - 1) / kRowWaves);
     if (w <= 1024)
-        layernorm_rows_kernel<kPack, 4, kVec, kForm>
+        layernorm_rows_kernel<kPack, 4, kVec, kForm, kRms>
             <<<grid, 64 * kRowWaves, 0, stream>>>(A, B, gamma, beta, eps, Y, rows, w, q, qscale, k_pad, rows_pad, range);
     else if (w <= 2048)
-        layernorm_rows_kernel<kPack, 8, kVec, kForm>
+        layernorm_rows_kernel<kPack, 8, kVec, kForm, kRms>
             <<<grid, 64 * kRowWaves, 0, stream>>>(A, B, gamma, beta, eps, Y, rows, w, q, qscale, k_pad, rows_pad, range);
     else
-        layernorm_rows_kernel<kPack, 16, kVec, kForm>
+        layernorm_rows_kernel<kPack, 16, kVec, kForm, kRms>
             <<<grid, 64 * kRowWaves, 0, stream>>>(A, B, gamma, beta, eps, Y, rows, w, q, qscale, k_pad, rows_pad, range);
     return hipGetLastError();
 }
 
-template <bool kPack, int kForm = kFormPost>
+template <bool kPack, int kForm = kFormPost, bool kRms = false>
 hipError_t launch_ln_any(const float *A, const float *B, const float *gamma, const float *beta, float eps, float *Y,
                          int64_t rows, int w, int8_t *q, float *qscale, int64_t k_pad, int64_t rows_pad, float range,
                          int64_t grid_rows, hipStream_t stream) {
     const bool vec = w % 4 == 0 && al16(A) && al16(B) && al16(gamma) && al16(beta) && al16(Y);
-    return vec ? launch_ln<kPack, true, kForm>(A, B, gamma, beta, eps, Y, rows, w, q, qscale, k_pad, rows_pad, range,
+    return vec ? launch_ln<kPack, true, kForm, kRms>(A, B, gamma, beta, eps, Y, rows, w, q, qscale, k_pad, rows_pad, range,
                                                grid_rows, stream)
-               : launch_ln<kPack, false, kForm>(A, B, gamma, beta, eps, Y, rows, w, q, qscale, k_pad, rows_pad, range,
+               : launch_ln<kPack, false, kForm, kRms>(A, B, gamma, beta, eps, Y, rows, w, q, qscale, k_pad, rows_pad, range,
                                                 grid_rows, stream);
 }
 
@@ -231,6 +243,34 @@ hipError_t launch_prenorm_pack(const float *A, const float *B, const float *gamm
     if (!out.q || out.k_pad < w || out.rows_pad < rows) return hipErrorInvalidValue;
     return launch_ln_any<true, kFormPre>(A, B, gamma, beta, eps, S, rows, w, out.q, out.scale, out.k_pad, out.rows_pad,
                                          range, out.rows_pad, stream);
+}
+
+// The RMS forms (the contract is at qgemm_rmsnorm_rows in include/qgemm.h): the three launchers above on
+// the kernel's kRms instantiations -- no mean pass, no beta
+hipError_t launch_rmsnorm_rows(const float *A, const float *B, const float *gamma, float eps, float *Y, int64_t rows,
+                               int w, hipStream_t stream) {
+    if (!A || !gamma || !Y || w < 1 || w > kMaxRowLen || rows < 0) return hipErrorInvalidValue;
+    if (rows == 0) return hipSuccess;
+    return launch_ln_any<false, kFormPost, true>(A, B, gamma, nullptr, eps, Y, rows, w, nullptr, nullptr, 0, 0, 0.0f,
+                                                 rows, stream);
+}
+
+hipError_t launch_rmsnorm_rows_pack(const float *A, const float *B, const float *gamma, float eps, float *Y,
+                                    int64_t rows, int w, float range, PackedView out, hipStream_t stream) {
+    if (!A || !gamma || !Y || w < 1 || w > kMaxRowLen || rows < 0) return hipErrorInvalidValue;
+    if (rows == 0) return hipSuccess;
+    if (!out.q || out.k_pad < w || out.rows_pad < rows) return hipErrorInvalidValue;
+    return launch_ln_any<true, kFormPost, true>(A, B, gamma, nullptr, eps, Y, rows, w, out.q, out.scale, out.k_pad,
+                                                out.rows_pad, range, out.rows_pad, stream);
+}
+
+hipError_t launch_prenorm_rms_pack(const float *A, const float *B, const float *gamma, float eps, float *S,
+                                   int64_t rows, int w, float range, PackedView out, hipStream_t stream) {
+    if (!A || !gamma || w < 1 || w > kMaxRowLen || rows < 0) return hipErrorInvalidValue;
+    if (rows == 0) return hipSuccess;
+    if (!out.q || out.k_pad < w || out.rows_pad < rows) return hipErrorInvalidValue;
+    return launch_ln_any<true, kFormPre, true>(A, B, gamma, nullptr, eps, S, rows, w, out.q, out.scale, out.k_pad,
+                                               out.rows_pad, range, out.rows_pad, stream);
 }
 
 // S = A + B, the same rows and paths without a norm

@@ -605,12 +605,29 @@ hipError_t launch_add_rows(const float *A, const float *B, float *S, int64_t row
 // m x k matrix, k <= 16384: the packed view of the GELU'd matrix, which is never written
 hipError_t launch_gelu_rows(const float *X, int64_t xsh, float *Y, int64_t ysh, int64_t rows, int w, hipStream_t stream);
 hipError_t launch_gelu_pack(const float *X, int64_t xsh, int m, int k, float range, PackedView out, hipStream_t stream);
+// Llama-style blocks (the contracts are at qgemm_rmsnorm_rows and qgemm_glu_rows in include/qgemm.h).
+// norm.hip: the RMS forms of the three launchers above -- no mean, no beta, the same kernel, rules and checks
+hipError_t launch_rmsnorm_rows(const float *A, const float *B, const float *gamma, float eps, float *Y, int64_t rows,
+                               int w, hipStream_t stream);
+hipError_t launch_rmsnorm_rows_pack(const float *A, const float *B, const float *gamma, float eps, float *Y,
+                                    int64_t rows, int w, float range, PackedView out, hipStream_t stream);
+hipError_t launch_prenorm_rms_pack(const float *A, const float *B, const float *gamma, float eps, float *S,
+                                   int64_t rows, int w, float range, PackedView out, hipStream_t stream);
+// glu.hip: h = act(gate) * up on rows of [gate: w | up: w] floats (activation: QGEMM_ACT_*), elementwise and fused
+// into pack_rows of the m x k product, k <= 16384, which is never written
+hipError_t launch_glu_rows(const float *X, int64_t xsh, float *Y, int64_t ysh, int64_t rows, int w, int activation,
+                           hipStream_t stream);
+hipError_t launch_glu_pack(const float *X, int64_t xsh, int m, int k, int activation, float range, PackedView out,
+                           hipStream_t stream);
 // transformer.hip: the architecture of a stack (stack_create's arch: 0 the reference's block, 1 the standard one with
 // its new tensors allocated and set, b_* = +0, gamma = 1, beta = +0; activation: 0 relu, 1 tanh GELU, arch 1 only;
 // arch 0x101 the pre-LN block and 0x301 the pre-LN block with a final norm, QGEMM_ARCH_NORM_FIRST / _FINAL_NORM;
-// 0x400 QGEMM_ARCH_DECODER_ONLY with cross alone, 0x800 QGEMM_ARCH_ROPE on the standard block alone);
+// 0x400 QGEMM_ARCH_DECODER_ONLY with cross alone, 0x800 QGEMM_ARCH_ROPE on the standard block alone; 0x2000
+// QGEMM_ARCH_RMSNORM and 0x4000 QGEMM_ARCH_GATED_FFN on the standard block alone, activation 2, SiLU, with the gate
+// alone); stack_activation_ok is the one check of arch and activation together;
 // stack_describe reads back what creation was given.
 bool stack_arch_ok(int arch, bool cross);
+bool stack_activation_ok(int arch, int activation, int d_ff);
 struct StackDesc {
     int cross, d_model, n_heads, d_ff, n_blocks, max_seq, max_enc_seq;
     uint64_t seed;

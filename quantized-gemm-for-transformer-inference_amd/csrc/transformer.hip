@@ -22,6 +22,9 @@
 //             boundary after W_O2
 //   t = act(x W1 + b1) W2 + b2           transformer.cu:62-75 / :152-167, linear.cuh:50-54.  relu in W1's epilogue; with
 //                                        GELU W1 runs without relu and the pack in front of W2 is gelu.hip's fused one
+//   gated (QGEMM_ARCH_GATED_FFN):  t = (act(x W1 + b1) * (x W3 + b3)) W2 + b2 -- the block's packed W1 is
+//                                        [W1 | W3], so ONE GEMM writes gate | up, and the pack in front of W2 is
+//                                        glu.hip's: activate the gate, multiply by up, quantize; the same three launches
 //   boundary after W2
 //
 // THE BOUNDARIES.  The architecture (qgemm_model_create's arch) is what stands between the
@@ -42,6 +45,8 @@
 //     never written).  Block 0 begins with LN1 + pack of X in place of pack_rows(X) (run_blocks' prologue); the last
 //     boundary is the post-LN kernel with gamma_f, beta_f (kinds 26, 27, the stack's own allocation) or
 //     launch_add_rows.  enc_out enters the cross-attention as given.
+//   QGEMM_ARCH_RMSNORM: every LN above, post-LN or pre-LN, is the RMS norm with gamma alone -- the same
+//     launches on norm.hip's RMS instantiations (norm_rows, norm_rows_pack, prenorm_pack below pick them).
 //
 // Decisions where the reference cannot run as written:
 //   * arity (transformer.cu:37 calls forward(X, X, out); attention.cuh:47 takes (X, out)): self attention on the block
@@ -131,24 +136,39 @@ enum WeightKind { kWq = 0, kWk = 1, kWv = 2, kWo = 3, kW1 = 4, kB1 = 5, kW2 = 6,
                   // the final norm of a pre-LN stack, 1 x d_model each, block 0's
                   kGf = 26, kBef = 27,
                   // the rotary tables of a ROPE stack, max_seq x d_k / 2 each, block 0's
-                  kRopeCos = 28, kRopeSin = 29 };
+                  kRopeCos = 28, kRopeSin = 29,
+                  // the gated FFN's up projection and its bias: d_model x d_ff and 1 x d_ff, every block's
+                  kW3 = 30, kB3 = 31 };
 
 // QGEMM_ARCH_NORM_FIRST / _FINAL_NORM / _DECODER_ONLY / _ROPE (include/qgemm.h): modifier bits above the
-// architecture's low byte
+// architecture's low byte; _RMSNORM / _GATED_FFN above a hole: 0x1000 is no bit of arch
 constexpr int kArchNormFirst = 0x100, kArchFinalNorm = 0x200, kArchDecoderOnly = 0x400, kArchRope = 0x800;
+constexpr int kArchRms = 0x2000, kArchGated = 0x4000;
+constexpr int kActRelu = 0, kActGelu = 1, kActSilu = 2;  // QGEMM_ACT_*
 
 }  // namespace
 
 // arch as qgemm_model_create takes it: the reference's block or the standard one in the low byte; above it NORM_FIRST
-// and ROPE on the standard block alone, FINAL_NORM with NORM_FIRST alone, DECODER_ONLY on a descriptor of the decoder
-// family (cross = 1) alone, and no other bit
+// ROPE, RMSNORM and GATED_FFN on the standard block alone, FINAL_NORM with NORM_FIRST alone, DECODER_ONLY on a
+// descriptor of the decoder family (cross = 1) alone, and no other bit
 bool stack_arch_ok(int arch, bool cross) {
     const int base = arch & 0xff, mods = arch & ~0xff;
-    if ((base != 0 && base != 1) || (mods & ~(kArchNormFirst | kArchFinalNorm | kArchDecoderOnly | kArchRope)))
+    if ((base != 0 && base != 1) ||
+        (mods & ~(kArchNormFirst | kArchFinalNorm | kArchDecoderOnly | kArchRope | kArchRms | kArchGated)))
         return false;
-    if ((mods & (kArchNormFirst | kArchRope)) && base != 1) return false;
+    if ((mods & (kArchNormFirst | kArchRope | kArchRms | kArchGated)) && base != 1) return false;
     if ((mods & kArchDecoderOnly) && !cross) return false;
     return !(mods & kArchFinalNorm) || (mods & kArchNormFirst);
+}
+
+// activation as qgemm_model_create takes it, beside a valid arch: relu anywhere, the tanh GELU on the standard block,
+// SiLU with the gate alone; the GELU pack and the gated pack hold rows of at most 16384 floats
+bool stack_activation_ok(int arch, int activation, int d_ff) {
+    const bool gated = (arch & kArchGated) != 0;
+    if (activation < kActRelu || activation > kActSilu) return false;
+    if ((arch & 0xff) == 0 && activation != kActRelu) return false;
+    if (activation == kActSilu && !gated) return false;
+    return !(gated || activation == kActGelu) || d_ff <= 16384;
 }
 
 // Seed of one weight tensor: every tensor its own counter stream (documented for the oracle).
@@ -160,9 +180,10 @@ uint64_t encoder_weight_seed(uint64_t base, int block, int kind, int head) {
 float encoder_init_bound(int n) { return (float)(1.0 / std::sqrt((double)n)); }
 
 struct Block {
-    void *wqkv = nullptr, *wo = nullptr, *w1 = nullptr, *w2 = nullptr;  // packed (W^T int8 + Cw)
+    // packed (W^T int8 + Cw); on a gated stack w1 is [W1 | W3], d_model x 2 d_ff, gate and up in ONE GEMM
+    void *wqkv = nullptr, *wo = nullptr, *w1 = nullptr, *w2 = nullptr;
     void *wq2 = nullptr, *wkv2 = nullptr, *wo2 = nullptr;               // cross
-    float *b1 = nullptr, *b2 = nullptr;
+    float *b1 = nullptr, *b2 = nullptr;  // (gated: b1 is [b1 | b3], 2 d_ff floats)
     // the standard architecture's vectors, ONE allocation `sp` (nullptr on a reference stack, and so is every pointer
     // into it: a nullptr bias is the reference's GEMM call): [bqkv: 3d][bo][g1][be1][g3][be3] and with cross-attention
     // [bq2][bkv2: 2d][bo2][g2][be2] -- the order of kinds 12 .. 25, the fused biases side by side as their fused
@@ -184,6 +205,10 @@ struct Stack {
     int n_slots = 1;        // sequences the caches hold side by side (qgemm_decoder_create_slots)
     bool standard = false;  // the post-LN block with biases, block-input residuals and a real LayerNorm
     bool gelu = false;      // standard: the FFN's activation is the tanh-form GELU, fused into the pack in front of W2
+    // standard: every norm is the RMS one, gamma alone; the FFN is (act(x W1 + b1) * (x W3 + b3)) W2 + b2,
+    // act the stack's activation, applied by glu.hip's pack in front of W2 (gelu is false on a gated stack)
+    bool rms = false, gated = false;
+    int activation = 0;     // as created: QGEMM_ACT_*
     float ln_eps = 0.0f;    // standard: every LN's epsilon
     // standard: the pre-LN block -- every sub-layer normalises its own input and adds its output to
     // the un-normalised stream -- and whether LNf follows the last block; fn = [gamma_f][beta_f], final_norm only
@@ -294,15 +319,17 @@ hipError_t stack_create(int d_model, int n_heads, int d_ff, int n_blocks, int ma
     const bool cross = decoder && !(arch & kArchDecoderOnly);
     if (decoder && !cross && max_enc_seq != 0) return hipErrorInvalidValue;
     if ((arch & kArchRope) && (n_heads < 1 || d_model % n_heads || (d_model / n_heads) % 2)) return hipErrorInvalidValue;
-    if (!stack_arch_ok(arch, decoder) || (activation != 0 && activation != 1) || ((arch & 0xff) == 0 && activation != 0) ||
-        !(ln_eps >= 0.0f) || (activation == 1 && d_ff > 16384))  // (the GELU pack's row limit)
+    if (!stack_arch_ok(arch, decoder) || !stack_activation_ok(arch, activation, d_ff) || !(ln_eps >= 0.0f))
         return hipErrorInvalidValue;
+    // what the W1 GEMM writes per row: d_ff floats, on a gated stack gate and up side by side
+    const bool gated = (arch & kArchGated) != 0;
+    const int64_t ffw = gated ? 2 * (int64_t)d_ff : d_ff;
     // max_rows: the row-local kernels (pack, GEMM epilogue, add + layernorm) address an activation buffer of
-    // scratch_rows x 3 d_model or x d_ff floats and its packed image of rows padded to 256 x columns padded to 128;
+    // scratch_rows x 3 d_model or x ffw floats and its packed image of rows padded to 256 x columns padded to 128;
     // with that padded product inside int32 no element index leaves its type, whichever type a kernel forms it in
     if (max_rows < 0) return hipErrorInvalidValue;
     if (max_rows > 0 && d_model >= 2 && d_ff >= 2 &&
-        (((int64_t)max_rows + 255) & ~(int64_t)255) * (((int64_t)std::max(3 * (int64_t)d_model, (int64_t)d_ff) + 127) & ~(int64_t)127) > INT32_MAX)
+        (((int64_t)max_rows + 255) & ~(int64_t)255) * ((std::max(3 * (int64_t)d_model, ffw) + 127) & ~(int64_t)127) > INT32_MAX)
         return hipErrorInvalidValue;
     if (kv_cache && !causal) return hipErrorInvalidValue;
     if (n_slots < 1 || n_slots > kDecodeMaxBatch || (n_slots > 1 && !(decoder && kv_cache))) return hipErrorInvalidValue;
@@ -327,7 +354,10 @@ hipError_t stack_create(int d_model, int n_heads, int d_ff, int n_blocks, int ma
     S->norm_first = (arch & kArchNormFirst) != 0;
     S->final_norm = (arch & kArchFinalNorm) != 0;
     S->arch = arch;
-    S->gelu = activation == 1;
+    S->rms = (arch & kArchRms) != 0;
+    S->gated = gated;
+    S->activation = activation;
+    S->gelu = activation == kActGelu && !gated;
     S->ln_eps = ln_eps;
     S->seed = seed;
     S->max_rows = max_rows;
@@ -355,13 +385,13 @@ hipError_t stack_create(int d_model, int n_heads, int d_ff, int n_blocks, int ma
         (e = alloc_f(&S->scores, (size_t)n_heads * (size_t)max_seq * (size_t)max_kv)))
         return fail(e);
     if ((e = alloc_f(&S->qkv, Sq * 3 * d)) || (e = alloc_f(&S->heads, Sq * d)) ||
-        (e = alloc_f(&S->t, Sq * d)) || (e = alloc_f(&S->ffn, Sq * d_ff)) || (e = alloc_f(&S->x, Sq * d)) ||
+        (e = alloc_f(&S->t, Sq * d)) || (e = alloc_f(&S->ffn, Sq * (size_t)ffw)) || (e = alloc_f(&S->x, Sq * d)) ||
         (e = alloc_f(&S->xa, Sq * d)) || (e = alloc_f(&S->xb, Sq * d)))
         return fail(e);
     if (cross && ((e = alloc_f(&S->q2, Sq * d)) || (e = alloc_f(&S->kv2, Se * 2 * d)) || (e = alloc_f(&S->heads2, Sq * d))))
         return fail(e);
     // workspace: split-K scratch for the largest of the linear shapes + the packed activations (+ the packed enc_out)
-    const int shapes[5][3] = {{rows, 3 * d, d}, {rows, d, d}, {rows, d_ff, d}, {rows, d, d_ff},
+    const int shapes[5][3] = {{rows, 3 * d, d}, {rows, d, d}, {rows, (int)ffw, d}, {rows, d, d_ff},
                               {S->max_enc_seq, 2 * d, d}};  // (m, n, k); the last one exists only with cross
     size_t scratch = 0;
     for (int i = 0; i < (cross ? 5 : 4); ++i)
@@ -382,7 +412,7 @@ hipError_t stack_create(int d_model, int n_heads, int d_ff, int n_blocks, int ma
 
     // weights, drawn once with the reference's init bounds (attention.cuh:37-41, linear.cuh:34-39,
     // transformer.cu:53, :120, :144) and packed
-    const size_t maxk = std::max(d, d_ff), maxn = std::max(3 * d, d_ff);
+    const size_t maxk = std::max(d, d_ff), maxn = std::max<size_t>(3 * d, ffw);
     float *tmp = nullptr;
     if ((e = alloc_f(&tmp, maxk * maxn + maxk * maxn))) return fail(e);
     hipStream_t s = nullptr;
@@ -402,9 +432,13 @@ hipError_t stack_create(int d_model, int n_heads, int d_ff, int n_blocks, int ma
             if ((e = encoder_make_packed(d, 2 * d, head_seeds(kWk2, kWv2), dk, bk, &B.wkv2, tmp, s))) break;
             if ((e = encoder_make_packed(d, d, {encoder_weight_seed(seed, i, kWo2, 0)}, d, 1.0f, &B.wo2, tmp, s))) break;
         }
-        if ((e = encoder_make_packed(d, d_ff, {encoder_weight_seed(seed, i, kW1, 0)}, d_ff, bd, &B.w1, tmp, s))) break;
+        // gated: [W1 | W3], the up projection W3 drawn as a tensor of its own with W1's bound; b3 = +0
+        std::vector<uint64_t> w1_seeds = {encoder_weight_seed(seed, i, kW1, 0)};
+        if (gated) w1_seeds.push_back(encoder_weight_seed(seed, i, kW3, 0));
+        if ((e = encoder_make_packed(d, (int)ffw, w1_seeds, d_ff, bd, &B.w1, tmp, s))) break;
         if ((e = encoder_make_packed(d_ff, d, {encoder_weight_seed(seed, i, kW2, 0)}, d, bf, &B.w2, tmp, s))) break;
-        if ((e = alloc_f(&B.b1, d_ff)) || (e = alloc_f(&B.b2, d))) break;
+        if ((e = alloc_f(&B.b1, (size_t)ffw)) || (e = alloc_f(&B.b2, d))) break;
+        if (gated && (e = hipMemsetAsync(B.b1 + d_ff, 0, sizeof(float) * d_ff, s))) break;
         if (kv_cache && ((e = alloc_f(&B.qkv_cache, (size_t)n_slots * max_seq * 3 * d)) ||
                          (cross && (e = alloc_f(&B.kv2_cache, (size_t)n_slots * Se * 2 * d)))))
             break;
@@ -656,16 +690,35 @@ hipError_t boundary_reference(Stack &S, int i, Boundary where, int rows, Carry &
                     : launch_add_layernorm_rows(S.t, mho, out, rows, d, s);
 }
 
+// The stack's norm in its three forms, ONE launch each: the LayerNorm with gamma and beta, or on an RMSNORM stack
+//  the RMS norm with gamma alone -- the same kernel's other instantiation, beta never read
+hipError_t norm_rows(Stack &S, const float *A, const float *B, const float *g, const float *be, float *Y, int rows,
+                     hipStream_t s) {
+    return S.rms ? launch_rmsnorm_rows(A, B, g, S.ln_eps, Y, rows, S.d_model, s)
+                 : launch_layernorm_rows(A, B, g, be, S.ln_eps, Y, rows, S.d_model, s);
+}
+hipError_t norm_rows_pack(Stack &S, const float *A, const float *B, const float *g, const float *be, float *Y, int rows,
+                          const PackedView &va, hipStream_t s) {
+    return S.rms ? launch_rmsnorm_rows_pack(A, B, g, S.ln_eps, Y, rows, S.d_model, 127.0f, va, s)
+                 : launch_layernorm_rows_pack(A, B, g, be, S.ln_eps, Y, rows, S.d_model, 127.0f, va, s);
+}
+hipError_t prenorm_pack(Stack &S, const float *A, const float *B, const float *g, const float *be, float *res, int rows,
+                        hipStream_t s) {
+    const PackedView va = act_view(S, rows, S.d_model);
+    return S.rms ? launch_prenorm_rms_pack(A, B, g, S.ln_eps, res, rows, S.d_model, 127.0f, va, s)
+                 : launch_prenorm_pack(A, B, g, be, S.ln_eps, res, rows, S.d_model, 127.0f, va, s);
+}
+
 // post-LN: x1 = LN1(in + t), x2 = LN2(x1 + t) in place over x1, y = LN3(x + t) with x the FFN's own input
 hipError_t boundary_post_ln(Stack &S, int i, Boundary where, int rows, Carry &c, float *Y, hipStream_t s) {
     const int d = S.d_model;
     const Block &B = S.blocks[i];
     const PackedView va = act_view(S, rows, d);
-    if (where == kAfterWo) return launch_layernorm_rows_pack(S.t, c.in, B.g1, B.be1, S.ln_eps, S.x, rows, d, 127.0f, va, s);
-    if (where == kAfterWo2) return launch_layernorm_rows_pack(S.t, S.x, B.g2, B.be2, S.ln_eps, S.x, rows, d, 127.0f, va, s);
+    if (where == kAfterWo) return norm_rows_pack(S, S.t, c.in, B.g1, B.be1, S.x, rows, va, s);
+    if (where == kAfterWo2) return norm_rows_pack(S, S.t, S.x, B.g2, B.be2, S.x, rows, va, s);
     float *out = block_out(S, i, Y, c);
-    return c.packed ? launch_layernorm_rows_pack(S.t, S.x, B.g3, B.be3, S.ln_eps, out, rows, d, 127.0f, va, s)
-                    : launch_layernorm_rows(S.t, S.x, B.g3, B.be3, S.ln_eps, out, rows, d, s);
+    return c.packed ? norm_rows_pack(S, S.t, S.x, B.g3, B.be3, out, rows, va, s)
+                    : norm_rows(S, S.t, S.x, B.g3, B.be3, out, rows, s);
 }
 
 // pre-LN: stream += t, the LN in front of the NEXT sub-layer -- LN2, LN3 (after W_O too in an encoder),
@@ -675,13 +728,12 @@ hipError_t boundary_pre_ln(Stack &S, int i, Boundary where, int rows, Carry &c, 
     const int d = S.d_model;
     const float *res = c.res;
     if (where == kAfterW2 && i == S.n_blocks - 1)
-        return S.final_norm ? launch_layernorm_rows(res, S.t, S.fn, S.fn + d, S.ln_eps, Y, rows, d, s)
-                            : launch_add_rows(res, S.t, Y, rows, d, s);
+        return S.final_norm ? norm_rows(S, res, S.t, S.fn, S.fn + d, Y, rows, s) : launch_add_rows(res, S.t, Y, rows, d, s);
     const Block &B = S.blocks[where == kAfterW2 ? i + 1 : i];
     const bool ln2 = where == kAfterWo && S.cross;
     const float *g = where == kAfterW2 ? B.g1 : ln2 ? B.g2 : B.g3, *be = where == kAfterW2 ? B.be1 : ln2 ? B.be2 : B.be3;
     c.res = S.x;
-    return launch_prenorm_pack(res, S.t, g, be, S.ln_eps, S.x, rows, d, 127.0f, act_view(S, rows, d), s);
+    return prenorm_pack(S, res, S.t, g, be, S.x, rows, s);
 }
 
 // One pass over the blocks on the p.rows rows of X into Y: the block of the header, once and in order.  The pass kind is
@@ -694,9 +746,7 @@ hipError_t run_blocks(Stack *S, const Pass &p, const float *X, float *Y, hipStre
     Carry c = {X, false, X};
     hipError_t e;
     if (S->norm_first) {  // LN1 of block 0 on X as it is: no add, nothing to store
-        if ((e = launch_prenorm_pack(X, nullptr, S->blocks[0].g1, S->blocks[0].be1, S->ln_eps, nullptr, rows, d, 127.0f,
-                                     act_view(*S, rows, d), s)))
-            return e;
+        if ((e = prenorm_pack(*S, X, nullptr, S->blocks[0].g1, S->blocks[0].be1, nullptr, rows, s))) return e;
         c.packed = true;
     }
     for (int i = 0; i < S->n_blocks; ++i) {
@@ -716,10 +766,15 @@ hipError_t run_blocks(Stack *S, const Pass &p, const float *X, float *Y, hipStre
         }
         // ---- FFN: t = act(x W1 + b1) W2 + b2, bias and relu fused into the GEMMs.  GELU: W1 without relu, and the pack
         // in front of W2 applies GELU as it quantizes -- the launch count is the relu path's
-        if ((e = linear(*S, nullptr, rows, d, B.w1, S->d_ff, S->ffn, B.b1, !S->gelu, s))) return e;
-        if (S->gelu) {
+        // Gated: ONE GEMM on [W1 | W3] writes gate | up, glu.hip's pack activates the gate, multiplies
+        // by up and quantizes -- the same three launches, the product never written
+        const int ffw = S->gated ? 2 * S->d_ff : S->d_ff;
+        if ((e = linear(*S, nullptr, rows, d, B.w1, ffw, S->ffn, B.b1, !S->gelu && !S->gated, s))) return e;
+        if (S->gated || S->gelu) {
             const PackedView va = act_view(*S, rows, S->d_ff);
-            if ((e = launch_gelu_pack(S->ffn, S->d_ff, rows, S->d_ff, 127.0f, va, s))) return e;
+            if ((e = S->gated ? launch_glu_pack(S->ffn, ffw, rows, S->d_ff, S->activation, 127.0f, va, s)
+                              : launch_gelu_pack(S->ffn, S->d_ff, rows, S->d_ff, 127.0f, va, s)))
+                return e;
             if ((e = gemm(*S, va, rows, S->d_ff, B.w2, d, S->t, B.b2, false, s))) return e;
         } else if ((e = linear(*S, S->ffn, rows, S->d_ff, B.w2, d, S->t, B.b2, false, s))) {
             return e;
@@ -1102,6 +1157,8 @@ struct WeightPlace {
 };
 
 bool weight_kind_ok(const Stack *S, int kind) {
+    if (kind >= kW3) return S->gated && kind <= kB3;  // the up projection and its bias of a gated stack
+    if (S->rms && (kind == kBe1 || kind == kBe2 || kind == kBe3 || kind == kBef)) return false;  // an RMS norm has no beta
     if (kind >= kRopeCos) return S->rope && kind <= kRopeSin;  // the rotary tables of a stack that has them
     if (kind >= kGf) return S->final_norm && kind <= kBef;  // the final norm of a pre-LN stack that has one
     if (kind >= kBq) return S->standard && kind <= (S->cross ? kBe2 : kBe3);  // a reference stack lacks them
@@ -1110,12 +1167,14 @@ bool weight_kind_ok(const Stack *S, int kind) {
 bool weight_per_head(int kind) { return (kind >= kWq && kind <= kWv) || (kind >= kWq2 && kind <= kWv2); }
 
 bool weight_place(const Stack *S, const Block &B, int kind, int head, WeightPlace *p) {
-    const int d = S->d_model, dk = d / S->n_heads, ff = S->d_ff;
+    const int d = S->d_model, dk = d / S->n_heads, ff = S->d_ff, ffw = S->gated ? 2 * ff : ff;
     if (!weight_kind_ok(S, kind) || head < 0 || head >= (weight_per_head(kind) ? S->n_heads : 1)) return false;
     switch (kind) {
         case kWq: case kWk: case kWv: *p = {B.wqkv, nullptr, d, 3 * d, (kind - kWq) * d + head * dk, dk}; break;
         case kWo: *p = {B.wo, nullptr, d, d, 0, d}; break;
-        case kW1: *p = {B.w1, nullptr, d, ff, 0, ff}; break;
+        case kW1: *p = {B.w1, nullptr, d, ffw, 0, ff}; break;  // (gated: the gate, the left half of [W1 | W3])
+        case kW3: *p = {B.w1, nullptr, d, ffw, ff, ff}; break;
+        case kB3: *p = {nullptr, B.b1 + ff, 1, ff, 0, ff}; break;
         case kB1: *p = {nullptr, B.b1, 1, ff, 0, ff}; break;
         case kW2: *p = {B.w2, nullptr, ff, d, 0, d}; break;
         case kB2: *p = {nullptr, B.b2, 1, d, 0, d}; break;
@@ -1153,7 +1212,7 @@ hipError_t stack_set_weight(Stack *S, int block, int kind, int head, const void 
                             hipStream_t s) {
     WeightPlace p;
     if (!S || block < 0 || block >= S->n_blocks || !W || (dtype != 0 && dtype != 1) || sh < 0 || sw < 0 ||
-        (kind >= kGf && block != 0) || !weight_place(S, S->blocks[block], kind, head, &p))
+        (kind >= kGf && kind <= kRopeSin && block != 0) || !weight_place(S, S->blocks[block], kind, head, &p))
         return hipErrorInvalidValue;
     hipError_t e = hipSuccess;
     if (p.bias) {  // a bias is one row; a rotary table max_seq of them, one copy each
@@ -1180,11 +1239,11 @@ hipError_t stack_packed_weight(const Stack *S, int block, int which, const void 
     if (!S || block < 0 || block >= S->n_blocks || which < 0 || which > (S->cross ? 6 : 3) || !packed)
         return hipErrorInvalidValue;
     const Block &B = S->blocks[block];
-    const int d = S->d_model, ff = S->d_ff;
+    const int d = S->d_model, ff = S->d_ff, ffw = S->gated ? 2 * ff : ff;  // (gated: which = 2 is [W1 | W3])
     const struct {
         const void *p;
         int n, k;
-    } w[7] = {{B.wqkv, 3 * d, d}, {B.wo, d, d}, {B.w1, ff, d}, {B.w2, d, ff}, {B.wq2, d, d}, {B.wkv2, 2 * d, d}, {B.wo2, d, d}};
+    } w[7] = {{B.wqkv, 3 * d, d}, {B.wo, d, d}, {B.w1, ffw, d}, {B.w2, d, ff}, {B.wq2, d, d}, {B.wkv2, 2 * d, d}, {B.wo2, d, d}};
     *packed = w[which].p;
     if (n) *n = w[which].n;
     if (k) *k = w[which].k;
@@ -1195,7 +1254,8 @@ hipError_t stack_packed_weight(const Stack *S, int block, int which, const void 
 // block 0's), n floats on the device
 hipError_t stack_bias(const Stack *S, int block, int kind, const float **bias, int *n) {
     WeightPlace p;
-    if (!S || block < 0 || block >= S->n_blocks || !bias || (kind >= kGf && block != 0) || kind >= kRopeCos ||
+    if (!S || block < 0 || block >= S->n_blocks || !bias || (kind >= kGf && kind <= kBef && block != 0) ||
+        kind == kRopeCos || kind == kRopeSin ||
         !weight_place(S, S->blocks[block], kind, 0, &p) || !p.bias)
         return hipErrorInvalidValue;
     *bias = p.bias;
@@ -1219,7 +1279,7 @@ hipError_t stack_describe(const Stack *S, StackDesc *out) {
     // (QGEMM_DECODER_CAUSAL = 1, QGEMM_DECODER_KV_CACHE = 8, include/qgemm.h)
     *out = StackDesc{S->decoder, S->d_model, S->n_heads, S->d_ff, S->n_blocks, S->max_seq, S->max_enc_seq, S->seed,
                      (S->causal ? 1 : 0) | (S->kv_cache ? 8 : 0), S->n_slots, S->max_rows, S->arch,
-                     S->gelu ? 1 : 0, S->ln_eps};
+                     S->activation, S->ln_eps};
     return hipSuccess;
 }
 
