@@ -208,8 +208,9 @@ QGEMM_API int qgemm_encoder_destroy(void *encoder);
  * One fused launch (the scores stay on chip) for d_k <= 64 and seq_kv <= 512, any seq_q; outside that three
  * launches through `workspace`, n_heads x seq_q x seq_kv floats of scores: qgemm_attention_workspace_size returns
  * that size in bytes, 0 inside the fused envelope (workspace may then be NULL) and 0 for invalid dimensions.
- * (seq_q <= 8 with d_k <= 64 takes a launch of its own, up to 4096 keys, which leaves the workspace untouched:
- * qgemm_attention_plan below.  The workspace rules do not change with it.)
+ * (seq_q <= 8 with d_k <= 64, or with d_k 96 or 128, takes a launch of its own, up to 4096 keys, which leaves the
+ * workspace untouched: qgemm_attention_plan below.  The workspace rules do not change with it: at d_k 96 / 128 every
+ * shape still has to bring the workspace.)
  * The call allocates nothing and makes no host synchronization.
  * hipErrorInvalidValue before any launch: a null Q / K / V / O, seq_q < 0, seq_kv < 1, n_heads < 1, d_k < 1,
  * seq_kv > 4096 (qgemm_softmax_rows' row limit), a short workspace or, on the three launches only, a row stride
@@ -241,7 +242,8 @@ QGEMM_API int qgemm_attention_causal(const float *Q, int64_t q_stride_h, const f
                            void *workspace, size_t ws_bytes, void *stream);
 /* Diagnostics: the launch qgemm_attention / qgemm_attention_causal take for a shape, with or without a mask.  Returns
  * 0 and, when kernel is non-NULL, a static string in *kernel that begins "attention_decode" (seq_q <= 8, d_k <= 64:
- * one workgroup per (head, query row), up to 4096 keys -- a decoding step), "attention_fused" (d_k <= 64,
+ * one workgroup per (head, query row), up to 4096 keys -- a decoding step; "attention_decode_wide_kernel" is the same
+ * launch at d_k 96 or 128; any other d_k above 64 has no decode launch), "attention_fused" (d_k <= 64,
  * seq_kv <= 512) or "three_launches"; hipErrorInvalidValue for dimensions the calls refuse.  Every path gives the
  * same bits.  qgemm_attention_workspace_size does not depend on it: the decode launch leaves a workspace it is
  * handed untouched, and a shape outside the fused envelope still has to bring one.  Needs no GPU. */
@@ -308,7 +310,7 @@ QGEMM_API int qgemm_decoder_destroy(void *decoder);
  * qgemm_attention_causal with q_pos0[b] gives on those query rows and the seq_kv[b] rows of slab kv_slot[b].  Two
  * sequences may share a slab.  O must not overlap Q, K or V (not checked).
  * hipErrorInvalidValue before any launch: a null Q / K / V / O / seq_kv, n_seqs < 0 or > 64, rows_per_seq < 1 or > 8,
- * d_k < 1 or > 64, n_heads < 1, any seq_kv[b] < 1 or > 4096, any q_pos0[b] < 0, any kv_slot[b] < 0; n_seqs == 0
+ * d_k < 1 or outside both decode envelopes (d_k <= 64; d_k 96 or 128), n_heads < 1, any seq_kv[b] < 1 or > 4096, any q_pos0[b] < 0, any kv_slot[b] < 0; n_seqs == 0
  * returns 0. */
 enum { QGEMM_DECODE_MAX_BATCH = 64 };
 QGEMM_API int qgemm_attention_decode_batched(const float *Q, int64_t q_stride_h,
@@ -334,7 +336,7 @@ QGEMM_API int qgemm_attention_decode_batched(const float *Q, int64_t q_stride_h,
  *               (per-row quantization scales, exact int32 accumulation, per-element dequantization, one-row layernorm),
  *               and the attention of all sequences is one qgemm_attention_decode_batched launch over the cache slabs.
  *               On success filled[slots[b]] = pos[b] + r; an earlier pos rewinds that sequence alone.  Needs
- *               d_model / n_heads <= 64.  The Q third of the cache rows it writes is unspecified.
+ *               d_model / n_heads <= 64, or 96 or 128 (the decode launch's envelopes).  The Q third of the cache rows it writes is unspecified.
  *   copy_slot   forks a sequence: rows 0 .. filled - 1 of every block's self cache and rows 0 .. enc_seq - 1 of its
  *               cross cache, device to device in stream order; dst takes src's enc_seq and filled length.
  *   slot_state  the host state of a slot (enc_seq 0: not begun); enc_seq / filled may be NULL.  No GPU call.
@@ -342,7 +344,8 @@ QGEMM_API int qgemm_attention_decode_batched(const float *Q, int64_t q_stride_h,
  * still does one thing at a time.  forward on a slotted decoder touches no cache.
  * hipErrorInvalidValue before any launch and without moving any filled length: a decoder without the cache flag, a
  * null pointer, a slot out of range or not begun (begin_slot: out of range), the same slot twice in one step_batch,
- * pos[b] < 0, pos[b] > filled, pos[b] + r > max_seq, n_seqs or rows_per_seq out of range, d_k > 64 (step_batch);
+ * pos[b] < 0, pos[b] > filled, pos[b] + r > max_seq, n_seqs or rows_per_seq out of range, d_k outside the
+ * decode envelopes (step_batch: d_k <= 64, 96 or 128);
  * copy_slot with dst == src or a source not begun; create_slots with other flags, n_slots < 1 or > 64 or a null
  * handle (the handle is left NULL). */
 QGEMM_API int qgemm_decoder_create_slots(int d_model, int n_heads, int d_ff, int n_blocks, int max_seq, int max_enc_seq,
@@ -493,7 +496,8 @@ QGEMM_API int qgemm_head_destroy(void *head);
  * hipErrorInvalidValue before any launch and without moving any filled length: a null pointer, a decoder without
  * caches, a head without E or of another d_model, n_seqs < 1, > n_slots or > the head's max_rows, n_new < 0, a slot out
  * of range, not begun or named twice, pos[b] < 0, pos[b] > filled, pos[b] + n_new > max_seq (or > the head's max_pos
- * with a P), d_model / n_heads > 64 (step_batch).  n_new == 0 returns 0. */
+ * with a P), d_model / n_heads outside step_batch's envelope (<= 64, 96 or 128; the same for qgemm_decoder_generate_sampled,
+ * _generate_beam and _generate_beam_indirect).  n_new == 0 returns 0. */
 QGEMM_API int qgemm_decoder_generate(void *decoder, void *head, int n_seqs, const int *slots, const int32_t *tokens_in,
                            int n_new, const int *pos, int32_t *tokens_out, void *stream);
 
@@ -1079,7 +1083,8 @@ QGEMM_API int qgemm_rope_rows_varlen(float *X, int64_t stride_h, int groups, int
  * Two more modifier bits on qgemm_model_desc.arch, which does not grow, valid on QGEMM_ARCH_STANDARD only; either
  * combines with post-LN or pre-LN, with an encoder, a decoder or a decoder-only model, and with or without ROPE.  Bit
  * 0x1000 is NOT a bit of arch and stays refused, as does every bit from 0x8000 up.  Grouped-query attention is not
- * part of this: n_kv_heads = n_heads (the Llama-1 / Llama-2 7B and 13B shape).
+ * part of this: n_kv_heads = n_heads (the Llama-1 / Llama-2 7B and 13B shape, whose d_k = 128 the decode launches,
+ * qgemm_decoder_step_batch* and qgemm_decoder_generate* take since the wide decode kernel).
  *
  * QGEMM_ARCH_RMSNORM: every norm of the model -- LN1, LN2, LN3 and the final norm -- is the root-mean-square norm of
  * Llama, Mistral, Qwen, Gemma and T5, with gamma alone.  The beta kinds 17, 19, 25 and 27 do not exist on such a model:

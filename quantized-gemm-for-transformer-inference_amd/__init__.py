@@ -1638,7 +1638,8 @@ def attention(Q, K, V, n_heads: int, scale=None, O=None, causal: bool = False, q
     tensors or views with unit inner stride (column slices of wider buffers included); O (seq_q x d) must not
     overlap them.  scale defaults to fl32(1 / sqrt(d_k)), as the encoder computes it.  One fused launch for
     d_k <= 64 and seq_kv <= 512, else three launches through a scores workspace allocated here; at most 8 query rows
-    with d_k <= 64 take the decode launch instead, up to 4096 keys (attention_plan names the launch; the same bits).
+    with d_k <= 64, or with d_k 96 or 128, take the decode launch instead, up to 4096 keys (attention_plan names the
+    launch; the same bits).
     causal=True (qgemm_attention_causal): query row i sees keys 0 .. min(seq_kv, i + q_pos0 + 1) - 1, the masked
     columns of P are +0.  q_pos0 is the key position of query row 0; left out it is seq_kv - seq_q, the queries
     aligned to the end of the keys as with a key / value cache (seq_kv >= seq_q is then asserted)."""
@@ -1695,7 +1696,7 @@ def attention_decode_batched(Q, K, V, n_heads: int, seq_kv, q_pos0=None, kv_slot
     device tensors or views with unit inner stride; sequence b attends to rows 0 .. seq_kv[b] - 1 of slab kv_slot[b]
     (left out: slab b).  q_pos0 (one per sequence) masks as attention(causal=True, q_pos0=q_pos0[b]); left out there
     is no mask.  seq_kv, q_pos0 and kv_slot are host sequences of ints, read at the call.  Rows b * rows_per_seq .. of
-    the result equal attention() on that sequence's views bit for bit."""
+    the result equal attention() on that sequence's views bit for bit.  d_k <= 64, or 96 or 128."""
     import math
     import torch
     _require_device_f32(Q, "Q")

@@ -9,11 +9,14 @@ namespace qgemm {
 
 const char *attention_plan_name(int seq_q, int seq_kv, int dk) {
     if (attention_decode_ok(seq_q, seq_kv, dk)) return "attention_decode_kernel";
+    if (attention_decode_wide_ok(seq_q, seq_kv, dk)) return "attention_decode_wide_kernel";
     return attention_fused_ok(seq_kv, dk) ? "attention_fused_kernel" : "three_launches";
 }
 
 // scores only where some call can reach the three launches: never inside the fused envelope, and never with at most
-// kAttnDecodeMaxQ query rows inside the decode envelope (a call of fewer rows or keys needs none either way)
+// kAttnDecodeMaxQ query rows inside the decode envelope (a call of fewer rows or keys needs none either way).  The
+// wide decode envelope (d_k 96 / 128) is left out on purpose: a forward at those widths still runs the three launches,
+// and a decode-shaped public call brings the workspace as it did before the wide instantiation (which never touches it)
 bool attention_needs_scores(int max_q, int max_kv, int dk) {
     return !attention_fused_ok(max_kv, dk) && !attention_decode_ok(max_q, max_kv, dk);
 }
@@ -111,11 +114,11 @@ hipError_t launch_attention_batched(const float *Q, int64_t ldq, const float *K,
                                     int rows_per_seq, const int *kv_slot, const int *seq_kv, const int *q_pos0,
                                     int n_heads, int dk, float scale, hipStream_t stream) {
     if (!Q || !K || !V || !O || !seq_kv || n_seqs < 0 || n_seqs > kDecodeMaxBatch || n_heads < 1 ||
-        !attention_decode_ok(rows_per_seq, 1, dk) || rows_per_seq < 1 || dk < 1)
+        !attention_decode_any_ok(rows_per_seq, 1, dk) || rows_per_seq < 1 || dk < 1)
         return hipErrorInvalidValue;
     DecodeBatchTable tab = {};  // entries past n_seqs are never read; zeroed so the arguments are defined bytes
     for (int b = 0; b < n_seqs; ++b) {
-        if (seq_kv[b] < 1 || !attention_decode_ok(rows_per_seq, seq_kv[b], dk) || (q_pos0 && q_pos0[b] < 0) ||
+        if (seq_kv[b] < 1 || !attention_decode_any_ok(rows_per_seq, seq_kv[b], dk) || (q_pos0 && q_pos0[b] < 0) ||
             (kv_slot && kv_slot[b] < 0))
             return hipErrorInvalidValue;
         tab.kv_slot[b] = kv_slot ? kv_slot[b] : b;
@@ -138,12 +141,12 @@ hipError_t launch_attention_indirect(const float *Q, int64_t ldq, const float *K
                                      const int *tab_row, const int *seq_kv, const int *q_pos0, int n_heads, int dk,
                                      float scale, hipStream_t stream) {
     if (!Q || !K || !V || !O || !seq_kv || !row_slab || n_seqs < 0 || n_seqs > kDecodeMaxBatch || n_heads < 1 ||
-        !attention_decode_ok(rows_per_seq, 1, dk) || rows_per_seq < 1 || dk < 1 || n_slabs < 1 ||
+        !attention_decode_any_ok(rows_per_seq, 1, dk) || rows_per_seq < 1 || dk < 1 || n_slabs < 1 ||
         n_slabs > kDecodeMaxBatch)
         return hipErrorInvalidValue;
     DecodeBatchTable tab = {};  // kv_slot: the table row
     for (int b = 0; b < n_seqs; ++b) {
-        if (seq_kv[b] < 1 || !attention_decode_ok(rows_per_seq, seq_kv[b], dk) || (q_pos0 && q_pos0[b] < 0) ||
+        if (seq_kv[b] < 1 || !attention_decode_any_ok(rows_per_seq, seq_kv[b], dk) || (q_pos0 && q_pos0[b] < 0) ||
             (tab_row && tab_row[b] < 0) || row_slab_stride < seq_kv[b])
             return hipErrorInvalidValue;
         tab.kv_slot[b] = tab_row ? tab_row[b] : b;

@@ -352,7 +352,7 @@ int generate_steps(void *decoder, void *head, int n_seqs, const int *slots, cons
     if (!h || !h->E || !slots || !tokens_in || n_new < 0 || decoder_limits(S, &d_model, &d_k, &max_seq, &n_slots))
         return (int)hipErrorInvalidValue;
     if (n_seqs < 1 || n_seqs > n_slots || n_seqs > h->max_rows || n_seqs > kEmbedMaxSeqs || d_model != h->d_model ||
-        d_k > 64 || (n_new > 0 && !tokens_out))
+        !attention_decode_any_ok(1, 1, d_k) || (n_new > 0 && !tokens_out))
         return (int)hipErrorInvalidValue;
     uint64_t counters[kEmbedMaxSeqs];
     SampleArgs a = {};
@@ -415,7 +415,7 @@ int generate_beam_steps(void *decoder, void *head, int n_groups, int beams, cons
         return (int)hipErrorInvalidValue;
     if (n_groups < 1 || head_beam_check(h, n_groups, beams) != hipSuccess ||
         n_groups * beams > kBeamGenerateMaxRows || 2 * n_groups * beams > n_slots || d_model != h->d_model ||
-        d_k > 64 || (n_new > 0 && (!tokens_out || !parents_out || !scores_out)))
+        !attention_decode_any_ok(1, 1, d_k) || (n_new > 0 && (!tokens_out || !parents_out || !scores_out)))
         return (int)hipErrorInvalidValue;
     const int rows = n_groups * beams;
     int at[kBeamGenerateMaxRows], next_rows[kBeamGenerateMaxRows];  // per row / per group
@@ -481,7 +481,7 @@ int generate_beam_indirect_steps(void *decoder, void *head, int n_groups, int be
         decoder_limits(S, &d_model, &d_k, &max_seq, &n_slots))
         return (int)hipErrorInvalidValue;
     if (n_groups < 1 || head_beam_check(h, n_groups, beams) != hipSuccess || n_groups * beams > kEmbedMaxSeqs ||
-        n_groups * beams > n_slots || d_model != h->d_model || d_k > 64 ||
+        n_groups * beams > n_slots || d_model != h->d_model || !attention_decode_any_ok(1, 1, d_k) ||
         (n_new > 0 && (!tokens_out || !parents_out || !scores_out)))
         return (int)hipErrorInvalidValue;
     const int rows = n_groups * beams;

@@ -344,8 +344,14 @@ hipError_t launch_attention_fused(const float *Q, int64_t ldq, const float *K, i
                                   float *O, int64_t ldo, int seq_q, int seq_kv, int n_heads, int dk, float scale,
                                   int q_pos0, hipStream_t stream);
 // The launch for a few query rows against up to 4096 keys (attention_decode.hip): one workgroup per (head, query
-// row), the same bits; hipErrorNotSupported outside attention_decode_ok (seq_q <= 8, seq_kv <= 4096, d_k <= 64).
+// row), the same bits; hipErrorNotSupported outside attention_decode_ok (seq_q <= 8, seq_kv <= 4096, d_k <= 64) and
+// attention_decode_wide_ok (the same rows and keys, d_k 96 or 128: the kernel's wide instantiation).
 bool attention_decode_ok(int seq_q, int seq_kv, int dk);
+bool attention_decode_wide_ok(int seq_q, int seq_kv, int dk);
+// either envelope: what the decode launches, the batched decoder steps and the generation loops accept
+inline bool attention_decode_any_ok(int seq_q, int seq_kv, int dk) {
+    return attention_decode_ok(seq_q, seq_kv, dk) || attention_decode_wide_ok(seq_q, seq_kv, dk);
+}
 hipError_t launch_attention_decode(const float *Q, int64_t ldq, const float *K, int64_t ldk, const float *V, int64_t ldv,
                                    float *O, int64_t ldo, int seq_q, int seq_kv, int n_heads, int dk, float scale,
                                    int q_pos0, hipStream_t stream);
@@ -398,7 +404,7 @@ hipError_t launch_attention_varlen(const float *Q, int64_t ldq, const float *K, 
                                    const int64_t *kv_row0, const int *seq_kv, const int *q_pos0, int n_heads, int dk,
                                    float scale, float *scores, hipStream_t stream);
 // the batched decode launch from host arrays of n_seqs entries (kv_slot nullptr: 0, 1, 2, ..; q_pos0 nullptr: no mask):
-// hipErrorInvalidValue before any launch outside n_seqs <= 64, 1 <= rows_per_seq <= 8, 1 <= d_k <= 64,
+// hipErrorInvalidValue before any launch outside n_seqs <= 64, 1 <= rows_per_seq <= 8, 1 <= d_k <= 64 or d_k 96 / 128,
 // 1 <= seq_kv[b] <= 4096, q_pos0[b] >= 0, kv_slot[b] >= 0; n_seqs == 0 launches nothing
 hipError_t launch_attention_batched(const float *Q, int64_t ldq, const float *K, int64_t ldk, int64_t k_stride_seq,
                                     const float *V, int64_t ldv, int64_t v_stride_seq, float *O, int64_t ldo, int n_seqs,

@@ -883,7 +883,8 @@ hipError_t decoder_step_batch(Stack *S, int n_seqs, const int *slots, const int 
         rows_per_seq < 1 || rows_per_seq > 8)
         return hipErrorInvalidValue;
     const int r = rows_per_seq;
-    if (!attention_decode_ok(r, 1, S->d_model / S->n_heads)) return hipErrorInvalidValue;  // d_k > 64: no batched launch
+    // d_k outside both decode envelopes (<= 64, or 96 / 128): no batched launch
+    if (!attention_decode_any_ok(r, 1, S->d_model / S->n_heads)) return hipErrorInvalidValue;
     // (n_seqs * r <= scratch_rows: n_seqs <= n_slots, and r <= max_seq with one slot)
     Pass p = {PassKind::Batch, n_seqs * r, n_seqs, r};
     uint64_t seen = 0;
@@ -1052,7 +1053,7 @@ hipError_t decoder_step_batch_indirect(Stack *S, int n_seqs, const int *slots, c
         rows_per_seq < 1 || rows_per_seq > 8)
         return hipErrorInvalidValue;
     const int r = rows_per_seq;
-    if (!attention_decode_ok(r, 1, S->d_model / S->n_heads)) return hipErrorInvalidValue;
+    if (!attention_decode_any_ok(r, 1, S->d_model / S->n_heads)) return hipErrorInvalidValue;
     Pass p = {PassKind::BatchIndirect, n_seqs * r, n_seqs, r};
     uint64_t seen = 0;
     for (int b = 0; b < n_seqs; ++b) {
