@@ -1157,6 +1157,57 @@ QGEMM_API int qgemm_glu_rows(const float *X, int64_t x_stride_h, float *Y, int64
 QGEMM_API int qgemm_glu_pack_a(const float *X, int64_t x_stride_h, int m, int k, int activation, float range,
                      void *packed_a, void *stream);
 
+/* ---- Grouped-query attention core ---------------------------------------------------------------
+ * The attention core above with n_kv_heads <= n_heads, n_heads % n_kv_heads == 0, G = n_heads / n_kv_heads: Q and O have
+ * n_heads * d_k columns, K and V have n_kv_heads * d_k, and query head h uses columns (h / G) * d_k .. of K and V
+ * (Hugging Face's repeat_kv, Meta's repeat_interleave; Llama 3, Mistral, Qwen2).  G = 1 is multi-head attention, G =
+ * n_heads multi-query attention.  The models' stacks (qgemm_model_create) do NOT take n_kv_heads yet: these are entry
+ * points for a caller that keeps its own K / V cache.
+ * Contract: nothing new numerically.  The rows of query head h are BIT FOR BIT what qgemm_attention (causal == 0),
+ * qgemm_attention_causal (causal != 0, with q_pos0), qgemm_attention_decode_batched or _indirect return on K and V with
+ * every head repeated G times -- the score chain from +0 over k ascending, zero-padded to 32; the softmax of
+ * qgemm_softmax_rows[_causal], its one sequential sum, its NaN behaviour; P V over ALL keys, masked keys included with
+ * P = +0; quiet NaNs for an indirect table entry that names no slab.  The caller saves the repeated copy: 1 / G of the
+ * cache memory and of the K / V bytes a decoding step reads.
+ * qgemm_attention_gqa takes one of three routes, named by qgemm_attention_gqa_plan (needs no GPU):
+ *   G == 1                                        exactly qgemm_attention[_causal]: its launch, its plan name and
+ *                                                 its workspace rule
+ *   seq_q <= 8, d_k <= 64 or d_k 96 / 128,        "attention_decode_gqa_kernel" / "attention_decode_gqa_wide_kernel": one
+ *   2 <= G <= 16                                  workgroup per (KV head, block of up to 4 query heads of its group,
+ *                                                 query row), every K / V row fetched ONCE for the block; no workspace
+ *   everything else (prefill, forward, G > 16)    "grouped_three_launches": the two batched fp32 GEMMs in G rounds of
+ *                                                 n_kv_heads batches and one softmax between them, through
+ *                                                 `workspace`, n_heads x seq_q x seq_kv floats -- also where
+ *                                                 qgemm_attention would take its fused launch
+ * qgemm_attention_gqa_workspace_size returns the bytes of the route (0 on the decode kernel, which leaves a workspace it
+ * is handed untouched; 0 for invalid dimensions).  Strides, aliasing, the mask and q_pos0 as qgemm_attention_causal;
+ * q_pos0 is ignored when causal == 0.  The call allocates nothing and makes no host synchronization.
+ * hipErrorInvalidValue before any launch: whatever qgemm_attention[_causal] refuses, n_kv_heads < 1,
+ * n_heads % n_kv_heads != 0.
+ * qgemm_attention_decode_batched_gqa / _indirect_gqa: qgemm_attention_decode_batched / _indirect with K and V slabs of
+ * n_kv_heads * d_k columns; every other argument, the tables in the kernel arguments and capturability are theirs.  They
+ * refuse what those refuse, n_kv_heads < 1, n_heads % n_kv_heads != 0 and G > 16; G == 1 is exactly those calls. */
+QGEMM_API size_t qgemm_attention_gqa_workspace_size(int seq_q, int seq_kv, int n_heads, int n_kv_heads, int d_k);
+QGEMM_API int qgemm_attention_gqa(const float *Q, int64_t q_stride_h, const float *K, int64_t k_stride_h,
+                        const float *V, int64_t v_stride_h, float *O, int64_t o_stride_h,
+                        int seq_q, int seq_kv, int n_heads, int n_kv_heads, int d_k, float scale,
+                        int causal, int q_pos0, void *workspace, size_t ws_bytes, void *stream);
+QGEMM_API int qgemm_attention_gqa_plan(int seq_q, int seq_kv, int n_heads, int n_kv_heads, int d_k,
+                             const char **kernel);
+QGEMM_API int qgemm_attention_decode_batched_gqa(const float *Q, int64_t q_stride_h,
+                                       const float *K, int64_t k_stride_h, int64_t k_stride_seq,
+                                       const float *V, int64_t v_stride_h, int64_t v_stride_seq,
+                                       float *O, int64_t o_stride_h, int n_seqs, int rows_per_seq,
+                                       const int *kv_slot, const int *seq_kv, const int *q_pos0,
+                                       int n_heads, int n_kv_heads, int d_k, float scale, void *stream);
+QGEMM_API int qgemm_attention_decode_indirect_gqa(const float *Q, int64_t q_stride_h,
+                                        const float *K, int64_t k_stride_h, int64_t k_stride_seq,
+                                        const float *V, int64_t v_stride_h, int64_t v_stride_seq,
+                                        float *O, int64_t o_stride_h, int n_seqs, int rows_per_seq,
+                                        const uint8_t *row_slab, int64_t row_slab_stride, int n_slabs,
+                                        const int *tab_row, const int *seq_kv, const int *q_pos0,
+                                        int n_heads, int n_kv_heads, int d_k, float scale, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -153,6 +153,11 @@ EXPORTED_SYMBOLS = (
     "qgemm_prenorm_rms_pack_a",
     "qgemm_glu_rows",
     "qgemm_glu_pack_a",
+    "qgemm_attention_gqa_workspace_size",
+    "qgemm_attention_gqa",
+    "qgemm_attention_gqa_plan",
+    "qgemm_attention_decode_batched_gqa",
+    "qgemm_attention_decode_indirect_gqa",
 )
 
 # Every symbol include/qgemm_dist.h declares (libqgemm_dist.so: M-shards + RCCL all-gather).
@@ -478,6 +483,19 @@ def load() -> ctypes.CDLL:
         L.qgemm_glu_rows.restype = i32
         L.qgemm_glu_pack_a.argtypes = [vp, i64, i32, i32, i32, f32, vp, vp]
         L.qgemm_glu_pack_a.restype = i32
+        L.qgemm_attention_gqa_workspace_size.argtypes = [i32, i32, i32, i32, i32]
+        L.qgemm_attention_gqa_workspace_size.restype = sz
+        L.qgemm_attention_gqa.argtypes = [vp, i64, vp, i64, vp, i64, vp, i64, i32, i32, i32, i32, i32, f32, i32, i32, vp,
+                                          sz, vp]
+        L.qgemm_attention_gqa.restype = i32
+        L.qgemm_attention_gqa_plan.argtypes = [i32, i32, i32, i32, i32, ctypes.POINTER(ctypes.c_char_p)]
+        L.qgemm_attention_gqa_plan.restype = i32
+        L.qgemm_attention_decode_batched_gqa.argtypes = [vp, i64, vp, i64, i64, vp, i64, i64, vp, i64, i32, i32, ip, ip,
+                                                         ip, i32, i32, i32, f32, vp]
+        L.qgemm_attention_decode_batched_gqa.restype = i32
+        L.qgemm_attention_decode_indirect_gqa.argtypes = [vp, i64, vp, i64, i64, vp, i64, i64, vp, i64, i32, i32, vp, i64,
+                                                          i32, ip, ip, ip, i32, i32, i32, f32, vp]
+        L.qgemm_attention_decode_indirect_gqa.restype = i32
         _lib = L
         return L
 
@@ -1632,7 +1650,14 @@ class Encoder(_ModelWeights):
             pass
 
 
-def attention(Q, K, V, n_heads: int, scale=None, O=None, causal: bool = False, q_pos0=None):
+def _kv_heads(n_heads: int, n_kv_heads) -> int:
+    """n_kv_heads of a grouped-query call (None: n_heads, multi-head attention)."""
+    n_kv = n_heads if n_kv_heads is None else int(n_kv_heads)
+    assert n_heads >= 1 and n_kv >= 1 and n_heads % n_kv == 0, "n_heads % n_kv_heads == 0"
+    return n_kv
+
+
+def attention(Q, K, V, n_heads: int, scale=None, O=None, causal: bool = False, q_pos0=None, n_kv_heads=None):
     """Multi-head fp32 attention core (qgemm_attention): O_h = softmax(Q_h K_h^T * scale) V_h on columns
     h*d_k .. of each matrix, d_k = Q.shape[1] / n_heads.  Q: seq_q x d, K and V: seq_kv x d -- 2-D fp32 device
     tensors or views with unit inner stride (column slices of wider buffers included); O (seq_q x d) must not
@@ -1642,7 +1667,10 @@ def attention(Q, K, V, n_heads: int, scale=None, O=None, causal: bool = False, q
     launch; the same bits).
     causal=True (qgemm_attention_causal): query row i sees keys 0 .. min(seq_kv, i + q_pos0 + 1) - 1, the masked
     columns of P are +0.  q_pos0 is the key position of query row 0; left out it is seq_kv - seq_q, the queries
-    aligned to the end of the keys as with a key / value cache (seq_kv >= seq_q is then asserted)."""
+    aligned to the end of the keys as with a key / value cache (seq_kv >= seq_q is then asserted).
+    n_kv_heads (grouped-query attention, qgemm_attention_gqa): K and V are seq_kv x n_kv_heads * d_k and
+    query head h reads their head h // (n_heads // n_kv_heads) -- the bits of this call on K / V with every head
+    repeated; attention_gqa_plan names the launch.  None or n_heads is exactly the call without it."""
     import math
     import torch
     for t, nm in ((Q, "Q"), (K, "K"), (V, "V")):
@@ -1650,9 +1678,10 @@ def attention(Q, K, V, n_heads: int, scale=None, O=None, causal: bool = False, q
         assert t.stride(1) == 1 or t.shape[1] == 1, f"{nm} must have unit inner stride"
     seq_q, d = Q.shape
     seq_kv = K.shape[0]
-    assert K.shape == (seq_kv, d) and V.shape == (seq_kv, d), "K and V: seq_kv x d, d as Q"
     assert n_heads >= 1 and d % n_heads == 0, "d % n_heads == 0"
     dk = d // n_heads
+    n_kv = _kv_heads(n_heads, n_kv_heads)
+    assert K.shape == (seq_kv, n_kv * dk) and V.shape == (seq_kv, n_kv * dk), "K and V: seq_kv x n_kv_heads * d_k"
     if scale is None:
         scale = ctypes.c_float(1.0 / math.sqrt(float(dk))).value  # attention.cuh:64
     if O is None:
@@ -1664,6 +1693,16 @@ def attention(Q, K, V, n_heads: int, scale=None, O=None, causal: bool = False, q
         assert seq_kv >= seq_q, "causal without q_pos0 aligns the queries to the end of the keys: seq_kv >= seq_q"
         q_pos0 = seq_kv - seq_q
     L = load()
+    if n_kv != n_heads:
+        assert not causal or q_pos0 >= 0
+        need = L.qgemm_attention_gqa_workspace_size(seq_q, seq_kv, n_heads, n_kv, dk)
+        ws = torch.empty(need, dtype=torch.uint8, device=Q.device) if need else None
+        _check("qgemm_attention_gqa",
+               L.qgemm_attention_gqa(Q.data_ptr(), Q.stride(0), K.data_ptr(), K.stride(0), V.data_ptr(), V.stride(0),
+                                     O.data_ptr(), O.stride(0), seq_q, seq_kv, n_heads, n_kv, dk, float(scale),
+                                     int(causal), q_pos0 if causal else 0, ws.data_ptr() if need else None, need,
+                                     _stream(Q.device)))
+        return O
     need = L.qgemm_attention_workspace_size(seq_q, seq_kv, n_heads, dk)
     ws = torch.empty(need, dtype=torch.uint8, device=Q.device) if need else None
     if causal:
@@ -1697,6 +1736,15 @@ def attention_decode_batched(Q, K, V, n_heads: int, seq_kv, q_pos0=None, kv_slot
     (left out: slab b).  q_pos0 (one per sequence) masks as attention(causal=True, q_pos0=q_pos0[b]); left out there
     is no mask.  seq_kv, q_pos0 and kv_slot are host sequences of ints, read at the call.  Rows b * rows_per_seq .. of
     the result equal attention() on that sequence's views bit for bit.  d_k <= 64, or 96 or 128."""
+    return attention_decode_batched_gqa(Q, K, V, n_heads, None, seq_kv, q_pos0, kv_slot, rows_per_seq, scale, O)
+
+
+def attention_decode_batched_gqa(Q, K, V, n_heads: int, n_kv_heads, seq_kv, q_pos0=None, kv_slot=None,
+                                 rows_per_seq: int = 1, scale=None, O=None):
+    """attention_decode_batched for grouped-query heads (qgemm_attention_decode_batched_gqa): K and V
+    are [slabs, rows, n_kv_heads * d_k] and query head h reads their head h // (n_heads // n_kv_heads), at most 16 query
+    heads per KV head -- the bits of attention_decode_batched on K / V with every head repeated.  n_kv_heads None or
+    n_heads is exactly attention_decode_batched."""
     import math
     import torch
     _require_device_f32(Q, "Q")
@@ -1706,11 +1754,12 @@ def attention_decode_batched(Q, K, V, n_heads: int, seq_kv, q_pos0=None, kv_slot
             f"{nm}: a 3-D float32 device tensor [slabs, rows, d]"
         assert t.stride(2) == 1 or t.shape[2] == 1, f"{nm} must have unit inner stride"
     rows, d = Q.shape
-    assert K.shape[2] == d and V.shape[2] == d, "K and V: [slabs, rows, d], d as Q"
     assert rows_per_seq >= 1 and rows % rows_per_seq == 0, "Q holds rows_per_seq rows per sequence"
     n_seqs = rows // rows_per_seq
     assert n_heads >= 1 and d % n_heads == 0, "d % n_heads == 0"
     dk = d // n_heads
+    n_kv = _kv_heads(n_heads, n_kv_heads)
+    assert K.shape[2] == n_kv * dk and V.shape[2] == n_kv * dk, "K and V: [slabs, rows, n_kv_heads * d_k]"
     seq_kv = [int(v) for v in seq_kv]
     slots = list(range(n_seqs)) if kv_slot is None else [int(v) for v in kv_slot]
     assert len(seq_kv) == n_seqs and len(slots) == n_seqs, "seq_kv and kv_slot: one entry per sequence"
@@ -1723,12 +1772,15 @@ def attention_decode_batched(Q, K, V, n_heads: int, seq_kv, q_pos0=None, kv_slot
         O = torch.empty((rows, d), dtype=torch.float32, device=Q.device)
     _require_device_f32(O, "O")
     assert O.shape == (rows, d) and (O.stride(1) == 1 or d == 1), "O: as Q, with unit inner stride"
+    head = (Q.data_ptr(), Q.stride(0), K.data_ptr(), K.stride(1), K.stride(0), V.data_ptr(), V.stride(1), V.stride(0),
+            O.data_ptr(), O.stride(0), n_seqs, rows_per_seq, _int_array(kv_slot, n_seqs, "kv_slot"),
+            _int_array(seq_kv, n_seqs, "seq_kv"), _int_array(q_pos0, n_seqs, "q_pos0"), n_heads)
+    if n_kv != n_heads:
+        _check("qgemm_attention_decode_batched_gqa",
+               load().qgemm_attention_decode_batched_gqa(*head, n_kv, dk, float(scale), _stream(Q.device)))
+        return O
     _check("qgemm_attention_decode_batched",
-           load().qgemm_attention_decode_batched(
-               Q.data_ptr(), Q.stride(0), K.data_ptr(), K.stride(1), K.stride(0), V.data_ptr(), V.stride(1),
-               V.stride(0), O.data_ptr(), O.stride(0), n_seqs, rows_per_seq, _int_array(kv_slot, n_seqs, "kv_slot"),
-               _int_array(seq_kv, n_seqs, "seq_kv"), _int_array(q_pos0, n_seqs, "q_pos0"), n_heads, dk, float(scale),
-               _stream(Q.device)))
+           load().qgemm_attention_decode_batched(*head, dk, float(scale), _stream(Q.device)))
     return O
 
 
@@ -1742,12 +1794,13 @@ def _require_row_table(t, name):
 
 
 def attention_decode_indirect(Q, K, V, n_heads: int, row_slab, seq_kv, q_pos0=None, tab_row=None,
-                              rows_per_seq: int = 1, scale=None, O=None):
+                              rows_per_seq: int = 1, scale=None, O=None, n_kv_heads=None):
     """attention_decode_batched through a per-row slab table (qgemm_attention_decode_indirect): K / V
     row j of sequence b is row j of slab row_slab[tab_row[b]][j] (tab_row left out: row b).  row_slab: a 2-D uint8
     device tensor or view [table rows, entries], unit inner stride, any row stride and alignment; an entry >= the
     number of slabs stands for a row of quiet NaNs.  Bit for bit attention_decode_batched on slabs gathered that
-    way."""
+    way.  n_kv_heads: as attention_decode_batched_gqa's (qgemm_attention_decode_indirect_gqa); None or n_heads is
+    exactly the call without it."""
     import math
     import torch
     _require_device_f32(Q, "Q")
@@ -1758,11 +1811,12 @@ def attention_decode_indirect(Q, K, V, n_heads: int, row_slab, seq_kv, q_pos0=No
         assert t.stride(2) == 1 or t.shape[2] == 1, f"{nm} must have unit inner stride"
     _require_row_table(row_slab, "row_slab")
     rows, d = Q.shape
-    assert K.shape[2] == d and V.shape[2] == d, "K and V: [slabs, rows, d], d as Q"
     assert rows_per_seq >= 1 and rows % rows_per_seq == 0, "Q holds rows_per_seq rows per sequence"
     n_seqs = rows // rows_per_seq
     assert n_heads >= 1 and d % n_heads == 0, "d % n_heads == 0"
     dk = d // n_heads
+    n_kv = _kv_heads(n_heads, n_kv_heads)
+    assert K.shape[2] == n_kv * dk and V.shape[2] == n_kv * dk, "K and V: [slabs, rows, n_kv_heads * d_k]"
     seq_kv = [int(v) for v in seq_kv]
     trows = list(range(n_seqs)) if tab_row is None else [int(v) for v in tab_row]
     assert len(seq_kv) == n_seqs and len(trows) == n_seqs, "seq_kv and tab_row: one entry per sequence"
@@ -1776,13 +1830,17 @@ def attention_decode_indirect(Q, K, V, n_heads: int, row_slab, seq_kv, q_pos0=No
         O = torch.empty((rows, d), dtype=torch.float32, device=Q.device)
     _require_device_f32(O, "O")
     assert O.shape == (rows, d) and (O.stride(1) == 1 or d == 1), "O: as Q, with unit inner stride"
+    head = (Q.data_ptr(), Q.stride(0), K.data_ptr(), K.stride(1), K.stride(0), V.data_ptr(), V.stride(1), V.stride(0),
+            O.data_ptr(), O.stride(0), n_seqs, rows_per_seq, row_slab.data_ptr(),
+            row_slab.stride(0) if row_slab.shape[0] > 1 else row_slab.shape[1], n_slabs,
+            _int_array(tab_row, n_seqs, "tab_row"), _int_array(seq_kv, n_seqs, "seq_kv"),
+            _int_array(q_pos0, n_seqs, "q_pos0"), n_heads)
+    if n_kv != n_heads:
+        _check("qgemm_attention_decode_indirect_gqa",
+               load().qgemm_attention_decode_indirect_gqa(*head, n_kv, dk, float(scale), _stream(Q.device)))
+        return O
     _check("qgemm_attention_decode_indirect",
-           load().qgemm_attention_decode_indirect(
-               Q.data_ptr(), Q.stride(0), K.data_ptr(), K.stride(1), K.stride(0), V.data_ptr(), V.stride(1),
-               V.stride(0), O.data_ptr(), O.stride(0), n_seqs, rows_per_seq, row_slab.data_ptr(),
-               row_slab.stride(0) if row_slab.shape[0] > 1 else row_slab.shape[1], n_slabs,
-               _int_array(tab_row, n_seqs, "tab_row"), _int_array(seq_kv, n_seqs, "seq_kv"),
-               _int_array(q_pos0, n_seqs, "q_pos0"), n_heads, dk, float(scale), _stream(Q.device)))
+           load().qgemm_attention_decode_indirect(*head, dk, float(scale), _stream(Q.device)))
     return O
 
 
@@ -1885,6 +1943,16 @@ def attention_plan(seq_q: int, seq_kv: int, n_heads: int, d_k: int) -> str:
     "attention_fused" or "three_launches".  Needs no GPU; raises QGemmError for dimensions attention() refuses."""
     name = ctypes.c_char_p()
     _check("qgemm_attention_plan", load().qgemm_attention_plan(seq_q, seq_kv, n_heads, d_k, ctypes.byref(name)))
+    return name.value.decode()
+
+
+def attention_gqa_plan(seq_q: int, seq_kv: int, n_heads: int, n_kv_heads: int, d_k: int) -> str:
+    """The launch attention(n_kv_heads=...) takes (qgemm_attention_gqa_plan): attention_plan's answer at n_kv_heads ==
+    n_heads, else "attention_decode_gqa_kernel", "attention_decode_gqa_wide_kernel" or "grouped_three_launches".
+    Needs no GPU; raises QGemmError for dimensions attention() refuses."""
+    name = ctypes.c_char_p()
+    _check("qgemm_attention_gqa_plan",
+           load().qgemm_attention_gqa_plan(seq_q, seq_kv, n_heads, n_kv_heads, d_k, ctypes.byref(name)))
     return name.value.decode()
 
 

@@ -576,6 +576,61 @@ int qgemm_attention_decode_indirect(const float *Q, int64_t q_stride_h, const fl
                                          seq_kv, q_pos0, n_heads, d_k, scale, static_cast<hipStream_t>(stream)));
 }
 
+// ---- grouped-query attention ----
+
+// G = 1: qgemm_attention's rule; else the grouped three launches' scores, nothing where the decode kernel runs
+size_t qgemm_attention_gqa_workspace_size(int seq_q, int seq_kv, int n_heads, int n_kv_heads, int d_k) {
+    if (seq_q < 0 || seq_kv < 1 || seq_kv > 4096 || n_heads < 1 || d_k < 1 || n_kv_heads < 1 || n_heads % n_kv_heads)
+        return 0;
+    if (n_kv_heads == n_heads) return qgemm_attention_workspace_size(seq_q, seq_kv, n_heads, d_k);
+    if (attention_decode_gqa_ok(seq_q, seq_kv, d_k, n_heads, n_kv_heads)) return 0;
+    return sizeof(float) * (size_t)n_heads * (size_t)seq_q * (size_t)seq_kv;
+}
+
+int qgemm_attention_gqa(const float *Q, int64_t q_stride_h, const float *K, int64_t k_stride_h, const float *V,
+                        int64_t v_stride_h, float *O, int64_t o_stride_h, int seq_q, int seq_kv, int n_heads,
+                        int n_kv_heads, int d_k, float scale, int causal, int q_pos0, void *workspace, size_t ws_bytes,
+                        void *stream) {
+    if (!Q || !K || !V || !O || seq_q < 0 || seq_kv < 1 || seq_kv > 4096 || n_heads < 1 || d_k < 1 || n_kv_heads < 1 ||
+        n_heads % n_kv_heads || (causal && q_pos0 < 0))
+        return err(hipErrorInvalidValue);
+    const size_t need = qgemm_attention_gqa_workspace_size(seq_q, seq_kv, n_heads, n_kv_heads, d_k);
+    if (need && (!workspace || ws_bytes < need)) return err(hipErrorInvalidValue);
+    if (seq_q == 0) return 0;
+    return err(launch_attention_gqa(Q, q_stride_h, K, k_stride_h, V, v_stride_h, O, o_stride_h, seq_q, seq_kv, n_heads,
+                                    n_kv_heads, d_k, scale, causal ? q_pos0 : kNoMask,
+                                    need ? static_cast<float *>(workspace) : nullptr, static_cast<hipStream_t>(stream)));
+}
+
+int qgemm_attention_gqa_plan(int seq_q, int seq_kv, int n_heads, int n_kv_heads, int d_k, const char **kernel) {
+    if (seq_q < 0 || seq_kv < 1 || seq_kv > 4096 || n_heads < 1 || d_k < 1 || n_kv_heads < 1 || n_heads % n_kv_heads)
+        return (int)hipErrorInvalidValue;
+    if (kernel) *kernel = attention_gqa_plan_name(seq_q, seq_kv, d_k, n_heads, n_kv_heads);
+    return 0;
+}
+
+int qgemm_attention_decode_batched_gqa(const float *Q, int64_t q_stride_h, const float *K, int64_t k_stride_h,
+                                       int64_t k_stride_seq, const float *V, int64_t v_stride_h, int64_t v_stride_seq,
+                                       float *O, int64_t o_stride_h, int n_seqs, int rows_per_seq, const int *kv_slot,
+                                       const int *seq_kv, const int *q_pos0, int n_heads, int n_kv_heads, int d_k,
+                                       float scale, void *stream) {
+    return err(launch_attention_batched_gqa(Q, q_stride_h, K, k_stride_h, k_stride_seq, V, v_stride_h, v_stride_seq, O,
+                                            o_stride_h, n_seqs, rows_per_seq, kv_slot, seq_kv, q_pos0, n_heads,
+                                            n_kv_heads, d_k, scale, static_cast<hipStream_t>(stream)));
+}
+
+int qgemm_attention_decode_indirect_gqa(const float *Q, int64_t q_stride_h, const float *K, int64_t k_stride_h,
+                                        int64_t k_stride_seq, const float *V, int64_t v_stride_h, int64_t v_stride_seq,
+                                        float *O, int64_t o_stride_h, int n_seqs, int rows_per_seq,
+                                        const uint8_t *row_slab, int64_t row_slab_stride, int n_slabs,
+                                        const int *tab_row, const int *seq_kv, const int *q_pos0, int n_heads,
+                                        int n_kv_heads, int d_k, float scale, void *stream) {
+    return err(launch_attention_indirect_gqa(Q, q_stride_h, K, k_stride_h, k_stride_seq, V, v_stride_h, v_stride_seq, O,
+                                             o_stride_h, n_seqs, rows_per_seq, row_slab, row_slab_stride, n_slabs,
+                                             tab_row, seq_kv, q_pos0, n_heads, n_kv_heads, d_k, scale,
+                                             static_cast<hipStream_t>(stream)));
+}
+
 int qgemm_decoder_beam_begin(void *decoder, int n_groups, int beams, const int *slots, const int *src_slots,
                              const int *pos, void *stream) {
     return err(decoder_beam_begin(static_cast<Stack *>(decoder), n_groups, beams, slots, src_slots, pos,

@@ -159,4 +159,112 @@ hipError_t launch_attention_indirect(const float *Q, int64_t ldq, const float *K
                                             n_heads, dk, scale, stream);
 }
 
+// ---- grouped-query attention ----
+
+const char *attention_gqa_plan_name(int seq_q, int seq_kv, int dk, int n_heads, int n_kv_heads) {
+    if (n_heads == n_kv_heads) return attention_plan_name(seq_q, seq_kv, dk);
+    if (!attention_decode_gqa_ok(seq_q, seq_kv, dk, n_heads, n_kv_heads)) return "grouped_three_launches";
+    return attention_decode_ok(seq_q, seq_kv, dk) ? "attention_decode_gqa_kernel" : "attention_decode_gqa_wide_kernel";
+}
+
+// q_pos0: kNoMask or the causal mask's offset.  Outside the decode kernel's envelope: launch_attention's three launches
+// with batch = n_kv_heads, in G rounds.  Round j serves head j of every group: Q, O and the scores start j heads in and
+// step a whole group per batch (G d_k columns, G seq_q x seq_kv scores), K and V step one KV head.  The scores end up
+// laid out as launch_attention's, so ONE softmax runs over all n_heads x seq_q rows between the GEMM rounds.  Each
+// head's GEMMs are launch_mm_f32_batched's on the operands launch_attention would hand it with K / V repeated, and the
+// fp32 GEMM gives the same bits on every plan.
+hipError_t launch_attention_gqa(const float *Q, int64_t ldq, const float *K, int64_t ldk, const float *V, int64_t ldv,
+                                float *O, int64_t ldo, int seq_q, int seq_kv, int n_heads, int n_kv_heads, int dk,
+                                float scale, int q_pos0, float *scores, hipStream_t stream) {
+    if (n_heads < 1 || n_kv_heads < 1 || n_heads % n_kv_heads) return hipErrorInvalidValue;
+    const int G = n_heads / n_kv_heads;
+    if (G == 1) return launch_attention(Q, ldq, K, ldk, V, ldv, O, ldo, seq_q, seq_kv, n_heads, dk, scale, q_pos0, scores, stream);
+    hipError_t e = launch_attention_decode_gqa(Q, ldq, K, ldk, V, ldv, O, ldo, seq_q, seq_kv, n_heads, n_kv_heads, dk,
+                                               scale, q_pos0, stream);
+    if (e != hipErrorNotSupported) return e;
+    if (seq_q == 0) return hipSuccess;
+    if (!scores) return hipErrorInvalidValue;
+    const int64_t sbs = (int64_t)seq_q * seq_kv, gd = (int64_t)G * dk;
+    // launch_attention's stride-envelope checks, for every round (the rounds' bases differ in alignment), before the
+    // first launch
+    for (int j = 0; j < G; ++j) {
+        const MmF32Plan qk = mm_f32_plan(seq_q, seq_kv, dk, n_kv_heads, ldq, 1, gd, mm_f32_al16(Q + j * dk), 1, ldk, dk,
+                                         mm_f32_al16(K));
+        const MmF32Plan pv = mm_f32_plan(seq_q, dk, seq_kv, n_kv_heads, seq_kv, 1, G * sbs, mm_f32_al16(scores + j * sbs),
+                                         ldv, 1, dk, mm_f32_al16(V));
+        if (!mm_f32_strides_ok(qk, ldq, 1, 1, ldk, seq_kv, 1, seq_q, seq_kv, dk) ||
+            !mm_f32_strides_ok(pv, seq_kv, 1, ldv, 1, ldo, 1, seq_q, dk, seq_kv))
+            return hipErrorInvalidValue;
+    }
+    for (int j = 0; j < G; ++j)
+        if ((e = launch_mm_f32_batched(Q + j * dk, ldq, 1, gd, K, 1, ldk, dk, scores + j * sbs, seq_kv, 1, G * sbs, seq_q,
+                                       seq_kv, dk, n_kv_heads, stream)))
+            return e;
+    e = q_pos0 == kNoMask
+            ? launch_softmax_rows(scores, scores, (int64_t)n_heads * seq_q, seq_kv, scale, stream)
+            : launch_softmax_rows_causal(scores, scores, (int64_t)n_heads * seq_q, seq_kv, scale, seq_q, q_pos0, stream);
+    if (e) return e;
+    for (int j = 0; j < G; ++j)
+        if ((e = launch_mm_f32_batched(scores + j * sbs, seq_kv, 1, G * sbs, V, ldv, 1, dk, O + j * dk, ldo, 1, gd, seq_q,
+                                       dk, seq_kv, n_kv_heads, stream)))
+            return e;
+    return hipSuccess;
+}
+
+// launch_attention_batched's and launch_attention_indirect's checks and table (row_slab == nullptr: the batched
+// form), then the grouped decode launch; the host arrays are read HERE, nothing is copied, allocated or synchronized
+static hipError_t batched_gqa(const float *Q, int64_t ldq, const float *K, int64_t ldk, int64_t k_stride_seq,
+                              const float *V, int64_t ldv, int64_t v_stride_seq, float *O, int64_t ldo, int n_seqs,
+                              int rows_per_seq, bool indirect, const uint8_t *row_slab, int64_t row_slab_stride,
+                              int n_slabs, const int *slot, const int *seq_kv, const int *q_pos0, int n_heads,
+                              int n_kv_heads, int dk, float scale, hipStream_t stream) {
+    if (!Q || !K || !V || !O || !seq_kv || n_seqs < 0 || n_seqs > kDecodeMaxBatch || rows_per_seq < 1 || dk < 1 ||
+        !attention_decode_gqa_ok(rows_per_seq, 1, dk, n_heads, n_kv_heads) ||
+        (indirect && (!row_slab || n_slabs < 1 || n_slabs > kDecodeMaxBatch)))
+        return hipErrorInvalidValue;
+    DecodeBatchTable tab = {};  // entries past n_seqs are never read; zeroed so the arguments are defined bytes
+    for (int b = 0; b < n_seqs; ++b) {
+        if (seq_kv[b] < 1 || !attention_decode_any_ok(rows_per_seq, seq_kv[b], dk) || (q_pos0 && q_pos0[b] < 0) ||
+            (slot && slot[b] < 0) || (indirect && row_slab_stride < seq_kv[b]))
+            return hipErrorInvalidValue;
+        tab.kv_slot[b] = slot ? slot[b] : b;
+        tab.seq_kv[b] = seq_kv[b];
+        // past seq_kv - 1 the mask hides nothing: clamped, so the kernel's row limit cannot overflow
+        tab.q_pos0[b] = q_pos0 ? (q_pos0[b] < seq_kv[b] ? q_pos0[b] : seq_kv[b]) : 0;
+    }
+    if (n_seqs == 0) return hipSuccess;
+    if (indirect)
+        return launch_attention_decode_indirect_gqa(Q, ldq, K, ldk, k_stride_seq, V, ldv, v_stride_seq, O, ldo, n_seqs,
+                                                    rows_per_seq, row_slab, row_slab_stride, n_slabs, tab,
+                                                    q_pos0 != nullptr, n_heads, n_kv_heads, dk, scale, stream);
+    return launch_attention_decode_batched_gqa(Q, ldq, K, ldk, k_stride_seq, V, ldv, v_stride_seq, O, ldo, n_seqs,
+                                               rows_per_seq, tab, q_pos0 != nullptr, n_heads, n_kv_heads, dk, scale,
+                                               stream);
+}
+
+hipError_t launch_attention_batched_gqa(const float *Q, int64_t ldq, const float *K, int64_t ldk, int64_t k_stride_seq,
+                                        const float *V, int64_t ldv, int64_t v_stride_seq, float *O, int64_t ldo,
+                                        int n_seqs, int rows_per_seq, const int *kv_slot, const int *seq_kv,
+                                        const int *q_pos0, int n_heads, int n_kv_heads, int dk, float scale,
+                                        hipStream_t stream) {
+    if (n_heads >= 1 && n_kv_heads == n_heads)
+        return launch_attention_batched(Q, ldq, K, ldk, k_stride_seq, V, ldv, v_stride_seq, O, ldo, n_seqs, rows_per_seq,
+                                        kv_slot, seq_kv, q_pos0, n_heads, dk, scale, stream);
+    return batched_gqa(Q, ldq, K, ldk, k_stride_seq, V, ldv, v_stride_seq, O, ldo, n_seqs, rows_per_seq, false, nullptr,
+                       0, 0, kv_slot, seq_kv, q_pos0, n_heads, n_kv_heads, dk, scale, stream);
+}
+
+hipError_t launch_attention_indirect_gqa(const float *Q, int64_t ldq, const float *K, int64_t ldk, int64_t k_stride_seq,
+                                         const float *V, int64_t ldv, int64_t v_stride_seq, float *O, int64_t ldo,
+                                         int n_seqs, int rows_per_seq, const uint8_t *row_slab, int64_t row_slab_stride,
+                                         int n_slabs, const int *tab_row, const int *seq_kv, const int *q_pos0,
+                                         int n_heads, int n_kv_heads, int dk, float scale, hipStream_t stream) {
+    if (n_heads >= 1 && n_kv_heads == n_heads)
+        return launch_attention_indirect(Q, ldq, K, ldk, k_stride_seq, V, ldv, v_stride_seq, O, ldo, n_seqs,
+                                         rows_per_seq, row_slab, row_slab_stride, n_slabs, tab_row, seq_kv, q_pos0,
+                                         n_heads, dk, scale, stream);
+    return batched_gqa(Q, ldq, K, ldk, k_stride_seq, V, ldv, v_stride_seq, O, ldo, n_seqs, rows_per_seq, true, row_slab,
+                       row_slab_stride, n_slabs, tab_row, seq_kv, q_pos0, n_heads, n_kv_heads, dk, scale, stream);
+}
+
 }  // namespace qgemm

@@ -426,6 +426,49 @@ bool attention_needs_scores(int max_q, int max_kv, int dk);
 hipError_t launch_attention(const float *Q, int64_t ldq, const float *K, int64_t ldk, const float *V, int64_t ldv,
                             float *O, int64_t ldo, int seq_q, int seq_kv, int n_heads, int dk, float scale, int q_pos0,
                             float *scores, hipStream_t stream);
+// Grouped-query attention: Q and O have n_heads * d_k columns, K and V n_kv_heads * d_k, query head h
+// reads K / V head h / G, G = n_heads / n_kv_heads; every query head's rows are bit for bit the launches' above on K / V
+// with each head repeated G times.
+// The decode kernel for groups (attention_decode_gqa.hip): one workgroup per (KV head, block of <= 4 heads of its
+// group, query row[, sequence]), every K / V chunk staged once for the block.  Its envelope: either decode envelope
+// and 2 <= G <= 16.
+bool attention_decode_gqa_ok(int seq_q, int seq_kv, int dk, int n_heads, int n_kv_heads);
+// launch_attention_decode / _decode_batched / _decode_indirect with n_kv_heads: the same checks, tables and returns
+// (hipErrorNotSupported outside attention_decode_gqa_ok from the first, hipErrorInvalidValue from the table forms)
+hipError_t launch_attention_decode_gqa(const float *Q, int64_t ldq, const float *K, int64_t ldk, const float *V,
+                                       int64_t ldv, float *O, int64_t ldo, int seq_q, int seq_kv, int n_heads,
+                                       int n_kv_heads, int dk, float scale, int q_pos0, hipStream_t stream);
+hipError_t launch_attention_decode_batched_gqa(const float *Q, int64_t ldq, const float *K, int64_t ldk,
+                                               int64_t k_stride_seq, const float *V, int64_t ldv, int64_t v_stride_seq,
+                                               float *O, int64_t ldo, int n_seqs, int rows_per_seq,
+                                               const DecodeBatchTable &tab, bool causal, int n_heads, int n_kv_heads,
+                                               int dk, float scale, hipStream_t stream);
+hipError_t launch_attention_decode_indirect_gqa(const float *Q, int64_t ldq, const float *K, int64_t ldk,
+                                                int64_t k_stride_seq, const float *V, int64_t ldv, int64_t v_stride_seq,
+                                                float *O, int64_t ldo, int n_seqs, int rows_per_seq,
+                                                const uint8_t *row_slab, int64_t row_slab_stride, int n_slabs,
+                                                const DecodeBatchTable &tab, bool causal, int n_heads, int n_kv_heads,
+                                                int dk, float scale, hipStream_t stream);
+// Dispatch (attention_launch.hip).  The launch launch_attention_gqa takes: attention_plan_name's answer at G = 1,
+// "attention_decode_gqa_kernel" / "attention_decode_gqa_wide_kernel" inside attention_decode_gqa_ok, else
+// "grouped_three_launches" -- the three launches in G rounds of n_kv_heads batches each (round j: the j-th head of
+// every group), one softmax over all rows, through scores (n_heads x seq_q x seq_kv floats, needed on that path alone).
+const char *attention_gqa_plan_name(int seq_q, int seq_kv, int dk, int n_heads, int n_kv_heads);
+hipError_t launch_attention_gqa(const float *Q, int64_t ldq, const float *K, int64_t ldk, const float *V, int64_t ldv,
+                                float *O, int64_t ldo, int seq_q, int seq_kv, int n_heads, int n_kv_heads, int dk,
+                                float scale, int q_pos0, float *scores, hipStream_t stream);
+// launch_attention_batched / launch_attention_indirect with n_kv_heads (G = 1: those launches; G > 16 refused);
+// row_slab == nullptr: the batched form
+hipError_t launch_attention_batched_gqa(const float *Q, int64_t ldq, const float *K, int64_t ldk, int64_t k_stride_seq,
+                                        const float *V, int64_t ldv, int64_t v_stride_seq, float *O, int64_t ldo,
+                                        int n_seqs, int rows_per_seq, const int *kv_slot, const int *seq_kv,
+                                        const int *q_pos0, int n_heads, int n_kv_heads, int dk, float scale,
+                                        hipStream_t stream);
+hipError_t launch_attention_indirect_gqa(const float *Q, int64_t ldq, const float *K, int64_t ldk, int64_t k_stride_seq,
+                                         const float *V, int64_t ldv, int64_t v_stride_seq, float *O, int64_t ldo,
+                                         int n_seqs, int rows_per_seq, const uint8_t *row_slab, int64_t row_slab_stride,
+                                         int n_slabs, const int *tab_row, const int *seq_kv, const int *q_pos0,
+                                         int n_heads, int n_kv_heads, int dk, float scale, hipStream_t stream);
 hipError_t launch_softmax_rows(const float *S, float *P, int64_t rows, int w, float scale, hipStream_t stream);
 // the same on a stack of rows / seq_q matrices under the causal mask: row r is query i = r % seq_q and its softmax
 // runs over its first min(w, i + q_pos0 + 1) columns, +0 stored past them (P may be S)
