@@ -1208,6 +1208,40 @@ QGEMM_API int qgemm_attention_decode_indirect_gqa(const float *Q, int64_t q_stri
                                         const int *tab_row, const int *seq_kv, const int *q_pos0,
                                         int n_heads, int n_kv_heads, int d_k, float scale, void *stream);
 
+/* ---- Grouped-query prefill over packed sequences: one fused launch, d_k up to 128 ----------------
+ * qgemm_attention_varlen_gqa: qgemm_attention_varlen with n_kv_heads (after n_heads).  Q and O have n_heads * d_k
+ * columns, K and V n_kv_heads * d_k, query head h uses columns (h / G) * d_k .. of K and V, G = n_heads / n_kv_heads.
+ * The five host arrays, the row offsets, the mask and capturability are qgemm_attention_varlen's: nothing is copied to
+ * the device, allocated or synchronized.
+ * Contract: nothing new numerically.  For every b, rows q_row0[b] .. q_row0[b] + seq_q[b] - 1 of O are BIT FOR BIT
+ * what qgemm_attention_gqa gives on sequence b's views, which is what qgemm_attention[_causal] gives on K and V with
+ * every head repeated G times (the contract at qgemm_attention_gqa); no other row of O is written.
+ * Routes, named by qgemm_attention_varlen_gqa_plan (needs no GPU):
+ *   G == 1                                   exactly qgemm_attention_varlen: its launch, plan name and workspace rule
+ *   every seq_kv[b] <= 512 and d_k <= 64     "attention_fused_gqa_kernel<many>": ONE launch, a workgroup per (sequence,
+ *                                            query head, 32-query tile), S and P in LDS, K / V in 256-key chunks
+ *   every seq_kv[b] <= 512, d_k 96 or 128    "attention_fused_gqa_wide_kernel<many>": the same kernel at row width 128,
+ *                                            K / V in 128-key chunks
+ *   everything else                          "per_sequence": qgemm_attention_gqa sequence by sequence in order, each
+ *                                            sequence on the route it takes there, through `workspace`
+ * Any G >= 2 that divides n_heads is served by the fused routes (no cap of 16), and any seq_q, decode shapes included.
+ * qgemm_attention_varlen_gqa_workspace_size: 0 on the fused routes (a workspace handed in is left untouched);
+ * per sequence the largest qgemm_attention_gqa_workspace_size over the sequences with seq_q[b] > 0; at G == 1
+ * qgemm_attention_varlen_workspace_size; 0 for arguments the call refuses.
+ * hipErrorInvalidValue before any launch: whatever qgemm_attention_varlen refuses (a null pointer or array, n_seqs < 0
+ * or > 64, a negative row offset, seq_q[b] < 0, seq_kv[b] < 1 or > 4096, q_pos0[b] < 0, n_heads < 1, d_k < 1, too small
+ * a workspace), n_kv_heads < 1, n_heads % n_kv_heads != 0; n_seqs == 0 returns 0 without a launch.  (On the grouped
+ * three launches alone a row stride outside qgemm_mm_fp32's stride envelope is refused when its sequence is reached.) */
+QGEMM_API size_t qgemm_attention_varlen_gqa_workspace_size(int n_seqs, const int *seq_q, const int *seq_kv,
+                                                 int n_heads, int n_kv_heads, int d_k);
+QGEMM_API int qgemm_attention_varlen_gqa(const float *Q, int64_t q_stride_h, const float *K, int64_t k_stride_h,
+                               const float *V, int64_t v_stride_h, float *O, int64_t o_stride_h, int n_seqs,
+                               const int64_t *q_row0, const int *seq_q, const int64_t *kv_row0, const int *seq_kv,
+                               const int *q_pos0 /* NULL: no mask */, int n_heads, int n_kv_heads, int d_k,
+                               float scale, void *workspace, size_t ws_bytes, void *stream);
+QGEMM_API int qgemm_attention_varlen_gqa_plan(int n_seqs, const int *seq_q, const int *seq_kv, int n_heads,
+                                    int n_kv_heads, int d_k, const char **kernel);
+
 #ifdef __cplusplus
 }
 #endif

@@ -158,6 +158,9 @@ EXPORTED_SYMBOLS = (
     "qgemm_attention_gqa_plan",
     "qgemm_attention_decode_batched_gqa",
     "qgemm_attention_decode_indirect_gqa",
+    "qgemm_attention_varlen_gqa_workspace_size",
+    "qgemm_attention_varlen_gqa",
+    "qgemm_attention_varlen_gqa_plan",
 )
 
 # Every symbol include/qgemm_dist.h declares (libqgemm_dist.so: M-shards + RCCL all-gather).
@@ -496,6 +499,13 @@ def load() -> ctypes.CDLL:
         L.qgemm_attention_decode_indirect_gqa.argtypes = [vp, i64, vp, i64, i64, vp, i64, i64, vp, i64, i32, i32, vp, i64,
                                                           i32, ip, ip, ip, i32, i32, i32, f32, vp]
         L.qgemm_attention_decode_indirect_gqa.restype = i32
+        L.qgemm_attention_varlen_gqa_workspace_size.argtypes = [i32, ip, ip, i32, i32, i32]
+        L.qgemm_attention_varlen_gqa_workspace_size.restype = sz
+        L.qgemm_attention_varlen_gqa.argtypes = [vp, i64, vp, i64, vp, i64, vp, i64, i32, lp, ip, lp, ip, ip, i32, i32, i32,
+                                                 f32, vp, sz, vp]
+        L.qgemm_attention_varlen_gqa.restype = i32
+        L.qgemm_attention_varlen_gqa_plan.argtypes = [i32, ip, ip, i32, i32, i32, ctypes.POINTER(ctypes.c_char_p)]
+        L.qgemm_attention_varlen_gqa_plan.restype = i32
         _lib = L
         return L
 
@@ -1935,6 +1945,67 @@ def attention_varlen_plan(seq_q, seq_kv, n_heads: int, d_k: int) -> str:
     _check("qgemm_attention_varlen_plan",
            load().qgemm_attention_varlen_plan(n, _int_array(seq_q, n, "seq_q"), _int_array(seq_kv, n, "seq_kv"), n_heads,
                                               d_k, ctypes.byref(name)))
+    return name.value.decode()
+
+
+def attention_varlen_gqa(Q, K, V, n_heads: int, n_kv_heads, seq_q, seq_kv, q_row0=None, kv_row0=None, q_pos0=None,
+                         scale=None, O=None):
+    """attention_varlen for grouped-query heads (qgemm_attention_varlen_gqa): K and V have n_kv_heads * d_k
+    columns and query head h reads their head h // (n_heads // n_kv_heads).  Where every seq_kv[b] <= 512 and d_k <= 64
+    or d_k is 96 or 128 the call is ONE launch of the fused grouped kernel, for any group size and any seq_q, without a
+    workspace; else it runs attention(n_kv_heads=...) sequence by sequence (attention_varlen_gqa_plan names the path).
+    Each sequence's rows of the result equal attention_varlen's on K / V with every head repeated bit for bit, and no
+    other row of O is written (a fresh O is zero-filled).  n_kv_heads None or n_heads is exactly attention_varlen."""
+    import math
+    import torch
+    for t, nm in ((Q, "Q"), (K, "K"), (V, "V")):
+        _require_device_f32(t, nm)
+        assert t.dim() == 2 and (t.stride(1) == 1 or t.shape[1] == 1), f"{nm} must be 2-D with unit inner stride"
+    d = Q.shape[1]
+    assert n_heads >= 1 and d % n_heads == 0, "d % n_heads == 0"
+    dk = d // n_heads
+    n_kv = _kv_heads(n_heads, n_kv_heads)
+    assert K.shape[1] == n_kv * dk and V.shape[1] == n_kv * dk, "K and V: n_kv_heads * d_k columns"
+    seq_q, seq_kv = [int(v) for v in seq_q], [int(v) for v in seq_kv]
+    n = len(seq_q)
+    assert len(seq_kv) == n, "seq_q and seq_kv: one entry per sequence"
+    q_row0 = _prefix_sums(seq_q) if q_row0 is None else [int(v) for v in q_row0]
+    kv_row0 = _prefix_sums(seq_kv) if kv_row0 is None else [int(v) for v in kv_row0]
+    assert len(q_row0) == n and len(kv_row0) == n, "q_row0 and kv_row0: one entry per sequence"
+    if O is None:
+        O = torch.zeros((Q.shape[0], d), dtype=torch.float32, device=Q.device)
+    _require_device_f32(O, "O")
+    assert O.dim() == 2 and O.shape[1] == d and (O.stride(1) == 1 or d == 1), "O: d columns, unit inner stride"
+    for b in range(n):  # the rows the call reads and writes exist
+        if q_row0[b] >= 0 and seq_q[b] >= 0:
+            assert q_row0[b] + seq_q[b] <= min(Q.shape[0], O.shape[0]), f"sequence {b}'s query rows exceed Q / O"
+        if kv_row0[b] >= 0 and seq_kv[b] >= 0:
+            assert kv_row0[b] + seq_kv[b] <= min(K.shape[0], V.shape[0]), f"sequence {b}'s keys exceed K / V"
+    if scale is None:
+        scale = ctypes.c_float(1.0 / math.sqrt(float(dk))).value  # attention.cuh:64
+    L = load()
+    sq, skv = _int_array(seq_q, n, "seq_q"), _int_array(seq_kv, n, "seq_kv")
+    need = L.qgemm_attention_varlen_gqa_workspace_size(n, sq, skv, n_heads, n_kv, dk)
+    ws = torch.empty(need, dtype=torch.uint8, device=Q.device) if need else None
+    _check("qgemm_attention_varlen_gqa",
+           L.qgemm_attention_varlen_gqa(Q.data_ptr(), Q.stride(0), K.data_ptr(), K.stride(0), V.data_ptr(), V.stride(0),
+                                        O.data_ptr(), O.stride(0), n, _int64_array(q_row0, n, "q_row0"), sq,
+                                        _int64_array(kv_row0, n, "kv_row0"), skv, _int_array(q_pos0, n, "q_pos0"),
+                                        n_heads, n_kv, dk, float(scale), ws.data_ptr() if need else None, need,
+                                        _stream(Q.device)))
+    return O
+
+
+def attention_varlen_gqa_plan(seq_q, seq_kv, n_heads: int, n_kv_heads: int, d_k: int) -> str:
+    """The path attention_varlen_gqa() takes (qgemm_attention_varlen_gqa_plan): "attention_fused_gqa_kernel<many>" or
+    "attention_fused_gqa_wide_kernel<many>", one launch over the table of sequences, "per_sequence", or at n_kv_heads ==
+    n_heads attention_varlen_plan's answer.  Needs no GPU; raises QGemmError for arguments the call refuses."""
+    seq_q, seq_kv = [int(v) for v in seq_q], [int(v) for v in seq_kv]
+    n = len(seq_q)
+    name = ctypes.c_char_p()
+    _check("qgemm_attention_varlen_gqa_plan",
+           load().qgemm_attention_varlen_gqa_plan(n, _int_array(seq_q, n, "seq_q"), _int_array(seq_kv, n, "seq_kv"),
+                                                  n_heads, n_kv_heads, d_k, ctypes.byref(name)))
     return name.value.decode()
 
 

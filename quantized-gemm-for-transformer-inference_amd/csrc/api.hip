@@ -609,6 +609,55 @@ int qgemm_attention_gqa_plan(int seq_q, int seq_kv, int n_heads, int n_kv_heads,
     return 0;
 }
 
+// ---- grouped-query prefill over packed sequences ----
+
+// what qgemm_attention_varlen_gqa refuses of the arguments the plan and the workspace query also take
+static bool varlen_gqa_dims_ok(int n_seqs, const int *seq_q, const int *seq_kv, int n_heads, int n_kv_heads, int d_k) {
+    if (n_seqs < 0 || n_seqs > QGEMM_VARLEN_MAX_SEQS || !seq_q || !seq_kv || n_heads < 1 || d_k < 1 || n_kv_heads < 1 ||
+        n_heads % n_kv_heads)
+        return false;
+    for (int b = 0; b < n_seqs; ++b)
+        if (seq_q[b] < 0 || seq_kv[b] < 1 || seq_kv[b] > 4096) return false;
+    return true;
+}
+
+// G = 1: qgemm_attention_varlen's rule; 0 on the fused plans; else the largest single-call workspace over the
+// sequences that have query rows
+size_t qgemm_attention_varlen_gqa_workspace_size(int n_seqs, const int *seq_q, const int *seq_kv, int n_heads,
+                                                 int n_kv_heads, int d_k) {
+    if (!varlen_gqa_dims_ok(n_seqs, seq_q, seq_kv, n_heads, n_kv_heads, d_k)) return 0;
+    if (n_kv_heads == n_heads) return qgemm_attention_varlen_workspace_size(n_seqs, seq_q, seq_kv, n_heads, d_k);
+    if (attention_varlen_fused_gqa_ok(n_seqs, seq_kv, d_k)) return 0;
+    size_t need = 0;
+    for (int b = 0; b < n_seqs; ++b)
+        if (seq_q[b] > 0)
+            need = std::max(need, qgemm_attention_gqa_workspace_size(seq_q[b], seq_kv[b], n_heads, n_kv_heads, d_k));
+    return need;
+}
+
+int qgemm_attention_varlen_gqa(const float *Q, int64_t q_stride_h, const float *K, int64_t k_stride_h, const float *V,
+                               int64_t v_stride_h, float *O, int64_t o_stride_h, int n_seqs, const int64_t *q_row0,
+                               const int *seq_q, const int64_t *kv_row0, const int *seq_kv, const int *q_pos0,
+                               int n_heads, int n_kv_heads, int d_k, float scale, void *workspace, size_t ws_bytes,
+                               void *stream) {
+    if (!Q || !K || !V || !O || !q_row0 || !kv_row0 ||
+        !varlen_gqa_dims_ok(n_seqs, seq_q, seq_kv, n_heads, n_kv_heads, d_k))
+        return err(hipErrorInvalidValue);
+    const size_t need = qgemm_attention_varlen_gqa_workspace_size(n_seqs, seq_q, seq_kv, n_heads, n_kv_heads, d_k);
+    if (need && (!workspace || ws_bytes < need)) return err(hipErrorInvalidValue);
+    return err(launch_attention_varlen_gqa(Q, q_stride_h, K, k_stride_h, V, v_stride_h, O, o_stride_h, n_seqs, q_row0,
+                                           seq_q, kv_row0, seq_kv, q_pos0, n_heads, n_kv_heads, d_k, scale,
+                                           need ? static_cast<float *>(workspace) : nullptr,
+                                           static_cast<hipStream_t>(stream)));
+}
+
+int qgemm_attention_varlen_gqa_plan(int n_seqs, const int *seq_q, const int *seq_kv, int n_heads, int n_kv_heads,
+                                    int d_k, const char **kernel) {
+    if (!varlen_gqa_dims_ok(n_seqs, seq_q, seq_kv, n_heads, n_kv_heads, d_k)) return err(hipErrorInvalidValue);
+    if (kernel) *kernel = attention_varlen_gqa_plan_name(n_seqs, seq_kv, d_k, n_heads, n_kv_heads);
+    return 0;
+}
+
 int qgemm_attention_decode_batched_gqa(const float *Q, int64_t q_stride_h, const float *K, int64_t k_stride_h,
                                        int64_t k_stride_seq, const float *V, int64_t v_stride_h, int64_t v_stride_seq,
                                        float *O, int64_t o_stride_h, int n_seqs, int rows_per_seq, const int *kv_slot,

@@ -211,6 +211,66 @@ hipError_t launch_attention_gqa(const float *Q, int64_t ldq, const float *K, int
     return hipSuccess;
 }
 
+// ---- grouped-query prefill over a table of sequences ----
+
+// one table launch serves a grouped call exactly when every sequence lies inside the kernel's envelope
+bool attention_varlen_fused_gqa_ok(int n_seqs, const int *seq_kv, int dk) {
+    for (int b = 0; b < n_seqs; ++b)
+        if (!attention_fused_gqa_ok(seq_kv[b], dk)) return false;
+    return attention_fused_gqa_ok(1, dk);
+}
+
+const char *attention_varlen_gqa_plan_name(int n_seqs, const int *seq_kv, int dk, int n_heads, int n_kv_heads) {
+    if (n_heads == n_kv_heads) return attention_varlen_plan_name(n_seqs, seq_kv, dk);
+    if (!attention_varlen_fused_gqa_ok(n_seqs, seq_kv, dk)) return "per_sequence";
+    return dk <= 64 ? "attention_fused_gqa_kernel<many>" : "attention_fused_gqa_wide_kernel<many>";
+}
+
+// launch_attention_varlen's checks and table; the host arrays are read HERE, nothing is copied, allocated or
+// synchronized.  Every check comes before the first launch (per sequence, the fp32 GEMMs' stride envelope alone is
+// tested when its sequence is reached, as by launch_attention_varlen).
+hipError_t launch_attention_varlen_gqa(const float *Q, int64_t ldq, const float *K, int64_t ldk, const float *V,
+                                       int64_t ldv, float *O, int64_t ldo, int n_seqs, const int64_t *q_row0,
+                                       const int *seq_q, const int64_t *kv_row0, const int *seq_kv, const int *q_pos0,
+                                       int n_heads, int n_kv_heads, int dk, float scale, float *scores,
+                                       hipStream_t stream) {
+    if (n_heads < 1 || n_kv_heads < 1 || n_heads % n_kv_heads) return hipErrorInvalidValue;
+    if (n_kv_heads == n_heads)
+        return launch_attention_varlen(Q, ldq, K, ldk, V, ldv, O, ldo, n_seqs, q_row0, seq_q, kv_row0, seq_kv, q_pos0,
+                                       n_heads, dk, scale, scores, stream);
+    if (!Q || !K || !V || !O || !q_row0 || !seq_q || !kv_row0 || !seq_kv || n_seqs < 0 || n_seqs > kVarlenMaxSeqs ||
+        dk < 1)
+        return hipErrorInvalidValue;
+    FusedSeqTable tab = {};  // entries past n_seqs are never read; zeroed so the arguments are defined bytes
+    bool need_scores = false;
+    for (int b = 0; b < n_seqs; ++b) {
+        if (q_row0[b] < 0 || kv_row0[b] < 0 || seq_q[b] < 0 || seq_kv[b] < 1 || seq_kv[b] > 4096 ||
+            (q_pos0 && q_pos0[b] < 0))
+            return hipErrorInvalidValue;
+        tab.q_row0[b] = q_row0[b];
+        tab.kv_row0[b] = kv_row0[b];
+        tab.seq_q[b] = seq_q[b];
+        tab.seq_kv[b] = seq_kv[b];
+        // past seq_kv - 1 the mask hides nothing: clamped, so the kernel's row limits cannot overflow
+        tab.q_pos0[b] = q_pos0 ? (q_pos0[b] < seq_kv[b] ? q_pos0[b] : seq_kv[b]) : 0;
+        need_scores = need_scores ||
+                      (seq_q[b] > 0 && !attention_decode_gqa_ok(seq_q[b], seq_kv[b], dk, n_heads, n_kv_heads));
+    }
+    if (n_seqs == 0) return hipSuccess;
+    if (attention_varlen_fused_gqa_ok(n_seqs, seq_kv, dk))
+        return launch_attention_fused_gqa_many(Q, ldq, K, ldk, V, ldv, O, ldo, n_seqs, tab, q_pos0 != nullptr, n_heads,
+                                               n_kv_heads, dk, scale, stream);
+    if (need_scores && !scores) return hipErrorInvalidValue;
+    for (int b = 0; b < n_seqs; ++b) {
+        const hipError_t e =
+            launch_attention_gqa(Q + q_row0[b] * ldq, ldq, K + kv_row0[b] * ldk, ldk, V + kv_row0[b] * ldv, ldv,
+                                 O + q_row0[b] * ldo, ldo, seq_q[b], seq_kv[b], n_heads, n_kv_heads, dk, scale,
+                                 q_pos0 ? q_pos0[b] : kNoMask, scores, stream);
+        if (e) return e;
+    }
+    return hipSuccess;
+}
+
 // launch_attention_batched's and launch_attention_indirect's checks and table (row_slab == nullptr: the batched
 // form), then the grouped decode launch; the host arrays are read HERE, nothing is copied, allocated or synchronized
 static hipError_t batched_gqa(const float *Q, int64_t ldq, const float *K, int64_t ldk, int64_t k_stride_seq,

@@ -469,6 +469,29 @@ hipError_t launch_attention_indirect_gqa(const float *Q, int64_t ldq, const floa
                                          int n_seqs, int rows_per_seq, const uint8_t *row_slab, int64_t row_slab_stride,
                                          int n_slabs, const int *tab_row, const int *seq_kv, const int *q_pos0,
                                          int n_heads, int n_kv_heads, int dk, float scale, hipStream_t stream);
+// The fused prefill kernel for groups over a table of sequences (attention_gqa.hip): one workgroup per
+// (sequence, query head, 32-query tile), query head h on KV head h / G.  Its envelope: seq_kv <= 512 and d_k <= 64
+// (row width 64) or d_k 96 / 128 (row width 128); any G that divides n_heads.
+bool attention_fused_gqa_ok(int seq_kv, int dk);
+// tab already checked and clamped (q_pos0[b] <= seq_kv[b]); causal = false ignores q_pos0; sequences with
+// seq_q[b] == 0 get no workgroup; hipErrorInvalidValue outside the envelope
+hipError_t launch_attention_fused_gqa_many(const float *Q, int64_t ldq, const float *K, int64_t ldk, const float *V,
+                                           int64_t ldv, float *O, int64_t ldo, int n_seqs, const FusedSeqTable &tab,
+                                           bool causal, int n_heads, int n_kv_heads, int dk, float scale,
+                                           hipStream_t stream);
+// launch_attention_varlen with n_kv_heads (attention_launch.hip): its checks and table, and n_heads % n_kv_heads == 0.
+// G = 1: launch_attention_varlen.  Every sequence inside attention_fused_gqa_ok: ONE launch_attention_fused_gqa_many
+// ("attention_fused_gqa_kernel<many>" at d_k <= 64, "attention_fused_gqa_wide_kernel<many>" at 96 / 128), scores
+// untouched.  Else "per_sequence": launch_attention_gqa sequence by sequence in order through `scores` (the largest
+// n_heads x seq_q[b] x seq_kv[b] floats of a sequence that takes the grouped three launches).
+// (attention_varlen_fused_gqa_ok: whether the one launch serves the call; no sequence: by d_k alone)
+bool attention_varlen_fused_gqa_ok(int n_seqs, const int *seq_kv, int dk);
+const char *attention_varlen_gqa_plan_name(int n_seqs, const int *seq_kv, int dk, int n_heads, int n_kv_heads);
+hipError_t launch_attention_varlen_gqa(const float *Q, int64_t ldq, const float *K, int64_t ldk, const float *V,
+                                       int64_t ldv, float *O, int64_t ldo, int n_seqs, const int64_t *q_row0,
+                                       const int *seq_q, const int64_t *kv_row0, const int *seq_kv, const int *q_pos0,
+                                       int n_heads, int n_kv_heads, int dk, float scale, float *scores,
+                                       hipStream_t stream);
 hipError_t launch_softmax_rows(const float *S, float *P, int64_t rows, int w, float scale, hipStream_t stream);
 // the same on a stack of rows / seq_q matrices under the causal mask: row r is query i = r % seq_q and its softmax
 // runs over its first min(w, i + q_pos0 + 1) columns, +0 stored past them (P may be S)
