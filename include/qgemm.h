@@ -1242,6 +1242,52 @@ QGEMM_API int qgemm_attention_varlen_gqa(const float *Q, int64_t q_stride_h, con
 QGEMM_API int qgemm_attention_varlen_gqa_plan(int n_seqs, const int *seq_q, const int *seq_kv, int n_heads,
                                     int n_kv_heads, int d_k, const char **kernel);
 
+/* ---- Decode attention over a bf16 K / V cache, and the kernel that fills one ----------------------
+ * qgemm_attention_decode_batched_kv16 / _indirect_kv16: qgemm_attention_decode_batched_gqa / _indirect_gqa with K and V
+ * as bf16 slabs [slabs, rows, n_kv_heads * d_k] (the upper halves of the fp32 values, QGEMM_BF16's element); their
+ * strides count bf16 elements.  Q and O stay fp32.  The tables travel in the kernel arguments: nothing is copied to the
+ * device, allocated or synchronized, so the calls can be captured in a graph.
+ * Contract: nothing new numerically.  bf16 -> fp32 is exact and the arithmetic is fp32, so every output row is BIT FOR
+ * BIT what qgemm_attention_decode_batched_gqa / _indirect_gqa (G >= 2) and qgemm_attention_decode_batched / _indirect
+ * (G == 1) return on K and V widened to fp32; an indirect table entry that names no slab reads as quiet NaNs.
+ * ONE kernel serves every call, "attention_decode_kv16_kernel" (d_k <= 64) or "attention_decode_kv16_wide_kernel"
+ * (d_k 96 or 128), named by qgemm_attention_decode_kv16_plan (needs no GPU); K / V stream through LDS in 256-key chunks
+ * of bf16 rows.  16-byte loads need a 16-byte-aligned first row, strides that are multiples of 8 elements and
+ * d_k % 8 == 0; anything else is read element by element, chosen once per matrix.
+ * Envelope: 1 .. 8 rows per sequence, up to 64 sequences, seq_kv[b] in 1 .. 4096, d_k <= 64 or 96 or 128,
+ * 1 <= G = n_heads / n_kv_heads <= 16 (G == 1: a bf16 multi-head cache).  No other path reads bf16, so outside the
+ * envelope -- and for whatever the fp32 calls refuse -- the calls return hipErrorInvalidValue before any launch;
+ * n_seqs == 0 returns 0 without a launch.
+ * qgemm_kv_append_bf16: ONE launch rounds the new K and V rows of up to 64 sequences to bf16 -- nearest even, +-inf
+ * past the bf16 maximum, subnormals kept, -0 kept, NaN stays NaN: the rounding of the bf16 GEMM epilogue -- and writes
+ * them into the cache.  K / V: n_seqs * rows_per_seq fp32 rows of `width` columns, row stride k / v_stride_h floats
+ * (e.g. the K and V thirds of a [Q | K | V] buffer); source row b * rows_per_seq + r goes to row pos[b] + r of slab
+ * kv_slot[b] (NULL: slab b) of Kc / Vc, whose row and slab strides count bf16 elements.  16-byte stores where the
+ * destination allows (aligned base, strides multiples of 8), element stores otherwise; no other element of Kc / Vc is
+ * written.  The caller keeps the rows inside the slabs.  kv_slot and pos are host arrays read at the call; nothing is
+ * copied to the device, allocated or synchronized.  hipErrorInvalidValue before the launch: a null pointer (kv_slot
+ * aside), n_seqs outside 1 .. 64, rows_per_seq < 1, width < 1, a negative pos[b] or kv_slot[b]. */
+QGEMM_API int qgemm_attention_decode_batched_kv16(const float *Q, int64_t q_stride_h,
+                                        const void *K, int64_t k_stride_h, int64_t k_stride_seq,
+                                        const void *V, int64_t v_stride_h, int64_t v_stride_seq,
+                                        float *O, int64_t o_stride_h, int n_seqs, int rows_per_seq,
+                                        const int *kv_slot, const int *seq_kv, const int *q_pos0,
+                                        int n_heads, int n_kv_heads, int d_k, float scale, void *stream);
+QGEMM_API int qgemm_attention_decode_indirect_kv16(const float *Q, int64_t q_stride_h,
+                                         const void *K, int64_t k_stride_h, int64_t k_stride_seq,
+                                         const void *V, int64_t v_stride_h, int64_t v_stride_seq,
+                                         float *O, int64_t o_stride_h, int n_seqs, int rows_per_seq,
+                                         const uint8_t *row_slab, int64_t row_slab_stride, int n_slabs,
+                                         const int *tab_row, const int *seq_kv, const int *q_pos0,
+                                         int n_heads, int n_kv_heads, int d_k, float scale, void *stream);
+QGEMM_API int qgemm_attention_decode_kv16_plan(int rows_per_seq, int n_heads, int n_kv_heads, int d_k,
+                                     const char **kernel);
+QGEMM_API int qgemm_kv_append_bf16(const float *K, int64_t k_stride_h, const float *V, int64_t v_stride_h,
+                         void *Kc, int64_t kc_stride_h, int64_t kc_stride_seq,
+                         void *Vc, int64_t vc_stride_h, int64_t vc_stride_seq,
+                         int n_seqs, int rows_per_seq, const int *kv_slot, const int *pos, int width,
+                         void *stream);
+
 #ifdef __cplusplus
 }
 #endif

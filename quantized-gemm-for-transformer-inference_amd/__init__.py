@@ -161,6 +161,10 @@ EXPORTED_SYMBOLS = (
     "qgemm_attention_varlen_gqa_workspace_size",
     "qgemm_attention_varlen_gqa",
     "qgemm_attention_varlen_gqa_plan",
+    "qgemm_attention_decode_batched_kv16",
+    "qgemm_attention_decode_indirect_kv16",
+    "qgemm_attention_decode_kv16_plan",
+    "qgemm_kv_append_bf16",
 )
 
 # Every symbol include/qgemm_dist.h declares (libqgemm_dist.so: M-shards + RCCL all-gather).
@@ -506,6 +510,14 @@ def load() -> ctypes.CDLL:
         L.qgemm_attention_varlen_gqa.restype = i32
         L.qgemm_attention_varlen_gqa_plan.argtypes = [i32, ip, ip, i32, i32, i32, ctypes.POINTER(ctypes.c_char_p)]
         L.qgemm_attention_varlen_gqa_plan.restype = i32
+        L.qgemm_attention_decode_batched_kv16.argtypes = L.qgemm_attention_decode_batched_gqa.argtypes
+        L.qgemm_attention_decode_batched_kv16.restype = i32
+        L.qgemm_attention_decode_indirect_kv16.argtypes = L.qgemm_attention_decode_indirect_gqa.argtypes
+        L.qgemm_attention_decode_indirect_kv16.restype = i32
+        L.qgemm_attention_decode_kv16_plan.argtypes = [i32, i32, i32, i32, ctypes.POINTER(ctypes.c_char_p)]
+        L.qgemm_attention_decode_kv16_plan.restype = i32
+        L.qgemm_kv_append_bf16.argtypes = [vp, i64, vp, i64, vp, i64, i64, vp, i64, i64, i32, i32, ip, ip, i32, vp]
+        L.qgemm_kv_append_bf16.restype = i32
         _lib = L
         return L
 
@@ -1852,6 +1864,124 @@ def attention_decode_indirect(Q, K, V, n_heads: int, row_slab, seq_kv, q_pos0=No
     _check("qgemm_attention_decode_indirect",
            load().qgemm_attention_decode_indirect(*head, dk, float(scale), _stream(Q.device)))
     return O
+
+
+def _require_bf16_slabs(t, name):
+    """A bf16 cache: a 3-D bfloat16 device tensor or view [slabs, rows, d] with unit inner stride."""
+    import torch
+    assert isinstance(t, torch.Tensor) and t.dim() == 3 and t.is_cuda and t.dtype == torch.bfloat16, \
+        f"{name}: a 3-D bfloat16 device tensor [slabs, rows, d]"
+    assert t.stride(2) == 1 or t.shape[2] == 1, f"{name} must have unit inner stride"
+
+
+def _kv16_call(Q, K, V, n_heads, n_kv_heads, rows_per_seq, scale, O):
+    """What the two bf16-cache decode calls share: the checks of Q / K / V / O and (rows, n_seqs, dk, n_kv, scale, O)."""
+    import math
+    import torch
+    _require_device_f32(Q, "Q")
+    assert Q.stride(1) == 1 or Q.shape[1] == 1, "Q must have unit inner stride"
+    _require_bf16_slabs(K, "K")
+    _require_bf16_slabs(V, "V")
+    rows, d = Q.shape
+    assert rows_per_seq >= 1 and rows % rows_per_seq == 0, "Q holds rows_per_seq rows per sequence"
+    assert n_heads >= 1 and d % n_heads == 0, "d % n_heads == 0"
+    dk = d // n_heads
+    n_kv = _kv_heads(n_heads, n_kv_heads)
+    assert K.shape[2] == n_kv * dk and V.shape[2] == n_kv * dk, "K and V: [slabs, rows, n_kv_heads * d_k]"
+    if scale is None:
+        scale = ctypes.c_float(1.0 / math.sqrt(float(dk))).value  # attention.cuh:64
+    if O is None:
+        O = torch.empty((rows, d), dtype=torch.float32, device=Q.device)
+    _require_device_f32(O, "O")
+    assert O.shape == (rows, d) and (O.stride(1) == 1 or d == 1), "O: as Q, with unit inner stride"
+    return rows // rows_per_seq, dk, n_kv, float(scale), O
+
+
+def attention_decode_batched_kv16(Q, K, V, n_heads: int, n_kv_heads, seq_kv, q_pos0=None, kv_slot=None,
+                                  rows_per_seq: int = 1, scale=None, O=None):
+    """attention_decode_batched_gqa over a bf16 cache (qgemm_attention_decode_batched_kv16): K and V are
+    [slabs, rows, n_kv_heads * d_k] torch.bfloat16 device tensors or views with unit inner stride, Q and O fp32.  The
+    rows are bit for bit attention_decode_batched_gqa's (n_kv_heads None or n_heads: attention_decode_batched's) on
+    K.float() / V.float().  1 <= n_heads // n_kv_heads <= 16, d_k <= 64 or 96 or 128, at most 8 rows per sequence;
+    nothing else reads bf16, so outside that the call fails."""
+    n_seqs, dk, n_kv, scale, O = _kv16_call(Q, K, V, n_heads, n_kv_heads, rows_per_seq, scale, O)
+    seq_kv = [int(v) for v in seq_kv]
+    slots = list(range(n_seqs)) if kv_slot is None else [int(v) for v in kv_slot]
+    assert len(seq_kv) == n_seqs and len(slots) == n_seqs, "seq_kv and kv_slot: one entry per sequence"
+    for b in range(n_seqs):  # the slabs and rows the call reads exist
+        assert 0 <= slots[b] < min(K.shape[0], V.shape[0]), f"kv_slot[{b}] names no slab of K / V"
+        assert seq_kv[b] <= min(K.shape[1], V.shape[1]), f"seq_kv[{b}] exceeds the slab's rows"
+    _check("qgemm_attention_decode_batched_kv16",
+           load().qgemm_attention_decode_batched_kv16(
+               Q.data_ptr(), Q.stride(0), K.data_ptr(), K.stride(1), K.stride(0), V.data_ptr(), V.stride(1),
+               V.stride(0), O.data_ptr(), O.stride(0), n_seqs, rows_per_seq, _int_array(kv_slot, n_seqs, "kv_slot"),
+               _int_array(seq_kv, n_seqs, "seq_kv"), _int_array(q_pos0, n_seqs, "q_pos0"), n_heads, n_kv, dk, scale,
+               _stream(Q.device)))
+    return O
+
+
+def attention_decode_indirect_kv16(Q, K, V, n_heads: int, row_slab, seq_kv, q_pos0=None, tab_row=None,
+                                   rows_per_seq: int = 1, scale=None, O=None, n_kv_heads=None):
+    """attention_decode_indirect over a bf16 cache (qgemm_attention_decode_indirect_kv16): K / V row j of
+    sequence b is row j of slab row_slab[tab_row[b]][j] of the torch.bfloat16 slabs K / V, an entry >= the number of
+    slabs a row of quiet NaNs.  Bit for bit attention_decode_indirect(..., n_kv_heads=) on K.float() / V.float(); the
+    envelope is attention_decode_batched_kv16's."""
+    n_seqs, dk, n_kv, scale, O = _kv16_call(Q, K, V, n_heads, n_kv_heads, rows_per_seq, scale, O)
+    _require_row_table(row_slab, "row_slab")
+    seq_kv = [int(v) for v in seq_kv]
+    trows = list(range(n_seqs)) if tab_row is None else [int(v) for v in tab_row]
+    assert len(seq_kv) == n_seqs and len(trows) == n_seqs, "seq_kv and tab_row: one entry per sequence"
+    for b in range(n_seqs):  # the table rows, entries and slab rows the call reads exist
+        assert 0 <= trows[b] < row_slab.shape[0], f"tab_row[{b}] names no row of the table"
+        assert seq_kv[b] <= min(K.shape[1], V.shape[1], row_slab.shape[1]), f"seq_kv[{b}] exceeds the slab's rows"
+    _check("qgemm_attention_decode_indirect_kv16",
+           load().qgemm_attention_decode_indirect_kv16(
+               Q.data_ptr(), Q.stride(0), K.data_ptr(), K.stride(1), K.stride(0), V.data_ptr(), V.stride(1),
+               V.stride(0), O.data_ptr(), O.stride(0), n_seqs, rows_per_seq, row_slab.data_ptr(),
+               row_slab.stride(0) if row_slab.shape[0] > 1 else row_slab.shape[1], min(K.shape[0], V.shape[0]),
+               _int_array(tab_row, n_seqs, "tab_row"), _int_array(seq_kv, n_seqs, "seq_kv"),
+               _int_array(q_pos0, n_seqs, "q_pos0"), n_heads, n_kv, dk, scale, _stream(Q.device)))
+    return O
+
+
+def attention_decode_kv16_plan(rows_per_seq: int, n_heads: int, n_kv_heads: int, d_k: int) -> str:
+    """The kernel the bf16-cache decode calls launch (qgemm_attention_decode_kv16_plan; needs no GPU):
+    "attention_decode_kv16_kernel" (d_k <= 64) or "attention_decode_kv16_wide_kernel" (d_k 96 or 128).  Raises
+    QGemmError outside the envelope."""
+    name = ctypes.c_char_p()
+    _check("qgemm_attention_decode_kv16_plan",
+           load().qgemm_attention_decode_kv16_plan(rows_per_seq, n_heads, n_kv_heads, d_k, ctypes.byref(name)))
+    return name.value.decode()
+
+
+def kv_append_bf16(K, V, Kc, Vc, pos, kv_slot=None, rows_per_seq: int = 1):
+    """Round new K / V rows to bf16 into a cache, one launch (qgemm_kv_append_bf16).  K and V: 2-D fp32
+    device tensors or views (n_seqs * rows_per_seq) x width with unit inner stride (e.g. the thirds of a [Q | K | V]
+    buffer); Kc and Vc: [slabs, rows, width] torch.bfloat16 device tensors or views.  Source row b * rows_per_seq + r
+    lands in row pos[b] + r of slab kv_slot[b] (left out: slab b), rounded to nearest even as Tensor.to(bfloat16)
+    rounds; nothing else is written.  pos and kv_slot are host sequences of ints, read at the call."""
+    _require_device_f32(K, "K")
+    _require_device_f32(V, "V")
+    _require_bf16_slabs(Kc, "Kc")
+    _require_bf16_slabs(Vc, "Vc")
+    rows, width = K.shape
+    assert V.shape == K.shape and width >= 1, "K and V: the same rows x width"
+    assert (K.stride(1) == 1 and V.stride(1) == 1) or width == 1, "K and V must have unit inner stride"
+    assert rows_per_seq >= 1 and rows >= 1 and rows % rows_per_seq == 0, "rows_per_seq rows per sequence"
+    n_seqs = rows // rows_per_seq
+    assert Kc.shape[2] == width and Vc.shape[2] == width, "Kc and Vc: [slabs, rows, width]"
+    pos = [int(v) for v in pos]
+    slots = list(range(n_seqs)) if kv_slot is None else [int(v) for v in kv_slot]
+    assert len(pos) == n_seqs and len(slots) == n_seqs, "pos and kv_slot: one entry per sequence"
+    for b in range(n_seqs):  # the slabs and rows the call writes exist
+        assert 0 <= slots[b] < min(Kc.shape[0], Vc.shape[0]), f"kv_slot[{b}] names no slab of Kc / Vc"
+        assert 0 <= pos[b] and pos[b] + rows_per_seq <= min(Kc.shape[1], Vc.shape[1]), \
+            f"pos[{b}] + rows_per_seq exceeds the slab's rows"
+    _check("qgemm_kv_append_bf16",
+           load().qgemm_kv_append_bf16(K.data_ptr(), K.stride(0), V.data_ptr(), V.stride(0), Kc.data_ptr(),
+                                       Kc.stride(1), Kc.stride(0), Vc.data_ptr(), Vc.stride(1), Vc.stride(0), n_seqs,
+                                       rows_per_seq, _int_array(kv_slot, n_seqs, "kv_slot"),
+                                       _int_array(pos, n_seqs, "pos"), width, _stream(K.device)))
 
 
 def beam_reindex(row_slab, slots, parents, n_rows, beams: int):

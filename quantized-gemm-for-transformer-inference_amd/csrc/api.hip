@@ -994,6 +994,47 @@ int qgemm_attention_plan(int seq_q, int seq_kv, int n_heads, int d_k, const char
     return 0;
 }
 
+// ---- decode attention over a bf16 K / V cache and its append ----
+
+int qgemm_attention_decode_batched_kv16(const float *Q, int64_t q_stride_h, const void *K, int64_t k_stride_h,
+                                        int64_t k_stride_seq, const void *V, int64_t v_stride_h, int64_t v_stride_seq,
+                                        float *O, int64_t o_stride_h, int n_seqs, int rows_per_seq, const int *kv_slot,
+                                        const int *seq_kv, const int *q_pos0, int n_heads, int n_kv_heads, int d_k,
+                                        float scale, void *stream) {
+    return err(launch_attention_batched_kv16(Q, q_stride_h, static_cast<const bf16_t *>(K), k_stride_h, k_stride_seq,
+                                             static_cast<const bf16_t *>(V), v_stride_h, v_stride_seq, O, o_stride_h,
+                                             n_seqs, rows_per_seq, kv_slot, seq_kv, q_pos0, n_heads, n_kv_heads, d_k,
+                                             scale, static_cast<hipStream_t>(stream)));
+}
+
+int qgemm_attention_decode_indirect_kv16(const float *Q, int64_t q_stride_h, const void *K, int64_t k_stride_h,
+                                         int64_t k_stride_seq, const void *V, int64_t v_stride_h, int64_t v_stride_seq,
+                                         float *O, int64_t o_stride_h, int n_seqs, int rows_per_seq,
+                                         const uint8_t *row_slab, int64_t row_slab_stride, int n_slabs,
+                                         const int *tab_row, const int *seq_kv, const int *q_pos0, int n_heads,
+                                         int n_kv_heads, int d_k, float scale, void *stream) {
+    return err(launch_attention_indirect_kv16(Q, q_stride_h, static_cast<const bf16_t *>(K), k_stride_h, k_stride_seq,
+                                              static_cast<const bf16_t *>(V), v_stride_h, v_stride_seq, O, o_stride_h,
+                                              n_seqs, rows_per_seq, row_slab, row_slab_stride, n_slabs, tab_row, seq_kv,
+                                              q_pos0, n_heads, n_kv_heads, d_k, scale,
+                                              static_cast<hipStream_t>(stream)));
+}
+
+int qgemm_attention_decode_kv16_plan(int rows_per_seq, int n_heads, int n_kv_heads, int d_k, const char **kernel) {
+    if (!attention_decode_kv16_ok(rows_per_seq, 1, d_k, n_heads, n_kv_heads)) return (int)hipErrorInvalidValue;
+    if (kernel) *kernel = attention_decode_kv16_plan_name(d_k);
+    return 0;
+}
+
+int qgemm_kv_append_bf16(const float *K, int64_t k_stride_h, const float *V, int64_t v_stride_h, void *Kc,
+                         int64_t kc_stride_h, int64_t kc_stride_seq, void *Vc, int64_t vc_stride_h,
+                         int64_t vc_stride_seq, int n_seqs, int rows_per_seq, const int *kv_slot, const int *pos,
+                         int width, void *stream) {
+    return err(launch_kv_append_bf16(K, k_stride_h, V, v_stride_h, static_cast<bf16_t *>(Kc), kc_stride_h, kc_stride_seq,
+                                     static_cast<bf16_t *>(Vc), vc_stride_h, vc_stride_seq, n_seqs, rows_per_seq,
+                                     kv_slot, pos, width, static_cast<hipStream_t>(stream)));
+}
+
 #ifndef QGEMM_SRC_HASH
 #define QGEMM_SRC_HASH "unknown"
 #endif

@@ -708,4 +708,26 @@ struct StackDesc {
 };
 hipError_t stack_describe(const Stack *S, StackDesc *out);
 
+// attention_decode_kv16.hip: decode attention over bf16 K / V slabs (strides in bf16 elements), one
+// kernel for 1 <= G <= 16, the bits of the fp32 decode launches on the widened cache.  attention_decode_kv16_ok: 1 .. 8
+// rows, seq_kv 1 .. 4096, d_k <= 64 or 96 / 128, whole groups of at most 16; the plan name goes by d_k.  The launches run
+// launch_attention_batched's / _indirect's checks and table and return hipErrorInvalidValue outside the envelope.
+bool attention_decode_kv16_ok(int rows_per_seq, int seq_kv, int dk, int n_heads, int n_kv_heads);
+const char *attention_decode_kv16_plan_name(int dk);
+hipError_t launch_attention_batched_kv16(const float *Q, int64_t ldq, const bf16_t *K, int64_t ldk, int64_t k_stride_seq,
+                                         const bf16_t *V, int64_t ldv, int64_t v_stride_seq, float *O, int64_t ldo,
+                                         int n_seqs, int rows_per_seq, const int *kv_slot, const int *seq_kv,
+                                         const int *q_pos0, int n_heads, int n_kv_heads, int dk, float scale,
+                                         hipStream_t stream);
+hipError_t launch_attention_indirect_kv16(const float *Q, int64_t ldq, const bf16_t *K, int64_t ldk,
+                                          int64_t k_stride_seq, const bf16_t *V, int64_t ldv, int64_t v_stride_seq,
+                                          float *O, int64_t ldo, int n_seqs, int rows_per_seq, const uint8_t *row_slab,
+                                          int64_t row_slab_stride, int n_slabs, const int *tab_row, const int *seq_kv,
+                                          const int *q_pos0, int n_heads, int n_kv_heads, int dk, float scale,
+                                          hipStream_t stream);
+// ... and its cache append: fp32 rows rounded to bf16 (pk_bf16) into rows pos[b] .. of slab kv_slot[b] (nullptr: b)
+hipError_t launch_kv_append_bf16(const float *K, int64_t k_ld, const float *V, int64_t v_ld, bf16_t *Kc, int64_t kc_ld,
+                                 int64_t kc_stride_seq, bf16_t *Vc, int64_t vc_ld, int64_t vc_stride_seq, int n_seqs,
+                                 int rows_per_seq, const int *kv_slot, const int *pos, int width, hipStream_t stream);
+
 }  // namespace qgemm
