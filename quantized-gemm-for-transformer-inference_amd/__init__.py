@@ -1761,49 +1761,12 @@ def attention_decode_batched(Q, K, V, n_heads: int, seq_kv, q_pos0=None, kv_slot
     return attention_decode_batched_gqa(Q, K, V, n_heads, None, seq_kv, q_pos0, kv_slot, rows_per_seq, scale, O)
 
 
-def attention_decode_batched_gqa(Q, K, V, n_heads: int, n_kv_heads, seq_kv, q_pos0=None, kv_slot=None,
-                                 rows_per_seq: int = 1, scale=None, O=None):
-    """attention_decode_batched for grouped-query heads (qgemm_attention_decode_batched_gqa, DESIGN.md s30): K and V
-    are [slabs, rows, n_kv_heads * d_k] and query head h reads their head h // (n_heads // n_kv_heads), at most 16 query
-    heads per KV head -- the bits of attention_decode_batched on K / V with every head repeated.  n_kv_heads None or
-    n_heads is exactly attention_decode_batched."""
-    import math
+def _require_slabs(t, name, dtype):
+    """A K / V cache: a 3-D device tensor or view [slabs, rows, d] of dtype with unit inner stride."""
     import torch
-    _require_device_f32(Q, "Q")
-    assert Q.stride(1) == 1 or Q.shape[1] == 1, "Q must have unit inner stride"
-    for t, nm in ((K, "K"), (V, "V")):
-        assert isinstance(t, torch.Tensor) and t.dim() == 3 and t.is_cuda and t.dtype == torch.float32, \
-            f"{nm}: a 3-D float32 device tensor [slabs, rows, d]"
-        assert t.stride(2) == 1 or t.shape[2] == 1, f"{nm} must have unit inner stride"
-    rows, d = Q.shape
-    assert rows_per_seq >= 1 and rows % rows_per_seq == 0, "Q holds rows_per_seq rows per sequence"
-    n_seqs = rows // rows_per_seq
-    assert n_heads >= 1 and d % n_heads == 0, "d % n_heads == 0"
-    dk = d // n_heads
-    n_kv = _kv_heads(n_heads, n_kv_heads)
-    assert K.shape[2] == n_kv * dk and V.shape[2] == n_kv * dk, "K and V: [slabs, rows, n_kv_heads * d_k]"
-    seq_kv = [int(v) for v in seq_kv]
-    slots = list(range(n_seqs)) if kv_slot is None else [int(v) for v in kv_slot]
-    assert len(seq_kv) == n_seqs and len(slots) == n_seqs, "seq_kv and kv_slot: one entry per sequence"
-    for b in range(n_seqs):  # the slabs and rows the call reads exist
-        assert 0 <= slots[b] < min(K.shape[0], V.shape[0]), f"kv_slot[{b}] names no slab of K / V"
-        assert seq_kv[b] <= min(K.shape[1], V.shape[1]), f"seq_kv[{b}] exceeds the slab's rows"
-    if scale is None:
-        scale = ctypes.c_float(1.0 / math.sqrt(float(dk))).value  # attention.cuh:64
-    if O is None:
-        O = torch.empty((rows, d), dtype=torch.float32, device=Q.device)
-    _require_device_f32(O, "O")
-    assert O.shape == (rows, d) and (O.stride(1) == 1 or d == 1), "O: as Q, with unit inner stride"
-    head = (Q.data_ptr(), Q.stride(0), K.data_ptr(), K.stride(1), K.stride(0), V.data_ptr(), V.stride(1), V.stride(0),
-            O.data_ptr(), O.stride(0), n_seqs, rows_per_seq, _int_array(kv_slot, n_seqs, "kv_slot"),
-            _int_array(seq_kv, n_seqs, "seq_kv"), _int_array(q_pos0, n_seqs, "q_pos0"), n_heads)
-    if n_kv != n_heads:
-        _check("qgemm_attention_decode_batched_gqa",
-               load().qgemm_attention_decode_batched_gqa(*head, n_kv, dk, float(scale), _stream(Q.device)))
-        return O
-    _check("qgemm_attention_decode_batched",
-           load().qgemm_attention_decode_batched(*head, dk, float(scale), _stream(Q.device)))
-    return O
+    assert isinstance(t, torch.Tensor) and t.dim() == 3 and t.is_cuda and t.dtype == dtype, \
+        f"{name}: a 3-D {str(dtype).split('.')[-1]} device tensor [slabs, rows, d]"
+    assert t.stride(2) == 1 or t.shape[2] == 1, f"{name} must have unit inner stride"
 
 
 def _require_row_table(t, name):
@@ -1815,23 +1778,19 @@ def _require_row_table(t, name):
     assert t.shape[0] <= 1 or t.stride(0) >= t.shape[1], f"{name}: the row stride covers a row"
 
 
-def attention_decode_indirect(Q, K, V, n_heads: int, row_slab, seq_kv, q_pos0=None, tab_row=None,
-                              rows_per_seq: int = 1, scale=None, O=None, n_kv_heads=None):
-    """attention_decode_batched through a per-row slab table (qgemm_attention_decode_indirect, DESIGN.md s23): K / V
-    row j of sequence b is row j of slab row_slab[tab_row[b]][j] (tab_row left out: row b).  row_slab: a 2-D uint8
-    device tensor or view [table rows, entries], unit inner stride, any row stride and alignment; an entry >= the
-    number of slabs stands for a row of quiet NaNs.  Bit for bit attention_decode_batched on slabs gathered that
-    way.  n_kv_heads: as attention_decode_batched_gqa's (qgemm_attention_decode_indirect_gqa); None or n_heads is
-    exactly the call without it."""
+def _decode_table_call(Q, K, V, kv_dtype, n_heads, n_kv_heads, row_slab, seq_kv, q_pos0, slot, rows_per_seq, scale, O):
+    """What the four decode-table calls share: the checks of Q / K / V (of kv_dtype) / O and of the per-sequence lists.
+    row_slab None: the batched forms, slot = kv_slot; else the indirect forms, slot = tab_row.  Returns the C-ABI
+    arguments up to n_heads, n_kv_heads, the arguments after it (d_k, scale, stream), and O."""
     import math
     import torch
     _require_device_f32(Q, "Q")
     assert Q.stride(1) == 1 or Q.shape[1] == 1, "Q must have unit inner stride"
-    for t, nm in ((K, "K"), (V, "V")):
-        assert isinstance(t, torch.Tensor) and t.dim() == 3 and t.is_cuda and t.dtype == torch.float32, \
-            f"{nm}: a 3-D float32 device tensor [slabs, rows, d]"
-        assert t.stride(2) == 1 or t.shape[2] == 1, f"{nm} must have unit inner stride"
-    _require_row_table(row_slab, "row_slab")
+    _require_slabs(K, "K", kv_dtype)
+    _require_slabs(V, "V", kv_dtype)
+    slot_name = "kv_slot" if row_slab is None else "tab_row"
+    if row_slab is not None:
+        _require_row_table(row_slab, "row_slab")
     rows, d = Q.shape
     assert rows_per_seq >= 1 and rows % rows_per_seq == 0, "Q holds rows_per_seq rows per sequence"
     n_seqs = rows // rows_per_seq
@@ -1840,61 +1799,63 @@ def attention_decode_indirect(Q, K, V, n_heads: int, row_slab, seq_kv, q_pos0=No
     n_kv = _kv_heads(n_heads, n_kv_heads)
     assert K.shape[2] == n_kv * dk and V.shape[2] == n_kv * dk, "K and V: [slabs, rows, n_kv_heads * d_k]"
     seq_kv = [int(v) for v in seq_kv]
-    trows = list(range(n_seqs)) if tab_row is None else [int(v) for v in tab_row]
-    assert len(seq_kv) == n_seqs and len(trows) == n_seqs, "seq_kv and tab_row: one entry per sequence"
+    slots = list(range(n_seqs)) if slot is None else [int(v) for v in slot]
+    assert len(seq_kv) == n_seqs and len(slots) == n_seqs, f"seq_kv and {slot_name}: one entry per sequence"
     n_slabs = min(K.shape[0], V.shape[0])
-    for b in range(n_seqs):  # the table rows, entries and slab rows the call reads exist
-        assert 0 <= trows[b] < row_slab.shape[0], f"tab_row[{b}] names no row of the table"
-        assert seq_kv[b] <= min(K.shape[1], V.shape[1], row_slab.shape[1]), f"seq_kv[{b}] exceeds the slab's rows"
+    for b in range(n_seqs):  # the slabs (table rows, entries) and slab rows the call reads exist
+        if row_slab is None:
+            assert 0 <= slots[b] < n_slabs, f"{slot_name}[{b}] names no slab of K / V"
+            assert seq_kv[b] <= min(K.shape[1], V.shape[1]), f"seq_kv[{b}] exceeds the slab's rows"
+        else:
+            assert 0 <= slots[b] < row_slab.shape[0], f"{slot_name}[{b}] names no row of the table"
+            assert seq_kv[b] <= min(K.shape[1], V.shape[1], row_slab.shape[1]), f"seq_kv[{b}] exceeds the slab's rows"
     if scale is None:
         scale = ctypes.c_float(1.0 / math.sqrt(float(dk))).value  # attention.cuh:64
     if O is None:
         O = torch.empty((rows, d), dtype=torch.float32, device=Q.device)
     _require_device_f32(O, "O")
     assert O.shape == (rows, d) and (O.stride(1) == 1 or d == 1), "O: as Q, with unit inner stride"
+    table = () if row_slab is None else (
+        row_slab.data_ptr(), row_slab.stride(0) if row_slab.shape[0] > 1 else row_slab.shape[1], n_slabs)
     head = (Q.data_ptr(), Q.stride(0), K.data_ptr(), K.stride(1), K.stride(0), V.data_ptr(), V.stride(1), V.stride(0),
-            O.data_ptr(), O.stride(0), n_seqs, rows_per_seq, row_slab.data_ptr(),
-            row_slab.stride(0) if row_slab.shape[0] > 1 else row_slab.shape[1], n_slabs,
-            _int_array(tab_row, n_seqs, "tab_row"), _int_array(seq_kv, n_seqs, "seq_kv"),
-            _int_array(q_pos0, n_seqs, "q_pos0"), n_heads)
+            O.data_ptr(), O.stride(0), n_seqs, rows_per_seq, *table, _int_array(slot, n_seqs, slot_name),
+            _int_array(seq_kv, n_seqs, "seq_kv"), _int_array(q_pos0, n_seqs, "q_pos0"), n_heads)
+    return head, n_kv, (dk, float(scale), _stream(Q.device)), O
+
+
+def attention_decode_batched_gqa(Q, K, V, n_heads: int, n_kv_heads, seq_kv, q_pos0=None, kv_slot=None,
+                                 rows_per_seq: int = 1, scale=None, O=None):
+    """attention_decode_batched for grouped-query heads (qgemm_attention_decode_batched_gqa, DESIGN.md s30): K and V
+    are [slabs, rows, n_kv_heads * d_k] and query head h reads their head h // (n_heads // n_kv_heads), at most 16 query
+    heads per KV head -- the bits of attention_decode_batched on K / V with every head repeated.  n_kv_heads None or
+    n_heads is exactly attention_decode_batched."""
+    import torch
+    head, n_kv, tail, O = _decode_table_call(Q, K, V, torch.float32, n_heads, n_kv_heads, None, seq_kv, q_pos0,
+                                             kv_slot, rows_per_seq, scale, O)
     if n_kv != n_heads:
-        _check("qgemm_attention_decode_indirect_gqa",
-               load().qgemm_attention_decode_indirect_gqa(*head, n_kv, dk, float(scale), _stream(Q.device)))
+        _check("qgemm_attention_decode_batched_gqa", load().qgemm_attention_decode_batched_gqa(*head, n_kv, *tail))
         return O
-    _check("qgemm_attention_decode_indirect",
-           load().qgemm_attention_decode_indirect(*head, dk, float(scale), _stream(Q.device)))
+    _check("qgemm_attention_decode_batched", load().qgemm_attention_decode_batched(*head, *tail))
     return O
 
 
-def _require_bf16_slabs(t, name):
-    """A bf16 cache: a 3-D bfloat16 device tensor or view [slabs, rows, d] with unit inner stride."""
+def attention_decode_indirect(Q, K, V, n_heads: int, row_slab, seq_kv, q_pos0=None, tab_row=None,
+                              rows_per_seq: int = 1, scale=None, O=None, n_kv_heads=None):
+    """attention_decode_batched through a per-row slab table (qgemm_attention_decode_indirect, DESIGN.md s23): K / V
+    row j of sequence b is row j of slab row_slab[tab_row[b]][j] (tab_row left out: row b).  row_slab: a 2-D uint8
+    device tensor or view [table rows, entries], unit inner stride, any row stride and alignment; an entry >= the
+    number of slabs stands for a row of quiet NaNs.  Bit for bit attention_decode_batched on slabs gathered that
+    way.  n_kv_heads: as attention_decode_batched_gqa's (qgemm_attention_decode_indirect_gqa); None or n_heads is
+    exactly the call without it."""
     import torch
-    assert isinstance(t, torch.Tensor) and t.dim() == 3 and t.is_cuda and t.dtype == torch.bfloat16, \
-        f"{name}: a 3-D bfloat16 device tensor [slabs, rows, d]"
-    assert t.stride(2) == 1 or t.shape[2] == 1, f"{name} must have unit inner stride"
-
-
-def _kv16_call(Q, K, V, n_heads, n_kv_heads, rows_per_seq, scale, O):
-    """What the two bf16-cache decode calls share: the checks of Q / K / V / O and (rows, n_seqs, dk, n_kv, scale, O)."""
-    import math
-    import torch
-    _require_device_f32(Q, "Q")
-    assert Q.stride(1) == 1 or Q.shape[1] == 1, "Q must have unit inner stride"
-    _require_bf16_slabs(K, "K")
-    _require_bf16_slabs(V, "V")
-    rows, d = Q.shape
-    assert rows_per_seq >= 1 and rows % rows_per_seq == 0, "Q holds rows_per_seq rows per sequence"
-    assert n_heads >= 1 and d % n_heads == 0, "d % n_heads == 0"
-    dk = d // n_heads
-    n_kv = _kv_heads(n_heads, n_kv_heads)
-    assert K.shape[2] == n_kv * dk and V.shape[2] == n_kv * dk, "K and V: [slabs, rows, n_kv_heads * d_k]"
-    if scale is None:
-        scale = ctypes.c_float(1.0 / math.sqrt(float(dk))).value  # attention.cuh:64
-    if O is None:
-        O = torch.empty((rows, d), dtype=torch.float32, device=Q.device)
-    _require_device_f32(O, "O")
-    assert O.shape == (rows, d) and (O.stride(1) == 1 or d == 1), "O: as Q, with unit inner stride"
-    return rows // rows_per_seq, dk, n_kv, float(scale), O
+    assert row_slab is not None, "row_slab: a 2-D uint8 device tensor"
+    head, n_kv, tail, O = _decode_table_call(Q, K, V, torch.float32, n_heads, n_kv_heads, row_slab, seq_kv, q_pos0,
+                                             tab_row, rows_per_seq, scale, O)
+    if n_kv != n_heads:
+        _check("qgemm_attention_decode_indirect_gqa", load().qgemm_attention_decode_indirect_gqa(*head, n_kv, *tail))
+        return O
+    _check("qgemm_attention_decode_indirect", load().qgemm_attention_decode_indirect(*head, *tail))
+    return O
 
 
 def attention_decode_batched_kv16(Q, K, V, n_heads: int, n_kv_heads, seq_kv, q_pos0=None, kv_slot=None,
@@ -1904,19 +1865,10 @@ def attention_decode_batched_kv16(Q, K, V, n_heads: int, n_kv_heads, seq_kv, q_p
     rows are bit for bit attention_decode_batched_gqa's (n_kv_heads None or n_heads: attention_decode_batched's) on
     K.float() / V.float().  1 <= n_heads // n_kv_heads <= 16, d_k <= 64 or 96 or 128, at most 8 rows per sequence;
     nothing else reads bf16, so outside that the call fails."""
-    n_seqs, dk, n_kv, scale, O = _kv16_call(Q, K, V, n_heads, n_kv_heads, rows_per_seq, scale, O)
-    seq_kv = [int(v) for v in seq_kv]
-    slots = list(range(n_seqs)) if kv_slot is None else [int(v) for v in kv_slot]
-    assert len(seq_kv) == n_seqs and len(slots) == n_seqs, "seq_kv and kv_slot: one entry per sequence"
-    for b in range(n_seqs):  # the slabs and rows the call reads exist
-        assert 0 <= slots[b] < min(K.shape[0], V.shape[0]), f"kv_slot[{b}] names no slab of K / V"
-        assert seq_kv[b] <= min(K.shape[1], V.shape[1]), f"seq_kv[{b}] exceeds the slab's rows"
-    _check("qgemm_attention_decode_batched_kv16",
-           load().qgemm_attention_decode_batched_kv16(
-               Q.data_ptr(), Q.stride(0), K.data_ptr(), K.stride(1), K.stride(0), V.data_ptr(), V.stride(1),
-               V.stride(0), O.data_ptr(), O.stride(0), n_seqs, rows_per_seq, _int_array(kv_slot, n_seqs, "kv_slot"),
-               _int_array(seq_kv, n_seqs, "seq_kv"), _int_array(q_pos0, n_seqs, "q_pos0"), n_heads, n_kv, dk, scale,
-               _stream(Q.device)))
+    import torch
+    head, n_kv, tail, O = _decode_table_call(Q, K, V, torch.bfloat16, n_heads, n_kv_heads, None, seq_kv, q_pos0,
+                                             kv_slot, rows_per_seq, scale, O)
+    _check("qgemm_attention_decode_batched_kv16", load().qgemm_attention_decode_batched_kv16(*head, n_kv, *tail))
     return O
 
 
@@ -1926,21 +1878,11 @@ def attention_decode_indirect_kv16(Q, K, V, n_heads: int, row_slab, seq_kv, q_po
     sequence b is row j of slab row_slab[tab_row[b]][j] of the torch.bfloat16 slabs K / V, an entry >= the number of
     slabs a row of quiet NaNs.  Bit for bit attention_decode_indirect(..., n_kv_heads=) on K.float() / V.float(); the
     envelope is attention_decode_batched_kv16's."""
-    n_seqs, dk, n_kv, scale, O = _kv16_call(Q, K, V, n_heads, n_kv_heads, rows_per_seq, scale, O)
-    _require_row_table(row_slab, "row_slab")
-    seq_kv = [int(v) for v in seq_kv]
-    trows = list(range(n_seqs)) if tab_row is None else [int(v) for v in tab_row]
-    assert len(seq_kv) == n_seqs and len(trows) == n_seqs, "seq_kv and tab_row: one entry per sequence"
-    for b in range(n_seqs):  # the table rows, entries and slab rows the call reads exist
-        assert 0 <= trows[b] < row_slab.shape[0], f"tab_row[{b}] names no row of the table"
-        assert seq_kv[b] <= min(K.shape[1], V.shape[1], row_slab.shape[1]), f"seq_kv[{b}] exceeds the slab's rows"
-    _check("qgemm_attention_decode_indirect_kv16",
-           load().qgemm_attention_decode_indirect_kv16(
-               Q.data_ptr(), Q.stride(0), K.data_ptr(), K.stride(1), K.stride(0), V.data_ptr(), V.stride(1),
-               V.stride(0), O.data_ptr(), O.stride(0), n_seqs, rows_per_seq, row_slab.data_ptr(),
-               row_slab.stride(0) if row_slab.shape[0] > 1 else row_slab.shape[1], min(K.shape[0], V.shape[0]),
-               _int_array(tab_row, n_seqs, "tab_row"), _int_array(seq_kv, n_seqs, "seq_kv"),
-               _int_array(q_pos0, n_seqs, "q_pos0"), n_heads, n_kv, dk, scale, _stream(Q.device)))
+    import torch
+    assert row_slab is not None, "row_slab: a 2-D uint8 device tensor"
+    head, n_kv, tail, O = _decode_table_call(Q, K, V, torch.bfloat16, n_heads, n_kv_heads, row_slab, seq_kv, q_pos0,
+                                             tab_row, rows_per_seq, scale, O)
+    _check("qgemm_attention_decode_indirect_kv16", load().qgemm_attention_decode_indirect_kv16(*head, n_kv, *tail))
     return O
 
 
@@ -1960,10 +1902,11 @@ def kv_append_bf16(K, V, Kc, Vc, pos, kv_slot=None, rows_per_seq: int = 1):
     buffer); Kc and Vc: [slabs, rows, width] torch.bfloat16 device tensors or views.  Source row b * rows_per_seq + r
     lands in row pos[b] + r of slab kv_slot[b] (left out: slab b), rounded to nearest even as Tensor.to(bfloat16)
     rounds; nothing else is written.  pos and kv_slot are host sequences of ints, read at the call."""
+    import torch
     _require_device_f32(K, "K")
     _require_device_f32(V, "V")
-    _require_bf16_slabs(Kc, "Kc")
-    _require_bf16_slabs(Vc, "Vc")
+    _require_slabs(Kc, "Kc", torch.bfloat16)
+    _require_slabs(Vc, "Vc", torch.bfloat16)
     rows, width = K.shape
     assert V.shape == K.shape and width >= 1, "K and V: the same rows x width"
     assert (K.stride(1) == 1 and V.stride(1) == 1) or width == 1, "K and V must have unit inner stride"

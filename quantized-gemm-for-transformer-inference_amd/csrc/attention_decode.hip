@@ -41,19 +41,13 @@ hipError_t launch_attention_decode(const float *Q, int64_t ldq, const float *K, 
     return decode_launch_any(grid, q_pos0 != kNoMask, Q, ldq, K, ldk, V, ldv, O, ldo, dk, scale, one, stream);
 }
 
-// tab: checked and clamped by launch_attention_batched (attention_launch.hip); the envelope is tested again here,
-// where the kernel's LDS arrays and grid are sized
+// tab: checked and clamped by launch_attention_batched (attention_launch.hip); the envelope is tested again here
+// (decode_table_ok), where the kernel's LDS arrays and grid are sized
 hipError_t launch_attention_decode_batched(const float *Q, int64_t ldq, const float *K, int64_t ldk, int64_t k_stride_seq,
                                            const float *V, int64_t ldv, int64_t v_stride_seq, float *O, int64_t ldo,
                                            int n_seqs, int rows_per_seq, const DecodeBatchTable &tab, bool causal,
                                            int n_heads, int dk, float scale, hipStream_t stream) {
-    if (n_seqs < 1 || n_seqs > kDecodeMaxBatch || rows_per_seq < 1 || rows_per_seq > kAttnDecodeMaxQ || dk < 1 ||
-        !attention_decode_any_ok(rows_per_seq, 1, dk) || n_heads < 1)
-        return hipErrorInvalidValue;
-    for (int b = 0; b < n_seqs; ++b)
-        if (tab.seq_kv[b] < 1 || tab.seq_kv[b] > kDecMaxSeq || tab.kv_slot[b] < 0 || tab.q_pos0[b] < 0 ||
-            tab.q_pos0[b] > tab.seq_kv[b])
-            return hipErrorInvalidValue;
+    if (n_heads < 1 || !decode_table_ok(tab, n_seqs, rows_per_seq, dk, false, 0)) return hipErrorInvalidValue;
     const dim3 grid((unsigned)n_heads, (unsigned)rows_per_seq, (unsigned)n_seqs);
     const DecodeMany many{k_stride_seq, v_stride_seq, rows_per_seq, tab};
     return decode_launch_any(grid, causal, Q, ldq, K, ldk, V, ldv, O, ldo, dk, scale, many, stream);
@@ -66,13 +60,9 @@ hipError_t launch_attention_decode_indirect(const float *Q, int64_t ldq, const f
                                             int n_seqs, int rows_per_seq, const uint8_t *row_slab,
                                             int64_t row_slab_stride, int n_slabs, const DecodeBatchTable &tab,
                                             bool causal, int n_heads, int dk, float scale, hipStream_t stream) {
-    if (n_seqs < 1 || n_seqs > kDecodeMaxBatch || rows_per_seq < 1 || rows_per_seq > kAttnDecodeMaxQ || dk < 1 ||
-        !attention_decode_any_ok(rows_per_seq, 1, dk) || n_heads < 1 || !row_slab || n_slabs < 1 || n_slabs > kDecodeMaxBatch)
+    if (n_heads < 1 || !row_slab || n_slabs < 1 || n_slabs > kDecodeMaxBatch ||
+        !decode_table_ok(tab, n_seqs, rows_per_seq, dk, true, row_slab_stride))
         return hipErrorInvalidValue;
-    for (int b = 0; b < n_seqs; ++b)
-        if (tab.seq_kv[b] < 1 || tab.seq_kv[b] > kDecMaxSeq || tab.kv_slot[b] < 0 || tab.q_pos0[b] < 0 ||
-            tab.q_pos0[b] > tab.seq_kv[b] || row_slab_stride < tab.seq_kv[b])
-            return hipErrorInvalidValue;
     const dim3 grid((unsigned)n_heads, (unsigned)rows_per_seq, (unsigned)n_seqs);
     const DecodeIndirect ind{k_stride_seq, v_stride_seq, rows_per_seq, n_slabs, row_slab, row_slab_stride, tab};
     return decode_launch_any(grid, causal, Q, ldq, K, ldk, V, ldv, O, ldo, dk, scale, ind, stream);

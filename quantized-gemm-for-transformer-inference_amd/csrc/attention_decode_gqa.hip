@@ -21,6 +21,8 @@
 // The stream is attention_decode_kernel's, text and reasons: K chunks then V chunks of 128 keys, two chunks in flight
 // in registers, the branch-free clamped fetch, the zero / NaN select in `put`, vector or scalar loads chosen once per
 // matrix, the indirect form's table row and slab offsets in LDS with nxo read before the refilled buffer is `put`.
+// (The kernel's text is a copy on purpose: with the prologue and the softmax as shared functions this kernel measured
+// up to 6 % slower, and the shared stream moved its register table; DESIGN.md s33, profiles/decode_refactor_probe.log.)
 // LDS: four score rows (64 KiB) + one chunk (34 / 66 KiB) + four query rows + the indirect form's tables (5 KiB): 137
 // KiB at kW = 128, one workgroup per CU.  Four heads per workgroup is what that budget holds; a group of G > 4 heads
 // takes ceil(G / 4) workgroups, the last of them with G % 4 heads (a runtime count: G = 3, 5, 7 are real models').
@@ -31,24 +33,21 @@ namespace qgemm {
 
 namespace {
 
-constexpr int kGqaHeads = 4;      // query heads of one KV group per workgroup
-constexpr int kGqaMaxGroup = 16;  // the largest G the decode launches take
-
 // group: G.  grid x = n_kv_heads * ceil(G / 4), y = query rows, z = sequences (DecodeMany, DecodeIndirect).
 template <bool kCausal, typename Seqs, int kW>
 __global__ __launch_bounds__(kDecThreads) void attention_decode_gqa_kernel(
     const float *__restrict__ Q, int64_t ldq, const float *__restrict__ K, int64_t ldk, const float *__restrict__ V,
     int64_t ldv, float *__restrict__ O, int64_t ldo, int dk, float scale, int group, Seqs seqs) {
-    __shared__ __attribute__((aligned(16))) float S[kGqaHeads][kDecMaxSeq];
+    __shared__ __attribute__((aligned(16))) float S[kDecGroupHeads][kDecMaxSeq];
     constexpr int kPieces = kW / 4, kShift = kW == 64 ? 4 : 5;       // float4 pieces of a row: f >> kShift = the key
     constexpr int kDecStride = kW + 4;                                // chunk row stride (floats)
     constexpr int kDecPer = kDecChunk * kPieces / kDecThreads;        // float4 pieces of a chunk per thread
     __shared__ __attribute__((aligned(16))) float KV[kDecChunk * kDecStride];
-    __shared__ __attribute__((aligned(16))) float Qs[kGqaHeads][kW];
-    const int nblk = (group + kGqaHeads - 1) / kGqaHeads;
+    __shared__ __attribute__((aligned(16))) float Qs[kDecGroupHeads][kW];
+    const int nblk = (group + kDecGroupHeads - 1) / kDecGroupHeads;
     const int kvh = blockIdx.x / nblk, blk = blockIdx.x - kvh * nblk, qi = blockIdx.y;
-    const int h0 = kvh * group + kGqaHeads * blk;                     // the block's first query head
-    const int nh = min(kGqaHeads, group - kGqaHeads * blk);           // its heads: 1 .. 4
+    const int h0 = kvh * group + kDecGroupHeads * blk;                // the block's first query head
+    const int nh = min(kDecGroupHeads, group - kDecGroupHeads * blk); // its heads: 1 .. 4
     int seq_kv, q_pos0;
     constexpr bool kIndirect = std::is_same<Seqs, DecodeIndirect>::value;
     // DecodeIndirect alone, as attention_decode_kernel: the sequence's table row and the slabs' offsets in LDS
@@ -173,7 +172,7 @@ __global__ __launch_bounds__(kDecThreads) void attention_decode_gqa_kernel(
     if constexpr (kIndirect) slabs_g(1);
     fetch_g(pfb, 1);
     // the block's query rows, zeros past d_k and in the rows of heads the block does not have
-    for (int i = t; i < kGqaHeads * kW; i += kDecThreads) {
+    for (int i = t; i < kDecGroupHeads * kW; i += kDecThreads) {
         const int hh = i / kW, c = i & (kW - 1);
         Qs[hh][c] = hh < nh && c < dk ? Qb[(int64_t)hh * dk + c] : 0.0f;
     }
@@ -340,38 +339,26 @@ __global__ __launch_bounds__(kDecThreads) void attention_decode_gqa_kernel(
     }
 }
 
-template <int kW, typename Seqs>
-hipError_t gqa_launch_w(const dim3 &grid, bool causal, const float *Q, int64_t ldq, const float *K, int64_t ldk,
-                        const float *V, int64_t ldv, float *O, int64_t ldo, int dk, float scale, int group,
-                        const Seqs &seqs, hipStream_t stream) {
-    auto *kernel = causal ? attention_decode_gqa_kernel<true, Seqs, kW> : attention_decode_gqa_kernel<false, Seqs, kW>;
-    kernel<<<grid, kDecThreads, 0, stream>>>(Q, ldq, K, ldk, V, ldv, O, ldo, dk, scale, group, seqs);
-    return hipGetLastError();
-}
-
 // the instantiation a launch takes (the caller has tested that d_k lies in one of the two envelopes), on the grid
 // (KV heads x blocks of a group, rows, sequences)
 template <typename Seqs>
 hipError_t gqa_launch(int rows, int n_seqs, bool causal, const float *Q, int64_t ldq, const float *K, int64_t ldk,
                       const float *V, int64_t ldv, float *O, int64_t ldo, int n_heads, int n_kv_heads, int dk,
                       float scale, const Seqs &seqs, hipStream_t stream) {
-    const int group = n_heads / n_kv_heads;
-    const dim3 grid((unsigned)(n_kv_heads * ((group + kGqaHeads - 1) / kGqaHeads)), (unsigned)rows, (unsigned)n_seqs);
-    if (dk > kDecMaxDk)
-        return gqa_launch_w<kDecWideDk>(grid, causal, Q, ldq, K, ldk, V, ldv, O, ldo, dk, scale, group, seqs, stream);
-    return gqa_launch_w<kDecMaxDk>(grid, causal, Q, ldq, K, ldk, V, ldv, O, ldo, dk, scale, group, seqs, stream);
-}
-
-// what the three launch functions below share: whole groups of 2 .. 16 heads
-bool groups_ok(int n_heads, int n_kv_heads) {
-    return n_kv_heads >= 1 && n_heads >= 1 && n_heads % n_kv_heads == 0 && n_heads / n_kv_heads >= 2 &&
-           n_heads / n_kv_heads <= kGqaMaxGroup;
+    auto *kernel = dk > kDecMaxDk ? (causal ? attention_decode_gqa_kernel<true, Seqs, kDecWideDk>
+                                            : attention_decode_gqa_kernel<false, Seqs, kDecWideDk>)
+                                  : (causal ? attention_decode_gqa_kernel<true, Seqs, kDecMaxDk>
+                                            : attention_decode_gqa_kernel<false, Seqs, kDecMaxDk>);
+    kernel<<<decode_group_grid(n_heads, n_kv_heads, rows, n_seqs), kDecThreads, 0, stream>>>(
+        Q, ldq, K, ldk, V, ldv, O, ldo, dk, scale, n_heads / n_kv_heads, seqs);
+    return hipGetLastError();
 }
 
 }  // namespace
 
+// whole groups of 2 .. 16 heads inside either decode envelope
 bool attention_decode_gqa_ok(int seq_q, int seq_kv, int dk, int n_heads, int n_kv_heads) {
-    return attention_decode_any_ok(seq_q, seq_kv, dk) && groups_ok(n_heads, n_kv_heads);
+    return attention_decode_any_ok(seq_q, seq_kv, dk) && groups_ok(n_heads, n_kv_heads, 2);
 }
 
 hipError_t launch_attention_decode_gqa(const float *Q, int64_t ldq, const float *K, int64_t ldk, const float *V,
@@ -388,19 +375,14 @@ hipError_t launch_attention_decode_gqa(const float *Q, int64_t ldq, const float 
 }
 
 // tab: checked and clamped by launch_attention_batched_gqa (attention_launch.hip); what sizes the kernel's LDS arrays
-// and grid is tested again here, as in launch_attention_decode_batched
+// and grid is tested again here (decode_table_ok), as in launch_attention_decode_batched
 hipError_t launch_attention_decode_batched_gqa(const float *Q, int64_t ldq, const float *K, int64_t ldk,
                                                int64_t k_stride_seq, const float *V, int64_t ldv, int64_t v_stride_seq,
                                                float *O, int64_t ldo, int n_seqs, int rows_per_seq,
                                                const DecodeBatchTable &tab, bool causal, int n_heads, int n_kv_heads,
                                                int dk, float scale, hipStream_t stream) {
-    if (n_seqs < 1 || n_seqs > kDecodeMaxBatch || rows_per_seq < 1 || rows_per_seq > kAttnDecodeMaxQ || dk < 1 ||
-        !attention_decode_gqa_ok(rows_per_seq, 1, dk, n_heads, n_kv_heads))
+    if (!groups_ok(n_heads, n_kv_heads, 2) || !decode_table_ok(tab, n_seqs, rows_per_seq, dk, false, 0))
         return hipErrorInvalidValue;
-    for (int b = 0; b < n_seqs; ++b)
-        if (tab.seq_kv[b] < 1 || tab.seq_kv[b] > kDecMaxSeq || tab.kv_slot[b] < 0 || tab.q_pos0[b] < 0 ||
-            tab.q_pos0[b] > tab.seq_kv[b])
-            return hipErrorInvalidValue;
     const DecodeMany many{k_stride_seq, v_stride_seq, rows_per_seq, tab};
     return gqa_launch(rows_per_seq, n_seqs, causal, Q, ldq, K, ldk, V, ldv, O, ldo, n_heads, n_kv_heads, dk, scale, many,
                       stream);
@@ -413,14 +395,9 @@ hipError_t launch_attention_decode_indirect_gqa(const float *Q, int64_t ldq, con
                                                 const uint8_t *row_slab, int64_t row_slab_stride, int n_slabs,
                                                 const DecodeBatchTable &tab, bool causal, int n_heads, int n_kv_heads,
                                                 int dk, float scale, hipStream_t stream) {
-    if (n_seqs < 1 || n_seqs > kDecodeMaxBatch || rows_per_seq < 1 || rows_per_seq > kAttnDecodeMaxQ || dk < 1 ||
-        !attention_decode_gqa_ok(rows_per_seq, 1, dk, n_heads, n_kv_heads) || !row_slab || n_slabs < 1 ||
-        n_slabs > kDecodeMaxBatch)
+    if (!groups_ok(n_heads, n_kv_heads, 2) || !row_slab || n_slabs < 1 || n_slabs > kDecodeMaxBatch ||
+        !decode_table_ok(tab, n_seqs, rows_per_seq, dk, true, row_slab_stride))
         return hipErrorInvalidValue;
-    for (int b = 0; b < n_seqs; ++b)
-        if (tab.seq_kv[b] < 1 || tab.seq_kv[b] > kDecMaxSeq || tab.kv_slot[b] < 0 || tab.q_pos0[b] < 0 ||
-            tab.q_pos0[b] > tab.seq_kv[b] || row_slab_stride < tab.seq_kv[b])
-            return hipErrorInvalidValue;
     const DecodeIndirect ind{k_stride_seq, v_stride_seq, rows_per_seq, n_slabs, row_slab, row_slab_stride, tab};
     return gqa_launch(rows_per_seq, n_seqs, causal, Q, ldq, K, ldk, V, ldv, O, ldo, n_heads, n_kv_heads, dk, scale, ind,
                       stream);

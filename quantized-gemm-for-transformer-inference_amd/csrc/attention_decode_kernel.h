@@ -75,6 +75,21 @@ struct DecodeIndirect {
     DecodeBatchTable tab;
 };
 
+// What the grouped decode launches share (attention_decode_gqa.hip, attention_decode_kv16.hip): a workgroup serves a block
+// of up to kDecGroupHeads query heads of one KV group, G = n_heads / n_kv_heads <= kDecMaxGroup.
+constexpr int kDecGroupHeads = 4;
+constexpr int kDecMaxGroup = 16;
+// whole groups of min_group .. kDecMaxGroup heads
+inline bool groups_ok(int n_heads, int n_kv_heads, int min_group) {
+    return n_kv_heads >= 1 && n_heads >= 1 && n_heads % n_kv_heads == 0 && n_heads / n_kv_heads >= min_group &&
+           n_heads / n_kv_heads <= kDecMaxGroup;
+}
+// the grouped kernels' grid: (KV heads x blocks of a group, rows, sequences)
+inline dim3 decode_group_grid(int n_heads, int n_kv_heads, int rows, int n_seqs) {
+    const int group = n_heads / n_kv_heads;
+    return dim3((unsigned)(n_kv_heads * ((group + kDecGroupHeads - 1) / kDecGroupHeads)), (unsigned)rows, (unsigned)n_seqs);
+}
+
 // The kW = 128 instantiations (attention_decode_wide.hip), one launch per Seqs type; d_k 96 or 128, everything else
 // as checked by the launch functions of attention_decode.hip.
 hipError_t launch_decode_wide(const dim3 &grid, bool causal, const float *Q, int64_t ldq, const float *K, int64_t ldk,

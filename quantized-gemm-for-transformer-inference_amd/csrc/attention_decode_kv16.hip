@@ -18,7 +18,8 @@
 //   s_h[j]     thread t owns key t of the chunk: it reads its K row from LDS ONCE as b128 reads of 8 elements, widens
 //              in registers (low half x << 16, high half x & 0xffff0000) and runs the chains of ALL the block's heads
 //              against it; the upper two chains are skipped by a workgroup-uniform branch when the block has <= 2 heads
-//   softmax    wave w = head w, everything wave-local: attention_decode_gqa_kernel's text
+//   softmax    wave w = head w, everything wave-local: attention_decode_gqa_kernel's text (a copy on purpose: shared
+//              with the prologue it measured 1 - 2 % slower through the indirect table)
 //   O_h = p V  wave w = head w at both widths; lane l owns columns 2l and 2l + 1: ONE b32 LDS read per key feeds both
 //              columns' fmaf chains, P comes from one broadcast row; lanes with 2l >= d_k sit idle
 // so a key costs half the barriers and half the memory round trips of the fp32 kernels.
@@ -35,8 +36,6 @@ namespace qgemm {
 
 namespace {
 
-constexpr int kKv16Heads = 4;       // query heads of one KV group per workgroup
-constexpr int kKv16MaxGroup = 16;   // the largest G the launches take
 constexpr int kKv16Chunk = 256;     // keys per staged K / V chunk: one per thread
 constexpr int kKv16Pad = 8;         // bf16 elements of padding behind a staged row
 
@@ -50,7 +49,7 @@ __global__ __launch_bounds__(kDecThreads) void attention_decode_kv16_kernel(
     const float *__restrict__ Q, int64_t ldq, const bf16_t *__restrict__ K, int64_t ldk, const bf16_t *__restrict__ V,
     int64_t ldv, float *__restrict__ O, int64_t ldo, int dk, float scale, int group, Seqs seqs) {
     static_assert(kKv16Chunk == kDecThreads, "thread t owns key t of a chunk");
-    __shared__ __attribute__((aligned(16))) float S[kKv16Heads][kDecMaxSeq];
+    __shared__ __attribute__((aligned(16))) float S[kDecGroupHeads][kDecMaxSeq];
     constexpr int kPieces = kW / 8;                                   // 8-element pieces of a row: 8 / 16
     constexpr int kStride = (kW + kKv16Pad) / 2;                      // chunk row stride (dwords): 36 / 68
     constexpr int kPer = kKv16Chunk * kPieces / kDecThreads;          // pieces of a chunk per thread: 8 / 16
@@ -59,11 +58,11 @@ __global__ __launch_bounds__(kDecThreads) void attention_decode_kv16_kernel(
     constexpr int kSeg = kPieces / 8, kRows = kPer / kSeg;
     static_assert(kRows == 8 && kRows * 32 == kKv16Chunk, "rows (t >> 3) + 32 r, r < 8, cover the chunk");
     __shared__ __attribute__((aligned(16))) uint32_t KV[kKv16Chunk * kStride];
-    __shared__ __attribute__((aligned(16))) float Qs[kKv16Heads][kW];
-    const int nblk = (group + kKv16Heads - 1) / kKv16Heads;
+    __shared__ __attribute__((aligned(16))) float Qs[kDecGroupHeads][kW];
+    const int nblk = (group + kDecGroupHeads - 1) / kDecGroupHeads;
     const int kvh = blockIdx.x / nblk, blk = blockIdx.x - kvh * nblk, qi = blockIdx.y;
-    const int h0 = kvh * group + kKv16Heads * blk;                    // the block's first query head
-    const int nh = min(kKv16Heads, group - kKv16Heads * blk);         // its heads: 1 .. 4
+    const int h0 = kvh * group + kDecGroupHeads * blk;                // the block's first query head
+    const int nh = min(kDecGroupHeads, group - kDecGroupHeads * blk); // its heads: 1 .. 4
     int seq_kv, q_pos0;
     constexpr bool kIndirect = std::is_same<Seqs, DecodeIndirect>::value;
     // DecodeIndirect alone, as attention_decode_kernel: the sequence's table row and the slabs' offsets in LDS
@@ -211,7 +210,7 @@ __global__ __launch_bounds__(kDecThreads) void attention_decode_kv16_kernel(
     if constexpr (kIndirect) slabs_g(1);
     fetch_g(pfb, 1);
     // the block's query rows, zeros past d_k and in the rows of heads the block does not have
-    for (int i = t; i < kKv16Heads * kW; i += kDecThreads) {
+    for (int i = t; i < kDecGroupHeads * kW; i += kDecThreads) {
         const int hh = i / kW, c = i & (kW - 1);
         Qs[hh][c] = hh < nh && c < dk ? Qb[(int64_t)hh * dk + c] : 0.0f;
     }
@@ -386,27 +385,19 @@ __global__ __launch_bounds__(kDecThreads) void attention_decode_kv16_kernel(
     }
 }
 
-template <int kW, typename Seqs>
-hipError_t kv16_launch_w(const dim3 &grid, bool causal, const float *Q, int64_t ldq, const bf16_t *K, int64_t ldk,
-                         const bf16_t *V, int64_t ldv, float *O, int64_t ldo, int dk, float scale, int group,
-                         const Seqs &seqs, hipStream_t stream) {
-    auto *kernel =
-        causal ? attention_decode_kv16_kernel<true, Seqs, kW> : attention_decode_kv16_kernel<false, Seqs, kW>;
-    kernel<<<grid, kDecThreads, 0, stream>>>(Q, ldq, K, ldk, V, ldv, O, ldo, dk, scale, group, seqs);
-    return hipGetLastError();
-}
-
 // the instantiation a launch takes (the caller has tested the envelope), on the grid (KV heads x blocks of a group,
 // rows, sequences)
 template <typename Seqs>
 hipError_t kv16_launch(int rows, int n_seqs, bool causal, const float *Q, int64_t ldq, const bf16_t *K, int64_t ldk,
                        const bf16_t *V, int64_t ldv, float *O, int64_t ldo, int n_heads, int n_kv_heads, int dk,
                        float scale, const Seqs &seqs, hipStream_t stream) {
-    const int group = n_heads / n_kv_heads;
-    const dim3 grid((unsigned)(n_kv_heads * ((group + kKv16Heads - 1) / kKv16Heads)), (unsigned)rows, (unsigned)n_seqs);
-    if (dk > kDecMaxDk)
-        return kv16_launch_w<kDecWideDk>(grid, causal, Q, ldq, K, ldk, V, ldv, O, ldo, dk, scale, group, seqs, stream);
-    return kv16_launch_w<kDecMaxDk>(grid, causal, Q, ldq, K, ldk, V, ldv, O, ldo, dk, scale, group, seqs, stream);
+    auto *kernel = dk > kDecMaxDk ? (causal ? attention_decode_kv16_kernel<true, Seqs, kDecWideDk>
+                                            : attention_decode_kv16_kernel<false, Seqs, kDecWideDk>)
+                                  : (causal ? attention_decode_kv16_kernel<true, Seqs, kDecMaxDk>
+                                            : attention_decode_kv16_kernel<false, Seqs, kDecMaxDk>);
+    kernel<<<decode_group_grid(n_heads, n_kv_heads, rows, n_seqs), kDecThreads, 0, stream>>>(
+        Q, ldq, K, ldk, V, ldv, O, ldo, dk, scale, n_heads / n_kv_heads, seqs);
+    return hipGetLastError();
 }
 
 // ---- kv_append_bf16_kernel: grid (source rows, 2048-column blocks, K | V); a thread rounds one piece of 8 columns.
@@ -451,44 +442,30 @@ __global__ __launch_bounds__(kDecThreads) void kv_append_bf16_kernel(AppendSide 
     }
 }
 
-// whole groups of 1 .. 16 heads
-bool kv16_groups_ok(int n_heads, int n_kv_heads) {
-    return n_kv_heads >= 1 && n_heads >= 1 && n_heads % n_kv_heads == 0 && n_heads / n_kv_heads <= kKv16MaxGroup;
-}
-
 }  // namespace
 
+// whole groups of 1 .. 16 heads inside either decode envelope
 bool attention_decode_kv16_ok(int rows_per_seq, int seq_kv, int dk, int n_heads, int n_kv_heads) {
     return rows_per_seq >= 1 && seq_kv >= 1 && dk >= 1 && attention_decode_any_ok(rows_per_seq, seq_kv, dk) &&
-           kv16_groups_ok(n_heads, n_kv_heads);
+           groups_ok(n_heads, n_kv_heads, 1);
 }
 
 const char *attention_decode_kv16_plan_name(int dk) {
     return dk <= kDecMaxDk ? "attention_decode_kv16_kernel" : "attention_decode_kv16_wide_kernel";
 }
 
-// launch_attention_batched's and launch_attention_indirect's checks and table (row_slab == nullptr with indirect
-// false: the batched form); the host arrays are read HERE, nothing is copied, allocated or synchronized.  Every check
-// comes before the launch, and nothing outside the envelope has another path: hipErrorInvalidValue.
+// decode_table_from_host's checks and table (attention_launch.hip) and the envelope.  Every check comes before the
+// launch, and nothing outside the envelope has another path: hipErrorInvalidValue.
 static hipError_t batched_kv16(const float *Q, int64_t ldq, const bf16_t *K, int64_t ldk, int64_t k_stride_seq,
                                const bf16_t *V, int64_t ldv, int64_t v_stride_seq, float *O, int64_t ldo, int n_seqs,
                                int rows_per_seq, bool indirect, const uint8_t *row_slab, int64_t row_slab_stride,
                                int n_slabs, const int *slot, const int *seq_kv, const int *q_pos0, int n_heads,
                                int n_kv_heads, int dk, float scale, hipStream_t stream) {
-    if (!Q || !K || !V || !O || !seq_kv || n_seqs < 0 || n_seqs > kDecodeMaxBatch ||
-        !attention_decode_kv16_ok(rows_per_seq, 1, dk, n_heads, n_kv_heads) ||
-        (indirect && (!row_slab || n_slabs < 1 || n_slabs > kDecodeMaxBatch)))
+    DecodeBatchTable tab;  // filled by decode_table_from_host, read only after its success
+    if (!Q || !K || !V || !O || !attention_decode_kv16_ok(rows_per_seq, 1, dk, n_heads, n_kv_heads) ||
+        decode_table_from_host(n_seqs, rows_per_seq, dk, slot, seq_kv, q_pos0, indirect, row_slab, row_slab_stride,
+                               n_slabs, tab))
         return hipErrorInvalidValue;
-    DecodeBatchTable tab = {};  // entries past n_seqs are never read; zeroed so the arguments are defined bytes
-    for (int b = 0; b < n_seqs; ++b) {
-        if (seq_kv[b] < 1 || seq_kv[b] > kDecMaxSeq || (q_pos0 && q_pos0[b] < 0) || (slot && slot[b] < 0) ||
-            (indirect && row_slab_stride < seq_kv[b]))
-            return hipErrorInvalidValue;
-        tab.kv_slot[b] = slot ? slot[b] : b;
-        tab.seq_kv[b] = seq_kv[b];
-        // past seq_kv - 1 the mask hides nothing: clamped, so the kernel's row limit cannot overflow
-        tab.q_pos0[b] = q_pos0 ? (q_pos0[b] < seq_kv[b] ? q_pos0[b] : seq_kv[b]) : 0;
-    }
     if (n_seqs == 0) return hipSuccess;
     if (indirect) {
         const DecodeIndirect ind{k_stride_seq, v_stride_seq, rows_per_seq, n_slabs, row_slab, row_slab_stride, tab};

@@ -105,54 +105,74 @@ hipError_t launch_attention_varlen(const float *Q, int64_t ldq, const float *K, 
     return hipSuccess;
 }
 
-// The decode launch over a batch of sequences (attention_decode.hip, DecodeMany): the host arrays are read HERE, into
-// the table that travels in the kernel arguments -- nothing is copied to the device, allocated or synchronized, and a
-// captured graph replays the values of the capture.  kv_slot == nullptr: slab b for sequence b; q_pos0 == nullptr: no
-// mask.  Every check comes before the launch.
-hipError_t launch_attention_batched(const float *Q, int64_t ldq, const float *K, int64_t ldk, int64_t k_stride_seq,
-                                    const float *V, int64_t ldv, int64_t v_stride_seq, float *O, int64_t ldo, int n_seqs,
-                                    int rows_per_seq, const int *kv_slot, const int *seq_kv, const int *q_pos0,
-                                    int n_heads, int dk, float scale, hipStream_t stream) {
-    if (!Q || !K || !V || !O || !seq_kv || n_seqs < 0 || n_seqs > kDecodeMaxBatch || n_heads < 1 ||
-        !attention_decode_any_ok(rows_per_seq, 1, dk) || rows_per_seq < 1 || dk < 1)
+// ---- the decode launches over a table of sequences ----
+
+// What every table launch checks and fills, ONE text for the multi-head, grouped and bf16-cache forms: the host arrays
+// are read HERE, into the table that travels in the kernel arguments -- nothing is copied to the device, allocated or
+// synchronized, and a captured graph replays the values of the capture.  slot == nullptr: slab (indirect: table row) b
+// for sequence b; q_pos0 == nullptr: no mask.  indirect: also what keeps the kernel's table reads inside the table's
+// rows (a stride that covers seq_kv[b] entries) and its clamp meaningful (1 <= n_slabs <= 64).
+hipError_t decode_table_from_host(int n_seqs, int rows_per_seq, int dk, const int *slot, const int *seq_kv,
+                                  const int *q_pos0, bool indirect, const uint8_t *row_slab, int64_t row_slab_stride,
+                                  int n_slabs, DecodeBatchTable &tab) {
+    if (!seq_kv || n_seqs < 0 || n_seqs > kDecodeMaxBatch || rows_per_seq < 1 || dk < 1 ||
+        !attention_decode_any_ok(rows_per_seq, 1, dk) ||
+        (indirect && (!row_slab || n_slabs < 1 || n_slabs > kDecodeMaxBatch)))
         return hipErrorInvalidValue;
-    DecodeBatchTable tab = {};  // entries past n_seqs are never read; zeroed so the arguments are defined bytes
+    tab = {};  // entries past n_seqs are never read; zeroed so the arguments are defined bytes
     for (int b = 0; b < n_seqs; ++b) {
         if (seq_kv[b] < 1 || !attention_decode_any_ok(rows_per_seq, seq_kv[b], dk) || (q_pos0 && q_pos0[b] < 0) ||
-            (kv_slot && kv_slot[b] < 0))
+            (slot && slot[b] < 0) || (indirect && row_slab_stride < seq_kv[b]))
             return hipErrorInvalidValue;
-        tab.kv_slot[b] = kv_slot ? kv_slot[b] : b;
+        tab.kv_slot[b] = slot ? slot[b] : b;
         tab.seq_kv[b] = seq_kv[b];
         // past seq_kv - 1 the mask hides nothing: clamped, so the kernel's row limit cannot overflow
         tab.q_pos0[b] = q_pos0 ? (q_pos0[b] < seq_kv[b] ? q_pos0[b] : seq_kv[b]) : 0;
     }
+    return hipSuccess;
+}
+
+// The re-check of a built table where a kernel's LDS arrays and grid are sized (the launches that take a table: the
+// transformer stack brings its own).  indirect: the table's row stride covers every sequence's entries.
+bool decode_table_ok(const DecodeBatchTable &tab, int n_seqs, int rows_per_seq, int dk, bool indirect,
+                     int64_t row_slab_stride) {
+    if (n_seqs < 1 || n_seqs > kDecodeMaxBatch || rows_per_seq < 1 || dk < 1 ||
+        !attention_decode_any_ok(rows_per_seq, 1, dk))
+        return false;
+    for (int b = 0; b < n_seqs; ++b)
+        if (tab.seq_kv[b] < 1 || !attention_decode_any_ok(rows_per_seq, tab.seq_kv[b], dk) || tab.kv_slot[b] < 0 ||
+            tab.q_pos0[b] < 0 || tab.q_pos0[b] > tab.seq_kv[b] ||
+            (indirect && row_slab_stride < tab.seq_kv[b]))
+            return false;
+    return true;
+}
+
+// kv_slot == nullptr: slab b for sequence b; q_pos0 == nullptr: no mask.  Every check comes before the launch.
+hipError_t launch_attention_batched(const float *Q, int64_t ldq, const float *K, int64_t ldk, int64_t k_stride_seq,
+                                    const float *V, int64_t ldv, int64_t v_stride_seq, float *O, int64_t ldo, int n_seqs,
+                                    int rows_per_seq, const int *kv_slot, const int *seq_kv, const int *q_pos0,
+                                    int n_heads, int dk, float scale, hipStream_t stream) {
+    DecodeBatchTable tab;  // filled by decode_table_from_host, read only after its success
+    if (!Q || !K || !V || !O || n_heads < 1 ||
+        decode_table_from_host(n_seqs, rows_per_seq, dk, kv_slot, seq_kv, q_pos0, false, nullptr, 0, 0, tab))
+        return hipErrorInvalidValue;
     if (n_seqs == 0) return hipSuccess;
     return launch_attention_decode_batched(Q, ldq, K, ldk, k_stride_seq, V, ldv, v_stride_seq, O, ldo, n_seqs,
                                            rows_per_seq, tab, q_pos0 != nullptr, n_heads, dk, scale, stream);
 }
 
-// The same launch through a per-row slab table in device memory (attention_decode.hip, DecodeIndirect).
-// The host arrays are read HERE as above; the table's bytes are read by the kernel.  tab_row == nullptr: table row b
-// for sequence b.  Every check comes before the launch: the batched launch's, and what keeps the kernel's table reads
-// inside the table's rows (a stride that covers seq_kv[b] entries) and its clamp meaningful (1 <= n_slabs <= 64).
+// The same launch through a per-row slab table in device memory (attention_decode.hip, DecodeIndirect):
+// the table's bytes are read by the kernel.  tab_row == nullptr: table row b for sequence b.
 hipError_t launch_attention_indirect(const float *Q, int64_t ldq, const float *K, int64_t ldk, int64_t k_stride_seq,
                                      const float *V, int64_t ldv, int64_t v_stride_seq, float *O, int64_t ldo, int n_seqs,
                                      int rows_per_seq, const uint8_t *row_slab, int64_t row_slab_stride, int n_slabs,
                                      const int *tab_row, const int *seq_kv, const int *q_pos0, int n_heads, int dk,
                                      float scale, hipStream_t stream) {
-    if (!Q || !K || !V || !O || !seq_kv || !row_slab || n_seqs < 0 || n_seqs > kDecodeMaxBatch || n_heads < 1 ||
-        !attention_decode_any_ok(rows_per_seq, 1, dk) || rows_per_seq < 1 || dk < 1 || n_slabs < 1 ||
-        n_slabs > kDecodeMaxBatch)
+    DecodeBatchTable tab;  // filled by decode_table_from_host (kv_slot: the table row), read only after its success
+    if (!Q || !K || !V || !O || n_heads < 1 ||
+        decode_table_from_host(n_seqs, rows_per_seq, dk, tab_row, seq_kv, q_pos0, true, row_slab, row_slab_stride,
+                               n_slabs, tab))
         return hipErrorInvalidValue;
-    DecodeBatchTable tab = {};  // kv_slot: the table row
-    for (int b = 0; b < n_seqs; ++b) {
-        if (seq_kv[b] < 1 || !attention_decode_any_ok(rows_per_seq, seq_kv[b], dk) || (q_pos0 && q_pos0[b] < 0) ||
-            (tab_row && tab_row[b] < 0) || row_slab_stride < seq_kv[b])
-            return hipErrorInvalidValue;
-        tab.kv_slot[b] = tab_row ? tab_row[b] : b;
-        tab.seq_kv[b] = seq_kv[b];
-        tab.q_pos0[b] = q_pos0 ? (q_pos0[b] < seq_kv[b] ? q_pos0[b] : seq_kv[b]) : 0;
-    }
     if (n_seqs == 0) return hipSuccess;
     return launch_attention_decode_indirect(Q, ldq, K, ldk, k_stride_seq, V, ldv, v_stride_seq, O, ldo, n_seqs,
                                             rows_per_seq, row_slab, row_slab_stride, n_slabs, tab, q_pos0 != nullptr,
@@ -271,27 +291,17 @@ hipError_t launch_attention_varlen_gqa(const float *Q, int64_t ldq, const float 
     return hipSuccess;
 }
 
-// launch_attention_batched's and launch_attention_indirect's checks and table (row_slab == nullptr: the batched
-// form), then the grouped decode launch; the host arrays are read HERE, nothing is copied, allocated or synchronized
+// decode_table_from_host's checks and table and the group check, then the grouped decode launch
 static hipError_t batched_gqa(const float *Q, int64_t ldq, const float *K, int64_t ldk, int64_t k_stride_seq,
                               const float *V, int64_t ldv, int64_t v_stride_seq, float *O, int64_t ldo, int n_seqs,
                               int rows_per_seq, bool indirect, const uint8_t *row_slab, int64_t row_slab_stride,
                               int n_slabs, const int *slot, const int *seq_kv, const int *q_pos0, int n_heads,
                               int n_kv_heads, int dk, float scale, hipStream_t stream) {
-    if (!Q || !K || !V || !O || !seq_kv || n_seqs < 0 || n_seqs > kDecodeMaxBatch || rows_per_seq < 1 || dk < 1 ||
-        !attention_decode_gqa_ok(rows_per_seq, 1, dk, n_heads, n_kv_heads) ||
-        (indirect && (!row_slab || n_slabs < 1 || n_slabs > kDecodeMaxBatch)))
+    DecodeBatchTable tab;  // filled by decode_table_from_host, read only after its success
+    if (!Q || !K || !V || !O || !attention_decode_gqa_ok(rows_per_seq, 1, dk, n_heads, n_kv_heads) ||
+        decode_table_from_host(n_seqs, rows_per_seq, dk, slot, seq_kv, q_pos0, indirect, row_slab, row_slab_stride,
+                               n_slabs, tab))
         return hipErrorInvalidValue;
-    DecodeBatchTable tab = {};  // entries past n_seqs are never read; zeroed so the arguments are defined bytes
-    for (int b = 0; b < n_seqs; ++b) {
-        if (seq_kv[b] < 1 || !attention_decode_any_ok(rows_per_seq, seq_kv[b], dk) || (q_pos0 && q_pos0[b] < 0) ||
-            (slot && slot[b] < 0) || (indirect && row_slab_stride < seq_kv[b]))
-            return hipErrorInvalidValue;
-        tab.kv_slot[b] = slot ? slot[b] : b;
-        tab.seq_kv[b] = seq_kv[b];
-        // past seq_kv - 1 the mask hides nothing: clamped, so the kernel's row limit cannot overflow
-        tab.q_pos0[b] = q_pos0 ? (q_pos0[b] < seq_kv[b] ? q_pos0[b] : seq_kv[b]) : 0;
-    }
     if (n_seqs == 0) return hipSuccess;
     if (indirect)
         return launch_attention_decode_indirect_gqa(Q, ldq, K, ldk, k_stride_seq, V, ldv, v_stride_seq, O, ldo, n_seqs,

@@ -417,6 +417,15 @@ hipError_t launch_attention_indirect(const float *Q, int64_t ldq, const float *K
                                      int rows_per_seq, const uint8_t *row_slab, int64_t row_slab_stride, int n_slabs,
                                      const int *tab_row, const int *seq_kv, const int *q_pos0, int n_heads, int dk,
                                      float scale, hipStream_t stream);
+// What the table launches above and their grouped and bf16-cache forms share (attention_launch.hip).
+// decode_table_from_host: the checks listed at launch_attention_batched (indirect: and launch_attention_indirect's), then
+// tab filled and clamped; hipErrorInvalidValue or hipSuccess (n_seqs == 0 included: the caller launches nothing).
+// decode_table_ok: the re-check of a built table by the launches that take one (row_slab_stride counts with indirect).
+hipError_t decode_table_from_host(int n_seqs, int rows_per_seq, int dk, const int *slot, const int *seq_kv,
+                                  const int *q_pos0, bool indirect, const uint8_t *row_slab, int64_t row_slab_stride,
+                                  int n_slabs, DecodeBatchTable &tab);
+bool decode_table_ok(const DecodeBatchTable &tab, int n_seqs, int rows_per_seq, int dk, bool indirect,
+                     int64_t row_slab_stride);
 // the kernel launch_attention takes for a shape (qgemm_attention_plan): a static string
 const char *attention_plan_name(int seq_q, int seq_kv, int dk);
 // whether a call of at most max_q query rows and max_kv keys can reach the three launches, and so needs `scores`

@@ -12,6 +12,7 @@ import torch
 
 import attn_oracle
 import causal_oracle
+from decode_table_cases import check_unmasked_tables
 from oracle import oracle as O
 from util import assert_bits_equal
 
@@ -191,3 +192,22 @@ def test_graph_capture_and_replay(qg, oracle, device):
         for b, (Q, Kb, Vb) in enumerate(seqs):
             assert_bits_equal(got[b * ROWS:(b + 1) * ROWS], _want(Q, Kb, Vb, H, n_kv, seq_kv[b] - ROWS),
                               f"graph replay {i}, sequence {b}")
+
+
+# (rows per sequence, seq_kv, heads, kv heads, d_k, sliced): unmasked, two sequences on one K / V history -- 129 and 300
+# keys (one key past a chunk; three chunks, so both prefetch buffers and both parities of the K chunk count), G = 3 (a
+# block of three heads) and G = 5 (a second block of one head), both widths, vector and element loads
+UNMASKED = ((1, (129, 300), 6, 2, 64, False), (3, (300, 129), 10, 2, 20, True),
+            (3, (129, 300), 6, 2, 96, False), (1, (300, 129), 10, 2, 128, True))
+
+
+@pytest.mark.parametrize("case", UNMASKED, ids=str)
+def test_unmasked_batched_and_indirect(qg, oracle, device, case):
+    """attention_decode_gqa_kernel<false, DecodeMany | DecodeIndirect, 64 | 128> (decode_table_cases.py)"""
+    rows, seq_kv, H, n_kv, dk, sliced = case
+    assert qg.attention_gqa_plan(rows, max(seq_kv), H, n_kv, dk) == _plan(dk)
+    check_unmasked_tables(
+        device, rows, seq_kv, H, n_kv, dk, sliced, torch.float32,
+        lambda Q, K, V, n, slot, out: qg.attention_decode_batched_gqa(Q, K, V, H, n_kv, n, kv_slot=slot, rows_per_seq=rows, O=out),
+        lambda Q, K, V, tab, n, out: qg.attention_decode_indirect(Q, K, V, H, tab, n, rows_per_seq=rows, O=out, n_kv_heads=n_kv),
+        lambda Q, K, V: _want(Q, K, V, H, n_kv, None), 761)

@@ -11,6 +11,7 @@ import torch
 
 import attn_oracle
 import causal_oracle
+from decode_table_cases import check_unmasked_tables
 from oracle import oracle as O
 from util import assert_bits_equal
 
@@ -174,3 +175,22 @@ def test_graph_capture_and_replay(qg, oracle, device):
         for b, (Q, Kb, Vb) in enumerate(seqs):
             assert_bits_equal(got[b * ROWS:(b + 1) * ROWS], _want(Q, Kb, Vb, H, n_kv, seq_kv[b] - ROWS),
                               f"graph replay {i}, sequence {b}")
+
+
+# (rows per sequence, seq_kv, heads, kv heads, d_k, sliced): unmasked, two sequences on one K / V history -- 257 and 600
+# keys (one key past a 256-key chunk; three chunks, so both prefetch buffers and both parities of the K chunk count),
+# G = 3 (a block of three heads), G = 5 (a second block of one head) and G = 1, both widths, 16-byte and element loads
+UNMASKED = ((1, (257, 600), 6, 2, 64, False), (3, (600, 257), 10, 2, 20, True),
+            (3, (257, 600), 6, 2, 96, False), (1, (600, 257), 10, 2, 128, True), (3, (257, 600), 2, 2, 128, False))
+
+
+@pytest.mark.parametrize("case", UNMASKED, ids=str)
+def test_unmasked_batched_and_indirect(qg, oracle, device, case):
+    """attention_decode_kv16_kernel<false, DecodeMany | DecodeIndirect, 64 | 128> (decode_table_cases.py)"""
+    rows, seq_kv, H, n_kv, dk, sliced = case
+    assert qg.attention_decode_kv16_plan(rows, H, n_kv, dk) == _plan(dk)
+    check_unmasked_tables(
+        device, rows, seq_kv, H, n_kv, dk, sliced, torch.bfloat16,
+        lambda Q, K, V, n, slot, out: qg.attention_decode_batched_kv16(Q, K, V, H, n_kv, n, kv_slot=slot, rows_per_seq=rows, O=out),
+        lambda Q, K, V, tab, n, out: qg.attention_decode_indirect_kv16(Q, K, V, H, tab, n, rows_per_seq=rows, O=out, n_kv_heads=n_kv),
+        lambda Q, K, V: _want(Q, K, V, H, n_kv, None), 881)

@@ -10,6 +10,7 @@ import torch
 
 import attn_oracle
 import causal_oracle
+from decode_table_cases import check_unmasked_tables
 from util import assert_bits_equal
 
 pytestmark = pytest.mark.gpu
@@ -124,3 +125,20 @@ def test_indirect_with_mixed_slabs_and_an_entry_that_names_no_slab(qg, oracle, d
     got = _check_sequences(qg, lambda Q, p, out: qg.attention_decode_indirect(Q, Kd, Vd, H, ownd, list(SEQ_KV), q_pos0=p,
                                                                               rows_per_seq=ROWS, O=out), seqs, device, "indirect")
     assert np.isfinite(got[:2 * ROWS]).all() and np.isnan(got[2 * ROWS:]).all()
+
+
+# (rows per sequence, seq_kv, heads, d_k, sliced): unmasked, two sequences on one K / V history -- 129 and 300 keys (one
+# key past a chunk; three chunks, so both prefetch buffers and both parities of the K chunk count), vector and element loads
+UNMASKED = ((1, (129, 300), 2, 128, False), (3, (300, 129), 2, 96, True))
+
+
+@pytest.mark.parametrize("case", UNMASKED, ids=str)
+def test_unmasked_batched_and_indirect(qg, oracle, device, case):
+    """attention_decode_kernel<false, DecodeMany | DecodeIndirect, 128> (decode_table_cases.py)"""
+    rows, seq_kv, heads, dk, sliced = case
+    assert qg.attention_plan(rows, max(seq_kv), heads, dk) == WIDE
+    check_unmasked_tables(
+        device, rows, seq_kv, heads, heads, dk, sliced, torch.float32,
+        lambda Q, K, V, n, slot, out: qg.attention_decode_batched(Q, K, V, heads, n, kv_slot=slot, rows_per_seq=rows, O=out),
+        lambda Q, K, V, tab, n, out: qg.attention_decode_indirect(Q, K, V, heads, tab, n, rows_per_seq=rows, O=out),
+        lambda Q, K, V: _want(Q, K, V, heads, None), 461)
