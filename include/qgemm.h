@@ -1288,6 +1288,62 @@ QGEMM_API int qgemm_kv_append_bf16(const float *K, int64_t k_stride_h, const flo
                          int n_seqs, int rows_per_seq, const int *kv_slot, const int *pos, int width,
                          void *stream);
 
+/* ---- Split-key decode attention: contexts up to 131072 keys, small batches spread over the chip ----
+ * qgemm_attention_decode_split: the arguments and layouts of qgemm_attention_decode_batched_gqa -- Q and O fp32 with
+ * n_heads * d_k columns, K and V fp32 slabs with n_kv_heads * d_k columns, 1 <= G = n_heads / n_kv_heads <= 16 -- with the
+ * keys of every (KV head, block of up to 4 query heads, row, sequence) SPLIT over several workgroups in runs of
+ * L = split_keys keys, and a second launch that merges the runs' partial softmaxes (flash-decoding).  The sequential
+ * calls above stop at 4096 keys and give one sequence 8 workgroups; this one takes seq_kv[b] up to 131072.
+ * Contract: its OWN numerical definition, NOT the sequential calls' bits; nothing promises equality with them.
+ * Query row r of sequence b sees keys 0 .. lim - 1, lim = min(seq_kv[b], q_pos0[b] + r + 1); q_pos0 == NULL: no mask,
+ * lim = seq_kv[b].  A key at or past lim contributes NOTHING: a non-finite value stored there does not reach the output.
+ * (The sequential contract differs: there a masked key enters P V as fmaf(+0, v, acc), so an infinity in a masked V
+ * row gives NaN.)  Split s covers keys [s L, min((s + 1) L, lim)); row r has S = ceil(lim / L) splits.  Per (sequence, row,
+ * query head, split), with score_j the sequential calls' fmaf chain from +0 over k ascending (d_k zero-padded to 32) and
+ * x_j = fl(score_j * scale):
+ *   m_s    = max_j x_j                     ("if (x > m) m = x" from -inf: a NaN never wins)
+ *   l_s    = sum_j e_j, e_j = fl32(exp((double)fl(x_j - m_s)))   (64 partial sums, partial i over the split's keys i, i + 64,
+ *                                          .. ascending, then six pairwise steps: p[i] += p[i ^ 32], ^ 16, .., ^ 1)
+ *   a_s[c] = sum_j e_j * V[key j][c]       (one fmaf chain from +0 over the split's keys ascending)
+ * and the merge: M = max_s m_s, w_s = fl32(exp((double)fl(m_s - M))),
+ *   O[c] = fl(A[c] / D), A[c] = sum_s w_s a_s[c], D = sum_s w_s l_s   (fmaf chains from +0, s ascending)
+ * So: the result is a deterministic function of the arguments and of L alone -- not of the device, the grid or the
+ * batch: a row computed alone and inside a batch of 64 has the same bits.  With S == 1, w_0 = exp(0) = 1 exactly.  A NaN at
+ * a visible key (in Q, K, V, or an infinite score) yields NaN in that head's row.
+ * Envelope: 1 .. 8 rows per sequence, up to 64 sequences, seq_kv[b] in 1 .. 131072, d_k <= 64 or 96 or 128, 1 <= G <= 16,
+ * split_keys a multiple of 128 in 128 .. 1024, or 0 for the library's choice.
+ * split_keys == 0 is resolved by this fixed function of the arguments, with max_seq_kv = the largest seq_kv[b]:
+ *   W    = n_seqs * rows_per_seq * n_kv_heads * ceil(G / 4)        the workgroups of an unsplit launch
+ *   want = ceil(512 / W)                                           splits per row for about two workgroups per CU on 256
+ *   L    = ceil(max_seq_kv / want), rounded up to a multiple of 128, clamped to 128 .. 1024
+ * The 512 rests on NO measurement; the rule is a starting point (scripts/decode_split_probe.py sweeps L beside it).
+ * workspace: at least qgemm_attention_decode_split_workspace_size bytes for the batch's largest seq_kv[b] and the L in
+ * use, = n_seqs * rows_per_seq * n_heads * ceil(max_seq_kv / L) * (d_k + 2) * 4 (per split: m, l and the d_k sums); its
+ * contents are unspecified afterwards.  With split_keys == 0 the size function does not know n_kv_heads and returns the
+ * size for the smallest L the rule gives for any n_kv_heads (W >= n_seqs * rows_per_seq * ceil(n_heads / 4)): enough for
+ * every grouping; qgemm_attention_decode_split_plan gives the exact L.  0 for arguments the call refuses.
+ * The tables travel in the kernel arguments: nothing is allocated, copied to the device or synchronized; the call is
+ * two launches ("attention_decode_split_kernel" at d_k <= 64 or "attention_decode_split_wide_kernel" at d_k 96 / 128,
+ * named by the plan, then "attention_decode_merge_kernel") and can be captured in a graph.  No row of O outside the
+ * n_seqs * rows_per_seq rows is written.
+ * qgemm_attention_decode_split_plan (needs no GPU): *split_keys in: 0 or a value; out: the value used (split_keys NULL:
+ * as 0, nothing returned); *kernel: the first launch's name.
+ * hipErrorInvalidValue before any launch: what qgemm_attention_decode_batched_gqa refuses (with 131072 keys in the place
+ * of 4096, and G == 1 served here), a split_keys outside the list above, a null or too small workspace; n_seqs == 0
+ * returns 0 without a launch. */
+QGEMM_API int qgemm_attention_decode_split(const float *Q, int64_t q_stride_h,
+                                 const float *K, int64_t k_stride_h, int64_t k_stride_seq,
+                                 const float *V, int64_t v_stride_h, int64_t v_stride_seq,
+                                 float *O, int64_t o_stride_h, int n_seqs, int rows_per_seq,
+                                 const int *kv_slot, const int *seq_kv, const int *q_pos0,
+                                 int n_heads, int n_kv_heads, int d_k, float scale, int split_keys,
+                                 void *workspace, size_t ws_bytes, void *stream);
+QGEMM_API size_t qgemm_attention_decode_split_workspace_size(int n_seqs, int rows_per_seq, int max_seq_kv, int n_heads,
+                                                   int d_k, int split_keys);
+QGEMM_API int qgemm_attention_decode_split_plan(int n_seqs, int rows_per_seq, int max_seq_kv, int n_heads, int n_kv_heads,
+                                      int d_k, int *split_keys /* in: 0 or a value; out: the value used */,
+                                      const char **kernel);
+
 #ifdef __cplusplus
 }
 #endif

@@ -165,6 +165,9 @@ EXPORTED_SYMBOLS = (
     "qgemm_attention_decode_indirect_kv16",
     "qgemm_attention_decode_kv16_plan",
     "qgemm_kv_append_bf16",
+    "qgemm_attention_decode_split",
+    "qgemm_attention_decode_split_workspace_size",
+    "qgemm_attention_decode_split_plan",
 )
 
 # Every symbol include/qgemm_dist.h declares (libqgemm_dist.so: M-shards + RCCL all-gather).
@@ -518,6 +521,14 @@ def load() -> ctypes.CDLL:
         L.qgemm_attention_decode_kv16_plan.restype = i32
         L.qgemm_kv_append_bf16.argtypes = [vp, i64, vp, i64, vp, i64, i64, vp, i64, i64, i32, i32, ip, ip, i32, vp]
         L.qgemm_kv_append_bf16.restype = i32
+        L.qgemm_attention_decode_split.argtypes = [vp, i64, vp, i64, i64, vp, i64, i64, vp, i64, i32, i32, ip, ip, ip,
+                                                   i32, i32, i32, f32, i32, vp, sz, vp]
+        L.qgemm_attention_decode_split.restype = i32
+        L.qgemm_attention_decode_split_workspace_size.argtypes = [i32, i32, i32, i32, i32, i32]
+        L.qgemm_attention_decode_split_workspace_size.restype = sz
+        L.qgemm_attention_decode_split_plan.argtypes = [i32, i32, i32, i32, i32, i32, ip,
+                                                        ctypes.POINTER(ctypes.c_char_p)]
+        L.qgemm_attention_decode_split_plan.restype = i32
         _lib = L
         return L
 
@@ -1894,6 +1905,56 @@ def attention_decode_kv16_plan(rows_per_seq: int, n_heads: int, n_kv_heads: int,
     _check("qgemm_attention_decode_kv16_plan",
            load().qgemm_attention_decode_kv16_plan(rows_per_seq, n_heads, n_kv_heads, d_k, ctypes.byref(name)))
     return name.value.decode()
+
+
+def attention_decode_split_plan(n_seqs: int, rows_per_seq: int, max_seq_kv: int, n_heads: int, n_kv_heads, d_k: int,
+                                split_keys=None):
+    """(keys per split, kernel) of an attention_decode_split call (qgemm_attention_decode_split_plan; needs no GPU):
+    split_keys None or 0 asks for the library's rule (include/qgemm.h), any other value is checked and returned; the
+    kernel is "attention_decode_split_kernel" (d_k <= 64) or "attention_decode_split_wide_kernel" (d_k 96 or 128).
+    Raises QGemmError outside the envelope."""
+    split, name = ctypes.c_int(int(split_keys or 0)), ctypes.c_char_p()
+    _check("qgemm_attention_decode_split_plan",
+           load().qgemm_attention_decode_split_plan(n_seqs, rows_per_seq, max_seq_kv, n_heads,
+                                                    _kv_heads(n_heads, n_kv_heads), d_k, ctypes.byref(split),
+                                                    ctypes.byref(name)))
+    return split.value, name.value.decode()
+
+
+def attention_decode_split_workspace_size(n_seqs: int, rows_per_seq: int, max_seq_kv: int, n_heads: int, d_k: int,
+                                          split_keys=None) -> int:
+    """The bytes attention_decode_split needs for sequences of up to max_seq_kv keys
+    (qgemm_attention_decode_split_workspace_size): n_seqs * rows_per_seq * n_heads * ceil(max_seq_kv / split_keys) *
+    (d_k + 2) * 4.  split_keys None or 0: enough for the library's choice under any n_kv_heads.  0 outside the envelope."""
+    return int(load().qgemm_attention_decode_split_workspace_size(n_seqs, rows_per_seq, max_seq_kv, n_heads, d_k,
+                                                                  int(split_keys or 0)))
+
+
+def attention_decode_split(Q, K, V, n_heads: int, n_kv_heads, slots, seq_kv, q_pos0=None, rows_per_seq: int = 1,
+                           split_keys=None, workspace=None, out=None):
+    """Decode attention with the keys of every row split over several workgroups and merged (qgemm_attention_decode_split,
+    DESIGN.md s34): attention_decode_batched_gqa's arguments (slots: its kv_slot, None for slab b) for sequences of up to
+    131072 keys, two launches.  Its own numerics: softmax attention over the visible keys in fp32, a deterministic
+    function of the arguments and of split_keys (a multiple of 128 in 128 .. 1024; None: the library's rule), not the
+    sequential calls' bits; a key the mask hides contributes nothing.  workspace: a device tensor of at least
+    attention_decode_split_workspace_size bytes, allocated here when None."""
+    import torch
+    head, n_kv, tail, O = _decode_table_call(Q, K, V, torch.float32, n_heads, n_kv_heads, None, seq_kv, q_pos0, slots,
+                                             rows_per_seq, None, out)
+    n_seqs = Q.shape[0] // rows_per_seq
+    split = int(split_keys or 0)
+    if workspace is None:
+        longest = max([int(v) for v in seq_kv], default=1)
+        if not split and n_seqs:
+            split, _ = attention_decode_split_plan(n_seqs, rows_per_seq, longest, n_heads, n_kv, tail[0])
+        need = attention_decode_split_workspace_size(n_seqs, rows_per_seq, longest, n_heads, tail[0], split)
+        workspace = torch.empty(max(need, 4), dtype=torch.uint8, device=Q.device)
+    assert isinstance(workspace, torch.Tensor) and workspace.is_cuda and workspace.is_contiguous(), \
+        "workspace: a contiguous device tensor"
+    ws_bytes = workspace.numel() * workspace.element_size()
+    _check("qgemm_attention_decode_split",
+           load().qgemm_attention_decode_split(*head, n_kv, *tail[:2], split, workspace.data_ptr(), ws_bytes, tail[2]))
+    return O
 
 
 def kv_append_bf16(K, V, Kc, Vc, pos, kv_slot=None, rows_per_seq: int = 1):

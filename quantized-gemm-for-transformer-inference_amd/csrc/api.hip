@@ -1035,6 +1035,43 @@ int qgemm_kv_append_bf16(const float *K, int64_t k_stride_h, const float *V, int
                                      kv_slot, pos, width, static_cast<hipStream_t>(stream)));
 }
 
+// ---- split-key decode attention ----
+
+int qgemm_attention_decode_split(const float *Q, int64_t q_stride_h, const float *K, int64_t k_stride_h,
+                                 int64_t k_stride_seq, const float *V, int64_t v_stride_h, int64_t v_stride_seq,
+                                 float *O, int64_t o_stride_h, int n_seqs, int rows_per_seq, const int *kv_slot,
+                                 const int *seq_kv, const int *q_pos0, int n_heads, int n_kv_heads, int d_k, float scale,
+                                 int split_keys, void *workspace, size_t ws_bytes, void *stream) {
+    return err(launch_attention_split(Q, q_stride_h, K, k_stride_h, k_stride_seq, V, v_stride_h, v_stride_seq, O,
+                                      o_stride_h, n_seqs, rows_per_seq, kv_slot, seq_kv, q_pos0, n_heads, n_kv_heads, d_k,
+                                      scale, split_keys, workspace, ws_bytes, static_cast<hipStream_t>(stream)));
+}
+
+// split_keys == 0: n_kv_heads is no argument here, so the size at the smallest value the rule gives for any n_kv_heads --
+// the rule's L never falls when W grows, and W >= n_seqs * rows * ceil(n_heads / 4)
+size_t qgemm_attention_decode_split_workspace_size(int n_seqs, int rows_per_seq, int max_seq_kv, int n_heads, int d_k,
+                                                   int split_keys) {
+    if (!attention_split_ok(n_seqs, rows_per_seq, max_seq_kv, d_k, n_heads, n_heads) ||
+        (split_keys != 0 && !split_keys_ok(split_keys)))
+        return 0;
+    const int quads = (n_heads + 3) / 4;
+    const int split =
+        split_keys ? split_keys : attention_split_default_keys(n_seqs, rows_per_seq, max_seq_kv, 4 * quads, quads);
+    return attention_split_workspace_bytes(n_seqs, rows_per_seq, max_seq_kv, n_heads, d_k, split);
+}
+
+int qgemm_attention_decode_split_plan(int n_seqs, int rows_per_seq, int max_seq_kv, int n_heads, int n_kv_heads, int d_k,
+                                      int *split_keys, const char **kernel) {
+    const int asked = split_keys ? *split_keys : 0;
+    if (!attention_split_ok(n_seqs, rows_per_seq, max_seq_kv, d_k, n_heads, n_kv_heads) ||
+        (asked != 0 && !split_keys_ok(asked)))
+        return (int)hipErrorInvalidValue;
+    if (split_keys && !asked)
+        *split_keys = attention_split_default_keys(n_seqs, rows_per_seq, max_seq_kv, n_heads, n_kv_heads);
+    if (kernel) *kernel = attention_split_plan_name(d_k);
+    return 0;
+}
+
 #ifndef QGEMM_SRC_HASH
 #define QGEMM_SRC_HASH "unknown"
 #endif

@@ -112,17 +112,19 @@ hipError_t launch_attention_varlen(const float *Q, int64_t ldq, const float *K, 
 // synchronized, and a captured graph replays the values of the capture.  slot == nullptr: slab (indirect: table row) b
 // for sequence b; q_pos0 == nullptr: no mask.  indirect: also what keeps the kernel's table reads inside the table's
 // rows (a stride that covers seq_kv[b] entries) and its clamp meaningful (1 <= n_slabs <= 64).
-hipError_t decode_table_from_host(int n_seqs, int rows_per_seq, int dk, const int *slot, const int *seq_kv,
-                                  const int *q_pos0, bool indirect, const uint8_t *row_slab, int64_t row_slab_stride,
-                                  int n_slabs, DecodeBatchTable &tab) {
+// max_kv: the launch's key limit -- 4096 for the sequential kernels (decode_table_from_host: the score row of
+// attention_decode_any_ok), kSplitMaxSeq for the split-key launch.
+hipError_t decode_table_from_host_max(int n_seqs, int rows_per_seq, int dk, const int *slot, const int *seq_kv,
+                                      const int *q_pos0, bool indirect, const uint8_t *row_slab, int64_t row_slab_stride,
+                                      int n_slabs, int max_kv, DecodeBatchTable &tab) {
     if (!seq_kv || n_seqs < 0 || n_seqs > kDecodeMaxBatch || rows_per_seq < 1 || dk < 1 ||
         !attention_decode_any_ok(rows_per_seq, 1, dk) ||
         (indirect && (!row_slab || n_slabs < 1 || n_slabs > kDecodeMaxBatch)))
         return hipErrorInvalidValue;
     tab = {};  // entries past n_seqs are never read; zeroed so the arguments are defined bytes
     for (int b = 0; b < n_seqs; ++b) {
-        if (seq_kv[b] < 1 || !attention_decode_any_ok(rows_per_seq, seq_kv[b], dk) || (q_pos0 && q_pos0[b] < 0) ||
-            (slot && slot[b] < 0) || (indirect && row_slab_stride < seq_kv[b]))
+        if (seq_kv[b] < 1 || seq_kv[b] > max_kv || (q_pos0 && q_pos0[b] < 0) || (slot && slot[b] < 0) ||
+            (indirect && row_slab_stride < seq_kv[b]))
             return hipErrorInvalidValue;
         tab.kv_slot[b] = slot ? slot[b] : b;
         tab.seq_kv[b] = seq_kv[b];
@@ -130,6 +132,14 @@ hipError_t decode_table_from_host(int n_seqs, int rows_per_seq, int dk, const in
         tab.q_pos0[b] = q_pos0 ? (q_pos0[b] < seq_kv[b] ? q_pos0[b] : seq_kv[b]) : 0;
     }
     return hipSuccess;
+}
+
+// the six sequential table launches: 4096 keys
+hipError_t decode_table_from_host(int n_seqs, int rows_per_seq, int dk, const int *slot, const int *seq_kv,
+                                  const int *q_pos0, bool indirect, const uint8_t *row_slab, int64_t row_slab_stride,
+                                  int n_slabs, DecodeBatchTable &tab) {
+    return decode_table_from_host_max(n_seqs, rows_per_seq, dk, slot, seq_kv, q_pos0, indirect, row_slab,
+                                      row_slab_stride, n_slabs, 4096, tab);
 }
 
 // The re-check of a built table where a kernel's LDS arrays and grid are sized (the launches that take a table: the
@@ -335,6 +345,52 @@ hipError_t launch_attention_indirect_gqa(const float *Q, int64_t ldq, const floa
                                          n_heads, dk, scale, stream);
     return batched_gqa(Q, ldq, K, ldk, k_stride_seq, V, ldv, v_stride_seq, O, ldo, n_seqs, rows_per_seq, true, row_slab,
                        row_slab_stride, n_slabs, tab_row, seq_kv, q_pos0, n_heads, n_kv_heads, dk, scale, stream);
+}
+
+// ---- split-key decode attention ----
+
+const char *attention_split_plan_name(int dk) {
+    return dk <= 64 ? "attention_decode_split_kernel" : "attention_decode_split_wide_kernel";
+}
+
+// The rule of include/qgemm.h, in integers.  W: the workgroups of an unsplit launch; want: the splits per row that bring
+// the launch to 512 workgroups, two per CU on 256 CUs -- a round figure that rests on no measurement.
+int attention_split_default_keys(int n_seqs, int rows_per_seq, int max_seq_kv, int n_heads, int n_kv_heads) {
+    const int group = n_heads / n_kv_heads;
+    const int64_t w = (int64_t)n_seqs * rows_per_seq * n_kv_heads * ((group + 3) / 4);
+    const int64_t want = (512 + w - 1) / w;
+    const int64_t keys = (max_seq_kv + want - 1) / want;
+    const int64_t split = (keys + kSplitStep - 1) / kSplitStep * kSplitStep;
+    return (int)(split < kSplitStep ? kSplitStep : split > kSplitMaxKeys ? kSplitMaxKeys : split);
+}
+
+size_t attention_split_workspace_bytes(int n_seqs, int rows_per_seq, int max_seq_kv, int n_heads, int dk, int split) {
+    return (size_t)n_seqs * rows_per_seq * n_heads * ((max_seq_kv + split - 1) / split) * (dk + 2) * sizeof(float);
+}
+
+// decode_table_from_host's checks and table with kSplitMaxSeq keys, the group check from G = 1, the split and the
+// workspace it needs for the batch's longest sequence; then the two launches
+hipError_t launch_attention_split(const float *Q, int64_t ldq, const float *K, int64_t ldk, int64_t k_stride_seq,
+                                  const float *V, int64_t ldv, int64_t v_stride_seq, float *O, int64_t ldo, int n_seqs,
+                                  int rows_per_seq, const int *kv_slot, const int *seq_kv, const int *q_pos0, int n_heads,
+                                  int n_kv_heads, int dk, float scale, int split_keys, void *workspace, size_t ws_bytes,
+                                  hipStream_t stream) {
+    DecodeBatchTable tab;  // filled by decode_table_from_host_max, read only after its success
+    if (!Q || !K || !V || !O || !attention_split_ok(1, rows_per_seq, 1, dk, n_heads, n_kv_heads) ||
+        (split_keys != 0 && !split_keys_ok(split_keys)) ||
+        decode_table_from_host_max(n_seqs, rows_per_seq, dk, kv_slot, seq_kv, q_pos0, false, nullptr, 0, 0, kSplitMaxSeq,
+                                   tab))
+        return hipErrorInvalidValue;
+    if (n_seqs == 0) return hipSuccess;
+    int max_kv = 1;
+    for (int b = 0; b < n_seqs; ++b) max_kv = seq_kv[b] > max_kv ? seq_kv[b] : max_kv;
+    const int split =
+        split_keys ? split_keys : attention_split_default_keys(n_seqs, rows_per_seq, max_kv, n_heads, n_kv_heads);
+    if (!workspace || ws_bytes < attention_split_workspace_bytes(n_seqs, rows_per_seq, max_kv, n_heads, dk, split))
+        return hipErrorInvalidValue;
+    return launch_attention_decode_split(Q, ldq, K, ldk, k_stride_seq, V, ldv, v_stride_seq, O, ldo, n_seqs,
+                                         rows_per_seq, tab, q_pos0 != nullptr, n_heads, n_kv_heads, dk, scale, split,
+                                         static_cast<float *>(workspace), ws_bytes, stream);
 }
 
 }  // namespace qgemm

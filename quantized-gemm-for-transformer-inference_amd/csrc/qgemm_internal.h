@@ -426,6 +426,40 @@ hipError_t decode_table_from_host(int n_seqs, int rows_per_seq, int dk, const in
                                   int n_slabs, DecodeBatchTable &tab);
 bool decode_table_ok(const DecodeBatchTable &tab, int n_seqs, int rows_per_seq, int dk, bool indirect,
                      int64_t row_slab_stride);
+// decode_table_from_host with the key limit as a parameter: every seq_kv[b] in 1 .. max_kv.  decode_table_from_host is
+// this with max_kv = 4096, the sequential kernels' score row; the split-key launch passes kSplitMaxSeq.
+hipError_t decode_table_from_host_max(int n_seqs, int rows_per_seq, int dk, const int *slot, const int *seq_kv,
+                                      const int *q_pos0, bool indirect, const uint8_t *row_slab, int64_t row_slab_stride,
+                                      int n_slabs, int max_kv, DecodeBatchTable &tab);
+// Split-key decode attention (attention_decode_split.hip): the keys of one (KV head, block of <= 4 query
+// heads, row, sequence) split over several workgroups in runs of `split` keys, the partial softmaxes merged by a second
+// kernel -- a numerical contract of its own (include/qgemm.h), up to kSplitMaxSeq keys.
+constexpr int kSplitMaxSeq = 131072;  // keys per sequence
+constexpr int kSplitStep = 128;       // split_keys: a multiple of this ..
+constexpr int kSplitMaxKeys = 1024;   // .. up to this: the score rows a workgroup holds in LDS
+inline bool split_keys_ok(int split) { return split >= kSplitStep && split <= kSplitMaxKeys && split % kSplitStep == 0; }
+// either decode envelope's rows and d_k, whole groups of 1 .. 16 heads, 1 .. 64 sequences, 1 .. kSplitMaxSeq keys
+bool attention_split_ok(int n_seqs, int rows_per_seq, int max_seq_kv, int dk, int n_heads, int n_kv_heads);
+// the library's choice of split_keys, a fixed function of its arguments (written out in include/qgemm.h); the caller
+// has tested attention_split_ok
+int attention_split_default_keys(int n_seqs, int rows_per_seq, int max_seq_kv, int n_heads, int n_kv_heads);
+// n_seqs * rows * n_heads * ceil(max_seq_kv / split) records of d_k + 2 floats
+size_t attention_split_workspace_bytes(int n_seqs, int rows_per_seq, int max_seq_kv, int n_heads, int dk, int split);
+const char *attention_split_plan_name(int dk);
+// tab already checked and clamped (decode_table_from_host_max with kSplitMaxSeq), split a valid split_keys; the launch
+// tests again what sizes its grid, LDS rows and workspace records: two launches, nothing else
+hipError_t launch_attention_decode_split(const float *Q, int64_t ldq, const float *K, int64_t ldk, int64_t k_stride_seq,
+                                         const float *V, int64_t ldv, int64_t v_stride_seq, float *O, int64_t ldo,
+                                         int n_seqs, int rows_per_seq, const DecodeBatchTable &tab, bool causal,
+                                         int n_heads, int n_kv_heads, int dk, float scale, int split, float *workspace,
+                                         size_t ws_bytes, hipStream_t stream);
+// from host arrays (attention_launch.hip): launch_attention_batched_gqa's checks with kSplitMaxSeq keys, split_keys 0 or
+// valid, a workspace of attention_split_workspace_bytes for the batch's longest sequence; n_seqs == 0 launches nothing
+hipError_t launch_attention_split(const float *Q, int64_t ldq, const float *K, int64_t ldk, int64_t k_stride_seq,
+                                  const float *V, int64_t ldv, int64_t v_stride_seq, float *O, int64_t ldo, int n_seqs,
+                                  int rows_per_seq, const int *kv_slot, const int *seq_kv, const int *q_pos0, int n_heads,
+                                  int n_kv_heads, int dk, float scale, int split_keys, void *workspace, size_t ws_bytes,
+                                  hipStream_t stream);
 // the kernel launch_attention takes for a shape (qgemm_attention_plan): a static string
 const char *attention_plan_name(int seq_q, int seq_kv, int dk);
 // whether a call of at most max_q query rows and max_kv keys can reach the three launches, and so needs `scores`
