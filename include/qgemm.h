@@ -1344,6 +1344,49 @@ QGEMM_API int qgemm_attention_decode_split_plan(int n_seqs, int rows_per_seq, in
                                       int d_k, int *split_keys /* in: 0 or a value; out: the value used */,
                                       const char **kernel);
 
+/* ---- Prefill attention tiled over the keys: any key count up to 131072, no score tensor -----------
+ * qgemm_attention_varlen_tiled: qgemm_attention_varlen_gqa's arguments and layouts without the workspace -- Q and O fp32
+ * with n_heads * d_k columns, K and V with n_kv_heads * d_k, query head h on K / V head h / G, G = n_heads / n_kv_heads;
+ * the five host arrays, the row offsets and the mask as there.  The keys of a sequence are walked in chunks of 64 with a
+ * running maximum and sum ("flash" attention): the scores never leave the registers of the workgroup that made them.
+ * No existing call is routed here.
+ * Contract: its OWN numerical definition, NOT the fused or three-launch bits.
+ * Visibility.  Row i of sequence b sees keys 0 .. lim - 1, lim = min(seq_kv[b], q_pos0[b] + i + 1) >= 1; q_pos0 == NULL:
+ * lim = seq_kv[b].  A workgroup owns (sequence, query head, 64 consecutive rows) and reads key chunk c (keys 64 c ..
+ * 64 c + 63) only if it starts below the largest lim of its rows.
+ * Hidden keys.  A key at or past the SEQUENCE's largest lim contributes nothing, whatever is stored there (NaN, inf, rows
+ * past seq_kv): it is replaced by zeros before any arithmetic and its score by -inf.  A key hidden from a row but
+ * visible to a later row of the same 64 enters that row with weight exactly +0 (its score is SELECTED to -inf, and
+ * exp2(-inf) = +0) and leaves the row's result unchanged when V is finite there.  A chunk in which a row sees nothing
+ * leaves that row's m and l bit for bit as they were (alpha = exp2(0) = 1, every p = +0).  Chunk 0 holds key 0, which
+ * every row sees, so m is finite from the first chunk on.
+ * Per row and chunk, with s_j the fp32 MFMA dot product of the row and key j over d_k (v_mfma_f32_16x16x4_f32, four
+ * columns a step, zero-padded to a multiple of 32 columns) and x_j = fl(s_j * fl(scale * log2 e)):
+ *   m' = max(m, max_j x_j)    alpha = exp2(m - m')    p_j = exp2(x_j - m')
+ *   l  = fl(fl(l * alpha) + sum_j p_j)    acc[c] = fl(acc[c] * alpha) + sum_j p_j V[j][c]   (MFMA, fp32 operands)
+ * from m = -inf, l = 0, acc = 0; after the last chunk O[c] = fl(acc[c] / l).  exp2 is the hardware's v_exp_f32 (1 ulp;
+ * results below 2^-126 flush to +0) -- NOT the double-precision exp of the other softmax paths, which dominates the
+ * kernels that use it and buys nothing under a tolerance.  The sums run in a fixed order that depends
+ * on d_k and on the key's place in its chunk alone.
+ * Numerics: fp32 softmax attention; tests/test_gpu_attention_tiled.py holds it within 8 x the error of the same formula
+ * in numpy fp32 against float64.
+ * Determinism: a sequence's rows are a function of its own arguments only -- alone and as one of 64 in a batch it gives
+ * the same bits; the grid and the device do not enter.
+ * Envelope: 0 <= n_seqs <= 64 (0 launches nothing), seq_q[b] >= 0, 1 <= seq_kv[b] <= 131072, d_k <= 64 ("attention_tiled_
+ * kernel") or d_k 96 / 128 ("attention_tiled_wide_kernel": the names qgemm_attention_varlen_tiled_plan returns, without a
+ * GPU), n_kv_heads divides n_heads (any G, G = 1 included), sum_b ceil(seq_q[b] / 64) * n_heads <= INT32_MAX.
+ * ONE launch; nothing is allocated, copied to the device or synchronized; no workspace; capturable in a graph.  No row
+ * of O outside the sequences' rows is written.  O must not overlap Q, K or V.
+ * hipErrorInvalidValue before the launch: a null pointer or array (q_pos0 aside), a negative row offset or q_pos0[b],
+ * and everything outside the envelope. */
+QGEMM_API int qgemm_attention_varlen_tiled(const float *Q, int64_t q_stride_h, const float *K, int64_t k_stride_h,
+                                 const float *V, int64_t v_stride_h, float *O, int64_t o_stride_h, int n_seqs,
+                                 const int64_t *q_row0, const int *seq_q, const int64_t *kv_row0, const int *seq_kv,
+                                 const int *q_pos0 /* NULL: no mask */, int n_heads, int n_kv_heads, int d_k,
+                                 float scale, void *stream);
+QGEMM_API int qgemm_attention_varlen_tiled_plan(int n_seqs, const int *seq_q, const int *seq_kv, int n_heads,
+                                      int n_kv_heads, int d_k, const char **kernel);
+
 #ifdef __cplusplus
 }
 #endif

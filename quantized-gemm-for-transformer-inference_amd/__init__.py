@@ -168,6 +168,8 @@ EXPORTED_SYMBOLS = (
     "qgemm_attention_decode_split",
     "qgemm_attention_decode_split_workspace_size",
     "qgemm_attention_decode_split_plan",
+    "qgemm_attention_varlen_tiled",
+    "qgemm_attention_varlen_tiled_plan",
 )
 
 # Every symbol include/qgemm_dist.h declares (libqgemm_dist.so: M-shards + RCCL all-gather).
@@ -513,6 +515,11 @@ def load() -> ctypes.CDLL:
         L.qgemm_attention_varlen_gqa.restype = i32
         L.qgemm_attention_varlen_gqa_plan.argtypes = [i32, ip, ip, i32, i32, i32, ctypes.POINTER(ctypes.c_char_p)]
         L.qgemm_attention_varlen_gqa_plan.restype = i32
+        L.qgemm_attention_varlen_tiled.argtypes = [vp, i64, vp, i64, vp, i64, vp, i64, i32, lp, ip, lp, ip, ip, i32, i32,
+                                                   i32, f32, vp]
+        L.qgemm_attention_varlen_tiled.restype = i32
+        L.qgemm_attention_varlen_tiled_plan.argtypes = [i32, ip, ip, i32, i32, i32, ctypes.POINTER(ctypes.c_char_p)]
+        L.qgemm_attention_varlen_tiled_plan.restype = i32
         L.qgemm_attention_decode_batched_kv16.argtypes = L.qgemm_attention_decode_batched_gqa.argtypes
         L.qgemm_attention_decode_batched_kv16.restype = i32
         L.qgemm_attention_decode_indirect_kv16.argtypes = L.qgemm_attention_decode_indirect_gqa.argtypes
@@ -2140,6 +2147,62 @@ def attention_varlen_gqa_plan(seq_q, seq_kv, n_heads: int, n_kv_heads: int, d_k:
     _check("qgemm_attention_varlen_gqa_plan",
            load().qgemm_attention_varlen_gqa_plan(n, _int_array(seq_q, n, "seq_q"), _int_array(seq_kv, n, "seq_kv"),
                                                   n_heads, n_kv_heads, d_k, ctypes.byref(name)))
+    return name.value.decode()
+
+
+def attention_varlen_tiled(Q, K, V, n_heads: int, n_kv_heads, seq_q, seq_kv, q_row0=None, kv_row0=None, q_pos0=None,
+                           scale=None, O=None):
+    """Prefill attention tiled over the keys with a running maximum and sum (qgemm_attention_varlen_tiled, DESIGN.md
+    s35): attention_varlen_gqa's arguments and layouts -- n_kv_heads None or n_heads: multi-head -- with up to 131072
+    keys per sequence, in ONE launch for any mix of lengths, without a score tensor or a workspace.  d_k <= 64, 96 or
+    128.  Its numerical contract is its own (include/qgemm.h): fp32 softmax attention, not attention_varlen_gqa's bits;
+    a sequence's rows do not depend on the rest of the batch.  No other row of O is written (a fresh O is zero-filled)."""
+    import math
+    import torch
+    for t, nm in ((Q, "Q"), (K, "K"), (V, "V")):
+        _require_device_f32(t, nm)
+        assert t.dim() == 2 and (t.stride(1) == 1 or t.shape[1] == 1), f"{nm} must be 2-D with unit inner stride"
+    d = Q.shape[1]
+    assert n_heads >= 1 and d % n_heads == 0, "d % n_heads == 0"
+    dk = d // n_heads
+    n_kv = _kv_heads(n_heads, n_kv_heads)
+    assert K.shape[1] == n_kv * dk and V.shape[1] == n_kv * dk, "K and V: n_kv_heads * d_k columns"
+    seq_q, seq_kv = [int(v) for v in seq_q], [int(v) for v in seq_kv]
+    n = len(seq_q)
+    assert len(seq_kv) == n, "seq_q and seq_kv: one entry per sequence"
+    q_row0 = _prefix_sums(seq_q) if q_row0 is None else [int(v) for v in q_row0]
+    kv_row0 = _prefix_sums(seq_kv) if kv_row0 is None else [int(v) for v in kv_row0]
+    assert len(q_row0) == n and len(kv_row0) == n, "q_row0 and kv_row0: one entry per sequence"
+    if O is None:
+        O = torch.zeros((Q.shape[0], d), dtype=torch.float32, device=Q.device)
+    _require_device_f32(O, "O")
+    assert O.dim() == 2 and O.shape[1] == d and (O.stride(1) == 1 or d == 1), "O: d columns, unit inner stride"
+    for b in range(n):  # the rows the call reads and writes exist
+        if q_row0[b] >= 0 and seq_q[b] >= 0:
+            assert q_row0[b] + seq_q[b] <= min(Q.shape[0], O.shape[0]), f"sequence {b}'s query rows exceed Q / O"
+        if kv_row0[b] >= 0 and seq_kv[b] >= 0:
+            assert kv_row0[b] + seq_kv[b] <= min(K.shape[0], V.shape[0]), f"sequence {b}'s keys exceed K / V"
+    if scale is None:
+        scale = ctypes.c_float(1.0 / math.sqrt(float(dk))).value
+    _check("qgemm_attention_varlen_tiled",
+           load().qgemm_attention_varlen_tiled(Q.data_ptr(), Q.stride(0), K.data_ptr(), K.stride(0), V.data_ptr(),
+                                               V.stride(0), O.data_ptr(), O.stride(0), n,
+                                               _int64_array(q_row0, n, "q_row0"), _int_array(seq_q, n, "seq_q"),
+                                               _int64_array(kv_row0, n, "kv_row0"), _int_array(seq_kv, n, "seq_kv"),
+                                               _int_array(q_pos0, n, "q_pos0"), n_heads, n_kv, dk, float(scale),
+                                               _stream(Q.device)))
+    return O
+
+
+def attention_varlen_tiled_plan(seq_q, seq_kv, n_heads: int, n_kv_heads: int, d_k: int) -> str:
+    """The kernel attention_varlen_tiled() launches (qgemm_attention_varlen_tiled_plan): "attention_tiled_kernel" at
+    d_k <= 64, "attention_tiled_wide_kernel" at d_k 96 / 128.  Needs no GPU; raises QGemmError outside the envelope."""
+    seq_q, seq_kv = [int(v) for v in seq_q], [int(v) for v in seq_kv]
+    n = len(seq_q)
+    name = ctypes.c_char_p()
+    _check("qgemm_attention_varlen_tiled_plan",
+           load().qgemm_attention_varlen_tiled_plan(n, _int_array(seq_q, n, "seq_q"), _int_array(seq_kv, n, "seq_kv"),
+                                                    n_heads, n_kv_heads, d_k, ctypes.byref(name)))
     return name.value.decode()
 
 

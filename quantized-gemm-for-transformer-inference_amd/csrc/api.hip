@@ -658,6 +658,37 @@ int qgemm_attention_varlen_gqa_plan(int n_seqs, const int *seq_q, const int *seq
     return 0;
 }
 
+// ---- prefill tiled over the keys ----
+
+// what qgemm_attention_varlen_tiled refuses of the arguments its plan also takes
+static bool varlen_tiled_dims_ok(int n_seqs, const int *seq_q, const int *seq_kv, int n_heads, int n_kv_heads, int d_k) {
+    if (n_seqs < 0 || n_seqs > QGEMM_VARLEN_MAX_SEQS || !seq_q || !seq_kv || n_heads < 1 || n_kv_heads < 1 ||
+        n_heads % n_kv_heads || !attention_tiled_ok(1, d_k))
+        return false;
+    for (int b = 0; b < n_seqs; ++b)
+        if (seq_q[b] < 0 || !attention_tiled_ok(seq_kv[b], d_k)) return false;
+    return true;
+}
+
+int qgemm_attention_varlen_tiled(const float *Q, int64_t q_stride_h, const float *K, int64_t k_stride_h, const float *V,
+                                 int64_t v_stride_h, float *O, int64_t o_stride_h, int n_seqs, const int64_t *q_row0,
+                                 const int *seq_q, const int64_t *kv_row0, const int *seq_kv, const int *q_pos0,
+                                 int n_heads, int n_kv_heads, int d_k, float scale, void *stream) {
+    if (!Q || !K || !V || !O || !q_row0 || !kv_row0 ||
+        !varlen_tiled_dims_ok(n_seqs, seq_q, seq_kv, n_heads, n_kv_heads, d_k))
+        return err(hipErrorInvalidValue);
+    return err(launch_attention_tiled(Q, q_stride_h, K, k_stride_h, V, v_stride_h, O, o_stride_h, n_seqs, q_row0, seq_q,
+                                      kv_row0, seq_kv, q_pos0, n_heads, n_kv_heads, d_k, scale,
+                                      static_cast<hipStream_t>(stream)));
+}
+
+int qgemm_attention_varlen_tiled_plan(int n_seqs, const int *seq_q, const int *seq_kv, int n_heads, int n_kv_heads,
+                                      int d_k, const char **kernel) {
+    if (!varlen_tiled_dims_ok(n_seqs, seq_q, seq_kv, n_heads, n_kv_heads, d_k)) return err(hipErrorInvalidValue);
+    if (kernel) *kernel = attention_tiled_plan_name(d_k);
+    return 0;
+}
+
 int qgemm_attention_decode_batched_gqa(const float *Q, int64_t q_stride_h, const float *K, int64_t k_stride_h,
                                        int64_t k_stride_seq, const float *V, int64_t v_stride_h, int64_t v_stride_seq,
                                        float *O, int64_t o_stride_h, int n_seqs, int rows_per_seq, const int *kv_slot,

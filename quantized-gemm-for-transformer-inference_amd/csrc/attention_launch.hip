@@ -301,6 +301,34 @@ hipError_t launch_attention_varlen_gqa(const float *Q, int64_t ldq, const float 
     return hipSuccess;
 }
 
+// ---- prefill tiled over the keys, online softmax ----
+
+// launch_attention_varlen_gqa's checks with kSplitMaxSeq keys in the place of 4096 (G = 1 is served here too: nothing is
+// rerouted), its table and clamp; then the one launch, which tests the envelope (d_k, the work map) again
+hipError_t launch_attention_tiled(const float *Q, int64_t ldq, const float *K, int64_t ldk, const float *V, int64_t ldv,
+                                  float *O, int64_t ldo, int n_seqs, const int64_t *q_row0, const int *seq_q,
+                                  const int64_t *kv_row0, const int *seq_kv, const int *q_pos0, int n_heads,
+                                  int n_kv_heads, int dk, float scale, hipStream_t stream) {
+    if (n_heads < 1 || n_kv_heads < 1 || n_heads % n_kv_heads || !Q || !K || !V || !O || !q_row0 || !seq_q || !kv_row0 ||
+        !seq_kv || n_seqs < 0 || n_seqs > kVarlenMaxSeqs || !attention_tiled_ok(1, dk))
+        return hipErrorInvalidValue;
+    FusedSeqTable tab = {};  // entries past n_seqs are never read; zeroed so the arguments are defined bytes
+    for (int b = 0; b < n_seqs; ++b) {
+        if (q_row0[b] < 0 || kv_row0[b] < 0 || seq_q[b] < 0 || !attention_tiled_ok(seq_kv[b], dk) ||
+            (q_pos0 && q_pos0[b] < 0))
+            return hipErrorInvalidValue;
+        tab.q_row0[b] = q_row0[b];
+        tab.kv_row0[b] = kv_row0[b];
+        tab.seq_q[b] = seq_q[b];
+        tab.seq_kv[b] = seq_kv[b];
+        // past seq_kv - 1 the mask hides nothing: clamped, so the kernel's row limits cannot overflow
+        tab.q_pos0[b] = q_pos0 ? (q_pos0[b] < seq_kv[b] ? q_pos0[b] : seq_kv[b]) : 0;
+    }
+    if (n_seqs == 0) return hipSuccess;
+    return launch_attention_tiled_many(Q, ldq, K, ldk, V, ldv, O, ldo, n_seqs, tab, q_pos0 != nullptr, n_heads,
+                                       n_kv_heads, dk, scale, stream);
+}
+
 // decode_table_from_host's checks and table and the group check, then the grouped decode launch
 static hipError_t batched_gqa(const float *Q, int64_t ldq, const float *K, int64_t ldk, int64_t k_stride_seq,
                               const float *V, int64_t ldv, int64_t v_stride_seq, float *O, int64_t ldo, int n_seqs,

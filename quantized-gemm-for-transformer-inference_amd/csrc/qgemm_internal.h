@@ -535,6 +535,24 @@ hipError_t launch_attention_varlen_gqa(const float *Q, int64_t ldq, const float 
                                        const int *seq_q, const int64_t *kv_row0, const int *seq_kv, const int *q_pos0,
                                        int n_heads, int n_kv_heads, int dk, float scale, float *scores,
                                        hipStream_t stream);
+// Prefill attention tiled over the keys with a running maximum and sum (attention_tiled.hip): one
+// workgroup per (sequence, query head, 64-query tile) walks the keys in 64-key chunks; no score tensor, no workspace, a
+// numerical contract of its own (include/qgemm.h).  Its envelope: seq_kv <= kSplitMaxSeq and d_k <= 64 (row width 64,
+// "attention_tiled_kernel") or d_k 96 / 128 (row width 128, "attention_tiled_wide_kernel"); any G that divides n_heads.
+bool attention_tiled_ok(int seq_kv, int dk);
+const char *attention_tiled_plan_name(int dk);
+// tab already checked and clamped (q_pos0[b] <= seq_kv[b]); causal = false ignores q_pos0; sequences with
+// seq_q[b] == 0 get no workgroup; hipErrorInvalidValue outside the envelope or where the work items overflow an int
+hipError_t launch_attention_tiled_many(const float *Q, int64_t ldq, const float *K, int64_t ldk, const float *V,
+                                       int64_t ldv, float *O, int64_t ldo, int n_seqs, const FusedSeqTable &tab,
+                                       bool causal, int n_heads, int n_kv_heads, int dk, float scale,
+                                       hipStream_t stream);
+// from host arrays (attention_launch.hip): launch_attention_varlen_gqa's checks with kSplitMaxSeq keys in the place of
+// 4096 and G = 1 served here, the table filled and clamped, then the ONE launch; n_seqs == 0 launches nothing
+hipError_t launch_attention_tiled(const float *Q, int64_t ldq, const float *K, int64_t ldk, const float *V, int64_t ldv,
+                                  float *O, int64_t ldo, int n_seqs, const int64_t *q_row0, const int *seq_q,
+                                  const int64_t *kv_row0, const int *seq_kv, const int *q_pos0, int n_heads,
+                                  int n_kv_heads, int dk, float scale, hipStream_t stream);
 hipError_t launch_softmax_rows(const float *S, float *P, int64_t rows, int w, float scale, hipStream_t stream);
 // the same on a stack of rows / seq_q matrices under the causal mask: row r is query i = r % seq_q and its softmax
 // runs over its first min(w, i + q_pos0 + 1) columns, +0 stored past them (P may be S)
