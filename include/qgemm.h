@@ -1255,8 +1255,9 @@ QGEMM_API int qgemm_attention_varlen_gqa_plan(int n_seqs, const int *seq_q, cons
  * of bf16 rows.  16-byte loads need a 16-byte-aligned first row, strides that are multiples of 8 elements and
  * d_k % 8 == 0; anything else is read element by element, chosen once per matrix.
  * Envelope: 1 .. 8 rows per sequence, up to 64 sequences, seq_kv[b] in 1 .. 4096, d_k <= 64 or 96 or 128,
- * 1 <= G = n_heads / n_kv_heads <= 16 (G == 1: a bf16 multi-head cache).  No other path reads bf16, so outside the
- * envelope -- and for whatever the fp32 calls refuse -- the calls return hipErrorInvalidValue before any launch;
+ * 1 <= G = n_heads / n_kv_heads <= 16 (G == 1: a bf16 multi-head cache).  These calls have no other path, so outside
+ * the envelope -- and for whatever the fp32 calls refuse -- they return hipErrorInvalidValue before any launch (past
+ * 4096 keys: qgemm_attention_decode_split_kv16, below);
  * n_seqs == 0 returns 0 without a launch.
  * qgemm_kv_append_bf16: ONE launch rounds the new K and V rows of up to 64 sequences to bf16 -- nearest even, +-inf
  * past the bf16 maximum, subnormals kept, -0 kept, NaN stays NaN: the rounding of the bf16 GEMM epilogue -- and writes
@@ -1343,6 +1344,40 @@ QGEMM_API size_t qgemm_attention_decode_split_workspace_size(int n_seqs, int row
 QGEMM_API int qgemm_attention_decode_split_plan(int n_seqs, int rows_per_seq, int max_seq_kv, int n_heads, int n_kv_heads,
                                       int d_k, int *split_keys /* in: 0 or a value; out: the value used */,
                                       const char **kernel);
+
+/* ---- Split-key decode attention over a bf16 K / V cache, up to 131072 keys -------------------------
+ * qgemm_attention_decode_split_kv16: qgemm_attention_decode_split with K and V as the bf16 slabs of
+ * qgemm_attention_decode_batched_kv16 -- [slabs, rows, n_kv_heads * d_k], strides counted in bf16 elements, the cache
+ * qgemm_kv_append_bf16 fills.  Q, O and the workspace stay fp32.  It is the one call that reads a bf16 cache past key
+ * 4096, and it moves half the K / V bytes of the fp32 split call.
+ * Contract: nothing new numerically.  bf16 -> fp32 is exact and the arithmetic is the definition written out above, so
+ * every output row is BIT FOR BIT what qgemm_attention_decode_split returns on K and V widened to fp32 with the same
+ * split_keys; split_keys == 0 is resolved by the same fixed rule, so the default agrees bit for bit too.  What carries
+ * over with it: a key at or past lim contributes nothing, whatever is stored there; the result is a function of the
+ * arguments and L alone (a sequence alone equals its rows in a batch); two launches
+ * ("attention_decode_split_kv16_kernel" at d_k <= 64 or "attention_decode_split_kv16_wide_kernel" at d_k 96 / 128, then
+ * "attention_decode_merge_kernel"), nothing allocated, copied to the device or synchronized, capturable in a graph.
+ * K / V stream through LDS as bf16 rows in chunks of 256 keys (d_k <= 64) or 128 keys (d_k 96 / 128).  16-byte loads
+ * need a 16-byte-aligned first row, row strides that are multiples of 8 elements and d_k % 8 == 0; anything else is read
+ * element by element, chosen once per matrix.
+ * Envelope: qgemm_attention_decode_split's -- 1 .. 8 rows per sequence, up to 64 sequences, seq_kv[b] in 1 .. 131072,
+ * d_k <= 64 or 96 or 128, 1 <= G <= 16, split_keys a multiple of 128 in 128 .. 1024 or 0.
+ * workspace: the fp32 call's, record for record; qgemm_attention_decode_split_workspace_size serves both calls.
+ * qgemm_attention_decode_split_kv16_plan (needs no GPU): qgemm_attention_decode_split_plan's arguments and split_keys,
+ * *kernel: this call's first launch.
+ * hipErrorInvalidValue before any launch for what qgemm_attention_decode_split refuses; n_seqs == 0 returns 0 without a
+ * launch. */
+QGEMM_API int qgemm_attention_decode_split_kv16(const float *Q, int64_t q_stride_h,
+                                      const void *K, int64_t k_stride_h, int64_t k_stride_seq,
+                                      const void *V, int64_t v_stride_h, int64_t v_stride_seq,
+                                      float *O, int64_t o_stride_h, int n_seqs, int rows_per_seq,
+                                      const int *kv_slot, const int *seq_kv, const int *q_pos0,
+                                      int n_heads, int n_kv_heads, int d_k, float scale, int split_keys,
+                                      void *workspace, size_t ws_bytes, void *stream);
+QGEMM_API int qgemm_attention_decode_split_kv16_plan(int n_seqs, int rows_per_seq, int max_seq_kv, int n_heads,
+                                           int n_kv_heads, int d_k,
+                                           int *split_keys /* in: 0 or a value; out: the value used */,
+                                           const char **kernel);
 
 /* ---- Prefill attention tiled over the keys: any key count up to 131072, no score tensor -----------
  * qgemm_attention_varlen_tiled: qgemm_attention_varlen_gqa's arguments and layouts without the workspace -- Q and O fp32

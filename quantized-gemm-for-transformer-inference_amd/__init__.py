@@ -168,6 +168,8 @@ EXPORTED_SYMBOLS = (
     "qgemm_attention_decode_split",
     "qgemm_attention_decode_split_workspace_size",
     "qgemm_attention_decode_split_plan",
+    "qgemm_attention_decode_split_kv16",
+    "qgemm_attention_decode_split_kv16_plan",
     "qgemm_attention_varlen_tiled",
     "qgemm_attention_varlen_tiled_plan",
 )
@@ -536,6 +538,10 @@ def load() -> ctypes.CDLL:
         L.qgemm_attention_decode_split_plan.argtypes = [i32, i32, i32, i32, i32, i32, ip,
                                                         ctypes.POINTER(ctypes.c_char_p)]
         L.qgemm_attention_decode_split_plan.restype = i32
+        L.qgemm_attention_decode_split_kv16.argtypes = L.qgemm_attention_decode_split.argtypes
+        L.qgemm_attention_decode_split_kv16.restype = i32
+        L.qgemm_attention_decode_split_kv16_plan.argtypes = L.qgemm_attention_decode_split_plan.argtypes
+        L.qgemm_attention_decode_split_kv16_plan.restype = i32
         _lib = L
         return L
 
@@ -1881,8 +1887,8 @@ def attention_decode_batched_kv16(Q, K, V, n_heads: int, n_kv_heads, seq_kv, q_p
     """attention_decode_batched_gqa over a bf16 cache (qgemm_attention_decode_batched_kv16): K and V are
     [slabs, rows, n_kv_heads * d_k] torch.bfloat16 device tensors or views with unit inner stride, Q and O fp32.  The
     rows are bit for bit attention_decode_batched_gqa's (n_kv_heads None or n_heads: attention_decode_batched's) on
-    K.float() / V.float().  1 <= n_heads // n_kv_heads <= 16, d_k <= 64 or 96 or 128, at most 8 rows per sequence;
-    nothing else reads bf16, so outside that the call fails."""
+    K.float() / V.float().  1 <= n_heads // n_kv_heads <= 16, d_k <= 64 or 96 or 128, at most 8 rows per sequence and
+    4096 keys; outside that the call fails (past 4096 keys: attention_decode_split_kv16)."""
     import torch
     head, n_kv, tail, O = _decode_table_call(Q, K, V, torch.bfloat16, n_heads, n_kv_heads, None, seq_kv, q_pos0,
                                              kv_slot, rows_per_seq, scale, O)
@@ -1920,11 +1926,15 @@ def attention_decode_split_plan(n_seqs: int, rows_per_seq: int, max_seq_kv: int,
     split_keys None or 0 asks for the library's rule (include/qgemm.h), any other value is checked and returned; the
     kernel is "attention_decode_split_kernel" (d_k <= 64) or "attention_decode_split_wide_kernel" (d_k 96 or 128).
     Raises QGemmError outside the envelope."""
+    return _decode_split_plan("qgemm_attention_decode_split_plan", n_seqs, rows_per_seq, max_seq_kv, n_heads,
+                              n_kv_heads, d_k, split_keys)
+
+
+def _decode_split_plan(symbol, n_seqs, rows_per_seq, max_seq_kv, n_heads, n_kv_heads, d_k, split_keys):
+    """The two split-key plan queries: (keys per split, kernel) from C-ABI function `symbol`."""
     split, name = ctypes.c_int(int(split_keys or 0)), ctypes.c_char_p()
-    _check("qgemm_attention_decode_split_plan",
-           load().qgemm_attention_decode_split_plan(n_seqs, rows_per_seq, max_seq_kv, n_heads,
-                                                    _kv_heads(n_heads, n_kv_heads), d_k, ctypes.byref(split),
-                                                    ctypes.byref(name)))
+    _check(symbol, getattr(load(), symbol)(n_seqs, rows_per_seq, max_seq_kv, n_heads, _kv_heads(n_heads, n_kv_heads),
+                                           d_k, ctypes.byref(split), ctypes.byref(name)))
     return split.value, name.value.decode()
 
 
@@ -1946,7 +1956,15 @@ def attention_decode_split(Q, K, V, n_heads: int, n_kv_heads, slots, seq_kv, q_p
     sequential calls' bits; a key the mask hides contributes nothing.  workspace: a device tensor of at least
     attention_decode_split_workspace_size bytes, allocated here when None."""
     import torch
-    head, n_kv, tail, O = _decode_table_call(Q, K, V, torch.float32, n_heads, n_kv_heads, None, seq_kv, q_pos0, slots,
+    return _decode_split_call("qgemm_attention_decode_split", torch.float32, Q, K, V, n_heads, n_kv_heads, slots, seq_kv,
+                              q_pos0, rows_per_seq, split_keys, workspace, out)
+
+
+def _decode_split_call(symbol, kv_dtype, Q, K, V, n_heads, n_kv_heads, slots, seq_kv, q_pos0, rows_per_seq, split_keys,
+                       workspace, out):
+    """The two split-key calls: K / V of kv_dtype into C-ABI function `symbol`; one split rule, one workspace size."""
+    import torch
+    head, n_kv, tail, O = _decode_table_call(Q, K, V, kv_dtype, n_heads, n_kv_heads, None, seq_kv, q_pos0, slots,
                                              rows_per_seq, None, out)
     n_seqs = Q.shape[0] // rows_per_seq
     split = int(split_keys or 0)
@@ -1959,9 +1977,29 @@ def attention_decode_split(Q, K, V, n_heads: int, n_kv_heads, slots, seq_kv, q_p
     assert isinstance(workspace, torch.Tensor) and workspace.is_cuda and workspace.is_contiguous(), \
         "workspace: a contiguous device tensor"
     ws_bytes = workspace.numel() * workspace.element_size()
-    _check("qgemm_attention_decode_split",
-           load().qgemm_attention_decode_split(*head, n_kv, *tail[:2], split, workspace.data_ptr(), ws_bytes, tail[2]))
+    _check(symbol, getattr(load(), symbol)(*head, n_kv, *tail[:2], split, workspace.data_ptr(), ws_bytes, tail[2]))
     return O
+
+
+def attention_decode_split_kv16_plan(n_seqs: int, rows_per_seq: int, max_seq_kv: int, n_heads: int, n_kv_heads,
+                                     d_k: int, split_keys=None):
+    """attention_decode_split_plan for attention_decode_split_kv16 (qgemm_attention_decode_split_kv16_plan; needs no
+    GPU): the same keys per split, and "attention_decode_split_kv16_kernel" (d_k <= 64) or
+    "attention_decode_split_kv16_wide_kernel" (d_k 96 or 128)."""
+    return _decode_split_plan("qgemm_attention_decode_split_kv16_plan", n_seqs, rows_per_seq, max_seq_kv, n_heads,
+                              n_kv_heads, d_k, split_keys)
+
+
+def attention_decode_split_kv16(Q, K, V, n_heads: int, n_kv_heads, slots, seq_kv, q_pos0=None, rows_per_seq: int = 1,
+                                split_keys=None, workspace=None, out=None):
+    """attention_decode_split over a bf16 cache (qgemm_attention_decode_split_kv16): K and V are
+    [slabs, rows, n_kv_heads * d_k] torch.bfloat16 device tensors or views with unit inner stride (the cache
+    kv_append_bf16 fills), Q, the result and the workspace fp32; sequences of up to 131072 keys.  The rows are bit for
+    bit attention_decode_split's on K.float() / V.float() with the same split_keys, the default included; the workspace
+    is that call's (attention_decode_split_workspace_size)."""
+    import torch
+    return _decode_split_call("qgemm_attention_decode_split_kv16", torch.bfloat16, Q, K, V, n_heads, n_kv_heads, slots,
+                              seq_kv, q_pos0, rows_per_seq, split_keys, workspace, out)
 
 
 def kv_append_bf16(K, V, Kc, Vc, pos, kv_slot=None, rows_per_seq: int = 1):

@@ -1103,6 +1103,28 @@ int qgemm_attention_decode_split_plan(int n_seqs, int rows_per_seq, int max_seq_
     return 0;
 }
 
+// ---- ... over a bf16 K / V cache ----
+
+int qgemm_attention_decode_split_kv16(const float *Q, int64_t q_stride_h, const void *K, int64_t k_stride_h,
+                                      int64_t k_stride_seq, const void *V, int64_t v_stride_h, int64_t v_stride_seq,
+                                      float *O, int64_t o_stride_h, int n_seqs, int rows_per_seq, const int *kv_slot,
+                                      const int *seq_kv, const int *q_pos0, int n_heads, int n_kv_heads, int d_k,
+                                      float scale, int split_keys, void *workspace, size_t ws_bytes, void *stream) {
+    return err(launch_attention_split_kv16(Q, q_stride_h, static_cast<const bf16_t *>(K), k_stride_h, k_stride_seq,
+                                           static_cast<const bf16_t *>(V), v_stride_h, v_stride_seq, O, o_stride_h,
+                                           n_seqs, rows_per_seq, kv_slot, seq_kv, q_pos0, n_heads, n_kv_heads, d_k, scale,
+                                           split_keys, workspace, ws_bytes, static_cast<hipStream_t>(stream)));
+}
+
+// the fp32 plan's checks and split_keys (ONE rule: the bits depend on it), the bf16 kernel's name
+int qgemm_attention_decode_split_kv16_plan(int n_seqs, int rows_per_seq, int max_seq_kv, int n_heads, int n_kv_heads,
+                                           int d_k, int *split_keys, const char **kernel) {
+    const int e = qgemm_attention_decode_split_plan(n_seqs, rows_per_seq, max_seq_kv, n_heads, n_kv_heads, d_k, split_keys,
+                                                    nullptr);
+    if (e == 0 && kernel) *kernel = attention_split_kv16_plan_name(d_k);
+    return e;
+}
+
 #ifndef QGEMM_SRC_HASH
 #define QGEMM_SRC_HASH "unknown"
 #endif

@@ -336,13 +336,11 @@ bool attention_split_ok(int n_seqs, int rows_per_seq, int max_seq_kv, int dk, in
            groups_ok(n_heads, n_kv_heads, 1);
 }
 
-// tab: checked and clamped by launch_attention_split (attention_launch.hip); what sizes the grid, the kernels' LDS rows
-// and the workspace records is tested again here
-hipError_t launch_attention_decode_split(const float *Q, int64_t ldq, const float *K, int64_t ldk, int64_t k_stride_seq,
-                                         const float *V, int64_t ldv, int64_t v_stride_seq, float *O, int64_t ldo,
-                                         int n_seqs, int rows_per_seq, const DecodeBatchTable &tab, bool causal,
-                                         int n_heads, int n_kv_heads, int dk, float scale, int split, float *workspace,
-                                         size_t ws_bytes, hipStream_t stream) {
+// What sizes the grid, the kernels' LDS rows and the workspace records of a split-key launch, tested again on the
+// built table: ws_splits = the workspace's split dimension, grid_z = the most splits a row of the batch has
+hipError_t attention_split_launch_dims(int n_seqs, int rows_per_seq, const DecodeBatchTable &tab, bool causal,
+                                       int n_heads, int n_kv_heads, int dk, int split, const float *workspace,
+                                       size_t ws_bytes, int &ws_splits, int &grid_z) {
     if (!workspace || !split_keys_ok(split) || !attention_split_ok(n_seqs, rows_per_seq, 1, dk, n_heads, n_kv_heads))
         return hipErrorInvalidValue;
     int max_kv = 1, max_lim = 1;
@@ -356,13 +354,37 @@ hipError_t launch_attention_decode_split(const float *Q, int64_t ldq, const floa
         max_kv = tab.seq_kv[b] > max_kv ? tab.seq_kv[b] : max_kv;
         max_lim = seen > max_lim ? seen : max_lim;
     }
-    const int ws_splits = (max_kv + split - 1) / split;
     if (ws_bytes < attention_split_workspace_bytes(n_seqs, rows_per_seq, max_kv, n_heads, dk, split))
+        return hipErrorInvalidValue;
+    ws_splits = (max_kv + split - 1) / split;
+    grid_z = (max_lim + split - 1) / split;
+    return hipSuccess;
+}
+
+// the second launch of a split-key call: one wave per (head, row of a sequence) over the records the first one wrote
+hipError_t launch_attention_decode_merge(const float *workspace, float *O, int64_t ldo, int n_seqs, int rows_per_seq,
+                                         const DecodeBatchTable &tab, bool causal, int n_heads, int dk, int split,
+                                         int ws_splits, hipStream_t stream) {
+    const DecodeMany many{0, 0, rows_per_seq, tab};  // (the merge reads no K / V: the strides are not used)
+    attention_decode_merge_kernel<<<dim3((unsigned)n_heads, (unsigned)(rows_per_seq * n_seqs)), 64, 0, stream>>>(
+        workspace, O, ldo, dk, n_heads, split, ws_splits, causal ? 1 : 0, many);
+    return hipGetLastError();
+}
+
+// tab: checked and clamped by launch_attention_split (attention_launch.hip)
+hipError_t launch_attention_decode_split(const float *Q, int64_t ldq, const float *K, int64_t ldk, int64_t k_stride_seq,
+                                         const float *V, int64_t ldv, int64_t v_stride_seq, float *O, int64_t ldo,
+                                         int n_seqs, int rows_per_seq, const DecodeBatchTable &tab, bool causal,
+                                         int n_heads, int n_kv_heads, int dk, float scale, int split, float *workspace,
+                                         size_t ws_bytes, hipStream_t stream) {
+    int ws_splits, grid_z;
+    if (attention_split_launch_dims(n_seqs, rows_per_seq, tab, causal, n_heads, n_kv_heads, dk, split, workspace, ws_bytes,
+                                    ws_splits, grid_z))
         return hipErrorInvalidValue;
     const int group = n_heads / n_kv_heads;
     const DecodeMany many{k_stride_seq, v_stride_seq, rows_per_seq, tab};
     const dim3 grid((unsigned)(n_kv_heads * ((group + kDecGroupHeads - 1) / kDecGroupHeads)),
-                    (unsigned)(rows_per_seq * n_seqs), (unsigned)((max_lim + split - 1) / split));
+                    (unsigned)(rows_per_seq * n_seqs), (unsigned)grid_z);
     auto *kernel = dk > kDecMaxDk ? (causal ? attention_decode_split_kernel<true, kDecWideDk>
                                             : attention_decode_split_kernel<false, kDecWideDk>)
                                   : (causal ? attention_decode_split_kernel<true, kDecMaxDk>
@@ -371,9 +393,8 @@ hipError_t launch_attention_decode_split(const float *Q, int64_t ldq, const floa
                                              ws_splits, many);
     hipError_t e = hipGetLastError();
     if (e) return e;
-    attention_decode_merge_kernel<<<dim3((unsigned)n_heads, (unsigned)(rows_per_seq * n_seqs)), 64, 0, stream>>>(
-        workspace, O, ldo, dk, n_heads, split, ws_splits, causal ? 1 : 0, many);
-    return hipGetLastError();
+    return launch_attention_decode_merge(workspace, O, ldo, n_seqs, rows_per_seq, tab, causal, n_heads, dk, split,
+                                         ws_splits, stream);
 }
 
 }  // namespace qgemm

@@ -397,12 +397,14 @@ size_t attention_split_workspace_bytes(int n_seqs, int rows_per_seq, int max_seq
 }
 
 // decode_table_from_host's checks and table with kSplitMaxSeq keys, the group check from G = 1, the split and the
-// workspace it needs for the batch's longest sequence; then the two launches
-hipError_t launch_attention_split(const float *Q, int64_t ldq, const float *K, int64_t ldk, int64_t k_stride_seq,
-                                  const float *V, int64_t ldv, int64_t v_stride_seq, float *O, int64_t ldo, int n_seqs,
-                                  int rows_per_seq, const int *kv_slot, const int *seq_kv, const int *q_pos0, int n_heads,
-                                  int n_kv_heads, int dk, float scale, int split_keys, void *workspace, size_t ws_bytes,
-                                  hipStream_t stream) {
+// workspace it needs for the batch's longest sequence; then the two launches.  T: float (launch_attention_decode_split)
+// or bf16_t (launch_attention_decode_split_kv16) -- one text, so both resolve split_keys == 0 alike.
+template <typename T, typename Launch>
+static hipError_t split_from_host(Launch launch, const float *Q, int64_t ldq, const T *K, int64_t ldk,
+                                  int64_t k_stride_seq, const T *V, int64_t ldv, int64_t v_stride_seq, float *O,
+                                  int64_t ldo, int n_seqs, int rows_per_seq, const int *kv_slot, const int *seq_kv,
+                                  const int *q_pos0, int n_heads, int n_kv_heads, int dk, float scale, int split_keys,
+                                  void *workspace, size_t ws_bytes, hipStream_t stream) {
     DecodeBatchTable tab;  // filled by decode_table_from_host_max, read only after its success
     if (!Q || !K || !V || !O || !attention_split_ok(1, rows_per_seq, 1, dk, n_heads, n_kv_heads) ||
         (split_keys != 0 && !split_keys_ok(split_keys)) ||
@@ -416,9 +418,29 @@ hipError_t launch_attention_split(const float *Q, int64_t ldq, const float *K, i
         split_keys ? split_keys : attention_split_default_keys(n_seqs, rows_per_seq, max_kv, n_heads, n_kv_heads);
     if (!workspace || ws_bytes < attention_split_workspace_bytes(n_seqs, rows_per_seq, max_kv, n_heads, dk, split))
         return hipErrorInvalidValue;
-    return launch_attention_decode_split(Q, ldq, K, ldk, k_stride_seq, V, ldv, v_stride_seq, O, ldo, n_seqs,
-                                         rows_per_seq, tab, q_pos0 != nullptr, n_heads, n_kv_heads, dk, scale, split,
-                                         static_cast<float *>(workspace), ws_bytes, stream);
+    return launch(Q, ldq, K, ldk, k_stride_seq, V, ldv, v_stride_seq, O, ldo, n_seqs, rows_per_seq, tab,
+                  q_pos0 != nullptr, n_heads, n_kv_heads, dk, scale, split, static_cast<float *>(workspace), ws_bytes,
+                  stream);
+}
+
+hipError_t launch_attention_split(const float *Q, int64_t ldq, const float *K, int64_t ldk, int64_t k_stride_seq,
+                                  const float *V, int64_t ldv, int64_t v_stride_seq, float *O, int64_t ldo, int n_seqs,
+                                  int rows_per_seq, const int *kv_slot, const int *seq_kv, const int *q_pos0, int n_heads,
+                                  int n_kv_heads, int dk, float scale, int split_keys, void *workspace, size_t ws_bytes,
+                                  hipStream_t stream) {
+    return split_from_host(launch_attention_decode_split, Q, ldq, K, ldk, k_stride_seq, V, ldv, v_stride_seq, O, ldo,
+                           n_seqs, rows_per_seq, kv_slot, seq_kv, q_pos0, n_heads, n_kv_heads, dk, scale, split_keys,
+                           workspace, ws_bytes, stream);
+}
+
+hipError_t launch_attention_split_kv16(const float *Q, int64_t ldq, const bf16_t *K, int64_t ldk, int64_t k_stride_seq,
+                                       const bf16_t *V, int64_t ldv, int64_t v_stride_seq, float *O, int64_t ldo,
+                                       int n_seqs, int rows_per_seq, const int *kv_slot, const int *seq_kv,
+                                       const int *q_pos0, int n_heads, int n_kv_heads, int dk, float scale, int split_keys,
+                                       void *workspace, size_t ws_bytes, hipStream_t stream) {
+    return split_from_host(launch_attention_decode_split_kv16, Q, ldq, K, ldk, k_stride_seq, V, ldv, v_stride_seq, O,
+                           ldo, n_seqs, rows_per_seq, kv_slot, seq_kv, q_pos0, n_heads, n_kv_heads, dk, scale, split_keys,
+                           workspace, ws_bytes, stream);
 }
 
 }  // namespace qgemm

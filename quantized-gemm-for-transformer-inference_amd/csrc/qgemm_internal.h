@@ -460,6 +460,31 @@ hipError_t launch_attention_split(const float *Q, int64_t ldq, const float *K, i
                                   int rows_per_seq, const int *kv_slot, const int *seq_kv, const int *q_pos0, int n_heads,
                                   int n_kv_heads, int dk, float scale, int split_keys, void *workspace, size_t ws_bytes,
                                   hipStream_t stream);
+// What the two split-key launches (fp32 K / V above, bf16 below) share, both in attention_decode_split.hip.
+// attention_split_launch_dims: the re-check of a built table, of split and of the workspace; on success ws_splits = the
+// workspace's split dimension, grid_z = the most splits a row of the batch has.  launch_attention_decode_merge: the
+// second launch, attention_decode_merge_kernel over the records the first one wrote.
+hipError_t attention_split_launch_dims(int n_seqs, int rows_per_seq, const DecodeBatchTable &tab, bool causal,
+                                       int n_heads, int n_kv_heads, int dk, int split, const float *workspace,
+                                       size_t ws_bytes, int &ws_splits, int &grid_z);
+hipError_t launch_attention_decode_merge(const float *workspace, float *O, int64_t ldo, int n_seqs, int rows_per_seq,
+                                         const DecodeBatchTable &tab, bool causal, int n_heads, int dk, int split,
+                                         int ws_splits, hipStream_t stream);
+// Split-key decode attention over a bf16 cache (attention_decode_split_kv16.hip): the launches above with
+// K / V as bf16 slabs (strides in bf16 elements), the same envelope, split rule, workspace and records, and the bits of
+// the fp32 launch on the widened cache.
+const char *attention_split_kv16_plan_name(int dk);
+hipError_t launch_attention_decode_split_kv16(const float *Q, int64_t ldq, const bf16_t *K, int64_t ldk,
+                                              int64_t k_stride_seq, const bf16_t *V, int64_t ldv, int64_t v_stride_seq,
+                                              float *O, int64_t ldo, int n_seqs, int rows_per_seq,
+                                              const DecodeBatchTable &tab, bool causal, int n_heads, int n_kv_heads, int dk,
+                                              float scale, int split, float *workspace, size_t ws_bytes,
+                                              hipStream_t stream);
+hipError_t launch_attention_split_kv16(const float *Q, int64_t ldq, const bf16_t *K, int64_t ldk, int64_t k_stride_seq,
+                                       const bf16_t *V, int64_t ldv, int64_t v_stride_seq, float *O, int64_t ldo,
+                                       int n_seqs, int rows_per_seq, const int *kv_slot, const int *seq_kv,
+                                       const int *q_pos0, int n_heads, int n_kv_heads, int dk, float scale, int split_keys,
+                                       void *workspace, size_t ws_bytes, hipStream_t stream);
 // the kernel launch_attention takes for a shape (qgemm_attention_plan): a static string
 const char *attention_plan_name(int seq_q, int seq_kv, int dk);
 // whether a call of at most max_q query rows and max_kv keys can reach the three launches, and so needs `scores`
