@@ -1422,6 +1422,35 @@ QGEMM_API int qgemm_attention_varlen_tiled(const float *Q, int64_t q_stride_h, c
 QGEMM_API int qgemm_attention_varlen_tiled_plan(int n_seqs, const int *seq_q, const int *seq_kv, int n_heads,
                                       int n_kv_heads, int d_k, const char **kernel);
 
+/* ---- Tiled prefill attention over a bf16 K / V cache, up to 131072 keys ----------------------------
+ * qgemm_attention_varlen_tiled_kv16: qgemm_attention_varlen_tiled with K and V as bf16 rows -- n_kv_heads * d_k columns,
+ * row strides counted in bf16 elements, the rows qgemm_kv_append_bf16 fills.  Q and O stay fp32; the five host arrays,
+ * the row offsets and the mask offset are that call's, and there is no workspace.  A cache slab [slabs, rows, width]
+ * whose slab stride is a multiple of its row stride is addressed through kv_row0[b] = slot * rows.  It is the one call
+ * that lets more than 8 query rows per sequence attend to a bf16 cache: a chunk of a prompt, a speculative block, a
+ * second turn on a kept cache.
+ * Contract: nothing new numerically.  bf16 -> fp32 is exact and the arithmetic is the definition written out above, so
+ * every output row is BIT FOR BIT what qgemm_attention_varlen_tiled returns on K and V widened to fp32.  What carries
+ * over with it: the visibility rule; a key at or past the sequence's largest lim contributes nothing, whatever bf16
+ * pattern is stored there; a sequence's rows are a function of its own arguments alone; ONE launch
+ * ("attention_tiled_kv16_kernel" at d_k <= 64 or "attention_tiled_kv16_wide_kernel" at d_k 96 / 128: the names
+ * qgemm_attention_varlen_tiled_kv16_plan returns, without a GPU), nothing allocated, copied to the device or
+ * synchronized, capturable in a graph; no row of O outside the sequences' rows is written.
+ * K / V stay bf16 through LDS (two 64-key chunks, one barrier per chunk) and are widened where an MFMA operand is
+ * formed.  16-byte loads need a 16-byte-aligned first row (kv_row0[b] and the head's offset included), a row stride
+ * that is a multiple of 8 elements and d_k % 8 == 0; anything else is read element by element, chosen once per matrix.
+ * Envelope and refusals: qgemm_attention_varlen_tiled's -- 0 <= n_seqs <= 64, seq_q[b] >= 0, 1 <= seq_kv[b] <= 131072,
+ * d_k <= 64 or 96 / 128, n_kv_heads divides n_heads; hipErrorInvalidValue before the launch for a null pointer or
+ * array (q_pos0 aside), a negative row offset or q_pos0[b] and everything outside the envelope; n_seqs == 0 returns 0
+ * without a launch. */
+QGEMM_API int qgemm_attention_varlen_tiled_kv16(const float *Q, int64_t q_stride_h, const void *K, int64_t k_stride_h,
+                                      const void *V, int64_t v_stride_h, float *O, int64_t o_stride_h, int n_seqs,
+                                      const int64_t *q_row0, const int *seq_q, const int64_t *kv_row0,
+                                      const int *seq_kv, const int *q_pos0 /* NULL: no mask */, int n_heads,
+                                      int n_kv_heads, int d_k, float scale, void *stream);
+QGEMM_API int qgemm_attention_varlen_tiled_kv16_plan(int n_seqs, const int *seq_q, const int *seq_kv, int n_heads,
+                                           int n_kv_heads, int d_k, const char **kernel);
+
 #ifdef __cplusplus
 }
 #endif

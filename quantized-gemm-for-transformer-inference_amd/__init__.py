@@ -172,6 +172,8 @@ EXPORTED_SYMBOLS = (
     "qgemm_attention_decode_split_kv16_plan",
     "qgemm_attention_varlen_tiled",
     "qgemm_attention_varlen_tiled_plan",
+    "qgemm_attention_varlen_tiled_kv16",
+    "qgemm_attention_varlen_tiled_kv16_plan",
 )
 
 # Every symbol include/qgemm_dist.h declares (libqgemm_dist.so: M-shards + RCCL all-gather).
@@ -542,6 +544,10 @@ def load() -> ctypes.CDLL:
         L.qgemm_attention_decode_split_kv16.restype = i32
         L.qgemm_attention_decode_split_kv16_plan.argtypes = L.qgemm_attention_decode_split_plan.argtypes
         L.qgemm_attention_decode_split_kv16_plan.restype = i32
+        L.qgemm_attention_varlen_tiled_kv16.argtypes = L.qgemm_attention_varlen_tiled.argtypes
+        L.qgemm_attention_varlen_tiled_kv16.restype = i32
+        L.qgemm_attention_varlen_tiled_kv16_plan.argtypes = L.qgemm_attention_varlen_tiled_plan.argtypes
+        L.qgemm_attention_varlen_tiled_kv16_plan.restype = i32
         _lib = L
         return L
 
@@ -2195,10 +2201,21 @@ def attention_varlen_tiled(Q, K, V, n_heads: int, n_kv_heads, seq_q, seq_kv, q_r
     keys per sequence, in ONE launch for any mix of lengths, without a score tensor or a workspace.  d_k <= 64, 96 or
     128.  Its numerical contract is its own (include/qgemm.h): fp32 softmax attention, not attention_varlen_gqa's bits;
     a sequence's rows do not depend on the rest of the batch.  No other row of O is written (a fresh O is zero-filled)."""
+    import torch
+    return _varlen_tiled_call("qgemm_attention_varlen_tiled", torch.float32, Q, K, V, n_heads, n_kv_heads, seq_q, seq_kv,
+                              q_row0, kv_row0, q_pos0, scale, O)
+
+
+def _varlen_tiled_call(symbol, kv_dtype, Q, K, V, n_heads, n_kv_heads, seq_q, seq_kv, q_row0, kv_row0, q_pos0, scale, O):
+    """The two tiled prefill calls: K / V of kv_dtype into C-ABI function `symbol`; one set of checks and tables."""
     import math
     import torch
     for t, nm in ((Q, "Q"), (K, "K"), (V, "V")):
-        _require_device_f32(t, nm)
+        if nm == "Q" or kv_dtype == torch.float32:
+            _require_device_f32(t, nm)
+        else:
+            assert isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == kv_dtype, \
+                f"{nm}: a 2-D {str(kv_dtype).split('.')[-1]} device tensor"
         assert t.dim() == 2 and (t.stride(1) == 1 or t.shape[1] == 1), f"{nm} must be 2-D with unit inner stride"
     d = Q.shape[1]
     assert n_heads >= 1 and d % n_heads == 0, "d % n_heads == 0"
@@ -2222,26 +2239,46 @@ def attention_varlen_tiled(Q, K, V, n_heads: int, n_kv_heads, seq_q, seq_kv, q_r
             assert kv_row0[b] + seq_kv[b] <= min(K.shape[0], V.shape[0]), f"sequence {b}'s keys exceed K / V"
     if scale is None:
         scale = ctypes.c_float(1.0 / math.sqrt(float(dk))).value
-    _check("qgemm_attention_varlen_tiled",
-           load().qgemm_attention_varlen_tiled(Q.data_ptr(), Q.stride(0), K.data_ptr(), K.stride(0), V.data_ptr(),
-                                               V.stride(0), O.data_ptr(), O.stride(0), n,
-                                               _int64_array(q_row0, n, "q_row0"), _int_array(seq_q, n, "seq_q"),
-                                               _int64_array(kv_row0, n, "kv_row0"), _int_array(seq_kv, n, "seq_kv"),
-                                               _int_array(q_pos0, n, "q_pos0"), n_heads, n_kv, dk, float(scale),
-                                               _stream(Q.device)))
+    _check(symbol, getattr(load(), symbol)(Q.data_ptr(), Q.stride(0), K.data_ptr(), K.stride(0), V.data_ptr(), V.stride(0),
+                                           O.data_ptr(), O.stride(0), n, _int64_array(q_row0, n, "q_row0"),
+                                           _int_array(seq_q, n, "seq_q"), _int64_array(kv_row0, n, "kv_row0"),
+                                           _int_array(seq_kv, n, "seq_kv"), _int_array(q_pos0, n, "q_pos0"), n_heads,
+                                           n_kv, dk, float(scale), _stream(Q.device)))
     return O
 
 
 def attention_varlen_tiled_plan(seq_q, seq_kv, n_heads: int, n_kv_heads: int, d_k: int) -> str:
     """The kernel attention_varlen_tiled() launches (qgemm_attention_varlen_tiled_plan): "attention_tiled_kernel" at
     d_k <= 64, "attention_tiled_wide_kernel" at d_k 96 / 128.  Needs no GPU; raises QGemmError outside the envelope."""
+    return _varlen_tiled_plan("qgemm_attention_varlen_tiled_plan", seq_q, seq_kv, n_heads, n_kv_heads, d_k)
+
+
+def _varlen_tiled_plan(symbol, seq_q, seq_kv, n_heads, n_kv_heads, d_k):
+    """The two tiled plan queries: the kernel's name from C-ABI function `symbol`."""
     seq_q, seq_kv = [int(v) for v in seq_q], [int(v) for v in seq_kv]
     n = len(seq_q)
     name = ctypes.c_char_p()
-    _check("qgemm_attention_varlen_tiled_plan",
-           load().qgemm_attention_varlen_tiled_plan(n, _int_array(seq_q, n, "seq_q"), _int_array(seq_kv, n, "seq_kv"),
-                                                    n_heads, n_kv_heads, d_k, ctypes.byref(name)))
+    _check(symbol, getattr(load(), symbol)(n, _int_array(seq_q, n, "seq_q"), _int_array(seq_kv, n, "seq_kv"), n_heads,
+                                           n_kv_heads, d_k, ctypes.byref(name)))
     return name.value.decode()
+
+
+def attention_varlen_tiled_kv16(Q, K, V, n_heads: int, n_kv_heads, seq_q, seq_kv, q_row0=None, kv_row0=None, q_pos0=None,
+                                scale=None, O=None):
+    """attention_varlen_tiled over bf16 K / V rows (qgemm_attention_varlen_tiled_kv16): K and V are 2-D
+    torch.bfloat16 device tensors or views with unit inner stride (a [slabs, rows, width] cache kv_append_bf16 fills,
+    flattened to rows: kv_row0[b] = slot * rows), Q and O fp32.  The rows are bit for bit attention_varlen_tiled's on
+    K.float() / V.float(); the envelope, the arguments and the one launch without a workspace are that call's."""
+    import torch
+    return _varlen_tiled_call("qgemm_attention_varlen_tiled_kv16", torch.bfloat16, Q, K, V, n_heads, n_kv_heads, seq_q,
+                              seq_kv, q_row0, kv_row0, q_pos0, scale, O)
+
+
+def attention_varlen_tiled_kv16_plan(seq_q, seq_kv, n_heads: int, n_kv_heads: int, d_k: int) -> str:
+    """The kernel attention_varlen_tiled_kv16() launches (qgemm_attention_varlen_tiled_kv16_plan; needs no GPU):
+    "attention_tiled_kv16_kernel" at d_k <= 64, "attention_tiled_kv16_wide_kernel" at d_k 96 / 128.  Raises QGemmError
+    outside the envelope."""
+    return _varlen_tiled_plan("qgemm_attention_varlen_tiled_kv16_plan", seq_q, seq_kv, n_heads, n_kv_heads, d_k)
 
 
 def attention_plan(seq_q: int, seq_kv: int, n_heads: int, d_k: int) -> str:

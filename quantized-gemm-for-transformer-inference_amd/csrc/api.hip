@@ -1125,6 +1125,29 @@ int qgemm_attention_decode_split_kv16_plan(int n_seqs, int rows_per_seq, int max
     return e;
 }
 
+// ---- prefill tiled over the keys of a bf16 K / V cache ----
+
+int qgemm_attention_varlen_tiled_kv16(const float *Q, int64_t q_stride_h, const void *K, int64_t k_stride_h,
+                                      const void *V, int64_t v_stride_h, float *O, int64_t o_stride_h, int n_seqs,
+                                      const int64_t *q_row0, const int *seq_q, const int64_t *kv_row0, const int *seq_kv,
+                                      const int *q_pos0, int n_heads, int n_kv_heads, int d_k, float scale, void *stream) {
+    if (!Q || !K || !V || !O || !q_row0 || !kv_row0 ||
+        !varlen_tiled_dims_ok(n_seqs, seq_q, seq_kv, n_heads, n_kv_heads, d_k))
+        return err(hipErrorInvalidValue);
+    return err(launch_attention_tiled_kv16(Q, q_stride_h, static_cast<const bf16_t *>(K), k_stride_h,
+                                           static_cast<const bf16_t *>(V), v_stride_h, O, o_stride_h, n_seqs, q_row0,
+                                           seq_q, kv_row0, seq_kv, q_pos0, n_heads, n_kv_heads, d_k, scale,
+                                           static_cast<hipStream_t>(stream)));
+}
+
+// the fp32 plan's checks, the bf16 kernel's name
+int qgemm_attention_varlen_tiled_kv16_plan(int n_seqs, const int *seq_q, const int *seq_kv, int n_heads, int n_kv_heads,
+                                           int d_k, const char **kernel) {
+    if (!varlen_tiled_dims_ok(n_seqs, seq_q, seq_kv, n_heads, n_kv_heads, d_k)) return err(hipErrorInvalidValue);
+    if (kernel) *kernel = attention_tiled_kv16_plan_name(d_k);
+    return 0;
+}
+
 #ifndef QGEMM_SRC_HASH
 #define QGEMM_SRC_HASH "unknown"
 #endif

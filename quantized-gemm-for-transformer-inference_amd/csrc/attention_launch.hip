@@ -304,9 +304,11 @@ hipError_t launch_attention_varlen_gqa(const float *Q, int64_t ldq, const float 
 // ---- prefill tiled over the keys, online softmax ----
 
 // launch_attention_varlen_gqa's checks with kSplitMaxSeq keys in the place of 4096 (G = 1 is served here too: nothing is
-// rerouted), its table and clamp; then the one launch, which tests the envelope (d_k, the work map) again
-hipError_t launch_attention_tiled(const float *Q, int64_t ldq, const float *K, int64_t ldk, const float *V, int64_t ldv,
-                                  float *O, int64_t ldo, int n_seqs, const int64_t *q_row0, const int *seq_q,
+// rerouted), its table and clamp; then the one launch, which tests the envelope (d_k, the work map) again.  T: float
+// (launch_attention_tiled) or bf16_t (launch_attention_tiled_kv16) -- one text for both tables.
+template <typename T, typename Launch>
+static hipError_t tiled_from_host(Launch launch, const float *Q, int64_t ldq, const T *K, int64_t ldk, const T *V,
+                                  int64_t ldv, float *O, int64_t ldo, int n_seqs, const int64_t *q_row0, const int *seq_q,
                                   const int64_t *kv_row0, const int *seq_kv, const int *q_pos0, int n_heads,
                                   int n_kv_heads, int dk, float scale, hipStream_t stream) {
     if (n_heads < 1 || n_kv_heads < 1 || n_heads % n_kv_heads || !Q || !K || !V || !O || !q_row0 || !seq_q || !kv_row0 ||
@@ -325,8 +327,23 @@ hipError_t launch_attention_tiled(const float *Q, int64_t ldq, const float *K, i
         tab.q_pos0[b] = q_pos0 ? (q_pos0[b] < seq_kv[b] ? q_pos0[b] : seq_kv[b]) : 0;
     }
     if (n_seqs == 0) return hipSuccess;
-    return launch_attention_tiled_many(Q, ldq, K, ldk, V, ldv, O, ldo, n_seqs, tab, q_pos0 != nullptr, n_heads,
-                                       n_kv_heads, dk, scale, stream);
+    return launch(Q, ldq, K, ldk, V, ldv, O, ldo, n_seqs, tab, q_pos0 != nullptr, n_heads, n_kv_heads, dk, scale, stream);
+}
+
+hipError_t launch_attention_tiled(const float *Q, int64_t ldq, const float *K, int64_t ldk, const float *V, int64_t ldv,
+                                  float *O, int64_t ldo, int n_seqs, const int64_t *q_row0, const int *seq_q,
+                                  const int64_t *kv_row0, const int *seq_kv, const int *q_pos0, int n_heads,
+                                  int n_kv_heads, int dk, float scale, hipStream_t stream) {
+    return tiled_from_host(launch_attention_tiled_many, Q, ldq, K, ldk, V, ldv, O, ldo, n_seqs, q_row0, seq_q, kv_row0,
+                           seq_kv, q_pos0, n_heads, n_kv_heads, dk, scale, stream);
+}
+
+hipError_t launch_attention_tiled_kv16(const float *Q, int64_t ldq, const bf16_t *K, int64_t ldk, const bf16_t *V,
+                                       int64_t ldv, float *O, int64_t ldo, int n_seqs, const int64_t *q_row0,
+                                       const int *seq_q, const int64_t *kv_row0, const int *seq_kv, const int *q_pos0,
+                                       int n_heads, int n_kv_heads, int dk, float scale, hipStream_t stream) {
+    return tiled_from_host(launch_attention_tiled_kv16_many, Q, ldq, K, ldk, V, ldv, O, ldo, n_seqs, q_row0, seq_q,
+                           kv_row0, seq_kv, q_pos0, n_heads, n_kv_heads, dk, scale, stream);
 }
 
 // decode_table_from_host's checks and table and the group check, then the grouped decode launch

@@ -578,6 +578,18 @@ hipError_t launch_attention_tiled(const float *Q, int64_t ldq, const float *K, i
                                   float *O, int64_t ldo, int n_seqs, const int64_t *q_row0, const int *seq_q,
                                   const int64_t *kv_row0, const int *seq_kv, const int *q_pos0, int n_heads,
                                   int n_kv_heads, int dk, float scale, hipStream_t stream);
+// The same over bf16 K / V rows (attention_tiled_kv16.hip; strides in bf16 elements): the envelope
+// (attention_tiled_ok), the table, the work map and the bits of the fp32 launch on the widened K / V; two bf16 chunks in
+// LDS, one barrier per chunk, permuted staged rows ("attention_tiled_kv16_kernel" / "attention_tiled_kv16_wide_kernel").
+const char *attention_tiled_kv16_plan_name(int dk);
+hipError_t launch_attention_tiled_kv16_many(const float *Q, int64_t ldq, const bf16_t *K, int64_t ldk, const bf16_t *V,
+                                            int64_t ldv, float *O, int64_t ldo, int n_seqs, const FusedSeqTable &tab,
+                                            bool causal, int n_heads, int n_kv_heads, int dk, float scale,
+                                            hipStream_t stream);
+hipError_t launch_attention_tiled_kv16(const float *Q, int64_t ldq, const bf16_t *K, int64_t ldk, const bf16_t *V,
+                                       int64_t ldv, float *O, int64_t ldo, int n_seqs, const int64_t *q_row0,
+                                       const int *seq_q, const int64_t *kv_row0, const int *seq_kv, const int *q_pos0,
+                                       int n_heads, int n_kv_heads, int dk, float scale, hipStream_t stream);
 hipError_t launch_softmax_rows(const float *S, float *P, int64_t rows, int w, float scale, hipStream_t stream);
 // the same on a stack of rows / seq_q matrices under the causal mask: row r is query i = r % seq_q and its softmax
 // runs over its first min(w, i + q_pos0 + 1) columns, +0 stored past them (P may be S)
